@@ -20,6 +20,11 @@ region: bit-equal to the eager command-list path, within the bf16 bound of an fp
 1e-3 of the CPU oracle) + `parity_mode` (throughput and measured error of the mode that passes north_star's 1e-3)
 + `end_to_end` (wav files on tmpfs -> decode -> H2D -> forward -> D2H -> .pt files through the driver)
 + `cpu_baseline` (CPU oracle, reference-style batch-of-one driver, bounded sample, rank 0 at N=1 only).
+`ms_per_step` is the wall time of one counted step.
+
+`--dump-outputs DIR` writes what the last timed step computed (a fixed sample of its hidden states, float32 .npy) to DIR
+right after the timed region; the inputs and weights are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import json
@@ -205,14 +210,15 @@ def bench_text(args, geo, rank, world, device, D):
     torch.cuda.synchronize()
     sides = [torch.cuda.Stream(device=device) for _ in parts[1:]]
     graph = torch.cuda.CUDAGraph()
+    hs = [None] * len(parts)                                       # the HiddenStates every replay writes, one per group
     with torch.cuda.graph(graph):
         main_stream = torch.cuda.current_stream()
         for st in sides:
             st.wait_stream(main_stream)
         for slot, st in enumerate(sides, start=1):
             with torch.cuda.stream(st):
-                enc.forward_device(*parts[slot], slot=slot)
-        enc.forward_device(*parts[0], slot=0)
+                hs[slot] = enc.forward_device(*parts[slot], slot=slot)
+        hs[0] = enc.forward_device(*parts[0], slot=0)
         for st in sides:
             main_stream.wait_stream(st)
     for _ in range(args.warmup):
@@ -223,6 +229,8 @@ def bench_text(args, geo, rank, world, device, D):
         graph.replay()
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, hs)
     if rank == 0:
         Dm, F, L = geo.hidden, geo.ffn, geo.num_layers
         gf = L * (2.0 * T * Dm * 3 * Dm + 2.0 * T * Dm * Dm + 4.0 * T * T * Dm + 4.0 * T * Dm * F) / 1e9
@@ -247,6 +255,26 @@ def kernel_source_digest():
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir, hs_list, budget=48 << 20):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- hidden states 0..L of every utterance
+    of every group -- as .npy files.  All of it is 1.6 GB at the headline shape, so at most `budget` bytes of (utterance, frame)
+    rows are kept, drawn with a fixed seed from the output's shape alone: two builds run with the same arguments dump the same rows.
+      hidden_states.npy  float32 [L+1, R, D]: the sampled rows of every state
+      rows.npy           float64 [R, 3]: (group, utterance in the group, frame) of each sampled row"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    index = np.array([(g, u, t) for g, h in enumerate(hs_list) for u in range(h.batch) for t in range(h.frames(u))], dtype=np.int64)
+    n_states, dim = min(h.computed for h in hs_list), hs_list[0].states.shape[-1]
+    keep = min(len(index), budget // (4 * n_states * dim))
+    rows = index[np.sort(np.random.default_rng(0).choice(len(index), size=keep, replace=False))]    # (g, u, t) order = group order
+    parts = []
+    for g, h in enumerate(hs_list):
+        sel = [h.frame_offs[u] + t for _, u, t in rows[rows[:, 0] == g]]
+        parts.append(h.states[:n_states].index_select(1, torch.tensor(sel, dtype=torch.long, device=h.states.device)).float().cpu())
+    np.save(os.path.join(out_dir, "hidden_states.npy"), torch.cat(parts, 1).numpy())
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
 
 
 def rel_err(got, ref):
@@ -388,6 +416,9 @@ def main():
     ap.add_argument("--inflight", type=int, default=0,
                     help="whole batches in flight at once, one hipGraph branch (HIP stream) each -- the drivers' two-slot pipeline; "
                          "--inflight 1 --micro 2 is the round-1/2 form (one batch split into two groups of 8)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write the hidden states the last timed step computed to DIR/*.npy "
+                         "(rank 0; a fixed, seeded sample of the rows, < 64 MB: see dump_outputs)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -487,6 +518,8 @@ def main():
         return dt, (hs if hs is not None else hs_ref[0])
 
     elapsed, hs_timed = timed(enc, groups)
+    if rank == 0 and args.dump_outputs:                           # before any later leg re-uses the arenas
+        dump_outputs(args.dump_outputs, hs_timed)
 
     # ---- verification of what was just timed (rank 0): the states the LAST replay left in HBM
     verification = None

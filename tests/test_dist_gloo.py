@@ -98,6 +98,9 @@ def _write_wavs(wav_dir):
 def _driver_worker(rank, world, port, root, extra):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port), SER_TEST_LOG_DIR=root)
+    # the model call is stubbed, so the driver takes its CPU path on every box: with a GPU visible it would bind rank r to
+    # device r, which a one-GPU machine does not have for rank 1
+    torch.cuda.is_available = lambda: False
     from interspeech_ser_amd import dist as D
     from interspeech_ser_amd import driver
     D.init("gloo")

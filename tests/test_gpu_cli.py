@@ -232,8 +232,7 @@ def test_config4_extract_train_eval_end_to_end(tmp_path, capsys):
     bin/train_cat_bimodal_lazy_1head.py here) runs 2 epochs from a reference-style config JSON and saves the best-F1
     ``multimodal_ser.pt`` -> the eval counterpart writes results/dev.csv.  The checkpoint is a checkpoint of the REFERENCE head:
     it loads strictly into the restated class that tests/golden/fusion_head_pins.npz pins to the reference's own definition and
-    gives the same logits as the product model (/root/reference does not exist on this box; the CPU suite loads the same kind
-    of checkpoint into the reference's class itself)."""
+    gives the same logits as the product model."""
     import json
     import pandas as pd
     from interspeech_ser_amd import driver
