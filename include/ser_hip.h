@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SER_ABI_VERSION 14
+#define SER_ABI_VERSION 15
 
 #define SER_MODE_BF16  1   /* act tensors have 1 plane; GEMMs do 1 bf16 MFMA product   */
 #define SER_MODE_FP32X 2   /* act tensors have 2 planes; GEMMs do hi*hi + lo*hi + hi*lo */
@@ -189,6 +189,14 @@ typedef struct ser_gemm_args {
      * clipped ones (preprocess_speech.py:46,72-73: a bad file is a printed failure, never silent garbage).  ser_layernorm_v,
      * ser_row_center_v, ser_wave_frames_v, ser_pack_act_v and ser_pack_f16m take the same word. */
     uint32_t*       range_flag;
+    /* GroupNorm-over-time stem (ABI 15; conv layer 0 of the *-base checkpoints, HF WavLMGroupNormConvLayer): with gn_scale != NULL the
+     * epilogue applies, after the bias and before act,  v = v * gn_scale[u][n] + gn_shift[u][n]  where u is the utterance of row m
+     * (gn_row_offs[u] <= m < gn_row_offs[u + 1], B + 1 entries): the per-(utterance, channel) affine ser_gn_stats_v computes.  A block
+     * tile may straddle utterances.  Needs groups == 1, no LayerNorm epilogue, no deferred LayerNorm.  NULL (zero) = no affine. */
+    const float*    gn_scale;       /* [gn_B][gn_ld] */
+    const float*    gn_shift;       /* [gn_B][gn_ld] */
+    const int32_t*  gn_row_offs;    /* [gn_B + 1] */
+    int32_t         gn_B, gn_ld;
 } ser_gemm_args;
 int ser_gemm(const ser_gemm_args* args, void* stream);
 
@@ -384,10 +392,30 @@ int ser_pack_act_v(const ser_pack_act_args* args, void* stream);
 
 typedef struct ser_wave_frames_args {
     const float* wav; const int64_t* sample_offs; const int32_t* frame_offs; int32_t B, k, stride, mode;
-    void* out; int64_t out_plane_stride; void* work; int32_t total_rows, reserved0;
+    void* out; int64_t out_plane_stride; void* work; int32_t total_rows;
+    int32_t no_norm;                                /* ABI 15: 1 = frames of the raw samples (do_normalize=False checkpoints); 0 = normalise */
     uint32_t* range_flag;                           /* fp16 range guard, may be NULL (ABI 13) */
 } ser_wave_frames_args;
 int ser_wave_frames_v(const ser_wave_frames_args* args, void* stream);
+
+/* K2g (ABI 15)  GroupNorm-over-time statistics of conv layer 0 for the *-base checkpoints (Conv1d(1, C, k, stride) -> GroupNorm(C, C,
+ * eps) -> GELU, HF WavLMGroupNormConvLayer; the reference runs one file at a time, preprocess_speech.py:76-81, so the statistics of an
+ * utterance cover exactly its frames).  Channel c is linear in the k-sample frame, so per utterance  mean_c = w_c . m + b_c,
+ * var_c = w_c^T S w_c  from the frame mean m and covariance S: one read of the waveform, fp64 moments over a fixed chunking (32 chunks
+ * per utterance, fixed merge order, no atomics: independent of the batch).  The frames are those ser_wave_frames writes: normalised
+ * with its statistics (wave_stats = its workspace, so it must run first on the stream) unless no_norm.  Writes per (utterance b, channel c)
+ *   scale[b * ld + c] = gamma_c * rstd_c,   shift[b * ld + c] = beta_c - mean_c * scale,
+ * the ser_gemm_args.gn_scale / gn_shift of the conv-0 GEMM, and optionally stat_out[(b * C + c) * 2 + {0, 1}] = (mean_c, rstd_c).
+ * w: [C][k] fp32 (k <= 10); bias may be NULL; frame_offs: rows of conv layer 0 [B + 1]; work: ser_workspace_bytes(SER_WS_GN_STATS, B). */
+typedef struct ser_gn_stats_args {
+    const float* wav; const int64_t* sample_offs; const int32_t* frame_offs;
+    const float* w; const float* bias; const float* gamma; const float* beta;
+    const void* wave_stats;
+    float* scale; float* shift; float* stat_out; void* work;
+    int32_t B, C, k, stride, ld, no_norm;
+    float eps; int32_t reserved0;
+} ser_gn_stats_args;
+int ser_gn_stats_v(const ser_gn_stats_args* args, void* stream);
 
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
@@ -396,6 +424,7 @@ int ser_wave_frames_v(const ser_wave_frames_args* args, void* stream);
 #define SER_OP_ROW_CENTER 5
 #define SER_OP_LOGMEL 6
 #define SER_OP_PACK_ACT 7
+#define SER_OP_GN_STATS 8
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -406,6 +435,7 @@ typedef struct ser_cmd {
         ser_row_center_args  row_center;
         ser_logmel_args      logmel;
         ser_pack_act_args    pack_act;
+        ser_gn_stats_args    gn_stats;
     } u;
 } ser_cmd;
 
@@ -425,6 +455,7 @@ int     ser_pt_write_f32(const char* path, const float* host_data, int64_t rows,
 
 #define SER_WS_LOGMEL 1
 #define SER_WS_WAVE_FRAMES 2
+#define SER_WS_GN_STATS 3
 size_t ser_workspace_bytes(int op, int B, int T, int D, int H, int mode);
 
 #ifdef __cplusplus

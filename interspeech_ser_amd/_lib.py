@@ -25,7 +25,8 @@ ACT_NONE = 0
 ACT_GELU = 1
 WS_LOGMEL = 1
 WS_WAVE_FRAMES = 2
-ABI_VERSION = 14
+WS_GN_STATS = 3
+ABI_VERSION = 15
 
 c_void_p, c_int, c_i64, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -51,6 +52,7 @@ class GemmArgs(C.Structure):
         ("ln_shift", c_void_p), ("mean_out", c_void_p), ("lnstat_out", c_void_p),
         ("a_scale", c_void_p), ("a_scale_ld", c_i64), ("w_scale", c_void_p), ("w_scale_ld", c_i64),
         ("out_scale", c_void_p), ("out_scale_ld", c_i64), ("range_flag", c_void_p),
+        ("gn_scale", c_void_p), ("gn_shift", c_void_p), ("gn_row_offs", c_void_p), ("gn_B", C.c_int32), ("gn_ld", C.c_int32),
     ]
 
 
@@ -89,8 +91,20 @@ class WaveFramesArgs(C.Structure):
         ("wav", c_void_p), ("sample_offs", c_void_p), ("frame_offs", c_void_p),
         ("B", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("mode", C.c_int32),
         ("out", c_void_p), ("out_plane_stride", c_i64), ("work", c_void_p),
-        ("total_rows", C.c_int32), ("reserved0", C.c_int32),
+        ("total_rows", C.c_int32), ("no_norm", C.c_int32),
         ("range_flag", c_void_p),
+    ]
+
+
+class GnStatsArgs(C.Structure):
+    """Mirror of ``ser_gn_stats_args`` (ABI 15)."""
+    _fields_ = [
+        ("wav", c_void_p), ("sample_offs", c_void_p), ("frame_offs", c_void_p),
+        ("w", c_void_p), ("bias", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
+        ("wave_stats", c_void_p),
+        ("scale", c_void_p), ("shift", c_void_p), ("stat_out", c_void_p), ("work", c_void_p),
+        ("B", C.c_int32), ("C", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("ld", C.c_int32), ("no_norm", C.c_int32),
+        ("eps", c_float), ("reserved0", C.c_int32),
     ]
 
 
@@ -119,7 +133,7 @@ class PackActArgs(C.Structure):
 
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
-                ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs)]
+                ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs)]
 
 
 class Cmd(C.Structure):
@@ -127,10 +141,10 @@ class Cmd(C.Structure):
     _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("u", _CmdUnion)]
 
 
-OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT = 1, 2, 3, 4, 5, 6, 7
+OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS = 1, 2, 3, 4, 5, 6, 7, 8
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
-                  "ser_pack_act_args": PackActArgs, "ser_cmd": Cmd}
+                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -148,6 +162,7 @@ _SIGNATURES = {
     "ser_layernorm_v": (c_int, [c_void_p, c_void_p]),
     "ser_wave_frames_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_act_v": (c_int, [c_void_p, c_void_p]),
+    "ser_gn_stats_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -37,6 +37,10 @@ class EncoderGeometry:
     conv_stride: Tuple[int, ...] = (5, 2, 2, 2, 2, 2, 2)
     conv_bias: bool = False
     feat_proj_layer_norm: bool = True      # HuBERT makes this optional
+    # the *-base checkpoints (HF config defaults): GroupNorm(C, C) over time after conv layer 0 and no norm after layers 1..6
+    # ("group"), post-LayerNorm encoder layers (stable_layer_norm False); the *-large / xlarge / XLS-R ones: "layer", True
+    feat_extract_norm: str = "layer"
+    stable_layer_norm: bool = True
     pos_conv_kernel: int = 128
     pos_conv_groups: int = 16
     # WavLM gated relative position bias
@@ -122,6 +126,18 @@ DEBERTA_V2_XXLARGE = EncoderGeometry(
     pad_token_id=0, type_vocab_size=0, layer_norm_eps=1e-7, position_buckets=256, text_conv_kernel=3,
     name="microsoft/deberta-v2-xxlarge")
 
+# the base checkpoints: transformers' WavLMConfig() / Wav2Vec2Config() / HubertConfig() defaults (GroupNorm stem, post-LN encoder)
+WAVLM_BASE = EncoderGeometry(
+    family=FAMILY_WAVLM, num_layers=12, hidden=768, heads=12, ffn=3072, conv_bias=False,
+    feat_extract_norm="group", stable_layer_norm=False, name="microsoft/wavlm-base")
+WAVLM_BASE_PLUS = replace(WAVLM_BASE, name="microsoft/wavlm-base-plus")
+WAV2VEC2_BASE = EncoderGeometry(
+    family=FAMILY_WAV2VEC2, num_layers=12, hidden=768, heads=12, ffn=3072, conv_bias=False,
+    feat_extract_norm="group", stable_layer_norm=False, name="facebook/wav2vec2-base")
+HUBERT_BASE = EncoderGeometry(
+    family=FAMILY_HUBERT, num_layers=12, hidden=768, heads=12, ffn=3072, conv_bias=False,
+    feat_extract_norm="group", stable_layer_norm=False, name="facebook/hubert-base-ls960")
+
 _REGISTRY = {
     "microsoft/deberta-v3-large": DEBERTA_V3_LARGE,
     "microsoft/deberta-v2-xlarge": DEBERTA_V2_XLARGE,
@@ -135,15 +151,22 @@ _REGISTRY = {
     "facebook/hubert-xlarge-ls960-ft": HUBERT_XLARGE,
     "facebook/hubert-xlarge-ll60k": HUBERT_XLARGE,
     "openai/whisper-large-v3": WHISPER_LARGE_V3,
+    "microsoft/wavlm-base": WAVLM_BASE,             # "wavlm-base": the reference's organiser baseline (suffix rule of geometry_for)
+    "microsoft/wavlm-base-plus": WAVLM_BASE_PLUS,
+    "microsoft/wavlm-base-plus-sv": replace(WAVLM_BASE, name="microsoft/wavlm-base-plus-sv"),
+    "facebook/wav2vec2-base": WAV2VEC2_BASE,
+    "facebook/hubert-base-ls960": HUBERT_BASE,
 }
 
 
 def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int = 2,
-                  ffn: int = 256, conv_dim: int = 64, pos_groups: int = 2, text_conv_kernel: int = 0) -> EncoderGeometry:
+                  ffn: int = 256, conv_dim: int = 64, pos_groups: int = 2, text_conv_kernel: int = 0,
+                  base: bool = False) -> EncoderGeometry:
     """Small geometries with the real kernel/stride tuples; used by the parity
     fixtures under tests/golden (SURVEY 8c item 1).  ``hidden // heads`` selects
     the head-dim code path (64 WavLM/Whisper, 80 HuBERT-XL, 120 XLS-R-2B) and
-    ``hidden // pos_groups`` the pos-conv group width (64 / 80 / 120 in the real models)."""
+    ``hidden // pos_groups`` the pos-conv group width (64 / 80 / 120 in the real models).  ``base=True``: the *-base form of a
+    speech family (GroupNorm stem, post-LN encoder, no conv bias)."""
     if family == FAMILY_ROBERTA:
         return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn,
                                vocab_size=300, max_positions=90, name=f"tiny-{family}-d{hidden}h{heads}")
@@ -157,6 +180,12 @@ def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int
         return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads,
                                ffn=ffn, n_mels=128, max_source_positions=1500,
                                name=f"tiny-{family}-d{hidden}h{heads}")
+    if base:
+        return EncoderGeometry(
+            family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn,
+            conv_dim=(conv_dim,) * 7, conv_bias=False, pos_conv_groups=pos_groups,
+            feat_extract_norm="group", stable_layer_norm=False,
+            name=f"tiny-{family}-base-d{hidden}h{heads}")
     return EncoderGeometry(
         family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn,
         conv_dim=(conv_dim,) * 7, conv_bias=(family != FAMILY_WAVLM),
@@ -181,17 +210,20 @@ def geometry_for(ssl_type: str) -> EncoderGeometry:
 def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
     """Geometry from a checkpoint's ``config.json`` -- what ``AutoModel.from_pretrained(--ssl_type)`` reads for ANY hub id or
     local snapshot (preprocess_speech.py:111-112, preprocess_whisper.py:119-120), so fine-tunes published under another name
-    work without a registry entry.  Variants this build does not implement are refused with ``OSError``, the class the
-    reference's driver reports as "No pretrained model found" (:115-117): GroupNorm feature extractors
-    (``feat_extract_norm="group"``: wav2vec2-base, hubert-base / large-ll60k) and post-LayerNorm encoders
-    (``do_stable_layer_norm=False``)."""
+    work without a registry entry.  Two speech forms are implemented: the layer-norm stem with a stable-LayerNorm encoder
+    (*-large / xlarge / XLS-R) and the GroupNorm stem with a post-LayerNorm encoder (*-base: ``feat_extract_norm="group"``,
+    ``do_stable_layer_norm=False``).  The two mixed combinations, which no published checkpoint uses, are refused with
+    ``OSError``, the class the reference's driver reports as "No pretrained model found" (:115-117)."""
     mt = str(cfg.get("model_type", "")).lower()
     name = name or str(cfg.get("_name_or_path", "")) or mt
     if mt in (FAMILY_WAVLM, FAMILY_WAV2VEC2, FAMILY_HUBERT):
-        if cfg.get("feat_extract_norm", "group") != "layer":
+        norm, stable = cfg.get("feat_extract_norm", "group"), bool(cfg.get("do_stable_layer_norm", False))
+        if norm not in ("layer", "group"):
+            raise OSError(f"{name}: feat_extract_norm='{norm}' is not supported")
+        if norm != "layer" and stable:
             raise OSError(f"{name}: feat_extract_norm='{cfg.get('feat_extract_norm', 'group')}' (GroupNorm over time) is not supported; "
                           "the path implements the layer-norm feature extractor of the *-large / xlarge / XLS-R checkpoints")
-        if not cfg.get("do_stable_layer_norm", False):
+        if norm == "layer" and not stable:
             raise OSError(f"{name}: do_stable_layer_norm=False (post-LayerNorm encoder) is not supported")
         if mt == FAMILY_HUBERT and not cfg.get("feat_proj_layer_norm", True):
             raise OSError(f"{name}: feat_proj_layer_norm=False is not supported")
@@ -204,7 +236,7 @@ def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
             conv_bias=bool(cfg.get("conv_bias", False)), feat_proj_layer_norm=bool(cfg.get("feat_proj_layer_norm", True)),
             pos_conv_kernel=int(cfg.get("num_conv_pos_embeddings", 128)), pos_conv_groups=int(cfg.get("num_conv_pos_embedding_groups", 16)),
             num_buckets=int(cfg.get("num_buckets", 320)), max_bucket_distance=int(cfg.get("max_bucket_distance", 800)),
-            layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), name=name)
+            layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), feat_extract_norm=norm, stable_layer_norm=stable, name=name)
     if mt == FAMILY_WHISPER:
         return EncoderGeometry(
             family=FAMILY_WHISPER, num_layers=int(cfg["encoder_layers"]), hidden=int(cfg["d_model"]),
@@ -266,6 +298,33 @@ def resolve_geometry(ssl_type: str, checkpoint: str = "") -> EncoderGeometry:
     return geometry_for(ssl_type)
 
 
+def find_preprocessor_config(ssl_type: str, checkpoint: str = "") -> str:
+    """Path of the ``preprocessor_config.json`` beside the ``config.json`` that ``find_config_json`` picks ("" when there is none):
+    what ``AutoFeatureExtractor.from_pretrained(--ssl_type)`` reads (preprocess_speech.py:43)."""
+    import os
+    cfg = find_config_json(ssl_type, checkpoint)
+    if cfg:
+        p = os.path.join(os.path.dirname(cfg), "preprocessor_config.json")
+        return p if os.path.isfile(p) else ""
+    return ""
+
+
+def resolve_do_normalize(ssl_type: str, checkpoint: str = "") -> bool:
+    """``do_normalize`` of the checkpoint's feature extractor: the zero-mean / unit-variance input normalisation
+    (HF feature_extraction_wav2vec2.py).  True when the snapshot has no ``preprocessor_config.json`` (the path's behaviour
+    before it read the file; also the value of the *-large checkpoints)."""
+    import json
+    path = find_preprocessor_config(ssl_type, checkpoint)
+    if not path:
+        return True
+    try:
+        with open(path, "r") as f:
+            cfg = json.load(f)
+    except (OSError, ValueError) as e:
+        raise OSError(f"cannot read {path}: {e}")
+    return bool(cfg.get("do_normalize", True))
+
+
 def with_layers(geo: EncoderGeometry, layers: int) -> EncoderGeometry:
     return replace(geo, num_layers=layers)
 
@@ -279,3 +338,7 @@ TINY_WHISPER = tiny_geometry(FAMILY_WHISPER, hidden=128, heads=2, ffn=256)
 TINY_ROBERTA = tiny_geometry(FAMILY_ROBERTA, hidden=128, heads=2, ffn=256)
 TINY_DEBERTA = tiny_geometry(FAMILY_DEBERTA, hidden=128, heads=2, ffn=256)
 TINY_DEBERTA_CONV = tiny_geometry(FAMILY_DEBERTA, hidden=128, heads=2, ffn=256, text_conv_kernel=3)      # deberta-v2-xlarge style
+# *-base fixture geometries (GroupNorm stem, post-LN encoder; tests/golden/tiny_*_base_*.npz)
+TINY_WAVLM_BASE = tiny_geometry(FAMILY_WAVLM, hidden=128, heads=2, ffn=256, pos_groups=2, base=True)
+TINY_WAV2VEC2_BASE = tiny_geometry(FAMILY_WAV2VEC2, hidden=128, heads=2, ffn=256, pos_groups=2, base=True)
+TINY_HUBERT_BASE = tiny_geometry(FAMILY_HUBERT, hidden=128, heads=2, ffn=256, pos_groups=2, base=True)

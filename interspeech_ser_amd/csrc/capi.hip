@@ -18,6 +18,8 @@ extern "C" size_t ser_workspace_bytes(int op, int B, int T, int D, int H, int mo
         case SER_WS_LOGMEL:
             // per-block partial maxima [B][256] floats + the fp64 twiddle table [400][208] x (cos, -sin) + the Hann window (ser_logmel_init)
             return (size_t)(B > 0 ? B : 1) * 1024 + (size_t)400 * 208 * 16 + 400 * 4;
+        case SER_WS_GN_STATS:
+            return (size_t)(B > 0 ? B : 1) * 32 * 65 * sizeof(double);     // [B][32 chunks][65 frame moments] (rowops.hip K2g)
         case SER_WS_WAVE_FRAMES:
             return (size_t)(B > 0 ? B : 1) * 64 * 2 * sizeof(double);      // [B][64] partial (sum, sum^2)
         default:
@@ -59,6 +61,10 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
             }
             case SER_OP_PACK_ACT: {
                 rc = ser_pack_act_v(&c.u.pack_act, stream);
+                break;
+            }
+            case SER_OP_GN_STATS: {
+                rc = ser_gn_stats_v(&c.u.gn_stats, stream);
                 break;
             }
             default:

@@ -990,6 +990,16 @@ void ser_gemm_kernel(const ser_gemm_args p) {
             }
             const float cshift = cs[mi];
             if (p.shift_out && nt == 0 && g == 0 && wn == 0 && fq == 0) p.shift_out[m] = cshift;
+            // GroupNorm-over-time stem (ABI 15): per-(utterance, column) affine of the row's utterance; a tile may straddle utterances, so
+            // each row finds its own (binary search of gn_row_offs, wave-uniform flag: launches without it pay one branch)
+            const float* gsc = nullptr;
+            const float* gsh = nullptr;
+            if (p.gn_scale) {
+                int lo = 0, hi = p.gn_B;                              // largest u with gn_row_offs[u] <= m
+                while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (p.gn_row_offs[mid] <= m) lo = mid; else hi = mid; }
+                gsc = p.gn_scale + (int64_t)lo * p.gn_ld + ncol0;
+                gsh = p.gn_shift + (int64_t)lo * p.gn_ld + ncol0;
+            }
             float st1 = 0.f, st2 = 0.f;
             unsigned mcode[2] = {0u, 0u};                             // FP16M out copy: (P, Q) codes of the two blocks of a 64-column tile
 #pragma unroll
@@ -1001,6 +1011,7 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                     const int nj = ni + (r >> 2), rr = r & 3;
                     // LN(x) W^T = rstd * (x W'^T - mu * colsum(W')) + (beta W^T + b)
                     float x = fmaf(rs, acc[nj][mi][rr] - mu * csum[nj * 4 + rr], bias[nj * 4 + rr]);
+                    if (gsc && ncol0 + nj * 16 < p.N) x = fmaf(x, gsc[nj * 16 + rr], gsh[nj * 16 + rr]);   // GroupNorm: (acc + b) * gamma*rstd + (beta - mean*gamma*rstd)
                     if (do_scale && ncol0 + nj * 16 < p.col_scale_end) x *= p.col_scale;   // e.g. q *= dh^-0.5 * log2(e)
                     v[r] = x;
                 }
@@ -1280,6 +1291,10 @@ extern "C" int ser_gemm(const ser_gemm_args* a, void* stream) {
     if (a->out_mode && a->out_mode != a->mode && a->ln_gamma)
         return ser_fail(-21, "ser_gemm: out_mode %d with the LayerNorm epilogue", a->out_mode);
     if (a->col_scale_end % 4) return ser_fail(-17, "ser_gemm: col_scale_end must be a multiple of 4");
+    if (a->gn_scale && (!a->gn_shift || !a->gn_row_offs || a->gn_B < 1 || a->gn_ld < a->N || (a->gn_ld % 4) || a->groups != 1 ||
+                        a->ln_gamma || a->ln_stats_in))
+        return ser_fail(-25, "ser_gemm: gn_scale needs gn_shift, gn_row_offs, gn_B >= 1, gn_ld >= N (multiple of 4), groups == 1, "
+                             "no LayerNorm epilogue and no deferred LayerNorm");
     if ((a->ldo_act % 8) || (a->c_group_stride % 8)) return ser_fail(-18, "ser_gemm: act pitch / group stride must be multiples of 8");
     if (a->f32_col_begin < 0 || (a->f32_col_begin % 8)) return ser_fail(-16, "ser_gemm: f32_col_begin must be a non-negative multiple of 8");
 #ifdef SER_EXPERIMENTS

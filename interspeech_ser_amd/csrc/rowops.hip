@@ -75,7 +75,8 @@ __global__ __launch_bounds__(256) void wave_stats_kernel(const float* __restrict
 template <int MODE>
 __global__ __launch_bounds__(256) void wave_frames_kernel(const float* __restrict__ wav, const int64_t* __restrict__ soffs,
                                                           const int32_t* __restrict__ foffs, const double* __restrict__ part,
-                                                          unsigned short* __restrict__ out, int64_t plane, int k, int stride, uint32_t* __restrict__ rflag) {
+                                                          unsigned short* __restrict__ out, int64_t plane, int k, int stride, uint32_t* __restrict__ rflag,
+                                                          int no_norm) {
     __shared__ float stat[2];
     float ramax = 0.f;
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void wave_frames_kernel(const float* __restric
         }
     }
     __syncthreads();
-    const float mean = stat[0], rstd = stat[1];
+    const float mean = no_norm ? 0.f : stat[0], rstd = no_norm ? 1.f : stat[1];     // no_norm: do_normalize=False checkpoints
     const int row_begin = foffs[b], T = foffs[b + 1] - row_begin;
     const float* x = wav + s0;
     const int c = tid & 7;                                        // 16-byte chunk of the 128-byte row
@@ -127,7 +128,8 @@ extern "C" int ser_wave_frames_v(const ser_wave_frames_args* a, void* stream) {
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
 #define SER_WF(M_) hipLaunchKernelGGL(wave_frames_kernel<M_>, dim3(blocks, B), dim3(256), 0, s, wav, sample_offs, frame_offs, \
-                                      (const double*)work, (unsigned short*)out, out_plane_stride, k, stride, a->range_flag)
+                                      (const double*)work, (unsigned short*)out, out_plane_stride, k, stride, a->range_flag, \
+                                      a->no_norm)
     if (mode == SER_MODE_FP32X) SER_WF(SER_MODE_FP32X);
     else if (mode == SER_MODE_FP16X) SER_WF(SER_MODE_FP16X);
     else SER_WF(SER_MODE_BF16);
@@ -750,4 +752,131 @@ extern "C" int ser_pack_f16m(const float* x, int64_t ldx, int rows, int cols, vo
     hipLaunchKernelGGL(pack_f16m_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ldx, rows, cols,
                        (unsigned short*)out, ldo, plane_stride, scales, scale_ld, is_weight, range_flag);
     return ser_check_launch("ser_pack_f16m");
+}
+
+// ------------------------------------------------------------------------------- K2g
+// GroupNorm-over-time statistics of conv layer 0 (the *-base checkpoints: Conv1d(1, C, k, s) -> GroupNorm(C, C) -> GELU, HF
+// modeling_wavlm.py WavLMGroupNormConvLayer).  Channel c of frame t is w_c . f_t + b_c with f_t the k samples of the frame, so over
+// one utterance  mean_c = w_c . m + b_c  and  var_c = w_c^T S w_c  (biased), m / S = mean / covariance of its frames: k + k(k+1)/2
+// fp64 moments per utterance instead of a pass over the [frames, C] conv output.  The moments are taken over the RAW samples; the
+// waveform normalisation of ser_wave_frames is affine (f' = (f - mu) r), so m' = (m - mu) r and S' = r^2 S in closed form.
+// Fixed chunk grid per utterance, fixed merge order, no atomics: the result of an utterance does not depend on its batch.
+#define SER_GN_KMAX 10
+#define SER_GN_NMOM (SER_GN_KMAX + SER_GN_KMAX * (SER_GN_KMAX + 1) / 2)     // 65
+#define SER_GN_CHUNKS 32
+
+__global__ __launch_bounds__(256) void gn_moments_kernel(const float* __restrict__ wav, const int64_t* __restrict__ soffs,
+                                                         const int32_t* __restrict__ foffs, int k, int stride,
+                                                         double* __restrict__ part /*[B][CHUNKS][NMOM]*/) {
+    __shared__ double red[4][SER_GN_NMOM];
+    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int T = foffs[b + 1] - foffs[b];
+    const int per = (T + SER_GN_CHUNKS - 1) / SER_GN_CHUNKS;
+    const int lo = chunk * per, hi = (lo + per < T) ? lo + per : T;
+    const float* x = wav + soffs[b];
+    double s[SER_GN_KMAX], q[SER_GN_NMOM - SER_GN_KMAX];
+#pragma unroll
+    for (int j = 0; j < SER_GN_KMAX; ++j) s[j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < SER_GN_NMOM - SER_GN_KMAX; ++j) q[j] = 0.0;
+    for (int t = lo + tid; t < hi; t += 256) {                    // frame t = samples [t*stride, t*stride + k): inside the utterance
+        double f[SER_GN_KMAX];
+#pragma unroll
+        for (int j = 0; j < SER_GN_KMAX; ++j) f[j] = (j < k) ? (double)x[(int64_t)t * stride + j] : 0.0;
+#pragma unroll
+        for (int i = 0, n = 0; i < SER_GN_KMAX; ++i) {
+            s[i] += f[i];
+#pragma unroll
+            for (int j = i; j < SER_GN_KMAX; ++j, ++n) q[n] = fma(f[i], f[j], q[n]);
+        }
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < SER_GN_NMOM; ++j) {
+        double v = j < SER_GN_KMAX ? s[j] : q[j - SER_GN_KMAX];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[wv][j] = v;
+    }
+    __syncthreads();
+    if (tid < SER_GN_NMOM)
+        part[((int64_t)b * SER_GN_CHUNKS + chunk) * SER_GN_NMOM + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, const double* __restrict__ wstat,
+                                                          const int64_t* __restrict__ soffs, const int32_t* __restrict__ foffs,
+                                                          const float* __restrict__ w, const float* __restrict__ bias,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float* __restrict__ scale, float* __restrict__ shift, int ld,
+                                                          float* __restrict__ stat_out, int C, int k, int no_norm, float eps) {
+    __shared__ double mom[SER_GN_NMOM];
+    __shared__ double nrm[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid < SER_GN_NMOM) {
+        double a = 0.0;
+        for (int c = 0; c < SER_GN_CHUNKS; ++c) a += part[((int64_t)b * SER_GN_CHUNKS + c) * SER_GN_NMOM + tid];
+        mom[tid] = a;
+    }
+    if (tid < 64) {             // the per-utterance normalisation ser_wave_frames applied, bit for bit (its fp32 mean and 1/std)
+        double a1 = wstat ? wstat[((int64_t)b * 64 + tid) * 2] : 0.0, a2 = wstat ? wstat[((int64_t)b * 64 + tid) * 2 + 1] : 0.0;
+        for (int o = 32; o > 0; o >>= 1) { a1 += __shfl_xor(a1, o, 64); a2 += __shfl_xor(a2, o, 64); }
+        if (tid == 0) {
+            const double n = (double)(soffs[b + 1] - soffs[b]);
+            const double mean = a1 / n, var = a2 / n - mean * mean;
+            nrm[0] = no_norm ? 0.0 : (double)(float)mean;
+            nrm[1] = no_norm ? 1.0 : (double)(1.0f / sqrtf((float)(var > 0.0 ? var : 0.0) + 1e-7f));
+        }
+    }
+    __syncthreads();
+    const double T = (double)(foffs[b + 1] - foffs[b]);
+    const double mu = nrm[0], r = nrm[1];
+    double m[SER_GN_KMAX], S[SER_GN_KMAX][SER_GN_KMAX];
+#pragma unroll
+    for (int i = 0; i < SER_GN_KMAX; ++i) m[i] = mom[i] / T;
+#pragma unroll
+    for (int i = 0, n = 0; i < SER_GN_KMAX; ++i)
+#pragma unroll
+        for (int j = i; j < SER_GN_KMAX; ++j, ++n) {
+            const double c = (mom[SER_GN_KMAX + n] / T - m[i] * m[j]) * (r * r);     // covariance of the normalised frames
+            S[i][j] = c; S[j][i] = c;
+        }
+#pragma unroll
+    for (int i = 0; i < SER_GN_KMAX; ++i) m[i] = (m[i] - mu) * r;
+    for (int c = tid; c < C; c += 256) {
+        double wc[SER_GN_KMAX];
+#pragma unroll
+        for (int j = 0; j < SER_GN_KMAX; ++j) wc[j] = (j < k) ? (double)w[(int64_t)c * k + j] : 0.0;
+        double mean = bias ? (double)bias[c] : 0.0, var = 0.0;
+#pragma unroll
+        for (int i = 0; i < SER_GN_KMAX; ++i) {
+            mean = fma(wc[i], m[i], mean);
+            double row = 0.0;
+#pragma unroll
+            for (int j = 0; j < SER_GN_KMAX; ++j) row = fma(S[i][j], wc[j], row);
+            var = fma(wc[i], row, var);
+        }
+        const double rstd = 1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps);
+        const double sc = (double)gamma[c] * rstd;
+        scale[(int64_t)b * ld + c] = (float)sc;
+        shift[(int64_t)b * ld + c] = (float)((double)beta[c] - mean * sc);
+        if (stat_out) {
+            stat_out[((int64_t)b * C + c) * 2] = (float)mean;
+            stat_out[((int64_t)b * C + c) * 2 + 1] = (float)rstd;
+        }
+    }
+}
+
+extern "C" int ser_gn_stats_v(const ser_gn_stats_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_gn_stats: null pointer");
+    if (!a->wav || !a->sample_offs || !a->frame_offs || !a->w || !a->gamma || !a->beta || !a->scale || !a->shift || !a->work)
+        return ser_fail(-1, "ser_gn_stats: null pointer");
+    if (!a->no_norm && !a->wave_stats) return ser_fail(-1, "ser_gn_stats: normalised input needs wave_stats (ser_wave_frames' workspace)");
+    if (a->B <= 0 || a->C <= 0 || a->k < 1 || a->k > SER_GN_KMAX || a->stride < 1 || a->ld < a->C)
+        return ser_fail(-2, "ser_gn_stats: bad B=%d C=%d k=%d (1..%d) stride=%d ld=%d", a->B, a->C, a->k, SER_GN_KMAX, a->stride, a->ld);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(gn_moments_kernel, dim3(SER_GN_CHUNKS, a->B), dim3(256), 0, s, a->wav, a->sample_offs, a->frame_offs,
+                       a->k, a->stride, (double*)a->work);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(a->B), dim3(256), 0, s, (const double*)a->work,
+                       a->no_norm ? (const double*)nullptr : (const double*)a->wave_stats, a->sample_offs, a->frame_offs,
+                       a->w, a->bias, a->gamma, a->beta, a->scale, a->shift, a->ld, a->stat_out, a->C, a->k, a->no_norm, a->eps);
+    return ser_check_launch("ser_gn_stats");
 }

@@ -151,7 +151,12 @@ class _Extractor:
             # reference's four) runs the 3-product split everywhere instead -- same or better parity, ~10 % slower
             print(f"--mode {args.mode} needs hidden / feed-forward widths that are multiples of 64 (here {self.geo.hidden} / {self.geo.ffn}): using f16x")
             args.mode = "f16x"
-        self.enc = build_encoder(self.geo, sd, device, args.mode)
+        if not whisper and not self.geo.stable_layer_norm and args.mode not in ("bf16", "fp32x", "f16x"):
+            # the post-LayerNorm (*-base) encoders run the text encoders' modes; the others need FP16M copies out of ser_layernorm
+            print(f"--mode {args.mode} is not implemented for post-LayerNorm encoders ({args.ssl_type}): using f16x")
+            args.mode = "f16x"
+        normalize = True if whisper else C.resolve_do_normalize(args.ssl_type, args.checkpoint)   # AutoFeatureExtractor's do_normalize
+        self.enc = build_encoder(self.geo, sd, device, args.mode, normalize=normalize)
         del sd                                                # the fp32 broadcast bucket (views of it) is not needed any more
         if torch.cuda.is_available():
             torch.cuda.empty_cache()

@@ -378,7 +378,7 @@ class _EncoderBase:
               out_rowmap=None, a_ptr_offset=0, k_algo=None, ln=None, ln_eps=1e-5, tile_cfg=0,
               ln_stats=None, ln_groups=0, stat_out=None, stat_groups=0, f32_col_begin=0,
               col_scale=1.0, col_scale_end=0, shift=None, ln_mean=None, stem=False, out_mode=0, mode=None, out_col=0,
-              lnstat_out=None):
+              lnstat_out=None, gn=None):
         rec = self._rec
         g = rec.slot("gemm") if rec is not None else GemmArgs()
         g.A = a.ptr + a_ptr_offset
@@ -421,6 +421,8 @@ class _EncoderBase:
             g.ln_shift, g.mean_out = _ptr(ln_mean[0]), ln_mean[1].data_ptr()
         g.lnstat_out = _ptr(lnstat_out)         # (relative mean, rstd) of the A rows for the attention kernel's in-kernel gate
         g.range_flag = self._flag if out_act is not None else None
+        if gn is not None:                      # GroupNorm-over-time stem: (scale, shift, row offsets, B) -- per-(utterance, column) affine
+            g.gn_scale, g.gn_shift, g.gn_row_offs, g.gn_B, g.gn_ld = gn[0].data_ptr(), gn[1].data_ptr(), gn[2].data_ptr(), gn[3], gn[0].shape[1]
         if g.mode == _lib.MODE_FP16M:           # block scales of both operands
             g.a_scale, g.a_scale_ld = a.scale.data_ptr(), a.scale_ld
             g.w_scale, g.w_scale_ld = lin.wscale.data_ptr(), lin.wscale.shape[1]
@@ -429,7 +431,7 @@ class _EncoderBase:
                 raise ValueError("an FP16M output must start on a 64-column tile")
             g.out_scale, g.out_scale_ld = out_act.scale.data_ptr() + 4 * (out_col // 64) * out_act.scale_ld, out_act.scale_ld
         if rec is not None:
-            rec.commit(_lib.OP_GEMM, g, M=M)
+            rec.commit(_lib.OP_GEMM, g, M=M, **({} if gn is None else {"gn_B": gn[3]}))
             return
         if self.gemm_trace is None:
             check(lib.ser_gemm(C.byref(g), self._s()), "ser_gemm")
@@ -798,12 +800,22 @@ def _fold_weight_norm(sd) -> torch.Tensor:
 
 
 class SpeechEncoder(_EncoderBase):
-    """WavLM / wav2vec2 / HuBERT (stable-LayerNorm, layer-norm conv stack) on libserhip."""
+    """WavLM / wav2vec2 / HuBERT on libserhip: the *-large / xlarge / XLS-R form (layer-norm conv stack, stable-LayerNorm encoder) and
+    the *-base form (GroupNorm-over-time conv layer 0, post-LayerNorm encoder; ``geo.stable_layer_norm`` False).  ``normalize``: the
+    feature extractor's ``do_normalize`` (zero-mean / unit-variance input per utterance)."""
 
-    def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "bf16"):
+    POST_LN_MODES = ("bf16", "fp32x", "f16x")
+
+    def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "bf16", normalize: bool = True):
+        if not geo.stable_layer_norm and mode not in self.POST_LN_MODES:
+            raise ValueError(f"the post-LayerNorm (*-base) encoders support the {', '.join(self.POST_LN_MODES)} numerics modes")
         super().__init__(geo, device, mode)
         if geo.family == FAMILY_WHISPER:
             raise ValueError("use WhisperEncoder for the whisper family")
+        self.normalize = bool(normalize)
+        self.post_ln = not geo.stable_layer_norm
+        if self.post_ln != (geo.feat_extract_norm == "group"):
+            raise NotImplementedError("GroupNorm stems come with post-LN encoders and layer-norm stems with stable-LN ones")
         if not geo.feat_proj_layer_norm:
             raise NotImplementedError("feat_proj_layer_norm=False checkpoints are not supported")
         sd = state_dict
@@ -820,7 +832,11 @@ class SpeechEncoder(_EncoderBase):
         w0 = torch.zeros((C0, 64), dtype=torch.float32)
         w0[:, : geo.conv_kernel[0]] = sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]).float()
         self.conv0 = self._linear(w0, sd[p0 + ".conv.bias"] if geo.conv_bias else None, stem=True)
-        self.conv_ln = [self._ln_pair(sd, f"feature_extractor.conv_layers.{i}.layer_norm") for i in range(len(geo.conv_dim))]
+        if self.post_ln:        # GroupNorm(C, C) of conv layer 0 (its affine); layers 1..6 have no norm
+            self.gn0 = self._ln_pair(sd, p0 + ".layer_norm")
+            self.conv_ln = [None] * len(geo.conv_dim)
+        else:
+            self.conv_ln = [self._ln_pair(sd, f"feature_extractor.conv_layers.{i}.layer_norm") for i in range(len(geo.conv_dim))]
         self.convs: List[Linear] = []
         for i in range(1, len(geo.conv_dim)):
             p = f"feature_extractor.conv_layers.{i}.conv"
@@ -848,12 +864,43 @@ class SpeechEncoder(_EncoderBase):
         self.layers = []
         for i in range(geo.num_layers):
             p = f"encoder.layers.{i}"
+            if self.post_ln:
+                self.layers.append(self._post_ln_layer_weights(sd, p))
+                continue
             self.layers.append(self._layer_weights(
                 sd, p, p + ".attention", p + ".layer_norm", p + ".final_layer_norm",
                 p + ".feed_forward.intermediate_dense", p + ".feed_forward.output_dense",
                 k_bias=True, gate=(geo.family == FAMILY_WAVLM), index=i))
         if geo.family == FAMILY_WAVLM:
             self.rel_embed = self._dev_f32(sd["encoder.layers.0.attention.rel_attn_embed.weight"])
+
+    def _post_ln_layer_weights(self, sd, p: str):
+        """One post-LN layer (HF WavLMEncoderLayer / Wav2Vec2EncoderLayer): plain GEMM operands, the two LayerNorms run as
+        ser_layernorm between them (the norm of a 768-wide row spans several GEMM tiles).  WavLM's gate pre-activations ride as 2H
+        extra columns of the packed projection: they are linear in the attention's input, which here is the layer input itself."""
+        D, H, dh = self.geo.hidden, self.geo.heads, self.geo.head_dim
+        a = p + ".attention"
+        ws = [sd[a + ".q_proj.weight"], sd[a + ".k_proj.weight"], sd[a + ".v_proj.weight"]]
+        bs = [sd[a + ".q_proj.bias"], sd[a + ".k_proj.bias"], sd[a + ".v_proj.bias"]]
+        lay = {}
+        if self.geo.family == FAMILY_WAVLM:
+            w8, b8 = sd[a + ".gru_rel_pos_linear.weight"].float(), sd[a + ".gru_rel_pos_linear.bias"].float()
+            wa, wb = w8[:4].sum(0), w8[4:].sum(0)
+            pad = (-2 * H) % 8                                   # GEMM N must stay a multiple of 8
+            wg = torch.zeros(2 * H + pad, D, device=w8.device)
+            for h in range(H):
+                wg[2 * h, h * dh:(h + 1) * dh] = wa
+                wg[2 * h + 1, h * dh:(h + 1) * dh] = wb
+            ws.append(wg)
+            bs.append(torch.cat([torch.stack([b8[:4].sum(), b8[4:].sum()]).repeat(H), torch.zeros(pad, device=w8.device)]))
+            lay["gate_c"] = self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
+        lay["qkv"] = self._linear(torch.cat(ws, 0), torch.cat(bs, 0))
+        lay["out"] = self._linear(sd[a + ".out_proj.weight"], sd[a + ".out_proj.bias"])
+        lay["ln1"] = self._ln_pair(sd, p + ".layer_norm")
+        lay["fc1"] = self._linear(sd[p + ".feed_forward.intermediate_dense.weight"], sd[p + ".feed_forward.intermediate_dense.bias"])
+        lay["fc2"] = self._linear(sd[p + ".feed_forward.output_dense.weight"], sd[p + ".feed_forward.output_dense.bias"])
+        lay["ln2"] = self._ln_pair(sd, p + ".final_layer_norm")
+        return lay
 
     # ------------------------------------------------------------------ batch plan
     # ------------------------------------------------------------------ per-slot arenas + plans
@@ -883,7 +930,10 @@ class SpeechEncoder(_EncoderBase):
         ar["halo_act"] = self._new_act(cap["halo"], D, zero=True, extra_rows=1, stem=self.pos_in_stem)
         ar["states"] = torch.empty((geo.num_layers + 1, cap["M"], D), dtype=torch.float32, device=dev)
         ar["first_groups"] = 2                               # ser_row_center writes one (sum, sum^2) slot + one zero slot
-        self._layer_buffers(ar, cap["M"], ar["first_groups"])
+        if self.post_ln:
+            self._post_ln_buffers(ar, cap)
+        else:
+            self._layer_buffers(ar, cap["M"], ar["first_groups"])
         if geo.family == FAMILY_WAVLM:
             ar["table"] = torch.empty(geo.heads * (2 * cap["Tmax"] - 1), dtype=torch.float32, device=dev)
         # small per-batch tables: one pinned host blob -> one async H2D into one device blob (int64 words)
@@ -897,6 +947,21 @@ class SpeechEncoder(_EncoderBase):
         ar["plan"] = None                                   # (lengths, plan) currently laid out in this arena
         arenas[slot] = ar
         return ar
+
+    def _post_ln_buffers(self, ar, cap):
+        """Arena buffers of the *-base form: the GroupNorm stem's per-(utterance, channel) affine + its workspace, and the post-LN layers'."""
+        geo, dev = self.geo, self.device
+        M, D, C0, B = cap["M"], geo.hidden, geo.conv_dim[0], cap["B"]
+        ar["gn_scale"] = torch.empty((B, C0), dtype=torch.float32, device=dev)
+        ar["gn_shift"] = torch.empty((B, C0), dtype=torch.float32, device=dev)
+        ar["gn_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_GN_STATS, B, 0, 0, 0, self.stem_mode), dtype=torch.uint8, device=dev)
+        if self.fp16_planes:
+            ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        nqkv = 3 * D + (((2 * geo.heads + 7) // 8) * 8 if geo.family == FAMILY_WAVLM else 0)
+        ar["xa"], ar["ha"], ar["ctx"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
+        ar["qkv"], ar["ffn"] = self._new_act(M, nqkv), self._new_act(M, geo.ffn)
+        ar["tmp"] = torch.empty((M, D), dtype=torch.float32, device=dev)
+        ar["h"] = torch.empty((M, D), dtype=torch.float32, device=dev)
 
     def _plan(self, lengths: Sequence[int], slot: int = 0):
         """Row bookkeeping of one ragged batch in slot ``slot``'s arena.  Only O(B) integers are computed on the
@@ -1050,7 +1115,9 @@ class SpeechEncoder(_EncoderBase):
                 finally:
                     self._rec = None
                 ar["tape"] = tape
-            tape.inputs["wav"].wav = packed_wave.data_ptr()
+            for key in ("wav", "wav_gn"):                   # the launches that read the waveform
+                if key in tape.inputs:
+                    tape.inputs[key].wav = packed_wave.data_ptr()
             tape.run(pl["sizes"], self._s(), last_state)
         hs = HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1)
         hs.range_flag = flag
@@ -1067,6 +1134,7 @@ class SpeechEncoder(_EncoderBase):
         a.wav, a.sample_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["frame_offs0"].data_ptr()
         a.B, a.k, a.stride, a.mode = B, geo.conv_kernel[0], geo.conv_stride[0], self.stem_mode
         a.out, a.out_plane_stride, a.work, a.total_rows = fr.ptr, fr.plane_stride, pl["wave_work"].data_ptr(), pl["rows"][0]
+        a.no_norm = 0 if self.normalize else 1
         a.range_flag = self._flag
         if rec is not None:
             rec.inputs["wav"] = a
@@ -1074,8 +1142,11 @@ class SpeechEncoder(_EncoderBase):
         else:
             check(lib.ser_wave_frames_v(C.byref(a), self._s()), "ser_wave_frames")
         a_in = pl["conv_act"][0]
-        self._gemm(fr, self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
-                   k_algo=geo.conv_kernel[0], stem=True)
+        if self.post_ln:
+            self._groupnorm_stem(pl, packed_wave)
+        else:
+            self._gemm(fr, self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
+                       k_algo=geo.conv_kernel[0], stem=True)
         # a7: conv layers 1..6 as implicit GEMMs with LayerNorm(C)+GELU fused into the epilogue
         # (the 512-wide output row lives in one block tile, so the pre-LN activations never touch HBM)
         nl = len(geo.conv_dim)
@@ -1087,7 +1158,7 @@ class SpeechEncoder(_EncoderBase):
                 a_view.t, a_view.rows, a_view.cols, a_view.planes = a_out.t, rows, C0, a_out.planes
                 a_view.plane_stride = a_out.plane_stride
                 self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
-                           ln=self.conv_ln[i], ln_eps=1e-5, out_act=a_view, stem=True)
+                           ln=self.conv_ln[i], ln_eps=1e-5, out_act=a_view, stem=True)     # (ln None: *-base, GELU only)
                 a_in = a_view
             else:
                 self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
@@ -1103,9 +1174,70 @@ class SpeechEncoder(_EncoderBase):
         self._gemm(pl["halo_act"], self.pos, M, a_rowoff=pl["pos_rowoff"], kc=kc, ldj=D, groups=G,
                    a_group_stride=Cg, w_group_stride=Cg * geo.pos_conv_kernel * kc, c_group_stride=Cg,
                    N=Cg, K=geo.pos_conv_kernel * kc, act=_lib.ACT_GELU, residual=pl["proj_f32"], ldr=D,
-                   out_f32=states[0], ldo_f32=D, k_algo=geo.pos_conv_kernel * Cg, stem=self.pos_in_stem)
+                   out_f32=pl["tmp"] if self.post_ln else states[0], ldo_f32=D, k_algo=geo.pos_conv_kernel * Cg, stem=self.pos_in_stem)
+        if self.post_ln:
+            # post-LN encoder: hidden_states[0] = encoder.layer_norm(proj + posconv(proj)) (HF WavLMEncoder), then the layers
+            self._layernorm(pl["tmp"], D, self.enc_ln, M, D, out_f32=states[0], out_act=pl["xa"])
+            self._run_post_ln_layers(pl, states, B, pl["Tmax"], last_state)
+            return
         # a11/a12: stable-LayerNorm encoder layers (LayerNorms deferred into the GEMMs)
         self._run_layers(pl, states, pl["first_groups"], B, pl["Tmax"], last_state)
+
+
+    def _groupnorm_stem(self, pl, packed_wave: torch.Tensor) -> None:
+        """Conv layer 0 of the *-base form: GroupNorm(C, C) over each utterance's frames, then GELU.  ser_gn_stats_v derives the
+        per-(utterance, channel) statistics from the frame moments of the waveform (one read, no pass over the conv output) and the
+        conv-0 GEMM applies them in its epilogue (ser_gemm_args.gn_scale): layer 1's operand planes are its only output."""
+        geo = self.geo
+        B, C0 = pl["B"], geo.conv_dim[0]
+        rec = self._rec
+        a = rec.slot("gn_stats") if rec is not None else _lib.GnStatsArgs()
+        a.wav, a.sample_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["frame_offs0"].data_ptr()
+        a.w, a.bias, a.gamma, a.beta = self.conv0_w.data_ptr(), _ptr(self.conv0_b), self.gn0[0].data_ptr(), self.gn0[1].data_ptr()
+        a.wave_stats = pl["wave_work"].data_ptr()                # what ser_wave_frames normalised the frames with (launched just before)
+        a.scale, a.shift, a.stat_out, a.work = pl["gn_scale"].data_ptr(), pl["gn_shift"].data_ptr(), None, pl["gn_work"].data_ptr()
+        a.B, a.C, a.k, a.stride, a.ld = B, C0, geo.conv_kernel[0], geo.conv_stride[0], C0
+        a.no_norm, a.eps = 0 if self.normalize else 1, 1e-5      # nn.GroupNorm's default eps (HF WavLMGroupNormConvLayer)
+        if rec is not None:
+            rec.inputs["wav_gn"] = a
+            rec.commit(_lib.OP_GN_STATS, a, B=B)
+        else:
+            check(lib.ser_gn_stats_v(C.byref(a), self._s()), "ser_gn_stats")
+        self._gemm(pl["frames"], self.conv0, pl["rows"][0], act=_lib.ACT_GELU, out_act=pl["conv_act"][0], k_algo=geo.conv_kernel[0],
+                   stem=True, gn=(pl["gn_scale"], pl["gn_shift"], pl["frame_offs0"], B))
+
+    def _run_post_ln_layers(self, pl, states, B: int, max_frames: int, last_state: Optional[int] = None):
+        """Post-LN encoder layers (HF WavLMEncoderLayer / Wav2Vec2EncoderLayer), the order of TextEncoder.forward_device:
+        x -> [QKV(+gate) GEMM] -> attention -> [out GEMM + x] -> LN1 -> h -> [FC1 GEMM, GELU] -> [FC2 GEMM + h] -> LN2 -> next x.
+        states[0] and its operand copy come from ser_layernorm (encoder.layer_norm); every LN2 writes states[i+1] and the next copy."""
+        geo = self.geo
+        M, D, L = pl["M"], geo.hidden, geo.num_layers
+        wavlm = geo.family == FAMILY_WAVLM
+        scale = geo.head_dim ** -0.5 * 1.4426950408889634     # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
+        rec = self._rec
+        if rec is not None:
+            rec.marks[0] = rec.n
+        elif last_state == 0:
+            return
+        for i, lay in enumerate(self.layers):
+            x = states[i]
+            last = i + 1 == L
+            self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
+            if wavlm:
+                self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], table=pl["table"], table_T=pl["Tmax"],
+                                gru_const=lay["gate_c"])
+            else:
+                self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"])
+            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=pl["tmp"], ldo_f32=D)
+            self._layernorm(pl["tmp"], D, lay["ln1"], M, D, out_f32=pl["h"], out_act=pl["ha"])
+            self._gemm(pl["ha"], lay["fc1"], M, act=_lib.ACT_GELU, out_act=pl["ffn"])
+            self._gemm(pl["ffn"], lay["fc2"], M, residual=pl["h"], ldr=D, out_f32=pl["tmp"], ldo_f32=D)
+            self._layernorm(pl["tmp"], D, lay["ln2"], M, D, out_f32=states[i + 1], out_act=None if last else pl["xa"])
+            if not last:
+                if rec is not None:
+                    rec.marks[i + 1] = rec.n
+                elif last_state == i + 1:
+                    return
 
 
 class WhisperEncoder(_EncoderBase):
@@ -1575,11 +1707,12 @@ def mean_last4(hs: HiddenStates) -> torch.Tensor:
     return out
 
 
-def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16"):
+def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):
+    """``normalize``: the speech families' input normalisation (``do_normalize`` of the checkpoint's feature extractor)."""
     if geo.family == "deberta":
         return DebertaEncoder(geo, state_dict, device, mode)
     if geo.family == FAMILY_ROBERTA:
         return TextEncoder(geo, state_dict, device, mode)
     if geo.family == FAMILY_WHISPER:
         return WhisperEncoder(geo, state_dict, device, mode)
-    return SpeechEncoder(geo, state_dict, device, mode)
+    return SpeechEncoder(geo, state_dict, device, mode, normalize=normalize)

@@ -129,7 +129,8 @@ def synthetic_state_dict(geo: EncoderGeometry, seed: int = 0, fast: bool = False
         sd[p + ".conv.weight"] = r.normal(c, cin, k, std=math.sqrt(2.0 / (cin * k)))
         if geo.conv_bias:
             sd[p + ".conv.bias"] = r.normal(c, std=0.05)
-        _layer_norm(sd, r, p + ".layer_norm", c)
+        if geo.feat_extract_norm == "layer" or i == 0:     # "group": GroupNorm(C, C) on layer 0 only, same key names and [C] shapes
+            _layer_norm(sd, r, p + ".layer_norm", c)
         cin = c
     if geo.feat_proj_layer_norm:
         _layer_norm(sd, r, "feature_projection.layer_norm", cin)
