@@ -184,8 +184,8 @@ typedef struct ser_gemm_args {
     const uint32_t* w_scale;  int64_t w_scale_ld;
     uint32_t*       out_scale; int64_t out_scale_ld;
     /* fp16 range guard (ABI 13): when not NULL, the launch ORs into *range_flag bit 0 if any value it rounds to an fp16 operand plane
-     * (out_act in the FP16 / FP16X / FP16M formats) exceeds 65504 in magnitude (or is a NaN) BEFORE the saturating conversion, bit 1 if
-     * one exceeds half that -- the host reads the word back with the batch's features and fails that batch's files instead of writing
+     * (out_act in the FP16 / FP16X / FP16M formats) exceeds 65504 in magnitude (or is a NaN or Inf) BEFORE the saturating conversion, bit 1 if
+     * one exceeds half that (bit 0 never comes alone).  Only values the launch stores count, not the tail columns of a tile past N -- the host reads the word back with the batch's features and fails that batch's files instead of writing
      * clipped ones (preprocess_speech.py:46,72-73: a bad file is a printed failure, never silent garbage).  ser_layernorm_v,
      * ser_row_center_v, ser_wave_frames_v, ser_pack_act_v and ser_pack_f16m take the same word. */
     uint32_t*       range_flag;

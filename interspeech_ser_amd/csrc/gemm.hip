@@ -928,11 +928,8 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                     const int c8 = ni * 16 + ((fq & 1) ? 12 : 0);     // after the swap this lane holds columns c8..c8+7
                     store_act8_swap<MODE>((unsigned short*)p.out_act + orow * p.ldo_act + gcol + c8, p.out_plane_stride,
                                           ncol0 + c8 < p.N, v);
-                    if constexpr (mode_traits<MODE>::f16) {           // fp16 range guard (ser_hip.h range_flag)
-                        if (p.range_flag) {
-#pragma unroll
-                            for (int r = 0; r < 8; r += 2) ramax = fmaxf(ramax, fmaxf(fabsf(v[r]), fabsf(v[r + 1])));
-                        }
+                    if constexpr (mode_traits<MODE>::f16) {           // fp16 range guard (ser_hip.h range_flag): stored columns only
+                        if (p.range_flag) range_fold8(ramax, v, ok0, ok1);
                     }
                 }
             }
@@ -1060,7 +1057,8 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                             ax = fmaxf(ax, fmaxf(fabsf(v[r]), fabsf(v[r + 1])));
                             al = fmaxf(al, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
                         }
-                        ramax = fmaxf(ramax, ax);
+                        // range guard: stored columns only (N % 64 == 0: a block is stored whole or not at all, so its scales see no tail)
+                        if (p.range_flag) range_fold8(ramax, v, ok0, ok1);
                         ax = max_rowquad(ax); al = max_rowquad(al);
                         const unsigned cx = mx_code(ax), cl = mx_code(al);
                         const float ix = mx_inv(cx), il = mx_inv(cl);
@@ -1076,11 +1074,8 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                     } else {
                         store_act8_swap<OM>((unsigned short*)p.out_act + orow * p.ldo_act + gcol + c8, p.out_plane_stride,
                                             ncol0 + c8 < p.N, v);
-                        if constexpr (mode_traits<OM>::f16) {             // fp16 range guard (ser_hip.h range_flag)
-                            if (p.range_flag) {
-#pragma unroll
-                                for (int r = 0; r < 8; r += 2) ramax = fmaxf(ramax, fmaxf(fabsf(v[r]), fabsf(v[r + 1])));
-                            }
+                        if constexpr (mode_traits<OM>::f16) {             // fp16 range guard (ser_hip.h range_flag): stored columns only
+                            if (p.range_flag) range_fold8(ramax, v, ok0, ok1);
                         }
                     }
                 }

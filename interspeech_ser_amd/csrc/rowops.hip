@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void wave_frames_kernel(const float* __restric
         store_act4<MODE>(dst + 4, plane, v[4], v[5], v[6], v[7]);
         if constexpr (mode_traits<MODE>::f16) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ramax = fmaxf(ramax, fabsf(v[i]));
+            for (int i = 0; i < 8; ++i) ramax = range_fold(ramax, v[i]);
         }
     }
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             }
             if (of) *(f32x4*)(of + (int64_t)row * ldof + c) = y;
             if (oa) store_act4<MODE>(oa + (int64_t)row * ldoa + c, plane, y[0], y[1], y[2], y[3]);
-            if constexpr (mode_traits<MODE>::f16) { if (oa) ramax = fmaxf(ramax, fmaxf(fmaxf(fabsf(y[0]), fabsf(y[1])), fmaxf(fabsf(y[2]), fabsf(y[3])))); }
+            if constexpr (mode_traits<MODE>::f16) { if (oa) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); } }
         }
     }
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
@@ -385,13 +385,13 @@ __global__ __launch_bounds__(256) void row_center_kernel(const float* __restrict
 #pragma unroll
             for (int j = 0; j < 4; ++j) { d[j] = v[i][j] - mean; q += d[j] * d[j]; r1 += d[j]; }
             if constexpr (MODE != SER_MODE_FP16M) store_act4<MODE>(oa + (int64_t)row * ldoa + c, plane, d[0], d[1], d[2], d[3]);
-            if constexpr (mode_traits<MODE>::f16 && MODE != SER_MODE_FP16M) ramax = fmaxf(ramax, fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fmaxf(fabsf(d[2]), fabsf(d[3]))));
+            if constexpr (mode_traits<MODE>::f16 && MODE != SER_MODE_FP16M) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, d[j]); }
         }
         if constexpr (MODE == SER_MODE_FP16M) {                       // (D % 64 == 0: whole 32-column blocks; every lane joins the block shuffles)
             if (i * 256 < D) {
                 const bool in = c < D;
                 const float d4[4] = {in ? v[i][0] - mean : 0.f, in ? v[i][1] - mean : 0.f, in ? v[i][2] - mean : 0.f, in ? v[i][3] - mean : 0.f};
-                ramax = fmaxf(ramax, mx_store_row<4>(d4, in, oa + (int64_t)row * ldoa, (unsigned char*)(oa + plane + (int64_t)row * ldoa), c,
+                ramax = range_fold(ramax, mx_store_row<4>(d4, in, oa + (int64_t)row * ldoa, (unsigned char*)(oa + plane + (int64_t)row * ldoa), c,
                                                      oscale + row, oscale_ld, false));
             }
         }
@@ -695,7 +695,7 @@ __global__ void pack_act_kernel(const float* __restrict__ x, int B, int C, int T
         for (int j = 0; j < 4; ++j) v[j] = x[((int64_t)b * C + cg * 4 + j) * T + t];
     }
     store_act4<MODE>(o + ((int64_t)b * Tp + tp) * ldo + cg * 4, plane, v[0], v[1], v[2], v[3]);
-    if constexpr (mode_traits<MODE>::f16) range_report(rflag, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+    if constexpr (mode_traits<MODE>::f16) range_report(rflag, range_fold(range_fold(range_fold(fabsf(v[0]), v[1]), v[2]), v[3]));
 }
 
 extern "C" int ser_pack_act_v(const ser_pack_act_args* a, void* stream) {
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(256) void pack_f16m_kernel(const float* __restrict_
             const f32x4 a = *(const f32x4*)(x + (int64_t)row * ldx + c), b = *(const f32x4*)(x + (int64_t)row * ldx + c + 4);
             v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
         }
-        ramax = fmaxf(ramax, mx_store_row<8>(v, c < cols, out + (int64_t)row * ldo, (unsigned char*)(out + plane + (int64_t)row * ldo), c,
+        ramax = range_fold(ramax, mx_store_row<8>(v, c < cols, out + (int64_t)row * ldo, (unsigned char*)(out + plane + (int64_t)row * ldo), c,
                                              scales + row, sld, weight != 0));
     }
     range_report(rflag, ramax);

@@ -340,16 +340,33 @@ __device__ __forceinline__ void transpose_rowquad(unsigned (&r)[4]) {
     const auto b1 = __builtin_amdgcn_permlane16_swap(a0[1], a1[1], false, false);
     r[0] = b0[0]; r[1] = b0[1]; r[2] = b1[0]; r[3] = b1[1];
 }
+// |v| folded into a lane's running maximum for the fp16 range guard (range_report).  NaN-propagating (llvm.maximum: one v_maximum3_f32
+// with |.| source modifiers, the cost of the v_max_f32 it replaces): fmaxf returns the operand that is not a NaN, so a NaN rounded to an
+// fp16 plane never reached the guard.
+__device__ __forceinline__ float range_fold(float amax, float v) {
+    return __builtin_elementwise_maximum(amax, fabsf(v));
+}
+// The GEMM epilogues' fold: v[0..3] / v[4..7] = the lane's 4 columns of fragment blocks ni / ni+1 (before the store's lane swap), ok0 / ok1 =
+// whether those columns are < N.  Tail columns are products with the clamped last W row and are never stored: they must not set the flag.
+__device__ __forceinline__ void range_fold8(float& amax, const float (&v)[8], bool ok0, bool ok1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (ok0) amax = range_fold(amax, v[r]);
+        if (ok1) amax = range_fold(amax, v[r + 4]);
+    }
+}
 // Row kernels: VPL (4 or 8) consecutive values of one row per lane, 32 / VPL consecutive lanes per scale block, 64 / VPL per 64-column tile.
 //   hi_row: the row in plane 0; x8_row: the same row in plane 1 (as bytes); col: the lane's first column (multiple of VPL);
 //   srow: scale words of this row (tile t at srow[t * sld]); weight: plane roles (ser_hip.h); every lane of the wave must call (shuffles) --
-//   `ok` gates the stores of lanes past the end of the row.  Returns max |value| of the lane (for the fp16 range guard).
+//   `ok` gates the stores of lanes past the end of the row.  Returns max |value| of the lane, NaN if it holds one (range_fold: the fp16
+//   range guard); callers pass 0 for the values of lanes whose `ok` is false.  The block scales (ax / al) keep fmaxf: a NaN only has to
+//   stay fault-free there, the batch fails on the guard.
 template <int VPL>
 __device__ __forceinline__ float mx_store_row(const float (&v)[VPL], bool ok, unsigned short* hi_row, unsigned char* x8_row, int col,
                                               uint32_t* srow, int64_t sld, bool weight) {
     static_assert(VPL == 4 || VPL == 8, "4 or 8 values per lane");
     constexpr int LPB = 32 / VPL;
-    float lo[VPL], ax = 0.f, al = 0.f;
+    float lo[VPL], ax = 0.f, al = 0.f, ramax = 0.f;
     unsigned hp[VPL / 2];
 #pragma unroll
     for (int i = 0; i < VPL; i += 2) {
@@ -358,8 +375,8 @@ __device__ __forceinline__ float mx_store_row(const float (&v)[VPL], bool ok, un
         lo[i + 1] = v[i + 1] - h2f((unsigned short)(hp[i / 2] >> 16));
         ax = fmaxf(ax, fmaxf(fabsf(v[i]), fabsf(v[i + 1])));
         al = fmaxf(al, fmaxf(fabsf(lo[i]), fabsf(lo[i + 1])));
+        ramax = range_fold(range_fold(ramax, v[i]), v[i + 1]);
     }
-    const float amax_lane = ax;
 #pragma unroll
     for (int o = 1; o < LPB; o <<= 1) { ax = fmaxf(ax, __shfl_xor(ax, o, 64)); al = fmaxf(al, __shfl_xor(al, o, 64)); }
     const unsigned cx = mx_code(ax), cl = mx_code(al);
@@ -387,10 +404,10 @@ __device__ __forceinline__ float mx_store_row(const float (&v)[VPL], bool ok, un
         }
         if ((col & 63) == 0) srow[(int64_t)(col >> 6) * sld] = cp | (cp1 << 8) | (cq << 16) | (cq1 << 24);
     }
-    return amax_lane;
+    return ramax;
 }
-// fp16 range guard (ser_hip.h range_flag): bit 0 = a value beyond +-65504 (or a NaN) was rounded to an fp16 operand plane (it saturated),
-// bit 1 = a value beyond half that range was.  One rare atomic per lane that saw such a value; nothing otherwise.
+// fp16 range guard (ser_hip.h range_flag): bit 0 = a value beyond +-65504 (an Inf, or a NaN: amax from range_fold) was rounded to an fp16
+// operand plane (it saturated), bit 1 = a value beyond half that range was.  One rare atomic per lane that saw such a value; nothing otherwise.
 __device__ __forceinline__ void range_report(uint32_t* flag, float amax) {
     if (flag && !(amax <= 0.5f * SER_F16_MAX)) atomicOr(flag, !(amax <= SER_F16_MAX) ? 3u : 2u);
 }

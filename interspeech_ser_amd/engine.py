@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import GemmArgs, check, lib
+from .weights import check_f16_weight
 from .config import EncoderGeometry, FAMILY_ROBERTA, FAMILY_WAVLM, FAMILY_WHISPER
 
 MODES = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X, "f16": _lib.MODE_FP16, "f16q": _lib.MODE_FP16, "f16a": _lib.MODE_FP16,
@@ -330,13 +331,19 @@ class _EncoderBase:
         8.6 GB XLS-R-2B) beside the 16-bit planes for the life of the run, and its start is only 4-byte aligned."""
         return t.detach().to(device=self.device, dtype=torch.float32, copy=True).contiguous()
 
-    def _linear(self, w: torch.Tensor, b: Optional[torch.Tensor], stem: bool = False, mode: Optional[int] = None) -> Linear:
-        """fp32 [N, K] -> 16-bit operand planes on the device (ser_split_bf16): bf16 hi (+ lo), or fp16 (hi + lo for FP16X)."""
+    def _linear(self, w: torch.Tensor, b: Optional[torch.Tensor], stem: bool = False, mode: Optional[int] = None,
+                name: str = "a weight") -> Linear:
+        """fp32 [N, K] -> 16-bit operand planes on the device (ser_split_bf16): bf16 hi (+ lo), or fp16 (hi + lo for FP16X).
+        fp16 planes refuse a weight they cannot hold (weights.check_f16_weight, ValueError naming ``name``)."""
         w = w.detach().to(torch.float32).contiguous()
         N, K = w.shape
-        src = w.to(self.device)
         if mode is None:
             mode = self.stem_mode if stem else self.mode
+        if mode in (_lib.MODE_FP16, _lib.MODE_FP16X, _lib.MODE_FP16M):
+            # on the host, on the exact fp32 tensor split below; ser_pack_f16m's range_flag would see the same values, so its weight
+            # launch passes none
+            check_f16_weight(w, name)
+        src = w.to(self.device)
         out = torch.empty((_PLANES[mode], N, K), dtype=_DTYPE[mode], device=self.device)
         if mode == _lib.MODE_FP16M:
             if K % 64:
@@ -350,12 +357,12 @@ class _EncoderBase:
         return Linear(out, None if b is None else self._dev_f32(b), N, K)
 
     def _linear_ln(self, w: torch.Tensor, b: Optional[torch.Tensor], ln_w: torch.Tensor, ln_b: torch.Tensor,
-                   mode: Optional[int] = None) -> Linear:
+                   mode: Optional[int] = None, name: str = "a weight") -> Linear:
         """Linear that consumes LayerNorm(x) given the RAW x (deferred LayerNorm, ser_hip.h):
         store W' = W * gamma, colsum(W') of exactly the bf16 planes the MFMAs will read, and
         t = beta W^T + b.  Load-time transform, like the weight-norm fold."""
         w64, g64, be64 = w.detach().double(), ln_w.detach().double(), ln_b.detach().double()
-        lin = self._linear((w64 * g64[None, :]).float(), None, mode=mode)
+        lin = self._linear((w64 * g64[None, :]).float(), None, mode=mode, name=f"{name} (folded with its LayerNorm weight)")
         t = w64 @ be64
         if b is not None:
             t = t + b.detach().double()
@@ -674,7 +681,7 @@ class _EncoderBase:
                                     sd[ln1 + ".weight"], sd[ln1 + ".bias"], H, dh)
             # operand planes [planes][H][2][dh] in the format the attention launch multiplies in (one MFMA chain per query block)
             gmode = self.qk_mode if self.qk_mode is not None else self.attn_mode
-            glin = self._linear(wg.float(), None, mode=gmode)
+            glin = self._linear(wg.float(), None, mode=gmode, name=a + ".gru_rel_pos_linear.weight (folded gate)")
             cs = glin.w.double().sum(dim=(0, 2)).view(H, 2)                             # column sums of exactly the planes the MFMAs read
             lay["gate_w"] = glin.w
             lay["gate_cb"] = self._dev_f32(torch.cat([cs.to(t.device), t], 1).float())
@@ -693,15 +700,17 @@ class _EncoderBase:
             bs.append(torch.cat([torch.stack([b8[:4].sum(), b8[4:].sum()]).repeat(H), torch.zeros(pad, device=wdev)]))
             lay["gate_c"] = self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
         if self.qk_mode is None:
-            lay["qkv"] = self._linear_ln(torch.cat(ws, 0), torch.cat(bs, 0), sd[ln1 + ".weight"], sd[ln1 + ".bias"], mode=lm["qkv_mode"])
+            lay["qkv"] = self._linear_ln(torch.cat(ws, 0), torch.cat(bs, 0), sd[ln1 + ".weight"], sd[ln1 + ".bias"], mode=lm["qkv_mode"],
+                                         name=a + ".{q,k,v}_proj.weight")
         else:
             # logit path [q | k | gate] on fp16 hi + lo planes (3 products), [v] on one fp16 plane
             lay["qk"] = self._linear_ln(torch.cat(ws[:2] + ws[3:], 0), torch.cat(bs[:2] + bs[3:], 0), sd[ln1 + ".weight"],
-                                        sd[ln1 + ".bias"], mode=self.qk_mode)
-            lay["v"] = self._linear_ln(ws[2], bs[2], sd[ln1 + ".weight"], sd[ln1 + ".bias"])
-        lay["out"] = self._linear(sd[a + ".out_proj.weight"], sd[a + ".out_proj.bias"], mode=_lib.MODE_FP16M if lm["out_m"] else self.attn_mode)
-        lay["fc1"] = self._linear_ln(sd[fc1 + ".weight"], sd[fc1 + ".bias"], sd[ln2 + ".weight"], sd[ln2 + ".bias"])
-        lay["fc2"] = self._linear(sd[fc2 + ".weight"], sd[fc2 + ".bias"])
+                                        sd[ln1 + ".bias"], mode=self.qk_mode, name=a + ".{q,k}_proj.weight")
+            lay["v"] = self._linear_ln(ws[2], bs[2], sd[ln1 + ".weight"], sd[ln1 + ".bias"], name=a + ".v_proj.weight")
+        lay["out"] = self._linear(sd[a + ".out_proj.weight"], sd[a + ".out_proj.bias"], mode=_lib.MODE_FP16M if lm["out_m"] else self.attn_mode,
+                                  name=a + ".out_proj.weight")
+        lay["fc1"] = self._linear_ln(sd[fc1 + ".weight"], sd[fc1 + ".bias"], sd[ln2 + ".weight"], sd[ln2 + ".bias"], name=fc1 + ".weight")
+        lay["fc2"] = self._linear(sd[fc2 + ".weight"], sd[fc2 + ".bias"], name=fc2 + ".weight")
         # load-time part of the operand shift: a uniform offset in a bias moves the row mean by exactly its mean
         lay["out_bias_mean"] = float(sd[a + ".out_proj.bias"].double().mean())
         lay["fc2_bias_mean"] = float(sd[fc2 + ".bias"].double().mean())
@@ -831,7 +840,7 @@ class SpeechEncoder(_EncoderBase):
             raise NotImplementedError("conv layer 0 kernel wider than 64 taps")
         w0 = torch.zeros((C0, 64), dtype=torch.float32)
         w0[:, : geo.conv_kernel[0]] = sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]).float()
-        self.conv0 = self._linear(w0, sd[p0 + ".conv.bias"] if geo.conv_bias else None, stem=True)
+        self.conv0 = self._linear(w0, sd[p0 + ".conv.bias"] if geo.conv_bias else None, stem=True, name=p0 + ".conv.weight")
         if self.post_ln:        # GroupNorm(C, C) of conv layer 0 (its affine); layers 1..6 have no norm
             self.gn0 = self._ln_pair(sd, p0 + ".layer_norm")
             self.conv_ln = [None] * len(geo.conv_dim)
@@ -842,9 +851,10 @@ class SpeechEncoder(_EncoderBase):
             p = f"feature_extractor.conv_layers.{i}.conv"
             w = sd[p + ".weight"].float()                                  # [Cout, Cin, k]
             w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)                # K index = tap*Cin + c
-            self.convs.append(self._linear(w2, sd[p + ".bias"] if geo.conv_bias else None, stem=True))
+            self.convs.append(self._linear(w2, sd[p + ".bias"] if geo.conv_bias else None, stem=True, name=p + ".weight"))
         self.proj_ln = self._ln_pair(sd, "feature_projection.layer_norm")
-        self.proj = self._linear(sd["feature_projection.projection.weight"], sd["feature_projection.projection.bias"], stem=True)
+        self.proj = self._linear(sd["feature_projection.projection.weight"], sd["feature_projection.projection.bias"], stem=True,
+                                 name="feature_projection.projection.weight")
         # positional conv: per group [Cg out][tap][Cg in padded to a multiple of 64]
         G, k = geo.pos_conv_groups, geo.pos_conv_kernel
         Cg = D // G
@@ -859,7 +869,8 @@ class SpeechEncoder(_EncoderBase):
         # "f16q" / "f16a" keep it on the stem format always: an error in hidden_states[0] enters layer 0's logits, and these modes
         # exist for attention maps sharp enough to amplify it (LoRA stress fixture: 1.4e-3 -> see DESIGN.md section 4)
         self.pos_in_stem = (self.mode_name == "f16" and Cg * k > 128 * 80) or self.mode_name in ("f16q", "f16a", "f16m", "f16mf")
-        self.pos = self._linear(wp.reshape(G * Cg, k * self.pos_kc), sd["encoder.pos_conv_embed.conv.bias"], stem=self.pos_in_stem)
+        self.pos = self._linear(wp.reshape(G * Cg, k * self.pos_kc), sd["encoder.pos_conv_embed.conv.bias"], stem=self.pos_in_stem,
+                                name="encoder.pos_conv_embed.conv.weight (weight-norm folded)")
         self.enc_ln = self._ln_pair(sd, "encoder.layer_norm")
         self.layers = []
         for i in range(geo.num_layers):
@@ -894,11 +905,13 @@ class SpeechEncoder(_EncoderBase):
             ws.append(wg)
             bs.append(torch.cat([torch.stack([b8[:4].sum(), b8[4:].sum()]).repeat(H), torch.zeros(pad, device=w8.device)]))
             lay["gate_c"] = self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
-        lay["qkv"] = self._linear(torch.cat(ws, 0), torch.cat(bs, 0))
-        lay["out"] = self._linear(sd[a + ".out_proj.weight"], sd[a + ".out_proj.bias"])
+        lay["qkv"] = self._linear(torch.cat(ws, 0), torch.cat(bs, 0), name=a + ".{q,k,v}_proj.weight")
+        lay["out"] = self._linear(sd[a + ".out_proj.weight"], sd[a + ".out_proj.bias"], name=a + ".out_proj.weight")
         lay["ln1"] = self._ln_pair(sd, p + ".layer_norm")
-        lay["fc1"] = self._linear(sd[p + ".feed_forward.intermediate_dense.weight"], sd[p + ".feed_forward.intermediate_dense.bias"])
-        lay["fc2"] = self._linear(sd[p + ".feed_forward.output_dense.weight"], sd[p + ".feed_forward.output_dense.bias"])
+        lay["fc1"] = self._linear(sd[p + ".feed_forward.intermediate_dense.weight"], sd[p + ".feed_forward.intermediate_dense.bias"],
+                                  name=p + ".feed_forward.intermediate_dense.weight")
+        lay["fc2"] = self._linear(sd[p + ".feed_forward.output_dense.weight"], sd[p + ".feed_forward.output_dense.bias"],
+                                  name=p + ".feed_forward.output_dense.weight")
         lay["ln2"] = self._ln_pair(sd, p + ".final_layer_norm")
         return lay
 
@@ -1256,8 +1269,8 @@ class WhisperEncoder(_EncoderBase):
         self.mel = self._dev_f32(torch.from_numpy(whisper_mel_filters(geo.n_mels) if mel_filters is None else mel_filters))
         w1 = sd["encoder.conv1.weight"].float()
         w2 = sd["encoder.conv2.weight"].float()
-        self.conv1 = self._linear(w1.permute(0, 2, 1).reshape(D, -1), sd["encoder.conv1.bias"], stem=True)
-        self.conv2 = self._linear(w2.permute(0, 2, 1).reshape(D, -1), sd["encoder.conv2.bias"], stem=True)
+        self.conv1 = self._linear(w1.permute(0, 2, 1).reshape(D, -1), sd["encoder.conv1.bias"], stem=True, name="encoder.conv1.weight")
+        self.conv2 = self._linear(w2.permute(0, 2, 1).reshape(D, -1), sd["encoder.conv2.bias"], stem=True, name="encoder.conv2.weight")
         self.pos_emb = self._dev_f32(sd["encoder.embed_positions.weight"])
         self.enc_ln = self._ln_pair(sd, "encoder.layer_norm")
         self.layers = []

@@ -302,6 +302,25 @@ def fold_wavlm_gate(w8: torch.Tensor, b8: torch.Tensor, gamma: torch.Tensor, bet
     return wg, t
 
 
+F16_MAX = 65504.0
+
+
+def check_f16_weight(w: torch.Tensor, name: str) -> None:
+    """Refuse, at load, a weight that fp16 operand planes cannot hold (the FP16 / FP16X / FP16M formats of the "f16*" modes).  The kernels
+    saturate at +-65504 on the way in and the activations' range guard (ser_hip.h range_flag) never sees the weights, so a weight beyond
+    that range, or a NaN / Inf, would be wrong in every output without a failure line.  ``w`` is the fp32 tensor actually split, e.g.
+    after a LayerNorm gamma fold; ``name`` says which checkpoint tensor it came from."""
+    w = w.detach()
+    finite = torch.isfinite(w)
+    if not bool(finite.all()):
+        raise ValueError(f"{name}: {int((~finite).sum())} non-finite value(s); fp16 operand planes cannot hold them -- "
+                         "use --mode fp32x to inspect the checkpoint")
+    amax = float(w.abs().max()) if w.numel() else 0.0
+    if amax > F16_MAX:
+        raise ValueError(f"{name}: |value| up to {amax:.6g} exceeds the fp16 operand range ({F16_MAX:g}) and would saturate -- "
+                         "use --mode fp32x (bf16 planes, fp32 range)")
+
+
 def state_dict_digest(sd: StateDict) -> str:
     """Order-independent checksum of a state dict (fixtures record it so a drift of
     the RNG stream between containers is detected instead of silently compared)."""

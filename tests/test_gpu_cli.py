@@ -464,6 +464,70 @@ def test_fp16_range_guard_sees_the_feed_forward_intermediate(tmp_path, capsys):
         C._REGISTRY.pop("tiny-range-test")
 
 
+def test_fp16_range_guard_fails_the_files_on_a_nan(tmp_path, capsys):
+    """A NaN reaching an fp16 operand plane is a failed batch, like a value beyond the range: one NaN in an FC2 bias (the bias stays fp32,
+    no load-time check sees it) makes every hidden state after that layer NaN.  The kernels' range fold used fmaxf, which drops a NaN, so
+    these files were written full of NaN with no failure line.  In every fp16-plane mode all files of the batch fail with the --mode fp32x
+    hint and nothing is written."""
+    from safetensors.torch import save_file
+    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd import driver
+    from interspeech_ser_amd.weights import synthetic_state_dict
+    geo = C.TINY_WAVLM
+    sd = synthetic_state_dict(geo, 47)
+    sd["encoder.layers.0.feed_forward.output_dense.bias"][11] = float("nan")
+    ck = tmp_path / "nan.safetensors"
+    save_file({k: v.contiguous() for k, v in sd.items()}, str(ck))
+    wav_dir = tmp_path / "wav"
+    wav_dir.mkdir()
+    for i, n in enumerate((16000, 9000, 12000)):
+        write_wav(wav_dir / f"u{i}.wav", synth(90 + i, n))
+    C._REGISTRY["tiny-range-test"] = geo
+    try:
+        for mode in ("f16mf", "f16x", "f16m"):
+            out = tmp_path / f"pt_{mode}"
+            assert driver.run_speech(["--ssl_type", "tiny-range-test", "--wav_dir", str(wav_dir), "--save_path", str(out), "--checkpoint", str(ck),
+                                      "--use_n_layer", "--n_layer", "-1", "--mode", mode]) == 0
+            log = capsys.readouterr().out
+            assert log.count("Failed to process") == 3 and "fp16 operand range" in log and "--mode fp32x" in log, (mode, log)
+            assert os.listdir(out) == []
+    finally:
+        C._REGISTRY.pop("tiny-range-test")
+
+
+def test_weight_beyond_the_fp16_range_is_refused_at_load(tmp_path, capsys):
+    """Weight planes have no device-side guard: a weight beyond 65504 would saturate silently in every fp16-plane mode.  The encoder refuses
+    it at load with a ValueError naming the tensor and --mode fp32x, where the same checkpoint loads and extracts."""
+    from safetensors.torch import save_file
+    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd import driver
+    from interspeech_ser_amd.weights import synthetic_state_dict
+    geo = C.TINY_WAVLM
+    sd = synthetic_state_dict(geo, 48)
+    name = "encoder.layers.1.feed_forward.output_dense.weight"
+    sd[name][3, 5] = 7.0e4
+    ck = tmp_path / "big_w.safetensors"
+    save_file({k: v.contiguous() for k, v in sd.items()}, str(ck))
+    wav_dir = tmp_path / "wav"
+    wav_dir.mkdir()
+    write_wav(wav_dir / "u0.wav", synth(95, 16000))
+    C._REGISTRY["tiny-range-test"] = geo
+    try:
+        for mode in ("f16mf", "f16x"):
+            with pytest.raises(ValueError) as e:
+                driver.run_speech(["--ssl_type", "tiny-range-test", "--wav_dir", str(wav_dir), "--save_path", str(tmp_path / f"pt_{mode}"),
+                                   "--checkpoint", str(ck), "--use_n_layer", "--n_layer", "-1", "--mode", mode])
+            assert name in str(e.value) and "--mode fp32x" in str(e.value)
+            capsys.readouterr()
+        out = tmp_path / "pt_fp32x"
+        assert driver.run_speech(["--ssl_type", "tiny-range-test", "--wav_dir", str(wav_dir), "--save_path", str(out), "--checkpoint", str(ck),
+                                  "--use_n_layer", "--n_layer", "-1", "--mode", "fp32x"]) == 0
+        log = capsys.readouterr().out
+        assert "Failed to process" not in log and os.listdir(out) == ["u0.pt"], log
+    finally:
+        C._REGISTRY.pop("tiny-range-test")
+
+
 def test_whisper_lora_checkpoint_through_the_driver(tmp_path, capsys):
     """preprocessing/preprocess_whisper_pretrained.py:115-190: a PEFT-wrapped Whisper (``whisper.base_model.model.*``, adapters on
     q_proj / v_proj of encoder AND decoder, a classifier head) saved with torch.save as a ``.pt`` state dict, extracted with the
