@@ -128,7 +128,7 @@ def find_weights(ssl_type: str, checkpoint: str, synthetic: bool, seed: int, geo
 # ------------------------------------------------------------------------ the loop
 class _Extractor:
     def __init__(self, args, whisper: bool, device: str):
-        from .engine import build_encoder
+        from .engine import POST_LN_MODES, build_encoder
         self.args, self.whisper = args, whisper
         self.geo = C.resolve_geometry(args.ssl_type, args.checkpoint)      # config.json of the checkpoint, else the built-in table
         if whisper != (self.geo.family == C.FAMILY_WHISPER):
@@ -151,7 +151,7 @@ class _Extractor:
             # reference's four) runs the 3-product split everywhere instead -- same or better parity, ~10 % slower
             print(f"--mode {args.mode} needs hidden / feed-forward widths that are multiples of 64 (here {self.geo.hidden} / {self.geo.ffn}): using f16x")
             args.mode = "f16x"
-        if not whisper and not self.geo.stable_layer_norm and args.mode not in ("bf16", "fp32x", "f16x"):
+        if not whisper and not self.geo.stable_layer_norm and args.mode not in POST_LN_MODES:
             # the post-LayerNorm (*-base) encoders run the text encoders' modes; the others need FP16M copies out of ser_layernorm
             print(f"--mode {args.mode} is not implemented for post-LayerNorm encoders ({args.ssl_type}): using f16x")
             args.mode = "f16x"
@@ -547,6 +547,7 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
 # ------------------------------------------------------------------ text extractor (8f-1)
 def build_text_parser() -> argparse.ArgumentParser:
     """Flags of the reference's preprocessing/preprocess_roberta.py:12-21, unchanged, + additive ones."""
+    from .engine import POST_LN_MODES
     p = argparse.ArgumentParser()
     p.add_argument("--seed", type=int, default=7)
     p.add_argument("--roberta_type", type=str, default="roberta")
@@ -556,7 +557,7 @@ def build_text_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_len", type=int, default=80, help="tokens per text (at most 512, the models' position range)")
     p.add_argument("--use_average", type=str, default="n")
     p.add_argument("--batch_size", type=int, default=64)
-    p.add_argument("--mode", type=str, default="f16x", choices=["f16x", "fp32x", "bf16"],
+    p.add_argument("--mode", type=str, default="f16x", choices=list(POST_LN_MODES),
                    help="numerics: f16x (default: the speech drivers' 3-product split on fp16 hi + lo planes; 5e-6 of the fp32 reference on Gaussian "
                         "weights, 2-5e-5 under sharp attention at 24 layers; values must stay below 65 504 -- checked per batch), fp32x (the same split on "
                         "bf16 planes: fp32 range, 2e-5 / 2-3e-4), bf16 (1e-2)")

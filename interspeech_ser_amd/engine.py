@@ -55,6 +55,9 @@ MODES = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X, "f16": _lib.MODE_FP16
 # the feed-forward pair (62 % of the layer FLOPs) on single fp16 products.  oracle/numerics_whatif.py: under sharp attention the
 # error comes from the attention block as a whole -- rounding v, P, the context rows or the output-projection weights once is
 # amplified by the following layers' softmax as much as rounding q and k -- while the feed-forward rounding is benign.
+# The modes of the post-LayerNorm encoders (RoBERTa, DeBERTa, the *-base speech encoders; f16x first: the text drivers' default).  The
+# others would need an FP16M operand copy out of ser_layernorm, which runs between their GEMMs.
+POST_LN_MODES = ("f16x", "fp32x", "bf16")
 _PLANES = {_lib.MODE_BF16: 1, _lib.MODE_FP32X: 2, _lib.MODE_FP16: 1, _lib.MODE_FP16X: 2, _lib.MODE_FP16M: 2}
 _DTYPE = {_lib.MODE_BF16: torch.bfloat16, _lib.MODE_FP32X: torch.bfloat16, _lib.MODE_FP16: torch.float16,
           _lib.MODE_FP16X: torch.float16, _lib.MODE_FP16M: torch.float16}
@@ -195,11 +198,13 @@ class HiddenStates:
     ``states`` is one fp32 tensor [L+1, rows, D]; utterance b owns rows
     frame_offs[b]:frame_offs[b+1] (crop to the true frame count is implicit)."""
 
-    def __init__(self, states: torch.Tensor, frame_offs: Sequence[int], computed: Optional[int] = None):
+    def __init__(self, states: torch.Tensor, frame_offs: Sequence[int], computed: Optional[int] = None,
+                 range_flag: Optional[torch.Tensor] = None):
         self.states = states
         self.frame_offs = list(int(x) for x in frame_offs)
         # states[0 .. computed-1] hold this batch's results; a forward stopped early (``last_state``) leaves the rest stale
         self.computed = states.shape[0] if computed is None else int(computed)
+        self.range_flag = range_flag
 
     def __len__(self) -> int:
         return self.states.shape[0]
@@ -221,7 +226,6 @@ class HiddenStates:
     # f16a, f16q, f16 modes) ORs into the slot's device word -- bit 0: a value beyond +-65504 (it saturated), bit 1: beyond half of that.
     # ``range_flag`` is that word (int32 [1] on the device, None in the bf16-plane modes); the caller reads it back with the features
     # and clears it (``take_range_bits``).  Round 4 reduced max|hidden state| with a torch pass on sampled batches only.
-    range_flag: Optional[torch.Tensor] = None
 
     def take_range_bits(self, pinned_out: Optional[torch.Tensor] = None):
         """Enqueue (current stream) the read-back of the guard word into ``pinned_out`` (int32 [1], page-locked) and its reset; with no
@@ -240,9 +244,12 @@ class HiddenStates:
 
 
 class _EncoderBase:
-    def __init__(self, geo: EncoderGeometry, device, mode: str):
+    def __init__(self, geo: EncoderGeometry, device, mode: str, post_ln: bool = False):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {list(MODES)}")
+        if post_ln and mode not in POST_LN_MODES:
+            raise ValueError(f"the post-LayerNorm encoders support the {', '.join(POST_LN_MODES)} numerics modes")
+        self.post_ln = post_ln
         if not torch.cuda.is_available():
             raise _lib.SerHipError("no HIP device visible: the extraction path has no CPU fallback")
         self.geo = geo
@@ -537,10 +544,29 @@ class _EncoderBase:
     def _gate_in(pl, lay):
         return (pl["xa"], pl["gst"], lay["gate_w"], lay["gate_cb"]) if "gate_w" in lay else None
 
+    def _gate_width(self) -> int:
+        """the WavLM gate's two pre-activations per head as packed-projection columns, padded to a multiple of 8 (GEMM N)"""
+        return ((2 * self.geo.heads + 7) // 8) * 8
+
     def _gate_pad(self) -> int:
-        """extra columns of the packed projection: the WavLM gate's two pre-activations per head, padded to a multiple of 8"""
-        in_cols = any(not self._lay_modes(i)["gate_in_attn"] for i in range(self.geo.num_layers))   # some layer keeps the gate in the projection
-        return ((2 * self.geo.heads + 7) // 8) * 8 if (self.geo.family == FAMILY_WAVLM and in_cols) else 0
+        """extra columns of the stable-LN packed projection: the gate's, when some layer keeps the gate in the projection"""
+        in_cols = any(not self._lay_modes(i)["gate_in_attn"] for i in range(self.geo.num_layers))
+        return self._gate_width() if (self.geo.family == FAMILY_WAVLM and in_cols) else 0
+
+    def _gate_cols(self, sd, a: str):
+        """WavLM's gate as extra rows of a packed projection (HF modeling_wavlm.py:167-180): its two pre-activations per head are the sums
+        of gru_rel_pos_linear's first and last four outputs over the head's dh input channels.  Returns (weight rows [_gate_width(), D],
+        their bias, gru_rel_pos_const on the device); the padding rows are zero."""
+        D, H, dh = self.geo.hidden, self.geo.heads, self.geo.head_dim
+        w8, b8 = sd[a + ".gru_rel_pos_linear.weight"].float(), sd[a + ".gru_rel_pos_linear.bias"].float()
+        wa, wb = w8[:4].sum(0), w8[4:].sum(0)
+        wg = torch.zeros(self._gate_width(), D, device=w8.device)
+        for h in range(H):
+            wg[2 * h, h * dh:(h + 1) * dh] = wa
+            wg[2 * h + 1, h * dh:(h + 1) * dh] = wb
+        bg = torch.zeros(self._gate_width(), device=w8.device)
+        bg[:2 * H] = torch.stack([b8[:4].sum(), b8[4:].sum()]).repeat(H)
+        return wg, bg, self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
 
     def _qkv_cols(self):
         """(q, k, v, gate) first columns inside the packed projection output"""
@@ -566,6 +592,33 @@ class _EncoderBase:
                    col_scale_end=D, ln_mean=ln_mean, mode=self.qk_mode, lnstat_out=lnstat)
         self._gemm(pl["xa"], lay["v"], M, ln_stats=stats, ln_groups=gx, out_act=pl["qkv"], out_col=self._qkv_cols()[2])
 
+    def _attention_block(self, pl, lay, first: bool, gx: int, B: int, max_frames: int, residual: torch.Tensor, out_f32: torch.Tensor,
+                         shifted: bool = True) -> None:
+        """One stable-LN layer's attention block: packed QKV(+gate) projection -> attention -> output projection (+ ``residual`` ->
+        ``out_f32``, operand copy ``ha``).  ``gx``: partial-sum groups of the layer input's producer; ``shifted``: the shifted operand
+        copies (see _run_layers)."""
+        M, D = pl["M"], self.geo.hidden
+        gD = self._stat_groups(D)
+        self._qkv_gemm(pl, lay, M, first, gx, (pl["sx"], pl["mx"]) if shifted else None)
+        if self.geo.family == FAMILY_WAVLM:
+            self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], table=pl["table"],
+                            table_T=pl["Tmax"], gru_const=lay["gate_c"], gate_in=self._gate_in(pl, lay), out_m=lay["out_m"])
+        else:
+            self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], out_m=lay["out_m"])
+        self._gemm(pl["ctx"], lay["out"], M, residual=residual, ldr=D, out_f32=out_f32, ldo_f32=D,
+                   out_act=pl["ha"], stat_out=pl["ph"], stat_groups=gD, mode=_lib.MODE_FP16M if lay["out_m"] else self.attn_mode, out_mode=self.mode,
+                   shift=(pl["mx"], pl["sh"], lay["out_bias_mean"]) if shifted else None)
+
+    def _post_ln_tail(self, pl, lay, x: torch.Tensor, out_f32: torch.Tensor, out_act: Optional[Act]) -> None:
+        """The rest of a post-LN layer once attention has written ``ctx``: [out GEMM + x] -> LN1 -> h (copy ha) -> [FC1 GEMM, GELU]
+        -> [FC2 GEMM + h] -> LN2 -> ``out_f32`` and its operand copy ``out_act`` (None: no copy)."""
+        M, D = pl["M"], self.geo.hidden
+        self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=pl["tmp"], ldo_f32=D)
+        self._layernorm(pl["tmp"], D, lay["ln1"], M, D, out_f32=pl["h"], out_act=pl["ha"])
+        self._gemm(pl["ha"], lay["fc1"], M, act=_lib.ACT_GELU, out_act=pl["ffn"])
+        self._gemm(pl["ffn"], lay["fc2"], M, residual=pl["h"], ldr=D, out_f32=pl["tmp"], ldo_f32=D)
+        self._layernorm(pl["tmp"], D, lay["ln2"], M, D, out_f32=out_f32, out_act=out_act)
+
     @staticmethod
     def _stat_groups(n_cols: int, groups: int = 1) -> int:
         """64-column partial-sum slots a GEMM output of `groups` x `n_cols` columns produces (made even)."""
@@ -582,7 +635,6 @@ class _EncoderBase:
         the one-pass variance.  states[0] is centred once by ser_row_center."""
         geo = self.geo
         M, D, L = pl["M"], geo.hidden, geo.num_layers
-        wavlm = geo.family == FAMILY_WAVLM
         gD = self._stat_groups(D)
         gx = first_groups
         # ``last_state`` = N: the caller reads hidden_states[N] only (the reference's speech script keeps one state,
@@ -602,15 +654,7 @@ class _EncoderBase:
             if self.block_trace is not None:
                 b0 = torch.cuda.Event(enable_timing=True)
                 b0.record()
-            self._qkv_gemm(pl, lay, M, i == 0, gx, (pl["sx"], pl["mx"]) if shifted else None)
-            if wavlm:
-                self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], table=pl["table"],
-                                table_T=pl["Tmax"], gru_const=lay["gate_c"], gate_in=self._gate_in(pl, lay), out_m=lay["out_m"])
-            else:
-                self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], out_m=lay["out_m"])
-            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=pl["h"], ldo_f32=D,
-                       out_act=pl["ha"], stat_out=pl["ph"], stat_groups=gD, mode=_lib.MODE_FP16M if lay["out_m"] else self.attn_mode, out_mode=self.mode,
-                       shift=(pl["mx"], pl["sh"], lay["out_bias_mean"]) if shifted else None)
+            self._attention_block(pl, lay, i == 0, gx, B, max_frames, x, pl["h"], shifted)
             if self.block_trace is not None:
                 b1 = torch.cuda.Event(enable_timing=True)
                 b1.record()
@@ -631,6 +675,28 @@ class _EncoderBase:
                     return
         self._layernorm(pl["last"], D, self.enc_ln, M, D, out_f32=states[L])
 
+    def _launch_or_replay(self, owner: dict, pl, packed_wave: torch.Tensor, last_state: Optional[int]) -> HiddenStates:
+        """One forward of ``self._launches``: launched one by one (``use_tape`` off, or a trace on), else the command list kept in
+        ``owner["tape"]`` (SpeechEncoder: the slot's arena; Whisper: the plan) replayed with this batch's sizes and waveform -- the
+        first forward over ``owner`` records it, launching nothing."""
+        flag = self._guard_word(pl)
+        if not self.use_tape or self.gemm_trace is not None or self.block_trace is not None:
+            self._launches(pl, packed_wave, last_state)      # eager: one Python -> C transition per kernel
+        else:
+            tape = owner.get("tape")
+            if tape is None:
+                self._rec = tape = Tape()
+                try:
+                    self._launches(pl, packed_wave)
+                finally:
+                    self._rec = None
+                owner["tape"] = tape
+            for key in ("wav", "wav_gn"):                   # the launches that read the waveform
+                if key in tape.inputs:
+                    tape.inputs[key].wav = packed_wave.data_ptr()
+            tape.run(pl.get("sizes", {}), self._s(), last_state)
+        return HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1, range_flag=flag)
+
     def recorded_tape(self, lengths: Sequence[int], slot: int) -> Tape:
         """the command list the slot's last forward over ``lengths`` replayed (SpeechEncoder: per arena; Whisper: per plan)"""
         pl = self._plan(lengths, slot)
@@ -646,21 +712,10 @@ class _EncoderBase:
         same kernels, stale but finite data), on the current stream.  Returns the number of layer calls."""
         pl = self._plan(lengths, slot)
         self._guard_word(pl)
-        geo = self.geo
-        M, D, B = pl["M"], geo.hidden, len(lengths)
-        max_frames = pl.get("Tmax", geo.max_source_positions)
-        wavlm = geo.family == FAMILY_WAVLM
-        gD = self._stat_groups(D)
+        max_frames = pl.get("Tmax", self.geo.max_source_positions)
+        gD = self._stat_groups(self.geo.hidden)
         for i, lay in enumerate(self.layers):
-            self._qkv_gemm(pl, lay, M, i == 0, pl["first_groups"] if i == 0 else gD, (pl["sx"], pl["mx"]))
-            if wavlm:
-                self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], table=pl["table"], table_T=pl["Tmax"],
-                                gru_const=lay["gate_c"], gate_in=self._gate_in(pl, lay), out_m=lay["out_m"])
-            else:
-                self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"], out_m=lay["out_m"])
-            self._gemm(pl["ctx"], lay["out"], M, residual=pl["h"], ldr=D, out_f32=pl["h"], ldo_f32=D, out_act=pl["ha"],
-                       stat_out=pl["ph"], stat_groups=gD, shift=(pl["mx"], pl["sh"], lay["out_bias_mean"]),
-                       mode=_lib.MODE_FP16M if lay["out_m"] else self.attn_mode, out_mode=self.mode)
+            self._attention_block(pl, lay, i == 0, pl["first_groups"] if i == 0 else gD, len(lengths), max_frames, pl["h"], pl["h"])
         return len(self.layers)
 
     def _layer_weights(self, sd, p: str, a: str, ln1: str, ln2: str, fc1: str, fc2: str, k_bias: bool, gate: bool, index: int = 0):
@@ -688,17 +743,10 @@ class _EncoderBase:
             lay["gate_c"] = self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
             gate = False                                                                # no gate columns in the packed projection
         if gate:
-            # (SER_GATE_IN_ATTN=0) the two pre-activations per head as 2H extra output columns of the packed projection
-            w8, b8 = sd[a + ".gru_rel_pos_linear.weight"].float(), sd[a + ".gru_rel_pos_linear.bias"].float()
-            wa, wb = w8[:4].sum(0), w8[4:].sum(0)
-            wg = torch.zeros(2 * H, D, device=wdev)
-            for h in range(H):
-                wg[2 * h, h * dh:(h + 1) * dh] = wa
-                wg[2 * h + 1, h * dh:(h + 1) * dh] = wb
-            pad = (-2 * H) % 8                                   # GEMM N must stay a multiple of 8
-            ws.append(torch.cat([wg, torch.zeros(pad, D, device=wdev)], 0))
-            bs.append(torch.cat([torch.stack([b8[:4].sum(), b8[4:].sum()]).repeat(H), torch.zeros(pad, device=wdev)]))
-            lay["gate_c"] = self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
+            # (SER_GATE_IN_ATTN=0, FP16M projections) the two pre-activations per head as extra output columns of the packed projection
+            wg, bg, lay["gate_c"] = self._gate_cols(sd, a)
+            ws.append(wg)
+            bs.append(bg)
         if self.qk_mode is None:
             lay["qkv"] = self._linear_ln(torch.cat(ws, 0), torch.cat(bs, 0), sd[ln1 + ".weight"], sd[ln1 + ".bias"], mode=lm["qkv_mode"],
                                          name=a + ".{q,k,v}_proj.weight")
@@ -715,6 +763,40 @@ class _EncoderBase:
         lay["out_bias_mean"] = float(sd[a + ".out_proj.bias"].double().mean())
         lay["fc2_bias_mean"] = float(sd[fc2 + ".bias"].double().mean())
         return lay
+
+    def _post_ln_layer_weights(self, sd, q: str, k: str, v: str, out: str, ln1: str, fc1: str, fc2: str, ln2: str, gate=None) -> dict:
+        """One post-LN layer (HF BERT / RoBERTa / DeBERTa, WavLMEncoderLayer / Wav2Vec2EncoderLayer) from the checkpoint key prefixes of
+        its tensors: plain GEMM operands, the two LayerNorms run as ser_layernorm between them (the norm of a 768-wide row spans several
+        GEMM tiles).  ``gate``: _gate_cols' WavLM gate, extra columns of the packed projection -- its pre-activations are linear in the
+        attention's input, which here is the layer input itself."""
+        def linear(p: str) -> Linear:
+            return self._linear(sd[p + ".weight"], sd[p + ".bias"], name=p + ".weight")
+
+        ws, bs = [sd[p + ".weight"] for p in (q, k, v)], [sd[p + ".bias"] for p in (q, k, v)]
+        lay = {}
+        if gate is not None:
+            ws.append(gate[0])
+            bs.append(gate[1])
+            lay["gate_c"] = gate[2]
+        lay["qkv"] = self._linear(torch.cat(ws, 0), torch.cat(bs, 0), name=" + ".join(p + ".weight" for p in (q, k, v)))
+        lay["out"] = linear(out)
+        lay["ln1"] = self._ln_pair(sd, ln1)
+        lay["fc1"] = linear(fc1)
+        lay["fc2"] = linear(fc2)
+        lay["ln2"] = self._ln_pair(sd, ln2)
+        return lay
+
+    def _post_ln_buffers(self, pl, M: int, nqkv: int) -> None:
+        """Activation set of M rows of post-LN layers (_post_ln_tail), packed projection ``nqkv`` columns wide: operand copies of the
+        layer input (xa), of LN1's output (ha), of the context rows, of the projection and of FC1's output; LN1's / LN2's fp32 input
+        (tmp) and LN1's output (h)."""
+        D, dev = self.geo.hidden, self.device
+        pl["xa"], pl["ha"], pl["ctx"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
+        pl["qkv"], pl["ffn"] = self._new_act(M, nqkv), self._new_act(M, self.geo.ffn)
+        pl["tmp"] = torch.empty((M, D), dtype=torch.float32, device=dev)
+        pl["h"] = torch.empty((M, D), dtype=torch.float32, device=dev)
+        if self.fp16_planes:
+            pl["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)   # the slot's fp16 range-guard word (HiddenStates.range_flag)
 
     def _layer_buffers(self, pl, M: int, first_groups: int):
         geo, dev = self.geo, self.device
@@ -813,16 +895,11 @@ class SpeechEncoder(_EncoderBase):
     the *-base form (GroupNorm-over-time conv layer 0, post-LayerNorm encoder; ``geo.stable_layer_norm`` False).  ``normalize``: the
     feature extractor's ``do_normalize`` (zero-mean / unit-variance input per utterance)."""
 
-    POST_LN_MODES = ("bf16", "fp32x", "f16x")
-
     def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "bf16", normalize: bool = True):
-        if not geo.stable_layer_norm and mode not in self.POST_LN_MODES:
-            raise ValueError(f"the post-LayerNorm (*-base) encoders support the {', '.join(self.POST_LN_MODES)} numerics modes")
-        super().__init__(geo, device, mode)
+        super().__init__(geo, device, mode, post_ln=not geo.stable_layer_norm)
         if geo.family == FAMILY_WHISPER:
             raise ValueError("use WhisperEncoder for the whisper family")
         self.normalize = bool(normalize)
-        self.post_ln = not geo.stable_layer_norm
         if self.post_ln != (geo.feat_extract_norm == "group"):
             raise NotImplementedError("GroupNorm stems come with post-LN encoders and layer-norm stems with stable-LN ones")
         if not geo.feat_proj_layer_norm:
@@ -876,7 +953,11 @@ class SpeechEncoder(_EncoderBase):
         for i in range(geo.num_layers):
             p = f"encoder.layers.{i}"
             if self.post_ln:
-                self.layers.append(self._post_ln_layer_weights(sd, p))
+                a = p + ".attention"
+                self.layers.append(self._post_ln_layer_weights(
+                    sd, a + ".q_proj", a + ".k_proj", a + ".v_proj", a + ".out_proj", p + ".layer_norm",
+                    p + ".feed_forward.intermediate_dense", p + ".feed_forward.output_dense", p + ".final_layer_norm",
+                    gate=self._gate_cols(sd, a) if geo.family == FAMILY_WAVLM else None))
                 continue
             self.layers.append(self._layer_weights(
                 sd, p, p + ".attention", p + ".layer_norm", p + ".final_layer_norm",
@@ -884,36 +965,6 @@ class SpeechEncoder(_EncoderBase):
                 k_bias=True, gate=(geo.family == FAMILY_WAVLM), index=i))
         if geo.family == FAMILY_WAVLM:
             self.rel_embed = self._dev_f32(sd["encoder.layers.0.attention.rel_attn_embed.weight"])
-
-    def _post_ln_layer_weights(self, sd, p: str):
-        """One post-LN layer (HF WavLMEncoderLayer / Wav2Vec2EncoderLayer): plain GEMM operands, the two LayerNorms run as
-        ser_layernorm between them (the norm of a 768-wide row spans several GEMM tiles).  WavLM's gate pre-activations ride as 2H
-        extra columns of the packed projection: they are linear in the attention's input, which here is the layer input itself."""
-        D, H, dh = self.geo.hidden, self.geo.heads, self.geo.head_dim
-        a = p + ".attention"
-        ws = [sd[a + ".q_proj.weight"], sd[a + ".k_proj.weight"], sd[a + ".v_proj.weight"]]
-        bs = [sd[a + ".q_proj.bias"], sd[a + ".k_proj.bias"], sd[a + ".v_proj.bias"]]
-        lay = {}
-        if self.geo.family == FAMILY_WAVLM:
-            w8, b8 = sd[a + ".gru_rel_pos_linear.weight"].float(), sd[a + ".gru_rel_pos_linear.bias"].float()
-            wa, wb = w8[:4].sum(0), w8[4:].sum(0)
-            pad = (-2 * H) % 8                                   # GEMM N must stay a multiple of 8
-            wg = torch.zeros(2 * H + pad, D, device=w8.device)
-            for h in range(H):
-                wg[2 * h, h * dh:(h + 1) * dh] = wa
-                wg[2 * h + 1, h * dh:(h + 1) * dh] = wb
-            ws.append(wg)
-            bs.append(torch.cat([torch.stack([b8[:4].sum(), b8[4:].sum()]).repeat(H), torch.zeros(pad, device=w8.device)]))
-            lay["gate_c"] = self._dev_f32(sd[a + ".gru_rel_pos_const"].reshape(-1))
-        lay["qkv"] = self._linear(torch.cat(ws, 0), torch.cat(bs, 0), name=a + ".{q,k,v}_proj.weight")
-        lay["out"] = self._linear(sd[a + ".out_proj.weight"], sd[a + ".out_proj.bias"], name=a + ".out_proj.weight")
-        lay["ln1"] = self._ln_pair(sd, p + ".layer_norm")
-        lay["fc1"] = self._linear(sd[p + ".feed_forward.intermediate_dense.weight"], sd[p + ".feed_forward.intermediate_dense.bias"],
-                                  name=p + ".feed_forward.intermediate_dense.weight")
-        lay["fc2"] = self._linear(sd[p + ".feed_forward.output_dense.weight"], sd[p + ".feed_forward.output_dense.bias"],
-                                  name=p + ".feed_forward.output_dense.weight")
-        lay["ln2"] = self._ln_pair(sd, p + ".final_layer_norm")
-        return lay
 
     # ------------------------------------------------------------------ batch plan
     # ------------------------------------------------------------------ per-slot arenas + plans
@@ -944,7 +995,11 @@ class SpeechEncoder(_EncoderBase):
         ar["states"] = torch.empty((geo.num_layers + 1, cap["M"], D), dtype=torch.float32, device=dev)
         ar["first_groups"] = 2                               # ser_row_center writes one (sum, sum^2) slot + one zero slot
         if self.post_ln:
-            self._post_ln_buffers(ar, cap)
+            # the GroupNorm stem's per-(utterance, channel) affine + its workspace
+            ar["gn_scale"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
+            ar["gn_shift"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
+            ar["gn_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_GN_STATS, cap["B"], 0, 0, 0, self.stem_mode), dtype=torch.uint8, device=dev)
+            self._post_ln_buffers(ar, cap["M"], 3 * D + (self._gate_width() if geo.family == FAMILY_WAVLM else 0))
         else:
             self._layer_buffers(ar, cap["M"], ar["first_groups"])
         if geo.family == FAMILY_WAVLM:
@@ -960,21 +1015,6 @@ class SpeechEncoder(_EncoderBase):
         ar["plan"] = None                                   # (lengths, plan) currently laid out in this arena
         arenas[slot] = ar
         return ar
-
-    def _post_ln_buffers(self, ar, cap):
-        """Arena buffers of the *-base form: the GroupNorm stem's per-(utterance, channel) affine + its workspace, and the post-LN layers'."""
-        geo, dev = self.geo, self.device
-        M, D, C0, B = cap["M"], geo.hidden, geo.conv_dim[0], cap["B"]
-        ar["gn_scale"] = torch.empty((B, C0), dtype=torch.float32, device=dev)
-        ar["gn_shift"] = torch.empty((B, C0), dtype=torch.float32, device=dev)
-        ar["gn_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_GN_STATS, B, 0, 0, 0, self.stem_mode), dtype=torch.uint8, device=dev)
-        if self.fp16_planes:
-            ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        nqkv = 3 * D + (((2 * geo.heads + 7) // 8) * 8 if geo.family == FAMILY_WAVLM else 0)
-        ar["xa"], ar["ha"], ar["ctx"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
-        ar["qkv"], ar["ffn"] = self._new_act(M, nqkv), self._new_act(M, geo.ffn)
-        ar["tmp"] = torch.empty((M, D), dtype=torch.float32, device=dev)
-        ar["h"] = torch.empty((M, D), dtype=torch.float32, device=dev)
 
     def _plan(self, lengths: Sequence[int], slot: int = 0):
         """Row bookkeeping of one ragged batch in slot ``slot``'s arena.  Only O(B) integers are computed on the
@@ -1114,27 +1154,7 @@ class SpeechEncoder(_EncoderBase):
         """packed raw samples [sum(lengths)] fp32 on the device -> L+1 hidden states (``last_state`` = N: only states 0..N,
         the launches that feed later states are skipped)."""
         pl = self._plan(lengths, slot)
-        last_state = self._check_last_state(last_state)
-        flag = self._guard_word(pl)
-        if not self.use_tape or self.gemm_trace is not None or self.block_trace is not None:
-            self._launches(pl, packed_wave, last_state)      # eager: one Python -> C transition per kernel
-        else:
-            ar = self._arenas[slot]
-            tape = ar.get("tape")
-            if tape is None:                                 # first forward in this arena: record, launch nothing
-                self._rec = tape = Tape()
-                try:
-                    self._launches(pl, packed_wave)
-                finally:
-                    self._rec = None
-                ar["tape"] = tape
-            for key in ("wav", "wav_gn"):                   # the launches that read the waveform
-                if key in tape.inputs:
-                    tape.inputs[key].wav = packed_wave.data_ptr()
-            tape.run(pl["sizes"], self._s(), last_state)
-        hs = HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1)
-        hs.range_flag = flag
-        return hs
+        return self._launch_or_replay(self._arenas[slot], pl, packed_wave, self._check_last_state(last_state))
 
     def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
         geo = self.geo
@@ -1220,9 +1240,9 @@ class SpeechEncoder(_EncoderBase):
                    stem=True, gn=(pl["gn_scale"], pl["gn_shift"], pl["frame_offs0"], B))
 
     def _run_post_ln_layers(self, pl, states, B: int, max_frames: int, last_state: Optional[int] = None):
-        """Post-LN encoder layers (HF WavLMEncoderLayer / Wav2Vec2EncoderLayer), the order of TextEncoder.forward_device:
-        x -> [QKV(+gate) GEMM] -> attention -> [out GEMM + x] -> LN1 -> h -> [FC1 GEMM, GELU] -> [FC2 GEMM + h] -> LN2 -> next x.
-        states[0] and its operand copy come from ser_layernorm (encoder.layer_norm); every LN2 writes states[i+1] and the next copy."""
+        """Post-LN encoder layers (HF WavLMEncoderLayer / Wav2Vec2EncoderLayer): x -> [QKV(+gate) GEMM] -> attention -> _post_ln_tail.
+        states[0] and its operand copy come from ser_layernorm (encoder.layer_norm); every LN2 but the last writes states[i+1] and the
+        next copy, the last one states[L] only."""
         geo = self.geo
         M, D, L = pl["M"], geo.hidden, geo.num_layers
         wavlm = geo.family == FAMILY_WAVLM
@@ -1233,7 +1253,6 @@ class SpeechEncoder(_EncoderBase):
         elif last_state == 0:
             return
         for i, lay in enumerate(self.layers):
-            x = states[i]
             last = i + 1 == L
             self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
             if wavlm:
@@ -1241,11 +1260,7 @@ class SpeechEncoder(_EncoderBase):
                                 gru_const=lay["gate_c"])
             else:
                 self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"])
-            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=pl["tmp"], ldo_f32=D)
-            self._layernorm(pl["tmp"], D, lay["ln1"], M, D, out_f32=pl["h"], out_act=pl["ha"])
-            self._gemm(pl["ha"], lay["fc1"], M, act=_lib.ACT_GELU, out_act=pl["ffn"])
-            self._gemm(pl["ffn"], lay["fc2"], M, residual=pl["h"], ldr=D, out_f32=pl["tmp"], ldo_f32=D)
-            self._layernorm(pl["tmp"], D, lay["ln2"], M, D, out_f32=states[i + 1], out_act=None if last else pl["xa"])
+            self._post_ln_tail(pl, lay, states[i], states[i + 1], None if last else pl["xa"])
             if not last:
                 if rec is not None:
                     rec.marks[i + 1] = rec.n
@@ -1368,26 +1383,11 @@ class WhisperEncoder(_EncoderBase):
         per plan and replayed with one ser_run call; only the waveform pointer changes from batch to batch.
         ``last_state`` = N stops after hidden state N (``--n_layer N``, preprocess_whisper.py:71)."""
         pl = self._plan(lengths, slot)
-        last_state = self._check_last_state(last_state)
-        flag = self._guard_word(pl)
-        if not self.use_tape or self.gemm_trace is not None or self.block_trace is not None:
-            self._logmel(pl, packed_wave)
-            self._encoder_launches(pl, pl["mel"], last_state)
-        else:
-            tape = pl.get("tape")
-            if tape is None:
-                self._rec = tape = Tape()
-                try:
-                    self._logmel(pl, packed_wave)
-                    self._encoder_launches(pl, pl["mel"])
-                finally:
-                    self._rec = None
-                pl["tape"] = tape
-            tape.inputs["wav"].wav = packed_wave.data_ptr()
-            tape.run({}, self._s(), last_state)
-        hs = HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1)
-        hs.range_flag = flag
-        return hs
+        return self._launch_or_replay(pl, pl, packed_wave, self._check_last_state(last_state))
+
+    def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
+        self._logmel(pl, packed_wave)
+        self._encoder_launches(pl, pl["mel"], last_state)
 
     @_on_stream
     def forward_features(self, input_features: torch.Tensor, lengths: Sequence[int], slot: int = 0) -> HiddenStates:
@@ -1399,9 +1399,7 @@ class WhisperEncoder(_EncoderBase):
                              f"got {tuple(input_features.shape)}")
         flag = self._guard_word(pl)
         self._encoder_launches(pl, input_features)
-        hs = HiddenStates(pl["states"], pl["frame_offs_host"])
-        hs.range_flag = flag
-        return hs
+        return HiddenStates(pl["states"], pl["frame_offs_host"], range_flag=flag)
 
     def _encoder_launches(self, pl, input_features: torch.Tensor, last_state: Optional[int] = None) -> None:
         geo = self.geo
@@ -1426,7 +1424,49 @@ class WhisperEncoder(_EncoderBase):
         self._run_layers(pl, states, pl["first_groups"], B, T2, last_state)
 
 
-class TextEncoder(_EncoderBase):
+class _TextEncoderBase(_EncoderBase):
+    """What the RoBERTa and DeBERTa encoders share: post-LN layers, ``forward``'s input checks and the plans, one per (slot, B, T)."""
+
+    def __init__(self, geo: EncoderGeometry, device, mode: str):
+        super().__init__(geo, device, mode, post_ln=True)
+
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, slot: int = 0) -> HiddenStates:
+        """``model(input_ids, attention_mask, output_hidden_states=True).hidden_states`` (preprocess_roberta.py /
+        preprocess_deroberta.py:57,68)."""
+        B, T = input_ids.shape
+        if attention_mask.shape != input_ids.shape:
+            raise ValueError("attention_mask must have the shape of input_ids")
+        if int(input_ids.min()) < 0 or int(input_ids.max()) >= self.geo.vocab_size:
+            raise ValueError("token id outside the vocabulary")
+        mask = attention_mask.to(torch.int64).cpu()
+        klen = mask.sum(dim=1)
+        if not torch.equal(mask, (torch.arange(T)[None, :] < klen[:, None]).to(torch.int64)) or int(klen.min()) < 1:
+            raise ValueError("attention_mask must be right-padded with at least one valid token per sequence")
+        ids = input_ids.to(device=self.device, dtype=torch.int32).contiguous()
+        return self.forward_device(ids, klen.to(device=self.device, dtype=torch.int32), slot)
+
+    def _plan(self, B: int, T: int, slot: int = 0):
+        key = (slot, B, T)
+        if key in self._cache:
+            return self._cache[key]
+        geo, dev = self.geo, self.device
+        M = B * T
+        pl = dict(B=B, T=T, M=M)
+        pl["frame_offs_host"] = [b * T for b in range(B + 1)]
+        pl["frame_offs"] = torch.tensor(pl["frame_offs_host"], dtype=torch.int32, device=dev)
+        pl["states"] = torch.empty((geo.num_layers + 1, M, geo.hidden), dtype=torch.float32, device=dev)
+        self._post_ln_buffers(pl, M, 3 * geo.hidden)
+        self._own_buffers(pl)
+        if len(self._cache) >= 4:
+            self._cache.pop(next(iter(self._cache)))
+        self._cache[key] = pl
+        return pl
+
+    def _own_buffers(self, pl) -> None:
+        """buffers of a plan beyond the shared set"""
+
+
+class TextEncoder(_TextEncoderBase):
     """RoBERTa text encoder (next row 8f-1: preprocessing/preprocess_roberta.py) on the same kernels:
     embeddings + L post-LayerNorm BERT layers.  ``forward(input_ids [B,T], attention_mask [B,T])`` returns
     L+1 states per sequence, ALL T rows each (the reference saves the padded positions too); padded KEYS
@@ -1436,10 +1476,7 @@ class TextEncoder(_EncoderBase):
         super().__init__(geo, device, mode)
         if geo.family != FAMILY_ROBERTA:
             raise ValueError("TextEncoder needs a roberta geometry")
-        if mode in ("f16", "f16q", "f16a", "f16m", "f16mf"):
-            raise ValueError("the text encoders support the bf16, fp32x and f16x numerics modes")
         sd = state_dict
-        D = geo.hidden
         self.wemb = self._dev_f32(sd["embeddings.word_embeddings.weight"])
         self.pemb = self._dev_f32(sd["embeddings.position_embeddings.weight"])
         self.temb = self._dev_f32(sd["embeddings.token_type_embeddings.weight"][0])
@@ -1448,53 +1485,17 @@ class TextEncoder(_EncoderBase):
         for i in range(geo.num_layers):
             p = f"encoder.layer.{i}"
             a = p + ".attention.self"
-            qkv_w = torch.cat([sd[a + ".query.weight"], sd[a + ".key.weight"], sd[a + ".value.weight"]], 0)
-            qkv_b = torch.cat([sd[a + ".query.bias"], sd[a + ".key.bias"], sd[a + ".value.bias"]], 0)
-            self.layers.append(dict(
-                qkv=self._linear(qkv_w, qkv_b),
-                out=self._linear(sd[p + ".attention.output.dense.weight"], sd[p + ".attention.output.dense.bias"]),
-                ln1=self._ln_pair(sd, p + ".attention.output.LayerNorm"),
-                fc1=self._linear(sd[p + ".intermediate.dense.weight"], sd[p + ".intermediate.dense.bias"]),
-                fc2=self._linear(sd[p + ".output.dense.weight"], sd[p + ".output.dense.bias"]),
-                ln2=self._ln_pair(sd, p + ".output.LayerNorm")))
-
-    def _plan(self, B: int, T: int, slot: int = 0):
-        key = (slot, B, T)
-        if key in self._cache:
-            return self._cache[key]
-        geo, dev = self.geo, self.device
-        D, Fd, M = geo.hidden, geo.ffn, B * T
-        pl = dict(B=B, T=T, M=M)
-        pl["frame_offs_host"] = [b * T for b in range(B + 1)]
-        pl["frame_offs"] = torch.tensor(pl["frame_offs_host"], dtype=torch.int32, device=dev)
-        pl["states"] = torch.empty((geo.num_layers + 1, M, D), dtype=torch.float32, device=dev)
-        pl["xa"], pl["ha"] = self._new_act(M, D), self._new_act(M, D)
-        pl["qkv"], pl["ctx"], pl["ffn"] = self._new_act(M, 3 * D), self._new_act(M, D), self._new_act(M, Fd)
-        pl["tmp"] = torch.empty((M, D), dtype=torch.float32, device=dev)
-        pl["h"] = torch.empty((M, D), dtype=torch.float32, device=dev)
-        if len(self._cache) >= 4:
-            self._cache.pop(next(iter(self._cache)))
-        self._cache[key] = pl
-        return pl
+            self.layers.append(self._post_ln_layer_weights(
+                sd, a + ".query", a + ".key", a + ".value", p + ".attention.output.dense", p + ".attention.output.LayerNorm",
+                p + ".intermediate.dense", p + ".output.dense", p + ".output.LayerNorm"))
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, slot: int = 0) -> HiddenStates:
         """``model(input_ids, attention_mask, output_hidden_states=True).hidden_states`` (preprocess_roberta.py:57,68)."""
-        geo = self.geo
-        B, T = input_ids.shape
-        if attention_mask.shape != input_ids.shape:
-            raise ValueError("attention_mask must have the shape of input_ids")
+        T, geo = input_ids.shape[-1], self.geo
         if T + geo.pad_token_id + 1 > geo.max_positions:
             # position ids run up to T + padding_idx (HF modeling_roberta.py:142): the table must hold them
             raise ValueError(f"{T} tokens need {T + geo.pad_token_id + 1} position embeddings, the model has {geo.max_positions}")
-        if int(input_ids.min()) < 0 or int(input_ids.max()) >= geo.vocab_size:
-            raise ValueError("token id outside the vocabulary")
-        mask = attention_mask.to(torch.int64).cpu()
-        klen = mask.sum(dim=1)
-        if not torch.equal(mask, (torch.arange(T)[None, :] < klen[:, None]).to(torch.int64)) or int(klen.min()) < 1:
-            raise ValueError("attention_mask must be right-padded with at least one valid token per sequence")
-        ids = input_ids.to(device=self.device, dtype=torch.int32).contiguous()
-        key_lens = klen.to(device=self.device, dtype=torch.int32)
-        return self.forward_device(ids, key_lens, slot)
+        return super().forward(input_ids, attention_mask, slot)
 
     @_on_stream
     def forward_device(self, ids: torch.Tensor, key_lens: torch.Tensor, slot: int = 0) -> HiddenStates:
@@ -1513,17 +1514,10 @@ class TextEncoder(_EncoderBase):
                                _stream()), "ser_embed_ln")
         scale = geo.head_dim ** -0.5 * 1.4426950408889634
         for i, lay in enumerate(self.layers):
-            x = states[i]
             self._gemm(xa, lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
             self._attention(pl["qkv"], pl["frame_offs"], B, T, pl["ctx"], key_lens=key_lens)
-            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=pl["tmp"], ldo_f32=D)
-            self._layernorm(pl["tmp"], D, lay["ln1"], M, D, out_f32=pl["h"], out_act=pl["ha"])
-            self._gemm(pl["ha"], lay["fc1"], M, act=_lib.ACT_GELU, out_act=pl["ffn"])
-            self._gemm(pl["ffn"], lay["fc2"], M, residual=pl["h"], ldr=D, out_f32=pl["tmp"], ldo_f32=D)
-            self._layernorm(pl["tmp"], D, lay["ln2"], M, D, out_f32=states[i + 1], out_act=xa)
-        hs = HiddenStates(states, pl["frame_offs_host"])
-        hs.range_flag = flag
-        return hs
+            self._post_ln_tail(pl, lay, states[i], states[i + 1], xa)
+        return HiddenStates(states, pl["frame_offs_host"], range_flag=flag)
 
 
 def _deberta_log_bucket(rel: torch.Tensor, bucket_size: int, max_position: int) -> torch.Tensor:
@@ -1538,7 +1532,7 @@ def _deberta_log_bucket(rel: torch.Tensor, bucket_size: int, max_position: int) 
     return torch.where(a <= mid, rel.to(torch.float32), logp * sign).to(torch.long)
 
 
-class DebertaEncoder(_EncoderBase):
+class DebertaEncoder(_TextEncoderBase):
     """DeBERTa-v2/v3 text encoder (preprocessing/preprocess_deroberta.py builds it with AutoModel) in its v3
     configuration: LayerNorm-ed word embeddings (no absolute positions / token types), L post-LayerNorm blocks with
     disentangled attention.  The relative-position side is input independent, so it is folded at load: LayerNorm of the
@@ -1551,8 +1545,6 @@ class DebertaEncoder(_EncoderBase):
         super().__init__(geo, device, mode)
         if geo.family != "deberta":
             raise ValueError("DebertaEncoder needs a deberta geometry")
-        if mode in ("f16", "f16q", "f16a", "f16m", "f16mf"):
-            raise ValueError("the text encoders support the bf16, fp32x and f16x numerics modes")
         if geo.head_dim != 64:
             raise ValueError("DeBERTa path: head dim must be 64 (K of the position GEMMs; deberta-v3 base/large have 64)")
         sd = state_dict
@@ -1568,23 +1560,18 @@ class DebertaEncoder(_EncoderBase):
             a = p + ".attention.self"
             wq, wk = sd[a + ".query_proj.weight"].double(), sd[a + ".key_proj.weight"].double()
             bq, bk = sd[a + ".query_proj.bias"].double(), sd[a + ".key_proj.bias"].double()
-            qkv_w = torch.cat([sd[a + ".query_proj.weight"], sd[a + ".key_proj.weight"], sd[a + ".value_proj.weight"]], 0)
-            qkv_b = torch.cat([sd[a + ".query_proj.bias"], sd[a + ".key_proj.bias"], sd[a + ".value_proj.bias"]], 0)
-            self.layers.append(dict(
-                qkv=self._linear(qkv_w, qkv_b),
-                pos_q=(rel @ wq.T + bq).float(), pos_k=(rel @ wk.T + bk).float(),       # [2 span, D] fp32, host: windows cut per T
-                out=self._linear(sd[p + ".attention.output.dense.weight"], sd[p + ".attention.output.dense.bias"]),
-                ln1=self._ln_pair(sd, p + ".attention.output.LayerNorm"),
-                fc1=self._linear(sd[p + ".intermediate.dense.weight"], sd[p + ".intermediate.dense.bias"]),
-                fc2=self._linear(sd[p + ".output.dense.weight"], sd[p + ".output.dense.bias"]),
-                ln2=self._ln_pair(sd, p + ".output.LayerNorm")))
+            lay = self._post_ln_layer_weights(
+                sd, a + ".query_proj", a + ".key_proj", a + ".value_proj", p + ".attention.output.dense", p + ".attention.output.LayerNorm",
+                p + ".intermediate.dense", p + ".output.dense", p + ".output.LayerNorm")
+            lay["pos_q"], lay["pos_k"] = (rel @ wq.T + bq).float(), (rel @ wk.T + bk).float()     # [2 span, D] fp32, host: windows cut per T
+            self.layers.append(lay)
         # deberta-v2 xlarge / xxlarge: ConvLayer after layer 0 (HF modeling_deberta_v2.py ConvLayer) as an implicit-conv GEMM
         self.text_conv = None
         if geo.text_conv_kernel:
             if geo.text_conv_kernel != 3:
                 raise ValueError("DeBERTa ConvLayer: kernel size 3 (deberta-v2-xlarge / xxlarge) is what is built")
             wc = sd["encoder.conv.conv.weight"].float()                                    # [out, in, tap]
-            self.text_conv = dict(lin=self._linear(wc.permute(0, 2, 1).reshape(D, 3 * D), sd["encoder.conv.conv.bias"]),
+            self.text_conv = dict(lin=self._linear(wc.permute(0, 2, 1).reshape(D, 3 * D), sd["encoder.conv.conv.bias"], name="encoder.conv.conv.weight"),
                                   ln=self._ln_pair(sd, "encoder.conv.LayerNorm"))
         self._windows: Dict[int, dict] = {}
 
@@ -1614,46 +1601,17 @@ class DebertaEncoder(_EncoderBase):
         self._windows[T] = w
         return w
 
-    def _plan(self, B: int, T: int, slot: int = 0):
-        key = (slot, B, T)
-        if key in self._cache:
-            return self._cache[key]
+    def _own_buffers(self, pl) -> None:
         geo, dev = self.geo, self.device
-        D, Fd, M = geo.hidden, geo.ffn, B * T
-        win = self._window(T)
-        pl = dict(B=B, T=T, M=M, win=win)
-        pl["frame_offs_host"] = [b * T for b in range(B + 1)]
-        pl["states"] = torch.empty((geo.num_layers + 1, M, D), dtype=torch.float32, device=dev)
-        pl["xa"], pl["ha"] = self._new_act(M, D), self._new_act(M, D)
-        pl["qkv"], pl["ctx"], pl["ffn"] = self._new_act(M, 3 * D), self._new_act(M, D), self._new_act(M, Fd)
+        B, T, M, D = pl["B"], pl["T"], pl["M"], geo.hidden
+        win = pl["win"] = self._window(T)
         pl["posterms"] = torch.empty((M, 2 * geo.heads * win["Nr"]), dtype=torch.float32, device=dev)   # [c2p of every head | p2c of every head]
-        pl["frame_offs"] = torch.tensor(pl["frame_offs_host"], dtype=torch.int32, device=dev)
         pl["bias2d"] = torch.zeros((B, geo.heads, T, (T + 63) // 64 * 64), dtype=torch.float32, device=dev)   # dense c2p + p2c bias
         if self.text_conv is not None:
             pl["conv_in"] = self._new_act(B * (T + 2), D, zero=True)                       # [0][tokens of sequence b][0] per sequence
             b_idx = np.repeat(np.arange(B, dtype=np.int64), T)
             t_idx = np.tile(np.arange(T, dtype=np.int64), B)
             pl["conv_rowoff"] = torch.tensor((b_idx * (T + 2) + t_idx) * D // 8, dtype=torch.int32, device=dev)   # tap 0 = token t-1
-        pl["tmp"] = torch.empty((M, D), dtype=torch.float32, device=dev)
-        pl["h"] = torch.empty((M, D), dtype=torch.float32, device=dev)
-        if len(self._cache) >= 4:
-            self._cache.pop(next(iter(self._cache)))
-        self._cache[key] = pl
-        return pl
-
-    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, slot: int = 0) -> HiddenStates:
-        """``model(input_ids, attention_mask, output_hidden_states=True).hidden_states`` (preprocess_deroberta.py:57,68)."""
-        B, T = input_ids.shape
-        if attention_mask.shape != input_ids.shape:
-            raise ValueError("attention_mask must have the shape of input_ids")
-        if int(input_ids.min()) < 0 or int(input_ids.max()) >= self.geo.vocab_size:
-            raise ValueError("token id outside the vocabulary")
-        mask = attention_mask.to(torch.int64).cpu()
-        klen = mask.sum(dim=1)
-        if not torch.equal(mask, (torch.arange(T)[None, :] < klen[:, None]).to(torch.int64)) or int(klen.min()) < 1:
-            raise ValueError("attention_mask must be right-padded with at least one valid token per sequence")
-        ids = input_ids.to(device=self.device, dtype=torch.int32).contiguous()
-        return self.forward_device(ids, klen.to(device=self.device, dtype=torch.int32), slot)
 
     @_on_stream
     def forward_device(self, ids: torch.Tensor, key_lens: torch.Tensor, slot: int = 0) -> HiddenStates:
@@ -1675,7 +1633,6 @@ class DebertaEncoder(_EncoderBase):
         s2 = (3.0 * dh) ** -0.5 * 1.4426950408889634
         bias2d = pl["bias2d"]
         for i, lay in enumerate(self.layers):
-            x = states[i]
             self._gemm(xa, lay["qkv"], M, out_act=qkv, col_scale=s2, col_scale_end=D)
             # content -> position (q x position keys) and position -> content (k x position queries) terms: one grouped GEMM,
             # group = (term, head), K = dh
@@ -1688,11 +1645,7 @@ class DebertaEncoder(_EncoderBase):
                                        win["p2c_col"].data_ptr(), key_lens.data_ptr(), bias2d.data_ptr(), bias2d.shape[-1],
                                        B, T, H, float(s2), st), "ser_deberta_bias")
             self._attention(qkv, pl["frame_offs"], B, T, pl["ctx"], key_lens=key_lens, bias2d=bias2d)
-            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=pl["tmp"], ldo_f32=D)
-            self._layernorm(pl["tmp"], D, lay["ln1"], M, D, out_f32=pl["h"], out_act=pl["ha"])
-            self._gemm(pl["ha"], lay["fc1"], M, act=_lib.ACT_GELU, out_act=pl["ffn"])
-            self._gemm(pl["ffn"], lay["fc2"], M, residual=pl["h"], ldr=D, out_f32=pl["tmp"], ldo_f32=D)
-            self._layernorm(pl["tmp"], D, lay["ln2"], M, D, out_f32=states[i + 1], out_act=xa)
+            self._post_ln_tail(pl, lay, states[i], states[i + 1], xa)
             if i == 0 and self.text_conv is not None:
                 # ConvLayer: LN(layer-0 output + gelu(Conv1d_k3(embeddings))) with padded rows zero.  (HF zeroes the padded
                 # rows of the conv output before the activation too; gelu(0) = 0 and those rows are zeroed at the end anyway.)
@@ -1703,9 +1656,7 @@ class DebertaEncoder(_EncoderBase):
                 self._layernorm(pl["tmp"], D, self.text_conv["ln"], M, D, out_f32=states[1], out_act=xa)
                 check(lib.ser_zero_padded_rows(states[1].data_ptr(), D, xa.ptr, D, xa.plane_stride, self.mode, key_lens.data_ptr(),
                                                B, T, D, st), "ser_zero_padded_rows")
-        hs = HiddenStates(states, pl["frame_offs_host"])
-        hs.range_flag = flag
-        return hs
+        return HiddenStates(states, pl["frame_offs_host"], range_flag=flag)
 
 
 def mean_last4(hs: HiddenStates) -> torch.Tensor:

@@ -705,3 +705,18 @@ def test_text_encoder_refuses_out_of_table_inputs():
     bad[0, 3] = geo.vocab_size
     with pytest.raises(ValueError):
         enc.forward(bad, torch.ones_like(bad))
+
+
+@pytest.mark.parametrize("case", ["roberta", "deberta"])
+def test_text_encoder_names_the_weight_it_refuses(case):
+    """A weight beyond the fp16 range refused at load in "f16x" names its checkpoint tensor and the way out (--mode fp32x)."""
+    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd.engine import DebertaEncoder, TextEncoder
+    from interspeech_ser_amd.weights import synthetic_state_dict
+    geo, cls, name = {"roberta": (C.TINY_ROBERTA, TextEncoder, "encoder.layer.0.attention.self.query.weight"),
+                      "deberta": (C.TINY_DEBERTA, DebertaEncoder, "encoder.layer.0.attention.self.query_proj.weight")}[case]
+    sd = synthetic_state_dict(geo, 2)
+    sd[name][3, 5] = 7.0e4
+    with pytest.raises(ValueError) as e:
+        cls(geo, sd, "cuda:0", mode="f16x")
+    assert name in str(e.value) and "--mode fp32x" in str(e.value), str(e.value)
