@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SER_ABI_VERSION 15
+#define SER_ABI_VERSION 16
 
 #define SER_MODE_BF16  1   /* act tensors have 1 plane; GEMMs do 1 bf16 MFMA product   */
 #define SER_MODE_FP32X 2   /* act tensors have 2 planes; GEMMs do hi*hi + lo*hi + hi*lo */
@@ -187,7 +187,7 @@ typedef struct ser_gemm_args {
      * (out_act in the FP16 / FP16X / FP16M formats) exceeds 65504 in magnitude (or is a NaN or Inf) BEFORE the saturating conversion, bit 1 if
      * one exceeds half that (bit 0 never comes alone).  Only values the launch stores count, not the tail columns of a tile past N -- the host reads the word back with the batch's features and fails that batch's files instead of writing
      * clipped ones (preprocess_speech.py:46,72-73: a bad file is a printed failure, never silent garbage).  ser_layernorm_v,
-     * ser_row_center_v, ser_wave_frames_v, ser_pack_act_v and ser_pack_f16m take the same word. */
+     * ser_row_center_v, ser_wave_frames_v, ser_pack_act_v, ser_pos_ln_v and ser_pack_f16m take the same word. */
     uint32_t*       range_flag;
     /* GroupNorm-over-time stem (ABI 15; conv layer 0 of the *-base checkpoints, HF WavLMGroupNormConvLayer): with gn_scale != NULL the
      * epilogue applies, after the bias and before act,  v = v * gn_scale[u][n] + gn_shift[u][n]  where u is the utterance of row m
@@ -417,6 +417,29 @@ typedef struct ser_gn_stats_args {
 } ser_gn_stats_args;
 int ser_gn_stats_v(const ser_gn_stats_args* args, void* stream);
 
+/* K6p (ABI 16)  data2vec-audio's positional stack (HF Data2VecAudioPositionalConvLayer / Data2VecAudioEncoder.forward): each of the
+ * num_conv_pos_embeddings layers is a grouped Conv1d (run as ser_gemm over the zero-halo'd operand copy, bias added, fp32 out) followed
+ * by LayerNorm(D, no affine, eps_pos) and GELU.  The LayerNorm spans all groups of a row, so it is a row pass of its own: one wave per row,
+ * two-pass fp32 mean / variance (rows of a conv output may have a large mean), exact-erf GELU.
+ *   last == 0 (intermediate layer):  y = gelu(LN(x))  -> out_act row out_rowmap[m] in `mode` (the next conv's operand planes at the
+ *             row's halo'd position; the halo rows are never written and stay zero).  out_rowmap NULL = row m.
+ *   last == 1 (last layer):          t = gelu(LN(x)) + residual;  z = LN(t) * g + b (encoder.layer_norm, eps)  -> out_f32 row m
+ *             (hidden_states[0]) and, when out_act is not NULL, its operand copy at row m (out_rowmap must be NULL).
+ * Modes SER_MODE_BF16 / FP32X / FP16 / FP16X.  rows <= 2^31, D % 4 == 0, D <= 2048, pitches multiples of 4.  range_flag: fp16 range
+ * guard of the out_act values (see ser_gemm_args.range_flag), may be NULL.  The reference has no counterpart (fp32 end to end). */
+typedef struct ser_pos_ln_args {
+    const float* x; int64_t ldx;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    const int32_t* out_rowmap;
+    const float* residual; int64_t ldr;
+    const float* g; const float* b;
+    float* out_f32; int64_t ldo_f32;
+    float eps_pos, eps;
+    int32_t last, mode, rows, D;
+    uint32_t* range_flag;
+} ser_pos_ln_args;
+int ser_pos_ln_v(const ser_pos_ln_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -425,6 +448,7 @@ int ser_gn_stats_v(const ser_gn_stats_args* args, void* stream);
 #define SER_OP_LOGMEL 6
 #define SER_OP_PACK_ACT 7
 #define SER_OP_GN_STATS 8
+#define SER_OP_POS_LN 9
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -436,6 +460,7 @@ typedef struct ser_cmd {
         ser_logmel_args      logmel;
         ser_pack_act_args    pack_act;
         ser_gn_stats_args    gn_stats;
+        ser_pos_ln_args      pos_ln;
     } u;
 } ser_cmd;
 

@@ -26,7 +26,7 @@ ACT_GELU = 1
 WS_LOGMEL = 1
 WS_WAVE_FRAMES = 2
 WS_GN_STATS = 3
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_void_p, c_int, c_i64, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -131,9 +131,25 @@ class PackActArgs(C.Structure):
                 ("range_flag", c_void_p)]
 
 
+class PosLnArgs(C.Structure):
+    """Mirror of ``ser_pos_ln_args`` (ABI 16)."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64),
+        ("out_rowmap", c_void_p),
+        ("residual", c_void_p), ("ldr", c_i64),
+        ("g", c_void_p), ("b", c_void_p),
+        ("out_f32", c_void_p), ("ldo_f32", c_i64),
+        ("eps_pos", c_float), ("eps", c_float),
+        ("last", C.c_int32), ("mode", C.c_int32), ("rows", C.c_int32), ("D", C.c_int32),
+        ("range_flag", c_void_p),
+    ]
+
+
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
-                ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs)]
+                ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
+                ("pos_ln", PosLnArgs)]
 
 
 class Cmd(C.Structure):
@@ -141,10 +157,10 @@ class Cmd(C.Structure):
     _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("u", _CmdUnion)]
 
 
-OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS = 1, 2, 3, 4, 5, 6, 7, 8
+OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS, OP_POS_LN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
-                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_cmd": Cmd}
+                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -163,6 +179,7 @@ _SIGNATURES = {
     "ser_wave_frames_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_act_v": (c_int, [c_void_p, c_void_p]),
     "ser_gn_stats_v": (c_int, [c_void_p, c_void_p]),
+    "ser_pos_ln_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -20,8 +20,9 @@ FAMILY_HUBERT = "hubert"
 FAMILY_WHISPER = "whisper"
 FAMILY_ROBERTA = "roberta"      # text side of the bimodal heads (next row 8f-1)
 FAMILY_DEBERTA = "deberta"      # DeBERTa-v2/v3 variant of the text side (engine.DebertaEncoder, csrc/deberta.hip)
+FAMILY_DATA2VEC_AUDIO = "data2vec-audio"   # layer-norm conv stem, post-LN encoder, a stack of LayerNorm'd positional convs
 
-SPEECH_FAMILIES = (FAMILY_WAVLM, FAMILY_WAV2VEC2, FAMILY_HUBERT)
+SPEECH_FAMILIES = (FAMILY_WAVLM, FAMILY_WAV2VEC2, FAMILY_HUBERT, FAMILY_DATA2VEC_AUDIO)
 
 
 @dataclass(frozen=True)
@@ -43,6 +44,10 @@ class EncoderGeometry:
     stable_layer_norm: bool = True
     pos_conv_kernel: int = 128
     pos_conv_groups: int = 16
+    # positional embedding: ONE weight-normed grouped conv + GELU ("weight": wavlm / wav2vec2 / hubert), or a stack of pos_conv_layers
+    # plain grouped convs, each followed by a non-affine LayerNorm and GELU ("layer": data2vec-audio, HF Data2VecAudioPositionalConvLayer)
+    pos_conv_layers: int = 1
+    pos_conv_norm: str = "weight"
     # WavLM gated relative position bias
     num_buckets: int = 320
     max_bucket_distance: int = 800
@@ -138,6 +143,17 @@ HUBERT_BASE = EncoderGeometry(
     family=FAMILY_HUBERT, num_layers=12, hidden=768, heads=12, ffn=3072, conv_bias=False,
     feat_extract_norm="group", stable_layer_norm=False, name="facebook/hubert-base-ls960")
 
+# data2vec-audio: layer-norm conv stem, post-LN encoder, positional embedding = 5 x [grouped Conv1d(k 19, pad 9, 16 groups) -> LayerNorm
+# (no affine) -> GELU].  Base = transformers' Data2VecAudioConfig() defaults; large = 1024 / 24 / 16 / 4096 with the same stem and
+# positional stack.  Written from the public hub configs, which cannot be fetched offline to be checked here: a snapshot's config.json
+# takes precedence over these entries (resolve_geometry).
+DATA2VEC_AUDIO_BASE = EncoderGeometry(
+    family=FAMILY_DATA2VEC_AUDIO, num_layers=12, hidden=768, heads=12, ffn=3072, conv_bias=False, stable_layer_norm=False,
+    pos_conv_kernel=19, pos_conv_groups=16, pos_conv_layers=5, pos_conv_norm="layer", name="facebook/data2vec-audio-base")
+DATA2VEC_AUDIO_LARGE = EncoderGeometry(
+    family=FAMILY_DATA2VEC_AUDIO, num_layers=24, hidden=1024, heads=16, ffn=4096, conv_bias=False, stable_layer_norm=False,
+    pos_conv_kernel=19, pos_conv_groups=16, pos_conv_layers=5, pos_conv_norm="layer", name="facebook/data2vec-audio-large")
+
 _REGISTRY = {
     "microsoft/deberta-v3-large": DEBERTA_V3_LARGE,
     "microsoft/deberta-v2-xlarge": DEBERTA_V2_XLARGE,
@@ -156,17 +172,21 @@ _REGISTRY = {
     "microsoft/wavlm-base-plus-sv": replace(WAVLM_BASE, name="microsoft/wavlm-base-plus-sv"),
     "facebook/wav2vec2-base": WAV2VEC2_BASE,
     "facebook/hubert-base-ls960": HUBERT_BASE,
+    "facebook/data2vec-audio-base": DATA2VEC_AUDIO_BASE,
+    "facebook/data2vec-audio-base-960h": replace(DATA2VEC_AUDIO_BASE, name="facebook/data2vec-audio-base-960h"),
+    "facebook/data2vec-audio-large": DATA2VEC_AUDIO_LARGE,
+    "facebook/data2vec-audio-large-960h": replace(DATA2VEC_AUDIO_LARGE, name="facebook/data2vec-audio-large-960h"),
 }
 
 
 def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int = 2,
                   ffn: int = 256, conv_dim: int = 64, pos_groups: int = 2, text_conv_kernel: int = 0,
-                  base: bool = False) -> EncoderGeometry:
+                  base: bool = False, conv_bias: bool = False) -> EncoderGeometry:
     """Small geometries with the real kernel/stride tuples; used by the parity
     fixtures under tests/golden (SURVEY 8c item 1).  ``hidden // heads`` selects
     the head-dim code path (64 WavLM/Whisper, 80 HuBERT-XL, 120 XLS-R-2B) and
     ``hidden // pos_groups`` the pos-conv group width (64 / 80 / 120 in the real models).  ``base=True``: the *-base form of a
-    speech family (GroupNorm stem, post-LN encoder, no conv bias)."""
+    speech family (GroupNorm stem, post-LN encoder, no conv bias).  ``conv_bias``: data2vec-audio only (the other families fix it)."""
     if family == FAMILY_ROBERTA:
         return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn,
                                vocab_size=300, max_positions=90, name=f"tiny-{family}-d{hidden}h{heads}")
@@ -180,6 +200,11 @@ def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int
         return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads,
                                ffn=ffn, n_mels=128, max_source_positions=1500,
                                name=f"tiny-{family}-d{hidden}h{heads}")
+    if family == FAMILY_DATA2VEC_AUDIO:
+        return EncoderGeometry(
+            family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn, conv_dim=(conv_dim,) * 7, conv_bias=conv_bias,
+            stable_layer_norm=False, pos_conv_kernel=19, pos_conv_groups=pos_groups, pos_conv_layers=5, pos_conv_norm="layer",
+            name=f"tiny-{family}-d{hidden}h{heads}g{pos_groups}")
     if base:
         return EncoderGeometry(
             family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn,
@@ -212,8 +237,9 @@ def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
     local snapshot (preprocess_speech.py:111-112, preprocess_whisper.py:119-120), so fine-tunes published under another name
     work without a registry entry.  Two speech forms are implemented: the layer-norm stem with a stable-LayerNorm encoder
     (*-large / xlarge / XLS-R) and the GroupNorm stem with a post-LayerNorm encoder (*-base: ``feat_extract_norm="group"``,
-    ``do_stable_layer_norm=False``).  The two mixed combinations, which no published checkpoint uses, are refused with
-    ``OSError``, the class the reference's driver reports as "No pretrained model found" (:115-117)."""
+    ``do_stable_layer_norm=False``).  For these three model types the two mixed combinations, which none of their published
+    checkpoints uses, are refused with ``OSError``, the class the reference's driver reports as "No pretrained model found"
+    (:115-117).  data2vec-audio always pairs the layer-norm stem with a post-LayerNorm encoder."""
     mt = str(cfg.get("model_type", "")).lower()
     name = name or str(cfg.get("_name_or_path", "")) or mt
     if mt in (FAMILY_WAVLM, FAMILY_WAV2VEC2, FAMILY_HUBERT):
@@ -261,8 +287,27 @@ def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
             max_positions=int(cfg.get("max_position_embeddings", 512)), pad_token_id=int(cfg.get("pad_token_id", 0)),
             type_vocab_size=int(cfg.get("type_vocab_size", 0)), layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-7)),
             position_buckets=int(cfg.get("position_buckets", 256)), text_conv_kernel=int(cfg.get("conv_kernel_size", 0) or 0), name=name)
+    if mt == FAMILY_DATA2VEC_AUDIO:
+        # HF Data2VecAudioConfig: the positional kernel is conv_pos_kernel_size and num_conv_pos_embeddings is the number of conv
+        # LAYERS (in the wavlm / wav2vec2 / hubert configs that key is the kernel).  The stem is always the layer-norm one
+        # (Data2VecAudioConvLayer) and the encoder always post-LN (Data2VecAudioEncoder); the config has no key for either.
+        if cfg.get("add_adapter", False):
+            raise OSError(f"{name}: add_adapter=True (an adapter stack after the encoder) is not supported")
+        k = int(cfg.get("conv_pos_kernel_size", 19))
+        if k % 2 == 0:
+            raise OSError(f"{name}: an even conv_pos_kernel_size ({k}) is not supported (Data2VecAudioPadLayer drops the last frame)")
+        return EncoderGeometry(
+            family=FAMILY_DATA2VEC_AUDIO, num_layers=int(cfg["num_hidden_layers"]), hidden=int(cfg["hidden_size"]),
+            heads=int(cfg["num_attention_heads"]), ffn=int(cfg["intermediate_size"]),
+            conv_dim=tuple(int(c) for c in cfg.get("conv_dim", (512,) * 7)),
+            conv_kernel=tuple(int(c) for c in cfg.get("conv_kernel", (10, 3, 3, 3, 3, 2, 2))),
+            conv_stride=tuple(int(c) for c in cfg.get("conv_stride", (5, 2, 2, 2, 2, 2, 2))),
+            conv_bias=bool(cfg.get("conv_bias", False)), feat_extract_norm="layer", stable_layer_norm=False,
+            pos_conv_kernel=k, pos_conv_groups=int(cfg.get("num_conv_pos_embedding_groups", 16)),
+            pos_conv_layers=int(cfg.get("num_conv_pos_embeddings", 5)), pos_conv_norm="layer",
+            layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), name=name)
     raise OSError(f"{name}: model_type '{mt}' is not an encoder this path implements "
-                  "(wavlm / wav2vec2 / hubert / whisper / roberta / deberta-v2)")
+                  "(wavlm / wav2vec2 / hubert / data2vec-audio / whisper / roberta / deberta-v2)")
 
 
 def find_config_json(ssl_type: str, checkpoint: str = "") -> str:
@@ -342,3 +387,7 @@ TINY_DEBERTA_CONV = tiny_geometry(FAMILY_DEBERTA, hidden=128, heads=2, ffn=256, 
 TINY_WAVLM_BASE = tiny_geometry(FAMILY_WAVLM, hidden=128, heads=2, ffn=256, pos_groups=2, base=True)
 TINY_WAV2VEC2_BASE = tiny_geometry(FAMILY_WAV2VEC2, hidden=128, heads=2, ffn=256, pos_groups=2, base=True)
 TINY_HUBERT_BASE = tiny_geometry(FAMILY_HUBERT, hidden=128, heads=2, ffn=256, pos_groups=2, base=True)
+# data2vec-audio fixture geometries (tests/golden/tiny_data2vec_audio_*.npz): positional group width 64, and 48 -- the real base
+# model's (768 / 16), not a multiple of 64, so the stack's GEMMs read the padded channels of pos_kc
+TINY_DATA2VEC_AUDIO = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=128, heads=2, ffn=256, pos_groups=2)
+TINY_DATA2VEC_AUDIO_G48 = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=192, heads=3, ffn=256, pos_groups=4, conv_bias=True)

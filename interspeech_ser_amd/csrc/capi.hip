@@ -67,6 +67,10 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_gn_stats_v(&c.u.gn_stats, stream);
                 break;
             }
+            case SER_OP_POS_LN: {
+                rc = ser_pos_ln_v(&c.u.pos_ln, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

@@ -351,6 +351,118 @@ extern "C" int ser_layernorm(const float* x, int64_t ldx, const float* g, const 
     return ser_layernorm_v(&a, stream);
 }
 
+// ------------------------------------------------------------------------------ K6p
+// data2vec-audio's positional stack, the row pass after each grouped conv (ser_hip.h ser_pos_ln_args).  Wave per row, row kept in
+// registers (D <= 2048), both LayerNorms two-pass in fp32.  LAST = 0: gelu(LN(x)) scattered to the halo'd row; LAST = 1: + residual,
+// then encoder.layer_norm.
+template <int MODE, bool LAST>
+__global__ __launch_bounds__(256) void pos_ln_kernel(const float* __restrict__ x, int64_t ldx, unsigned short* __restrict__ oa, int64_t ldoa,
+                                                     int64_t plane, const int32_t* __restrict__ rowmap, const float* __restrict__ res,
+                                                     int64_t ldr, const float* __restrict__ g, const float* __restrict__ b,
+                                                     float* __restrict__ of, int64_t ldof, float eps_pos, float eps, int rows, int D,
+                                                     uint32_t* __restrict__ rflag) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = x + (int64_t)row * ldx;
+    f32x4 v[8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int c = i * 256 + lane * 4;
+        if (c < D) { v[i] = *(const f32x4*)(xr + c); s += v[i][0] + v[i][1] + v[i][2] + v[i][3]; }
+        else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    float mean = wave_sum(s) / (float)D, q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int c = i * 256 + lane * 4;
+        if (c < D) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
+        }
+    }
+    float rstd = rsqrtf(wave_sum(q) / (float)D + eps_pos);
+    // y = gelu(LN(x)) (+ residual) in place
+    s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int c = i * 256 + lane * 4;
+        if (c < D) {
+            f32x4 r = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (LAST) r = *(const f32x4*)(res + (int64_t)row * ldr + c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[i][j] = gelu_erf((v[i][j] - mean) * rstd) + r[j];
+            s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
+        }
+    }
+    float ramax = 0.f;
+    if constexpr (!LAST) {
+        unsigned short* orow = oa + (int64_t)(rowmap ? rowmap[row] : row) * ldoa;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = i * 256 + lane * 4;
+            if (c < D) {
+                store_act4<MODE>(orow + c, plane, v[i][0], v[i][1], v[i][2], v[i][3]);
+                if constexpr (mode_traits<MODE>::f16) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, v[i][j]); }
+            }
+        }
+    } else {
+        mean = wave_sum(s) / (float)D;
+        q = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = i * 256 + lane * 4;
+            if (c < D) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
+            }
+        }
+        rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = i * 256 + lane * 4;
+            if (c < D) {
+                const f32x4 gg = *(const f32x4*)(g + c), bb = *(const f32x4*)(b + c);
+                f32x4 y;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * gg[j] + bb[j];
+                *(f32x4*)(of + (int64_t)row * ldof + c) = y;
+                if (oa) {
+                    store_act4<MODE>(oa + (int64_t)row * ldoa + c, plane, y[0], y[1], y[2], y[3]);
+                    if constexpr (mode_traits<MODE>::f16) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); }
+                }
+            }
+        }
+    }
+    if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
+}
+
+extern "C" int ser_pos_ln_v(const ser_pos_ln_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_pos_ln: null pointer");
+    const int last = a->last, mode = a->mode, rows = a->rows, D = a->D;
+    if (!a->x || (last ? (!a->out_f32 || !a->residual || !a->g || !a->b) : !a->out_act))
+        return ser_fail(-1, "ser_pos_ln: null pointer (x; intermediate: out_act; last: out_f32, residual, g, b)");
+    if (last != 0 && last != 1) return ser_fail(-2, "ser_pos_ln: last=%d must be 0 or 1", last);
+    if (last && a->out_rowmap) return ser_fail(-2, "ser_pos_ln: the last form writes row m (out_rowmap must be NULL)");
+    if (D % 4 || D > 2048 || D <= 0 || rows <= 0) return ser_fail(-2, "ser_pos_ln: D=%d rows=%d unsupported", D, rows);
+    if ((a->ldx % 4) || (a->out_act && a->ldo_act % 4) || (last && (a->ldr % 4 || a->ldo_f32 % 4)))
+        return ser_fail(-3, "ser_pos_ln: pitches must be multiples of 4");
+    dim3 grid((rows + 3) / 4), block(256);
+#define SER_PL(M_, L_) hipLaunchKernelGGL((pos_ln_kernel<M_, L_>), grid, block, 0, (hipStream_t)stream, a->x, a->ldx, \
+                                          (unsigned short*)a->out_act, a->ldo_act, a->out_plane_stride, a->out_rowmap, a->residual, a->ldr, \
+                                          a->g, a->b, a->out_f32, a->ldo_f32, a->eps_pos, a->eps, rows, D, a->range_flag)
+#define SER_PL2(M_) do { if (last) SER_PL(M_, true); else SER_PL(M_, false); } while (0)
+    if (mode == SER_MODE_FP32X) SER_PL2(SER_MODE_FP32X);
+    else if (mode == SER_MODE_BF16) SER_PL2(SER_MODE_BF16);
+    else if (mode == SER_MODE_FP16) SER_PL2(SER_MODE_FP16);
+    else if (mode == SER_MODE_FP16X) SER_PL2(SER_MODE_FP16X);
+    else return ser_fail(-4, "ser_pos_ln: bad mode %d", mode);
+#undef SER_PL2
+#undef SER_PL
+    return ser_check_launch("ser_pos_ln");
+}
+
 // ----------------------------------------------------------------- centred operand copy
 // Wave per row: act copy of (x - mean_row), its row partials and the shift, in the layout the deferred-LayerNorm GEMMs
 // consume (ser_gemm_args.ln_stats_in / shift_in).  Run ONCE per forward on hidden_states[0], whose row mean is produced

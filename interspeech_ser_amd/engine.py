@@ -28,7 +28,7 @@ import torch
 from . import _lib
 from ._lib import GemmArgs, check, lib
 from .weights import check_f16_weight
-from .config import EncoderGeometry, FAMILY_ROBERTA, FAMILY_WAVLM, FAMILY_WHISPER
+from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_WAVLM, FAMILY_WHISPER
 
 MODES = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X, "f16": _lib.MODE_FP16, "f16q": _lib.MODE_FP16, "f16a": _lib.MODE_FP16,
          "f16x": _lib.MODE_FP16X, "f16m": _lib.MODE_FP16M, "f16mf": _lib.MODE_FP16M}
@@ -892,15 +892,22 @@ def _fold_weight_norm(sd) -> torch.Tensor:
 
 class SpeechEncoder(_EncoderBase):
     """WavLM / wav2vec2 / HuBERT on libserhip: the *-large / xlarge / XLS-R form (layer-norm conv stack, stable-LayerNorm encoder) and
-    the *-base form (GroupNorm-over-time conv layer 0, post-LayerNorm encoder; ``geo.stable_layer_norm`` False).  ``normalize``: the
-    feature extractor's ``do_normalize`` (zero-mean / unit-variance input per utterance)."""
+    the *-base form (GroupNorm-over-time conv layer 0, post-LayerNorm encoder; ``geo.stable_layer_norm`` False).  data2vec-audio: the
+    layer-norm conv stack with a post-LayerNorm encoder, and a stack of LayerNorm'd positional convs (``geo.pos_conv_norm == "layer"``).
+    ``normalize``: the feature extractor's ``do_normalize`` (zero-mean / unit-variance input per utterance)."""
 
     def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "bf16", normalize: bool = True):
         super().__init__(geo, device, mode, post_ln=not geo.stable_layer_norm)
         if geo.family == FAMILY_WHISPER:
             raise ValueError("use WhisperEncoder for the whisper family")
         self.normalize = bool(normalize)
-        if self.post_ln != (geo.feat_extract_norm == "group"):
+        self.gn_stem = geo.feat_extract_norm == "group"
+        if (geo.family == FAMILY_DATA2VEC_AUDIO) != (geo.pos_conv_norm == "layer"):
+            raise NotImplementedError("the LayerNorm'd positional conv stack is data2vec-audio's, and data2vec-audio has only that one")
+        if geo.family == FAMILY_DATA2VEC_AUDIO:
+            if self.gn_stem or not self.post_ln:
+                raise NotImplementedError("data2vec-audio: the layer-norm conv stem with a post-LN encoder is the only form")
+        elif self.post_ln != self.gn_stem:
             raise NotImplementedError("GroupNorm stems come with post-LN encoders and layer-norm stems with stable-LN ones")
         if not geo.feat_proj_layer_norm:
             raise NotImplementedError("feat_proj_layer_norm=False checkpoints are not supported")
@@ -918,7 +925,7 @@ class SpeechEncoder(_EncoderBase):
         w0 = torch.zeros((C0, 64), dtype=torch.float32)
         w0[:, : geo.conv_kernel[0]] = sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]).float()
         self.conv0 = self._linear(w0, sd[p0 + ".conv.bias"] if geo.conv_bias else None, stem=True, name=p0 + ".conv.weight")
-        if self.post_ln:        # GroupNorm(C, C) of conv layer 0 (its affine); layers 1..6 have no norm
+        if self.gn_stem:        # GroupNorm(C, C) of conv layer 0 (its affine); layers 1..6 have no norm
             self.gn0 = self._ln_pair(sd, p0 + ".layer_norm")
             self.conv_ln = [None] * len(geo.conv_dim)
         else:
@@ -936,9 +943,11 @@ class SpeechEncoder(_EncoderBase):
         G, k = geo.pos_conv_groups, geo.pos_conv_kernel
         Cg = D // G
         self.pos_cg, self.pos_kc = Cg, ((Cg + 63) // 64) * 64
-        w = _fold_weight_norm(sd)                                          # [D, Cg, k]
-        wp = torch.zeros((G, Cg, k, self.pos_kc), dtype=torch.float32)
-        wp[:, :, :, :Cg] = w.view(G, Cg, Cg, k).permute(0, 1, 3, 2)
+
+        def pos_weight(w: torch.Tensor) -> torch.Tensor:                  # [D, Cg, k] -> [G * Cg, k * pos_kc]
+            wp = torch.zeros((G, Cg, k, self.pos_kc), dtype=torch.float32)
+            wp[:, :, :, :Cg] = w.float().view(G, Cg, Cg, k).permute(0, 1, 3, 2)
+            return wp.reshape(G * Cg, k * self.pos_kc)
         # The positional conv runs in the LAYER format when its dot products are short enough: in "f16" mode it then costs 3x
         # less than on the fp32x stem and, unlike the conv stack and the projection, moves the error by nothing measurable
         # (WavLM-large, K = 128 taps x 64 channels: 6.8e-4 either way; HuBERT-xlarge, 128 x 80: 8.0e-4 either way).  XLS-R-2B's
@@ -946,8 +955,14 @@ class SpeechEncoder(_EncoderBase):
         # "f16q" / "f16a" keep it on the stem format always: an error in hidden_states[0] enters layer 0's logits, and these modes
         # exist for attention maps sharp enough to amplify it (LoRA stress fixture: 1.4e-3 -> see DESIGN.md section 4)
         self.pos_in_stem = (self.mode_name == "f16" and Cg * k > 128 * 80) or self.mode_name in ("f16q", "f16a", "f16m", "f16mf")
-        self.pos = self._linear(wp.reshape(G * Cg, k * self.pos_kc), sd["encoder.pos_conv_embed.conv.bias"], stem=self.pos_in_stem,
-                                name="encoder.pos_conv_embed.conv.weight (weight-norm folded)")
+        if geo.pos_conv_norm == "layer":
+            # data2vec-audio: pos_conv_layers grouped convs, each one GEMM over the halo'd copy followed by ser_pos_ln_v
+            self.pos_stack = [self._linear(pos_weight(sd[f"encoder.pos_conv_embed.layers.{j}.conv.weight"]),
+                                           sd[f"encoder.pos_conv_embed.layers.{j}.conv.bias"], stem=self.pos_in_stem,
+                                           name=f"encoder.pos_conv_embed.layers.{j}.conv.weight") for j in range(geo.pos_conv_layers)]
+        else:
+            self.pos = self._linear(pos_weight(_fold_weight_norm(sd)), sd["encoder.pos_conv_embed.conv.bias"], stem=self.pos_in_stem,
+                                    name="encoder.pos_conv_embed.conv.weight (weight-norm folded)")
         self.enc_ln = self._ln_pair(sd, "encoder.layer_norm")
         self.layers = []
         for i in range(geo.num_layers):
@@ -994,11 +1009,12 @@ class SpeechEncoder(_EncoderBase):
         ar["halo_act"] = self._new_act(cap["halo"], D, zero=True, extra_rows=1, stem=self.pos_in_stem)
         ar["states"] = torch.empty((geo.num_layers + 1, cap["M"], D), dtype=torch.float32, device=dev)
         ar["first_groups"] = 2                               # ser_row_center writes one (sum, sum^2) slot + one zero slot
-        if self.post_ln:
+        if self.gn_stem:
             # the GroupNorm stem's per-(utterance, channel) affine + its workspace
             ar["gn_scale"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
             ar["gn_shift"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
             ar["gn_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_GN_STATS, cap["B"], 0, 0, 0, self.stem_mode), dtype=torch.uint8, device=dev)
+        if self.post_ln:
             self._post_ln_buffers(ar, cap["M"], 3 * D + (self._gate_width() if geo.family == FAMILY_WAVLM else 0))
         else:
             self._layer_buffers(ar, cap["M"], ar["first_groups"])
@@ -1175,7 +1191,7 @@ class SpeechEncoder(_EncoderBase):
         else:
             check(lib.ser_wave_frames_v(C.byref(a), self._s()), "ser_wave_frames")
         a_in = pl["conv_act"][0]
-        if self.post_ln:
+        if self.gn_stem:
             self._groupnorm_stem(pl, packed_wave)
         else:
             self._gemm(fr, self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
@@ -1201,9 +1217,14 @@ class SpeechEncoder(_EncoderBase):
         self._gemm(pl["feat_act"], self.proj, M, out_f32=pl["proj_f32"], ldo_f32=D,
                    out_act=pl["halo_act"], out_rowmap=pl["halo_rowmap"], stem=True,
                    out_mode=self.stem_mode if self.pos_in_stem else self.mode)
-        # a10: grouped positional conv + GELU + residual -> hidden_states[0]
         states = pl["states"]
         G, Cg, kc = geo.pos_conv_groups, self.pos_cg, self.pos_kc
+        if geo.pos_conv_norm == "layer":
+            # data2vec-audio: hidden_states[0] = encoder.layer_norm(proj + stack(proj)) (HF Data2VecAudioEncoder.forward), then the layers
+            self._pos_stack(pl, states)
+            self._run_post_ln_layers(pl, states, B, pl["Tmax"], last_state)
+            return
+        # a10: grouped positional conv + GELU + residual -> hidden_states[0]
         self._gemm(pl["halo_act"], self.pos, M, a_rowoff=pl["pos_rowoff"], kc=kc, ldj=D, groups=G,
                    a_group_stride=Cg, w_group_stride=Cg * geo.pos_conv_kernel * kc, c_group_stride=Cg,
                    N=Cg, K=geo.pos_conv_kernel * kc, act=_lib.ACT_GELU, residual=pl["proj_f32"], ldr=D,
@@ -1216,6 +1237,47 @@ class SpeechEncoder(_EncoderBase):
         # a11/a12: stable-LayerNorm encoder layers (LayerNorms deferred into the GEMMs)
         self._run_layers(pl, states, pl["first_groups"], B, pl["Tmax"], last_state)
 
+
+    def _pos_stack(self, pl, states) -> None:
+        """data2vec-audio's positional embedding (HF Data2VecAudioPositionalConvEmbedding): per layer j the grouped conv as an implicit
+        GEMM over the zero-halo'd copy (bias added, fp32 into ``tmp``), then ser_pos_ln_v: LayerNorm (no affine) + GELU written back
+        into the SAME halo'd copy at each row's halo'd position (stream order puts the GEMM's reads before the row pass's writes; the
+        halo rows and the spare row the padded channels of the last group reach stay zero).  After the last layer the row pass adds the
+        projection output and applies encoder.layer_norm: hidden_states[0] and layer 0's operand copy."""
+        geo = self.geo
+        M, D = pl["M"], geo.hidden
+        G, Cg, kc, k = geo.pos_conv_groups, self.pos_cg, self.pos_kc, geo.pos_conv_kernel
+        halo = pl["halo_act"]
+        n = len(self.pos_stack)
+        for j, lin in enumerate(self.pos_stack):
+            self._gemm(halo, lin, M, a_rowoff=pl["pos_rowoff"], kc=kc, ldj=D, groups=G, a_group_stride=Cg, w_group_stride=Cg * k * kc,
+                       c_group_stride=Cg, N=Cg, K=k * kc, out_f32=pl["tmp"], ldo_f32=D, k_algo=k * Cg, stem=self.pos_in_stem)
+            if j + 1 < n:
+                self._pos_ln(pl["tmp"], M, out_act=halo, rowmap=pl["halo_rowmap"], mode=self.stem_mode if self.pos_in_stem else self.mode)
+            else:
+                self._pos_ln(pl["tmp"], M, out_act=pl["xa"], mode=self.mode, residual=pl["proj_f32"], out_f32=states[0])
+
+    def _pos_ln(self, x: torch.Tensor, rows: int, *, out_act: Optional[Act], mode: int, rowmap=None, residual=None, out_f32=None) -> None:
+        """ser_pos_ln_v: the intermediate form (``residual`` None) or the last one (+ residual, encoder.layer_norm -> ``out_f32``)."""
+        D = self.geo.hidden
+        last = residual is not None
+        rec = self._rec
+        a = rec.slot("pos_ln") if rec is not None else _lib.PosLnArgs()
+        a.x, a.ldx = x.data_ptr(), D
+        a.out_act = None if out_act is None else out_act.ptr
+        a.ldo_act = 0 if out_act is None else out_act.cols
+        a.out_plane_stride = 0 if out_act is None else out_act.plane_stride
+        a.out_rowmap = _ptr(rowmap)
+        a.residual, a.ldr = _ptr(residual), D if last else 0
+        a.g, a.b = (self.enc_ln[0].data_ptr(), self.enc_ln[1].data_ptr()) if last else (None, None)
+        a.out_f32, a.ldo_f32 = _ptr(out_f32), D if last else 0
+        a.eps_pos, a.eps = 1e-5, float(self.geo.layer_norm_eps)          # nn.LayerNorm(D, elementwise_affine=False): the default eps
+        a.last, a.mode, a.rows, a.D = int(last), mode, rows, D
+        a.range_flag = self._flag if out_act is not None else None
+        if rec is not None:
+            rec.commit(_lib.OP_POS_LN, a, rows=rows)
+            return
+        check(lib.ser_pos_ln_v(C.byref(a), self._s()), "ser_pos_ln")
 
     def _groupnorm_stem(self, pl, packed_wave: torch.Tensor) -> None:
         """Conv layer 0 of the *-base form: GroupNorm(C, C) over each utterance's frames, then GELU.  ser_gn_stats_v derives the

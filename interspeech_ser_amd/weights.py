@@ -137,12 +137,27 @@ def synthetic_state_dict(geo: EncoderGeometry, seed: int = 0, fast: bool = False
     _linear(sd, r, "feature_projection.projection", D, cin)
 
     cg = D // geo.pos_conv_groups
+    if geo.pos_conv_norm == "layer":
+        # data2vec-audio: pos_conv_layers plain grouped convs (HF Data2VecAudioPositionalConvLayer; no weight norm, LayerNorm without
+        # parameters).  A branch of its own: the other families' streams, and so their fixture digests, stay as they were.
+        k = geo.pos_conv_kernel
+        for j in range(geo.pos_conv_layers):
+            p = f"encoder.pos_conv_embed.layers.{j}.conv"
+            sd[p + ".weight"] = r.normal(D, cg, k, std=math.sqrt(2.0 / (cg * k)))
+            sd[p + ".bias"] = r.normal(D, std=0.2)
+        return _encoder_layers(sd, r, geo)
     v = r.normal(D, cg, geo.pos_conv_kernel, std=math.sqrt(2.0 / (cg * geo.pos_conv_kernel)))
     vnorm = np.sqrt((v.numpy().astype(np.float64) ** 2).sum(axis=(0, 1), keepdims=True)).astype(np.float32)
     g = torch.from_numpy(vnorm) * r.normal(1, 1, geo.pos_conv_kernel, std=0.1, mean=1.0)
     sd["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = g
     sd["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = v
     sd["encoder.pos_conv_embed.conv.bias"] = r.normal(D, std=0.05)
+    return _encoder_layers(sd, r, geo)
+
+
+def _encoder_layers(sd: StateDict, r: _Rng, geo: EncoderGeometry) -> StateDict:
+    """encoder.layer_norm and the encoder layers of the wav2vec2-style families (after the positional embedding in the stream)."""
+    D, H, Fd, dh = geo.hidden, geo.heads, geo.ffn, geo.head_dim
     _layer_norm(sd, r, "encoder.layer_norm", D)
     for i in range(geo.num_layers):
         p = f"encoder.layers.{i}"
@@ -208,11 +223,11 @@ def apply_stress(sd: StateDict, geo: EncoderGeometry, kind: str) -> StateDict:
     return sd
 
 
-_STRIP_PREFIXES = ("wavlm.", "wav2vec2.", "hubert.", "model.", "roberta.", "deberta.")
+_STRIP_PREFIXES = ("wavlm.", "wav2vec2.", "hubert.", "data2vec_audio.", "model.", "roberta.", "deberta.")
 
 
 def normalize_names(sd: StateDict) -> StateDict:
-    """Strip task-head wrappers (``wav2vec2.`` in *ForCTC checkpoints, ``model.``
+    """Strip task-head wrappers (``wav2vec2.`` / ``data2vec_audio.`` in *ForCTC checkpoints, ``model.``
     in WhisperForConditionalGeneration) and drop everything off the encoder path
     (decoder, lm_head, quantizer, masked_spec_embed)."""
     out: StateDict = {}
