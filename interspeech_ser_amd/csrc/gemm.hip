@@ -1081,7 +1081,11 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                 }
             }
             if (p.stat_out) {
-                // row partials over this wave's 64 columns (deterministic: one slot per 64-column group)
+                // row partials over this wave's columns (deterministic: one slot per 64-column group).  A 128-column wave tile (the
+                // 3-product 256x256 tile) puts its partials in the first of its two slots and ZEROES in the second: every slot of the
+                // columns a launch covers is written.  When it left the second slot alone, a buffer whose rows another launch shape had
+                // filled before (the output projection's partials of "f16mf" with SER_F16M_OUT_M=1: FP16X layers, then FP16M layers,
+                // then the next forward's FP16X layers) fed those stale values to the consumer's LayerNorm.
                 st1 += __shfl_xor(st1, 16, 64); st2 += __shfl_xor(st2, 16, 64);
                 st1 += __shfl_xor(st1, 32, 64); st2 += __shfl_xor(st2, 32, 64);
                 const int cstart = n0 + wn * (TN * 16);
@@ -1089,6 +1093,9 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                 if (fq == 0 && cstart < p.N && grp < p.stat_groups) {
                     float* d = p.stat_out + ((int64_t)m * p.stat_groups + grp) * 2;
                     d[0] = st1; d[1] = st2;
+                    if constexpr (TN * 16 > 64) {
+                        if (cstart + 64 < p.N) { d[2] = 0.f; d[3] = 0.f; }     // (a second half past N: a padding slot, never written)
+                    }
                 }
             }
         }

@@ -815,13 +815,16 @@ extern "C" int ser_pack_act_v(const ser_pack_act_args* a, void* stream) {
     const float* x = a->x; void* out = a->out; const int B = a->B, C = a->C, T = a->T, halo = a->halo, mode = a->mode;
     const int64_t ldo = a->ldo, out_plane_stride = a->out_plane_stride;
     if (!x || !out || B <= 0 || C % 4 || T <= 0 || halo < 0) return ser_fail(-1, "ser_pack_act: bad arguments");
+    // the planes it writes: bf16 (+ lo), fp16 hi + lo; any other mode would get bf16 bits in its buffer
+    if (mode != SER_MODE_BF16 && mode != SER_MODE_FP32X && mode != SER_MODE_FP16X)
+        return ser_fail(-2, "ser_pack_act: mode %d (SER_MODE_BF16, SER_MODE_FP32X or SER_MODE_FP16X)", mode);
     const int64_t total = (int64_t)B * (T + 2 * halo) * (C / 4);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
 #define SER_PA(M_) hipLaunchKernelGGL(pack_act_kernel<M_>, grid, block, 0, (hipStream_t)stream, x, B, C, T, halo, (unsigned short*)out, ldo, \
                                       out_plane_stride, a->range_flag)
     if (mode == SER_MODE_FP32X) SER_PA(SER_MODE_FP32X);
     else if (mode == SER_MODE_FP16X) SER_PA(SER_MODE_FP16X);
-    else SER_PA(SER_MODE_BF16);
+    else if (mode == SER_MODE_BF16) SER_PA(SER_MODE_BF16);
 #undef SER_PA
     return ser_check_launch("ser_pack_act");
 }

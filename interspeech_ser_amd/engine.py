@@ -311,9 +311,11 @@ class _EncoderBase:
         if self.qkv_m_from is not None and i >= self.qkv_m_from:
             # ... and with head dim 64 (a head = one 64-column tile) ser_attention can write its context rows as FP16M operands (ABI 14), so that
             # the OUTPUT projection of these layers multiplies in the format too (what-if "qkv>=8+out>=8": 1.44e-4 / 4.1e-5; + 1.6 % on the
-            # default's step, same envelope on WavLM-large).  OPT-IN (SER_F16M_OUT_M=1), not the default: bench.py's Whisper-large-v3 record
-            # (two 8 x 30 s groups captured as concurrent graph branches, then replayed command lists) came back 0.57 from the oracle with it
-            # while the eager single-slot forward of the same batch is right (1.9e-5) -- found with no GPU time left in round 5 to chase it.
+            # default's step, same envelope on WavLM-large).  OPT-IN (SER_F16M_OUT_M=1), not the default (a performance decision of its own).
+            # Its 0.57 on bench.py's Whisper-large-v3 record was not the format: the FP16M output projections filled every 64-column slot of the
+            # row partials ``ph``, the 3-product output projection of the first layers (256 x 256 tile, 128-column waves) wrote only every
+            # other slot, and from the second forward over a plan on the first layers' LayerNorm summed the stale ones.  ser_gemm now zeroes
+            # the second slot of such a wave (tests/test_gpu_replay.py, test_gpu_kernels.py: stat_out slots).
             return dict(qkv_mode=_lib.MODE_FP16M, x_mode=_lib.MODE_FP16M, qkv_out_mode=self.attn_mode, gate_in_attn=False,
                         out_m=self.geo.head_dim == 64 and _os.environ.get("SER_F16M_OUT_M", "0") == "1")
         return dict(qkv_mode=self.qkv_mode, x_mode=self.x_mode, qkv_out_mode=self.qkv_out_mode, gate_in_attn=self.gate_in_attn, out_m=False)

@@ -117,3 +117,17 @@ def test_deberta_bucket_map_of_the_host_equals_the_oracle(built_library):
     d = torch.arange(-511, 512)
     for buckets, maxpos in ((256, 512), (16, 512), (32, 128)):
         assert torch.equal(_deberta_log_bucket(d, buckets, maxpos), O.deberta_log_bucket(d, buckets, maxpos))
+
+
+def test_pack_act_refuses_the_modes_it_does_not_write(built_library):
+    """ser_pack_act_v writes bf16, bf16 hi + lo or fp16 hi + lo planes.  SER_MODE_FP16 / FP16M / FP16Q used to fall through to the bf16
+    kernel and return 0 with bf16 bits in an fp16 buffer: refused before any launch, naming the mode (no GPU needed)."""
+    from interspeech_ser_amd import _lib
+    a = _lib.PackActArgs()
+    a.x, a.out, a.ldo, a.out_plane_stride = 256, 512, 80, 80 * 3002                 # never dereferenced: validation comes first
+    a.B, a.C, a.T, a.halo = 1, 80, 3000, 1
+    for mode in (_lib.MODE_FP16, _lib.MODE_FP16M, _lib.MODE_FP16Q, 0, 99):
+        a.mode = mode
+        assert _lib.lib.ser_pack_act_v(ctypes.byref(a), None) < 0, mode
+        assert f"ser_pack_act: mode {mode} ".encode() in _lib.lib.ser_last_error(), _lib.lib.ser_last_error()
+        assert _lib.lib.ser_pack_act(256, 1, 80, 3000, 1, 512, 80, 80 * 3002, mode, None) < 0, mode

@@ -90,7 +90,7 @@ def _speech_config(ssl_type, batch, seed, oracle_utts=(0,)):
     offs = [h.frame_offs for h in hs32]
     del enc32, hs32, kept32
     torch.cuda.empty_cache()
-    worst = {}
+    worst, same, graph_worst = {}, {}, {}
     for mode in ("bf16", "f16mf"):                                         # ("f16x" / "f16" / "f16a" at full geometry: bench.py's records, profiles/r03_config_tests.log, tests/test_gpu_depth.py; the suite's time budget)
         enc16, hs16, kept16 = run(mode)
         w = 0.0
@@ -164,7 +164,7 @@ def test_config3_whisper_large_v3_16x30s():
     offs = hs32.frame_offs
     del enc32, hs32
     torch.cuda.empty_cache()
-    worst = {}
+    worst, same, graph_worst = {}, {}, {}
     for mode in ("bf16", "f16mf"):                                         # f16mf: the whisper driver's default mode too
         enc16, mel16, hs16 = run(mode)
         s16 = hs16.states.cpu()
@@ -173,12 +173,29 @@ def test_config3_whisper_large_v3_16x30s():
             for layer in range(s16.shape[0]):
                 w = max(w, rel_err(s16[layer, offs[b]:offs[b + 1]], s32[layer, offs[b]:offs[b + 1]]))
         worst[mode] = w
-        del enc16, hs16, s16
+        del hs16, s16
+        # the flow bench.py times: two groups of 8 windows captured as parallel branches of one hipGraph, replayed; equal to the command
+        # lists of the same groups bit for bit, and each group's first utterance within the mode's bound of the fp32x run
+        groups = [(enc16.upload(waves[:8], slot=0), lengths[:8]), (enc16.upload(waves[8:], slot=1), lengths[8:])]
+        torch.cuda.synchronize()
+        graph, outs = enc16.capture_concurrent(groups)
+        graph.replay()
+        graph.replay()
+        torch.cuda.synchronize()
+        kept = [h.states.clone() for h in outs]
+        eager = [enc16.forward(wv, ln, slot=s) for s, (wv, ln) in enumerate(groups)]
+        torch.cuda.synchronize()
+        same[mode] = all(torch.equal(k, e.states) for k, e in zip(kept, eager))
+        graph_worst[mode] = max(rel_err(kept[s][layer, :1500].cpu(), s32[layer, offs[8 * s]:offs[8 * s] + 1500])
+                                for s in (0, 1) for layer in range(kept[s].shape[0]))
+        del enc16, graph, outs, kept, eager, groups
         torch.cuda.empty_cache()
     print(f"whisper-large-v3 B=16 x 30 s: log-mel abs err {worst_mel:.2e}; fp32x vs oracle {worst32:.3e}; "
-          f"vs fp32x: bf16 {worst['bf16']:.3e}, f16mf {worst['f16mf']:.3e}")
+          f"vs fp32x: bf16 {worst['bf16']:.3e}, f16mf {worst['f16mf']:.3e}; two-group graph vs fp32x {graph_worst}, equal to eager {same}")
     assert worst_mel < 1e-3, worst_mel
     assert worst32 < TOL_PARITY, worst32
     assert worst["bf16"] < TOL_BF16, worst
     assert worst["f16mf"] + worst32 < TOL_PARITY, worst
     assert worst["f16mf"] < 1e-4, worst
+    assert same == {"bf16": True, "f16mf": True}, same
+    assert graph_worst["bf16"] < TOL_BF16 and graph_worst["f16mf"] < 1e-4, graph_worst

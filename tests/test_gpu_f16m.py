@@ -262,3 +262,128 @@ def test_attention_writes_f16m_context_rows(L, bias):
     a.qkv, a.frame_offs, a.out, a.B, a.H, a.dh, a.max_frames, a.mode, a.out_mode, a.ld, a.ldo = qa.data_ptr(), foffs.data_ptr(), om.data_ptr(), 1, 4, 32, 8, 4, FP16M, 3 * D, D
     a.scale, a.out_scale, a.out_scale_ld = -1.0, sc.data_ptr(), M
     assert L.lib.ser_attention_v(C.byref(a), None) < 0
+
+
+def _attn_ref(qkv64, offs, b, h, rows=None, dh=64):
+    """float64 softmax(Q K^T) V of utterance b, head h (q pre-scaled into the exp2 domain, as the kernel takes it); ``rows``: query rows"""
+    D = qkv64.shape[1] // 3
+    r0, r1 = int(offs[b]), int(offs[b + 1])
+    q = qkv64[r0:r1, h * dh:(h + 1) * dh]
+    k = qkv64[r0:r1, D + h * dh:D + (h + 1) * dh]
+    v = qkv64[r0:r1, 2 * D + h * dh:2 * D + (h + 1) * dh]
+    if rows is not None:
+        q = q[rows]
+    s = q @ k.T
+    p = torch.exp2(s - s.amax(1, keepdim=True))
+    return (p / p.sum(1, keepdim=True)) @ v
+
+
+@pytest.mark.parametrize("Ts", [[1500] * 8, [5, 127, 128, 129, 1500]], ids=["whisper_large_8x1500", "ragged"])
+def test_attention_f16m_context_rows_against_float64(L, Ts):
+    """ser_attention_v with out_mode = SER_MODE_FP16M at Whisper-large-v3's launch shape (H = 20, dh = 64, B = 8, T = 1 500, pre-scaled q,
+    no table) and on ragged utterances around the 128-query block, against float64 softmax(Q K^T) V of the fp16 hi + lo operands:
+    plane 0 + plane 1 + the scale words decode (tests/f16m_ref.py) to hi, P, Q within fp16's and e4m3's bounds of that reference, and
+    the buffer rows past the last utterance -- planes and scale words -- keep a planted sentinel.  Then the output projection multiplies
+    those rows in FP16M (N = K = 1 280; M = 12 000 and 1 889, neither a multiple of any tile), A scales straight from the attention launch
+    with their leading dimension past M: against the float64 statement of the decoded planes, and against float64 (ctx W^T + b)."""
+    H, dh, EXTRA = 20, 64, 40
+    D = H * dh
+    M, B = sum(Ts), len(Ts)
+    g = torch.Generator().manual_seed(sum(Ts))
+    qkv = torch.randn(M, 3 * D, generator=g)
+    qkv[:, :D] *= 0.3                                                      # logits of a few log2 units: neither flat nor one-hot
+    qkv[:, 2 * D:] *= torch.logspace(-3, 2, D)[None, :]                    # value columns over five decades: the block scales matter
+    hi = qkv.to(torch.float16)
+    lo = (qkv - hi.float()).to(torch.float16)
+    qkv64 = hi.double() + lo.double()                                      # what the kernel multiplies
+    qa = torch.stack([hi, lo]).contiguous().to(DEV)
+    del qkv, hi, lo
+    offs = np.concatenate([[0], np.cumsum(Ts)])
+    foffs = torch.tensor(offs, dtype=torch.int32, device=DEV)
+    R_ = M + EXTRA                                                         # rows of the output buffer; the last EXTRA are never written
+
+    def run(out_m):
+        out = torch.full((2, R_, D), -1, dtype=torch.int16, device=DEV)     # 0xffff: an fp16 NaN, and two e4m3 NaN bytes
+        sc = torch.full((D // 64, R_), -1, dtype=torch.int32, device=DEV)    # code 255: never written (codes are clamped to 1 .. 254)
+        a = L.AttentionArgs()
+        a.qkv, a.ld, a.plane_stride = qa.data_ptr(), 3 * D, M * 3 * D
+        a.q_col, a.k_col, a.v_col, a.B = 0, D, 2 * D, B
+        a.frame_offs, a.max_frames = foffs.data_ptr(), max(Ts)
+        a.out, a.ldo, a.out_plane_stride = out.data_ptr(), D, R_ * D
+        a.H, a.dh, a.scale, a.mode = H, dh, -1.0, FP16X
+        if out_m:
+            a.out_mode, a.out_scale, a.out_scale_ld = FP16M, sc.data_ptr(), R_
+        rc = L.lib.ser_attention_v(C.byref(a), stream())
+        torch.cuda.synchronize()
+        assert rc == 0, L.lib.ser_last_error()
+        return out, sc
+
+    ox, _ = run(False)
+    om, sc = run(True)
+    assert torch.equal(om[0, :M], ox[0, :M])                               # plane 0 is the fp16 copy of the FP16X launch, every row
+    del ox
+    assert bool((om[:, M:] == -1).all()) and bool((sc[:, M:] == -1).all())  # nothing past the last utterance
+    assert not bool((om[0, :M] == -1).any())                               # every row of plane 0 written ...
+    assert not bool((om[1, :M].view(torch.uint8) == 0xFF).any())          # ... every cross-term byte ...
+    assert not bool((sc[:, :M] == -1).any())                               # ... and every scale word
+    om_c, sc_c = om.cpu(), sc.cpu()
+    hi64, P, Q = R.decode(om_c[0, :M].view(torch.float16), om_c[1, :M].contiguous().view(torch.uint8).reshape(M, 2 * D),
+                          sc_c[:, :M].contiguous())
+
+    def blockmax(t):
+        n = t.shape[0]
+        return t.abs().reshape(n, -1, 32).amax(-1, keepdim=True).expand(-1, -1, 32).reshape(n, -1)
+
+    # (utterance, head) pairs with all their rows against float64: every short utterance whole, a sample of the long ones' heads
+    pairs = [(b, h) for b, T in enumerate(Ts) if T < 1500 for h in range(H)]
+    pairs += [(b, h) for b, h in ((0, 0), (1, 7), (3, 13), (B - 1, 3), (B - 1, H - 1)) if b < B and Ts[b] == 1500]
+    for b, h in pairs:
+        r0, r1 = int(offs[b]), int(offs[b + 1])
+        cs = slice(h * dh, (h + 1) * dh)
+        ref = _attn_ref(qkv64, offs, b, h)
+        ghi, gp, gq = hi64[r0:r1, cs], P[r0:r1, cs], Q[r0:r1, cs]
+        slack = blockmax(ref) * 2.0 ** -14                                  # fp32 softmax / accumulation of up to 1 500 keys
+        assert ((ghi - ref).abs() <= ref.abs() * 2.0 ** -11 + 2.0 ** -25 + slack).all(), (b, h)    # (2^-25: half of fp16's subnormal step)
+        assert ((gp - (ref - ghi)).abs() <= blockmax(ref - ghi) * 2.0 ** -3 + slack).all(), (b, h)     # e4m3 of v - hi
+        assert ((gq - ref).abs() <= blockmax(ref) * 2.0 ** -3 + slack).all(), (b, h)                   # e4m3 of v
+        assert float((ghi + gp - ref).abs().max() / ref.abs().max()) < 2.0 ** -13, (b, h)            # what the output projection sees
+
+    # the output projection in FP16M on those rows
+    N = K = D
+    W, bias = rand_mat(N, K, 41, 0.03), rand_mat(1, N, 42)[0]
+    Wd, Ws = device_pack(L, W, True)
+    out = torch.full((M + EXTRA, N), float("nan"), device=DEV)
+    gm = L.GemmArgs()
+    gm.A, gm.a_plane_stride, gm.lda = om.data_ptr(), R_ * D, D
+    gm.W, gm.w_plane_stride = Wd.data_ptr(), N * K
+    gm.M, gm.N, gm.K, gm.groups, gm.mode = M, N, K, 1, FP16M
+    gm.a_scale, gm.a_scale_ld = sc.data_ptr(), R_
+    gm.w_scale, gm.w_scale_ld = Ws.data_ptr(), N
+    bias_d = bias.to(DEV)
+    gm.bias = bias_d.data_ptr()
+    gm.out_f32, gm.ldo_f32 = out.data_ptr(), N
+    L.check(L.lib.ser_gemm(C.byref(gm), stream()), "ser_gemm")
+    torch.cuda.synchronize()
+    assert bool(out[M:].isnan().all())                                    # rows past M untouched
+    got = out[:M].cpu().double()
+    assert bool(torch.isfinite(got).all())
+    # sampled rows: the first and last of every utterance, the last 300 rows (the partial last M tile of every tile shape), a spread
+    rows = sorted(set([int(o) for o in offs[:-1]] + [int(o) - 1 for o in offs[1:]] + list(range(max(0, M - 300), M))
+                      + list(range(0, M, 97))))
+    ri = torch.tensor(rows)
+    wh, wp, wq = R.decode(*planes_of(Wd, Ws))
+    stated = hi64[ri] @ wh.T + P[ri] @ wp.T + Q[ri] @ wq.T + bias.double()[None, :]
+    assert float((got[ri] - stated).abs().max()) <= 3e-6 * float(stated.abs().max())
+    # against float64 end to end: the context rows of the sampled rows over every head, times the fp32 weights
+    ctx = torch.zeros(len(rows), D, dtype=torch.float64)
+    ub = np.searchsorted(offs, np.array(rows), side="right") - 1
+    for b in sorted(set(ub.tolist())):
+        sel = np.nonzero(ub == b)[0]
+        local = torch.tensor(np.array(rows)[sel] - int(offs[b]))
+        for h in range(H):
+            ctx[torch.tensor(sel), h * dh:(h + 1) * dh] = _attn_ref(qkv64, offs, b, h, rows=local)
+    exact = ctx @ W.double().T + bias.double()[None, :]
+    rms = float((exact - bias.double()[None, :]).pow(2).mean().sqrt())
+    err = float((got[ri] - exact).pow(2).mean().sqrt()) / rms
+    print(f"FP16M context rows -> output projection: {err:.2e} rms of rms against float64")
+    assert err < 4e-5, err

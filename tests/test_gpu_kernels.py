@@ -1180,3 +1180,83 @@ def test_deberta_dense_bias_attention(L, mode, T):
     assert bool(torch.isfinite(bias).all())
     err = (act_value(out).cpu().double() - ref).abs().max().item()
     assert err < mode_tol(mode, 3e-2, 2e-4), err
+
+
+@pytest.mark.parametrize("Cn", [80, 128, 36])                 # Whisper's mel counts, and a channel count that is a multiple of 4 but not of 8
+@pytest.mark.parametrize("mode", [1, 2, 4])                   # bf16, bf16 hi + lo (fp32x), fp16 hi + lo (fp16x)
+def test_pack_act_channels_last_against_numpy(L, mode, Cn):
+    """ser_pack_act_v (OP_PACK_ACT, the first command of Whisper's list): [B, C, T] fp32 -> channels-last operand rows, utterance b at rows
+    b (T + 2 halo) .., its halo rows written as zeros by the kernel itself (planted garbage before the launch), columns C .. ldo and
+    rows past the last utterance untouched; the planes bit for bit those of numpy's transpose rounded to nearest even, and the range
+    guard's bits (fp16 planes only) those of the largest |x|.  Modes it does not write are refused with the buffer untouched."""
+    B, T, halo, EXTRA = 3, 3000, 1, 5
+    ldo, Tp = Cn + 4, T + 2 * halo
+    g = torch.Generator().manual_seed(Cn + mode)
+    x = torch.randn(B, Cn, T, generator=g) * torch.logspace(-4, 1, T)[None, None, :]
+    x[1, Cn - 1, T - 1] = 4.0e4                                          # past half of fp16's range: guard bit 1
+    planes, dt = (1, torch.bfloat16) if mode == 1 else ((2, torch.bfloat16) if mode == 2 else (2, torch.float16))
+    xt = x.permute(0, 2, 1)                                              # [B, T, C]
+    hi = xt.to(dt)
+    lo = (xt - hi.float()).to(dt)
+    want = torch.zeros(planes, B, Tp, Cn, dtype=dt)
+    want[0, :, halo:halo + T] = hi
+    if planes == 2:
+        want[1, :, halo:halo + T] = lo
+    xd = x.to(DEV).contiguous()
+    R_ = B * Tp + EXTRA
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+
+    def launch(m):
+        out = torch.full((planes, R_, ldo), -3, dtype=torch.int16, device=DEV)      # planted: garbage halo rows, pitch tail, spare rows
+        a = L.PackActArgs()
+        a.x, a.out, a.ldo, a.out_plane_stride = xd.data_ptr(), out.data_ptr(), ldo, R_ * ldo
+        a.B, a.C, a.T, a.halo, a.mode, a.range_flag = B, Cn, T, halo, m, flag.data_ptr()
+        rc = L.lib.ser_pack_act_v(C.byref(a), stream())
+        torch.cuda.synchronize()
+        return rc, out.cpu()
+
+    rc, out = launch(mode)
+    assert rc == 0, L.lib.ser_last_error()
+    got = out[:, :B * Tp, :Cn].reshape(planes, B, Tp, Cn)
+    assert torch.equal(got, want.view(torch.int16))                    # bit patterns: a -0.0 for +0.0 is a difference too
+    assert bool((out[:, :, Cn:] == -3).all()) and bool((out[:, B * Tp:] == -3).all())
+    assert int(flag.item()) == (2 if dt == torch.float16 else 0)
+    x[1, Cn - 1, T - 1] = 7.0e4                                          # beyond fp16's range: both bits (saturated in the fp16 plane)
+    xd.copy_(x.to(DEV))
+    flag.zero_()
+    rc, out = launch(mode)
+    assert rc == 0 and int(flag.item()) == (3 if dt == torch.float16 else 0)
+    for bad in (3, 5, 6):                                                # FP16, FP16Q, FP16M: not written by this kernel
+        flag.zero_()
+        rc, out = launch(bad)
+        assert rc < 0 and f"ser_pack_act: mode {bad} ".encode() in L.lib.ser_last_error()
+        assert bool((out == -3).all()) and int(flag.item()) == 0
+
+
+@pytest.mark.parametrize("mode", [2, 4])                       # the 3-product modes: bf16 hi + lo (fp32x), fp16 hi + lo (fp16x)
+def test_gemm_stat_out_writes_every_slot_it_covers(L, mode):
+    """Row partials (stat_out) of the 3-product 256x256 tile, whose waves cover 128 columns each -- what the output projection of Whisper-large
+    runs on at M = 12 000, N = 1 280: every 64-column slot of the N columns is written (the wave's partials in the first of its two slots, a
+    zero in the second) and the slots add up to the row sums of the values written.  Each slot starts as a planted NaN; the slots past the
+    N columns keep it.  A slot the launch left alone handed the consumer's LayerNorm whatever an earlier launch had put there: with the
+    FP16M context rows (SER_F16M_OUT_M=1) the FP16M output projections of the later layers fill it, and from the second forward on the
+    first layers' LayerNorm read it (Whisper-large-v3, "f16mf": 0.57 from the oracle)."""
+    M, N, K, G = 12000, 1280, 128, 22                              # 235 tiles of 256 x 256: the tile the launcher picks; 2 padding slots
+    g = torch.Generator().manual_seed(90 + mode)
+    A, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)
+    res = torch.randn(M, N, generator=g) + 0.5
+
+    def planes(x):
+        if mode == 2:
+            return to_act(x, 2)
+        h = x.half()
+        return torch.stack([h, (x - h.float()).half()]).contiguous().to(DEV)
+    stat = torch.full((M, G, 2), float("nan"), device=DEV)
+    out, _ = run_gemm(L, planes(A), planes(W), M, N, K, mode, residual=res.to(DEV), ldr=N, stat_out=stat)
+    st = stat.cpu().double()
+    assert not bool(st[:, :N // 64].isnan().any())                 # every slot of the N columns written ...
+    assert bool(st[:, N // 64:].isnan().all())                     # ... none past them
+    x = out.cpu().double()
+    s = st[:, :N // 64].sum(1)
+    assert float(((s[:, 0] - x.sum(1)).abs() / x.abs().sum(1)).max()) < 1e-5
+    assert float(((s[:, 1] - (x * x).sum(1)).abs() / (x * x).sum(1)).max()) < 1e-5
