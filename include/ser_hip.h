@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SER_ABI_VERSION 16
+#define SER_ABI_VERSION 17
 
 #define SER_MODE_BF16  1   /* act tensors have 1 plane; GEMMs do 1 bf16 MFMA product   */
 #define SER_MODE_FP32X 2   /* act tensors have 2 planes; GEMMs do hi*hi + lo*hi + hi*lo */
@@ -250,10 +250,16 @@ int ser_attention(const void* qkv, int64_t ld, int64_t plane_stride, int q_col, 
 
 /* next row 8f-1 (text side): RoBERTa embeddings word[id] + position[cumsum(non-pad)] + token_type[0] -> LayerNorm
  * (HF modeling_roberta.py:56-155; call site preprocessing/preprocess_roberta.py:47-57).  ids: [B,T] int32.
- * mode (here and in ser_embed_ln_masked / ser_pack_rows / ser_zero_padded_rows): the format of the operand copy, BF16 / FP32X / FP16X. */
+ * mode (here and in ser_embed_ln_masked / ser_pack_rows / ser_zero_padded_rows): the format of the operand copy, BF16 / FP32X / FP16X.
+ * The *_flagged forms (here, of ser_embed_ln_masked and of ser_pack_rows; ABI 17) take range_flag just before stream: the fp16 range
+ * guard of the values stored to out_act in FP16X (see ser_gemm_args.range_flag), may be NULL.  The unsuffixed forms keep their
+ * arguments and run the same launch with range_flag = NULL. */
 int ser_embed_ln(const int32_t* ids, const float* word_emb, const float* pos_emb, const float* type_emb,
                  const float* ln_g, const float* ln_b, float eps, float* out_f32, void* out_act,
                  int64_t out_plane_stride, int mode, int B, int T, int D, int pad_id, void* stream);
+int ser_embed_ln_flagged(const int32_t* ids, const float* word_emb, const float* pos_emb, const float* type_emb,
+                         const float* ln_g, const float* ln_b, float eps, float* out_f32, void* out_act,
+                         int64_t out_plane_stride, int mode, int B, int T, int D, int pad_id, uint32_t* range_flag, void* stream);
 
 /* K13 Whisper log-mel front end (HF feature_extraction_whisper.py:135-169): packed fp32
  * samples -> [B, n_mels, 3000] fp32 (zero-pad/truncate to 480000, reflect pad, Hann,
@@ -287,13 +293,19 @@ int ser_pack_act(const float* x, int B, int C, int T, int halo, void* out, int64
 int ser_embed_ln_masked(const int32_t* ids, const float* word_emb, const float* ln_g, const float* ln_b, float eps,
                         const int32_t* key_lens, float* out_f32, void* out_act, int64_t out_plane_stride,
                         int mode, int B, int T, int D, void* stream);
+int ser_embed_ln_masked_flagged(const int32_t* ids, const float* word_emb, const float* ln_g, const float* ln_b, float eps,
+                                const int32_t* key_lens, float* out_f32, void* out_act, int64_t out_plane_stride,
+                                int mode, int B, int T, int D, uint32_t* range_flag, void* stream);
 /* ConvLayer of deberta-v2-xlarge / xxlarge (HF modeling_deberta_v2.py ConvLayer; the checkpoint the reference's README runs
  * preprocess_deroberta.py with, README.md:66): Conv1d(D, D, 3) over the token axis of the embedding output, activation, + layer
  * 0's output, LayerNorm, padded rows zero.  The conv is ser_gemm's implicit-conv map over the halo'd copy ser_pack_rows makes
  * (row b*(T+2*halo) + halo + t of `out` = split(x[b*T + t]); the halo rows are the caller's zeros); ser_zero_padded_rows zeroes
- * rows t >= key_lens[b] of an fp32 matrix and / or its act copy. */
+ * rows t >= key_lens[b] of an fp32 matrix and / or its act copy.  ser_embed_ln_masked's padded rows store zeros and do not count for
+ * the range_flag of its _flagged form; ser_zero_padded_rows stores only zeros and has no such form. */
 int ser_pack_rows(const float* x, int64_t ldx, int B, int T, int D, int halo, void* out, int64_t ldo, int64_t out_plane_stride,
                   int mode, void* stream);
+int ser_pack_rows_flagged(const float* x, int64_t ldx, int B, int T, int D, int halo, void* out, int64_t ldo, int64_t out_plane_stride,
+                          int mode, uint32_t* range_flag, void* stream);
 int ser_zero_padded_rows(float* x, int64_t ldx, void* act, int64_t lda, int64_t plane_stride, int mode, const int32_t* key_lens,
                          int B, int T, int D, void* stream);
 

@@ -26,7 +26,7 @@ ACT_GELU = 1
 WS_LOGMEL = 1
 WS_WAVE_FRAMES = 2
 WS_GN_STATS = 3
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_void_p, c_int, c_i64, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -189,6 +189,8 @@ _SIGNATURES = {
     "ser_attention_v": (c_int, [c_void_p, c_void_p]),
     "ser_embed_ln": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                              c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ser_embed_ln_flagged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                     c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ser_logmel_init": (c_int, [c_void_p, c_int, c_void_p]),
     "ser_logmel_whisper": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ser_pack_act": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_i64, c_int, c_void_p]),
@@ -196,9 +198,12 @@ _SIGNATURES = {
     "ser_split_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p]),
     "ser_embed_ln_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_i64,
                                     c_int, c_int, c_int, c_int, c_void_p]),
+    "ser_embed_ln_masked_flagged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_i64,
+                                            c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ser_deberta_attention": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_pack_rows": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "ser_pack_rows_flagged": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p]),
     "ser_zero_padded_rows": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ser_deberta_bias": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int,
                                  c_float, c_void_p]),

@@ -9,12 +9,14 @@
 #include "ser_common.h"
 
 // ---------------------------------------------------------------------------------------------- embeddings
+// f16 planes: the stored values are folded into the fp16 range guard (rflag, may be NULL); a padded row stores zeros, so whatever its
+// token's embedding row holds never counts.
 template <int MODE>
 __global__ __launch_bounds__(256) void embed_ln_masked_kernel(const int32_t* __restrict__ ids, const float* __restrict__ wemb,
                                                               const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                               const int32_t* __restrict__ key_lens, float* __restrict__ of,
                                                               unsigned short* __restrict__ oa, int64_t plane, int T, int D,
-                                                              int rows) {
+                                                              int rows, uint32_t* __restrict__ rflag) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);                 // one wave per token
     if (row >= rows) return;
@@ -22,7 +24,7 @@ __global__ __launch_bounds__(256) void embed_ln_masked_kernel(const int32_t* __r
     const bool real = t < key_lens[seq];
     const float* w = wemb + (int64_t)ids[row] * D;
     f32x4 v[8];
-    float s = 0.f;
+    float s = 0.f, ramax = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = i * 256 + lane * 4;
@@ -52,13 +54,15 @@ __global__ __launch_bounds__(256) void embed_ln_masked_kernel(const int32_t* __r
             for (int j = 0; j < 4; ++j) y[j] = real ? (v[i][j] - mean) * rstd * gg[j] + bb[j] : 0.f;   // embeddings * mask
             if (of) *(f32x4*)(of + (int64_t)row * D + c) = y;
             if (oa) store_act4<MODE>(oa + (int64_t)row * D + c, plane, y[0], y[1], y[2], y[3]);
+            if constexpr (mode_traits<MODE>::f16) { if (oa) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); } }
         }
     }
+    if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
 }
 
-extern "C" int ser_embed_ln_masked(const int32_t* ids, const float* word_emb, const float* ln_g, const float* ln_b, float eps,
-                                   const int32_t* key_lens, float* out_f32, void* out_act, int64_t out_plane_stride,
-                                   int mode, int B, int T, int D, void* stream) {
+extern "C" int ser_embed_ln_masked_flagged(const int32_t* ids, const float* word_emb, const float* ln_g, const float* ln_b, float eps,
+                                           const int32_t* key_lens, float* out_f32, void* out_act, int64_t out_plane_stride,
+                                           int mode, int B, int T, int D, uint32_t* range_flag, void* stream) {
     if (!ids || !word_emb || !ln_g || !ln_b || !key_lens || (!out_f32 && !out_act))
         return ser_fail(-1, "ser_embed_ln_masked: null pointer");
     if (B <= 0 || T <= 0 || D % 4 || D > 2048) return ser_fail(-2, "ser_embed_ln_masked: bad B/T/D");
@@ -67,14 +71,21 @@ extern "C" int ser_embed_ln_masked(const int32_t* ids, const float* word_emb, co
     dim3 grid((rows + 3) / 4), block(256);
     if (mode == SER_MODE_FP32X)
         hipLaunchKernelGGL(embed_ln_masked_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b,
-                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows);
+                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
     else if (mode == SER_MODE_FP16X)
         hipLaunchKernelGGL(embed_ln_masked_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b,
-                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows);
+                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
     else
         hipLaunchKernelGGL(embed_ln_masked_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b,
-                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows);
+                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
     return ser_check_launch("ser_embed_ln_masked");
+}
+
+extern "C" int ser_embed_ln_masked(const int32_t* ids, const float* word_emb, const float* ln_g, const float* ln_b, float eps,
+                                   const int32_t* key_lens, float* out_f32, void* out_act, int64_t out_plane_stride,
+                                   int mode, int B, int T, int D, void* stream) {
+    return ser_embed_ln_masked_flagged(ids, word_emb, ln_g, ln_b, eps, key_lens, out_f32, out_act, out_plane_stride, mode, B, T, D,
+                                       nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- attention
@@ -167,10 +178,12 @@ __global__ __launch_bounds__(128) void deberta_attention_kernel(
 // DebertaV2Encoder runs a token-axis Conv1d(D, D, 3) over the EMBEDDING output after encoder layer 0 (HF
 // modeling_deberta_v2.py ConvLayer).  The conv itself is ser_gemm's implicit-conv map over a zero-halo'd copy of the rows
 // (one zero row before and after every sequence), GELU and the residual ride in its epilogue, ser_layernorm follows; these two
-// row kernels provide the halo'd operand copy and the final "padded rows are zero" of that layer.
+// row kernels provide the halo'd operand copy and the final "padded rows are zero" of that layer.  pack_rows reports the values it stores
+// to f16 planes to the fp16 range guard (rflag, may be NULL); zero_padded_rows stores only zeros and takes no word.
 template <int MODE>
 __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ x, int64_t ldx, int T, int D, int halo,
-                                                        unsigned short* __restrict__ o, int64_t ldo, int64_t plane, int64_t total) {
+                                                        unsigned short* __restrict__ o, int64_t ldo, int64_t plane, int64_t total,
+                                                        uint32_t* __restrict__ rflag) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;                    // one thread per 4 columns
     if (i >= total) return;
     const int c4 = (int)(i % (D / 4)) * 4;
@@ -179,25 +192,31 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict_
     const int t = (int)(row - b * T);
     const f32x4 v = *(const f32x4*)(x + row * ldx + c4);
     store_act4<MODE>(o + (b * (T + 2 * halo) + halo + t) * ldo + c4, plane, v[0], v[1], v[2], v[3]);
+    if constexpr (mode_traits<MODE>::f16) range_report(rflag, range_fold(range_fold(range_fold(fabsf(v[0]), v[1]), v[2]), v[3]));
 }
 
-extern "C" int ser_pack_rows(const float* x, int64_t ldx, int B, int T, int D, int halo, void* out, int64_t ldo,
-                             int64_t out_plane_stride, int mode, void* stream) {
+extern "C" int ser_pack_rows_flagged(const float* x, int64_t ldx, int B, int T, int D, int halo, void* out, int64_t ldo,
+                                     int64_t out_plane_stride, int mode, uint32_t* range_flag, void* stream) {
     if (!x || !out || B <= 0 || T <= 0 || D <= 0 || (D % 4) || halo < 0 || (ldx % 4) || (ldo % 4))
         return ser_fail(-1, "ser_pack_rows: bad arguments");
     const int64_t total = (int64_t)B * T * (D / 4);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (mode == SER_MODE_FP32X)
         hipLaunchKernelGGL(pack_rows_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo,
-                           (unsigned short*)out, ldo, out_plane_stride, total);
+                           (unsigned short*)out, ldo, out_plane_stride, total, range_flag);
     else if (mode == SER_MODE_BF16)
         hipLaunchKernelGGL(pack_rows_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo,
-                           (unsigned short*)out, ldo, out_plane_stride, total);
+                           (unsigned short*)out, ldo, out_plane_stride, total, range_flag);
     else if (mode == SER_MODE_FP16X)
         hipLaunchKernelGGL(pack_rows_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo,
-                           (unsigned short*)out, ldo, out_plane_stride, total);
+                           (unsigned short*)out, ldo, out_plane_stride, total, range_flag);
     else return ser_fail(-2, "ser_pack_rows: bad mode %d", mode);
     return ser_check_launch("ser_pack_rows");
+}
+
+extern "C" int ser_pack_rows(const float* x, int64_t ldx, int B, int T, int D, int halo, void* out, int64_t ldo,
+                             int64_t out_plane_stride, int mode, void* stream) {
+    return ser_pack_rows_flagged(x, ldx, B, T, D, halo, out, ldo, out_plane_stride, mode, nullptr, stream);
 }
 
 template <int MODE>

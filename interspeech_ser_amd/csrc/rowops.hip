@@ -551,12 +551,13 @@ extern "C" int ser_row_center(const float* x, int64_t ldx, void* out_act, int64_
 // ------------------------------------------------------------------ text embeddings (8f-1)
 // RoBERTa embeddings: word[id] + position[pos] + token_type[0] -> LayerNorm (HF modeling_roberta.py:56-120).
 // Wave per token; position ids = cumsum(non-pad)*non-pad + pad_id, computed per sequence with a wave scan.
+// f16 planes: the stored values are folded into the fp16 range guard (rflag, may be NULL), as layernorm_kernel does.
 template <int MODE>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids, const float* __restrict__ wemb,
                                                        const float* __restrict__ pemb, const float* __restrict__ temb,
                                                        const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                        float* __restrict__ of, unsigned short* __restrict__ oa, int64_t plane,
-                                                       int T, int D, int pad_id, int rows) {
+                                                       int T, int D, int pad_id, int rows, uint32_t* __restrict__ rflag) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -570,7 +571,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
     const float* w = wemb + (int64_t)id * D;
     const float* pe = pemb + (int64_t)pos * D;
     f32x4 v[8];
-    float s = 0.f;
+    float s = 0.f, ramax = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = i * 256 + lane * 4;
@@ -601,13 +602,16 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
             for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * gg[j] + bb[j];
             if (of) *(f32x4*)(of + (int64_t)row * D + c) = y;
             if (oa) store_act4<MODE>(oa + (int64_t)row * D + c, plane, y[0], y[1], y[2], y[3]);
+            if constexpr (mode_traits<MODE>::f16) { if (oa) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); } }
         }
     }
+    if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
 }
 
-extern "C" int ser_embed_ln(const int32_t* ids, const float* word_emb, const float* pos_emb, const float* type_emb,
-                            const float* ln_g, const float* ln_b, float eps, float* out_f32, void* out_act,
-                            int64_t out_plane_stride, int mode, int B, int T, int D, int pad_id, void* stream) {
+extern "C" int ser_embed_ln_flagged(const int32_t* ids, const float* word_emb, const float* pos_emb, const float* type_emb,
+                                    const float* ln_g, const float* ln_b, float eps, float* out_f32, void* out_act,
+                                    int64_t out_plane_stride, int mode, int B, int T, int D, int pad_id, uint32_t* range_flag,
+                                    void* stream) {
     if (!ids || !word_emb || !pos_emb || !type_emb || !ln_g || !ln_b || (!out_f32 && !out_act))
         return ser_fail(-1, "ser_embed_ln: null pointer");
     if (B <= 0 || T <= 0 || D % 4 || D > 2048) return ser_fail(-2, "ser_embed_ln: bad B/T/D");
@@ -616,14 +620,21 @@ extern "C" int ser_embed_ln(const int32_t* ids, const float* word_emb, const flo
     dim3 grid((rows + 3) / 4), block(256);
     if (mode == SER_MODE_FP32X)
         hipLaunchKernelGGL(embed_ln_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb,
-                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows);
+                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
     else if (mode == SER_MODE_FP16X)
         hipLaunchKernelGGL(embed_ln_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb,
-                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows);
+                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
     else
         hipLaunchKernelGGL(embed_ln_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb,
-                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows);
+                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
     return ser_check_launch("ser_embed_ln");
+}
+
+extern "C" int ser_embed_ln(const int32_t* ids, const float* word_emb, const float* pos_emb, const float* type_emb,
+                            const float* ln_g, const float* ln_b, float eps, float* out_f32, void* out_act,
+                            int64_t out_plane_stride, int mode, int B, int T, int D, int pad_id, void* stream) {
+    return ser_embed_ln_flagged(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, out_f32, out_act, out_plane_stride, mode, B, T, D,
+                                pad_id, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------ K8a

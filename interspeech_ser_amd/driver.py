@@ -576,13 +576,19 @@ class TextExtractor:
         from .engine import build_encoder
         self.enc = build_encoder(geo, state_dict, device, mode)      # RoBERTa (TextEncoder) or DeBERTa-v3 (DebertaEncoder)
         self.tokenize, self.average = tokenize, average
+        self._range_warned = False
 
     def extract(self, texts: Sequence[str]) -> List[torch.Tensor]:
         from .engine import mean_last4
         ids, mask = self.tokenize(list(texts))
         hs = self.enc.forward(ids, mask)
-        if hs.take_range_bits() & 1:                                 # fp16 operand planes saturate: fail the batch instead (speech driver's rule)
+        bits = hs.take_range_bits()
+        if bits & 1:                                                 # fp16 operand planes saturate: fail the batch instead (speech driver's rule)
             raise ValueError("a value beyond the fp16 operand range of --mode f16x (65504) was met inside the forward: re-run with --mode fp32x")
+        if bits & 2 and not self._range_warned:                      # beyond half of it: warn once per run, as the speech driver does
+            self._range_warned = True
+            print(f"WARNING: values within a factor 2 of the fp16 operand range of --mode {self.enc.mode_name} (65504); "
+                  f"--mode fp32x has fp32 range")
         sel = mean_last4(hs) if self.average else hs.states[-1]      # .last_hidden_state
         host = sel.to("cpu")
         return [host[hs.frame_offs[b]: hs.frame_offs[b + 1]] for b in range(len(texts))]

@@ -1572,10 +1572,10 @@ class TextEncoder(_TextEncoderBase):
         M, D = pl["M"], geo.hidden
         states = pl["states"]
         xa = pl["xa"]
-        check(lib.ser_embed_ln(ids.data_ptr(), self.wemb.data_ptr(), self.pemb.data_ptr(), self.temb.data_ptr(),
-                               self.emb_ln[0].data_ptr(), self.emb_ln[1].data_ptr(), float(geo.layer_norm_eps),
-                               states[0].data_ptr(), xa.ptr, xa.plane_stride, self.mode, B, T, D, geo.pad_token_id,
-                               _stream()), "ser_embed_ln")
+        check(lib.ser_embed_ln_flagged(ids.data_ptr(), self.wemb.data_ptr(), self.pemb.data_ptr(), self.temb.data_ptr(),
+                                       self.emb_ln[0].data_ptr(), self.emb_ln[1].data_ptr(), float(geo.layer_norm_eps),
+                                       states[0].data_ptr(), xa.ptr, xa.plane_stride, self.mode, B, T, D, geo.pad_token_id,
+                                       self._flag, _stream()), "ser_embed_ln_flagged")
         scale = geo.head_dim ** -0.5 * 1.4426950408889634
         for i, lay in enumerate(self.layers):
             self._gemm(xa, lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
@@ -1688,9 +1688,9 @@ class DebertaEncoder(_TextEncoderBase):
         Nr = win["Nr"]
         states, xa, qkv = pl["states"], pl["xa"], pl["qkv"]
         st = self._s()
-        check(lib.ser_embed_ln_masked(ids.data_ptr(), self.wemb.data_ptr(), self.emb_ln[0].data_ptr(), self.emb_ln[1].data_ptr(),
-                                      float(geo.layer_norm_eps), key_lens.data_ptr(), states[0].data_ptr(), xa.ptr, xa.plane_stride,
-                                      self.mode, B, T, D, st), "ser_embed_ln_masked")
+        check(lib.ser_embed_ln_masked_flagged(ids.data_ptr(), self.wemb.data_ptr(), self.emb_ln[0].data_ptr(), self.emb_ln[1].data_ptr(),
+                                              float(geo.layer_norm_eps), key_lens.data_ptr(), states[0].data_ptr(), xa.ptr,
+                                              xa.plane_stride, self.mode, B, T, D, self._flag, st), "ser_embed_ln_masked_flagged")
         # scores run in the exp2 domain: q leaves the projection multiplied by (3 dh)^-0.5 * log2(e), so the content term and the
         # content -> position term (a product with q) arrive scaled; the position -> content term (a product with k) is scaled
         # by ser_deberta_bias.  (HF: (Qc Kc^T + c2p + p2c) / sqrt(3 dh), modeling_deberta_v2.py DisentangledSelfAttention.)
@@ -1714,7 +1714,8 @@ class DebertaEncoder(_TextEncoderBase):
                 # ConvLayer: LN(layer-0 output + gelu(Conv1d_k3(embeddings))) with padded rows zero.  (HF zeroes the padded
                 # rows of the conv output before the activation too; gelu(0) = 0 and those rows are zeroed at the end anyway.)
                 ci = pl["conv_in"]
-                check(lib.ser_pack_rows(states[0].data_ptr(), D, B, T, D, 1, ci.ptr, D, ci.plane_stride, self.mode, st), "ser_pack_rows")
+                check(lib.ser_pack_rows_flagged(states[0].data_ptr(), D, B, T, D, 1, ci.ptr, D, ci.plane_stride, self.mode,
+                                                self._flag, st), "ser_pack_rows_flagged")
                 self._gemm(ci, self.text_conv["lin"], M, a_rowoff=pl["conv_rowoff"], kc=D, ldj=D, K=3 * D, act=_lib.ACT_GELU,
                            residual=states[1], ldr=D, out_f32=pl["tmp"], ldo_f32=D)
                 self._layernorm(pl["tmp"], D, self.text_conv["ln"], M, D, out_f32=states[1], out_act=xa)

@@ -108,6 +108,18 @@ def test_deberta_launchers_validate_arguments(built_library):
     assert b"ser_deberta_attention" in _lib.lib.ser_last_error()
 
 
+def test_flagged_text_launchers_validate_arguments(built_library):
+    """The *_flagged forms of the text row kernels (ABI 17: the same launches with the fp16 range-guard word) validate like the forms
+    without it, before any launch (no GPU needed)."""
+    from interspeech_ser_amd import _lib
+    assert _lib.lib.ser_embed_ln_flagged(None, None, None, None, None, None, 1e-5, None, None, 0, 1, 1, 8, 64, 1, None, None) < 0
+    assert b"ser_embed_ln: null pointer" in _lib.lib.ser_last_error()
+    assert _lib.lib.ser_embed_ln_masked_flagged(None, None, None, None, 1e-7, None, None, None, 0, 1, 1, 8, 64, None, None) < 0
+    assert b"ser_embed_ln_masked: null pointer" in _lib.lib.ser_last_error()
+    assert _lib.lib.ser_pack_rows_flagged(None, 64, 1, 8, 64, 1, None, 64, 0, 1, None, None) < 0
+    assert b"ser_pack_rows: bad arguments" in _lib.lib.ser_last_error()
+
+
 def test_deberta_bucket_map_of_the_host_equals_the_oracle(built_library):
     """The product's host-side log-bucket map (engine) and the oracle's are written separately; they must agree on every
     distance a 128-token sequence can produce, for the v3 setting (256 buckets, 512 positions) and the fixture's."""

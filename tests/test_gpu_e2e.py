@@ -440,6 +440,68 @@ def test_text_driver_fp16_range_guard(tmp_path, capsys):
         C._REGISTRY.pop("tiny-text-range")
 
 
+def _text_driver_with_embedding_bias(tmp_path, geo_name, bias, mode):
+    """Run the text driver of geometry ``geo_name`` on two texts with ``embeddings.LayerNorm.bias[3] = bias`` in ``--mode mode``;
+    returns (driver log, files written)."""
+    import pandas as pd
+    from safetensors.torch import save_file
+    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd import driver
+    from interspeech_ser_amd.weights import synthetic_state_dict
+    geo = getattr(C, geo_name)
+    sd = synthetic_state_dict(geo, 5)
+    sd["embeddings.LayerNorm.bias"][3] = bias
+    ck = tmp_path / f"emb_bias_{geo_name}.safetensors"
+    save_file({k: v.contiguous() for k, v in sd.items()}, str(ck))
+    csv = tmp_path / "t.csv"
+    pd.DataFrame({"FileName": ["a.wav", "b.wav"], "transcription": ["hello there", "one two three four"]}).to_csv(csv, index=False)
+
+    def fake_tokenize(texts):
+        ids = torch.full((len(texts), 16), geo.pad_token_id, dtype=torch.int64)
+        mask = torch.zeros((len(texts), 16), dtype=torch.int64)
+        for i, t in enumerate(texts):
+            toks = [0] + [3 + (len(w) * 7 + j) % (geo.vocab_size - 4) for j, w in enumerate(t.split())] + [2]
+            ids[i, : len(toks)] = torch.tensor(toks)
+            mask[i, : len(toks)] = 1
+        return ids, mask
+
+    run = driver.run_deberta if geo.family == C.FAMILY_DEBERTA else driver.run_roberta
+    out = tmp_path / f"{geo_name}_{mode}"
+    C._REGISTRY["tiny-text-emb-bias"] = geo
+    try:
+        assert run(["--roberta_type", "tiny-text-emb-bias", "--df_path", str(csv), "--save_path", str(out), "--checkpoint", str(ck),
+                    "--max_len", "16", "--mode", mode], tokenize=fake_tokenize) == 0
+    finally:
+        C._REGISTRY.pop("tiny-text-emb-bias")
+    return out, sorted(os.listdir(out))
+
+
+@pytest.mark.parametrize("geo_name", ["TINY_ROBERTA", "TINY_DEBERTA_CONV"])
+def test_text_driver_fp16_range_guard_embedding_bias(tmp_path, capsys, geo_name):
+    """A checkpoint whose EMBEDDING LayerNorm leaves fp16's range (bias 2e5 in one channel): hidden_states[0] is right in fp32, but its
+    f16x operand copy (the embedding kernel's; DeBERTa's ConvLayer packs the same row again) would be clipped, and every launch after it
+    sees only small values -- the QKV projection reads the clipped copy, the LayerNorms re-bound the rest.  So the embedding kernels
+    themselves must report: f16x fails both texts with the way out and writes nothing; fp32x writes both."""
+    out, files = _text_driver_with_embedding_bias(tmp_path, geo_name, 2.0e5, "f16x")
+    log = capsys.readouterr().out
+    assert log.count("Failed to process") == 2 and "--mode fp32x" in log, log
+    assert files == []
+    out, files = _text_driver_with_embedding_bias(tmp_path, geo_name, 2.0e5, "fp32x")
+    log = capsys.readouterr().out
+    assert "Failed to process" not in log and files == ["a.pt", "b.pt"], log
+
+
+@pytest.mark.parametrize("geo_name", ["TINY_ROBERTA", "TINY_DEBERTA_CONV"])
+def test_text_driver_warns_once_at_half_range(tmp_path, capsys, geo_name):
+    """Embedding bias 4e4: beyond half of fp16's range, inside it.  The text drivers warn once (as the speech driver does) and write the
+    files."""
+    out, files = _text_driver_with_embedding_bias(tmp_path, geo_name, 4.0e4, "f16x")
+    log = capsys.readouterr().out
+    assert "Failed to process" not in log and files == ["a.pt", "b.pt"], log
+    assert sum(line.startswith("WARNING") for line in log.splitlines()) == 1, log
+    assert "--mode fp32x" in log
+
+
 def test_roberta_driver_with_the_reference_tokenizer_call(tmp_path, capsys):
     """The text driver's DEFAULT tokenizer path -- HF RobertaTokenizer.from_pretrained(<local files>) called like the reference does
     (preprocess_roberta.py:45-54: padding="max_length", truncation=True, max_length=80) -- end to end through ``--tokenizer_path``:

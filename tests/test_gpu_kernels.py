@@ -25,12 +25,13 @@ def stream():
 
 
 def mode_tol(mode, bf16, fp32x):
-    """bound per numerics mode: fp16 operands (mode 3) round 8x finer than bf16; gate at 1/2.5 of the bf16 bound."""
-    return {1: bf16, 2: fp32x, 3: max(bf16 / 2.5, fp32x)}[mode]
+    """bound per numerics mode: fp16 operands (mode 3) round 8x finer than bf16; gate at 1/2.5 of the bf16 bound.  fp16 hi + lo (mode 4)
+    keeps 22 significand bits against fp32x's 16: it takes fp32x's bound."""
+    return {1: bf16, 2: fp32x, 3: max(bf16 / 2.5, fp32x), 4: fp32x}[mode]
 
 
 def act_dtype(mode):
-    return torch.float16 if mode == 3 else torch.bfloat16
+    return torch.float16 if mode in (3, 4) else torch.bfloat16
 
 
 def to_act(x, mode):
@@ -46,7 +47,8 @@ def to_act(x, mode):
 
 
 def act_value(t):
-    return t.float().sum(0)
+    """operand planes [P, ...] -> the value they hold, summed in float64 (an fp16 hi + lo pair need not add exactly in fp32)"""
+    return t.double().sum(0)
 
 
 def run_gemm(L, A_act, W_act, M, N, K, mode, **kw):
@@ -419,7 +421,7 @@ def test_gemm_rowmap_and_rowmod(L):
                          want_act=True, out_act_rows=2 * M + 1, out_rowmap=rowmap)
     ref = A @ W.T + pos.repeat(M // mod, 1)
     assert torch.equal(out.cpu(), ref)
-    got = act_value(oact).cpu()
+    got = act_value(oact).cpu().float()
     assert torch.equal(got[1::2][:M], ref.to(torch.bfloat16).float())
     assert torch.count_nonzero(got[0::2]) == 0
 
@@ -430,9 +432,11 @@ def test_gemm_rejects_bad_shapes(L):
     assert b"null" in L.lib.ser_last_error()
 
 
-@pytest.mark.parametrize("mode", [1, 2])
-@pytest.mark.parametrize("D,gelu", [(512, True), (1024, False), (1920, False), (64, True)])
+@pytest.mark.parametrize("mode", [1, 2, 3, 4])
+@pytest.mark.parametrize("D,gelu", [(512, True), (1024, False), (1920, False), (64, True), (1536, False)])
 def test_layernorm(L, mode, D, gelu):
+    """ser_layernorm in every mode it writes (3 = one fp16 plane, 4 = fp16 hi + lo: the post-LN layers of the text and *-base speech
+    encoders in f16x).  The planes are written from the same fp32 y as `of`, so they must be the host split of `of` bit for bit."""
     rows = 37
     g = torch.Generator().manual_seed(D)
     x = torch.randn(rows, D, generator=g) * 3 + 0.5
@@ -442,13 +446,20 @@ def test_layernorm(L, mode, D, gelu):
         ref = torch.nn.functional.gelu(ref)
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
     of = torch.empty(rows, D, device=DEV)
-    planes = 2 if mode == 2 else 1
-    oa = torch.empty(planes, rows, D, dtype=torch.bfloat16, device=DEV)
+    planes = 2 if mode in (2, 4) else 1
+    oa = torch.empty(planes, rows, D, dtype=act_dtype(mode), device=DEV)
     L.check(L.lib.ser_layernorm(xd.data_ptr(), D, wd.data_ptr(), bd.data_ptr(), 1e-5, int(gelu), of.data_ptr(), D,
                                 oa.data_ptr(), D, rows * D, mode, rows, D, stream()))
     torch.cuda.synchronize()
     assert (of.cpu().double() - ref).abs().max().item() < 2e-5
     assert (act_value(oa).cpu().double() - ref).abs().max().item() < mode_tol(mode, 4e-2, 1e-4)
+    f = of.cpu()
+    hi = f.clamp(-65504.0, 65504.0).half() if mode in (3, 4) else f.to(torch.bfloat16)
+    assert torch.equal(oa[0].cpu().view(torch.int16), hi.view(torch.int16))
+    if planes == 2:
+        d = f - hi.float()
+        lo = d.clamp(-65504.0, 65504.0).half() if mode == 4 else d.to(torch.bfloat16)
+        assert torch.equal(oa[1].cpu().view(torch.int16), lo.view(torch.int16))
 
 
 def test_wave_norm(L):
@@ -814,7 +825,7 @@ def test_gemm_reports_row_statistics_for_the_gate(L):
     out = torch.empty(M, N, device=DEV)
     lnst = torch.zeros(M, 2, device=DEV)
     mean_abs = torch.zeros(M, device=DEV)
-    pd, sd_, cs = part.to(DEV), shift.to(DEV), act_value(Wa).sum(1).contiguous()
+    pd, sd_, cs = part.to(DEV), shift.to(DEV), act_value(Wa).sum(1).float().contiguous()
     ga.A, ga.lda, ga.W, ga.M, ga.N, ga.K, ga.groups, ga.mode = Aa.data_ptr(), K, Wa.data_ptr(), M, N, K, 1, 1
     ga.out_f32, ga.ldo_f32 = out.data_ptr(), N
     ga.ln_stats_in, ga.ln_groups, ga.ln_colsum, ga.ln_eps = pd.data_ptr(), groups, cs.data_ptr(), 1e-5

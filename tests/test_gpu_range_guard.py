@@ -438,3 +438,117 @@ def test_pack_f16m_range_flag(L, weight, rows, cols, plant):
         ref = R.pack(stored.contiguous(), weight)
         assert torch.equal(out[0].cpu().view(torch.int16), ref["hi"].view(torch.int16))
         assert torch.equal(sc.cpu(), ref["scales"])
+
+
+# ---------------------------------------------------------------------------------------------------------- text embeddings / ConvLayer
+def text_ids(B, T, V, pad, gen):
+    ids = torch.randint(pad + 1, V, (B, T), generator=gen)
+    ids[1, T // 2:] = pad
+    ids[0, 5:8] = pad
+    return ids
+
+
+@pytest.mark.parametrize("plant", PLANTS)
+def test_embed_ln_range_flag(L, plant):
+    """ser_embed_ln_flagged (FP16X, the text drivers' default): word + position + token type -> LayerNorm, planted through the LayerNorm bias or
+    a NaN in a word embedding row; "masked" = a huge value in the position-embedding rows no token reaches (row 0 below the pad id's,
+    and the row past T + pad id)."""
+    B, T, D, V, pad = 3, 70, 200, 40, 1
+    gen = torch.Generator().manual_seed(11)
+    ids = text_ids(B, T, V, pad, gen)
+    w, pe, te = torch.randn(V, D, generator=gen), torch.randn(T + pad + 2, D, generator=gen), torch.randn(D, generator=gen)
+    g, b = 1.0 + torch.rand(D, generator=gen), torch.randn(D, generator=gen)
+    c = 17
+    if plant in ("half", "over", "inf"):
+        b[c] = planted(plant)
+    elif plant == "nan":
+        w[int(ids[2, 3]), c] = float("nan")
+    elif plant == "masked":
+        pe[0, c] = pe[T + pad + 1, c + 1] = 3.0e5
+    m = (ids != pad).long()
+    pos = torch.cumsum(m, 1) * m + pad
+    ref = torch.nn.functional.layer_norm((w[ids] + pe[pos] + te).double(), (D,), g.double(), b.double(), 1e-5)
+    idd = ids.to(torch.int32).to(DEV)
+    wd, ped, ted, gd, bd = (t.to(DEV) for t in (w, pe, te, g, b))
+
+    def launch(flag):
+        of = torch.zeros((B * T, D), device=DEV)
+        oa = torch.zeros((2, B * T, D), dtype=torch.float16, device=DEV)
+        L.check(L.lib.ser_embed_ln_flagged(idd.data_ptr(), wd.data_ptr(), ped.data_ptr(), ted.data_ptr(), gd.data_ptr(), bd.data_ptr(),
+                                           1e-5, of.data_ptr(), oa.data_ptr(), B * T * D, FP16X, B, T, D, pad, flag, stream()),
+                "ser_embed_ln_flagged")
+        return of, oa
+
+    bits, _ = run_flagged(launch)
+    assert bits == expected_bits(ref), (bits, expected_bits(ref))
+    if plant == "masked":
+        assert bits == 0
+
+
+@pytest.mark.parametrize("plant", PLANTS)
+def test_embed_ln_masked_range_flag(L, plant):
+    """ser_embed_ln_masked_flagged (FP16X): padded rows (t >= key_lens[b]) store zeros; "masked" = a NaN and 3e5 in the embedding row of the pad
+    token, which only padded positions read."""
+    B, T, D, V, pad = 3, 70, 200, 40, 0
+    lens = [70, 1, 33]
+    gen = torch.Generator().manual_seed(12)
+    ids = torch.randint(1, V, (B, T), generator=gen)
+    for bi, n in enumerate(lens):
+        ids[bi, n:] = pad
+    w = torch.randn(V, D, generator=gen)
+    g, b = 1.0 + torch.rand(D, generator=gen), torch.randn(D, generator=gen)
+    c = 9
+    if plant in ("half", "over", "inf"):
+        b[c] = planted(plant)
+    elif plant == "nan":
+        w[int(ids[2, 4]), c] = float("nan")
+    elif plant == "masked":
+        w[pad, c], w[pad, c + 1] = float("nan"), 3.0e5
+    real = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None]).reshape(-1)
+    ref = torch.nn.functional.layer_norm(w[ids].double(), (D,), g.double(), b.double(), 1e-7).view(B * T, D)
+    stored = ref[real]                                     # padded rows store zeros
+    idd, kl = ids.to(torch.int32).to(DEV), torch.tensor(lens, dtype=torch.int32, device=DEV)
+    wd, gd, bd = (t.to(DEV) for t in (w, g, b))
+
+    def launch(flag):
+        of = torch.zeros((B * T, D), device=DEV)
+        oa = torch.zeros((2, B * T, D), dtype=torch.float16, device=DEV)
+        L.check(L.lib.ser_embed_ln_masked_flagged(idd.data_ptr(), wd.data_ptr(), gd.data_ptr(), bd.data_ptr(), 1e-7, kl.data_ptr(),
+                                                  of.data_ptr(), oa.data_ptr(), B * T * D, FP16X, B, T, D, flag, stream()),
+                "ser_embed_ln_masked_flagged")
+        return of, oa
+
+    bits, (of, oa) = run_flagged(launch)
+    assert bits == expected_bits(stored), (bits, expected_bits(stored))
+    if plant == "masked":
+        assert bits == 0
+        assert bool((oa.cpu()[:, ~real] == 0).all())
+
+
+@pytest.mark.parametrize("plant", PLANTS)
+@pytest.mark.parametrize("halo", [0, 1])
+def test_pack_rows_range_flag(L, halo, plant):
+    """ser_pack_rows_flagged (FP16X, the ConvLayer's halo'd copy of hidden_states[0]): every value of the D columns is stored; "masked" = a huge
+    value in x's pitch columns past D, which the copy never reads."""
+    B, T, D = 3, 37, 200
+    ldx, ldo = D + 8, D + 4
+    gen = torch.Generator().manual_seed(13 + halo)
+    x = torch.randn(B * T, ldx, generator=gen)
+    if plant in ("half", "over", "nan", "inf"):
+        x[B * T - 1, D - 3] = planted(plant)
+    elif plant == "masked":
+        x[:, D:] = 3.0e5
+    xd = x.to(DEV)
+    R_ = B * (T + 2 * halo)
+
+    def launch(flag):
+        o = torch.zeros((2, R_, ldo), dtype=torch.float16, device=DEV)
+        L.check(L.lib.ser_pack_rows_flagged(xd.data_ptr(), ldx, B, T, D, halo, o.data_ptr(), ldo, R_ * ldo, FP16X, flag, stream()),
+                "ser_pack_rows_flagged")
+        return (o,)
+
+    bits, _ = run_flagged(launch)
+    stored = x[:, :D]
+    assert bits == expected_bits(stored), (bits, expected_bits(stored))
+    if plant == "masked":
+        assert bits == 0
