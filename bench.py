@@ -14,12 +14,14 @@ A counted step covers `--reps` such batches (default 8, stated in `config`), so 
 lasts > 1 s and a GPU-busy sampler can see it; `value` counts every utterance.  Round 3: `--inflight` whole batches (default 2)
 run at once on parallel branches of one hipGraph, as the drivers' two-slot pipeline does with real files.
 
-One JSON line on rank 0: metric/value/unit + `roofline` (dominant kernel = the MFMA GEMM, live HIP-event
-timing) + `verified` / `verification` (the outputs of the very graph that was timed, checked after the timed
-region: bit-equal to the eager command-list path, within the bf16 bound of an fp32x run, and that fp32x run within
-1e-3 of the CPU oracle) + `parity_mode` (throughput and measured error of the mode that passes north_star's 1e-3)
+One JSON line on rank 0: metric/value/unit/dtype/ms_per_step and the workload's configuration.  A plain run does
+nothing else: it sets up, warms up, times the steps, dumps (--dump-outputs) and prints.  `--full` adds, after the
+timed region, `roofline` (dominant kernel = the MFMA GEMM, live HIP-event timing) + `verified` / `verification` (the
+outputs of the very graph that was timed: bit-equal to the eager command-list path, within the timed mode's bound of
+the CPU oracle) + `parity_mode*` (throughput and measured error of each numerics mode against north_star's 1e-3)
 + `end_to_end` (wav files on tmpfs -> decode -> H2D -> forward -> D2H -> .pt files through the driver)
-+ `cpu_baseline` (CPU oracle, reference-style batch-of-one driver, bounded sample, rank 0 at N=1 only).
++ `other_encoders` + `cpu_baseline` (CPU oracle, reference-style batch-of-one driver, bounded sample, rank 0 at N=1
+only); the --no-* options drop single legs of such a run.
 `ms_per_step` is the wall time of one counted step.
 
 `--dump-outputs DIR` writes what the last timed step computed (a fixed sample of its hidden states, float32 .npy) to DIR
@@ -395,6 +397,10 @@ def main():
                     help="numerics mode(s) of the parity records, comma separated: the first fills `parity_mode`, "
                          "the others `parity_mode_<name>`")
     ap.add_argument("--layers", type=int, default=0, help="debug: truncate the encoder (invalidates the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the checks and the other measurements: output verification, roofline / "
+                         "attention-block / step-decomposition legs, parity modes, end-to-end legs, other encoders, CPU baseline "
+                         "(the --no-* options below drop single legs of a --full run; a plain run has none of them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-trace", action="store_true", help="skip per-launch GEMM events")
     ap.add_argument("--no-verify", action="store_true", help="skip the output checks of the timed path")
@@ -404,7 +410,7 @@ def main():
     ap.add_argument("--e2e-default-files", type=int, default=1024,
                     help="files of the second end-to-end leg, run in the drivers' DEFAULT numerics mode (0: skip)")
     ap.add_argument("--other-encoders", type=str, default="xlsr,hubert,whisper",
-                    help="after the headline: short verified runs (3 steps) of BASELINE configs[2..4]'s encoders on their own batch "
+                    help="after the headline of a --full run: short verified runs (3 steps) of BASELINE configs[2..4]'s encoders on their own batch "
                          "shapes, in the timed mode AND in the tolerance-grade modes (f16mf, f16x, f16m: throughput + error against the CPU oracle), "
                          "comma separated from xlsr,hubert,whisper ('' or none: skip -- what every script under tools/ passes; xlsr adds "
                          "~1 min of weight generation)")
@@ -420,6 +426,9 @@ def main():
                     help="after the timed steps, write the hidden states the last timed step computed to DIR/*.npy "
                          "(rank 0; a fixed, seeded sample of the rows, < 64 MB: see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:                  # the headline alone: every leg after the timed region is off
+        args.no_cpu_baseline = args.no_trace = args.no_verify = args.no_parity = args.no_e2e = True
+        args.other_encoders = "none"
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -463,8 +472,6 @@ def main():
     batches_waves = [synth_batch(args.batch, num_samples, 1234 + rank + 7919 * j) for j in range(inflight)]
     waves = batches_waves[0]
     lengths = [num_samples] * args.batch
-    packed = enc.upload(waves)
-    torch.cuda.synchronize()
 
     # `inflight` whole batches run at once, each on its own branch of one hipGraph (round 3: measured +4.3 % over one batch
     # split into two groups of 8, same box -- the launches have the shape BASELINE.json's config names, batch = 16, and the
@@ -556,6 +563,7 @@ def main():
         blocks, enc.block_trace = enc.block_trace, None
         # ... and once more with the whole batch in ONE launch per kernel (the shape BASELINE.json's config names)
         if micro > 1:
+            packed = enc.upload(waves)
             enc.block_trace = []
             for _ in range(max(2, args.steps // 4)):
                 enc.forward(packed, lengths, slot=len(groups))
@@ -847,7 +855,7 @@ def main():
         if e2e_default is not None:
             out["end_to_end_default_mode"] = e2e_default
         if world == 1 and args.other_encoders and args.other_encoders != "none":
-            del enc, hs_timed, groups, packed
+            del enc, hs_timed, groups
             torch.cuda.empty_cache()
             out["other_encoders"] = {n: other_encoder_run(n, device, args.mode) for n in args.other_encoders.split(",") if n in OTHER_ENCODERS}
             if "verified" in out:                     # a failed check of any encoder fails the line

@@ -9,7 +9,7 @@ TAG=${1:-r05}
 OUT=gpurun_out/prof
 mkdir -p $OUT profiles
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd - >/dev/null
-FLAGS="--no-trace --no-cpu-baseline --no-parity --no-e2e --other-encoders none"
+FLAGS="--full --no-trace --no-cpu-baseline --no-parity --no-e2e --other-encoders none"
 stats() {  # name, bench args...
     local name=$1; shift
     rm -rf $OUT/$name                       # rocprofv3 -d accumulates one subdirectory per run: never stamp a stale CSV
