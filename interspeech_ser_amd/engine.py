@@ -17,6 +17,7 @@ exist, so no attention / conv masking is needed) and waste no FLOPs on padding.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GemmArgs, check, lib
+from ._lib import check, lib
 from .weights import check_f16_weight
 from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_WAVLM, FAMILY_WHISPER
 
@@ -176,6 +177,12 @@ class Act:
     def ptr(self) -> int:
         return self.t.data_ptr()
 
+    def first_rows(self, rows: int) -> "Act":
+        """The first ``rows`` rows of every plane as an operand of their own: same storage, same plane stride."""
+        v = copy.copy(self)
+        v.rows = rows
+        return v
+
     def float(self) -> torch.Tensor:
         """fp32 view for tests (hi + lo)."""
         if self.scale is not None:
@@ -290,7 +297,7 @@ class _EncoderBase:
         self.fp16_planes = mode in ("f16x", "f16m", "f16mf", "f16a", "f16q", "f16") and _os.environ.get("SER_NO_RANGE_GUARD", "0") != "1"
         self._flag: Optional[int] = None    # device address of the range-guard word of the slot being launched / recorded
         self._st: Optional[int] = None      # launch stream of the forward in progress (looked up once per forward)
-        self._rec: Optional[Tape] = None    # when set, the launch helpers record into it instead of launching
+        self._rec: Optional[Tape] = None    # when set, _issue records the launch helpers' commands into it instead of launching them
 
     def _guard_word(self, pl) -> Optional[torch.Tensor]:
         """the slot's range-guard word (allocated with the plan); launch helpers pick its address up from ``self._flag``"""
@@ -388,6 +395,39 @@ class _EncoderBase:
         return Act(rows, cols, _PLANES[mode], self.device, zero=zero, extra_rows=extra_rows, dtype=_DTYPE[mode], mx=(mode == _lib.MODE_FP16M))
 
     # ------------------------------------------------------------------ launchers
+    # Every helper builds its launch once, as a ``ser_cmd``: recording and launching differ in WHEN it goes to the library, not in how it is built.
+    def _cmd(self, field: str):
+        """The zeroed argument struct (``ser_cmd`` union member) to fill: the command list's next slot when recording, else the member of
+        a fresh ``ser_cmd`` -- one per launch: the helpers rely on the zeros, and host threads share nothing."""
+        if self._rec is not None:
+            return self._rec.slot(field)
+        cmd = _lib.Cmd()
+        view = getattr(cmd.u, field)
+        view.cmd = cmd                      # a Python attribute, not a field: how _issue finds the command around ``view``
+        return view
+
+    def _issue(self, op: int, view, what: str, input: Optional[str] = None, **sizes) -> None:
+        """Recording: commit the filled command (``Sz`` sizes become patches, ``input`` names it as a reader of the per-batch waveform
+        pointer); else launch it now, alone, through the dispatcher the list goes through."""
+        rec = self._rec
+        if rec is not None:
+            if input is not None:
+                rec.inputs[input] = view
+            rec.commit(op, view, **sizes)
+            return
+        view.cmd.op = op
+        check(lib.ser_run(C.byref(view.cmd), 1, None, self._s()), what)
+
+    def _state_done(self, i: int, last_state: Optional[int]) -> bool:
+        """Hidden state ``i`` is complete; True = stop here.  ``last_state`` = N: the caller reads hidden_states[N] only (the reference's
+        speech script keeps one state, preprocess_speech.py:67), so the layers that only feed later states are not launched.  Recording
+        a command list marks where every state is complete instead (Tape.marks), and the replay stops there."""
+        rec = self._rec
+        if rec is None:
+            return last_state == i
+        rec.marks[i] = rec.n
+        return False
+
     def _gemm(self, a: Act, lin: Linear, M: int, *, a_rowoff=None, lda=None, kc=0, ldj=0, groups=1,
               a_group_stride=0, w_group_stride=0, c_group_stride=0, N=None, K=None, act=_lib.ACT_NONE,
               residual=None, ldr=0, res_row_mod=0, out_f32=None, ldo_f32=0, out_act: Optional[Act] = None,
@@ -395,8 +435,7 @@ class _EncoderBase:
               ln_stats=None, ln_groups=0, stat_out=None, stat_groups=0, f32_col_begin=0,
               col_scale=1.0, col_scale_end=0, shift=None, ln_mean=None, stem=False, out_mode=0, mode=None, out_col=0,
               lnstat_out=None, gn=None):
-        rec = self._rec
-        g = rec.slot("gemm") if rec is not None else GemmArgs()
+        g = self._cmd("gemm")
         g.A = a.ptr + a_ptr_offset
         g.a_plane_stride = a.plane_stride
         g.a_rowoff = _ptr(a_rowoff)
@@ -446,15 +485,13 @@ class _EncoderBase:
             if out_col % 64:
                 raise ValueError("an FP16M output must start on a 64-column tile")
             g.out_scale, g.out_scale_ld = out_act.scale.data_ptr() + 4 * (out_col // 64) * out_act.scale_ld, out_act.scale_ld
-        if rec is not None:
-            rec.commit(_lib.OP_GEMM, g, M=M, **({} if gn is None else {"gn_B": gn[3]}))
+        trace = self.gemm_trace                 # (never on while a list is recorded: _launch_or_replay)
+        if trace is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        self._issue(_lib.OP_GEMM, g, "ser_gemm", M=M, **({} if gn is None else {"gn_B": gn[3]}))
+        if trace is None:
             return
-        if self.gemm_trace is None:
-            check(lib.ser_gemm(C.byref(g), self._s()), "ser_gemm")
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib.ser_gemm(C.byref(g), self._s()), "ser_gemm")
         e1.record()
         # algorithmic FLOPs: 2*M*N*K over real (unpadded) channels, no tile-padding FLOPs
         k_real = g.K if k_algo is None else k_algo
@@ -463,7 +500,7 @@ class _EncoderBase:
         nbytes = 2.0 * planes * (M * k_real * groups + g.N * groups * k_real)
         nbytes += 4.0 * M * g.N * groups * ((residual is not None) + (out_f32 is not None))
         nbytes += 2.0 * planes * M * g.N * groups * (out_act is not None)
-        self.gemm_trace.append((e0, e1, 2.0 * M * g.N * groups * k_real, nbytes, _PRODUCTS[g.mode]))
+        trace.append((e0, e1, 2.0 * M * g.N * groups * k_real, nbytes, _PRODUCTS[g.mode]))
 
     def _layernorm(self, x: torch.Tensor, ldx: int, ln, rows: int, D: int, *, gelu=False, out_f32=None,
                    out_act: Optional[Act] = None, eps=None, stem=False):
@@ -478,37 +515,23 @@ class _EncoderBase:
         ldo_act = 0 if out_act is None else out_act.cols
         ops = 0 if out_act is None else out_act.plane_stride
         ldo_f32 = D if out_f32 is not None else 0
-        rec = self._rec
-        a = rec.slot("layernorm") if rec is not None else _lib.LayerNormArgs()
+        a = self._cmd("layernorm")
         a.x, a.ldx, a.g, a.b, a.eps, a.gelu = x.data_ptr(), ldx, g.data_ptr(), b.data_ptr(), eps, int(gelu)
         a.out_f32, a.ldo_f32, a.out_act, a.ldo_act, a.out_plane_stride = _ptr(out_f32), ldo_f32, o_act, ldo_act, ops
         a.mode, a.rows, a.D = mode, rows, D
         a.range_flag = self._flag if out_act is not None else None
-        if rec is not None:
-            rec.commit(_lib.OP_LAYERNORM, a, rows=rows)
-            return
-        check(lib.ser_layernorm_v(C.byref(a), self._s()), "ser_layernorm")
+        self._issue(_lib.OP_LAYERNORM, a, "ser_layernorm", rows=rows)
 
     def _row_center(self, x: torch.Tensor, out_act: Act, stats: torch.Tensor, shift: torch.Tensor, rows: int, D: int):
         """hidden_states[0] -> centred operand copy + row partials + shift for encoder layer 0 (ser_row_center)."""
         groups = stats.shape[1]
-        rec = self._rec
-        if rec is not None:
-            a = rec.slot("row_center")
-            a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), D, out_act.ptr, out_act.cols, out_act.plane_stride
-            a.stats, a.shift, a.stat_groups, a.mode, a.rows, a.D = stats.data_ptr(), shift.data_ptr(), groups, self._lay_modes(0)["x_mode"], rows, D
-            if out_act.scale is not None:
-                a.out_scale, a.out_scale_ld = out_act.scale.data_ptr(), out_act.scale_ld
-            a.range_flag = self._flag
-            rec.commit(_lib.OP_ROW_CENTER, a, rows=rows)
-            return
-        a = _lib.RowCenterArgs()
+        a = self._cmd("row_center")
         a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), D, out_act.ptr, out_act.cols, out_act.plane_stride
         a.stats, a.shift, a.stat_groups, a.mode, a.rows, a.D = stats.data_ptr(), shift.data_ptr(), groups, self._lay_modes(0)["x_mode"], rows, D
         if out_act.scale is not None:
             a.out_scale, a.out_scale_ld = out_act.scale.data_ptr(), out_act.scale_ld
         a.range_flag = self._flag
-        check(lib.ser_row_center_v(C.byref(a), self._s()), "ser_row_center")
+        self._issue(_lib.OP_ROW_CENTER, a, "ser_row_center", rows=rows)
 
     def _attention(self, qkv: Act, frame_offs_dev, B, max_frames, out: Act, *, table=None, table_T=0, gate=None,
                    gru_const=None, key_lens=None, bias2d=None, gate_in=None, out_m=False):
@@ -518,8 +541,7 @@ class _EncoderBase:
         # column blocks of the packed projection: [q | k | v | gate] or, with the logit path on its own launch ("f16q"), [q | k | gate | v]
         q_col, k_col, v_col, gate_col = self._qkv_cols()
         amode = _lib.MODE_FP16Q if self.qk_mode is not None else self.attn_mode
-        rec = self._rec
-        a = rec.slot("attention") if rec is not None else _lib.AttentionArgs()
+        a = self._cmd("attention")
         a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
         a.q_col, a.k_col, a.v_col, a.B = q_col, k_col, v_col, B
         a.frame_offs, a.table, a.gate = frame_offs_dev.data_ptr(), _ptr(table), _ptr(gate)
@@ -537,10 +559,7 @@ class _EncoderBase:
             a.gate_x, a.gate_x_ld, a.gate_x_plane_stride, a.gate_x_planes = xa.ptr, xa.cols, xa.plane_stride, xa.planes
             a.gate_stat, a.gate_w, a.gate_cb = lnstat.data_ptr(), gw.data_ptr(), gcb.data_ptr()
             a.gate_w_plane_stride = gw.shape[1] * gw.shape[2]
-        if rec is not None:
-            rec.commit(_lib.OP_ATTENTION, a, B=B, max_frames=max_frames, table_T=table_T)
-            return
-        check(lib.ser_attention_v(C.byref(a), self._s()), "ser_attention")
+        self._issue(_lib.OP_ATTENTION, a, "ser_attention", B=B, max_frames=max_frames, table_T=table_T)
 
     @staticmethod
     def _gate_in(pl, lay):
@@ -639,13 +658,7 @@ class _EncoderBase:
         M, D, L = pl["M"], geo.hidden, geo.num_layers
         gD = self._stat_groups(D)
         gx = first_groups
-        # ``last_state`` = N: the caller reads hidden_states[N] only (the reference's speech script keeps one state,
-        # preprocess_speech.py:67), so the layers that only feed later states are not launched.  Recording a command list marks
-        # where every state is complete instead (Tape.marks), and the replay stops there.
-        rec = self._rec
-        if rec is not None:
-            rec.marks[0] = rec.n
-        elif last_state == 0:
+        if self._state_done(0, last_state):
             return
         self._row_center(states[0], pl["xa"], pl["px0"], pl["sx"], M, D)
         shifted = not _NO_SHIFT
@@ -670,11 +683,8 @@ class _EncoderBase:
                            out_act=pl["xa"], stat_out=pl["px"], stat_groups=gD, out_mode=self.layers[i + 1]["x_mode"],
                            shift=(pl["mh"], pl["sx"], lay["fc2_bias_mean"]) if shifted else None)
             gx = gD
-            if not last:
-                if rec is not None:
-                    rec.marks[i + 1] = rec.n
-                elif last_state == i + 1:
-                    return
+            if not last and self._state_done(i + 1, last_state):
+                return
         self._layernorm(pl["last"], D, self.enc_ln, M, D, out_f32=states[L])
 
     def _launch_or_replay(self, owner: dict, pl, packed_wave: torch.Tensor, last_state: Optional[int]) -> HiddenStates:
@@ -683,7 +693,7 @@ class _EncoderBase:
         first forward over ``owner`` records it, launching nothing."""
         flag = self._guard_word(pl)
         if not self.use_tape or self.gemm_trace is not None or self.block_trace is not None:
-            self._launches(pl, packed_wave, last_state)      # eager: one Python -> C transition per kernel
+            self._launches(pl, packed_wave, last_state)      # one by one: a one-command ser_run per kernel
         else:
             tape = owner.get("tape")
             if tape is None:
@@ -1179,24 +1189,12 @@ class SpeechEncoder(_EncoderBase):
         B, M, D, C0 = pl["B"], pl["M"], geo.hidden, geo.conv_dim[0]
         # a6 + a7 (layer 0): zero-mean / unit-variance per utterance fused with framing, then
         # Conv1d(1,C,10,5)+LayerNorm+GELU on the matrix cores (K padded to 64, LayerNorm epilogue)
-        fr = pl["frames"]
-        rec = self._rec
-        a = rec.slot("wave_frames") if rec is not None else _lib.WaveFramesArgs()
-        a.wav, a.sample_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["frame_offs0"].data_ptr()
-        a.B, a.k, a.stride, a.mode = B, geo.conv_kernel[0], geo.conv_stride[0], self.stem_mode
-        a.out, a.out_plane_stride, a.work, a.total_rows = fr.ptr, fr.plane_stride, pl["wave_work"].data_ptr(), pl["rows"][0]
-        a.no_norm = 0 if self.normalize else 1
-        a.range_flag = self._flag
-        if rec is not None:
-            rec.inputs["wav"] = a
-            rec.commit(_lib.OP_WAVE_FRAMES, a, B=B, total_rows=pl["rows"][0])
-        else:
-            check(lib.ser_wave_frames_v(C.byref(a), self._s()), "ser_wave_frames")
+        self._wave_frames(pl, packed_wave)
         a_in = pl["conv_act"][0]
         if self.gn_stem:
             self._groupnorm_stem(pl, packed_wave)
         else:
-            self._gemm(fr, self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
+            self._gemm(pl["frames"], self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
                        k_algo=geo.conv_kernel[0], stem=True)
         # a7: conv layers 1..6 as implicit GEMMs with LayerNorm(C)+GELU fused into the epilogue
         # (the 512-wide output row lives in one block tile, so the pre-LN activations never touch HBM)
@@ -1204,10 +1202,7 @@ class SpeechEncoder(_EncoderBase):
         for i in range(1, nl):
             rows = pl["rows"][i]
             if i < nl - 1:
-                a_out = pl["conv_act"][i % 2]
-                a_view = Act.__new__(Act)
-                a_view.t, a_view.rows, a_view.cols, a_view.planes = a_out.t, rows, C0, a_out.planes
-                a_view.plane_stride = a_out.plane_stride
+                a_view = pl["conv_act"][i % 2].first_rows(rows)
                 self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
                            ln=self.conv_ln[i], ln_eps=1e-5, out_act=a_view, stem=True)     # (ln None: *-base, GELU only)
                 a_in = a_view
@@ -1239,6 +1234,17 @@ class SpeechEncoder(_EncoderBase):
         # a11/a12: stable-LayerNorm encoder layers (LayerNorms deferred into the GEMMs)
         self._run_layers(pl, states, pl["first_groups"], B, pl["Tmax"], last_state)
 
+    def _wave_frames(self, pl, packed_wave: torch.Tensor) -> None:
+        """ser_wave_frames: every utterance's samples normalised (``normalize``) and framed into conv layer 0's operand rows."""
+        geo, fr = self.geo, pl["frames"]
+        B, rows = pl["B"], pl["rows"][0]
+        a = self._cmd("wave_frames")
+        a.wav, a.sample_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["frame_offs0"].data_ptr()
+        a.B, a.k, a.stride, a.mode = B, geo.conv_kernel[0], geo.conv_stride[0], self.stem_mode
+        a.out, a.out_plane_stride, a.work, a.total_rows = fr.ptr, fr.plane_stride, pl["wave_work"].data_ptr(), rows
+        a.no_norm = 0 if self.normalize else 1
+        a.range_flag = self._flag
+        self._issue(_lib.OP_WAVE_FRAMES, a, "ser_wave_frames", input="wav", B=B, total_rows=rows)
 
     def _pos_stack(self, pl, states) -> None:
         """data2vec-audio's positional embedding (HF Data2VecAudioPositionalConvEmbedding): per layer j the grouped conv as an implicit
@@ -1263,8 +1269,7 @@ class SpeechEncoder(_EncoderBase):
         """ser_pos_ln_v: the intermediate form (``residual`` None) or the last one (+ residual, encoder.layer_norm -> ``out_f32``)."""
         D = self.geo.hidden
         last = residual is not None
-        rec = self._rec
-        a = rec.slot("pos_ln") if rec is not None else _lib.PosLnArgs()
+        a = self._cmd("pos_ln")
         a.x, a.ldx = x.data_ptr(), D
         a.out_act = None if out_act is None else out_act.ptr
         a.ldo_act = 0 if out_act is None else out_act.cols
@@ -1276,10 +1281,7 @@ class SpeechEncoder(_EncoderBase):
         a.eps_pos, a.eps = 1e-5, float(self.geo.layer_norm_eps)          # nn.LayerNorm(D, elementwise_affine=False): the default eps
         a.last, a.mode, a.rows, a.D = int(last), mode, rows, D
         a.range_flag = self._flag if out_act is not None else None
-        if rec is not None:
-            rec.commit(_lib.OP_POS_LN, a, rows=rows)
-            return
-        check(lib.ser_pos_ln_v(C.byref(a), self._s()), "ser_pos_ln")
+        self._issue(_lib.OP_POS_LN, a, "ser_pos_ln", rows=rows)
 
     def _groupnorm_stem(self, pl, packed_wave: torch.Tensor) -> None:
         """Conv layer 0 of the *-base form: GroupNorm(C, C) over each utterance's frames, then GELU.  ser_gn_stats_v derives the
@@ -1287,19 +1289,14 @@ class SpeechEncoder(_EncoderBase):
         conv-0 GEMM applies them in its epilogue (ser_gemm_args.gn_scale): layer 1's operand planes are its only output."""
         geo = self.geo
         B, C0 = pl["B"], geo.conv_dim[0]
-        rec = self._rec
-        a = rec.slot("gn_stats") if rec is not None else _lib.GnStatsArgs()
+        a = self._cmd("gn_stats")
         a.wav, a.sample_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["frame_offs0"].data_ptr()
         a.w, a.bias, a.gamma, a.beta = self.conv0_w.data_ptr(), _ptr(self.conv0_b), self.gn0[0].data_ptr(), self.gn0[1].data_ptr()
         a.wave_stats = pl["wave_work"].data_ptr()                # what ser_wave_frames normalised the frames with (launched just before)
         a.scale, a.shift, a.stat_out, a.work = pl["gn_scale"].data_ptr(), pl["gn_shift"].data_ptr(), None, pl["gn_work"].data_ptr()
         a.B, a.C, a.k, a.stride, a.ld = B, C0, geo.conv_kernel[0], geo.conv_stride[0], C0
         a.no_norm, a.eps = 0 if self.normalize else 1, 1e-5      # nn.GroupNorm's default eps (HF WavLMGroupNormConvLayer)
-        if rec is not None:
-            rec.inputs["wav_gn"] = a
-            rec.commit(_lib.OP_GN_STATS, a, B=B)
-        else:
-            check(lib.ser_gn_stats_v(C.byref(a), self._s()), "ser_gn_stats")
+        self._issue(_lib.OP_GN_STATS, a, "ser_gn_stats", input="wav_gn", B=B)
         self._gemm(pl["frames"], self.conv0, pl["rows"][0], act=_lib.ACT_GELU, out_act=pl["conv_act"][0], k_algo=geo.conv_kernel[0],
                    stem=True, gn=(pl["gn_scale"], pl["gn_shift"], pl["frame_offs0"], B))
 
@@ -1311,10 +1308,7 @@ class SpeechEncoder(_EncoderBase):
         M, D, L = pl["M"], geo.hidden, geo.num_layers
         wavlm = geo.family == FAMILY_WAVLM
         scale = geo.head_dim ** -0.5 * 1.4426950408889634     # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
-        rec = self._rec
-        if rec is not None:
-            rec.marks[0] = rec.n
-        elif last_state == 0:
+        if self._state_done(0, last_state):
             return
         for i, lay in enumerate(self.layers):
             last = i + 1 == L
@@ -1325,11 +1319,8 @@ class SpeechEncoder(_EncoderBase):
             else:
                 self._attention(pl["qkv"], pl["frame_offs"], B, max_frames, pl["ctx"])
             self._post_ln_tail(pl, lay, states[i], states[i + 1], None if last else pl["xa"])
-            if not last:
-                if rec is not None:
-                    rec.marks[i + 1] = rec.n
-                elif last_state == i + 1:
-                    return
+            if not last and self._state_done(i + 1, last_state):
+                return
 
 
 class WhisperEncoder(_EncoderBase):
@@ -1418,17 +1409,10 @@ class WhisperEncoder(_EncoderBase):
     download = SpeechEncoder.download
 
     def _logmel(self, pl, packed_wave: torch.Tensor) -> None:
-        rec = self._rec
-        if rec is not None:
-            a = rec.slot("logmel")
-            a.wav, a.sample_offs, a.mel = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), self.mel.data_ptr()
-            a.out, a.work, a.B, a.n_mels = pl["mel"].data_ptr(), pl["work"].data_ptr(), pl["B"], self.geo.n_mels
-            rec.inputs["wav"] = a
-            rec.commit(_lib.OP_LOGMEL, a)
-            return
-        check(lib.ser_logmel_whisper(packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["B"], self.mel.data_ptr(),
-                                     self.geo.n_mels, pl["mel"].data_ptr(), pl["work"].data_ptr(), self._s()),
-              "ser_logmel_whisper")
+        a = self._cmd("logmel")
+        a.wav, a.sample_offs, a.mel = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), self.mel.data_ptr()
+        a.out, a.work, a.B, a.n_mels = pl["mel"].data_ptr(), pl["work"].data_ptr(), pl["B"], self.geo.n_mels
+        self._issue(_lib.OP_LOGMEL, a, "ser_logmel_whisper", input="wav")
 
     @_on_stream
     def log_mel(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0) -> torch.Tensor:
@@ -1465,22 +1449,22 @@ class WhisperEncoder(_EncoderBase):
         self._encoder_launches(pl, input_features)
         return HiddenStates(pl["states"], pl["frame_offs_host"], range_flag=flag)
 
+    def _pack_act(self, pl, input_features: torch.Tensor) -> None:
+        """ser_pack_act: the [B, n_mels, 3000] features as conv1's operand rows (channels last, a zero halo row before and after each utterance)."""
+        ma, nm = pl["mel_act"], self.geo.n_mels
+        a = self._cmd("pack_act")
+        a.x, a.out, a.ldo, a.out_plane_stride = input_features.data_ptr(), ma.ptr, nm, ma.plane_stride
+        a.B, a.C, a.T, a.halo, a.mode = pl["B"], nm, self.N_FRAMES, 1, self.stem_mode
+        a.range_flag = self._flag
+        self._issue(_lib.OP_PACK_ACT, a, "ser_pack_act")
+
     def _encoder_launches(self, pl, input_features: torch.Tensor, last_state: Optional[int] = None) -> None:
         geo = self.geo
-        B, M, D, nm = pl["B"], pl["M"], geo.hidden, geo.n_mels
+        B, M, D = pl["B"], pl["M"], geo.hidden
         T1, T2 = self.N_FRAMES, geo.max_source_positions
-        ma = pl["mel_act"]
-        rec = self._rec
-        a = rec.slot("pack_act") if rec is not None else _lib.PackActArgs()
-        a.x, a.out, a.ldo, a.out_plane_stride = input_features.data_ptr(), ma.ptr, nm, ma.plane_stride
-        a.B, a.C, a.T, a.halo, a.mode = B, nm, T1, 1, self.stem_mode
-        a.range_flag = self._flag
-        if rec is not None:
-            rec.commit(_lib.OP_PACK_ACT, a)
-        else:
-            check(lib.ser_pack_act_v(C.byref(a), self._s()), "ser_pack_act")
+        self._pack_act(pl, input_features)
         # stem: gelu(conv1 k3 p1), gelu(conv2 k3 s2 p1) + embed_positions -> hidden_states[0]
-        self._gemm(ma, self.conv1, B * T1, a_rowoff=pl["c1_rowoff"], act=_lib.ACT_GELU, out_act=pl["c1_act"],
+        self._gemm(pl["mel_act"], self.conv1, B * T1, a_rowoff=pl["c1_rowoff"], act=_lib.ACT_GELU, out_act=pl["c1_act"],
                    out_rowmap=pl["c1_rowmap"], stem=True)
         states = pl["states"]
         self._gemm(pl["c1_act"], self.conv2, M, a_rowoff=pl["c2_rowoff"], act=_lib.ACT_GELU, residual=self.pos_emb,
