@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SER_ABI_VERSION 17
+#define SER_ABI_VERSION 18
 
 #define SER_MODE_BF16  1   /* act tensors have 1 plane; GEMMs do 1 bf16 MFMA product   */
 #define SER_MODE_FP32X 2   /* act tensors have 2 planes; GEMMs do hi*hi + lo*hi + hi*lo */
@@ -409,6 +409,28 @@ typedef struct ser_wave_frames_args {
     uint32_t* range_flag;                           /* fp16 range guard, may be NULL (ABI 13) */
 } ser_wave_frames_args;
 int ser_wave_frames_v(const ser_wave_frames_args* args, void* stream);
+
+/* a5r (ABI 18)  ser_resample: the resampling half of librosa.load(path, sr=16000) (preprocess_speech.py:47) for a ragged, MIXED-RATE
+ * batch in one launch: a Kaiser (beta 14) polyphase FIR, the filter scipy.signal.resample_poly designs (parity with librosa's soxr_hq is
+ * unpinned; pinned is the output length ceil(n * 16000 / sr)).  Per utterance b with g = gcd(sr, 16000), up = 16000 / g, down = sr / g,
+ * R = max(up, down), half = 10 R and the float64 bank h[0 .. 2 half] at bank + bank_off[b]
+ *   (h[k] = up w[k] / sum(w),  w[k] = sinc((k - half) / R) / R * kaiser_14(2 half + 1)[k]):
+ *   y[m] = sum_j x[j] h[m down - j up + half]  over 0 <= j < n with 0 <= m down - j up + half <= 2 half,   m = 0 .. n_out - 1,
+ * n = in_offs[b + 1] - in_offs[b], n_out = out_offs[b + 1] - out_offs[b] (the caller's (n up + down - 1) / down).  fp32 samples times
+ * float64 coefficients, accumulated in float64 in ascending j, rounded to fp32 once at the store: the order is fixed per output sample, so
+ * a result does not depend on the rest of the batch (no atomics).  up == down == 1 copies the utterance bit for bit (half, bank_off unused).
+ * Device: wav / out packed fp32, in_offs / out_offs / bank_off int64, up / down / half int32, bank float64 (every distinct bank of the
+ * batch, once).  Host: B, total_in / total_out (packed sample totals) and max_out (the longest n_out; sizes the grid) -- the only fields
+ * validated before the launch (-1 null pointer, -2 sizes); the per-utterance arrays are the caller's contract. */
+#define SER_RESAMPLE_TILE 1024                      /* output samples per block */
+typedef struct ser_resample_args {
+    const float* wav; const int64_t* in_offs; const int64_t* out_offs;
+    const int32_t* up; const int32_t* down; const int32_t* half; const int64_t* bank_off;
+    const double* bank; float* out;
+    int64_t total_in, total_out, max_out;
+    int32_t B, reserved0;
+} ser_resample_args;
+int ser_resample_v(const ser_resample_args* args, void* stream);
 
 /* K2g (ABI 15)  GroupNorm-over-time statistics of conv layer 0 for the *-base checkpoints (Conv1d(1, C, k, stride) -> GroupNorm(C, C,
  * eps) -> GELU, HF WavLMGroupNormConvLayer; the reference runs one file at a time, preprocess_speech.py:76-81, so the statistics of an

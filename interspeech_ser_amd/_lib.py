@@ -26,7 +26,8 @@ ACT_GELU = 1
 WS_LOGMEL = 1
 WS_WAVE_FRAMES = 2
 WS_GN_STATS = 3
-ABI_VERSION = 17
+RESAMPLE_TILE = 1024            # SER_RESAMPLE_TILE: output samples per block of ser_resample_v
+ABI_VERSION = 18
 
 c_void_p, c_int, c_i64, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -146,6 +147,17 @@ class PosLnArgs(C.Structure):
     ]
 
 
+class ResampleArgs(C.Structure):
+    """Mirror of ``ser_resample_args`` (ABI 18)."""
+    _fields_ = [
+        ("wav", c_void_p), ("in_offs", c_void_p), ("out_offs", c_void_p),
+        ("up", c_void_p), ("down", c_void_p), ("half", c_void_p), ("bank_off", c_void_p),
+        ("bank", c_void_p), ("out", c_void_p),
+        ("total_in", c_i64), ("total_out", c_i64), ("max_out", c_i64),
+        ("B", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
@@ -160,7 +172,7 @@ class Cmd(C.Structure):
 OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS, OP_POS_LN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
-                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_cmd": Cmd}
+                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -180,6 +192,7 @@ _SIGNATURES = {
     "ser_pack_act_v": (c_int, [c_void_p, c_void_p]),
     "ser_gn_stats_v": (c_int, [c_void_p, c_void_p]),
     "ser_pos_ln_v": (c_int, [c_void_p, c_void_p]),
+    "ser_resample_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

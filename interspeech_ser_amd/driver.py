@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from . import config as C
-from .frontend import feature_path, load_wav_16k, save_feature, whisper_saved_rows
+from .frontend import (RESAMPLE_MAX_R, TARGET_SR, decode_wav, feature_path, host_resample, load_wav_16k, resample_ratio,
+                       resampled_len, save_feature, whisper_saved_rows)
 
 
 # ------------------------------------------------------------------------------- CLI
@@ -73,7 +74,8 @@ def build_parser(whisper: bool) -> argparse.ArgumentParser:
                    help="pt (default): what the reference writes and its heads read (torch.save of a [T, D] float32 tensor); "
                         "npy: the same array as <name>.npy for consumers without torch")
     p.add_argument("--resample", action="store_true",
-                   help="accept non-16 kHz wav files through a polyphase resampler (parity with librosa's soxr_hq unpinned)")
+                   help="accept non-16 kHz wav files through a Kaiser polyphase resampler that runs on the GPU ahead of the forward "
+                        "(parity with librosa's soxr_hq unpinned)")
     p.add_argument("--lora_alpha", type=float, default=16.0,
                    help="LoRA alpha of a fine-tuned --checkpoint (the reference's LoraConfig: r=8, alpha=16)")
     p.add_argument("--timing", action="store_true", help="print where the launching thread spent its time")
@@ -171,11 +173,18 @@ class _Extractor:
         ex.average = args.use_average == "y"
         return ex
 
-    def extract(self, waves: List[np.ndarray], layer_index: int) -> List[torch.Tensor]:
+    def upload_resampled(self, waves: List[np.ndarray], rates: Optional[Sequence[int]], slot: int = 0):
+        """(packed 16 kHz device buffer, lengths at 16 kHz) of one batch.  ``rates`` (``--resample``): the files' own sample rates, the
+        raw samples go up and ser_resample_v brings them to 16 kHz on the current stream; None: 16 kHz samples, plain upload."""
+        if rates is None:
+            return self.enc.upload(waves, slot), [len(w) for w in waves]
+        return self.enc.upload_resampled(waves, rates, slot)
+
+    def extract(self, waves: List[np.ndarray], layer_index: int, rates: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
         """One ragged batch -> one CPU [T, D] tensor per utterance (rows a19/a20), synchronously."""
         from .engine import mean_last4
-        lengths = [len(w) for w in waves]
-        hs = self.enc.forward(self.enc.upload(waves), lengths, last_state=None if self.average else layer_index)
+        dev, lengths = self.upload_resampled(waves, rates)
+        hs = self.enc.forward(dev, lengths, last_state=None if self.average else layer_index)
         self._check_range(hs.take_range_bits())
         sel = mean_last4(hs) if self.average else hs.states[layer_index]
         out = []
@@ -221,20 +230,19 @@ class _Extractor:
     SLOTS = min(3, max(2, int(os.environ.get("SER_PIPE_SLOTS", "2"))))
     RUNNING = 2
 
-    def submit(self, waves: List[np.ndarray], layer_index: int, slot: int):
+    def submit(self, waves: List[np.ndarray], layer_index: int, slot: int, rates: Optional[Sequence[int]] = None):
         """Enqueue upload -> forward -> selection -> D2H of one ragged batch on slot ``slot``'s stream; returns a
         ticket for ``collect``.  Nothing here waits for the GPU."""
         from .engine import mean_last4
         st = self.__dict__.setdefault("_streams", {})
         if slot not in st:
             st[slot] = torch.cuda.Stream(device=self.enc.device)
-        lengths = [len(w) for w in waves]
-        tm = self.__dict__.setdefault("tm", dict(upload=0.0, forward=0.0, d2h=0.0))
+        tm = self.__dict__.setdefault("tm", dict(upload=0.0, upload_resample=0.0, forward=0.0, d2h=0.0))
         clock = time.perf_counter
         computed = self.__dict__.setdefault("_computed", [])      # "kernels done" events of the batches submitted so far, oldest first
         with torch.cuda.stream(st[slot]):
             t0 = clock()
-            dev = self.enc.upload(waves, slot)
+            dev, lengths = self.upload_resampled(waves, rates, slot)     # lengths: at 16 kHz
             t1 = clock()
             if len(computed) >= self.RUNNING:                     # start once the batch RUNNING places ahead has left the compute units
                 st[slot].wait_event(computed[-self.RUNNING])
@@ -256,7 +264,8 @@ class _Extractor:
             evt = torch.cuda.Event()
             evt.record()
             t3 = clock()
-        tm["upload"] += t1 - t0
+        # upload_resample: the batches that went through ser_resample_v (raw samples H2D, its O(B) tables, the launch)
+        tm["upload" if rates is None or all(r == TARGET_SR for r in rates) else "upload_resample"] += t1 - t0
         tm["forward"] += t2 - t1
         tm["d2h"] += t3 - t2
         return dict(slot=slot, event=evt, host=host, frame_offs=list(hs.frame_offs), lengths=lengths, watch=watch)
@@ -416,9 +425,19 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
     # launching thread (SER_PINNED_DECODE=0: A/B knob, the round-2 form)
     pinned_decode = torch.cuda.is_available() and os.environ.get("SER_PINNED_DECODE", "1") == "1"
 
+    # --resample: the raw samples go to the GPU at the file's own rate and ser_resample_v runs ahead of the forward (an extractor without
+    # upload_resampled -- the stubs of the host tests and tools -- keeps the host filter, as does a rate whose bank would be too large)
+    gpu_resample = args.resample and hasattr(ex, "upload_resampled")
+
     def decode(path):
+        """(path, (samples, their rate), None) or (path, None, error)."""
         try:
-            return path, load_wav_16k(path, resample=args.resample, pinned=pinned_decode), None
+            if not gpu_resample:
+                return path, (load_wav_16k(path, resample=args.resample, pinned=pinned_decode), TARGET_SR), None
+            x, sr = decode_wav(path, pinned_decode)
+            if sr != TARGET_SR and max(resample_ratio(sr)) > RESAMPLE_MAX_R:
+                x, sr = host_resample(x, sr), TARGET_SR
+            return path, (x, sr), None
         except Exception as e:                            # noqa: BLE001  (reference: except Exception -> print)
             return path, None, e
 
@@ -450,17 +469,22 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
         writes = []
         inflight = deque()
 
+        def run(fn, items, *a, **k):
+            """fn(waves, ...) of (samples, rate) items; the rates go along only where the GPU resamples."""
+            waves = [w for w, _ in items]
+            return fn(waves, *a, rates=[sr for _, sr in items], **k) if gpu_resample else fn(waves, *a, **k)
+
         def one_by_one(good):
             """A failed batch is retried per utterance so one bad file cannot drop its neighbours."""
             nonlocal done, audio_s
             if torch.cuda.is_available():
                 torch.cuda.synchronize()                      # the synchronous path shares slot 0's arena with the pipeline
-            for path, wave in good:
+            for path, (wave, sr) in good:
                 try:
-                    f = ex.extract([wave], layer_index)[0]
+                    f = run(ex.extract, [(wave, sr)], layer_index)[0]
                     writes.append(pool.submit(write, (path, f)))
                     done += 1
-                    audio_s += len(wave) / 16000.0
+                    audio_s += resampled_len(len(wave), sr) / 16000.0
                 except Exception as e1:                       # noqa: BLE001
                     print(f"Failed to process {path}: {e1}")
 
@@ -476,7 +500,7 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
             ex.hold(ticket["slot"], futs)
             writes.extend(futs)
             done += len(good)
-            audio_s += sum(len(w) for _, w in good) / 16000.0
+            audio_s += sum(resampled_len(len(w), sr) for _, (w, sr) in good) / 16000.0
 
         tm = dict(decode_wait=0.0, submit=0.0, finish=0.0)   # where the launching thread spends its time (--timing)
         clock = time.perf_counter
@@ -487,11 +511,11 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
             if bi + 1 < len(batches):
                 pending = pool.map(decode, batches[bi + 1])          # decode the next batch while the GPU works
             good = []
-            for path, wave, err in decoded:
+            for path, item, err in decoded:                   # item: (samples, their rate)
                 if err is not None:
                     print(f"Failed to process {path}: {err}")
                 else:
-                    good.append((path, wave))
+                    good.append((path, item))
             if good and bad_layer:
                 for path, _ in good:
                     print(f"Failed to process {path}: tuple index out of range")
@@ -499,15 +523,15 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
                 try:
                     if pipelined:
                         t_a = clock()
-                        ticket = ex.submit([w for _, w in good], layer_index, slot=bi % ex.SLOTS)
+                        ticket = run(ex.submit, [item for _, item in good], layer_index, slot=bi % ex.SLOTS)
                         tm["submit"] += clock() - t_a
                         ticket["good"] = good
                         inflight.append(ticket)
                     else:
-                        feats = ex.extract([w for _, w in good], layer_index)
-                        for (path, wave), f in zip(good, feats):
+                        feats = run(ex.extract, [item for _, item in good], layer_index)
+                        for (path, (wave, sr)), f in zip(good, feats):
                             writes.append(pool.submit(write, (path, f)))
-                            audio_s += len(wave) / 16000.0
+                            audio_s += resampled_len(len(wave), sr) / 16000.0
                         done += len(good)
                 except Exception:                             # noqa: BLE001
                     while inflight:                           # keep the per-slot order simple: drain, then retry singly

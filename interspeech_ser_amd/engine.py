@@ -1167,6 +1167,77 @@ class SpeechEncoder(_EncoderBase):
         pins[slot] = (pin, evt)
         return dev
 
+    def _resample_bank(self, up: int, down: int):
+        """(element offset, half) of the (up, down) polyphase bank inside this encoder's float64 bank buffer on the device; a ratio met
+        for the first time is appended (one blocking copy per ratio and encoder).  Appending never moves what launches in flight read: a
+        buffer that runs out of room is succeeded by a larger one and kept alive beside it."""
+        from .frontend import polyphase_bank
+        rs = self.__dict__.setdefault("_rs_banks", dict(buf=None, used=0, offs={}, retired=[]))
+        hit = rs["offs"].get((up, down))
+        if hit is not None:
+            return hit
+        h, half = polyphase_bank(up, down)
+        if rs["buf"] is None or rs["used"] + len(h) > rs["buf"].numel():
+            grown = torch.empty(max(1 << 16, 2 * (rs["used"] + len(h))), dtype=torch.float64, device=self.device)
+            if rs["buf"] is not None:
+                grown[: rs["used"]].copy_(rs["buf"][: rs["used"]])
+                rs["retired"].append(rs["buf"])
+            rs["buf"] = grown
+        off = rs["used"]
+        rs["buf"][off: off + len(h)].copy_(torch.from_numpy(h.copy()))      # the cached bank is read-only
+        torch.cuda.current_stream().synchronize()           # every slot's stream may read the bank from now on
+        rs["used"] = off + len(h)
+        rs["offs"][(up, down)] = (off, half)
+        return off, half
+
+    def upload_resampled(self, waves: Sequence[np.ndarray], rates: Sequence[int], slot: int = 0):
+        """``upload`` for utterances at their files' own sample rates: stages the raw samples like ``upload`` does, and enqueues ONE
+        ``ser_resample_v`` launch on the current stream that brings the ragged, mixed-rate batch to 16 kHz (Kaiser beta 14 polyphase
+        FIR, the ``--resample`` filter of frontend.load_wav_16k; parity with librosa's soxr_hq unpinned).  Returns (packed 16 kHz
+        device buffer, lengths) for ``forward``.  A batch that is all 16 kHz goes through plain ``upload``."""
+        from .frontend import TARGET_SR, resample_ratio
+        rates = [int(r) for r in rates]
+        if len(rates) != len(waves):
+            raise ValueError("one sample rate per utterance")
+        if all(r == TARGET_SR for r in rates):
+            return self.upload(waves, slot), [len(w) for w in waves]
+        B = len(waves)
+        ratios = [resample_ratio(r) for r in rates]
+        n_in = [len(w) for w in waves]
+        n_out = [(n * u + d - 1) // d for n, (u, d) in zip(n_in, ratios)]
+        banks = [(0, 0) if u == d == 1 else self._resample_bank(u, d) for u, d in ratios]
+        raw = self.upload(waves, slot)
+        # ---- O(B) tables -> this slot's pinned blob (int64 words: in_offs, out_offs, bank_off; then int32: up, down, half), one async copy
+        words = 3 * B + 2 + (3 * B + 1) // 2
+        tabs = self.__dict__.setdefault("_rs_tab", {})
+        host, dev, evt = tabs.get(slot, (None, None, None))
+        if host is None or host.numel() < words:
+            host = torch.empty(max(words, 256), dtype=torch.int64).pin_memory()
+            dev, evt = torch.empty(host.numel(), dtype=torch.int64, device=self.device), None
+        elif evt is not None:
+            evt.synchronize()                                 # the previous batch's copy out of the blob has finished
+        h64 = host.numpy()
+        h64[0: B + 1] = np.concatenate([[0], np.cumsum(n_in)])
+        h64[B + 1: 2 * B + 2] = np.concatenate([[0], np.cumsum(n_out)])
+        h64[2 * B + 2: 3 * B + 2] = [o for o, _ in banks]
+        h32 = h64[3 * B + 2:].view(np.int32)
+        h32[0: B] = [u for u, _ in ratios]
+        h32[B: 2 * B] = [d for _, d in ratios]
+        h32[2 * B: 3 * B] = [hf for _, hf in banks]
+        dev[:words].copy_(host[:words], non_blocking=True)
+        evt = torch.cuda.Event()
+        evt.record()
+        tabs[slot] = (host, dev, evt)
+        out = torch.empty(int(sum(n_out)), dtype=torch.float32, device=self.device)
+        a = _lib.ResampleArgs()
+        base, i32 = dev.data_ptr(), dev.data_ptr() + 8 * (3 * B + 2)
+        a.wav, a.in_offs, a.out_offs, a.bank_off = raw.data_ptr(), base, base + 8 * (B + 1), base + 8 * (2 * B + 2)
+        a.up, a.down, a.half = i32, i32 + 4 * B, i32 + 8 * B
+        a.bank, a.out = self._rs_banks["buf"].data_ptr(), out.data_ptr()
+        a.total_in, a.total_out, a.max_out, a.B = int(sum(n_in)), int(sum(n_out)), int(max(n_out)), B
+        check(lib.ser_resample_v(C.byref(a), _stream()), "ser_resample_v")
+        return out, n_out
+
     def download(self, t: torch.Tensor) -> torch.Tensor:
         """Device fp32 tensor -> fresh pinned host tensor (async D2H + one synchronisation)."""
         host = torch.empty(t.shape, dtype=t.dtype).pin_memory()
@@ -1406,6 +1477,8 @@ class WhisperEncoder(_EncoderBase):
         return pl
 
     upload = SpeechEncoder.upload
+    _resample_bank = SpeechEncoder._resample_bank
+    upload_resampled = SpeechEncoder.upload_resampled
     download = SpeechEncoder.download
 
     def _logmel(self, pl, packed_wave: torch.Tensor) -> None:

@@ -9,6 +9,7 @@ Mirrors, in this order, the reference's ``librosa.load(path, sr=16000)``
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 import wave as _wave
@@ -54,18 +55,43 @@ def _native_wav(path: str, pinned: bool = False):
     return x, int(sr.value)
 
 
-def load_wav_16k(path: str, resample: bool = False, pinned: bool = False) -> np.ndarray:
-    """Decode a RIFF/WAVE file to mono float32 in [-1, 1] the way soundfile (behind
-    ``librosa.load``) does: integer PCM / 2^(bits-1), channels averaged.
-    16 kHz input is bit-faithful to the reference.  Other rates: the reference resamples with soxr_hq
-    (librosa 0.10.1), which is not available offline and not restated -- by default such
-    files raise and the driver logs "Failed to process" like any other per-file error; with
-    ``resample=True`` (driver flag ``--resample``) they go through a Kaiser-windowed polyphase filter
-    (``scipy.signal.resample_poly``): usable features, but PARITY UNPINNED against the reference's resampler.
-    16 kHz files take the native reader (same arithmetic, no GIL); everything else the Python path below."""
-    native = _native_wav(path, pinned)
-    if native is not None and native[1] == TARGET_SR:
-        return native[0]
+def resample_ratio(sr: int):
+    """(up, down) of the rational rate change sr -> 16 kHz, in lowest terms."""
+    sr = int(sr)
+    if sr <= 0:
+        raise UnsupportedAudio(f"sample rate {sr} Hz")
+    g = math.gcd(sr, TARGET_SR)
+    return TARGET_SR // g, sr // g
+
+
+def resampled_len(n: int, sr: int) -> int:
+    """Samples of an n-sample utterance after resampling to 16 kHz: ceil(n * 16000 / sr) in integers (librosa ``resample`` +
+    ``fix_length``; scipy's ``resample_poly`` has the same rule).  Every frame count follows from it."""
+    up, down = resample_ratio(sr)
+    return (int(n) * up + down - 1) // down
+
+
+RESAMPLE_MAX_R = 1024     # largest max(up, down) whose bank goes to the device (every standard rate is <= 441); beyond it the host path
+
+
+@functools.lru_cache(maxsize=None)
+def polyphase_bank(up: int, down: int):
+    """(h, half): the float64 FIR ``scipy.signal.resample_poly(x, up, down, window=("kaiser", 14.0))`` designs, restated with numpy:
+    h[k] = up * w[k] / sum(w), w[k] = sinc((k - half) / R) / R * kaiser_14(2 half + 1)[k], R = max(up, down), half = 10 R.
+    Read-only and cached: ser_resample_v (engine.upload_resampled) reads it on the device."""
+    up, down = int(up), int(down)
+    R = max(up, down)
+    half = 10 * R
+    k = np.arange(2 * half + 1, dtype=np.float64)
+    w = np.sinc((k - half) / R) / R * np.kaiser(2 * half + 1, 14.0)
+    h = up * (w / w.sum())
+    h.setflags(write=False)
+    return h, half
+
+
+def _python_wav(path: str):
+    """The Python decoder: the sample formats ``ser_wav_read_f32`` declines, and every file when the native reader is switched off.
+    (mono fp32 samples, rate)."""
     try:
         with _wave.open(path, "rb") as wf:
             sr, ch, width, n = wf.getframerate(), wf.getnchannels(), wf.getsampwidth(), wf.getnframes()
@@ -94,14 +120,40 @@ def load_wav_16k(path: str, resample: bool = False, pinned: bool = False) -> np.
         x = x.reshape(-1)
     if ch > 1:
         x = x.reshape(-1, ch).mean(axis=1).astype(np.float32)
+    return np.ascontiguousarray(x, dtype=np.float32), int(sr)
+
+
+def decode_wav(path: str, pinned: bool = False):
+    """Decode a RIFF/WAVE file to (mono float32 samples in [-1, 1], the file's own sample rate) the way soundfile (behind
+    ``librosa.load``) does: integer PCM / 2^(bits-1), channels averaged.  The native reader's result at ANY rate (no GIL, one pass over
+    the file); the Python decoder for the sample formats it declines."""
+    native = _native_wav(path, pinned)
+    if native is not None:
+        return native
+    return _python_wav(path)
+
+
+def host_resample(x: np.ndarray, sr: int) -> np.ndarray:
+    """The host form of the ``--resample`` filter (``scipy.signal.resample_poly``, float64, Kaiser beta 14): what ser_resample_v computes
+    on the device, for the callers without one and for rates beyond RESAMPLE_MAX_R.  PARITY UNPINNED against librosa's soxr_hq."""
+    from scipy.signal import resample_poly
+    up, down = resample_ratio(sr)
+    return np.ascontiguousarray(resample_poly(x.astype(np.float64), up, down, window=("kaiser", 14.0)).astype(np.float32))
+
+
+def load_wav_16k(path: str, resample: bool = False, pinned: bool = False) -> np.ndarray:
+    """``decode_wav`` for 16 kHz consumers.  16 kHz input is bit-faithful to the reference.  Other rates: the reference resamples with
+    soxr_hq (librosa 0.10.1), which is not available offline and not restated -- by default such
+    files raise and the driver logs "Failed to process" like any other per-file error; with
+    ``resample=True`` (driver flag ``--resample``) they go through a Kaiser-windowed polyphase filter
+    (``scipy.signal.resample_poly`` here on the host; the drivers run the same filter on the GPU, engine.upload_resampled): usable
+    features, but PARITY UNPINNED against the reference's resampler.  A file is decoded once, by the native reader where it can."""
+    x, sr = decode_wav(path, pinned)
     if sr != TARGET_SR:
         if not resample:
             raise UnsupportedAudio(f"sample rate {sr} Hz: only {TARGET_SR} Hz input is supported (pass --resample for a "
                                    f"polyphase resampler whose parity with librosa's soxr_hq is unpinned)")
-        from math import gcd
-        from scipy.signal import resample_poly
-        g = gcd(int(sr), TARGET_SR)
-        x = resample_poly(x.astype(np.float64), TARGET_SR // g, int(sr) // g, window=("kaiser", 14.0)).astype(np.float32)
+        x = host_resample(x, sr)
     return np.ascontiguousarray(x, dtype=np.float32)
 
 
