@@ -38,12 +38,6 @@ extern "C" { void* ser_attn_dbg_ptr = nullptr; }
 // and the bias path does not zero accumulators it is about to overwrite.
 // NWV waves (x 32 queries) per block.  8 waves halve the K/V global->LDS traffic and the bias-row copies per query:
 // used for bf16 head dims <= 64 once an utterance has more than one 128-query tile.
-#ifndef SER_ATTN_LAZY
-#define SER_ATTN_LAZY 1          // pre-scaled launches keep a STALE row maximum inside the accumulators' start value (see the tile loop)
-#endif
-#ifndef SER_ATTN_MINW
-#define SER_ATTN_MINW 2          // waves per SIMD the register allocation must leave room for (A/B knob at build time)
-#endif
 // B2D: dense additive bias from global memory instead of the relative-position table (needs PRE, excludes TBL).
 // GB: the relative-position table is read from GLOBAL memory (L2: 2T-1 floats per head) instead of an LDS window -- the form for
 // utterances whose window (T + 192 distances x 4 shifted copies) does not fit the 160 KiB of LDS (beyond ~2 min of audio): the
@@ -59,7 +53,7 @@ template <int DHP, int MODE, bool PRE, bool TBL, int NWV = 4, bool B2D = false, 
 // waves per SIMD the registers leave room for: two everywhere (round 4: the 96-wide two-plane forms and the 128-wide ones WITHOUT a bias table
 // fit 256 registers unspilled -- head dim 80 in the 3-product modes 98.9 -> 49.9 us per 8 x 499 frames) except the 128-wide two-plane form
 // with a bias table (208 spilled registers at two; no encoder uses it: WavLM's head dim is 64)
-__global__ __launch_bounds__(64 * NWV, (DHP == 128 && mode_traits<MODE>::planes == 2 && TBL) ? 1 : (OCC ? 4 : ((DHP == 64 && mode_traits<MODE>::planes == 1) ? SER_ATTN_MINW : 2)))
+__global__ __launch_bounds__(64 * NWV, (DHP == 128 && mode_traits<MODE>::planes == 2 && TBL) ? 1 : (OCC ? 4 : 2))
 void attention_kernel(const AttnParams p) {
     constexpr int NT = 64 * NWV;                // threads per block
     // NP: planes of Q and K (the logit path S = K Q^T: 3 products when 2), NPV: planes of V and P.  FP16Q (the "f16q" numerics
@@ -322,9 +316,9 @@ void attention_kernel(const AttnParams p) {
     // score -- so the MFMA chain delivers scores already relative to the running maximum and the exponentials need no subtraction; m_run is
     // only raised when a tile's scores exceed it by more than LAZY_T (P <= 2^LAZY_T: far inside fp32 / fp16 range), which after the first
     // tiles is rare, and O and l are rescaled in that branch only.  O / l is unchanged: every P of a row carries the same factor
-    // 2^(m_true - m_run).  Measured (tools/attn_lazy_ab.sh, two A/B pairs): WavLM-large step 1 968 / 1 974 -> 1 988 / 1 985 utt/s.  Without a
+    // 2^(m_true - m_run).  Measured (two A/B pairs, profiles/r03_attn_lazy_ab.txt): WavLM-large step 1 968 / 1 974 -> 1 988 / 1 985 utt/s.  Without a
     // bias table the start value needs its own 16-register block that hipcc copies per tile: Whisper 380.4 -> 377.2, so those keep the exact maximum.
-    constexpr bool LAZY = SER_ATTN_LAZY && PRE && TBL;
+    constexpr bool LAZY = PRE && TBL;
     constexpr float LAZY_T = 8.0f;
     float m_run = LAZY ? 0.f : -1e30f, l_run = 0.f;
 #ifdef SER_ATTN_DBG
@@ -799,12 +793,6 @@ extern "C" int ser_attention_v(const ser_attention_args* args, void* stream) {
     p.nitems = (int)grid.x;
     hipStream_t s = (hipStream_t)stream;
     const bool pre = scale <= 0.f;
-#ifdef SER_EXPERIMENTS
-    if (!gbias) {                                                 // round-4 experiment (make EXPERIMENTS=1; SER_ATTN_RESIDENT=1): K / V of a whole
-        const int r = ser_attention_resident(p, mode, max_frames, s);      // (utterance, head) resident in LDS, attention_res.hip -- not faster, see its header
-        if (r <= 0) return r;
-    }
-#endif
 #define SER_ATTN_O(D_, M_, O_) (pre ? (table ? launch_attention<D_, M_, true, true, 4, false, false, O_>(p, grid, lds, s) : launch_attention<D_, M_, true, false, 4, false, false, O_>(p, grid, lds, s)) \
                                     : (table ? launch_attention<D_, M_, false, true, 4, false, false, O_>(p, grid, lds, s) : launch_attention<D_, M_, false, false, 4, false, false, O_>(p, grid, lds, s)))
 #define SER_ATTN(D_, M_) SER_ATTN_O(D_, M_, false)

@@ -1,4 +1,4 @@
-// Shared by the two forms of ser_attention: the tiled kernel (attention.hip) and the resident-K/V kernel (attention_res.hip).
+// Parameter block, debug stamps and LDS swizzles of ser_attention (attention.hip).
 #pragma once
 #include "ser_common.h"
 
@@ -28,7 +28,7 @@ struct AttnParams {
     unsigned short* out;
     int64_t ldo, out_plane;
     int H, dh, B, nq;
-    int nitems;           // grid size of the one-block-per-item form (PERSIST blocks walk items up to it)
+    int nitems;           // grid size (one block per item); no kernel reads it since the persistent forms left, kept so the argument layout stays
     int bias_stride;      // floats per shifted bias copy in LDS
     float scale;
     // dense additive bias (DeBERTa's disentangled-attention terms, built by ser_deberta_bias): [B][H][T][b2d_ld] fp32 in the
@@ -76,7 +76,3 @@ __device__ __forceinline__ int v_unit_swz(int key, int unit) {
 }
 
 struct __attribute__((packed, aligned(4))) f32x4_u { float v[4]; };       // 16-byte load from a 4-byte aligned address
-
-// attention_res.hip: K and V of one (utterance, head) resident in LDS.  Returns 0 when launched, < 0 on error, 1 when the launch
-// does not fit this form (the tiled kernel takes it).
-int ser_attention_resident(const AttnParams& p, int mode, int max_frames, hipStream_t s);

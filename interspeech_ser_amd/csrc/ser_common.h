@@ -136,17 +136,8 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 v) {
 // the conv-0 LayerNorm+GELU epilogue is VALU-bound (135 -> 118 us per 8-utterance group) and so is part of FC1's.
 // The constants are -c_k * log2(e) so that v_exp_f32 (2^x) evaluates exp(-y); v is clamped to +-8 inside the polynomial
 // only (beyond it the quintic's sign would flip near |v| = 10.7), the result still scales the unclamped v.
-__device__ __forceinline__ float gelu_fast(float v) {
-    const float x = __builtin_amdgcn_fmed3f(v, -8.0f, 8.0f);
-    const float u = x * x;
-    float p = 1.01881229e-03f;
-    p = fmaf(p, u, -1.06803738e-01f);
-    p = fmaf(p, u, -2.30109051e+00f);
-    const float e = __builtin_amdgcn_exp2f(x * p);
-    return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
-// the same arithmetic on two values through v_pk_mul / v_pk_fma / v_pk_add_f32 (6 packed + 2 clamps + 4 transcendental issues per pair
-// instead of 14 + 4): identical results, element for element.  Step 2 067 / 2 064 / 2 066 -> 2 072 / 2 075 / 2 072 utt/s (tools/lib_ab.sh).
+// Two values at a time through v_pk_mul / v_pk_fma / v_pk_add_f32 (6 packed + 2 clamps + 4 transcendental issues per pair instead of
+// 14 + 4 for two scalar evaluations): identical results, element for element.  Step 2 067 / 2 064 / 2 066 -> 2 072 / 2 075 / 2 072 utt/s (tools/lib_ab.sh).
 __device__ __forceinline__ f32x2 gelu_fast2(f32x2 v) {
     f32x2 x;
     x[0] = __builtin_amdgcn_fmed3f(v[0], -8.0f, 8.0f);
@@ -165,15 +156,10 @@ __device__ __forceinline__ f32x2 gelu_fast2(f32x2 v) {
     r[1] = __builtin_amdgcn_rcpf(e[1]);
     return v * r;
 }
-#ifndef SER_GELU_PK
-#define SER_GELU_PK 1
-#endif
 template <bool FAST>
 __device__ __forceinline__ f32x2 gelu2(f32x2 v) {
-    if constexpr (FAST) {
-        if constexpr (SER_GELU_PK) return gelu_fast2(v);
-        else return (f32x2){gelu_fast(v[0]), gelu_fast(v[1])};
-    } else return gelu_erf2(v);
+    if constexpr (FAST) return gelu_fast2(v);
+    else return gelu_erf2(v);
 }
 
 // One MFMA step on 8 + 8 operand elements per lane in MODE's 16-bit format (same lane maps for bf16 and f16).

@@ -125,16 +125,11 @@ def test_gemm_integer_exact(L, mode, M, N, K):
 
 
 @pytest.mark.parametrize("mode", [1, 2, 3])
-@pytest.mark.parametrize("cfg", [1, 2, 3, 4])
+@pytest.mark.parametrize("cfg", [1, 2, 3])
 @pytest.mark.parametrize("M,N,K", [(700, 520, 256), (257, 264, 64), (1030, 128, 640), (300, 136, 128), (140, 256, 192), (129, 8, 320)])
 def test_gemm_every_tile_config_integer_exact(L, mode, cfg, M, N, K):
     """128x128 / 256x128 / 256x256 block tiles (2- and 3-stage rings; K = 64..640 covers every ring fill / drain
-    length) forced through tile_cfg; 4 = the 256x256 tile on four waves with the hand-placed software pipeline (round 5; single-plane
-    modes -- the two-plane mode ignores it; built with `make EXPERIMENTS=1` only: a measured dead end)."""
-    if cfg == 4:
-        import subprocess
-        if b"ser_gemm_kernelILi2ELi2ELi8ELi8E" not in subprocess.run(["nm", "-D", L.LIB_PATH], capture_output=True).stdout:
-            pytest.skip("tile_cfg 4 exists in the EXPERIMENTS build only")
+    length) forced through tile_cfg."""
     g = torch.Generator().manual_seed(M + N + cfg)
     A = torch.randint(-3, 4, (M, K), generator=g).float()
     W = torch.randint(-3, 4, (N, K), generator=g).float() + (torch.arange(N)[:, None] % 3).float()
@@ -756,8 +751,8 @@ def test_attention_gate_from_operand_copy(L, mode, dh, H, pre):
     g = torch.Generator().manual_seed(dh + H)
     qkv = torch.randn(M, 3 * D, generator=g)
     qkv[:, : 2 * D] *= 1.5
-    if pre:                                            # what the encoders launch: q pre-scaled by the projection epilogue (head dim 64, single-plane
-        qkv[:, :D] *= dh ** -0.5 * 1.4426950408889634  # modes, <= 512 frames: the resident-K/V form, csrc/attention_res.hip)
+    if pre:                                            # what the encoders launch: q pre-scaled by the projection epilogue
+        qkv[:, :D] *= dh ** -0.5 * 1.4426950408889634
     qa = to_act(qkv, mode)
     qv = act_value(qa).cpu().double()
     if pre:
@@ -917,9 +912,8 @@ def test_attention_stale_running_maximum(L, mode, dh, bias):
 def test_attention_tile_and_query_block_edges(L, mode, bias, Ts):
     """Ragged batches whose lengths sit on every key-tile / query-block edge (1, 31 | 33, 64 | 65, 448 | 449, 512), a climbing score ramp
     with a late spike so that the stale running maximum is raised in later tiles, with and without the WavLM bias table, head dim 64,
-    single-plane modes, pre-scaled q.  (Written in round 4 for the K/V-resident experiment csrc/attention_res.hip -- an EXPERIMENTS-only
-    kernel; in the product library these shapes run the tiled kernel, which is what ships and what this test pins.  The gate_x form and
-    H = 16 are test_attention_gate_from_operand_copy[pre].)"""
+    single-plane modes, pre-scaled q.  (Written for the K/V-resident experiment of round 4, whose source is gone: DEADENDS.md; these shapes
+    run the tiled kernel, which is what this test pins.  The gate_x form and H = 16 are test_attention_gate_from_operand_copy[pre].)"""
     err = _prescaled_case(L, mode, 64, bias, Ts, ramp=60.0)
     assert err < mode_tol(mode, 3e-2, 3e-4), err
 

@@ -51,7 +51,7 @@ def main():
             if mode == 6:
                 g.tile_cfg = int(os.environ.get("SER_BENCH_CFG", "0"))        # 0 auto, 2 = 256x128, 3 = 256x256
             if mode in (1, 3):
-                g.tile_cfg = int(os.environ.get("SER_BENCH_CFG1", "0"))       # single-plane modes: 4 = 256x256 on four waves
+                g.tile_cfg = int(os.environ.get("SER_BENCH_CFG1", "0"))       # single-plane modes: 0 auto, 1 = 128x128, 2 = 256x128, 3 = 256x256
             g.out_act, g.ldo_act, g.out_plane_stride = oa.data_ptr(), N, M * N
             if mode == 6:
                 g.a_scale, g.a_scale_ld, g.w_scale, g.w_scale_ld = As.data_ptr(), M, Ws.data_ptr(), N
