@@ -474,6 +474,45 @@ typedef struct ser_pos_ln_args {
 } ser_pos_ln_args;
 int ser_pos_ln_v(const ser_pos_ln_args* args, void* stream);
 
+/* a22 (added under ABI 18: new entry points only, nothing existing changed)  The utterance-level tail of the organiser baseline's inference scripts (benchmark/train_eval_files/eval_cat_ser.py:164-177,
+ * eval_dim_ser.py): last_hidden_state -> AttentiveStatisticsPooling (benchmark/net/pooling.py) -> EmotionRegression (benchmark/net/ser.py).
+ * Neither launcher is a command-list op: they run after the recorded forward.  Both accumulate every sum in float64, in an order fixed
+ * by the utterance alone (never by what else is in the batch: no atomics), and round once to fp32 at each store.
+ *
+ * ser_asp_pool_v: attentive statistics pooling over a packed ragged batch.  Per utterance b with rows r = frame_offs[b] .. frame_offs[b+1]-1:
+ *   s_r = sum_d tanhf(hlin[r, d]) * a[d]          (hlin = x W^T + b of sap_linear, the caller's ser_gemm; accurate tanhf)
+ *   w_r = exp(s_r - max_r s) / sum_r exp(s_r - max_r s)
+ *   mu_d = sum_r w_r x[r, d];   rh_d = sqrt(max(sum_r w_r x[r, d]^2 - mu_d^2, 1e-5f))
+ *   out[b] = [mu | rh], 2 D wide.  One frame gives mu = x, rh = sqrt(1e-5f).
+ * Two launches: the scores (one wave per row, into the caller's workspace `scores` [rows]), then one block per (utterance, 64-column
+ * slab) that reads x once.  x [rows, ldx], hlin [rows, ldh], a [D]: fp32, 16-byte aligned, pitches multiples of 4; frame_offs int32
+ * [B + 1] on the device (the caller's contract: ascending, inside [0, rows]); out fp32 [B, ldo], ldo >= 2 D.  D % 4 == 0.  max_frames
+ * (the longest utterance) is checked against rows and changes no result.  Validated before the launch: -1 null pointer, -2 sizes. */
+typedef struct ser_asp_pool_args {
+    const float* x; int64_t ldx;
+    const float* hlin; int64_t ldh;
+    const float* a;
+    const int32_t* frame_offs;
+    float* scores;
+    float* out; int64_t ldo;
+    int32_t B, D, rows, max_frames;
+} ser_asp_pool_args;
+int ser_asp_pool_v(const ser_asp_pool_args* args, void* stream);
+
+/* ser_mlp_head_v: Linear(K, H) -> LayerNorm(H, eps) -> ReLU -> Linear(H, n_out) on B rows (EmotionRegression with one hidden layer;
+ * Dropout is the identity in eval).  p [B, ldp], W1 [H, K], b1 / gamma / beta [H], W2 [n_out, H], b2 [n_out], workspace hidden [B, H],
+ * out [B, n_out], all fp32.  Two launches: one wave per hidden unit (its W1 row in registers, looping over the B rows), then one block
+ * per row.  K % 4 == 0, K <= 4096, 1 <= n_out <= 8, p and W1 16-byte aligned, ldp a multiple of 4. */
+typedef struct ser_mlp_head_args {
+    const float* p; int64_t ldp;
+    const float* W1; const float* b1; const float* gamma; const float* beta;
+    const float* W2; const float* b2;
+    float* hidden; float* out;
+    float eps;
+    int32_t B, K, H, n_out, reserved0;
+} ser_mlp_head_args;
+int ser_mlp_head_v(const ser_mlp_head_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3

@@ -158,6 +158,26 @@ class ResampleArgs(C.Structure):
     ]
 
 
+class AspPoolArgs(C.Structure):
+    """Mirror of ``ser_asp_pool_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64), ("hlin", c_void_p), ("ldh", c_i64), ("a", c_void_p), ("frame_offs", c_void_p),
+        ("scores", c_void_p), ("out", c_void_p), ("ldo", c_i64),
+        ("B", C.c_int32), ("D", C.c_int32), ("rows", C.c_int32), ("max_frames", C.c_int32),
+    ]
+
+
+class MlpHeadArgs(C.Structure):
+    """Mirror of ``ser_mlp_head_args``."""
+    _fields_ = [
+        ("p", c_void_p), ("ldp", c_i64),
+        ("W1", c_void_p), ("b1", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
+        ("hidden", c_void_p), ("out", c_void_p),
+        ("eps", c_float),
+        ("B", C.c_int32), ("K", C.c_int32), ("H", C.c_int32), ("n_out", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
@@ -172,7 +192,8 @@ class Cmd(C.Structure):
 OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS, OP_POS_LN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
-                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_cmd": Cmd}
+                  "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
+                  "ser_mlp_head_args": MlpHeadArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -193,6 +214,8 @@ _SIGNATURES = {
     "ser_gn_stats_v": (c_int, [c_void_p, c_void_p]),
     "ser_pos_ln_v": (c_int, [c_void_p, c_void_p]),
     "ser_resample_v": (c_int, [c_void_p, c_void_p]),
+    "ser_asp_pool_v": (c_int, [c_void_p, c_void_p]),
+    "ser_mlp_head_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

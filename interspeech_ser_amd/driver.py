@@ -130,7 +130,7 @@ def find_weights(ssl_type: str, checkpoint: str, synthetic: bool, seed: int, geo
 # ------------------------------------------------------------------------ the loop
 class _Extractor:
     def __init__(self, args, whisper: bool, device: str):
-        from .engine import POST_LN_MODES, build_encoder
+        from .engine import build_encoder
         self.args, self.whisper = args, whisper
         self.geo = C.resolve_geometry(args.ssl_type, args.checkpoint)      # config.json of the checkpoint, else the built-in table
         if whisper != (self.geo.family == C.FAMILY_WHISPER):
@@ -148,21 +148,28 @@ class _Extractor:
         if D.broadcast_int(1 if (rank == 0 and sd is None) else 0) == 1:
             raise OSError(err or "rank 0 found no checkpoint")
         sd, self.bcast_s, self.bcast_bytes = D.broadcast_state_dict(sd)
-        if args.mode in ("f16mf", "f16m") and (self.geo.hidden % 64 or self.geo.ffn % 64):
-            # the block-scaled cross-term format works on 64-deep K tiles: a geometry whose widths are not multiples of 64 (none of the
-            # reference's four) runs the 3-product split everywhere instead -- same or better parity, ~10 % slower
-            print(f"--mode {args.mode} needs hidden / feed-forward widths that are multiples of 64 (here {self.geo.hidden} / {self.geo.ffn}): using f16x")
-            args.mode = "f16x"
-        if not whisper and not self.geo.stable_layer_norm and args.mode not in POST_LN_MODES:
-            # the post-LayerNorm (*-base) encoders run the text encoders' modes; the others need FP16M copies out of ser_layernorm
-            print(f"--mode {args.mode} is not implemented for post-LayerNorm encoders ({args.ssl_type}): using f16x")
-            args.mode = "f16x"
+        args.mode = self.supported_mode(self.geo, args.mode, whisper, args.ssl_type)
         normalize = True if whisper else C.resolve_do_normalize(args.ssl_type, args.checkpoint)   # AutoFeatureExtractor's do_normalize
         self.enc = build_encoder(self.geo, sd, device, args.mode, normalize=normalize)
         del sd                                                # the fp32 broadcast bucket (views of it) is not needed any more
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         self.average = args.use_average == "y"
+
+    @staticmethod
+    def supported_mode(geo, mode: str, whisper: bool, name: str) -> str:
+        """``mode``, or the mode that runs instead on this geometry (said in one printed line)."""
+        from .engine import POST_LN_MODES
+        if mode in ("f16mf", "f16m") and (geo.hidden % 64 or geo.ffn % 64):
+            # the block-scaled cross-term format works on 64-deep K tiles: a geometry whose widths are not multiples of 64 (none of the
+            # reference's four) runs the 3-product split everywhere instead -- same or better parity, ~10 % slower
+            print(f"--mode {mode} needs hidden / feed-forward widths that are multiples of 64 (here {geo.hidden} / {geo.ffn}): using f16x")
+            mode = "f16x"
+        if not whisper and not geo.stable_layer_norm and mode not in POST_LN_MODES:
+            # the post-LayerNorm (*-base) encoders run the text encoders' modes; the others need FP16M copies out of ser_layernorm
+            print(f"--mode {mode} is not implemented for post-LayerNorm encoders ({name}): using f16x")
+            mode = "f16x"
+        return mode
 
     @classmethod
     def from_encoder(cls, args, enc, whisper: bool, weight_source: str = "caller's encoder"):
@@ -180,13 +187,18 @@ class _Extractor:
             return self.enc.upload(waves, slot), [len(w) for w in waves]
         return self.enc.upload_resampled(waves, rates, slot)
 
+    def select(self, hs, layer_index, slot: int = 0) -> torch.Tensor:
+        """The device rows of a forward that go back to the host: one hidden state or the mean of the last four (a subclass may put
+        further device work here, on the current stream; baseline.BaselinePredictor runs its head)."""
+        from .engine import mean_last4
+        return mean_last4(hs) if self.average else hs.states[layer_index]
+
     def extract(self, waves: List[np.ndarray], layer_index: int, rates: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
         """One ragged batch -> one CPU [T, D] tensor per utterance (rows a19/a20), synchronously."""
-        from .engine import mean_last4
         dev, lengths = self.upload_resampled(waves, rates)
         hs = self.enc.forward(dev, lengths, last_state=None if self.average else layer_index)
         self._check_range(hs.take_range_bits())
-        sel = mean_last4(hs) if self.average else hs.states[layer_index]
+        sel = self.select(hs, layer_index)
         out = []
         host = self.enc.download(sel)
         for b, n in enumerate(lengths):
@@ -233,7 +245,6 @@ class _Extractor:
     def submit(self, waves: List[np.ndarray], layer_index: int, slot: int, rates: Optional[Sequence[int]] = None):
         """Enqueue upload -> forward -> selection -> D2H of one ragged batch on slot ``slot``'s stream; returns a
         ticket for ``collect``.  Nothing here waits for the GPU."""
-        from .engine import mean_last4
         st = self.__dict__.setdefault("_streams", {})
         if slot not in st:
             st[slot] = torch.cuda.Stream(device=self.enc.device)
@@ -248,7 +259,7 @@ class _Extractor:
                 st[slot].wait_event(computed[-self.RUNNING])
             hs = self.enc.forward(dev, lengths, slot=slot, last_state=None if self.average else layer_index)
             t2 = clock()
-            sel = mean_last4(hs) if self.average else hs.states[layer_index]
+            sel = self.select(hs, layer_index, slot)
             watch = None
             if hs.range_flag is not None:                         # the slot's guard word, read back with the features and cleared
                 watch = self.__dict__.setdefault("_range_pin", {}).get(slot)

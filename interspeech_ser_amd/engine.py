@@ -206,9 +206,12 @@ class HiddenStates:
     frame_offs[b]:frame_offs[b+1] (crop to the true frame count is implicit)."""
 
     def __init__(self, states: torch.Tensor, frame_offs: Sequence[int], computed: Optional[int] = None,
-                 range_flag: Optional[torch.Tensor] = None):
+                 range_flag: Optional[torch.Tensor] = None, frame_offs_dev: Optional[torch.Tensor] = None):
         self.states = states
         self.frame_offs = list(int(x) for x in frame_offs)
+        # the same offsets as int32 [B + 1] on the device, where the forward's plan keeps them (valid until the slot's next plan): what a
+        # consumer that stays on the device reads (PoolHead)
+        self.frame_offs_dev = frame_offs_dev
         # states[0 .. computed-1] hold this batch's results; a forward stopped early (``last_state``) leaves the rest stale
         self.computed = states.shape[0] if computed is None else int(computed)
         self.range_flag = range_flag
@@ -707,7 +710,8 @@ class _EncoderBase:
                 if key in tape.inputs:
                     tape.inputs[key].wav = packed_wave.data_ptr()
             tape.run(pl.get("sizes", {}), self._s(), last_state)
-        return HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1, range_flag=flag)
+        return HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1, range_flag=flag,
+                            frame_offs_dev=pl.get("frame_offs"))
 
     def recorded_tape(self, lengths: Sequence[int], slot: int) -> Tape:
         """the command list the slot's last forward over ``lengths`` replayed (SpeechEncoder: per arena; Whisper: per plan)"""
@@ -1791,6 +1795,104 @@ def mean_last4(hs: HiddenStates) -> torch.Tensor:
     check(lib.ser_mean4(s[-4].data_ptr(), s[-3].data_ptr(), s[-2].data_ptr(), s[-1].data_ptr(), out.data_ptr(), n, _stream()),
           "ser_mean4")
     return out
+
+
+class PoolHead:
+    """The organiser baseline's utterance-level tail on the device (benchmark/train_eval_files/eval_cat_ser.py:164-177):
+    ``last_hidden_state`` -> AttentiveStatisticsPooling -> EmotionRegression -> ``[B, n_out]`` logits, so a waveform -> prediction run
+    brings ``n_out`` floats per utterance back instead of ``[T, D]``.  Built from a speech encoder (its device and numerics mode) and the
+    two state dicts of ``final_pool.pt`` / ``final_ser.pt``.  ``forward`` enqueues five steps on the current stream, after the
+    encoder's recorded forward (no command-list op, the tapes stay as they are):
+      operand copy of ``hs.states[-1]`` (ser_pack_rows_flagged) -> ser_gemm with sap_linear (bias epilogue, fp32 out)
+      -> ser_asp_pool_v (scores, weighted moments) -> ser_mlp_head_v (hidden units, LayerNorm / ReLU / outputs).
+    GEMM operand format: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo in every other mode -- the product feeds tanh and
+    then a softmax over the frames, where single-product rounding is not benign."""
+
+    def __init__(self, enc: "_EncoderBase", pool_sd, ser_sd):
+        geo = enc.geo
+        if geo.family == FAMILY_WHISPER or not isinstance(enc, SpeechEncoder):
+            raise ValueError("PoolHead runs behind the speech encoders (WavLM / wav2vec2 / HuBERT / data2vec-audio), not Whisper or text")
+        D = geo.hidden
+        if D % 64:
+            raise ValueError(f"PoolHead needs a hidden width that is a multiple of 64 (ser_gemm's K rule), got {D}")
+        self.enc, self.D, self.device = enc, D, enc.device
+        self.op_mode = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X}.get(enc.mode_name, _lib.MODE_FP16X)
+        w, b, a = pool_sd["sap_linear.weight"], pool_sd["sap_linear.bias"], pool_sd["attention"]
+        if tuple(w.shape) != (D, D) or tuple(b.shape) != (D,) or a.numel() != D:
+            raise ValueError(f"pooling weights do not match hidden width {D}: sap_linear.weight {tuple(w.shape)}, attention {tuple(a.shape)}")
+        self.sap = enc._linear(w, b, mode=self.op_mode, name="final_pool.pt sap_linear.weight")
+        self.att = enc._dev_f32(a.reshape(D))
+        w1, w2 = ser_sd["fc.0.0.weight"], ser_sd["out.0.weight"]
+        self.H, self.n_out = int(w1.shape[0]), int(w2.shape[0])
+        if w1.shape[1] != 2 * D or w2.shape[1] != self.H or not 1 <= self.n_out <= 8 or 2 * D > 4096:
+            raise ValueError(f"head weights do not match: fc.0.0.weight {tuple(w1.shape)} (expected [H, {2 * D}]), out.0.weight "
+                             f"{tuple(w2.shape)} (expected [n_out <= 8, H])")
+        self.w1, self.b1 = enc._dev_f32(w1), enc._dev_f32(ser_sd["fc.0.0.bias"])
+        self.ln_g, self.ln_b = enc._dev_f32(ser_sd["fc.0.1.weight"]), enc._dev_f32(ser_sd["fc.0.1.bias"])
+        self.w2, self.b2 = enc._dev_f32(w2), enc._dev_f32(ser_sd["out.0.bias"])
+        self.ln_eps = 1e-5                                        # nn.LayerNorm's default (ser.py builds it without an eps)
+        self._bufs: Dict[int, dict] = {}
+        self.trace: Optional[list] = None                        # when a list: (name, start event, end event) per step (tools/pool_head_bench.py)
+
+    def _buffers(self, slot: int, M: int, B: int) -> dict:
+        """grow-only buffers of one pipeline slot (slots run on streams of their own, so they share nothing)"""
+        bf = self._bufs.get(slot)
+        if bf is not None and bf["M"] >= M and bf["B"] >= B:
+            return bf
+        M, B = max(M, bf["M"] if bf else 0), max(B, bf["B"] if bf else 0)
+        D, dev = self.D, self.device
+        bf = dict(M=M, B=B,
+                  xa=Act(M, D, _PLANES[self.op_mode], dev, dtype=_DTYPE[self.op_mode]),
+                  hlin=torch.empty((M, D), dtype=torch.float32, device=dev),
+                  scores=torch.empty(M, dtype=torch.float32, device=dev),
+                  pooled=torch.empty((B, 2 * D), dtype=torch.float32, device=dev),
+                  hidden=torch.empty((B, self.H), dtype=torch.float32, device=dev),
+                  out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
+                  offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
+        self._bufs[slot] = bf
+        return bf
+
+    def _step(self, name: str, fn) -> None:
+        if self.trace is None:
+            fn()
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        self.trace.append((name, e0, e1))
+
+    def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
+        """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``).  The range
+        guard of the fp16 operand copy reports into ``hs.range_flag``, the word the encoder's forward used; ``hs.states`` is only read."""
+        if hs.computed != hs.states.shape[0]:
+            raise IndexError("the head needs the last hidden state (run the forward without last_state)")
+        x = hs.states[-1]
+        M, B, D = int(hs.frame_offs[-1]), hs.batch, self.D
+        if x.shape[0] != M or x.shape[1] != D or x.stride(0) != D:
+            raise ValueError("hidden states do not match the head's width")
+        bf = self._buffers(slot, M, B)
+        st = _stream()
+        offs = hs.frame_offs_dev
+        if offs is None:
+            offs = bf["offs"][: B + 1]
+            offs.copy_(torch.tensor(hs.frame_offs, dtype=torch.int32))
+        xa = bf["xa"].first_rows(M)
+        flag = hs.range_flag.data_ptr() if (hs.range_flag is not None and self.op_mode == _lib.MODE_FP16X) else None
+        self._step("pack", lambda: check(lib.ser_pack_rows_flagged(x.data_ptr(), D, 1, M, D, 0, xa.ptr, D, xa.plane_stride, self.op_mode,
+                                                                    flag, st), "ser_pack_rows_flagged"))
+        self._step("gemm", lambda: self.enc._gemm(xa, self.sap, M, out_f32=bf["hlin"], ldo_f32=D, mode=self.op_mode))
+        p = _lib.AspPoolArgs()
+        p.x, p.ldx, p.hlin, p.ldh, p.a = x.data_ptr(), D, bf["hlin"].data_ptr(), D, self.att.data_ptr()
+        p.frame_offs, p.scores, p.out, p.ldo = offs.data_ptr(), bf["scores"].data_ptr(), bf["pooled"].data_ptr(), 2 * D
+        p.B, p.D, p.rows, p.max_frames = B, D, M, max(hs.frames(b) for b in range(B))
+        self._step("asp_pool", lambda: check(lib.ser_asp_pool_v(C.byref(p), st), "ser_asp_pool_v"))
+        h = _lib.MlpHeadArgs()
+        h.p, h.ldp, h.W1, h.b1, h.gamma, h.beta = bf["pooled"].data_ptr(), 2 * D, self.w1.data_ptr(), self.b1.data_ptr(), self.ln_g.data_ptr(), self.ln_b.data_ptr()
+        h.W2, h.b2, h.hidden, h.out, h.eps = self.w2.data_ptr(), self.b2.data_ptr(), bf["hidden"].data_ptr(), bf["out"].data_ptr(), self.ln_eps
+        h.B, h.K, h.H, h.n_out = B, 2 * D, self.H, self.n_out
+        self._step("mlp_head", lambda: check(lib.ser_mlp_head_v(C.byref(h), st), "ser_mlp_head_v"))
+        return bf["out"][:B]
 
 
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):
