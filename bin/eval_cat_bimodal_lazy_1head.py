@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Counterpart of the reference's bin/eval_cat_bimodal_lazy_1head.py: Development split through ``multimodal_ser.pt``,
-macro-F1 and ``results/dev.csv`` (interspeech_ser_amd/head.py)."""
+macro-F1 and ``results/dev.csv`` (interspeech_ser_amd/head.py).  ``--engine hip [--mode f16x|fp32x|bf16]`` runs the head as kernels of this
+library (every utterance alone, as the reference's batch_size=1 loop); the default ``--engine torch`` is the PyTorch module."""
 import os
 import sys
 

@@ -513,6 +513,97 @@ typedef struct ser_mlp_head_args {
 } ser_mlp_head_args;
 int ser_mlp_head_v(const ser_mlp_head_args* args, void* stream);
 
+/* a23 (added under ABI 18: new entry points only)  The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334,
+ * MultiModalEmotionClassifier) on packed ragged batches: every utterance alone, as the reference's evaluation runs it (batch_size = 1,
+ * bin/eval_cat_bimodal_lazy_1head.py:292) -- no pad frame enters the recurrence, the attention or a pooling softmax.  None of the four is a
+ * command-list op.  No atomics on float data; an utterance's result does not depend on what else is in the batch.
+ *
+ * ser_gru_v: the recurrence of nn.GRU(H, H, bidirectional=True), torch's convention (gates r, z, n; h_0 = 0):
+ *   r = sigmoid(gx_r + W_hr h + b_hr);  z likewise;  n = tanh(gx_n + r (W_hn h + b_hn));  h' = (1 - z) n + z h
+ * gx [rows, ldgx >= 6 H] fp32 = x W_ih^T + b_ih of BOTH directions (forward gates in columns 0 .. 3H-1, backward in 3H .. 6H-1: one ser_gemm
+ * over the stacked weight_ih matrices).  whh: fp16 hi + lo planes of the stacked [weight_hh_l0 ; weight_hh_l0_reverse] = [6 H, H]
+ * (ser_split_bf16 in SER_MODE_FP16X; whh_plane_stride in elements); bhh [6 H] fp32, stacked alike.  The backward direction runs from each
+ * utterance's own last row to its first.  out [rows, ldo >= 2 H] fp32: forward h in columns 0 .. H-1, backward in H .. 2H-1; out_act (may be
+ * NULL): the same rows as GEMM operand planes in `mode` (SER_MODE_BF16, FP32X or FP16X).
+ * Precision: W_hh h is always the 3-product split on v_mfma_f32_16x16x32_f16 (hi hi + lo hi + hi lo), h re-split into fp16 hi + lo every
+ * step (|h| < 1: no range guard); the gates are fp32 with accurate expf / tanhf.  Up to 16 utterances ride the MFMA's N dimension.
+ * Forms: a cluster of R blocks serves each (group of <= 16 utterances, direction); a block owns H / R hidden units x 3 gates, its W_hh slice
+ * resident in LDS when it fits, and the blocks exchange the new h every step through `work` as tagged 8-byte granules (double-buffered
+ * by step parity, tag = (epoch mod 4096) << 20 | step + 1; the workspace is also zeroed ahead of every launch, and a tag is never zero).
+ * cluster = 0 chooses R (the smallest whose slice fits LDS: 1 at H = 64, 32 at H = 512); an explicit value forces it and must divide H / 16.
+ * R = 1 is block-local (h through LDS, no global wait; weights streamed from L2 when they do not fit).  The order of every sum is the same
+ * for every R: results are bit-identical across cluster sizes.  At most 256 blocks per launch; the launcher loops over further groups.
+ * Every cluster wait is bounded (one second): on give-up the block stores SER_GRU_ERR_TIMEOUT to *err and the launch drains without
+ * waiting again; the caller zeroes *err, reads it back with the results and fails the batch when it is set.
+ * H % 64 == 0, H <= 512; max_frames < 2^20.  R > 1 needs work (16-byte aligned, work_bytes >= ser_gru_work_bytes) and err.
+ * ser_gru_work_bytes: the workspace bytes for (H, cluster), 0 for R = 1, -1 for a bad pair; *R_out (may be NULL) receives R. */
+#define SER_GRU_ERR_TIMEOUT 1
+typedef struct ser_gru_args {
+    const float* gx; int64_t ldgx;
+    const void* whh; int64_t whh_plane_stride;
+    const float* bhh;
+    const int32_t* frame_offs;
+    float* out; int64_t ldo;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    void* work; int64_t work_bytes;
+    uint32_t* err;
+    int32_t B, H, rows, max_frames, mode, cluster;
+    uint32_t epoch; int32_t reserved0;
+} ser_gru_args;
+int ser_gru_v(const ser_gru_args* args, void* stream);
+int64_t ser_gru_work_bytes(int32_t H, int32_t cluster, int32_t* R_out);
+
+/* ser_xattn_v: nn.MultiheadAttention(E, 1) between its in- and out-projection, over ragged pairs: utterance b's queries are rows
+ * q_offs[b] .. q_offs[b+1]-1 of q, its keys / values rows k_offs[b] .. k_offs[b+1]-1 of k / v (fp32, from ser_gemm; no mask):
+ *   ctx[r] = sum_j softmax_j(scale q[r] . k[j]) v[j]
+ * fp32 FMAs, online softmax in base 2 (logits pre-scaled by scale log2 e), one block per (utterance, 16 queries), keys in tiles of 16 from
+ * the utterance's first key: tiles never cross utterances.  out_act: ctx as GEMM operand planes in `mode` (BF16 / FP32X / FP16X; FP16X
+ * reports into range_flag, may be NULL); out_f32: ctx in fp32.  Either may be NULL, not both.  E % 64 == 0, E <= 1024; B <= 65535;
+ * q / k / v / out_f32 16-byte aligned, pitches multiples of 4.  max_q (the longest query side) sizes the grid. */
+typedef struct ser_xattn_args {
+    const float* q; int64_t ldq;
+    const float* k; int64_t ldk;
+    const float* v; int64_t ldv;
+    const int32_t* q_offs; const int32_t* k_offs;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    float* out_f32; int64_t ldo_f32;
+    uint32_t* range_flag;
+    float scale;
+    int32_t B, E, q_rows, k_rows, max_q, mode, reserved0;
+} ser_xattn_args;
+int ser_xattn_v(const ser_xattn_args* args, void* stream);
+
+/* ser_attn_pool_v: the head's attention pooling.  With x = a + b (a: the GRU output, b: the attention out-projection's fp32 output):
+ *   s_r = x[r] . w + bias;   out[u, col0 .. col0 + E - 1] = sum_r softmax_r(s) x[r]   over utterance u's rows.
+ * Pattern of ser_asp_pool_v: scores by one wave per row into the workspace `scores` [rows], then one block per (64-column slab, utterance);
+ * float64 accumulation in ascending frame order, fixed-order merges, one rounding at the store.  One frame gives a + b exactly.
+ * E % 4 == 0; a / b / w 16-byte aligned, pitches multiples of 4; ldo >= col0 + E. */
+typedef struct ser_attn_pool_args {
+    const float* a; int64_t lda;
+    const float* b; int64_t ldb;
+    const float* w;
+    const int32_t* frame_offs;
+    float* scores;
+    float* out; int64_t ldo;
+    float bias;
+    int32_t col0, B, E, rows, max_frames, reserved0;
+} ser_attn_pool_args;
+int ser_attn_pool_v(const ser_attn_pool_args* args, void* stream);
+
+/* ser_fusion_cls_v: LayerNorm(K, eps) -> Linear(K, H1) -> ReLU -> Linear(H1, n_out) on B rows (layer_norm and classifier of the head;
+ * Dropout is the identity in eval).  ser_mlp_head_v's pattern with the LayerNorm in front: p [B, ldp], gamma / beta [K], W1 [H1, K],
+ * b1 [H1], W2 [n_out, H1], b2 [n_out], workspaces xn [B, K] and hidden [B, H1], out [B, n_out], all fp32; float64 accumulation.
+ * K % 4 == 0, K <= 4096, 1 <= n_out <= 8, xn and W1 16-byte aligned. */
+typedef struct ser_fusion_cls_args {
+    const float* p; int64_t ldp;
+    const float* gamma; const float* beta;
+    const float* W1; const float* b1; const float* W2; const float* b2;
+    float* xn; float* hidden; float* out;
+    float eps;
+    int32_t B, K, H1, n_out, reserved0;
+} ser_fusion_cls_args;
+int ser_fusion_cls_v(const ser_fusion_cls_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3

@@ -26,6 +26,7 @@ ACT_GELU = 1
 WS_LOGMEL = 1
 WS_WAVE_FRAMES = 2
 WS_GN_STATS = 3
+GRU_ERR_TIMEOUT = 1             # SER_GRU_ERR_TIMEOUT: a cluster wait of ser_gru_v gave up
 RESAMPLE_TILE = 1024            # SER_RESAMPLE_TILE: output samples per block of ser_resample_v
 ABI_VERSION = 18
 
@@ -178,6 +179,48 @@ class MlpHeadArgs(C.Structure):
     ]
 
 
+class GruArgs(C.Structure):
+    """Mirror of ``ser_gru_args``."""
+    _fields_ = [
+        ("gx", c_void_p), ("ldgx", c_i64), ("whh", c_void_p), ("whh_plane_stride", c_i64), ("bhh", c_void_p), ("frame_offs", c_void_p),
+        ("out", c_void_p), ("ldo", c_i64), ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64),
+        ("work", c_void_p), ("work_bytes", c_i64), ("err", c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("rows", C.c_int32), ("max_frames", C.c_int32), ("mode", C.c_int32), ("cluster", C.c_int32),
+        ("epoch", C.c_uint32), ("reserved0", C.c_int32),
+    ]
+
+
+class XattnArgs(C.Structure):
+    """Mirror of ``ser_xattn_args``."""
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_i64), ("k", c_void_p), ("ldk", c_i64), ("v", c_void_p), ("ldv", c_i64),
+        ("q_offs", c_void_p), ("k_offs", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("out_f32", c_void_p), ("ldo_f32", c_i64),
+        ("range_flag", c_void_p), ("scale", c_float),
+        ("B", C.c_int32), ("E", C.c_int32), ("q_rows", C.c_int32), ("k_rows", C.c_int32), ("max_q", C.c_int32), ("mode", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class AttnPoolArgs(C.Structure):
+    """Mirror of ``ser_attn_pool_args``."""
+    _fields_ = [
+        ("a", c_void_p), ("lda", c_i64), ("b", c_void_p), ("ldb", c_i64), ("w", c_void_p), ("frame_offs", c_void_p),
+        ("scores", c_void_p), ("out", c_void_p), ("ldo", c_i64), ("bias", c_float),
+        ("col0", C.c_int32), ("B", C.c_int32), ("E", C.c_int32), ("rows", C.c_int32), ("max_frames", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class FusionClsArgs(C.Structure):
+    """Mirror of ``ser_fusion_cls_args``."""
+    _fields_ = [
+        ("p", c_void_p), ("ldp", c_i64), ("gamma", c_void_p), ("beta", c_void_p),
+        ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
+        ("xn", c_void_p), ("hidden", c_void_p), ("out", c_void_p), ("eps", c_float),
+        ("B", C.c_int32), ("K", C.c_int32), ("H1", C.c_int32), ("n_out", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
@@ -193,7 +236,8 @@ OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, O
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
-                  "ser_mlp_head_args": MlpHeadArgs, "ser_cmd": Cmd}
+                  "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_attn_pool_args": AttnPoolArgs,
+                  "ser_fusion_cls_args": FusionClsArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -216,6 +260,11 @@ _SIGNATURES = {
     "ser_resample_v": (c_int, [c_void_p, c_void_p]),
     "ser_asp_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_mlp_head_v": (c_int, [c_void_p, c_void_p]),
+    "ser_gru_v": (c_int, [c_void_p, c_void_p]),
+    "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "ser_xattn_v": (c_int, [c_void_p, c_void_p]),
+    "ser_attn_pool_v": (c_int, [c_void_p, c_void_p]),
+    "ser_fusion_cls_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

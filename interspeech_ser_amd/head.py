@@ -288,9 +288,16 @@ def train(config: Dict, seed: int = 7, device: Optional[str] = None) -> Dict:
     return best
 
 
-def evaluate(config: Dict, seed: int = 7, device: Optional[str] = None) -> Dict:
+def evaluate(config: Dict, seed: int = 7, device: Optional[str] = None, engine: str = "torch", mode: str = "f16x") -> Dict:
     """bin/eval_cat_bimodal_lazy_1head.py as a function: Development split through ``multimodal_ser.pt``, macro-F1,
-    ``<model_path>/results/dev.csv`` (Filename, Prediction letter, the 8 logits as class_i_prob)."""
+    ``<model_path>/results/dev.csv`` (Filename, Prediction letter, the 8 logits as class_i_prob).
+    ``engine="torch"`` (default): the PyTorch module, batches of ``config["batch_size"]`` padded to their longest utterance (padded frames
+    take part, as in the reference's class).  ``engine="hip"``: the head as kernels of this library (engine.FusionHead), 16 files at a
+    time as packed ragged batches -- every utterance alone, the arithmetic of the reference's own evaluation loop (``batch_size=1``)."""
+    if engine == "hip":
+        return _evaluate_hip(config, seed, device, mode)
+    if engine != "torch":
+        raise ValueError(f"engine must be 'torch' or 'hip', got {engine!r}")
     set_deterministic(seed)
     dev = _device(device)
     model_path = config["model_path"]
@@ -320,13 +327,116 @@ def evaluate(config: Dict, seed: int = 7, device: Optional[str] = None) -> Dict:
     return {"eval_loss": float(loss), "eval_f1": f1, "csv": csv_file, "n": len(utts)}
 
 
+HIP_BATCH = 16                      # files per packed ragged batch of the "hip" engine (one MFMA column group of ser_gru_v)
+NO_CPU_PATH = "Error: no MI355X visible -- this build has no CPU path (the CPU oracle under oracle/ is test-only)"
+
+
+def _evaluate_hip(config: Dict, seed: int, device: Optional[str], mode: str) -> Dict:
+    """``evaluate`` with the head on the device.  A batch whose range-guard word or ser_gru_v error word is set is retried file by file;
+    a file that still fails gets a printed line and no row, as in the baseline driver."""
+    if not torch.cuda.is_available():
+        print(NO_CPU_PATH)
+        return {"eval_loss": None, "eval_f1": None, "csv": None, "n": 0, "failed": 0}
+    from .engine import FusionHead
+    set_deterministic(seed)
+    dev = torch.device(device or "cuda:0")
+    model_path = config["model_path"]
+    os.makedirs(model_path, exist_ok=True)
+    log = _logger(model_path)
+    df = _frames(config)
+    val_df = df[df["Split_Set"] == "Development"]
+    names, labels = val_df["FileName"].tolist(), val_df[CLASSES].values
+    sd = torch.load(os.path.join(model_path, "multimodal_ser.pt"), map_location="cpu", weights_only=True)
+    head = FusionHead(sd, config["feat1_dim"], config["feat2_dim"], dev, mode)
+    log.info("Starting evaluation...")
+    done, rows, gold, failed = [], [], [], 0
+
+    def fail(name, err):
+        nonlocal failed
+        failed += 1
+        print(f"Failed to process {name}: {err}")
+
+    def run(items):
+        """items: (name, label row, feat1, feat2) -> error message or None; appends the rows of a clean batch"""
+        x1 = torch.cat([it[2] for it in items]).to(dev)
+        x2 = torch.cat([it[3] for it in items]).to(dev)
+        offs1 = np.concatenate([[0], np.cumsum([it[2].shape[0] for it in items])])
+        offs2 = np.concatenate([[0], np.cumsum([it[3].shape[0] for it in items])])
+        out = head.forward(x1, offs1, x2, offs2).cpu().numpy().copy()
+        err = FusionHead.failure(*head.status())
+        if err is None:
+            for it, row in zip(items, out):
+                done.append(it[0])
+                gold.append(it[1])
+                rows.append(row)
+        return err
+
+    first = True
+    for i in range(0, len(names), HIP_BATCH):
+        items = []
+        for name, lab in zip(names[i:i + HIP_BATCH], labels[i:i + HIP_BATCH]):
+            pt = name.replace(".wav", ".pt")
+            f1, f2 = os.path.join(config["lazy_dir1"], pt), os.path.join(config["lazy_dir2"], pt)
+            if first:
+                print(f1, f2)
+                first = False
+            try:
+                a, b = torch.load(f1, weights_only=True), torch.load(f2, weights_only=True)
+                if a.dim() != 2 or b.dim() != 2 or a.shape[0] < 1 or b.shape[0] < 1:
+                    raise ValueError(f"feature files must hold [T >= 1, D] matrices, got {tuple(a.shape)} and {tuple(b.shape)}")
+                items.append((name, lab, a.float().contiguous(), b.float().contiguous()))
+            except Exception as e:                              # noqa: BLE001  (per-file failure, as in the extraction drivers)
+                fail(name, e)
+        if not items:
+            continue
+        try:
+            err = run(items)
+        except Exception as e:                                  # noqa: BLE001
+            err = e
+        if err is not None and len(items) > 1:                  # one bad file must not drop its neighbours
+            for it in items:
+                try:
+                    e1 = run([it])
+                except Exception as e:                          # noqa: BLE001
+                    e1 = e
+                if e1 is not None:
+                    fail(it[0], e1)
+        elif err is not None:
+            fail(items[0][0], err)
+    loss, f1 = float("nan"), 0.0
+    if rows:
+        logits_all = torch.from_numpy(np.stack(rows))
+        labels_all = torch.tensor(np.stack(gold), dtype=torch.float)
+        loss = float(ce_weight_category(logits_all, labels_all, None))
+        f1 = macro_f1(labels_all.max(dim=1)[1].numpy(), torch.argmax(logits_all, dim=1).numpy())
+    log.info(f"|Metrics| eval_loss = {loss} eval f1 = {f1}")
+    os.makedirs(os.path.join(model_path, "results"), exist_ok=True)
+    csv_file = os.path.join(model_path, "results", "dev.csv")
+    with open(csv_file, mode="w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["Filename", "Prediction"] + [f"class_{i}_prob" for i in range(len(CLASSES))])
+        for row, utt in zip(rows, done):
+            w.writerow([utt, CLASS_LETTERS[int(np.argmax(row))]] + [f"{p:.4f}" for p in row.flatten()])
+    print(f"{len(done)} rows written, {failed} files failed")
+    for h in list(log.handlers):
+        h.close()
+        log.removeHandler(h)
+    return {"eval_loss": loss, "eval_f1": f1, "csv": csv_file, "n": len(done), "failed": failed}
+
+
 def main(argv: Optional[Sequence[str]] = None, evaluate_only: bool = False) -> int:
     import argparse
     p = argparse.ArgumentParser()
     p.add_argument("--seed", type=int, default=7)
     p.add_argument("--config_path", type=str, default="./configs/config_cat.json")
+    if evaluate_only:                                           # additive: the head as kernels of this library (engine.FusionHead)
+        p.add_argument("--engine", type=str, default="torch", choices=["torch", "hip"])
+        p.add_argument("--mode", type=str, default="f16x", choices=["f16x", "fp32x", "bf16"])
     args = p.parse_args(argv)
     with open(args.config_path, "r") as f:
         config = json.load(f)
-    (evaluate if evaluate_only else train)(config, seed=args.seed)
+    if evaluate_only and args.engine == "hip":
+        evaluate(config, seed=args.seed, engine="hip", mode=args.mode)
+    else:
+        (evaluate if evaluate_only else train)(config, seed=args.seed)
     return 0
