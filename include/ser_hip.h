@@ -573,6 +573,26 @@ typedef struct ser_xattn_args {
 } ser_xattn_args;
 int ser_xattn_v(const ser_xattn_args* args, void* stream);
 
+/* ser_xattn_mh_v: nn.MultiheadAttention(E, heads) between its in- and out-projection, over the same ragged pairs: ser_xattn_v's contract
+ * plus `heads`.  With dh = E / heads, head h is columns h dh .. (h+1) dh - 1 of q, k, v and of the context:
+ *   ctx[r, head h] = sum_j softmax_j(scale q_h[r] . k_h[j]) v_h[j]      over the utterance's own keys
+ * `scale` comes from the caller (dh^-0.5 for torch's module).  The same kernel as ser_xattn_v with the head as a grid dimension: one block per
+ * (16 queries, head, utterance) stages its head's dh columns only (LDS grows with dh, not E); heads == 1 is bit-identical to ser_xattn_v.
+ * No atomics on float data; an utterance's result does not depend on the batch around it.  heads >= 1, E % heads == 0, dh % 64 == 0,
+ * E <= 1024, B <= 65535; alignment, pitches, out_act / out_f32, `mode` and the FP16X report into range_flag as for ser_xattn_v. */
+typedef struct ser_xattn_mh_args {
+    const float* q; int64_t ldq;
+    const float* k; int64_t ldk;
+    const float* v; int64_t ldv;
+    const int32_t* q_offs; const int32_t* k_offs;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    float* out_f32; int64_t ldo_f32;
+    uint32_t* range_flag;
+    float scale;
+    int32_t B, E, heads, q_rows, k_rows, max_q, mode;
+} ser_xattn_mh_args;
+int ser_xattn_mh_v(const ser_xattn_mh_args* args, void* stream);
+
 /* ser_attn_pool_v: the head's attention pooling.  With x = a + b (a: the GRU output, b: the attention out-projection's fp32 output):
  *   s_r = x[r] . w + bias;   out[u, col0 .. col0 + E - 1] = sum_r softmax_r(s) x[r]   over utterance u's rows.
  * Pattern of ser_asp_pool_v: scores by one wave per row into the workspace `scores` [rows], then one block per (64-column slab, utterance);

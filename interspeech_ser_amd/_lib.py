@@ -202,6 +202,18 @@ class XattnArgs(C.Structure):
     ]
 
 
+class XattnMhArgs(C.Structure):
+    """Mirror of ``ser_xattn_mh_args``."""
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_i64), ("k", c_void_p), ("ldk", c_i64), ("v", c_void_p), ("ldv", c_i64),
+        ("q_offs", c_void_p), ("k_offs", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("out_f32", c_void_p), ("ldo_f32", c_i64),
+        ("range_flag", c_void_p), ("scale", c_float),
+        ("B", C.c_int32), ("E", C.c_int32), ("heads", C.c_int32), ("q_rows", C.c_int32), ("k_rows", C.c_int32), ("max_q", C.c_int32),
+        ("mode", C.c_int32),
+    ]
+
+
 class AttnPoolArgs(C.Structure):
     """Mirror of ``ser_attn_pool_args``."""
     _fields_ = [
@@ -236,7 +248,7 @@ OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, O
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
-                  "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_attn_pool_args": AttnPoolArgs,
+                  "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_xattn_mh_args": XattnMhArgs, "ser_attn_pool_args": AttnPoolArgs,
                   "ser_fusion_cls_args": FusionClsArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -263,6 +275,7 @@ _SIGNATURES = {
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),
+    "ser_xattn_mh_v": (c_int, [c_void_p, c_void_p]),
     "ser_attn_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_fusion_cls_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),

@@ -1,6 +1,7 @@
 // The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334, MultiModalEmotionClassifier) behind the encoders:
 //   ser_gru_v         bidirectional GRU recurrence over a packed ragged batch (the input products gx come from ser_gemm)
 //   ser_xattn_v       single-head cross-attention over ragged (query, key) utterance pairs, fp32 FMA, online softmax
+//   ser_xattn_mh_v    the same kernel with the head as a grid dimension: a block works on its head's E / heads columns
 //   ser_attn_pool_v   softmax attention pooling of (a + b) over an utterance's frames
 //   ser_fusion_cls_v  LayerNorm -> Linear -> ReLU -> Linear on the pooled rows
 // ser_hip.h states the arithmetic.  No atomics on float data; every sum runs in an order fixed by the utterance alone.
@@ -305,14 +306,16 @@ extern "C" int ser_gru_v(const ser_gru_args* a, void* stream) {
     return ser_check_launch("ser_gru");
 }
 
-// ================================================================================================ ser_xattn_v
-// Block (query tile of 16, utterance); thread (qi = tid / 16, c = tid % 16).  Per key tile of 16: K rows through LDS, thread (qi, c) owns the
-// logit of query qi and key c (four fp32 FMA chains over E, added as (s0 + s1) + (s2 + s3)), the 16 lanes of a query share the tile's max and sum by butterflies;
-// then V rows through the same LDS buffer, thread (qi, c) owns the context columns 4 c + 64 i.  Online softmax in base 2, logits pre-scaled
-// by scale log2(e).  Tiles start at the utterance's first row and never cross utterances: a result depends on its own pair alone.
+// ================================================================================================ ser_xattn_v, ser_xattn_mh_v
+// Block (query tile of 16, utterance, head); thread (qi = tid / 16, c = tid % 16).  A block sees a window of W columns of q, k, v and the
+// context, starting at column head * W: W = E and one head for ser_xattn_v, W = E / heads for ser_xattn_mh_v.  LDS holds W columns only.
+// Per key tile of 16: K rows through LDS, thread (qi, c) owns the logit of query qi and key c (four fp32 FMA chains over W, added as
+// (s0 + s1) + (s2 + s3)), the 16 lanes of a query share the tile's max and sum by butterflies; then V rows through the same LDS buffer,
+// thread (qi, c) owns the context columns 4 c + 64 i of the window.  Online softmax in base 2, logits pre-scaled by scale log2(e).
+// Tiles start at the utterance's first row and never cross utterances: a result depends on its own pair alone.
 #define XA_QT 16
 #define XA_KT 16
-#define XA_EV 16                      // 64-column steps of a context row: E <= 1024
+#define XA_EV 16                      // 64-column steps of a context row: W <= 1024
 
 struct xattn_params {
     const float* q; int64_t ldq; const float* k; int64_t ldk; const float* v; int64_t ldv;
@@ -321,13 +324,13 @@ struct xattn_params {
     float* out_f32; int64_t ldo_f32;
     uint32_t* range_flag;
     float scale2;
-    int E, q_rows, k_rows;
+    int W, q_rows, k_rows;
 };
 
 template <int MODE>
 __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int E = p.E, LD = E + 4;
+    const int E = p.W, LD = E + 4, w0 = blockIdx.z * p.W;   // E: the window's width from here on; w0: its first column
     float* qs = (float*)smem;                    // [16][LD]
     float* kv = qs + XA_QT * LD;                 // [16][LD]
     float* ps = kv + XA_KT * LD;                 // [16][17]
@@ -343,7 +346,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
     for (int i = tid; i < XA_QT * ev; i += 256) {
         const int r = i / ev, ch = i % ev;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (qt0 + r < Tq) v = *(const f32x4*)(p.q + (int64_t)(q0 + qt0 + r) * p.ldq + ch * 4);
+        if (qt0 + r < Tq) v = *(const f32x4*)(p.q + (int64_t)(q0 + qt0 + r) * p.ldq + w0 + ch * 4);
         *(f32x4*)(qs + r * LD + ch * 4) = v;
     }
     f32x4 acc[XA_EV];
@@ -355,7 +358,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
         for (int i = tid; i < XA_KT * ev; i += 256) {
             const int r = i / ev, ch = i % ev;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (kt0 + r < Tk) v = *(const f32x4*)(p.k + (int64_t)(k0 + kt0 + r) * p.ldk + ch * 4);
+            if (kt0 + r < Tk) v = *(const f32x4*)(p.k + (int64_t)(k0 + kt0 + r) * p.ldk + w0 + ch * 4);
             *(f32x4*)(kv + r * LD + ch * 4) = v;
         }
         __syncthreads();
@@ -389,7 +392,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
         for (int i = tid; i < XA_KT * ev; i += 256) {
             const int r = i / ev, ch = i % ev;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (kt0 + r < Tk) v = *(const f32x4*)(p.v + (int64_t)(k0 + kt0 + r) * p.ldv + ch * 4);
+            if (kt0 + r < Tk) v = *(const f32x4*)(p.v + (int64_t)(k0 + kt0 + r) * p.ldv + w0 + ch * 4);
             *(f32x4*)(kv + r * LD + ch * 4) = v;
         }
         __syncthreads();
@@ -418,7 +421,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
         for (int i = 0; i < XA_EV; ++i) {
             if (i * 64 < E) {
                 const f32x4 o = acc[i] * inv;
-                const int col = i * 64 + c * 4;
+                const int col = w0 + i * 64 + c * 4;
                 if (p.out_f32) *(f32x4*)(p.out_f32 + row * p.ldo_f32 + col) = o;
                 if (p.out_act) {
                     store_act4<MODE>(p.out_act + row * p.ldo_act + col, p.oplane, o[0], o[1], o[2], o[3]);
@@ -429,6 +432,38 @@ __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
         }
     }
     if (MODE == SER_MODE_FP16X) range_report(p.range_flag, amax);
+}
+
+// The launch of both entry points, after their validation: grid (query tiles, utterances, heads), LDS for a window of E / heads columns.
+static int xattn_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int32_t* q_offs,
+                        const int32_t* k_offs, void* out_act, int64_t ldo_act, int64_t out_plane_stride, float* out_f32, int64_t ldo_f32,
+                        uint32_t* range_flag, float scale, int B, int E, int heads, int q_rows, int k_rows, int max_q, int mode, void* stream,
+                        const char* who) {
+    xattn_params p;
+    p.q = q; p.ldq = ldq; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv; p.qo = q_offs; p.ko = k_offs;
+    p.out_act = (unsigned short*)out_act; p.ldo_act = ldo_act; p.oplane = out_plane_stride;
+    p.out_f32 = out_f32; p.ldo_f32 = ldo_f32; p.range_flag = range_flag;
+    p.scale2 = scale * 1.44269504088896340736f;
+    p.W = E / heads; p.q_rows = q_rows; p.k_rows = k_rows;
+    const int lds = (XA_QT + XA_KT) * (p.W + 4) * 4 + XA_QT * 17 * 4;
+    const dim3 grid((unsigned)((max_q + XA_QT - 1) / XA_QT), (unsigned)B, (unsigned)heads);
+    hipStream_t s = (hipStream_t)stream;
+    static std::atomic<bool> ready[3] = {{false}, {false}, {false}};
+#define XA_LAUNCH(MODE, I)                                                                                                          \
+    {                                                                                                                               \
+        auto kern = xattn_kernel<MODE>;                                                                                             \
+        if (!ready[I].load(std::memory_order_acquire)) {                                                                            \
+            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);          \
+            if (e != hipSuccess) return ser_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));                 \
+            ready[I].store(true, std::memory_order_release);                                                                        \
+        }                                                                                                                           \
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);                                                                       \
+    }
+    if (mode == SER_MODE_BF16) XA_LAUNCH(SER_MODE_BF16, 0)
+    else if (mode == SER_MODE_FP32X) XA_LAUNCH(SER_MODE_FP32X, 1)
+    else XA_LAUNCH(SER_MODE_FP16X, 2)
+#undef XA_LAUNCH
+    return ser_check_launch(who);
 }
 
 extern "C" int ser_xattn_v(const ser_xattn_args* a, void* stream) {
@@ -445,31 +480,28 @@ extern "C" int ser_xattn_v(const ser_xattn_args* a, void* stream) {
     if (a->out_f32 && (a->ldo_f32 < a->E || (a->ldo_f32 % 4))) return ser_fail(-2, "ser_xattn: bad ldo_f32=%lld (>= E, multiple of 4)", (long long)a->ldo_f32);
     if (a->out_act && a->mode != SER_MODE_BF16 && a->mode != SER_MODE_FP32X && a->mode != SER_MODE_FP16X)
         return ser_fail(-2, "ser_xattn: mode %d of the operand copy (BF16, FP32X or FP16X)", a->mode);
-    xattn_params p;
-    p.q = a->q; p.ldq = a->ldq; p.k = a->k; p.ldk = a->ldk; p.v = a->v; p.ldv = a->ldv; p.qo = a->q_offs; p.ko = a->k_offs;
-    p.out_act = (unsigned short*)a->out_act; p.ldo_act = a->ldo_act; p.oplane = a->out_plane_stride;
-    p.out_f32 = a->out_f32; p.ldo_f32 = a->ldo_f32; p.range_flag = a->range_flag;
-    p.scale2 = a->scale * 1.44269504088896340736f;
-    p.E = a->E; p.q_rows = a->q_rows; p.k_rows = a->k_rows;
-    const int lds = (XA_QT + XA_KT) * (a->E + 4) * 4 + XA_QT * 17 * 4;
-    const dim3 grid((unsigned)((a->max_q + XA_QT - 1) / XA_QT), (unsigned)a->B);
-    hipStream_t s = (hipStream_t)stream;
-    static std::atomic<bool> ready[3] = {{false}, {false}, {false}};
-#define XA_LAUNCH(MODE, I)                                                                                                          \
-    {                                                                                                                               \
-        auto k = xattn_kernel<MODE>;                                                                                                \
-        if (!ready[I].load(std::memory_order_acquire)) {                                                                            \
-            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);             \
-            if (e != hipSuccess) return ser_fail((int)e, "ser_xattn: hipFuncSetAttribute: %s", hipGetErrorString(e));               \
-            ready[I].store(true, std::memory_order_release);                                                                        \
-        }                                                                                                                           \
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, s, p);                                                                          \
-    }
-    if (a->mode == SER_MODE_BF16) XA_LAUNCH(SER_MODE_BF16, 0)
-    else if (a->mode == SER_MODE_FP32X) XA_LAUNCH(SER_MODE_FP32X, 1)
-    else XA_LAUNCH(SER_MODE_FP16X, 2)
-#undef XA_LAUNCH
-    return ser_check_launch("ser_xattn");
+    return xattn_launch(a->q, a->ldq, a->k, a->ldk, a->v, a->ldv, a->q_offs, a->k_offs, a->out_act, a->ldo_act, a->out_plane_stride, a->out_f32,
+                        a->ldo_f32, a->range_flag, a->scale, a->B, a->E, 1, a->q_rows, a->k_rows, a->max_q, a->mode, stream, "ser_xattn");
+}
+
+extern "C" int ser_xattn_mh_v(const ser_xattn_mh_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_xattn_mh: null pointer");
+    if (!a->q || !a->k || !a->v || !a->q_offs || !a->k_offs || (!a->out_act && !a->out_f32)) return ser_fail(-1, "ser_xattn_mh: null pointer");
+    if (a->B <= 0 || a->B > 65535 || a->E <= 0 || (a->E % 64) || a->E > 1024 || a->q_rows <= 0 || a->k_rows <= 0 || a->max_q <= 0 || a->max_q > a->q_rows)
+        return ser_fail(-2, "ser_xattn_mh: bad B=%d E=%d (multiple of 64, <= 1024) q_rows=%d k_rows=%d max_q=%d", a->B, a->E, a->q_rows, a->k_rows, a->max_q);
+    if (a->heads < 1 || (a->E % a->heads) || ((a->E / a->heads) % 64))
+        return ser_fail(-2, "ser_xattn_mh: bad heads=%d for E=%d (heads >= 1, E %% heads == 0, (E / heads) %% 64 == 0)", a->heads, a->E);
+    if (a->ldq < a->E || a->ldk < a->E || a->ldv < a->E || (a->ldq % 4) || (a->ldk % 4) || (a->ldv % 4))
+        return ser_fail(-2, "ser_xattn_mh: bad pitches ldq=%lld ldk=%lld ldv=%lld (>= E, multiples of 4)", (long long)a->ldq, (long long)a->ldk, (long long)a->ldv);
+    if ((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out_f32) & 15) || ((uintptr_t)a->out_act & 7))
+        return ser_fail(-2, "ser_xattn_mh: q, k, v and out_f32 must be 16-byte aligned, out_act 8-byte aligned");
+    if (a->out_act && (a->ldo_act < a->E || (a->ldo_act % 4) || (a->out_plane_stride % 4)))
+        return ser_fail(-2, "ser_xattn_mh: bad ldo_act=%lld (>= E, multiple of 4) out_plane_stride=%lld", (long long)a->ldo_act, (long long)a->out_plane_stride);
+    if (a->out_f32 && (a->ldo_f32 < a->E || (a->ldo_f32 % 4))) return ser_fail(-2, "ser_xattn_mh: bad ldo_f32=%lld (>= E, multiple of 4)", (long long)a->ldo_f32);
+    if (a->out_act && a->mode != SER_MODE_BF16 && a->mode != SER_MODE_FP32X && a->mode != SER_MODE_FP16X)
+        return ser_fail(-2, "ser_xattn_mh: mode %d of the operand copy (BF16, FP32X or FP16X)", a->mode);
+    return xattn_launch(a->q, a->ldq, a->k, a->ldk, a->v, a->ldv, a->q_offs, a->k_offs, a->out_act, a->ldo_act, a->out_plane_stride, a->out_f32,
+                        a->ldo_f32, a->range_flag, a->scale, a->B, a->E, a->heads, a->q_rows, a->k_rows, a->max_q, a->mode, stream, "ser_xattn_mh");
 }
 
 // ================================================================================================ ser_attn_pool_v

@@ -1914,40 +1914,49 @@ class _KernelHost(_EncoderBase):
         self._rec = None
 
 
-FUSION_KEYS = {"speech_projection.weight": ("h", "d1"), "speech_projection.bias": ("h",), "text_projection.weight": ("h", "d2"),
-               "text_projection.bias": ("h",), "speech_norm.weight": ("h",), "speech_norm.bias": ("h",), "text_norm.weight": ("h",),
-               "text_norm.bias": ("h",), "speech_attn.weight": (1, "e"), "speech_attn.bias": (1,), "text_attn.weight": (1, "e"),
-               "text_attn.bias": (1,), "classifier.0.weight": ("h1", "2e"), "classifier.0.bias": ("h1",), "classifier.3.weight": ("n", "h1"),
-               "classifier.3.bias": ("n",), "layer_norm.weight": ("2e",), "layer_norm.bias": ("2e",)}
-for _g in ("speech_gru", "text_gru"):
-    for _sfx in ("", "_reverse"):
-        FUSION_KEYS.update({f"{_g}.weight_ih_l0{_sfx}": ("3h", "h"), f"{_g}.weight_hh_l0{_sfx}": ("3h", "h"),
-                            f"{_g}.bias_ih_l0{_sfx}": ("3h",), f"{_g}.bias_hh_l0{_sfx}": ("3h",)})
-for _a in ("speech_attention", "text_attention"):
-    FUSION_KEYS.update({f"{_a}.in_proj_weight": ("3e", "e"), f"{_a}.in_proj_bias": ("3e",), f"{_a}.out_proj.weight": ("e", "e"),
-                        f"{_a}.out_proj.bias": ("e",)})
+def _fusion_keys(names) -> Dict[str, tuple]:
+    """state-dict keys and symbolic shapes of the reference's fusion head over the modalities ``names`` (feature width of modality i: "d<i+1>")"""
+    keys = {"classifier.0.weight": ("h1", "ne"), "classifier.0.bias": ("h1",), "classifier.3.weight": ("n", "h1"), "classifier.3.bias": ("n",),
+            "layer_norm.weight": ("ne",), "layer_norm.bias": ("ne",)}
+    for i, m in enumerate(names):
+        keys.update({f"{m}_projection.weight": ("h", f"d{i + 1}"), f"{m}_projection.bias": ("h",), f"{m}_norm.weight": ("h",),
+                     f"{m}_norm.bias": ("h",), f"{m}_attn.weight": (1, "e"), f"{m}_attn.bias": (1,),
+                     f"{m}_attention.in_proj_weight": ("3e", "e"), f"{m}_attention.in_proj_bias": ("3e",),
+                     f"{m}_attention.out_proj.weight": ("e", "e"), f"{m}_attention.out_proj.bias": ("e",)})
+        for sfx in ("", "_reverse"):
+            keys.update({f"{m}_gru.weight_ih_l0{sfx}": ("3h", "h"), f"{m}_gru.weight_hh_l0{sfx}": ("3h", "h"),
+                         f"{m}_gru.bias_ih_l0{sfx}": ("3h",), f"{m}_gru.bias_hh_l0{sfx}": ("3h",)})
+    return keys
+
+
+FUSION_KEYS = _fusion_keys(("speech", "text"))
+TRIMODAL_KEYS = _fusion_keys(("speech", "text", "prosody"))
 FUSION_BATCH = 16                                                 # utterances per MFMA column group of ser_gru_v
 
 
-class FusionHead:
-    """The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334, ``MultiModalEmotionClassifier``) on the device,
-    over packed ragged batches: speech rows ``x1 [M1, D1]`` with ``offs1``, text rows ``x2 [M2, D2]`` with ``offs2`` -> ``[B, n_out]`` logits.
-    EVERY UTTERANCE ALONE, as the reference's evaluation runs it (``batch_size=1``): no pad frame enters the recurrence, the attention or a
-    pooling softmax, and a batch is arithmetically that batch-of-one loop (``head.evaluate``'s torch path pads to the batch's longest
-    utterance instead).  ``forward`` enqueues on the current stream, outside the encoders' recorded tapes; per modality
+class _FusionBase:
+    """The reference's fusion heads over the modalities ``NAMES`` (the prefixes of their state-dict keys), on packed ragged batches, EVERY
+    UTTERANCE ALONE.  Everything of one ``forward`` goes on the current stream, in order: a ser_gru_v cluster makes progress only while all
+    of its blocks are resident, so two recurrences are never in flight together.  Per modality
       ser_pack_rows_flagged -> ser_gemm (projection) -> ser_layernorm_v (operand copy) -> ser_gemm (both directions' x W_ih^T) -> ser_gru_v
-    then the four in-projection GEMMs (q of one side, packed k | v of the other, both ways), 2 x ser_xattn_v, 2 x out-projection GEMM,
-    2 x ser_attn_pool_v and ser_fusion_cls_v.  GEMM operand format: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo otherwise;
-    the recurrent product is always fp16 hi + lo."""
+    then one q GEMM per attention module (queries: the module's own modality), one k | v GEMM per modality (its GRU output under the k | v
+    rows of every OTHER module's in_proj_weight, stacked), one cross-attention and one out-projection per (module, other modality) -- a
+    module's second out-projection adds its first through ser_gemm's residual epilogue --, one ser_attn_pool_v per modality and
+    ser_fusion_cls_v on the [B, n E] row."""
+    NAMES: tuple = ()
+    KEYS: Dict[str, tuple] = {}
+    WHAT = "fusion head"
 
-    def __init__(self, state_dict, d1: int, d2: int, device="cuda:0", mode: str = "f16x", cluster: int = 0):
+    def _init(self, state_dict, dims_in: Sequence[int], heads: Sequence[int], device, mode: str, cluster: int) -> None:
+        names, n = self.NAMES, len(self.NAMES)
         if mode not in MODES:
             raise ValueError(f"mode must be one of {list(MODES)}")
         self.op_mode = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X}.get(mode, _lib.MODE_FP16X)
-        if d1 <= 0 or d2 <= 0 or d1 % 64 or d2 % 64:
-            raise ValueError(f"FusionHead needs feature widths that are multiples of 64 (ser_gemm's K rule), got D1={d1} D2={d2}")
+        if any(d <= 0 or d % 64 for d in dims_in):
+            raise ValueError(f"{type(self).__name__} needs feature widths that are multiples of 64 (ser_gemm's K rule), got "
+                             + " ".join(f"D{i + 1}={d}" for i, d in enumerate(dims_in)))
         sd = state_dict
-        missing = [k for k in FUSION_KEYS if k not in sd]
+        missing = [k for k in self.KEYS if k not in sd]                # keys beyond the head's own (a ranking checkpoint's second classifier) are ignored
         if missing:
             raise ValueError(f"the head's state dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''} ({len(missing)} keys)")
         h = int(sd["speech_norm.weight"].shape[0])
@@ -1956,18 +1965,24 @@ class FusionHead:
         h1, n_out = int(sd["classifier.0.weight"].shape[0]), int(sd["classifier.3.weight"].shape[0])
         if not 1 <= n_out <= 8:
             raise ValueError(f"classifier.3.weight has {n_out} outputs (1..8)")
-        dims = {"h": h, "3h": 3 * h, "e": 2 * h, "2e": 4 * h, "3e": 6 * h, "d1": d1, "d2": d2, "h1": h1, "n": n_out}
-        for k, want in FUSION_KEYS.items():
+        E = 2 * h
+        heads = tuple(int(v) for v in heads)
+        if len(heads) != n or any(v < 1 or E % v or (E // v) % 64 for v in heads):
+            raise ValueError(f"heads={heads}: one count per attention module ({', '.join(names)}), each dividing E = {E} into multiples of 64")
+        dims = {"h": h, "3h": 3 * h, "e": E, "ne": n * E, "3e": 3 * E, "h1": h1, "n": n_out}
+        dims.update({f"d{i + 1}": d for i, d in enumerate(dims_in)})
+        for k, want in self.KEYS.items():
             want = tuple(dims.get(w, w) for w in want)
             if tuple(sd[k].shape) != want:
                 raise ValueError(f"{k} has shape {tuple(sd[k].shape)}, expected {want}")
         self.host = host = _KernelHost(device, mode, self.op_mode)
         self.device, self.mode_name = host.device, mode
-        self.h, self.E, self.h1, self.n_out, self.d1, self.d2, self.cluster = h, 2 * h, h1, n_out, d1, d2, int(cluster)
+        self.h, self.E, self.h1, self.n_out, self.dims_in, self.heads, self.cluster = h, E, h1, n_out, tuple(dims_in), heads, int(cluster)
         om = self.op_mode
         f32 = host._dev_f32
         self.mod = []
-        for name, gru in (("speech", "speech_gru"), ("text", "text_gru")):
+        for name in names:
+            gru = f"{name}_gru"
             wih = torch.cat([sd[f"{gru}.weight_ih_l0"], sd[f"{gru}.weight_ih_l0_reverse"]], dim=0)
             whh = torch.cat([sd[f"{gru}.weight_hh_l0"], sd[f"{gru}.weight_hh_l0_reverse"]], dim=0)
             self.mod.append(dict(
@@ -1977,16 +1992,20 @@ class FusionHead:
                 # the recurrent weights: fp16 hi + lo planes in every mode; an element beyond fp16's range is refused here, by name
                 whh=host._linear(whh, None, mode=_lib.MODE_FP16X, name=f"{gru}.weight_hh_l0"),
                 bhh=f32(torch.cat([sd[f"{gru}.bias_hh_l0"], sd[f"{gru}.bias_hh_l0_reverse"]]))))
-        E = self.E
+        self.others = [[j for j in range(n) if j != i] for i in range(n)]
         self.att = []
-        for name in ("speech", "text"):                           # attention whose queries are this modality's rows
+        for name in names:                                        # attention module whose queries are this modality's rows
             w, b = sd[f"{name}_attention.in_proj_weight"], sd[f"{name}_attention.in_proj_bias"]
             self.att.append(dict(
                 q=host._linear(w[:E], b[:E], mode=om, name=f"{name}_attention.in_proj_weight"),
-                kv=host._linear(w[E:], b[E:], mode=om, name=f"{name}_attention.in_proj_weight"),
                 out=host._linear(sd[f"{name}_attention.out_proj.weight"], sd[f"{name}_attention.out_proj.bias"], mode=om,
                                  name=f"{name}_attention.out_proj.weight"),
                 pool_w=f32(sd[f"{name}_attn.weight"].reshape(E)), pool_b=float(sd[f"{name}_attn.bias"].reshape(-1)[0])))
+        for j, name in enumerate(names):                          # modality j's rows under the k | v rows of every other module, stacked
+            ws = [sd[f"{names[i]}_attention.in_proj_weight"][E:] for i in self.others[j]]
+            bs = [sd[f"{names[i]}_attention.in_proj_bias"][E:] for i in self.others[j]]
+            self.mod[j]["kv"] = host._linear(torch.cat(ws, dim=0), torch.cat(bs), mode=om,
+                                             name=" | ".join(f"{names[i]}_attention.in_proj_weight" for i in self.others[j]))
         self.ln_g, self.ln_b = f32(sd["layer_norm.weight"]), f32(sd["layer_norm.bias"])
         self.w1, self.b1 = f32(sd["classifier.0.weight"]), f32(sd["classifier.0.bias"])
         self.w2, self.b2 = f32(sd["classifier.3.weight"]), f32(sd["classifier.3.bias"])
@@ -1999,21 +2018,24 @@ class FusionHead:
         self._bufs: Dict[int, dict] = {}
         self.trace: Optional[list] = None                        # when a list: (name, start event, end event) per step (tools/fusion_head_bench.py)
 
-    def _buffers(self, slot: int, M1: int, M2: int, B: int) -> dict:
+    def _buffers(self, slot: int, Ms: Sequence[int], B: int) -> dict:
         """grow-only buffers of one pipeline slot"""
         bf = self._bufs.get(slot)
-        if bf is not None and bf["M"][0] >= M1 and bf["M"][1] >= M2 and bf["B"] >= B:
+        if bf is not None and all(a >= b for a, b in zip(bf["M"], Ms)) and bf["B"] >= B:
             return bf
         if bf is not None:
-            M1, M2, B = max(M1, bf["M"][0]), max(M2, bf["M"][1]), max(B, bf["B"])
-        dev, h, E, om = self.device, self.h, self.E, self.op_mode
+            Ms, B = [max(a, b) for a, b in zip(bf["M"], Ms)], max(B, bf["B"])
+        dev, h, E, om, n = self.device, self.h, self.E, self.op_mode, len(self.NAMES)
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         act = lambda rows, cols: Act(rows, cols, _PLANES[om], dev, dtype=_DTYPE[om])
         side = []
-        for M, D in ((M1, self.d1), (M2, self.d2)):
-            side.append(dict(xa=act(M, D), proj=f(M, h), sa=act(M, h), gx=f(M, 6 * h), gh=f(M, E), gha=act(M, E), q=f(M, E), kv=f(M, 2 * E),
-                             ctx=act(M, E), att=f(M, E), scores=f(M), offs=torch.empty(B + 1, dtype=torch.int32, device=dev)))
-        bf = dict(M=(M1, M2), B=B, side=side, pooled=f(B, 2 * E), xn=f(B, 2 * E), hidden=f(B, self.h1), out=f(B, self.n_out),
+        for M, D in zip(Ms, self.dims_in):
+            sb = dict(xa=act(M, D), proj=f(M, h), sa=act(M, h), gx=f(M, 6 * h), gh=f(M, E), gha=act(M, E), q=f(M, E), kv=f(M, 2 * E * (n - 1)),
+                      ctx=[act(M, E) for _ in range(n - 1)], att=f(M, E), scores=f(M), offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
+            if n > 2:
+                sb["att_first"] = f(M, E)                         # the first out-projection of a module with two key sides (distinct from `att`)
+            side.append(sb)
+        bf = dict(M=tuple(Ms), B=B, side=side, pooled=f(B, n * E), xn=f(B, n * E), hidden=f(B, self.h1), out=f(B, self.n_out),
                   err=torch.zeros(1, dtype=torch.int32, device=dev), flag=torch.zeros(1, dtype=torch.int32, device=dev),
                   work=torch.zeros(max(self.work_bytes, 16), dtype=torch.uint8, device=dev))
         self._bufs[slot] = bf
@@ -2039,22 +2061,27 @@ class FusionHead:
         self._epoch += 1 + B // FUSION_BATCH
         check(lib.ser_gru_v(C.byref(g), st), "ser_gru_v")
 
-    def forward(self, x1: torch.Tensor, offs1: Sequence[int], x2: torch.Tensor, offs2: Sequence[int], slot: int = 0,
-                range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``).  The fp16 range
-        guard reports into ``range_flag`` (default: the slot's own word); ``status(slot)`` reads it and ser_gru_v's error word."""
-        offs = [[int(v) for v in offs1], [int(v) for v in offs2]]
+    def _xattn(self, xa, heads: int, st: int) -> None:
+        """launch the filled ``ser_xattn_mh_args``"""
+        xa.heads = heads
+        check(lib.ser_xattn_mh_v(C.byref(xa), st), "ser_xattn_mh_v")
+
+    _XattnArgs = _lib.XattnMhArgs
+
+    def _forward(self, xs: Sequence[torch.Tensor], offs_in: Sequence[Sequence[int]], slot: int, range_flag: Optional[torch.Tensor]) -> torch.Tensor:
+        names, n = self.NAMES, len(self.NAMES)
+        offs = [[int(v) for v in o] for o in offs_in]
         B = len(offs[0]) - 1
-        if B < 1 or len(offs[1]) != B + 1:
-            raise ValueError("offs1 and offs2 must list the same number (>= 1) of utterances")
-        xs, Ms, host, E, h, om = [x1, x2], [offs[0][-1], offs[1][-1]], self.host, self.E, self.h, self.op_mode
-        for i, (x, D, what) in enumerate(((x1, self.d1, "speech"), (x2, self.d2, "text"))):
+        if B < 1 or any(len(o) != B + 1 for o in offs):
+            raise ValueError(" and ".join(f"offs{i + 1}" for i in range(n)) + " must list the same number (>= 1) of utterances")
+        Ms, host, E, h, om = [o[-1] for o in offs], self.host, self.E, self.h, self.op_mode
+        for i, (x, D, what) in enumerate(zip(xs, self.dims_in, names)):
             if offs[i][0] != 0 or any(b <= a for a, b in zip(offs[i][:-1], offs[i][1:])):
                 raise ValueError(f"an empty {what} utterance (or offsets that do not ascend from 0): every utterance needs at least one row")
             if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != D or x.shape[0] < Ms[i] or x.stride(1) != 1 or x.stride(0) % 4 \
                     or x.data_ptr() % 16 or x.device != self.device:
                 raise ValueError(f"{what} rows must be an fp32 [>= {Ms[i]}, {D}] tensor on {self.device} (16-byte aligned, row pitch a multiple of 4)")
-        bf = self._buffers(slot, Ms[0], Ms[1], B)
+        bf = self._buffers(slot, Ms, B)
         st = _stream()
         flag_t = range_flag if range_flag is not None else bf["flag"]
         bf["flag_used"] = flag_t
@@ -2062,47 +2089,56 @@ class FusionHead:
         host._flag = flag
         bf["err"].zero_()
         maxf = [max(b - a for a, b in zip(o[:-1], o[1:])) for o in offs]
-        for i in (0, 1):
+        for i in range(n):
             sb, w, x, M = bf["side"][i], self.mod[i], xs[i], Ms[i]
             sb["offs"][: B + 1].copy_(torch.tensor(offs[i], dtype=torch.int32))
             D = x.shape[1]
             xa, sa = sb["xa"].first_rows(M), sb["sa"].first_rows(M)
-            tag = ("speech", "text")[i]
+            tag = names[i]
             self._step(f"{tag} pack", lambda: check(lib.ser_pack_rows_flagged(x.data_ptr(), x.stride(0), 1, M, D, 0, xa.ptr, D, xa.plane_stride, om,
                                                                              flag, st), "ser_pack_rows_flagged"))
             self._step(f"{tag} projection", lambda: host._gemm(xa, w["proj"], M, out_f32=sb["proj"], ldo_f32=h, mode=om))
             self._step(f"{tag} layernorm", lambda: host._layernorm(sb["proj"], h, w["ln"], M, h, out_act=sa, eps=1e-5))
             self._step(f"{tag} gx", lambda: host._gemm(sa, w["wih"], M, out_f32=sb["gx"], ldo_f32=6 * h, mode=om))
             self._step(f"{tag} gru", lambda: self._gru(bf, sb, w, B, M, maxf[i], st))
-        for i in (0, 1):                                          # attention i: queries of side i, keys / values of the other side
-            a, sq, sk = self.att[i], bf["side"][i], bf["side"][1 - i]
-            tag = ("speech", "text")[i]
-            self._step(f"{tag} q", lambda: host._gemm(sq["gha"].first_rows(Ms[i]), a["q"], Ms[i], out_f32=sq["q"], ldo_f32=E, mode=om))
-            self._step(f"{tag} kv", lambda: host._gemm(sk["gha"].first_rows(Ms[1 - i]), a["kv"], Ms[1 - i], out_f32=sk["kv"], ldo_f32=2 * E, mode=om))
-        for i in (0, 1):
-            sq, sk = bf["side"][i], bf["side"][1 - i]
-            ctx = sq["ctx"].first_rows(Ms[i])
-            xa = _lib.XattnArgs()
-            xa.q, xa.ldq, xa.k, xa.ldk, xa.v, xa.ldv = sq["q"].data_ptr(), E, sk["kv"].data_ptr(), 2 * E, sk["kv"].data_ptr() + 4 * E, 2 * E
-            xa.q_offs, xa.k_offs = sq["offs"].data_ptr(), sk["offs"].data_ptr()
-            xa.out_act, xa.ldo_act, xa.out_plane_stride, xa.range_flag = ctx.ptr, E, ctx.plane_stride, flag
-            xa.scale, xa.B, xa.E, xa.q_rows, xa.k_rows, xa.max_q, xa.mode = float(E) ** -0.5, B, E, Ms[i], Ms[1 - i], maxf[i], om
-            self._step(f"{('speech', 'text')[i]} xattn", lambda: check(lib.ser_xattn_v(C.byref(xa), st), "ser_xattn_v"))
-        for i in (0, 1):
+        ldkv = 2 * E * (n - 1)
+        for i in range(n):                                        # q: module i over its own modality; k | v: modality i under every other module
+            sb = bf["side"][i]
+            gha = sb["gha"].first_rows(Ms[i])
+            self._step(f"{names[i]} q", lambda: host._gemm(gha, self.att[i]["q"], Ms[i], out_f32=sb["q"], ldo_f32=E, mode=om))
+            self._step(f"{names[i]} kv", lambda: host._gemm(gha, self.mod[i]["kv"], Ms[i], out_f32=sb["kv"], ldo_f32=ldkv, mode=om))
+        for i in range(n):                                        # attention module i: queries of side i, keys / values of each other side
+            sq = bf["side"][i]
+            for t, j in enumerate(self.others[i]):
+                sk = bf["side"][j]
+                kcol = 2 * E * self.others[j].index(i)            # module i's k | v block inside modality j's stacked projection
+                ctx = sq["ctx"][t].first_rows(Ms[i])
+                xa = self._XattnArgs()
+                xa.q, xa.ldq, xa.k, xa.ldk = sq["q"].data_ptr(), E, sk["kv"].data_ptr() + 4 * kcol, ldkv
+                xa.v, xa.ldv = sk["kv"].data_ptr() + 4 * (kcol + E), ldkv
+                xa.q_offs, xa.k_offs = sq["offs"].data_ptr(), sk["offs"].data_ptr()
+                xa.out_act, xa.ldo_act, xa.out_plane_stride, xa.range_flag = ctx.ptr, E, ctx.plane_stride, flag
+                xa.scale, xa.B, xa.E, xa.q_rows, xa.k_rows, xa.max_q, xa.mode = float(E // self.heads[i]) ** -0.5, B, E, Ms[i], Ms[j], maxf[i], om
+                self._step(f"{names[i]} xattn" + (f" {names[j]}" if n > 2 else ""), lambda: self._xattn(xa, self.heads[i], st))
+        for i in range(n):
             sq, a = bf["side"][i], self.att[i]
-            self._step(f"{('speech', 'text')[i]} out_proj", lambda: host._gemm(sq["ctx"].first_rows(Ms[i]), a["out"], Ms[i], out_f32=sq["att"], ldo_f32=E, mode=om))
-        for i in (0, 1):
+            for t, j in enumerate(self.others[i]):
+                last = t == n - 2
+                self._step(f"{names[i]} out_proj" + (f" {names[j]}" if n > 2 else ""),
+                           lambda: host._gemm(sq["ctx"][t].first_rows(Ms[i]), a["out"], Ms[i], out_f32=sq["att"] if last else sq["att_first"], ldo_f32=E,
+                                              residual=sq["att_first"] if (last and t > 0) else None, ldr=E if (last and t > 0) else 0, mode=om))
+        for i in range(n):
             sq, a = bf["side"][i], self.att[i]
             p = _lib.AttnPoolArgs()
             p.a, p.lda, p.b, p.ldb, p.w, p.frame_offs = sq["gh"].data_ptr(), E, sq["att"].data_ptr(), E, a["pool_w"].data_ptr(), sq["offs"].data_ptr()
-            p.scores, p.out, p.ldo, p.bias, p.col0 = sq["scores"].data_ptr(), bf["pooled"].data_ptr(), 2 * E, a["pool_b"], i * E
+            p.scores, p.out, p.ldo, p.bias, p.col0 = sq["scores"].data_ptr(), bf["pooled"].data_ptr(), n * E, a["pool_b"], i * E
             p.B, p.E, p.rows, p.max_frames = B, E, Ms[i], maxf[i]
-            self._step(f"{('speech', 'text')[i]} attn_pool", lambda: check(lib.ser_attn_pool_v(C.byref(p), st), "ser_attn_pool_v"))
+            self._step(f"{names[i]} attn_pool", lambda: check(lib.ser_attn_pool_v(C.byref(p), st), "ser_attn_pool_v"))
         c = _lib.FusionClsArgs()
-        c.p, c.ldp, c.gamma, c.beta = bf["pooled"].data_ptr(), 2 * E, self.ln_g.data_ptr(), self.ln_b.data_ptr()
+        c.p, c.ldp, c.gamma, c.beta = bf["pooled"].data_ptr(), n * E, self.ln_g.data_ptr(), self.ln_b.data_ptr()
         c.W1, c.b1, c.W2, c.b2 = self.w1.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(), self.b2.data_ptr()
         c.xn, c.hidden, c.out, c.eps = bf["xn"].data_ptr(), bf["hidden"].data_ptr(), bf["out"].data_ptr(), 1e-5
-        c.B, c.K, c.H1, c.n_out = B, 2 * E, self.h1, self.n_out
+        c.B, c.K, c.H1, c.n_out = B, n * E, self.h1, self.n_out
         self._step("classifier", lambda: check(lib.ser_fusion_cls_v(C.byref(c), st), "ser_fusion_cls_v"))
         host._flag = None
         return bf["out"][:B]
@@ -2123,6 +2159,58 @@ class FusionHead:
         if bits & 1:
             return "a value beyond the fp16 operand range (+-65504) reached the fusion head (use --mode fp32x)"
         return None
+
+
+class FusionHead(_FusionBase):
+    """The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334, ``MultiModalEmotionClassifier``) on the device,
+    over packed ragged batches: speech rows ``x1 [M1, D1]`` with ``offs1``, text rows ``x2 [M2, D2]`` with ``offs2`` -> ``[B, n_out]`` logits.
+    EVERY UTTERANCE ALONE, as the reference's evaluation runs it (``batch_size=1``): no pad frame enters the recurrence, the attention or a
+    pooling softmax, and a batch is arithmetically that batch-of-one loop (``head.evaluate``'s torch path pads to the batch's longest
+    utterance instead).  ``forward`` enqueues on the current stream, outside the encoders' recorded tapes; per modality
+      ser_pack_rows_flagged -> ser_gemm (projection) -> ser_layernorm_v (operand copy) -> ser_gemm (both directions' x W_ih^T) -> ser_gru_v
+    then the four in-projection GEMMs (q of one side, packed k | v of the other, both ways), 2 x ser_xattn_v, 2 x out-projection GEMM,
+    2 x ser_attn_pool_v and ser_fusion_cls_v.  GEMM operand format: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo otherwise;
+    the recurrent product is always fp16 hi + lo."""
+    NAMES = ("speech", "text")
+    KEYS = FUSION_KEYS
+    _XattnArgs = _lib.XattnArgs
+
+    def __init__(self, state_dict, d1: int, d2: int, device="cuda:0", mode: str = "f16x", cluster: int = 0):
+        self._init(state_dict, (d1, d2), (1, 1), device, mode, cluster)
+        self.d1, self.d2 = d1, d2
+
+    def _xattn(self, xa, heads: int, st: int) -> None:
+        check(lib.ser_xattn_v(C.byref(xa), st), "ser_xattn_v")
+
+    def forward(self, x1: torch.Tensor, offs1: Sequence[int], x2: torch.Tensor, offs2: Sequence[int], slot: int = 0,
+                range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``).  The fp16 range
+        guard reports into ``range_flag`` (default: the slot's own word); ``status(slot)`` reads it and ser_gru_v's error word."""
+        return self._forward((x1, x2), (offs1, offs2), slot, range_flag)
+
+
+class TrimodalHead(_FusionBase):
+    """The reference's trimodal fusion head (bin/train_cat_trimodal_lazy_1head.py, ``MultiModalEmotionClassifier`` over speech, text and a
+    third feature stream, the ``prosody_*`` keys) on the device, every utterance alone (the ``batch_size=1`` of the reference's scoring
+    scripts).  Three recurrences, three q and three k | v (N = 4 E) GEMMs, six ser_xattn_mh_v launches -- each attention module serves both
+    of its query side's pairs, exactly as the reference shares them --, six out-projections (the second of a query side adds the first), three
+    ser_attn_pool_v into a [B, 3 E] row and ser_fusion_cls_v with K = 3 E.  ``heads``: the head count of each module; a state dict does not
+    record it, and the reference hard-codes (1, 1, 2)."""
+    NAMES = ("speech", "text", "prosody")
+    KEYS = TRIMODAL_KEYS
+
+    def __init__(self, state_dict, d1: int, d2: int, d3: int, device="cuda:0", mode: str = "f16x", cluster: int = 0,
+                 heads: Sequence[int] = (1, 1, 2)):
+        self._init(state_dict, (d1, d2, d3), heads, device, mode, cluster)
+        self.d1, self.d2, self.d3 = d1, d2, d3
+
+    def forward(self, x1: torch.Tensor, offs1: Sequence[int], x2: torch.Tensor, offs2: Sequence[int], x3: torch.Tensor, offs3: Sequence[int],
+                slot: int = 0, range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``); ``x3`` may be
+        ``[M3, D3, 1]`` (the reference squeezes the third stream's last axis)."""
+        if x3.dim() == 3 and x3.shape[-1] == 1:
+            x3 = x3.squeeze(-1)
+        return self._forward((x1, x2, x3), (offs1, offs2, offs3), slot, range_flag)
 
 
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):
