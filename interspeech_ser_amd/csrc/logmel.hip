@@ -148,7 +148,9 @@ __global__ __launch_bounds__(256, 3) void logmel_kernel(const float* __restrict_
                 f32x4 v;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    v[j] = log10f(fmaxf(acc[f4 + j], 1e-10f));
+                    // the 1e-10 guard's logarithm is the constant -10: log10f(1e-10f) comes out one ulp below it on the device (its
+                    // log2 of 33.2 is 1 ulp = 3.8e-6 off, 1.1e-6 after the scaling), and silence must be exactly (-10 + 4) / 4
+                    v[j] = acc[f4 + j] > 1e-10f ? log10f(acc[f4 + j]) : -10.0f;
                     lmax = fmaxf(lmax, v[j]);
                 }
                 *(f32x4*)(orow + f4) = v;
