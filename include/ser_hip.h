@@ -485,7 +485,8 @@ int ser_pos_ln_v(const ser_pos_ln_args* args, void* stream);
  *   mu_d = sum_r w_r x[r, d];   rh_d = sqrt(max(sum_r w_r x[r, d]^2 - mu_d^2, 1e-5f))
  *   out[b] = [mu | rh], 2 D wide.  One frame gives mu = x, rh = sqrt(1e-5f).
  * Two launches: the scores (one wave per row, into the caller's workspace `scores` [rows]), then one block per (utterance, 64-column
- * slab) that reads x once.  x [rows, ldx], hlin [rows, ldh], a [D]: fp32, 16-byte aligned, pitches multiples of 4; frame_offs int32
+ * slab) that reads x once -- the two kernels of ser_attn_pool_v, here with the tanh term and with the second moment kept.
+ * x [rows, ldx], hlin [rows, ldh], a [D]: fp32, 16-byte aligned, pitches multiples of 4; frame_offs int32
  * [B + 1] on the device (the caller's contract: ascending, inside [0, rows]); out fp32 [B, ldo], ldo >= 2 D.  D % 4 == 0.  max_frames
  * (the longest utterance) is checked against rows and changes no result.  Validated before the launch: -1 null pointer, -2 sizes. */
 typedef struct ser_asp_pool_args {
@@ -502,7 +503,8 @@ int ser_asp_pool_v(const ser_asp_pool_args* args, void* stream);
 /* ser_mlp_head_v: Linear(K, H) -> LayerNorm(H, eps) -> ReLU -> Linear(H, n_out) on B rows (EmotionRegression with one hidden layer;
  * Dropout is the identity in eval).  p [B, ldp], W1 [H, K], b1 / gamma / beta [H], W2 [n_out, H], b2 [n_out], workspace hidden [B, H],
  * out [B, n_out], all fp32.  Two launches: one wave per hidden unit (its W1 row in registers, looping over the B rows), then one block
- * per row.  K % 4 == 0, K <= 4096, 1 <= n_out <= 8, p and W1 16-byte aligned, ldp a multiple of 4. */
+ * per row -- the two kernels of ser_fusion_cls_v, here without the ReLU at the hidden units and with LayerNorm + ReLU ahead of the outputs.
+ * K % 4 == 0, K <= 4096, 1 <= n_out <= 8, p and W1 16-byte aligned, ldp a multiple of 4. */
 typedef struct ser_mlp_head_args {
     const float* p; int64_t ldp;
     const float* W1; const float* b1; const float* gamma; const float* beta;
@@ -553,7 +555,8 @@ typedef struct ser_gru_args {
 int ser_gru_v(const ser_gru_args* args, void* stream);
 int64_t ser_gru_work_bytes(int32_t H, int32_t cluster, int32_t* R_out);
 
-/* ser_xattn_v: nn.MultiheadAttention(E, 1) between its in- and out-projection, over ragged pairs: utterance b's queries are rows
+/* ser_xattn_v: ser_xattn_mh_v with heads = 1 (one validation and launch routine serves both; messages carry the entry point's own name):
+ * nn.MultiheadAttention(E, 1) between its in- and out-projection, over ragged pairs: utterance b's queries are rows
  * q_offs[b] .. q_offs[b+1]-1 of q, its keys / values rows k_offs[b] .. k_offs[b+1]-1 of k / v (fp32, from ser_gemm; no mask):
  *   ctx[r] = sum_j softmax_j(scale q[r] . k[j]) v[j]
  * fp32 FMAs, online softmax in base 2 (logits pre-scaled by scale log2 e), one block per (utterance, 16 queries), keys in tiles of 16 from
@@ -595,7 +598,8 @@ int ser_xattn_mh_v(const ser_xattn_mh_args* args, void* stream);
 
 /* ser_attn_pool_v: the head's attention pooling.  With x = a + b (a: the GRU output, b: the attention out-projection's fp32 output):
  *   s_r = x[r] . w + bias;   out[u, col0 .. col0 + E - 1] = sum_r softmax_r(s) x[r]   over utterance u's rows.
- * Pattern of ser_asp_pool_v: scores by one wave per row into the workspace `scores` [rows], then one block per (64-column slab, utterance);
+ * The two kernels of ser_asp_pool_v, here with the (a + b) . w term and source and the first moment only: scores by one wave per row into
+ * the workspace `scores` [rows], then one block per (64-column slab, utterance);
  * float64 accumulation in ascending frame order, fixed-order merges, one rounding at the store.  One frame gives a + b exactly.
  * E % 4 == 0; a / b / w 16-byte aligned, pitches multiples of 4; ldo >= col0 + E. */
 typedef struct ser_attn_pool_args {
@@ -611,7 +615,8 @@ typedef struct ser_attn_pool_args {
 int ser_attn_pool_v(const ser_attn_pool_args* args, void* stream);
 
 /* ser_fusion_cls_v: LayerNorm(K, eps) -> Linear(K, H1) -> ReLU -> Linear(H1, n_out) on B rows (layer_norm and classifier of the head;
- * Dropout is the identity in eval).  ser_mlp_head_v's pattern with the LayerNorm in front: p [B, ldp], gamma / beta [K], W1 [H1, K],
+ * Dropout is the identity in eval).  A LayerNorm kernel of its own, then the two kernels of ser_mlp_head_v (hidden units with the ReLU at
+ * their store, outputs without a LayerNorm): p [B, ldp], gamma / beta [K], W1 [H1, K],
  * b1 [H1], W2 [n_out, H1], b2 [n_out], workspaces xn [B, K] and hidden [B, H1], out [B, n_out], all fp32; float64 accumulation.
  * K % 4 == 0, K <= 4096, 1 <= n_out <= 8, xn and W1 16-byte aligned. */
 typedef struct ser_fusion_cls_args {

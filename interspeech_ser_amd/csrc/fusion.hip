@@ -1,10 +1,9 @@
 // The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334, MultiModalEmotionClassifier) behind the encoders:
 //   ser_gru_v         bidirectional GRU recurrence over a packed ragged batch (the input products gx come from ser_gemm)
-//   ser_xattn_v       single-head cross-attention over ragged (query, key) utterance pairs, fp32 FMA, online softmax
-//   ser_xattn_mh_v    the same kernel with the head as a grid dimension: a block works on its head's E / heads columns
-//   ser_attn_pool_v   softmax attention pooling of (a + b) over an utterance's frames
-//   ser_fusion_cls_v  LayerNorm -> Linear -> ReLU -> Linear on the pooled rows
-// ser_hip.h states the arithmetic.  No atomics on float data; every sum runs in an order fixed by the utterance alone.
+//   ser_xattn_mh_v    cross-attention over ragged (query, key) utterance pairs, fp32 FMA, online softmax; the head is a grid dimension: a
+//                     block works on its head's E / heads columns
+//   ser_xattn_v       ser_xattn_mh_v with heads = 1
+// The pooling and the classifier behind them (ser_attn_pool_v, ser_fusion_cls_v) share pool.hip's kernels.  ser_hip.h states the arithmetic.  No atomics on float data; every sum runs in an order fixed by the utterance alone.
 #include "ser_common.h"
 #include <atomic>
 
@@ -434,19 +433,31 @@ __global__ __launch_bounds__(256) void xattn_kernel(xattn_params p) {
     if (MODE == SER_MODE_FP16X) range_report(p.range_flag, amax);
 }
 
-// The launch of both entry points, after their validation: grid (query tiles, utterances, heads), LDS for a window of E / heads columns.
-static int xattn_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int32_t* q_offs,
-                        const int32_t* k_offs, void* out_act, int64_t ldo_act, int64_t out_plane_stride, float* out_f32, int64_t ldo_f32,
-                        uint32_t* range_flag, float scale, int B, int E, int heads, int q_rows, int k_rows, int max_q, int mode, void* stream,
-                        const char* who) {
+// Both entry points: validation, then grid (query tiles, utterances, heads) and LDS for a window of E / heads columns.  `who` prefixes the messages.
+static int xattn_run(const ser_xattn_mh_args* a, void* stream, const char* who) {
+    if (!a) return ser_fail(-1, "%s: null pointer", who);
+    if (!a->q || !a->k || !a->v || !a->q_offs || !a->k_offs || (!a->out_act && !a->out_f32)) return ser_fail(-1, "%s: null pointer", who);
+    if (a->B <= 0 || a->B > 65535 || a->E <= 0 || (a->E % 64) || a->E > 1024 || a->q_rows <= 0 || a->k_rows <= 0 || a->max_q <= 0 || a->max_q > a->q_rows)
+        return ser_fail(-2, "%s: bad B=%d E=%d (multiple of 64, <= 1024) q_rows=%d k_rows=%d max_q=%d", who, a->B, a->E, a->q_rows, a->k_rows, a->max_q);
+    if (a->heads < 1 || (a->E % a->heads) || ((a->E / a->heads) % 64))                             // never with ser_xattn_v's heads = 1
+        return ser_fail(-2, "%s: bad heads=%d for E=%d (heads >= 1, E %% heads == 0, (E / heads) %% 64 == 0)", who, a->heads, a->E);
+    if (a->ldq < a->E || a->ldk < a->E || a->ldv < a->E || (a->ldq % 4) || (a->ldk % 4) || (a->ldv % 4))
+        return ser_fail(-2, "%s: bad pitches ldq=%lld ldk=%lld ldv=%lld (>= E, multiples of 4)", who, (long long)a->ldq, (long long)a->ldk, (long long)a->ldv);
+    if ((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out_f32) & 15) || ((uintptr_t)a->out_act & 7))
+        return ser_fail(-2, "%s: q, k, v and out_f32 must be 16-byte aligned, out_act 8-byte aligned", who);
+    if (a->out_act && (a->ldo_act < a->E || (a->ldo_act % 4) || (a->out_plane_stride % 4)))
+        return ser_fail(-2, "%s: bad ldo_act=%lld (>= E, multiple of 4) out_plane_stride=%lld", who, (long long)a->ldo_act, (long long)a->out_plane_stride);
+    if (a->out_f32 && (a->ldo_f32 < a->E || (a->ldo_f32 % 4))) return ser_fail(-2, "%s: bad ldo_f32=%lld (>= E, multiple of 4)", who, (long long)a->ldo_f32);
+    if (a->out_act && a->mode != SER_MODE_BF16 && a->mode != SER_MODE_FP32X && a->mode != SER_MODE_FP16X)
+        return ser_fail(-2, "%s: mode %d of the operand copy (BF16, FP32X or FP16X)", who, a->mode);
     xattn_params p;
-    p.q = q; p.ldq = ldq; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv; p.qo = q_offs; p.ko = k_offs;
-    p.out_act = (unsigned short*)out_act; p.ldo_act = ldo_act; p.oplane = out_plane_stride;
-    p.out_f32 = out_f32; p.ldo_f32 = ldo_f32; p.range_flag = range_flag;
-    p.scale2 = scale * 1.44269504088896340736f;
-    p.W = E / heads; p.q_rows = q_rows; p.k_rows = k_rows;
+    p.q = a->q; p.ldq = a->ldq; p.k = a->k; p.ldk = a->ldk; p.v = a->v; p.ldv = a->ldv; p.qo = a->q_offs; p.ko = a->k_offs;
+    p.out_act = (unsigned short*)a->out_act; p.ldo_act = a->ldo_act; p.oplane = a->out_plane_stride;
+    p.out_f32 = a->out_f32; p.ldo_f32 = a->ldo_f32; p.range_flag = a->range_flag;
+    p.scale2 = a->scale * 1.44269504088896340736f;
+    p.W = a->E / a->heads; p.q_rows = a->q_rows; p.k_rows = a->k_rows;
     const int lds = (XA_QT + XA_KT) * (p.W + 4) * 4 + XA_QT * 17 * 4;
-    const dim3 grid((unsigned)((max_q + XA_QT - 1) / XA_QT), (unsigned)B, (unsigned)heads);
+    const dim3 grid((unsigned)((a->max_q + XA_QT - 1) / XA_QT), (unsigned)a->B, (unsigned)a->heads);
     hipStream_t s = (hipStream_t)stream;
     static std::atomic<bool> ready[3] = {{false}, {false}, {false}};
 #define XA_LAUNCH(MODE, I)                                                                                                          \
@@ -459,235 +470,22 @@ static int xattn_launch(const float* q, int64_t ldq, const float* k, int64_t ldk
         }                                                                                                                           \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);                                                                       \
     }
-    if (mode == SER_MODE_BF16) XA_LAUNCH(SER_MODE_BF16, 0)
-    else if (mode == SER_MODE_FP32X) XA_LAUNCH(SER_MODE_FP32X, 1)
+    if (a->mode == SER_MODE_BF16) XA_LAUNCH(SER_MODE_BF16, 0)
+    else if (a->mode == SER_MODE_FP32X) XA_LAUNCH(SER_MODE_FP32X, 1)
     else XA_LAUNCH(SER_MODE_FP16X, 2)
 #undef XA_LAUNCH
     return ser_check_launch(who);
 }
 
+extern "C" int ser_xattn_mh_v(const ser_xattn_mh_args* a, void* stream) { return xattn_run(a, stream, "ser_xattn_mh"); }
+
+// the single-head form: the same arguments without `heads`
 extern "C" int ser_xattn_v(const ser_xattn_args* a, void* stream) {
     if (!a) return ser_fail(-1, "ser_xattn: null pointer");
-    if (!a->q || !a->k || !a->v || !a->q_offs || !a->k_offs || (!a->out_act && !a->out_f32)) return ser_fail(-1, "ser_xattn: null pointer");
-    if (a->B <= 0 || a->B > 65535 || a->E <= 0 || (a->E % 64) || a->E > 1024 || a->q_rows <= 0 || a->k_rows <= 0 || a->max_q <= 0 || a->max_q > a->q_rows)
-        return ser_fail(-2, "ser_xattn: bad B=%d E=%d (multiple of 64, <= 1024) q_rows=%d k_rows=%d max_q=%d", a->B, a->E, a->q_rows, a->k_rows, a->max_q);
-    if (a->ldq < a->E || a->ldk < a->E || a->ldv < a->E || (a->ldq % 4) || (a->ldk % 4) || (a->ldv % 4))
-        return ser_fail(-2, "ser_xattn: bad pitches ldq=%lld ldk=%lld ldv=%lld (>= E, multiples of 4)", (long long)a->ldq, (long long)a->ldk, (long long)a->ldv);
-    if ((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out_f32) & 15) || ((uintptr_t)a->out_act & 7))
-        return ser_fail(-2, "ser_xattn: q, k, v and out_f32 must be 16-byte aligned, out_act 8-byte aligned");
-    if (a->out_act && (a->ldo_act < a->E || (a->ldo_act % 4) || (a->out_plane_stride % 4)))
-        return ser_fail(-2, "ser_xattn: bad ldo_act=%lld (>= E, multiple of 4) out_plane_stride=%lld", (long long)a->ldo_act, (long long)a->out_plane_stride);
-    if (a->out_f32 && (a->ldo_f32 < a->E || (a->ldo_f32 % 4))) return ser_fail(-2, "ser_xattn: bad ldo_f32=%lld (>= E, multiple of 4)", (long long)a->ldo_f32);
-    if (a->out_act && a->mode != SER_MODE_BF16 && a->mode != SER_MODE_FP32X && a->mode != SER_MODE_FP16X)
-        return ser_fail(-2, "ser_xattn: mode %d of the operand copy (BF16, FP32X or FP16X)", a->mode);
-    return xattn_launch(a->q, a->ldq, a->k, a->ldk, a->v, a->ldv, a->q_offs, a->k_offs, a->out_act, a->ldo_act, a->out_plane_stride, a->out_f32,
-                        a->ldo_f32, a->range_flag, a->scale, a->B, a->E, 1, a->q_rows, a->k_rows, a->max_q, a->mode, stream, "ser_xattn");
-}
-
-extern "C" int ser_xattn_mh_v(const ser_xattn_mh_args* a, void* stream) {
-    if (!a) return ser_fail(-1, "ser_xattn_mh: null pointer");
-    if (!a->q || !a->k || !a->v || !a->q_offs || !a->k_offs || (!a->out_act && !a->out_f32)) return ser_fail(-1, "ser_xattn_mh: null pointer");
-    if (a->B <= 0 || a->B > 65535 || a->E <= 0 || (a->E % 64) || a->E > 1024 || a->q_rows <= 0 || a->k_rows <= 0 || a->max_q <= 0 || a->max_q > a->q_rows)
-        return ser_fail(-2, "ser_xattn_mh: bad B=%d E=%d (multiple of 64, <= 1024) q_rows=%d k_rows=%d max_q=%d", a->B, a->E, a->q_rows, a->k_rows, a->max_q);
-    if (a->heads < 1 || (a->E % a->heads) || ((a->E / a->heads) % 64))
-        return ser_fail(-2, "ser_xattn_mh: bad heads=%d for E=%d (heads >= 1, E %% heads == 0, (E / heads) %% 64 == 0)", a->heads, a->E);
-    if (a->ldq < a->E || a->ldk < a->E || a->ldv < a->E || (a->ldq % 4) || (a->ldk % 4) || (a->ldv % 4))
-        return ser_fail(-2, "ser_xattn_mh: bad pitches ldq=%lld ldk=%lld ldv=%lld (>= E, multiples of 4)", (long long)a->ldq, (long long)a->ldk, (long long)a->ldv);
-    if ((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out_f32) & 15) || ((uintptr_t)a->out_act & 7))
-        return ser_fail(-2, "ser_xattn_mh: q, k, v and out_f32 must be 16-byte aligned, out_act 8-byte aligned");
-    if (a->out_act && (a->ldo_act < a->E || (a->ldo_act % 4) || (a->out_plane_stride % 4)))
-        return ser_fail(-2, "ser_xattn_mh: bad ldo_act=%lld (>= E, multiple of 4) out_plane_stride=%lld", (long long)a->ldo_act, (long long)a->out_plane_stride);
-    if (a->out_f32 && (a->ldo_f32 < a->E || (a->ldo_f32 % 4))) return ser_fail(-2, "ser_xattn_mh: bad ldo_f32=%lld (>= E, multiple of 4)", (long long)a->ldo_f32);
-    if (a->out_act && a->mode != SER_MODE_BF16 && a->mode != SER_MODE_FP32X && a->mode != SER_MODE_FP16X)
-        return ser_fail(-2, "ser_xattn_mh: mode %d of the operand copy (BF16, FP32X or FP16X)", a->mode);
-    return xattn_launch(a->q, a->ldq, a->k, a->ldk, a->v, a->ldv, a->q_offs, a->k_offs, a->out_act, a->ldo_act, a->out_plane_stride, a->out_f32,
-                        a->ldo_f32, a->range_flag, a->scale, a->B, a->E, a->heads, a->q_rows, a->k_rows, a->max_q, a->mode, stream, "ser_xattn_mh");
-}
-
-// ================================================================================================ ser_attn_pool_v
-__device__ __forceinline__ double fus_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double fus_block_sum_f64(double v, double* red) {
-    v = fus_wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// One wave per row: score[m] = sum_e (a + b)[m, e] w[e] + bias in float64, lane l owns columns 4 l + 256 i in ascending i, then the butterfly.
-__global__ __launch_bounds__(256) void fus_pool_scores_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb,
-                                                              const float* __restrict__ w, float bias, float* __restrict__ scores, int rows, int E) {
-    const int lane = threadIdx.x & 63;
-    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= rows) return;
-    double acc = 0.0;
-    for (int c = lane * 4; c < E; c += 256) {
-        const f32x4 va = *(const f32x4*)(a + m * lda + c), vb = *(const f32x4*)(b + m * ldb + c), vw = *(const f32x4*)(w + c);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = fma((double)va[j] + (double)vb[j], (double)vw[j], acc);
-    }
-    acc = fus_wave_sum_f64(acc);
-    if (lane == 0) scores[m] = (float)(acc + (double)bias);
-}
-
-// Block (64-column slab, utterance); thread (rg = tid / 16, cq = tid % 16) owns 4 columns and the frames rg, rg + 16, ...: float64 sums of
-// w_t and w_t (a + b) in ascending t, the 16 row groups merged in ascending rg, one division and one rounding at the store.
-__global__ __launch_bounds__(256) void fus_pool_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb,
-                                                       const float* __restrict__ scores, const int32_t* __restrict__ frame_offs,
-                                                       float* __restrict__ out, int64_t ldo, int col0, int E, int rows) {
-    __shared__ float smax[4];
-    __shared__ double red[16][16][5];
-    const int ub = blockIdx.y, tid = threadIdx.x;
-    int r0 = frame_offs[ub], r1 = frame_offs[ub + 1];
-    if (r0 < 0) r0 = 0;
-    if (r1 > rows) r1 = rows;
-    const int T = r1 - r0, c0 = blockIdx.x * 64;
-    float* o = out + (int64_t)ub * ldo + col0;
-    if (T <= 0) {
-        if (tid < 64 && c0 + tid < E) o[c0 + tid] = 0.f;
-        return;
-    }
-    const float* s = scores + r0;
-    float mx = -INFINITY;
-    for (int t = tid; t < T; t += 256) mx = fmaxf(mx, s[t]);
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) smax[tid >> 6] = mx;
-    __syncthreads();
-    const double smx = (double)fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-    const int rg = tid >> 4, cq = tid & 15, col = c0 + cq * 4;
-    const bool live = col < E;
-    double sw = 0.0, s1[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int t = rg; t < T; t += 16) {
-        const double w = exp((double)s[t] - smx);
-        sw += w;
-        if (live) {
-            const f32x4 va = *(const f32x4*)(a + (int64_t)(r0 + t) * lda + col), vb = *(const f32x4*)(b + (int64_t)(r0 + t) * ldb + col);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s1[j] = fma(w, (double)va[j] + (double)vb[j], s1[j]);
-        }
-    }
-    red[rg][cq][0] = sw;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[rg][cq][1 + j] = s1[j];
-    __syncthreads();
-    if (tid < 64 && c0 + tid < E) {
-        const int q = tid >> 2, j = tid & 3;
-        double w = 0.0, m1 = 0.0;
-        for (int g = 0; g < 16; ++g) { w += red[g][q][0]; m1 += red[g][q][1 + j]; }
-        o[c0 + tid] = (float)(m1 / w);
-    }
-}
-
-extern "C" int ser_attn_pool_v(const ser_attn_pool_args* a, void* stream) {
-    if (!a) return ser_fail(-1, "ser_attn_pool: null pointer");
-    if (!a->a || !a->b || !a->w || !a->frame_offs || !a->scores || !a->out) return ser_fail(-1, "ser_attn_pool: null pointer");
-    if (a->B <= 0 || a->B > 65535 || a->E <= 0 || (a->E % 4) || a->rows <= 0 || a->max_frames <= 0 || a->max_frames > a->rows || a->col0 < 0)
-        return ser_fail(-2, "ser_attn_pool: bad B=%d E=%d (E %% 4 == 0) rows=%d max_frames=%d col0=%d", a->B, a->E, a->rows, a->max_frames, a->col0);
-    if (a->lda < a->E || a->ldb < a->E || (a->lda % 4) || (a->ldb % 4) || a->ldo < (int64_t)a->col0 + a->E)
-        return ser_fail(-2, "ser_attn_pool: bad pitches lda=%lld ldb=%lld (>= E, multiples of 4) ldo=%lld (>= col0 + E)", (long long)a->lda,
-                        (long long)a->ldb, (long long)a->ldo);
-    if ((((uintptr_t)a->a | (uintptr_t)a->b | (uintptr_t)a->w) & 15) != 0) return ser_fail(-2, "ser_attn_pool: a, b and w must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fus_pool_scores_kernel, dim3((unsigned)((a->rows + 3) / 4)), dim3(256), 0, s, a->a, a->lda, a->b, a->ldb, a->w, a->bias,
-                       a->scores, a->rows, a->E);
-    hipLaunchKernelGGL(fus_pool_kernel, dim3((unsigned)((a->E + 63) / 64), (unsigned)a->B), dim3(256), 0, s, a->a, a->lda, a->b, a->ldb, a->scores,
-                       a->frame_offs, a->out, a->ldo, a->col0, a->E, a->rows);
-    return ser_check_launch("ser_attn_pool");
-}
-
-// ================================================================================================ ser_fusion_cls_v
-// LayerNorm(K): one block per row, two-pass float64 statistics (biased variance, eps inside the root), the normalised row rounded to fp32.
-__global__ __launch_bounds__(256) void fus_cls_ln_kernel(const float* __restrict__ p, int64_t ldp, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, float eps, float* __restrict__ xn, int K) {
-    __shared__ double red[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* x = p + (int64_t)b * ldp;
-    double s = 0.0;
-    for (int k = tid; k < K; k += 256) s += (double)x[k];
-    const double mean = fus_block_sum_f64(s, red) / (double)K;
-    double q = 0.0;
-    for (int k = tid; k < K; k += 256) { const double d = (double)x[k] - mean; q = fma(d, d, q); }
-    const double rstd = 1.0 / sqrt(fus_block_sum_f64(q, red) / (double)K + (double)eps);
-    for (int k = tid; k < K; k += 256) xn[(int64_t)b * K + k] = (float)(((double)x[k] - mean) * rstd * (double)gamma[k] + (double)beta[k]);
-}
-
-// One wave per hidden unit j: its W1 row in registers (lane l owns columns 4 l + 256 i), walking the B rows; bias and ReLU at the store.
-template <int KV>
-__global__ __launch_bounds__(256) void fus_cls_hidden_kernel(const float* __restrict__ xn, const float* __restrict__ W1, const float* __restrict__ b1,
-                                                             float* __restrict__ hidden, int B, int K, int H1) {
-    const int lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= H1) return;
-    f32x4 w[KV];
-#pragma unroll
-    for (int i = 0; i < KV; ++i) {
-        const int c = lane * 4 + 256 * i;
-        w[i] = c < K ? *(const f32x4*)(W1 + (int64_t)j * K + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const double bias = (double)b1[j];
-    for (int b = 0; b < B; ++b) {
-        const float* pr = xn + (int64_t)b * K;
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < KV; ++i) {
-            const int c = lane * 4 + 256 * i;
-            if (c < K) {
-                const f32x4 v = *(const f32x4*)(pr + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = fma((double)v[e], (double)w[i][e], acc);
-            }
-        }
-        acc = fus_wave_sum_f64(acc) + bias;
-        if (lane == 0) hidden[(int64_t)b * H1 + j] = (float)(acc > 0.0 ? acc : 0.0);
-    }
-}
-
-#define FUS_NOUT_MAX 8
-__global__ __launch_bounds__(256) void fus_cls_out_kernel(const float* __restrict__ hidden, const float* __restrict__ W2, const float* __restrict__ b2,
-                                                          float* __restrict__ out, int H1, int n_out) {
-    __shared__ double redo[4][FUS_NOUT_MAX];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* h = hidden + (int64_t)b * H1;
-    double acc[FUS_NOUT_MAX];
-#pragma unroll
-    for (int o = 0; o < FUS_NOUT_MAX; ++o) acc[o] = 0.0;
-    for (int k = tid; k < H1; k += 256) {
-        const double y = (double)h[k];
-#pragma unroll
-        for (int o = 0; o < FUS_NOUT_MAX; ++o)
-            if (o < n_out) acc[o] = fma(y, (double)W2[(int64_t)o * H1 + k], acc[o]);
-    }
-#pragma unroll
-    for (int o = 0; o < FUS_NOUT_MAX; ++o) {
-        const double v = fus_wave_sum_f64(acc[o]);
-        if ((tid & 63) == 0) redo[tid >> 6][o] = v;
-    }
-    __syncthreads();
-    if (tid < n_out) out[(int64_t)b * n_out + tid] = (float)(((redo[0][tid] + redo[1][tid]) + (redo[2][tid] + redo[3][tid])) + (double)b2[tid]);
-}
-
-extern "C" int ser_fusion_cls_v(const ser_fusion_cls_args* a, void* stream) {
-    if (!a) return ser_fail(-1, "ser_fusion_cls: null pointer");
-    if (!a->p || !a->gamma || !a->beta || !a->W1 || !a->b1 || !a->W2 || !a->b2 || !a->xn || !a->hidden || !a->out)
-        return ser_fail(-1, "ser_fusion_cls: null pointer");
-    if (a->n_out < 1 || a->n_out > FUS_NOUT_MAX) return ser_fail(-2, "ser_fusion_cls: n_out=%d (1..%d)", a->n_out, FUS_NOUT_MAX);
-    if (a->B <= 0 || a->B > 65535 || a->H1 <= 0 || a->K <= 0 || (a->K % 4) || a->K > 4096 || a->ldp < a->K)
-        return ser_fail(-2, "ser_fusion_cls: bad B=%d H1=%d K=%d (K %% 4 == 0, K <= 4096) ldp=%lld (>= K)", a->B, a->H1, a->K, (long long)a->ldp);
-    if ((((uintptr_t)a->xn | (uintptr_t)a->W1) & 15) != 0) return ser_fail(-2, "ser_fusion_cls: xn and W1 must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fus_cls_ln_kernel, dim3((unsigned)a->B), dim3(256), 0, s, a->p, a->ldp, a->gamma, a->beta, a->eps, a->xn, a->K);
-    const dim3 grid((unsigned)((a->H1 + 3) / 4)), block(256);
-#define FUS_HIDDEN(KV) hipLaunchKernelGGL(fus_cls_hidden_kernel<KV>, grid, block, 0, s, a->xn, a->W1, a->b1, a->hidden, a->B, a->K, a->H1)
-    if (a->K <= 256) FUS_HIDDEN(1);
-    else if (a->K <= 512) FUS_HIDDEN(2);
-    else if (a->K <= 1024) FUS_HIDDEN(4);
-    else if (a->K <= 2048) FUS_HIDDEN(8);
-    else FUS_HIDDEN(16);
-#undef FUS_HIDDEN
-    hipLaunchKernelGGL(fus_cls_out_kernel, dim3((unsigned)a->B), dim3(256), 0, s, a->hidden, a->W2, a->b2, a->out, a->H1, a->n_out);
-    return ser_check_launch("ser_fusion_cls");
+    ser_xattn_mh_args m;
+    m.q = a->q; m.ldq = a->ldq; m.k = a->k; m.ldk = a->ldk; m.v = a->v; m.ldv = a->ldv; m.q_offs = a->q_offs; m.k_offs = a->k_offs;
+    m.out_act = a->out_act; m.ldo_act = a->ldo_act; m.out_plane_stride = a->out_plane_stride; m.out_f32 = a->out_f32; m.ldo_f32 = a->ldo_f32;
+    m.range_flag = a->range_flag; m.scale = a->scale;
+    m.B = a->B; m.E = a->E; m.heads = 1; m.q_rows = a->q_rows; m.k_rows = a->k_rows; m.max_q = a->max_q; m.mode = a->mode;
+    return xattn_run(&m, stream, "ser_xattn");
 }

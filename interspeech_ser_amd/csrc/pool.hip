@@ -1,7 +1,11 @@
-// The organiser baseline's utterance-level tail (benchmark/train_eval_files/eval_cat_ser.py:164-177, eval_dim_ser.py): attentive
-// statistics pooling over a packed ragged batch (benchmark/net/pooling.py AttentiveStatisticsPooling.forward) and the 2D -> H -> n_out
-// head (benchmark/net/ser.py EmotionRegression).  ser_hip.h states the arithmetic.  Every sum accumulates in float64 in an order that
-// depends on the utterance alone (its frame count, D, K, H), never on the batch; one rounding to fp32 at each store.  No atomics.
+// The utterance-level tails of the three device heads, one kernel per pattern:
+//   ser_asp_pool_v    organiser baseline (benchmark/train_eval_files/eval_cat_ser.py:164-177, eval_dim_ser.py): attentive statistics pooling
+//                     over a packed ragged batch (benchmark/net/pooling.py AttentiveStatisticsPooling.forward)
+//   ser_mlp_head_v    its 2D -> H -> n_out head (benchmark/net/ser.py EmotionRegression)
+//   ser_attn_pool_v   fusion heads (bin/train_cat_bimodal_lazy_1head.py MultiModalEmotionClassifier): softmax attention pooling of (a + b)
+//   ser_fusion_cls_v  their LayerNorm -> Linear -> ReLU -> Linear on the pooled rows
+// ser_hip.h states the arithmetic.  Every sum accumulates in float64 in an order that depends on the utterance alone (its frame count and
+// the widths), never on the batch; one rounding to fp32 at each store.  No atomics.
 #include "ser_common.h"
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -17,47 +21,92 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red) {
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
+// LayerNorm statistics of one row per block, two-pass (mean, then the centred squares; biased variance, eps inside the root); thread t
+// owns elements t, t + 256, ...
+__device__ __forceinline__ void row_stats_f64(const float* x, int n, float eps, double* red, double& mean, double& rstd) {
+    double s = 0.0;
+    for (int k = threadIdx.x; k < n; k += 256) s += (double)x[k];
+    mean = block_sum_f64(s, red) / (double)n;
+    double q = 0.0;
+    for (int k = threadIdx.x; k < n; k += 256) { const double d = (double)x[k] - mean; q = fma(d, d, q); }
+    rstd = 1.0 / sqrt(block_sum_f64(q, red) / (double)n + (double)eps);
+}
 
 // ------------------------------------------------------------------------------- attention scores
-// One wave per row: scores[m] = sum_d tanhf(hlin[m, d]) * a[d].  Lane l owns columns 4 l + 256 i (16-byte loads), adds its products in
-// ascending i, then the wave butterfly.  tanhf is the library's (no fast-math in this build): <= 2 ulp.
-__global__ __launch_bounds__(256) void asp_scores_kernel(const float* __restrict__ hlin, int64_t ldh, const float* __restrict__ a,
-                                                         float* __restrict__ scores, int rows, int D) {
-    const int lane = threadIdx.x & 63;
-    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= rows) return;                                        // whole waves leave: the shuffles below stay wave-uniform
-    const float* h = hlin + m * ldh;
-    double acc = 0.0;
-    for (int c = lane * 4; c < D; c += 256) {
-        const f32x4 v = *(const f32x4*)(h + c);
+// One wave per row: lane l owns columns 4 l + 256 i (16-byte loads) and adds its terms in ascending i, then the wave butterfly; lane 0
+// stores.  TERM::add puts the four terms of row m at columns c .. c + 3 on the lane's sum; TERM::finish makes the stored score.
+struct asp_term {                                                 // ser_asp_pool_v: sum_d tanhf(hlin[m, d]) a[d]; tanhf is the library's
+    const float* hlin; int64_t ldh; const float* a;               // (no fast-math in this build): <= 2 ulp
+    __device__ void add(double& acc, int64_t m, int c) const {
+        const f32x4 v = *(const f32x4*)(hlin + m * ldh + c);
         const f32x4 w = *(const f32x4*)(a + c);
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc += (double)tanhf(v[j]) * (double)w[j];
     }
+    __device__ float finish(double acc) const { return (float)acc; }
+};
+struct sum_term {                                                 // ser_attn_pool_v: sum_e (a + b)[m, e] w[e] + bias
+    const float* a; int64_t lda; const float* b; int64_t ldb; const float* w; float bias;
+    __device__ void add(double& acc, int64_t m, int c) const {
+        const f32x4 va = *(const f32x4*)(a + m * lda + c), vb = *(const f32x4*)(b + m * ldb + c), vw = *(const f32x4*)(w + c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = fma((double)va[j] + (double)vb[j], (double)vw[j], acc);
+    }
+    __device__ float finish(double acc) const { return (float)(acc + (double)bias); }
+};
+
+template <class TERM>
+__global__ __launch_bounds__(256) void tail_scores_kernel(TERM term, float* __restrict__ scores, int rows, int W) {
+    const int lane = threadIdx.x & 63;
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= rows) return;                                        // whole waves leave: the shuffles below stay wave-uniform
+    double acc = 0.0;
+    for (int c = lane * 4; c < W; c += 256) term.add(acc, m, c);
     acc = wave_sum_f64(acc);
-    if (lane == 0) scores[m] = (float)acc;
+    if (lane == 0) scores[m] = term.finish(acc);
 }
 
 // ------------------------------------------------------------------------------- weighted moments
 // Block (column slab of 64, utterance).  Thread (rg = tid / 16, cq = tid % 16) owns columns 4 cq .. 4 cq + 3 of the slab and the frames
-// t = rg, rg + 16, ...: w_t = exp(s_t - max_t s) in float64, sums of w, w x, w x^2 in ascending t; the 16 row groups are merged in
-// ascending rg.  x is read once (every element by exactly one thread, 16 bytes at a time); the scores are re-read per slab (4 bytes a row).
-#define ASP_SLAB 64
-#define ASP_RG 16
-__global__ __launch_bounds__(256) void asp_pool_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ scores,
-                                                       const int32_t* __restrict__ frame_offs, float* __restrict__ out, int64_t ldo,
-                                                       int D, int rows) {
+// t = rg, rg + 16, ...: w_t = exp(s_t - max_t s) in float64, sums of w, w x (and w x^2 with M2) in ascending t; the 16 row groups are
+// merged in ascending rg.  The source is read once (every element by exactly one thread, 16 bytes at a time); the scores are re-read per
+// slab (4 bytes a row).  Stores: the mean at out[b, col0 + c]; with M2 also sqrt(max(variance, 1e-5f)) at out[b, col0 + W + c].
+struct one_src {                                                  // ser_asp_pool_v: x
+    const float* x; int64_t ldx;
+    __device__ void load(int64_t row, int col, double* xv) const {
+        const f32x4 v = *(const f32x4*)(x + row * ldx + col);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xv[j] = (double)v[j];
+    }
+};
+struct sum_src {                                                  // ser_attn_pool_v: a + b
+    const float* a; int64_t lda; const float* b; int64_t ldb;
+    __device__ void load(int64_t row, int col, double* xv) const {
+        const f32x4 va = *(const f32x4*)(a + row * lda + col), vb = *(const f32x4*)(b + row * ldb + col);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xv[j] = (double)va[j] + (double)vb[j];
+    }
+};
+
+#define POOL_SLAB 64
+#define POOL_RG 16
+template <bool M2, class SRC>
+__global__ __launch_bounds__(256) void tail_moments_kernel(SRC src, const float* __restrict__ scores, const int32_t* __restrict__ frame_offs,
+                                                           float* __restrict__ out, int64_t ldo, int col0, int W, int rows) {
     __shared__ float smax[4];
-    __shared__ double red[ASP_RG][16][9];                         // [row group][column quad][sum w | sum w x [4] | sum w x^2 [4]]
+    __shared__ double red[POOL_RG][16][M2 ? 9 : 5];               // [row group][column quad][sum w | sum w x [4] | sum w x^2 [4]]
     const int b = blockIdx.y, tid = threadIdx.x;
     int r0 = frame_offs[b], r1 = frame_offs[b + 1];
     if (r0 < 0) r0 = 0;                                           // the offsets are the caller's contract; never read outside [0, rows)
     if (r1 > rows) r1 = rows;
     const int T = r1 - r0;
-    const int col0 = blockIdx.x * ASP_SLAB;
-    float* o = out + (int64_t)b * ldo;
+    const int c0 = blockIdx.x * POOL_SLAB;
+    float* o = out + (int64_t)b * ldo + col0;
     if (T <= 0) {                                                 // an empty utterance: no frames to weigh
-        if (tid < ASP_SLAB && col0 + tid < D) { o[col0 + tid] = 0.f; o[D + col0 + tid] = (float)sqrt((double)1e-5f); }
+        if (tid < POOL_SLAB && c0 + tid < W) {
+            o[c0 + tid] = 0.f;
+            if (M2) o[W + c0 + tid] = (float)sqrt((double)1e-5f);
+        }
         return;
     }
     const float* s = scores + r0;
@@ -68,36 +117,44 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const float* __restrict__
     __syncthreads();
     const double smx = (double)fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
     const int rg = tid >> 4, cq = tid & 15;
-    const int col = col0 + cq * 4;
-    const bool live = col < D;                                    // D % 4 == 0: a quad is inside or outside as a whole
+    const int col = c0 + cq * 4;
+    const bool live = col < W;                                    // W % 4 == 0: a quad is inside or outside as a whole
     double sw = 0.0, s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    const float* xp = x + (int64_t)r0 * ldx + col;
-    for (int t = rg; t < T; t += ASP_RG) {
+    for (int t = rg; t < T; t += POOL_RG) {
         const double w = exp((double)s[t] - smx);
         sw += w;
         if (live) {
-            const f32x4 v = *(const f32x4*)(xp + (int64_t)t * ldx);
+            double xv[4];
+            src.load((int64_t)r0 + t, col, xv);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const double xv = (double)v[j];
-                s1[j] = fma(w, xv, s1[j]);
-                s2[j] = fma(w, xv * xv, s2[j]);
+                s1[j] = fma(w, xv[j], s1[j]);
+                if (M2) s2[j] = fma(w, xv[j] * xv[j], s2[j]);
             }
         }
     }
     red[rg][cq][0] = sw;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { red[rg][cq][1 + j] = s1[j]; red[rg][cq][5 + j] = s2[j]; }
+    for (int j = 0; j < 4; ++j) {
+        red[rg][cq][1 + j] = s1[j];
+        if (M2) red[rg][cq][5 + j] = s2[j];
+    }
     __syncthreads();
-    if (tid < ASP_SLAB && col0 + tid < D) {                       // one thread per column of the slab
+    if (tid < POOL_SLAB && c0 + tid < W) {                        // one thread per column of the slab
         const int q = tid >> 2, j = tid & 3;
         double w = 0.0, m1 = 0.0, m2 = 0.0;
-        for (int g = 0; g < ASP_RG; ++g) { w += red[g][q][0]; m1 += red[g][q][1 + j]; m2 += red[g][q][5 + j]; }
+        for (int g = 0; g < POOL_RG; ++g) {
+            w += red[g][q][0];
+            m1 += red[g][q][1 + j];
+            if (M2) m2 += red[g][q][5 + j];
+        }
         const double mu = m1 / w;
-        double var = m2 / w - mu * mu;
-        if (!(var >= (double)1e-5f)) var = (double)1e-5f;         // .clamp(min=1e-5) (pooling.py:56)
-        o[col0 + tid] = (float)mu;
-        o[D + col0 + tid] = (float)sqrt(var);
+        o[c0 + tid] = (float)mu;
+        if (M2) {
+            double var = m2 / w - mu * mu;
+            if (!(var >= (double)1e-5f)) var = (double)1e-5f;     // .clamp(min=1e-5) (pooling.py:56)
+            o[W + c0 + tid] = (float)sqrt(var);
+        }
     }
 }
 
@@ -111,18 +168,49 @@ extern "C" int ser_asp_pool_v(const ser_asp_pool_args* a, void* stream) {
                         (long long)a->ldh, (long long)a->ldo);
     if ((((uintptr_t)a->x | (uintptr_t)a->hlin | (uintptr_t)a->a) & 15) != 0) return ser_fail(-2, "ser_asp_pool: x, hlin and a must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(asp_scores_kernel, dim3((unsigned)((a->rows + 3) / 4)), dim3(256), 0, s, a->hlin, a->ldh, a->a, a->scores, a->rows, a->D);
-    hipLaunchKernelGGL(asp_pool_kernel, dim3((unsigned)((a->D + ASP_SLAB - 1) / ASP_SLAB), a->B), dim3(256), 0, s, a->x, a->ldx, a->scores,
-                       a->frame_offs, a->out, a->ldo, a->D, a->rows);
+    hipLaunchKernelGGL(tail_scores_kernel<asp_term>, dim3((unsigned)((a->rows + 3) / 4)), dim3(256), 0, s, asp_term{a->hlin, a->ldh, a->a},
+                       a->scores, a->rows, a->D);
+    hipLaunchKernelGGL((tail_moments_kernel<true, one_src>), dim3((unsigned)((a->D + POOL_SLAB - 1) / POOL_SLAB), (unsigned)a->B), dim3(256), 0, s,
+                       one_src{a->x, a->ldx}, a->scores, a->frame_offs, a->out, a->ldo, 0, a->D, a->rows);
     return ser_check_launch("ser_asp_pool");
 }
 
-// ------------------------------------------------------------------------------- head, first Linear
+extern "C" int ser_attn_pool_v(const ser_attn_pool_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_attn_pool: null pointer");
+    if (!a->a || !a->b || !a->w || !a->frame_offs || !a->scores || !a->out) return ser_fail(-1, "ser_attn_pool: null pointer");
+    if (a->B <= 0 || a->B > 65535 || a->E <= 0 || (a->E % 4) || a->rows <= 0 || a->max_frames <= 0 || a->max_frames > a->rows || a->col0 < 0)
+        return ser_fail(-2, "ser_attn_pool: bad B=%d E=%d (E %% 4 == 0) rows=%d max_frames=%d col0=%d", a->B, a->E, a->rows, a->max_frames, a->col0);
+    if (a->lda < a->E || a->ldb < a->E || (a->lda % 4) || (a->ldb % 4) || a->ldo < (int64_t)a->col0 + a->E)
+        return ser_fail(-2, "ser_attn_pool: bad pitches lda=%lld ldb=%lld (>= E, multiples of 4) ldo=%lld (>= col0 + E)", (long long)a->lda,
+                        (long long)a->ldb, (long long)a->ldo);
+    if ((((uintptr_t)a->a | (uintptr_t)a->b | (uintptr_t)a->w) & 15) != 0) return ser_fail(-2, "ser_attn_pool: a, b and w must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(tail_scores_kernel<sum_term>, dim3((unsigned)((a->rows + 3) / 4)), dim3(256), 0, s,
+                       sum_term{a->a, a->lda, a->b, a->ldb, a->w, a->bias}, a->scores, a->rows, a->E);
+    hipLaunchKernelGGL((tail_moments_kernel<false, sum_src>), dim3((unsigned)((a->E + POOL_SLAB - 1) / POOL_SLAB), (unsigned)a->B), dim3(256), 0, s,
+                       sum_src{a->a, a->lda, a->b, a->ldb}, a->scores, a->frame_offs, a->out, a->ldo, a->col0, a->E, a->rows);
+    return ser_check_launch("ser_attn_pool");
+}
+
+// ------------------------------------------------------------------------------- LayerNorm in front of the fusion classifier
+// One block per row: float64 statistics, the normalised row rounded to fp32.
+__global__ __launch_bounds__(256) void tail_ln_kernel(const float* __restrict__ p, int64_t ldp, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float eps, float* __restrict__ xn, int K) {
+    __shared__ double red[4];
+    const int b = blockIdx.x;
+    const float* x = p + (int64_t)b * ldp;
+    double mean, rstd;
+    row_stats_f64(x, K, eps, red, mean, rstd);
+    for (int k = threadIdx.x; k < K; k += 256) xn[(int64_t)b * K + k] = (float)(((double)x[k] - mean) * rstd * (double)gamma[k] + (double)beta[k]);
+}
+
+// ------------------------------------------------------------------------------- hidden units (first Linear)
 // One wave per hidden unit j: its W1 row sits in registers (KV 16-byte chunks per lane, lane l owns columns 4 l + 256 i), and the wave
-// walks the B utterances: hidden[b, j] = fp32(sum_k p[b, k] W1[j, k] + b1[j]), products added per lane in ascending column, then the butterfly.
-template <int KV>
-__global__ __launch_bounds__(256) void mlp_hidden_kernel(const float* __restrict__ p, int64_t ldp, const float* __restrict__ W1,
-                                                         const float* __restrict__ b1, float* __restrict__ hidden, int B, int K, int H) {
+// walks the B rows of p (pitch ldp): hidden[b, j] = fp32(sum_k p[b, k] W1[j, k] + b1[j]), through a ReLU with RELU; products added per
+// lane in ascending column, then the butterfly.
+template <int KV, bool RELU>
+__global__ __launch_bounds__(256) void tail_hidden_kernel(const float* __restrict__ p, int64_t ldp, const float* __restrict__ W1,
+                                                          const float* __restrict__ b1, float* __restrict__ hidden, int B, int K, int H) {
     const int lane = threadIdx.x & 63;
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= H) return;
@@ -145,40 +233,56 @@ __global__ __launch_bounds__(256) void mlp_hidden_kernel(const float* __restrict
                 for (int e = 0; e < 4; ++e) acc = fma((double)v[e], (double)w[i][e], acc);
             }
         }
-        acc = wave_sum_f64(acc);
-        if (lane == 0) hidden[(int64_t)b * H + j] = (float)(acc + bias);
+        acc = wave_sum_f64(acc) + bias;
+        if (RELU) acc = acc > 0.0 ? acc : 0.0;
+        if (lane == 0) hidden[(int64_t)b * H + j] = (float)acc;
     }
 }
 
-// ------------------------------------------------------------------------------- head, LayerNorm -> ReLU -> second Linear
-// One block per utterance.  LayerNorm(H) two-pass (mean, then the centred squares; biased variance, eps inside the root), thread t owns
-// units t, t + 256, ...; its n_out partial dot products run over the same units in ascending order.
-#define MLP_NOUT_MAX 8
-__global__ __launch_bounds__(256) void mlp_out_kernel(const float* __restrict__ hidden, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, float eps, const float* __restrict__ W2,
-                                                      const float* __restrict__ b2, float* __restrict__ out, int H, int n_out) {
-    __shared__ double red[4];
-    __shared__ double redo[4][MLP_NOUT_MAX];
+// the register plan of a W1 row: K <= 4096 in 1, 2, 4, 8 or 16 chunks a lane
+template <bool RELU>
+static void tail_hidden_launch(const float* p, int64_t ldp, const float* W1, const float* b1, float* hidden, int B, int K, int H, hipStream_t s) {
+    const dim3 grid((unsigned)((H + 3) / 4)), block(256);
+#define TAIL_HIDDEN(KV) hipLaunchKernelGGL((tail_hidden_kernel<KV, RELU>), grid, block, 0, s, p, ldp, W1, b1, hidden, B, K, H)
+    if (K <= 256) TAIL_HIDDEN(1);
+    else if (K <= 512) TAIL_HIDDEN(2);
+    else if (K <= 1024) TAIL_HIDDEN(4);
+    else if (K <= 2048) TAIL_HIDDEN(8);
+    else TAIL_HIDDEN(16);
+#undef TAIL_HIDDEN
+}
+
+// ------------------------------------------------------------------------------- outputs (second Linear)
+// One block per row; thread t owns units t, t + 256, ... and runs its n_out partial dot products over them in ascending order.  With LN
+// the units first pass LayerNorm(H) and a ReLU.
+#define TAIL_NOUT_MAX 8
+template <bool LN>
+__global__ __launch_bounds__(256) void tail_out_kernel(const float* __restrict__ hidden, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float eps, const float* __restrict__ W2,
+                                                       const float* __restrict__ b2, float* __restrict__ out, int H, int n_out) {
+    __shared__ double redo[4][TAIL_NOUT_MAX];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* h = hidden + (int64_t)b * H;
-    double s = 0.0;
-    for (int k = tid; k < H; k += 256) s += (double)h[k];
-    const double mean = block_sum_f64(s, red) / (double)H;
-    double q = 0.0;
-    for (int k = tid; k < H; k += 256) { const double d = (double)h[k] - mean; q = fma(d, d, q); }
-    const double rstd = 1.0 / sqrt(block_sum_f64(q, red) / (double)H + (double)eps);
-    double acc[MLP_NOUT_MAX];
+    double mean = 0.0, rstd = 1.0;
+    if constexpr (LN) {
+        __shared__ double red[4];
+        row_stats_f64(h, H, eps, red, mean, rstd);
+    }
+    double acc[TAIL_NOUT_MAX];
 #pragma unroll
-    for (int o = 0; o < MLP_NOUT_MAX; ++o) acc[o] = 0.0;
+    for (int o = 0; o < TAIL_NOUT_MAX; ++o) acc[o] = 0.0;
     for (int k = tid; k < H; k += 256) {
-        double y = ((double)h[k] - mean) * rstd * (double)gamma[k] + (double)beta[k];
-        y = y > 0.0 ? y : 0.0;
+        double y = (double)h[k];
+        if constexpr (LN) {
+            y = (y - mean) * rstd * (double)gamma[k] + (double)beta[k];
+            y = y > 0.0 ? y : 0.0;
+        }
 #pragma unroll
-        for (int o = 0; o < MLP_NOUT_MAX; ++o)
+        for (int o = 0; o < TAIL_NOUT_MAX; ++o)
             if (o < n_out) acc[o] = fma(y, (double)W2[(int64_t)o * H + k], acc[o]);
     }
 #pragma unroll
-    for (int o = 0; o < MLP_NOUT_MAX; ++o) {
+    for (int o = 0; o < TAIL_NOUT_MAX; ++o) {
         const double v = wave_sum_f64(acc[o]);
         if ((tid & 63) == 0) redo[tid >> 6][o] = v;
     }
@@ -190,20 +294,30 @@ extern "C" int ser_mlp_head_v(const ser_mlp_head_args* a, void* stream) {
     if (!a) return ser_fail(-1, "ser_mlp_head: null pointer");
     if (!a->p || !a->W1 || !a->b1 || !a->gamma || !a->beta || !a->W2 || !a->b2 || !a->hidden || !a->out)
         return ser_fail(-1, "ser_mlp_head: null pointer");
-    if (a->n_out < 1 || a->n_out > MLP_NOUT_MAX) return ser_fail(-2, "ser_mlp_head: n_out=%d (1..%d)", a->n_out, MLP_NOUT_MAX);
+    if (a->n_out < 1 || a->n_out > TAIL_NOUT_MAX) return ser_fail(-2, "ser_mlp_head: n_out=%d (1..%d)", a->n_out, TAIL_NOUT_MAX);
     if (a->B <= 0 || a->H <= 0 || a->K <= 0 || (a->K % 4) || a->K > 4096 || a->ldp < a->K || (a->ldp % 4))
         return ser_fail(-2, "ser_mlp_head: bad B=%d H=%d K=%d (K %% 4 == 0, K <= 4096) ldp=%lld (>= K, multiple of 4)", a->B, a->H, a->K,
                         (long long)a->ldp);
     if ((((uintptr_t)a->p | (uintptr_t)a->W1) & 15) != 0) return ser_fail(-2, "ser_mlp_head: p and W1 must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((a->H + 3) / 4)), block(256);
-#define MLP_HIDDEN(KV) hipLaunchKernelGGL(mlp_hidden_kernel<KV>, grid, block, 0, s, a->p, a->ldp, a->W1, a->b1, a->hidden, a->B, a->K, a->H)
-    if (a->K <= 256) MLP_HIDDEN(1);
-    else if (a->K <= 512) MLP_HIDDEN(2);
-    else if (a->K <= 1024) MLP_HIDDEN(4);
-    else if (a->K <= 2048) MLP_HIDDEN(8);
-    else MLP_HIDDEN(16);
-#undef MLP_HIDDEN
-    hipLaunchKernelGGL(mlp_out_kernel, dim3(a->B), dim3(256), 0, s, a->hidden, a->gamma, a->beta, a->eps, a->W2, a->b2, a->out, a->H, a->n_out);
+    tail_hidden_launch<false>(a->p, a->ldp, a->W1, a->b1, a->hidden, a->B, a->K, a->H, s);
+    hipLaunchKernelGGL(tail_out_kernel<true>, dim3((unsigned)a->B), dim3(256), 0, s, a->hidden, a->gamma, a->beta, a->eps, a->W2, a->b2, a->out,
+                       a->H, a->n_out);
     return ser_check_launch("ser_mlp_head");
+}
+
+extern "C" int ser_fusion_cls_v(const ser_fusion_cls_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_fusion_cls: null pointer");
+    if (!a->p || !a->gamma || !a->beta || !a->W1 || !a->b1 || !a->W2 || !a->b2 || !a->xn || !a->hidden || !a->out)
+        return ser_fail(-1, "ser_fusion_cls: null pointer");
+    if (a->n_out < 1 || a->n_out > TAIL_NOUT_MAX) return ser_fail(-2, "ser_fusion_cls: n_out=%d (1..%d)", a->n_out, TAIL_NOUT_MAX);
+    if (a->B <= 0 || a->B > 65535 || a->H1 <= 0 || a->K <= 0 || (a->K % 4) || a->K > 4096 || a->ldp < a->K)
+        return ser_fail(-2, "ser_fusion_cls: bad B=%d H1=%d K=%d (K %% 4 == 0, K <= 4096) ldp=%lld (>= K)", a->B, a->H1, a->K, (long long)a->ldp);
+    if ((((uintptr_t)a->xn | (uintptr_t)a->W1) & 15) != 0) return ser_fail(-2, "ser_fusion_cls: xn and W1 must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(tail_ln_kernel, dim3((unsigned)a->B), dim3(256), 0, s, a->p, a->ldp, a->gamma, a->beta, a->eps, a->xn, a->K);
+    tail_hidden_launch<true>(a->xn, a->K, a->W1, a->b1, a->hidden, a->B, a->K, a->H1, s);
+    hipLaunchKernelGGL(tail_out_kernel<false>, dim3((unsigned)a->B), dim3(256), 0, s, a->hidden, nullptr, nullptr, 0.f, a->W2, a->b2, a->out,
+                       a->H1, a->n_out);
+    return ser_check_launch("ser_fusion_cls");
 }

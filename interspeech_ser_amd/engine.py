@@ -253,91 +253,30 @@ class HiddenStates:
         return bits
 
 
-class _EncoderBase:
-    def __init__(self, geo: EncoderGeometry, device, mode: str, post_ln: bool = False):
-        if mode not in MODES:
-            raise ValueError(f"mode must be one of {list(MODES)}")
-        if post_ln and mode not in POST_LN_MODES:
-            raise ValueError(f"the post-LayerNorm encoders support the {', '.join(POST_LN_MODES)} numerics modes")
-        self.post_ln = post_ln
+def _operand_mode(mode_name: str) -> int:
+    """GEMM operand format of the heads: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo in every other mode -- their products
+    feed a softmax over the frames, where single-product rounding is not benign"""
+    return {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X}.get(mode_name, _lib.MODE_FP16X)
+
+
+class _LaunchHost:
+    """Weight and launch helpers (``_linear`` / ``_dev_f32`` / ``_gemm`` / ``_layernorm``): the base of every encoder, and used as it is by
+    the fusion heads -- one operand format for every GEMM, launches issued at once (nothing is recorded)."""
+
+    def __init__(self, device, mode_name: str, mode: int, stem_mode: int, fp16_planes: bool):
         if not torch.cuda.is_available():
             raise _lib.SerHipError("no HIP device visible: the extraction path has no CPU fallback")
-        self.geo = geo
         self.device = torch.device(device)
-        self.mode_name = mode
-        self.mode = MODES[mode]                                   # encoder layers
-        # conv stem (+ projection, positional conv): the 3-product split in every parity mode.  The fp16-layer modes take it on fp16 hi + lo
-        # planes (22-bit operands, round 3) rather than bf16 hi + lo (16-bit, the "fp32x" mode's): same cost, and the stem's share of the error
-        # -- which sharp attention amplifies like any other -- drops by the 6 extra bits per operand
-        self.stem_mode = (_lib.MODE_FP16X if _STEM_F16X else _lib.MODE_FP32X) if mode in ("f16", "f16q", "f16a") else self.mode
-        if mode in ("f16m", "f16mf"):
-            self.stem_mode = _lib.MODE_FP16X
-        # WavLM gate inside ser_attention (see the note at the top) -- except beside a packed projection in SER_MODE_FP16M, where it rides as 2H
-        # extra output columns (per layer: _lay_modes)
-        self.gate_in_attn = _os.environ.get("SER_GATE_IN_ATTN", "1") == "1"
-        self.qk_mode = _lib.MODE_FP16X if mode == "f16q" else None             # logit path on its own launch (None: one packed launch)
-        self.attn_mode = _lib.MODE_FP16X if mode in ("f16a", "f16m", "f16mf") else self.mode   # attention kernel, context rows, output projection
-        self.qkv_mode = self.attn_mode                                         # packed projection (layers before qkv_m_from)
-        self.x_mode = self.qk_mode or self.qkv_mode                            # format of the operand copy the packed projection reads
-        self.qkv_out_mode = self.x_mode                                        # format of q, k, v (what ser_attention reads)
-        # First layer whose PACKED PROJECTION multiplies in SER_MODE_FP16M (see _lay_modes): "f16m" 0 = every layer; "f16mf" a third of the
-        # depth (8 of 24, 16 of 48, 11 of 32).  An operand error injected by layer i passes through L - i more softmax layers: the what-if
-        # (oracle/numerics_whatif_f16m.py, sites "qkv>=N") puts the packed projection in that format from layer 8 of 24 on at 1.44e-4 / 3.7e-5
-        # (sharp x2 / LoRA) against 1.43e-4 / 2.7e-5 with none and 5.2e-4 / 4.7e-4 with all -- its error lives in the first layers.
-        self.qkv_m_from: Optional[int] = {"f16m": 0, "f16mf": (geo.num_layers + 2) // 3}.get(mode)
-        if mode == "f16mf" and _os.environ.get("SER_F16MF_QKV_FROM"):          # A/B knob (tools/): -1 = never
-            v = int(_os.environ["SER_F16MF_QKV_FROM"])
-            self.qkv_m_from = None if v < 0 else v
-        self.planes, self.stem_planes = _PLANES[self.mode], _PLANES[self.stem_mode]
-        self._cache: Dict = {}
+        self.mode_name = mode_name
+        self.mode, self.stem_mode = mode, stem_mode              # operand format of the layers' GEMMs / of the stem's
+        self.fp16_planes = fp16_planes                           # operand copies with fp16's range: the guard word is live
+        self.geo: Optional[EncoderGeometry] = None               # an encoder's geometry; without one, _layernorm needs its ``eps``
         # when a list, every ser_gemm launch appends (start_event, end_event, algorithmic_flops):
         # bench.py uses it for the live roofline figure of the dominant kernel
         self.gemm_trace: Optional[list] = None
-        # when a list, every encoder layer appends (start_event, end_event, utterances) around its attention block
-        # (packed QKV projection -> attention -> output projection): bench.py's "attention_block" figure
-        self.block_trace: Optional[list] = None
-        # operand copies with fp16's range: the guard word is live (SER_NO_RANGE_GUARD=1: A/B knob for tools/, never the drivers)
-        self.fp16_planes = mode in ("f16x", "f16m", "f16mf", "f16a", "f16q", "f16") and _os.environ.get("SER_NO_RANGE_GUARD", "0") != "1"
         self._flag: Optional[int] = None    # device address of the range-guard word of the slot being launched / recorded
         self._st: Optional[int] = None      # launch stream of the forward in progress (looked up once per forward)
         self._rec: Optional[Tape] = None    # when set, _issue records the launch helpers' commands into it instead of launching them
-
-    def _guard_word(self, pl) -> Optional[torch.Tensor]:
-        """the slot's range-guard word (allocated with the plan); launch helpers pick its address up from ``self._flag``"""
-        if not self.fp16_planes:
-            self._flag = None
-            return None
-        t = pl.get("range_flag")
-        if t is None:
-            t = pl["range_flag"] = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._flag = t.data_ptr()
-        return t
-
-    def _lay_modes(self, i: int) -> dict:
-        """Formats around layer i's packed projection: the GEMM's mode, the layer input's operand copy it reads (written by ser_row_center for
-        layer 0, by FC2 of layer i - 1 otherwise), q / k / v as ser_attention reads them, and where the WavLM gate is evaluated.  With the
-        projection in SER_MODE_FP16M the gate rides as 2H extra output columns: the in-kernel form multiplies the layer input's operand copy,
-        whose second plane is e4m3 bytes in that format."""
-        if self.qkv_m_from is not None and i >= self.qkv_m_from:
-            # ... and with head dim 64 (a head = one 64-column tile) ser_attention can write its context rows as FP16M operands (ABI 14), so that
-            # the OUTPUT projection of these layers multiplies in the format too (what-if "qkv>=8+out>=8": 1.44e-4 / 4.1e-5; + 1.6 % on the
-            # default's step, same envelope on WavLM-large).  OPT-IN (SER_F16M_OUT_M=1), not the default (a performance decision of its own).
-            # Its 0.57 on bench.py's Whisper-large-v3 record was not the format: the FP16M output projections filled every 64-column slot of the
-            # row partials ``ph``, the 3-product output projection of the first layers (256 x 256 tile, 128-column waves) wrote only every
-            # other slot, and from the second forward over a plan on the first layers' LayerNorm summed the stale ones.  ser_gemm now zeroes
-            # the second slot of such a wave (DESIGN.md section 10; tests/test_gpu_replay.py, test_gpu_kernels.py: stat_out slots).
-            return dict(qkv_mode=_lib.MODE_FP16M, x_mode=_lib.MODE_FP16M, qkv_out_mode=self.attn_mode, gate_in_attn=False,
-                        out_m=self.geo.head_dim == 64 and _os.environ.get("SER_F16M_OUT_M", "0") == "1")
-        return dict(qkv_mode=self.qkv_mode, x_mode=self.x_mode, qkv_out_mode=self.qkv_out_mode, gate_in_attn=self.gate_in_attn, out_m=False)
-
-    def _check_last_state(self, last_state: Optional[int]) -> Optional[int]:
-        if last_state is None:
-            return None
-        L = self.geo.num_layers
-        last_state = int(last_state)
-        if not 0 <= last_state <= L:
-            raise IndexError("tuple index out of range")         # what hidden_states[N] raises in the reference
-        return None if last_state == L else last_state
 
     def _s(self) -> int:
         """HIP stream of the current forward: torch.cuda.current_stream() costs ~15 us and a forward makes ~150 launches."""
@@ -420,16 +359,6 @@ class _EncoderBase:
             return
         view.cmd.op = op
         check(lib.ser_run(C.byref(view.cmd), 1, None, self._s()), what)
-
-    def _state_done(self, i: int, last_state: Optional[int]) -> bool:
-        """Hidden state ``i`` is complete; True = stop here.  ``last_state`` = N: the caller reads hidden_states[N] only (the reference's
-        speech script keeps one state, preprocess_speech.py:67), so the layers that only feed later states are not launched.  Recording
-        a command list marks where every state is complete instead (Tape.marks), and the replay stops there."""
-        rec = self._rec
-        if rec is None:
-            return last_state == i
-        rec.marks[i] = rec.n
-        return False
 
     def _gemm(self, a: Act, lin: Linear, M: int, *, a_rowoff=None, lda=None, kc=0, ldj=0, groups=1,
               a_group_stride=0, w_group_stride=0, c_group_stride=0, N=None, K=None, act=_lib.ACT_NONE,
@@ -524,6 +453,93 @@ class _EncoderBase:
         a.mode, a.rows, a.D = mode, rows, D
         a.range_flag = self._flag if out_act is not None else None
         self._issue(_lib.OP_LAYERNORM, a, "ser_layernorm", rows=rows)
+
+
+class _EncoderBase(_LaunchHost):
+    def __init__(self, geo: EncoderGeometry, device, mode: str, post_ln: bool = False):
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {list(MODES)}")
+        if post_ln and mode not in POST_LN_MODES:
+            raise ValueError(f"the post-LayerNorm encoders support the {', '.join(POST_LN_MODES)} numerics modes")
+        self.post_ln = post_ln
+        # conv stem (+ projection, positional conv): the 3-product split in every parity mode.  The fp16-layer modes take it on fp16 hi + lo
+        # planes (22-bit operands, round 3) rather than bf16 hi + lo (16-bit, the "fp32x" mode's): same cost, and the stem's share of the error
+        # -- which sharp attention amplifies like any other -- drops by the 6 extra bits per operand
+        stem_mode = (_lib.MODE_FP16X if _STEM_F16X else _lib.MODE_FP32X) if mode in ("f16", "f16q", "f16a") else MODES[mode]
+        if mode in ("f16m", "f16mf"):
+            stem_mode = _lib.MODE_FP16X
+        # operand copies with fp16's range: the guard word is live (SER_NO_RANGE_GUARD=1: A/B knob for tools/, never the drivers)
+        fp16_planes = mode in ("f16x", "f16m", "f16mf", "f16a", "f16q", "f16") and _os.environ.get("SER_NO_RANGE_GUARD", "0") != "1"
+        super().__init__(device, mode, MODES[mode], stem_mode, fp16_planes)
+        self.geo = geo
+        # WavLM gate inside ser_attention (see the note at the top) -- except beside a packed projection in SER_MODE_FP16M, where it rides as 2H
+        # extra output columns (per layer: _lay_modes)
+        self.gate_in_attn = _os.environ.get("SER_GATE_IN_ATTN", "1") == "1"
+        self.qk_mode = _lib.MODE_FP16X if mode == "f16q" else None             # logit path on its own launch (None: one packed launch)
+        self.attn_mode = _lib.MODE_FP16X if mode in ("f16a", "f16m", "f16mf") else self.mode   # attention kernel, context rows, output projection
+        self.qkv_mode = self.attn_mode                                         # packed projection (layers before qkv_m_from)
+        self.x_mode = self.qk_mode or self.qkv_mode                            # format of the operand copy the packed projection reads
+        self.qkv_out_mode = self.x_mode                                        # format of q, k, v (what ser_attention reads)
+        # First layer whose PACKED PROJECTION multiplies in SER_MODE_FP16M (see _lay_modes): "f16m" 0 = every layer; "f16mf" a third of the
+        # depth (8 of 24, 16 of 48, 11 of 32).  An operand error injected by layer i passes through L - i more softmax layers: the what-if
+        # (oracle/numerics_whatif_f16m.py, sites "qkv>=N") puts the packed projection in that format from layer 8 of 24 on at 1.44e-4 / 3.7e-5
+        # (sharp x2 / LoRA) against 1.43e-4 / 2.7e-5 with none and 5.2e-4 / 4.7e-4 with all -- its error lives in the first layers.
+        self.qkv_m_from: Optional[int] = {"f16m": 0, "f16mf": (geo.num_layers + 2) // 3}.get(mode)
+        if mode == "f16mf" and _os.environ.get("SER_F16MF_QKV_FROM"):          # A/B knob (tools/): -1 = never
+            v = int(_os.environ["SER_F16MF_QKV_FROM"])
+            self.qkv_m_from = None if v < 0 else v
+        self.planes, self.stem_planes = _PLANES[self.mode], _PLANES[self.stem_mode]
+        self._cache: Dict = {}
+        # when a list, every encoder layer appends (start_event, end_event, utterances) around its attention block
+        # (packed QKV projection -> attention -> output projection): bench.py's "attention_block" figure
+        self.block_trace: Optional[list] = None
+
+    def _guard_word(self, pl) -> Optional[torch.Tensor]:
+        """the slot's range-guard word (allocated with the plan); launch helpers pick its address up from ``self._flag``"""
+        if not self.fp16_planes:
+            self._flag = None
+            return None
+        t = pl.get("range_flag")
+        if t is None:
+            t = pl["range_flag"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._flag = t.data_ptr()
+        return t
+
+    def _lay_modes(self, i: int) -> dict:
+        """Formats around layer i's packed projection: the GEMM's mode, the layer input's operand copy it reads (written by ser_row_center for
+        layer 0, by FC2 of layer i - 1 otherwise), q / k / v as ser_attention reads them, and where the WavLM gate is evaluated.  With the
+        projection in SER_MODE_FP16M the gate rides as 2H extra output columns: the in-kernel form multiplies the layer input's operand copy,
+        whose second plane is e4m3 bytes in that format."""
+        if self.qkv_m_from is not None and i >= self.qkv_m_from:
+            # ... and with head dim 64 (a head = one 64-column tile) ser_attention can write its context rows as FP16M operands (ABI 14), so that
+            # the OUTPUT projection of these layers multiplies in the format too (what-if "qkv>=8+out>=8": 1.44e-4 / 4.1e-5; + 1.6 % on the
+            # default's step, same envelope on WavLM-large).  OPT-IN (SER_F16M_OUT_M=1), not the default (a performance decision of its own).
+            # Its 0.57 on bench.py's Whisper-large-v3 record was not the format: the FP16M output projections filled every 64-column slot of the
+            # row partials ``ph``, the 3-product output projection of the first layers (256 x 256 tile, 128-column waves) wrote only every
+            # other slot, and from the second forward over a plan on the first layers' LayerNorm summed the stale ones.  ser_gemm now zeroes
+            # the second slot of such a wave (DESIGN.md section 10; tests/test_gpu_replay.py, test_gpu_kernels.py: stat_out slots).
+            return dict(qkv_mode=_lib.MODE_FP16M, x_mode=_lib.MODE_FP16M, qkv_out_mode=self.attn_mode, gate_in_attn=False,
+                        out_m=self.geo.head_dim == 64 and _os.environ.get("SER_F16M_OUT_M", "0") == "1")
+        return dict(qkv_mode=self.qkv_mode, x_mode=self.x_mode, qkv_out_mode=self.qkv_out_mode, gate_in_attn=self.gate_in_attn, out_m=False)
+
+    def _check_last_state(self, last_state: Optional[int]) -> Optional[int]:
+        if last_state is None:
+            return None
+        L = self.geo.num_layers
+        last_state = int(last_state)
+        if not 0 <= last_state <= L:
+            raise IndexError("tuple index out of range")         # what hidden_states[N] raises in the reference
+        return None if last_state == L else last_state
+
+    def _state_done(self, i: int, last_state: Optional[int]) -> bool:
+        """Hidden state ``i`` is complete; True = stop here.  ``last_state`` = N: the caller reads hidden_states[N] only (the reference's
+        speech script keeps one state, preprocess_speech.py:67), so the layers that only feed later states are not launched.  Recording
+        a command list marks where every state is complete instead (Tape.marks), and the replay stops there."""
+        rec = self._rec
+        if rec is None:
+            return last_state == i
+        rec.marks[i] = rec.n
+        return False
 
     def _row_center(self, x: torch.Tensor, out_act: Act, stats: torch.Tensor, shift: torch.Tensor, rows: int, D: int):
         """hidden_states[0] -> centred operand copy + row partials + shift for encoder layer 0 (ser_row_center)."""
@@ -1797,7 +1813,22 @@ def mean_last4(hs: HiddenStates) -> torch.Tensor:
     return out
 
 
-class PoolHead:
+class _HeadBase:
+    """what the device heads share: the per-step timing of ``forward``"""
+    trace: Optional[list] = None          # when a list: (name, start event, end event) per step (tools/pool_head_bench.py, fusion_head_bench.py)
+
+    def _step(self, name: str, fn) -> None:
+        if self.trace is None:
+            fn()
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        self.trace.append((name, e0, e1))
+
+
+class PoolHead(_HeadBase):
     """The organiser baseline's utterance-level tail on the device (benchmark/train_eval_files/eval_cat_ser.py:164-177):
     ``last_hidden_state`` -> AttentiveStatisticsPooling -> EmotionRegression -> ``[B, n_out]`` logits, so a waveform -> prediction run
     brings ``n_out`` floats per utterance back instead of ``[T, D]``.  Built from a speech encoder (its device and numerics mode) and the
@@ -1816,7 +1847,7 @@ class PoolHead:
         if D % 64:
             raise ValueError(f"PoolHead needs a hidden width that is a multiple of 64 (ser_gemm's K rule), got {D}")
         self.enc, self.D, self.device = enc, D, enc.device
-        self.op_mode = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X}.get(enc.mode_name, _lib.MODE_FP16X)
+        self.op_mode = _operand_mode(enc.mode_name)
         w, b, a = pool_sd["sap_linear.weight"], pool_sd["sap_linear.bias"], pool_sd["attention"]
         if tuple(w.shape) != (D, D) or tuple(b.shape) != (D,) or a.numel() != D:
             raise ValueError(f"pooling weights do not match hidden width {D}: sap_linear.weight {tuple(w.shape)}, attention {tuple(a.shape)}")
@@ -1832,7 +1863,6 @@ class PoolHead:
         self.w2, self.b2 = enc._dev_f32(w2), enc._dev_f32(ser_sd["out.0.bias"])
         self.ln_eps = 1e-5                                        # nn.LayerNorm's default (ser.py builds it without an eps)
         self._bufs: Dict[int, dict] = {}
-        self.trace: Optional[list] = None                        # when a list: (name, start event, end event) per step (tools/pool_head_bench.py)
 
     def _buffers(self, slot: int, M: int, B: int) -> dict:
         """grow-only buffers of one pipeline slot (slots run on streams of their own, so they share nothing)"""
@@ -1851,16 +1881,6 @@ class PoolHead:
                   offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
         self._bufs[slot] = bf
         return bf
-
-    def _step(self, name: str, fn) -> None:
-        if self.trace is None:
-            fn()
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        self.trace.append((name, e0, e1))
 
     def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
         """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``).  The range
@@ -1895,25 +1915,6 @@ class PoolHead:
         return bf["out"][:B]
 
 
-class _KernelHost(_EncoderBase):
-    """The encoders' weight and launch helpers (``_linear`` / ``_dev_f32`` / ``_gemm`` / ``_layernorm``) without an encoder around them:
-    one operand format for every GEMM, launches issued at once (nothing is recorded)."""
-
-    def __init__(self, device, mode_name: str, op_mode: int):
-        if not torch.cuda.is_available():
-            raise _lib.SerHipError("no HIP device visible: the fusion head has no CPU path")
-        self.geo = None
-        self.device = torch.device(device)
-        self.mode_name = mode_name
-        self.mode = self.stem_mode = op_mode
-        self.fp16_planes = op_mode == _lib.MODE_FP16X
-        self._cache: Dict = {}
-        self.gemm_trace = None
-        self._flag = None
-        self._st = None
-        self._rec = None
-
-
 def _fusion_keys(names) -> Dict[str, tuple]:
     """state-dict keys and symbolic shapes of the reference's fusion head over the modalities ``names`` (feature width of modality i: "d<i+1>")"""
     keys = {"classifier.0.weight": ("h1", "ne"), "classifier.0.bias": ("h1",), "classifier.3.weight": ("n", "h1"), "classifier.3.bias": ("n",),
@@ -1934,7 +1935,7 @@ TRIMODAL_KEYS = _fusion_keys(("speech", "text", "prosody"))
 FUSION_BATCH = 16                                                 # utterances per MFMA column group of ser_gru_v
 
 
-class _FusionBase:
+class _FusionBase(_HeadBase):
     """The reference's fusion heads over the modalities ``NAMES`` (the prefixes of their state-dict keys), on packed ragged batches, EVERY
     UTTERANCE ALONE.  Everything of one ``forward`` goes on the current stream, in order: a ser_gru_v cluster makes progress only while all
     of its blocks are resident, so two recurrences are never in flight together.  Per modality
@@ -1951,7 +1952,7 @@ class _FusionBase:
         names, n = self.NAMES, len(self.NAMES)
         if mode not in MODES:
             raise ValueError(f"mode must be one of {list(MODES)}")
-        self.op_mode = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X}.get(mode, _lib.MODE_FP16X)
+        self.op_mode = _operand_mode(mode)
         if any(d <= 0 or d % 64 for d in dims_in):
             raise ValueError(f"{type(self).__name__} needs feature widths that are multiples of 64 (ser_gemm's K rule), got "
                              + " ".join(f"D{i + 1}={d}" for i, d in enumerate(dims_in)))
@@ -1975,7 +1976,7 @@ class _FusionBase:
             want = tuple(dims.get(w, w) for w in want)
             if tuple(sd[k].shape) != want:
                 raise ValueError(f"{k} has shape {tuple(sd[k].shape)}, expected {want}")
-        self.host = host = _KernelHost(device, mode, self.op_mode)
+        self.host = host = _LaunchHost(device, mode, self.op_mode, self.op_mode, self.op_mode == _lib.MODE_FP16X)
         self.device, self.mode_name = host.device, mode
         self.h, self.E, self.h1, self.n_out, self.dims_in, self.heads, self.cluster = h, E, h1, n_out, tuple(dims_in), heads, int(cluster)
         om = self.op_mode
@@ -2016,7 +2017,6 @@ class _FusionBase:
         self.R = r.value
         self._epoch = 1
         self._bufs: Dict[int, dict] = {}
-        self.trace: Optional[list] = None                        # when a list: (name, start event, end event) per step (tools/fusion_head_bench.py)
 
     def _buffers(self, slot: int, Ms: Sequence[int], B: int) -> dict:
         """grow-only buffers of one pipeline slot"""
@@ -2041,16 +2041,6 @@ class _FusionBase:
         self._bufs[slot] = bf
         return bf
 
-    def _step(self, name: str, fn) -> None:
-        if self.trace is None:
-            fn()
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        self.trace.append((name, e0, e1))
-
     def _gru(self, bf, sb, w, B: int, M: int, max_frames: int, st: int) -> None:
         g = _lib.GruArgs()
         g.gx, g.ldgx, g.whh, g.whh_plane_stride, g.bhh = sb["gx"].data_ptr(), 6 * self.h, w["whh"].w.data_ptr(), 6 * self.h * self.h, w["bhh"].data_ptr()
@@ -2060,13 +2050,6 @@ class _FusionBase:
         g.B, g.H, g.rows, g.max_frames, g.mode, g.cluster, g.epoch = B, self.h, M, max_frames, self.op_mode, self.cluster, self._epoch & 0xFFFFFFFF
         self._epoch += 1 + B // FUSION_BATCH
         check(lib.ser_gru_v(C.byref(g), st), "ser_gru_v")
-
-    def _xattn(self, xa, heads: int, st: int) -> None:
-        """launch the filled ``ser_xattn_mh_args``"""
-        xa.heads = heads
-        check(lib.ser_xattn_mh_v(C.byref(xa), st), "ser_xattn_mh_v")
-
-    _XattnArgs = _lib.XattnMhArgs
 
     def _forward(self, xs: Sequence[torch.Tensor], offs_in: Sequence[Sequence[int]], slot: int, range_flag: Optional[torch.Tensor]) -> torch.Tensor:
         names, n = self.NAMES, len(self.NAMES)
@@ -2113,13 +2096,14 @@ class _FusionBase:
                 sk = bf["side"][j]
                 kcol = 2 * E * self.others[j].index(i)            # module i's k | v block inside modality j's stacked projection
                 ctx = sq["ctx"][t].first_rows(Ms[i])
-                xa = self._XattnArgs()
+                xa = _lib.XattnMhArgs()
                 xa.q, xa.ldq, xa.k, xa.ldk = sq["q"].data_ptr(), E, sk["kv"].data_ptr() + 4 * kcol, ldkv
                 xa.v, xa.ldv = sk["kv"].data_ptr() + 4 * (kcol + E), ldkv
                 xa.q_offs, xa.k_offs = sq["offs"].data_ptr(), sk["offs"].data_ptr()
                 xa.out_act, xa.ldo_act, xa.out_plane_stride, xa.range_flag = ctx.ptr, E, ctx.plane_stride, flag
                 xa.scale, xa.B, xa.E, xa.q_rows, xa.k_rows, xa.max_q, xa.mode = float(E // self.heads[i]) ** -0.5, B, E, Ms[i], Ms[j], maxf[i], om
-                self._step(f"{names[i]} xattn" + (f" {names[j]}" if n > 2 else ""), lambda: self._xattn(xa, self.heads[i], st))
+                xa.heads = self.heads[i]
+                self._step(f"{names[i]} xattn" + (f" {names[j]}" if n > 2 else ""), lambda: check(lib.ser_xattn_mh_v(C.byref(xa), st), "ser_xattn_mh_v"))
         for i in range(n):
             sq, a = bf["side"][i], self.att[i]
             for t, j in enumerate(self.others[i]):
@@ -2168,19 +2152,15 @@ class FusionHead(_FusionBase):
     pooling softmax, and a batch is arithmetically that batch-of-one loop (``head.evaluate``'s torch path pads to the batch's longest
     utterance instead).  ``forward`` enqueues on the current stream, outside the encoders' recorded tapes; per modality
       ser_pack_rows_flagged -> ser_gemm (projection) -> ser_layernorm_v (operand copy) -> ser_gemm (both directions' x W_ih^T) -> ser_gru_v
-    then the four in-projection GEMMs (q of one side, packed k | v of the other, both ways), 2 x ser_xattn_v, 2 x out-projection GEMM,
+    then the four in-projection GEMMs (q of one side, packed k | v of the other, both ways), 2 x ser_xattn_mh_v (heads = 1), 2 x out-projection GEMM,
     2 x ser_attn_pool_v and ser_fusion_cls_v.  GEMM operand format: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo otherwise;
     the recurrent product is always fp16 hi + lo."""
     NAMES = ("speech", "text")
     KEYS = FUSION_KEYS
-    _XattnArgs = _lib.XattnArgs
 
     def __init__(self, state_dict, d1: int, d2: int, device="cuda:0", mode: str = "f16x", cluster: int = 0):
         self._init(state_dict, (d1, d2), (1, 1), device, mode, cluster)
         self.d1, self.d2 = d1, d2
-
-    def _xattn(self, xa, heads: int, st: int) -> None:
-        check(lib.ser_xattn_v(C.byref(xa), st), "ser_xattn_v")
 
     def forward(self, x1: torch.Tensor, offs1: Sequence[int], x2: torch.Tensor, offs2: Sequence[int], slot: int = 0,
                 range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:

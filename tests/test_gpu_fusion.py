@@ -30,6 +30,15 @@ def _dev(x, dtype=np.float32):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(DEV)
 
 
+def _dev_rows(x, ld=None):
+    """fp32 rows on the device at row pitch ``ld`` (default: contiguous); the padding columns hold NaN"""
+    if ld is None:
+        return _dev(x)
+    t = torch.full((x.shape[0], ld), float("nan"), dtype=torch.float32, device=DEV)
+    t[:, : x.shape[1]] = _dev(x)
+    return t
+
+
 def _report(what, err, e_ref, e_split):
     print(f"FUSION {what}: error {err:.3e}  e_ref {e_ref:.3e}  e_split {e_split:.3e}  gate {2.0 * (e_ref + e_split):.3e}")
 
@@ -234,16 +243,16 @@ def test_xattn_ragged_pairs(built_library, E):
 
 
 # ------------------------------------------------------------------------------- ser_attn_pool_v
-def gpu_attn_pool(a, b, w, bias, lengths, col0=0, width=None):
+def gpu_attn_pool(a, b, w, bias, lengths, col0=0, width=None, lda=None, ldb=None):
     from interspeech_ser_amd import _lib
     E, offs = a.shape[1], _offs(lengths)
     width = width or E
-    ad, bd, wd = _dev(a), _dev(b), _dev(w)
+    ad, bd, wd = _dev_rows(a, lda), _dev_rows(b, ldb), _dev(w)
     od = torch.tensor(offs, dtype=torch.int32, device=DEV)
     scores = torch.empty(offs[-1], dtype=torch.float32, device=DEV)
     out = torch.full((len(lengths), width), float("nan"), dtype=torch.float32, device=DEV)
     p = _lib.AttnPoolArgs()
-    p.a, p.lda, p.b, p.ldb, p.w, p.frame_offs, p.scores = ad.data_ptr(), E, bd.data_ptr(), E, wd.data_ptr(), od.data_ptr(), scores.data_ptr()
+    p.a, p.lda, p.b, p.ldb, p.w, p.frame_offs, p.scores = ad.data_ptr(), lda or E, bd.data_ptr(), ldb or E, wd.data_ptr(), od.data_ptr(), scores.data_ptr()
     p.out, p.ldo, p.bias, p.col0, p.B, p.E, p.rows, p.max_frames = out.data_ptr(), width, bias, col0, len(lengths), E, offs[-1], max(lengths)
     _lib.check(_lib.lib.ser_attn_pool_v(ctypes.byref(p), torch.cuda.current_stream().cuda_stream), "ser_attn_pool_v")
     torch.cuda.synchronize()
@@ -273,16 +282,30 @@ def test_attn_pool(built_library, E):
         assert np.array_equal(one[0].view(np.uint32), got[i, E:].view(np.uint32))
 
 
+def test_attn_pool_padded_rows_are_bit_equal(built_library):
+    """row pitches beyond E (lda = E + 4, ldb = E + 8) and an output window inside a wider row (col0 = 4, ldo = E + 8): the same bits as
+    contiguous rows, nothing written outside the window.  E = 68: a last slab with one live quad; 17 frames: two in row group 0"""
+    E, lengths = 68, (1, 17)
+    rng = np.random.default_rng(3 * E)
+    a, b = (rng.standard_normal((sum(lengths), E)).astype(np.float32) for _ in range(2))
+    w, bias = (rng.standard_normal(E) / np.sqrt(E)).astype(np.float32), 0.3
+    flat = gpu_attn_pool(a, b, w, bias, lengths)
+    padded = gpu_attn_pool(a, b, w, bias, lengths, col0=4, width=E + 8, lda=E + 4, ldb=E + 8)
+    assert np.isfinite(flat).all() and np.array_equal(flat[0], a[0] + b[0])
+    assert np.array_equal(padded[:, 4:4 + E].view(np.uint32), flat.view(np.uint32))
+    assert np.isnan(padded[:, :4]).all() and np.isnan(padded[:, 4 + E:]).all()
+
+
 # ------------------------------------------------------------------------------- ser_fusion_cls_v
-def gpu_cls(p, gamma, beta, w1, b1, w2, b2):
+def gpu_cls(p, gamma, beta, w1, b1, w2, b2, ldp=None):
     from interspeech_ser_amd import _lib
     B, K = p.shape
     H1, n_out = w1.shape[0], w2.shape[0]
-    t = [_dev(v) for v in (p, gamma, beta, w1, b1, w2, b2)]
+    t = [_dev_rows(p, ldp)] + [_dev(v) for v in (gamma, beta, w1, b1, w2, b2)]
     xn, hidden = torch.empty((B, K), dtype=torch.float32, device=DEV), torch.empty((B, H1), dtype=torch.float32, device=DEV)
     out = torch.full((B, n_out), float("nan"), dtype=torch.float32, device=DEV)
     c = _lib.FusionClsArgs()
-    c.p, c.ldp, c.gamma, c.beta, c.W1, c.b1, c.W2, c.b2 = t[0].data_ptr(), K, *(v.data_ptr() for v in t[1:])
+    c.p, c.ldp, c.gamma, c.beta, c.W1, c.b1, c.W2, c.b2 = t[0].data_ptr(), ldp or K, *(v.data_ptr() for v in t[1:])
     c.xn, c.hidden, c.out, c.eps, c.B, c.K, c.H1, c.n_out = xn.data_ptr(), hidden.data_ptr(), out.data_ptr(), 1e-5, B, K, H1, n_out
     _lib.check(_lib.lib.ser_fusion_cls_v(ctypes.byref(c), torch.cuda.current_stream().cuda_stream), "ser_fusion_cls_v")
     torch.cuda.synchronize()
@@ -306,6 +329,19 @@ def test_fusion_classifier(built_library, K, H1, n_out):
     assert got.shape == (5, n_out) and err <= 2.0 * e_ref
     for i in range(5):
         assert np.array_equal(gpu_cls(p[i:i + 1], gamma, beta, w1, b1, w2, b2)[0].view(np.uint32), got[i].view(np.uint32))
+
+
+def test_fusion_classifier_padded_rows_are_bit_equal(built_library):
+    """input pitch beyond K (ldp = K + 8): the same bits as contiguous rows.  K = 384: two chunks a lane, the second partly dead"""
+    K, H1, n_out = 384, 64, 3
+    rng = np.random.default_rng(K + n_out)
+    p = (1.5 * rng.standard_normal((3, K)) + 0.4).astype(np.float32)
+    gamma, beta = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32), (0.05 * rng.standard_normal(K)).astype(np.float32)
+    w1, b1 = (rng.standard_normal((H1, K)) / np.sqrt(K)).astype(np.float32), (0.05 * rng.standard_normal(H1)).astype(np.float32)
+    w2, b2 = (rng.standard_normal((n_out, H1)) / np.sqrt(H1)).astype(np.float32), (0.05 * rng.standard_normal(n_out)).astype(np.float32)
+    flat = gpu_cls(p, gamma, beta, w1, b1, w2, b2)
+    assert np.isfinite(flat).all()
+    assert np.array_equal(gpu_cls(p, gamma, beta, w1, b1, w2, b2, ldp=K + 8).view(np.uint32), flat.view(np.uint32))
 
 
 # ------------------------------------------------------------------------------- engine.FusionHead

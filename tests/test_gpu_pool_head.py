@@ -60,16 +60,26 @@ def ref32_head(p, sd):
 
 
 # ------------------------------------------------------------------------------- kernel launches
-def gpu_asp_pool(x, hlin, a, lengths):
+def _dev_rows(v, ld=None):
+    """fp32 rows on the device at row pitch ``ld`` (default: contiguous); the padding columns hold NaN"""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    if ld is None or v.ndim < 2:
+        return torch.from_numpy(v).to(DEV)
+    t = torch.full((v.shape[0], ld), float("nan"), dtype=torch.float32, device=DEV)
+    t[:, : v.shape[1]] = torch.from_numpy(v).to(DEV)
+    return t
+
+
+def gpu_asp_pool(x, hlin, a, lengths, ldx=None, ldh=None):
     from interspeech_ser_amd import _lib
     offs = _offs(lengths)
     rows, D, B = offs[-1], x.shape[1], len(lengths)
-    xd, hd, ad = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(DEV) for v in (x, hlin, a.reshape(-1)))
+    xd, hd, ad = _dev_rows(x, ldx), _dev_rows(hlin, ldh), _dev_rows(a.reshape(-1))
     od = torch.tensor(offs, dtype=torch.int32, device=DEV)
     scores = torch.empty(rows, dtype=torch.float32, device=DEV)
     out = torch.full((B, 2 * D), float("nan"), dtype=torch.float32, device=DEV)
     p = _lib.AspPoolArgs()
-    p.x, p.ldx, p.hlin, p.ldh, p.a = xd.data_ptr(), D, hd.data_ptr(), D, ad.data_ptr()
+    p.x, p.ldx, p.hlin, p.ldh, p.a = xd.data_ptr(), ldx or D, hd.data_ptr(), ldh or D, ad.data_ptr()
     p.frame_offs, p.scores, p.out, p.ldo = od.data_ptr(), scores.data_ptr(), out.data_ptr(), 2 * D
     p.B, p.D, p.rows, p.max_frames = B, D, rows, max(lengths)
     _lib.check(_lib.lib.ser_asp_pool_v(ctypes.byref(p), torch.cuda.current_stream().cuda_stream), "ser_asp_pool_v")
@@ -77,16 +87,16 @@ def gpu_asp_pool(x, hlin, a, lengths):
     return out.cpu().numpy()
 
 
-def gpu_mlp_head(p, sd):
+def gpu_mlp_head(p, sd, ldp=None):
     from interspeech_ser_amd import _lib
     t = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(DEV) for k, v in sd.items()}
-    pd = torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)).to(DEV)
-    B, K = pd.shape
+    pd = _dev_rows(p, ldp)
+    B, K = p.shape
     H, n_out = t["fc.0.0.weight"].shape[0], t["out.0.weight"].shape[0]
     hidden = torch.empty((B, H), dtype=torch.float32, device=DEV)
     out = torch.full((B, n_out), float("nan"), dtype=torch.float32, device=DEV)
     h = _lib.MlpHeadArgs()
-    h.p, h.ldp, h.W1, h.b1 = pd.data_ptr(), K, t["fc.0.0.weight"].data_ptr(), t["fc.0.0.bias"].data_ptr()
+    h.p, h.ldp, h.W1, h.b1 = pd.data_ptr(), ldp or K, t["fc.0.0.weight"].data_ptr(), t["fc.0.0.bias"].data_ptr()
     h.gamma, h.beta, h.W2, h.b2 = t["fc.0.1.weight"].data_ptr(), t["fc.0.1.bias"].data_ptr(), t["out.0.weight"].data_ptr(), t["out.0.bias"].data_ptr()
     h.hidden, h.out, h.eps, h.B, h.K, h.H, h.n_out = hidden.data_ptr(), out.data_ptr(), 1e-5, B, K, H, n_out
     _lib.check(_lib.lib.ser_mlp_head_v(ctypes.byref(h), torch.cuda.current_stream().cuda_stream), "ser_mlp_head_v")
@@ -151,6 +161,17 @@ def _check_asp_pool(D, lengths, case):
         assert np.array_equal(one[0].view(np.uint32), got[i].view(np.uint32)), (i, n)
 
 
+def test_asp_pool_padded_rows_are_bit_equal(built_library):
+    """row pitches beyond D (ldx = D + 4, ldh = D + 8): the same bits as contiguous rows.  D = 68: a last slab with one live quad; 17
+    frames: two frames in row group 0; one frame: mu = x"""
+    D, lengths = 68, (1, 17)
+    x, hlin, a = _pool_inputs(D, lengths, "plain")
+    flat = gpu_asp_pool(x, hlin, a, lengths)
+    padded = gpu_asp_pool(x, hlin, a, lengths, ldx=D + 4, ldh=D + 8)
+    assert np.isfinite(flat).all() and np.array_equal(flat[0, :D], x[0])
+    assert np.array_equal(padded.view(np.uint32), flat.view(np.uint32))
+
+
 # ------------------------------------------------------------------------------- ser_mlp_head_v alone
 @pytest.mark.parametrize("n_out", [8, 3])
 @pytest.mark.parametrize("K,H", [(128, 96), (384, 64)])
@@ -178,6 +199,18 @@ def _check_mlp_head(K, H, n_out):
     assert err <= 4.0 * e_ref32
     for i in range(p.shape[0]):
         assert np.array_equal(gpu_mlp_head(p[i: i + 1], sd)[0].view(np.uint32), got[i].view(np.uint32))
+
+
+def test_mlp_head_padded_rows_are_bit_equal(built_library):
+    """input pitch beyond K (ldp = K + 8): the same bits as contiguous rows.  K = 384: two chunks a lane, the second partly dead"""
+    from interspeech_ser_amd.baseline import synthetic_head_state_dicts
+    K, H, n_out = 384, 64, 3
+    _, sd = synthetic_head_state_dicts(K // 2, H, n_out, seed=K + n_out)
+    sd = {k: v.numpy() for k, v in sd.items()}
+    p = np.random.default_rng(K * H + n_out).standard_normal((3, K)).astype(np.float32)
+    flat = gpu_mlp_head(p, sd)
+    assert np.isfinite(flat).all()
+    assert np.array_equal(gpu_mlp_head(p, sd, ldp=K + 8).view(np.uint32), flat.view(np.uint32))
 
 
 # ------------------------------------------------------------------------------- PoolHead behind an encoder
