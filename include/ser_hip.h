@@ -323,6 +323,25 @@ int ser_deberta_attention(const void* qkv, int64_t ld, int64_t plane_stride, int
 int ser_mean4(const float* s0, const float* s1, const float* s2, const float* s3, float* out,
               int64_t n, void* stream);
 
+/* ser_select_rows_v: the device heads' ragged gather.  Utterance b's row t (t < dst_offs[b + 1] - dst_offs[b]) is read from source row
+ * src_offs[b] + t and written to packed row dst_offs[b] + t: as the GEMM operand copy out_act (SER_MODE_BF16 / FP32X / FP16X; the planes
+ * ser_pack_rows_flagged stores for the same fp32 values) and / or unsplit as out_f32 -- at least one of the two.  n_src == 1: the value of
+ * src[0]; n_src == 4: (((s0 + s1) + s2) + s3) / 4, ser_mean4's order.  The sources are fp32 row matrices of one pitch ld_src (>= D, a
+ * multiple of 4), 16-byte aligned; src_offs [B] in any order, dst_offs [B + 1] ascending from 0 with at least one row per utterance (int32,
+ * device); max_rows = the longest count (it sizes the grid: SER_SELECT_ROWS_TILE rows per block, one grid row per utterance, B <= 65535).
+ * In FP16X, range_flag (may be NULL) gets the fp16 range guard's bits over the SELECTED rows only: a source row no utterance selects
+ * is never read.  The caller guarantees that every selected row lies inside the sources.  Additive export of ABI 18. */
+#define SER_SELECT_ROWS_TILE 8
+typedef struct ser_select_rows_args {
+    const float* src[4]; int64_t ld_src;
+    const int32_t* src_offs; const int32_t* dst_offs;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    float* out_f32; int64_t ldo_f32;
+    uint32_t* range_flag;
+    int32_t n_src, B, D, max_rows, mode, reserved0;
+} ser_select_rows_args;
+int ser_select_rows_v(const ser_select_rows_args* args, void* stream);
+
 /* weights: fp32 -> bf16 hi (+ lo) planes, done once at load. */
 int ser_split_bf16(const float* x, void* out, int64_t plane_stride, int mode, int64_t n, void* stream);
 

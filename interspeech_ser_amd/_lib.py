@@ -28,6 +28,7 @@ WS_WAVE_FRAMES = 2
 WS_GN_STATS = 3
 GRU_ERR_TIMEOUT = 1             # SER_GRU_ERR_TIMEOUT: a cluster wait of ser_gru_v gave up
 RESAMPLE_TILE = 1024            # SER_RESAMPLE_TILE: output samples per block of ser_resample_v
+SELECT_ROWS_TILE = 8            # SER_SELECT_ROWS_TILE: rows per block tile of ser_select_rows_v
 ABI_VERSION = 18
 
 c_void_p, c_int, c_i64, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -233,6 +234,16 @@ class FusionClsArgs(C.Structure):
     ]
 
 
+class SelectRowsArgs(C.Structure):
+    """Mirror of ``ser_select_rows_args``."""
+    _fields_ = [
+        ("src", c_void_p * 4), ("ld_src", c_i64), ("src_offs", c_void_p), ("dst_offs", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("out_f32", c_void_p), ("ldo_f32", c_i64),
+        ("range_flag", c_void_p),
+        ("n_src", C.c_int32), ("B", C.c_int32), ("D", C.c_int32), ("max_rows", C.c_int32), ("mode", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
@@ -249,7 +260,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
                   "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_xattn_mh_args": XattnMhArgs, "ser_attn_pool_args": AttnPoolArgs,
-                  "ser_fusion_cls_args": FusionClsArgs, "ser_cmd": Cmd}
+                  "ser_fusion_cls_args": FusionClsArgs, "ser_select_rows_args": SelectRowsArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -278,6 +289,7 @@ _SIGNATURES = {
     "ser_xattn_mh_v": (c_int, [c_void_p, c_void_p]),
     "ser_attn_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_fusion_cls_v": (c_int, [c_void_p, c_void_p]),
+    "ser_select_rows_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -740,6 +740,77 @@ extern "C" int ser_mean4(const float* s0, const float* s1, const float* s2, cons
     return ser_check_launch("ser_mean4");
 }
 
+// ------------------------------------------------------------------------------ row selection (the device heads' ragged gather)
+// Utterance b's row t = source row src_offs[b] + t (one matrix, or the K15 mean of four in mean4_kernel's order) -> packed row dst_offs[b] + t,
+// as the operand copy (store_act4) and / or as fp32.  Block = (tile of SER_SELECT_ROWS_TILE rows, utterance): no search; a tile behind its
+// utterance's count leaves.  One thread per 4 columns and step, 16-byte loads; the fp16 range guard sees the selected rows only.
+template <int MODE, int NSRC>
+__global__ __launch_bounds__(256) void select_rows_kernel(const float* __restrict__ s0, const float* __restrict__ s1,
+                                                          const float* __restrict__ s2, const float* __restrict__ s3, int64_t lds,
+                                                          const int32_t* __restrict__ src_offs, const int32_t* __restrict__ dst_offs,
+                                                          unsigned short* __restrict__ oa, int64_t ldoa, int64_t plane,
+                                                          float* __restrict__ of, int64_t ldof, int D, uint32_t* __restrict__ rflag) {
+    const int b = blockIdx.y;
+    const int d0 = dst_offs[b];
+    const int count = dst_offs[b + 1] - d0;
+    const int t0 = blockIdx.x * SER_SELECT_ROWS_TILE;
+    if (t0 >= count) return;
+    const int rows = min(SER_SELECT_ROWS_TILE, count - t0);
+    const int D4 = D / 4;
+    const int64_t srow0 = (int64_t)src_offs[b] + t0, drow0 = (int64_t)d0 + t0;
+    float amax = 0.f;
+    for (int i = threadIdx.x; i < rows * D4; i += 256) {
+        const int r = i / D4, c4 = (i - r * D4) * 4;
+        const int64_t so = (srow0 + r) * lds + c4;
+        f32x4 v = *(const f32x4*)(s0 + so);
+        if constexpr (NSRC == 4) {
+            const f32x4 b1 = *(const f32x4*)(s1 + so), c1 = *(const f32x4*)(s2 + so), d1 = *(const f32x4*)(s3 + so);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (((v[j] + b1[j]) + c1[j]) + d1[j]) / 4.0f;
+        }
+        if (of) *(f32x4*)(of + (drow0 + r) * ldof + c4) = v;
+        if (oa) store_act4<MODE>(oa + (drow0 + r) * ldoa + c4, plane, v[0], v[1], v[2], v[3]);
+        if constexpr (mode_traits<MODE>::f16) amax = range_fold(range_fold(range_fold(range_fold(amax, v[0]), v[1]), v[2]), v[3]);
+    }
+    if constexpr (mode_traits<MODE>::f16) range_report(rflag, amax);
+}
+
+template <int MODE>
+static void select_rows_launch(const ser_select_rows_args* a, void* stream) {
+    dim3 grid((unsigned)((a->max_rows + SER_SELECT_ROWS_TILE - 1) / SER_SELECT_ROWS_TILE), (unsigned)a->B), block(256);
+    if (a->n_src == 4)
+        hipLaunchKernelGGL((select_rows_kernel<MODE, 4>), grid, block, 0, (hipStream_t)stream, a->src[0], a->src[1], a->src[2], a->src[3],
+                           a->ld_src, a->src_offs, a->dst_offs, (unsigned short*)a->out_act, a->ldo_act, a->out_plane_stride, a->out_f32,
+                           a->ldo_f32, a->D, a->range_flag);
+    else
+        hipLaunchKernelGGL((select_rows_kernel<MODE, 1>), grid, block, 0, (hipStream_t)stream, a->src[0], nullptr, nullptr, nullptr,
+                           a->ld_src, a->src_offs, a->dst_offs, (unsigned short*)a->out_act, a->ldo_act, a->out_plane_stride, a->out_f32,
+                           a->ldo_f32, a->D, a->range_flag);
+}
+
+extern "C" int ser_select_rows_v(const ser_select_rows_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_select_rows: null arguments");
+    if (a->n_src != 1 && a->n_src != 4) return ser_fail(-2, "ser_select_rows: n_src=%d (one matrix, or four for their mean)", a->n_src);
+    for (int i = 0; i < a->n_src; ++i)
+        if (!a->src[i] || ((uintptr_t)a->src[i] & 15)) return ser_fail(-1, "ser_select_rows: source %d is null or not 16-byte aligned", i);
+    if (!a->src_offs || !a->dst_offs) return ser_fail(-1, "ser_select_rows: null row offsets");
+    if (!a->out_act && !a->out_f32) return ser_fail(-3, "ser_select_rows: no output");
+    if (a->B <= 0 || a->B > 65535) return ser_fail(-4, "ser_select_rows: B=%d (1..65535: one grid row per utterance)", a->B);
+    if (a->D <= 0 || (a->D % 4)) return ser_fail(-5, "ser_select_rows: D=%d must be a positive multiple of 4", a->D);
+    if (a->ld_src < a->D || (a->ld_src % 4)) return ser_fail(-6, "ser_select_rows: ld_src=%lld (>= D, multiple of 4)", (long long)a->ld_src);
+    if (a->out_act && (a->ldo_act < a->D || (a->ldo_act % 4) || (a->out_plane_stride % 4) || ((uintptr_t)a->out_act & 7)))
+        return ser_fail(-6, "ser_select_rows: ldo_act=%lld / out_plane_stride=%lld (>= D, multiples of 4, 8-byte aligned)",
+                        (long long)a->ldo_act, (long long)a->out_plane_stride);
+    if (a->out_f32 && (a->ldo_f32 < a->D || (a->ldo_f32 % 4) || ((uintptr_t)a->out_f32 & 15)))
+        return ser_fail(-6, "ser_select_rows: ldo_f32=%lld (>= D, multiple of 4, 16-byte aligned)", (long long)a->ldo_f32);
+    if (a->max_rows <= 0) return ser_fail(-7, "ser_select_rows: max_rows=%d", a->max_rows);
+    if (a->mode == SER_MODE_FP32X) select_rows_launch<SER_MODE_FP32X>(a, stream);
+    else if (a->mode == SER_MODE_BF16) select_rows_launch<SER_MODE_BF16>(a, stream);
+    else if (a->mode == SER_MODE_FP16X) select_rows_launch<SER_MODE_FP16X>(a, stream);
+    else return ser_fail(-8, "ser_select_rows: bad mode %d", a->mode);
+    return ser_check_launch("ser_select_rows_v");
+}
+
 // ------------------------------------------------------------------- weights / packing
 __global__ void split_kernel(const float* __restrict__ x, unsigned short* __restrict__ o, int64_t plane, int mode,
                              int64_t n) {

@@ -1935,6 +1935,34 @@ TRIMODAL_KEYS = _fusion_keys(("speech", "text", "prosody"))
 FUSION_BATCH = 16                                                 # utterances per MFMA column group of ser_gru_v
 
 
+class RowSource:
+    """Rows a device head reads where they lie, in place of a packed ``[M, D]`` tensor: utterance b's row t is row ``src_offs[b] + t`` of
+    ``states`` -- one fp32 ``[rows, D]`` device view, or four of equal pitch for the mean of the four (``mean_last4``'s value, no buffer of
+    its own).  The counts are the head's packed offsets; ``src_offs`` need not ascend, and rows no utterance selects (a Whisper window
+    behind its crop) are never read."""
+
+    def __init__(self, states, src_offs: Sequence[int]):
+        self.states = [states] if isinstance(states, torch.Tensor) else list(states)
+        self.src_offs = [int(v) for v in src_offs]
+
+    def check(self, what: str, offs: Sequence[int], D: int, device) -> None:
+        st = self.states
+        if len(st) not in (1, 4):
+            raise ValueError(f"{what} rows: a RowSource holds one state, or four for their mean, got {len(st)}")
+        for x in st:
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != D or x.stride(1) != 1 \
+                    or x.stride(0) % 4 or x.stride(0) < D or x.data_ptr() % 16 or x.device != device:
+                raise ValueError(f"{what} rows must be fp32 [rows, {D}] views on {device} (16-byte aligned, row pitch a multiple of 4)")
+        if any(x.stride(0) != st[0].stride(0) for x in st):
+            raise ValueError(f"{what} rows: the four states of a mean must share one row pitch")
+        B, rows = len(offs) - 1, min(int(x.shape[0]) for x in st)
+        if len(self.src_offs) != B:
+            raise ValueError(f"{what} rows: {len(self.src_offs)} source offsets for {B} utterances")
+        for b, s0 in enumerate(self.src_offs):
+            if s0 < 0 or s0 + (offs[b + 1] - offs[b]) > rows:
+                raise ValueError(f"{what} rows: utterance {b} selects rows {s0} .. {s0 + offs[b + 1] - offs[b] - 1} of a {rows}-row source")
+
+
 class _FusionBase(_HeadBase):
     """The reference's fusion heads over the modalities ``NAMES`` (the prefixes of their state-dict keys), on packed ragged batches, EVERY
     UTTERANCE ALONE.  Everything of one ``forward`` goes on the current stream, in order: a ser_gru_v cluster makes progress only while all
@@ -1943,7 +1971,8 @@ class _FusionBase(_HeadBase):
     then one q GEMM per attention module (queries: the module's own modality), one k | v GEMM per modality (its GRU output under the k | v
     rows of every OTHER module's in_proj_weight, stacked), one cross-attention and one out-projection per (module, other modality) -- a
     module's second out-projection adds its first through ser_gemm's residual epilogue --, one ser_attn_pool_v per modality and
-    ser_fusion_cls_v on the [B, n E] row."""
+    ser_fusion_cls_v on the [B, n E] row.  A modality handed in as a ``RowSource`` replaces its ser_pack_rows_flagged by one ser_select_rows_v
+    into the same operand copy (same range-guard word, same place in the order); everything behind it is untouched."""
     NAMES: tuple = ()
     KEYS: Dict[str, tuple] = {}
     WHAT = "fusion head"
@@ -2031,7 +2060,8 @@ class _FusionBase(_HeadBase):
         side = []
         for M, D in zip(Ms, self.dims_in):
             sb = dict(xa=act(M, D), proj=f(M, h), sa=act(M, h), gx=f(M, 6 * h), gh=f(M, E), gha=act(M, E), q=f(M, E), kv=f(M, 2 * E * (n - 1)),
-                      ctx=[act(M, E) for _ in range(n - 1)], att=f(M, E), scores=f(M), offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
+                      ctx=[act(M, E) for _ in range(n - 1)], att=f(M, E), scores=f(M), offs=torch.empty(B + 1, dtype=torch.int32, device=dev),
+                      src=torch.empty(B, dtype=torch.int32, device=dev))
             if n > 2:
                 sb["att_first"] = f(M, E)                         # the first out-projection of a module with two key sides (distinct from `att`)
             side.append(sb)
@@ -2061,6 +2091,9 @@ class _FusionBase(_HeadBase):
         for i, (x, D, what) in enumerate(zip(xs, self.dims_in, names)):
             if offs[i][0] != 0 or any(b <= a for a, b in zip(offs[i][:-1], offs[i][1:])):
                 raise ValueError(f"an empty {what} utterance (or offsets that do not ascend from 0): every utterance needs at least one row")
+            if isinstance(x, RowSource):
+                x.check(what, offs[i], D, self.device)
+                continue
             if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != D or x.shape[0] < Ms[i] or x.stride(1) != 1 or x.stride(0) % 4 \
                     or x.data_ptr() % 16 or x.device != self.device:
                 raise ValueError(f"{what} rows must be an fp32 [>= {Ms[i]}, {D}] tensor on {self.device} (16-byte aligned, row pitch a multiple of 4)")
@@ -2075,11 +2108,21 @@ class _FusionBase(_HeadBase):
         for i in range(n):
             sb, w, x, M = bf["side"][i], self.mod[i], xs[i], Ms[i]
             sb["offs"][: B + 1].copy_(torch.tensor(offs[i], dtype=torch.int32))
-            D = x.shape[1]
+            D = self.dims_in[i]
             xa, sa = sb["xa"].first_rows(M), sb["sa"].first_rows(M)
             tag = names[i]
-            self._step(f"{tag} pack", lambda: check(lib.ser_pack_rows_flagged(x.data_ptr(), x.stride(0), 1, M, D, 0, xa.ptr, D, xa.plane_stride, om,
-                                                                             flag, st), "ser_pack_rows_flagged"))
+            if isinstance(x, RowSource):                          # the utterances' rows where they lie: one ragged gather into the same operand copy
+                sb["src"][:B].copy_(torch.tensor(x.src_offs, dtype=torch.int32))
+                g = _lib.SelectRowsArgs()
+                for k, s_ in enumerate(x.states):
+                    g.src[k] = s_.data_ptr()
+                g.ld_src, g.src_offs, g.dst_offs = x.states[0].stride(0), sb["src"].data_ptr(), sb["offs"].data_ptr()
+                g.out_act, g.ldo_act, g.out_plane_stride, g.range_flag = xa.ptr, D, xa.plane_stride, flag
+                g.n_src, g.B, g.D, g.max_rows, g.mode = len(x.states), B, D, maxf[i], om
+                self._step(f"{tag} pack", lambda: check(lib.ser_select_rows_v(C.byref(g), st), "ser_select_rows_v"))
+            else:
+                self._step(f"{tag} pack", lambda: check(lib.ser_pack_rows_flagged(x.data_ptr(), x.stride(0), 1, M, D, 0, xa.ptr, D, xa.plane_stride, om,
+                                                                                 flag, st), "ser_pack_rows_flagged"))
             self._step(f"{tag} projection", lambda: host._gemm(xa, w["proj"], M, out_f32=sb["proj"], ldo_f32=h, mode=om))
             self._step(f"{tag} layernorm", lambda: host._layernorm(sb["proj"], h, w["ln"], M, h, out_act=sa, eps=1e-5))
             self._step(f"{tag} gx", lambda: host._gemm(sa, w["wih"], M, out_f32=sb["gx"], ldo_f32=6 * h, mode=om))
@@ -2188,7 +2231,7 @@ class TrimodalHead(_FusionBase):
                 slot: int = 0, range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``); ``x3`` may be
         ``[M3, D3, 1]`` (the reference squeezes the third stream's last axis)."""
-        if x3.dim() == 3 and x3.shape[-1] == 1:
+        if isinstance(x3, torch.Tensor) and x3.dim() == 3 and x3.shape[-1] == 1:
             x3 = x3.squeeze(-1)
         return self._forward((x1, x2, x3), (offs1, offs2, offs3), slot, range_flag)
 

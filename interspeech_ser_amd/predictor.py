@@ -1,0 +1,399 @@
+"""Waveforms (+ transcripts, + a third stream's rows) -> the fusion heads' logits on one device, behind any of the encoders.
+
+``bimodal.BimodalPredictor`` runs one speech encoder and one text encoder in front of ``engine.FusionHead``.  The reference's strongest
+systems sit behind Whisper (``whisperlarge_roberta_1head``, ``whisperlarge_deberta_lasthidden_head1``), behind two audio encoders and no
+text at all (``whisperlarge_hubertxlarge_head1``), or behind three streams.  ``FusionPredictor`` takes two or three streams of any kind:
+every encoder's forward runs on the current stream, and the head reads each stream's rows WHERE THEY LIE (``engine.RowSource``, one
+ser_select_rows_v launch per stream): of a Whisper window only the ``min(ceil(len / 320), D)`` rows the reference keeps
+(preprocess_whisper.py:49-50,75-76), the mean of the last four states without a buffer of its own.  Only ``[B, n_out]`` floats come back.
+``score_from_wav`` is the test-set scoring of ``head.score`` from wav files and a transcript table, with no feature file in between
+(bin/predict_cat_from_wav.py).  One GPU, 16 kHz input."""
+from __future__ import annotations
+
+import csv
+import ctypes as C_
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import config as C
+from ._lib import SelectRowsArgs, SerHipError, check, lib
+from .engine import FusionHead, RowSource, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
+from .frontend import whisper_saved_rows
+
+
+class AudioStream:
+    """A speech encoder (WavLM / wav2vec2 / HuBERT / data2vec-audio) or Whisper over the batch's waveforms: ``hidden_states[state]``
+    (negative ``state`` as Python indexes), or with ``average`` the mean of the last four states."""
+
+    def __init__(self, enc, state: int = -1, average: bool = False):
+        self.enc, self.state, self.average = enc, int(state), bool(average)
+
+
+class TextStream:
+    """A text encoder (RoBERTa / DeBERTa) over the batch's tokens: the last state -- all ``max_len`` rows, as the text driver writes them --
+    or with ``average`` the mean of the last four."""
+
+    def __init__(self, enc, average: bool = False):
+        self.enc, self.average = enc, bool(average)
+
+
+class RowsStream:
+    """``[T, dim]`` rows per utterance handed in by the caller (the third stream's files: its extractor is not part of this library)."""
+
+    def __init__(self, dim: int):
+        self.dim = int(dim)
+
+
+def gather_rows(src: RowSource, offs: Sequence[int]) -> torch.Tensor:
+    """The rows a head reads through ``src`` with packed offsets ``offs``, as one fp32 ``[offs[-1], D]`` device tensor (ser_select_rows_v's
+    fp32 output): what the extraction drivers would have written to the utterances' files."""
+    offs = [int(v) for v in offs]
+    B, D = len(offs) - 1, int(src.states[0].shape[1])
+    dev = src.states[0].device
+    src.check("gathered", offs, D, dev)
+    out = torch.empty((offs[-1], D), dtype=torch.float32, device=dev)
+    so, do = torch.tensor(src.src_offs, dtype=torch.int32, device=dev), torch.tensor(offs, dtype=torch.int32, device=dev)
+    g = SelectRowsArgs()
+    for k, s in enumerate(src.states):
+        g.src[k] = s.data_ptr()
+    g.ld_src, g.src_offs, g.dst_offs, g.out_f32, g.ldo_f32 = src.states[0].stride(0), so.data_ptr(), do.data_ptr(), out.data_ptr(), D
+    g.n_src, g.B, g.D, g.max_rows, g.mode = len(src.states), B, D, max(b - a for a, b in zip(offs[:-1], offs[1:])), 1
+    check(lib.ser_select_rows_v(C_.byref(g), _stream()), "ser_select_rows_v")
+    return out
+
+
+class FusionPredictor:
+    """``streams``: two (``engine.FusionHead``) or three (``engine.TrimodalHead``, ``heads`` = (1, 1, 2) unless given) of ``AudioStream`` /
+    ``TextStream`` / ``RowsStream``, in the order of the head's modalities; ``head_sd``: the head's state dict; ``head_mode``: its numerics
+    (default: the first encoder's ``mode_name``).  All encoders and the head live on one device.  Constructor errors are
+    ``BimodalPredictor``'s: ``IndexError("tuple index out of range")`` for a state outside the tuple, ``ValueError`` for a mean over fewer
+    than four states or a stream width the state dict contradicts."""
+
+    def __init__(self, streams, head_sd, head_mode: Optional[str] = None, heads: Optional[Sequence[int]] = None):
+        streams = list(streams)
+        if len(streams) not in (2, 3):
+            raise ValueError(f"FusionPredictor runs two streams (engine.FusionHead) or three (engine.TrimodalHead), got {len(streams)}")
+        encs = [s.enc for s in streams if not isinstance(s, RowsStream)]
+        if not encs:
+            raise ValueError("FusionPredictor needs at least one encoder stream (rows alone go to the head directly)")
+        if len(set(map(id, encs))) != len(encs):
+            raise ValueError("one encoder object cannot serve two streams (its second forward would overwrite the first one's states)")
+        dims = []
+        for i, s in enumerate(streams):
+            if isinstance(s, RowsStream):
+                dims.append(s.dim)
+                continue
+            if isinstance(s, AudioStream):
+                if not isinstance(s.enc, (SpeechEncoder, WhisperEncoder)):
+                    raise ValueError(f"stream {i + 1}: an AudioStream needs a speech encoder or Whisper")
+            elif isinstance(s, TextStream):
+                if not isinstance(s.enc, _TextEncoderBase):
+                    raise ValueError(f"stream {i + 1}: a TextStream needs a text encoder (RoBERTa / DeBERTa)")
+            else:
+                raise ValueError(f"stream {i + 1}: expected an AudioStream, a TextStream or a RowsStream")
+            if s.enc.device != encs[0].device:
+                raise ValueError(f"all encoders must live on one device, got {encs[0].device} and {s.enc.device}")
+            L = s.enc.geo.num_layers
+            if s.average:
+                if L + 1 < 4:
+                    raise ValueError(f"average takes the mean of the last four hidden states; stream {i + 1}'s encoder has only {L + 1}")
+            elif isinstance(s, AudioStream):
+                idx = s.state if s.state >= 0 else L + 1 + s.state
+                if not 0 <= idx <= L:
+                    raise IndexError("tuple index out of range")           # what hidden_states[N] raises in the reference
+                s.index = idx
+            dims.append(s.enc.geo.hidden)
+        self.streams, self.device = streams, encs[0].device
+        mode = head_mode or encs[0].mode_name                              # the first stream's (the first encoder's, behind a RowsStream)
+        if len(streams) == 3:
+            self.head = TrimodalHead(head_sd, *dims, self.device, mode, heads=tuple(heads) if heads is not None else (1, 1, 2))
+        else:
+            if heads is not None and tuple(heads) != (1, 1):
+                raise ValueError("the bimodal head's two attention modules have one head each")
+            self.head = FusionHead(head_sd, *dims, self.device, mode)
+        self.n_out = self.head.n_out
+
+    @staticmethod
+    def _source(s, hs, counts):
+        """the stream's rows inside its forward's states, ``counts[b]`` of them from each utterance's first row"""
+        if s.average:
+            if hs.computed < hs.states.shape[0]:
+                raise IndexError("mean of the last four states needs the full forward")
+            states = [hs.states[k] for k in (-4, -3, -2, -1)]
+        else:
+            states = [hs.states[s.index if isinstance(s, AudioStream) else -1]]
+        return RowSource(states, hs.frame_offs[:-1]), [0] + [int(v) for v in np.cumsum(counts)], hs
+
+    def features(self, waves: Optional[Sequence[np.ndarray]] = None, input_ids: Optional[torch.Tensor] = None,
+                 attention_mask: Optional[torch.Tensor] = None, rows=None) -> List[tuple]:
+        """Per stream ``(rows, packed offsets, the forward's HiddenStates)``: the rows are an ``engine.RowSource`` over the encoder's
+        states (nothing copied; valid until that encoder's next forward), or for a ``RowsStream`` the caller's rows packed on the device
+        (and None for the HiddenStates).  The forwards run on the current stream in the order of the streams."""
+        B = None
+        if any(isinstance(s, AudioStream) for s in self.streams):
+            if waves is None:
+                raise ValueError("an AudioStream needs waves")
+            waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
+            B = len(waves)
+        if any(isinstance(s, TextStream) for s in self.streams):
+            if input_ids is None or attention_mask is None:
+                raise ValueError("a TextStream needs input_ids and attention_mask")
+            if B is not None and input_ids.shape[0] != B:
+                raise ValueError(f"{B} waveforms but {input_ids.shape[0]} token rows")
+            B = int(input_ids.shape[0])
+        if any(isinstance(s, RowsStream) for s in self.streams):
+            if rows is None:
+                raise ValueError("a RowsStream needs rows: one [T, D] matrix per utterance")
+            if len(rows) != B:
+                raise ValueError(f"{len(rows)} row matrices for {B} utterances")
+        out = []
+        for s in self.streams:
+            if isinstance(s, AudioStream):
+                lengths = [len(w) for w in waves]
+                hs = s.enc.forward(s.enc.upload(waves), lengths, last_state=None if s.average else s.index)
+                if isinstance(s.enc, WhisperEncoder):                      # the rows the reference keeps of each 1 500-row window
+                    counts = [min(whisper_saved_rows(n, s.enc.geo.hidden), hs.frames(b)) for b, n in enumerate(lengths)]
+                else:
+                    counts = [hs.frames(b) for b in range(B)]
+                out.append(self._source(s, hs, counts))
+            elif isinstance(s, TextStream):
+                hs = s.enc.forward(input_ids, attention_mask)
+                out.append(self._source(s, hs, [hs.frames(b) for b in range(B)]))
+            else:
+                mats = []
+                for r in rows:
+                    r = torch.as_tensor(r)
+                    if r.dim() == 3 and r.shape[-1] == 1:
+                        r = r.squeeze(-1)                                  # the reference squeezes the third stream's last axis
+                    if r.dim() != 2 or r.shape[0] < 1 or r.shape[1] != s.dim:
+                        raise ValueError(f"rows must be [T >= 1, {s.dim}] matrices, got {tuple(r.shape)}")
+                    mats.append(r.float().contiguous())
+                out.append((torch.cat(mats).to(self.device), [0] + [int(v) for v in np.cumsum([m.shape[0] for m in mats])], None))
+        return out
+
+    def predict(self, waves: Optional[Sequence[np.ndarray]] = None, input_ids: Optional[torch.Tensor] = None,
+                attention_mask: Optional[torch.Tensor] = None, rows=None) -> np.ndarray:
+        """Raw 16 kHz mono waveforms (every audio stream reads the same ones), right-padded tokens ``[B, T2]`` and / or per-utterance rows
+        -> ``[B, n_out]`` float32 logits, every utterance alone.  Raises ``SerHipError`` when the fp16 range guard of a forward or of the
+        head is set, or when ser_gru_v gave a cluster wait up."""
+        feats = self.features(waves, input_ids, attention_mask, rows)
+        args = []
+        for x, offs, _ in feats:
+            args += [x, offs]
+        out = self.head.forward(*args).cpu().numpy().copy()
+        bits = 0
+        for _, _, hs in feats:
+            if hs is not None:
+                bits |= hs.take_range_bits()
+        hbits, err = self.head.status()
+        msg = FusionHead.failure(bits | hbits, err)
+        if msg is not None:
+            raise SerHipError(msg)
+        return out
+
+
+# ----------------------------------------------------------------------------------------------------- test-set scoring from wav files
+FILES = "files"           # --encoder3 files: the third stream is read from config["lazy_dir3"]
+
+
+def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[str]):
+    """(geometry or None for "files") per stream, checked against the config's feat{i}_dim -- before any weight is loaded"""
+    if len(encoders) not in (2, 3):
+        raise ValueError(f"two or three encoders, got {len(encoders)}")
+    geos = []
+    for i, name in enumerate(encoders):
+        want = int(config[f"feat{i + 1}_dim"])
+        if name == FILES:
+            if i != 2:
+                raise ValueError("only the third stream can be read from files (--encoder3 files)")
+            geos.append(None)
+            continue
+        geo = C.resolve_geometry(name, checkpoints[i])
+        if geo.hidden != want:
+            raise ValueError(f"feat{i + 1}_dim = {want} in the config, but {name} has hidden size {geo.hidden}")
+        geos.append(geo)
+    if all(g is None or g.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA) for g in geos):
+        raise ValueError("no audio encoder among the streams: this command scores wav files (head.score reads feature files)")
+    return geos
+
+
+def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Sequence[int]] = None, averages: Optional[Sequence[bool]] = None,
+                   checkpoints: Optional[Sequence[str]] = None, test_csv: Optional[str] = None, mode: str = "f16mf", text_mode: str = "f16x",
+                   head_mode: Optional[str] = None, batch_size: int = 16, num_workers: int = 4, tokenizer_path: str = "", max_len: int = 80,
+                   synthetic_weights: bool = False, seed: int = 7, device: Optional[str] = None, tokenize=None) -> Dict:
+    """``head.score(engine="hip")`` from the corpus itself: the ``FileName`` column of ``test_csv``, wavs from ``config["wav_dir"]``
+    (16 kHz), transcripts from the table ``config["txt_dir"]`` (columns FileName, transcription), the head's weights from
+    ``<model_path>/multimodal_ser.pt`` -> ``<model_path>/results/test.csv`` in ``head.score``'s format.  ``encoders``: two or three
+    encoder ids (``config.resolve_geometry``; the family decides the stream kind), the third may be "files" (rows from
+    ``config["lazy_dir3"]``).  ``layers[i]`` / ``averages[i]``: the state an audio stream hands on; a text stream hands on its last state
+    or the mean.  ``mode`` / ``text_mode`` / ``head_mode``: numerics of the audio encoders, the text encoders and the head (default: the
+    first encoder's).  ``tokenize``: texts -> (input_ids, attention_mask), default ``driver.hf_tokenize_fn``.  A file that cannot be
+    decoded, has no transcript or is empty is printed and gets no row; a batch whose range-guard or GRU error word is set is retried file
+    by file.  Returns {"csv", "n", "failed"}."""
+    from . import head as HD
+    from .driver import _Extractor, find_weights, hf_tokenize_fn
+    from .engine import build_encoder
+    from .frontend import load_wav_16k
+    n = len(encoders)
+    layers = list(layers) if layers is not None else [-1] * n
+    averages = list(averages) if averages is not None else [False] * n
+    checkpoints = list(checkpoints) if checkpoints is not None else [""] * n
+    geos = _stream_kinds(config, encoders, checkpoints)
+    if max_len > 512:
+        raise ValueError(f"max_len {max_len}: the text encoders have 512 positions (the reference uses 80)")
+    if not torch.cuda.is_available():
+        print(HD.NO_CPU_PATH)
+        return {"csv": None, "n": 0, "failed": 0}
+    import pandas as pd
+    HD.set_deterministic(seed)
+    dev = str(torch.device(device or "cuda:0"))
+    model_path = config["model_path"]
+    os.makedirs(model_path, exist_ok=True)
+    log = HD._logger(model_path)
+    names = pd.read_csv(test_csv or HD.TEST_CSV)["FileName"].tolist()
+    texts: Dict[str, str] = {}
+    streams = []
+    for i, (name, geo) in enumerate(zip(encoders, geos)):
+        if geo is None:
+            streams.append(RowsStream(int(config[f"feat{i + 1}_dim"])))
+            continue
+        text = geo.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA)
+        whisper = geo.family == C.FAMILY_WHISPER
+        sd, src = find_weights(name, checkpoints[i], synthetic_weights, seed, geo)
+        if text:
+            if tokenize is None:
+                tokenize = hf_tokenize_fn(tokenizer_path or name, max_len, geo.family)
+            if not texts:
+                df = pd.read_csv(config["txt_dir"])
+                texts = {str(f): str(t) for f, t in zip(df.FileName.values, df.transcription.values)}
+            enc = build_encoder(geo, sd, dev, text_mode)
+            streams.append(TextStream(enc, averages[i]))
+        else:
+            m = _Extractor.supported_mode(geo, mode, whisper, name)
+            enc = build_encoder(geo, sd, dev, m, normalize=True if whisper else C.resolve_do_normalize(name, checkpoints[i]))
+            streams.append(AudioStream(enc, layers[i], averages[i]))
+        print(f"Stream {i + 1}: {name} ({src}; numerics mode {enc.mode_name})")
+        del sd
+    head_sd = torch.load(os.path.join(model_path, "multimodal_ser.pt"), map_location="cpu", weights_only=True)
+    pred = FusionPredictor(streams, head_sd, head_mode)
+    has_text, has_rows = any(isinstance(s, TextStream) for s in streams), any(isinstance(s, RowsStream) for s in streams)
+    log.info("Starting scoring test samples...")
+    done, rows_out, failed = [], [], 0
+
+    def fail(name, err):
+        nonlocal failed
+        failed += 1
+        print(f"Failed to process {name}: {err}")
+
+    def load(name):
+        """(name, waveform, transcript, third stream's rows, error)"""
+        try:
+            wave = load_wav_16k(os.path.join(config["wav_dir"], name))
+            if len(wave) < 1:
+                raise ValueError("empty waveform")
+            text = None
+            if has_text:
+                if name not in texts:
+                    raise KeyError(f"no transcript in {config['txt_dir']}")
+                text = texts[name]
+            third = None
+            if has_rows:
+                third = torch.load(os.path.join(config["lazy_dir3"], name.replace(".wav", ".pt")), weights_only=True)
+                if third.dim() == 3 and third.shape[-1] == 1:
+                    third = third.squeeze(-1)                          # the reference squeezes the third stream's last axis
+                if third.dim() != 2 or third.shape[0] < 1:
+                    raise ValueError(f"feature files must hold [T >= 1, D] matrices, got {tuple(third.shape)}")
+            return name, wave, text, third, None
+        except Exception as e:                                          # noqa: BLE001  (per-file failure, as in the extraction drivers)
+            return name, None, None, None, e
+
+    def run(items):
+        """items: (index, name, waveform, transcript, rows) -> error message or None; appends the rows of a clean batch"""
+        ids = mask = None
+        if has_text:
+            ids, mask = tokenize([it[3] for it in items])
+        out = pred.predict([it[2] for it in items], ids, mask, [it[4] for it in items] if has_rows else None)
+        for it, row in zip(items, out):
+            done.append(it[1])
+            rows_out.append(row)
+        return None
+
+    bs = max(1, int(batch_size))
+    windows = [names[i:i + bs] for i in range(0, len(names), bs)]
+    with ThreadPoolExecutor(max_workers=max(1, int(num_workers))) as pool:
+        pending = pool.map(load, windows[0]) if windows else []
+        for wi, window in enumerate(windows):
+            loaded = list(pending)
+            if wi + 1 < len(windows):
+                pending = pool.map(load, windows[wi + 1])               # decode the next batch while the GPU works
+            items = []
+            for k, (name, wave, text, third, err) in enumerate(loaded):
+                if err is not None:
+                    fail(name, err)
+                else:
+                    items.append((wi * bs + k, name, wave, text, third))
+            if not items:
+                continue
+            try:
+                err = run(items)
+            except Exception as e:                                      # noqa: BLE001
+                err = e
+            if err is not None and len(items) > 1:                      # one bad file must not drop its neighbours
+                for it in items:
+                    try:
+                        e1 = run([it])
+                    except Exception as e:                              # noqa: BLE001
+                        e1 = e
+                    if e1 is not None:
+                        fail(it[1], e1)
+            elif err is not None:
+                fail(items[0][1], err)
+    os.makedirs(os.path.join(model_path, "results"), exist_ok=True)
+    csv_file = os.path.join(model_path, "results", "test.csv")
+    with open(csv_file, mode="w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["FileName", "Prediction"] + [f"class_{i}_prob" for i in range(len(HD.CLASSES))])
+        for row, utt in zip(rows_out, done):
+            w.writerow([utt, HD.CLASS_LETTERS[int(np.argmax(row))]] + [f"{p:.4f}" for p in np.asarray(row).flatten()])
+    print(f"{len(done)} rows written, {failed} files failed")
+    for h in list(log.handlers):
+        h.close()
+        log.removeHandler(h)
+    return {"csv": csv_file, "n": len(done), "failed": failed}
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    import argparse
+    import json
+    from . import head as HD
+    p = argparse.ArgumentParser(description="score a test set from wav files and transcripts: encoders and fusion head on one GPU")
+    p.add_argument("--seed", type=int, default=7)
+    p.add_argument("--config_path", type=str, default="./configs/config_cat.json")
+    for i in (1, 2, 3):
+        p.add_argument(f"--encoder{i}", type=str, default="" if i == 3 else None, required=i < 3,
+                       help="encoder id" + (' or "files" (rows from lazy_dir3); empty: two streams' if i == 3 else ""))
+        p.add_argument(f"--layer{i}", type=int, default=-1, help="audio stream: hidden_states[N]")
+        p.add_argument(f"--average{i}", action="store_true", help="the mean of the last four hidden states")
+        p.add_argument(f"--checkpoint{i}", type=str, default="")
+    p.add_argument("--test_csv", type=str, default=HD.TEST_CSV)
+    p.add_argument("--mode", type=str, default="f16mf", help="numerics of the audio encoders (the extraction drivers' --mode)")
+    p.add_argument("--text_mode", type=str, default="f16x", help="numerics of the text encoders")
+    p.add_argument("--head_mode", type=str, default=None, help="numerics of the head (default: the first encoder's)")
+    p.add_argument("--batch_size", type=int, default=16)
+    p.add_argument("--num_workers", type=int, default=4)
+    p.add_argument("--tokenizer_path", type=str, default="")
+    p.add_argument("--max_len", type=int, default=80)
+    p.add_argument("--synthetic_weights", action="store_true")
+    a = p.parse_args(argv)
+    with open(a.config_path, "r") as f:
+        config = json.load(f)
+    k = 3 if a.encoder3 else 2
+    pick = lambda what: [getattr(a, f"{what}{i}") for i in range(1, k + 1)]
+    score_from_wav(config, pick("encoder"), pick("layer"), pick("average"), pick("checkpoint"), test_csv=a.test_csv, mode=a.mode,
+                   text_mode=a.text_mode, head_mode=a.head_mode, batch_size=a.batch_size, num_workers=a.num_workers,
+                   tokenizer_path=a.tokenizer_path, max_len=a.max_len, synthetic_weights=a.synthetic_weights, seed=a.seed)
+    return 0
