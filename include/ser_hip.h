@@ -648,6 +648,73 @@ typedef struct ser_fusion_cls_args {
 } ser_fusion_cls_args;
 int ser_fusion_cls_v(const ser_fusion_cls_args* args, void* stream);
 
+/* a25 (added under ABI 18: new entry points, ser_cmd members and SER_OP codes only; nothing existing changed)  The Whisper decoder's step
+ * (HF modeling_whisper.py WhisperDecoder; the reference's transcripts: test/Whisper transcriptions.ipynb): the three kernels of a decode
+ * step that are neither a GEMM nor a LayerNorm.  All sequences of a batch stand at the same position, which lives in device memory
+ * (`pos`, int32 [1]): a step takes ids[:, pos] to ids[:, pos + 1] with no host decision and no pointer that changes between steps, so its
+ * launches are command-list ops and a recorded step is replayed as it is.  No atomics on float data; a sequence's result does not depend on
+ * the batch around it.
+ *
+ * ser_dec_embed_v: out[b] = embed_tokens[ids[b, *pos]] + embed_positions[*pos], fp32 rows (one exact fp32 add per element).  ids int32
+ * [B, ld_ids >= max_pos]; tables fp32 [vocab, D] / [max_pos, D], 16-byte aligned; D % 4 == 0.  An id or position outside its table reads
+ * the nearest valid row (never out of bounds; ser_dec_select_v is what reports a position that left the buffer). */
+typedef struct ser_dec_embed_args {
+    const int32_t* ids; int64_t ld_ids;
+    const int32_t* pos;
+    const float* embed_tokens; const float* embed_positions;
+    float* out; int64_t ldo;
+    int32_t B, D, vocab, max_pos;
+} ser_dec_embed_args;
+int ser_dec_embed_v(const ser_dec_embed_args* args, void* stream);
+
+/* ser_dec_attn_v: one query per (sequence, head) over the first len[b] rows of that sequence's K / V cache:
+ *   ctx[b, h] = sum_j softmax_j(scale q_h . K_h[j]) V_h[j],   j < len[b] = len_add + (lens ? lens[b * lens_stride] : 0), clamped to [1, max_len]
+ * q [B, ldq], the caches (row j of sequence b at cache + b * batch_stride + j * ldc) and all arithmetic are fp32; online softmax in base 2;
+ * head h is columns 64 h .. 64 h + 63 (dh == 64, the head dim of every Whisper size).  Rows at or beyond len[b] are never read.
+ *   self-attention:  lens = the position word, lens_stride = 0, len_add = 1; k_new / v_new [B, ld_new] = this step's k and v rows (columns of
+ *     the packed projection's fp32 output).  The block of (b, h) stores its own 64 columns of both at row len[b] - 1 -- the append -- and
+ *     reads them from k_new / v_new, not back from the cache; no other block touches those columns.
+ *   cross-attention: lens = NULL, len_add = the encoder's row count, k_new = v_new = NULL (nothing is appended).
+ * One block per (head, sequence): 16 groups of 16 lanes, group g takes keys g, g + 16, ..., a lane owns 4 columns (16-byte loads, K / V straight
+ * to registers); the 16 partial results are merged in ascending group order.  The order of every sum is a function of len[b] alone.
+ * out_act: ctx [B, ldo_act] as GEMM operand planes in `mode` (SER_MODE_BF16, FP32X or FP16X; FP16X reports into range_flag, may be NULL).
+ * q, k_new, v_new and the caches 16-byte aligned, pitches and batch_stride multiples of 4, batch_stride >= max_len * ldc when B > 1. */
+typedef struct ser_dec_attn_args {
+    const float* q; int64_t ldq;
+    const float* k_new; const float* v_new; int64_t ld_new;
+    float* kcache; float* vcache; int64_t ldc; int64_t batch_stride;
+    const int32_t* lens; int32_t lens_stride, len_add;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    uint32_t* range_flag;
+    float scale;
+    int32_t B, H, dh, max_len, mode;
+} ser_dec_attn_args;
+int ser_dec_attn_v(const ser_dec_attn_args* args, void* stream);
+
+/* ser_dec_select_v: the greedy choice of a step and its bookkeeping.  With p = *pos, per row b (one block per row, wave reductions):
+ *   finished[b]            -> token = pad
+ *   forced[p] >= 0         -> token = forced[p]                                    (logits are not read: the host may skip their launches)
+ *   else                   -> token = argmax_{v < V} (logits[b, v] + mask[phase[p], v]), the lowest index on a tie (torch.argmax)
+ * mask fp32 [3, ldm]: rows 0 steady, 1 first generated position, 2 language set (0 or -inf); columns >= V of logits (the padded
+ * vocabulary) are never read.  Writes ids[b, p + 1] = token, margin[b, p] = the top-1 minus top-2 masked logit (+inf where nothing was
+ * decided: forced or finished rows, or a single unmasked token); token == eos sets finished[b].  The block that finishes last stores the count
+ * of unfinished rows to *unfinished and advances *pos (integer tickets in `work`, int32 [2], zero before the first launch and left zero).
+ * *err (ORed): bit 0 = a winning masked logit was not finite (a NaN counts as the winner) -- the batch fails, as with the range guard,
+ * never a silent token; bit 2 = p + 1 >= max_pos (nothing is written).  ids int32 [B, ld_ids >= max_pos], margin [B, ld_margin >= max_pos - 1],
+ * phase / forced int32 [max_pos]. */
+typedef struct ser_dec_select_args {
+    const float* logits; int64_t ldl;
+    const float* mask; int64_t ldm;
+    const int32_t* phase; const int32_t* forced;
+    int32_t* ids; int64_t ld_ids;
+    int32_t* finished;
+    float* margin; int64_t ld_margin;
+    int32_t* pos; int32_t* unfinished; int32_t* work;
+    uint32_t* err;
+    int32_t B, V, eos, pad, max_pos, reserved0;
+} ser_dec_select_args;
+int ser_dec_select_v(const ser_dec_select_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -657,6 +724,9 @@ int ser_fusion_cls_v(const ser_fusion_cls_args* args, void* stream);
 #define SER_OP_PACK_ACT 7
 #define SER_OP_GN_STATS 8
 #define SER_OP_POS_LN 9
+#define SER_OP_DEC_EMBED 10
+#define SER_OP_DEC_ATTN 11
+#define SER_OP_DEC_SELECT 12
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -669,6 +739,9 @@ typedef struct ser_cmd {
         ser_pack_act_args    pack_act;
         ser_gn_stats_args    gn_stats;
         ser_pos_ln_args      pos_ln;
+        ser_dec_embed_args   dec_embed;
+        ser_dec_attn_args    dec_attn;
+        ser_dec_select_args  dec_select;
     } u;
 } ser_cmd;
 

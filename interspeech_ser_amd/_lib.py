@@ -244,10 +244,41 @@ class SelectRowsArgs(C.Structure):
     ]
 
 
+class DecEmbedArgs(C.Structure):
+    """Mirror of ``ser_dec_embed_args``."""
+    _fields_ = [("ids", c_void_p), ("ld_ids", c_i64), ("pos", c_void_p), ("embed_tokens", c_void_p), ("embed_positions", c_void_p),
+                ("out", c_void_p), ("ldo", c_i64), ("B", C.c_int32), ("D", C.c_int32), ("vocab", C.c_int32), ("max_pos", C.c_int32)]
+
+
+class DecAttnArgs(C.Structure):
+    """Mirror of ``ser_dec_attn_args``."""
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_i64), ("k_new", c_void_p), ("v_new", c_void_p), ("ld_new", c_i64),
+        ("kcache", c_void_p), ("vcache", c_void_p), ("ldc", c_i64), ("batch_stride", c_i64),
+        ("lens", c_void_p), ("lens_stride", C.c_int32), ("len_add", C.c_int32),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("range_flag", c_void_p), ("scale", c_float),
+        ("B", C.c_int32), ("H", C.c_int32), ("dh", C.c_int32), ("max_len", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
+class DecSelectArgs(C.Structure):
+    """Mirror of ``ser_dec_select_args``."""
+    _fields_ = [
+        ("logits", c_void_p), ("ldl", c_i64), ("mask", c_void_p), ("ldm", c_i64), ("phase", c_void_p), ("forced", c_void_p),
+        ("ids", c_void_p), ("ld_ids", c_i64), ("finished", c_void_p), ("margin", c_void_p), ("ld_margin", c_i64),
+        ("pos", c_void_p), ("unfinished", c_void_p), ("work", c_void_p), ("err", c_void_p),
+        ("B", C.c_int32), ("V", C.c_int32), ("eos", C.c_int32), ("pad", C.c_int32), ("max_pos", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked logit was not finite
+DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
+
+
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
-                ("pos_ln", PosLnArgs)]
+                ("pos_ln", PosLnArgs), ("dec_embed", DecEmbedArgs), ("dec_attn", DecAttnArgs), ("dec_select", DecSelectArgs)]
 
 
 class Cmd(C.Structure):
@@ -256,11 +287,13 @@ class Cmd(C.Structure):
 
 
 OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS, OP_POS_LN = 1, 2, 3, 4, 5, 6, 7, 8, 9
+OP_DEC_EMBED, OP_DEC_ATTN, OP_DEC_SELECT = 10, 11, 12
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
                   "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_xattn_mh_args": XattnMhArgs, "ser_attn_pool_args": AttnPoolArgs,
-                  "ser_fusion_cls_args": FusionClsArgs, "ser_select_rows_args": SelectRowsArgs, "ser_cmd": Cmd}
+                  "ser_fusion_cls_args": FusionClsArgs, "ser_select_rows_args": SelectRowsArgs, "ser_dec_embed_args": DecEmbedArgs, "ser_dec_attn_args": DecAttnArgs,
+                  "ser_dec_select_args": DecSelectArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -290,6 +323,9 @@ _SIGNATURES = {
     "ser_attn_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_fusion_cls_v": (c_int, [c_void_p, c_void_p]),
     "ser_select_rows_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dec_embed_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dec_attn_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dec_select_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -12,7 +12,7 @@ by attribute access without importing this package.
 from __future__ import annotations
 
 from dataclasses import dataclass, field, replace
-from typing import Tuple
+from typing import Optional, Tuple
 
 FAMILY_WAVLM = "wavlm"
 FAMILY_WAV2VEC2 = "wav2vec2"
@@ -70,6 +70,33 @@ class EncoderGeometry:
     def head_dim(self) -> int:
         return self.hidden // self.heads
 
+    # Whisper decoder (engine.WhisperDecoder): attached by ``with_decoder``, read through the properties below.  It is deliberately not a
+    # dataclass field: an encoder geometry compares, hashes and round-trips through a checkpoint's config.json as it did before the
+    # decoder was described (the encoder-only consumers never look at it).  ``dataclasses.replace`` drops it; ``with_decoder`` re-attaches.
+    @property
+    def decoder(self) -> Optional["DecoderGeometry"]:
+        return self.__dict__.get("_decoder")
+
+    @property
+    def decoder_layers(self) -> int:
+        return self.decoder.layers if self.decoder else 0
+
+    @property
+    def decoder_attention_heads(self) -> int:
+        return self.decoder.attention_heads if self.decoder else 0
+
+    @property
+    def decoder_ffn_dim(self) -> int:
+        return self.decoder.ffn_dim if self.decoder else 0
+
+    @property
+    def decoder_vocab_size(self) -> int:
+        return self.decoder.vocab_size if self.decoder else 0
+
+    @property
+    def max_target_positions(self) -> int:
+        return self.decoder.max_target_positions if self.decoder else 448
+
     @property
     def num_hidden_states(self) -> int:
         return self.num_layers + 1
@@ -91,6 +118,25 @@ class EncoderGeometry:
         return out
 
 
+@dataclass(frozen=True)
+class DecoderGeometry:
+    """The decoder of a Whisper checkpoint (config.json: decoder_layers, decoder_attention_heads, decoder_ffn_dim, vocab_size,
+    max_target_positions); the model width is the encoder's ``hidden``."""
+    layers: int
+    attention_heads: int
+    ffn_dim: int
+    vocab_size: int
+    max_target_positions: int = 448
+
+
+def with_decoder(geo: EncoderGeometry, layers: int, attention_heads: int, ffn_dim: int, vocab_size: int,
+                 max_target_positions: int = 448) -> EncoderGeometry:
+    """A copy of a Whisper geometry that also describes the checkpoint's decoder."""
+    g = replace(geo)
+    object.__setattr__(g, "_decoder", DecoderGeometry(int(layers), int(attention_heads), int(ffn_dim), int(vocab_size), int(max_target_positions)))
+    return g
+
+
 WAVLM_LARGE = EncoderGeometry(
     family=FAMILY_WAVLM, num_layers=24, hidden=1024, heads=16, ffn=4096,
     conv_bias=False, name="microsoft/wavlm-large")
@@ -104,9 +150,9 @@ HUBERT_XLARGE = EncoderGeometry(
     conv_bias=True, feat_proj_layer_norm=True,
     name="facebook/hubert-xlarge-ls960-ft")
 
-WHISPER_LARGE_V3 = EncoderGeometry(
+WHISPER_LARGE_V3 = with_decoder(EncoderGeometry(
     family=FAMILY_WHISPER, num_layers=32, hidden=1280, heads=20, ffn=5120,
-    n_mels=128, max_source_positions=1500, name="openai/whisper-large-v3")
+    n_mels=128, max_source_positions=1500, name="openai/whisper-large-v3"), 32, 20, 5120, 51866, 448)
 
 ROBERTA_LARGE = EncoderGeometry(
     family=FAMILY_ROBERTA, num_layers=24, hidden=1024, heads=16, ffn=4096, name="roberta-large")
@@ -264,10 +310,14 @@ def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
             num_buckets=int(cfg.get("num_buckets", 320)), max_bucket_distance=int(cfg.get("max_bucket_distance", 800)),
             layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), feat_extract_norm=norm, stable_layer_norm=stable, name=name)
     if mt == FAMILY_WHISPER:
-        return EncoderGeometry(
+        geo = EncoderGeometry(
             family=FAMILY_WHISPER, num_layers=int(cfg["encoder_layers"]), hidden=int(cfg["d_model"]),
             heads=int(cfg["encoder_attention_heads"]), ffn=int(cfg["encoder_ffn_dim"]), n_mels=int(cfg.get("num_mel_bins", 80)),
             max_source_positions=int(cfg.get("max_source_positions", 1500)), name=name)
+        if int(cfg.get("decoder_layers", 0)) > 0 and "vocab_size" in cfg:
+            geo = with_decoder(geo, cfg["decoder_layers"], cfg.get("decoder_attention_heads", cfg["encoder_attention_heads"]),
+                               cfg.get("decoder_ffn_dim", cfg["encoder_ffn_dim"]), cfg["vocab_size"], cfg.get("max_target_positions", 448))
+        return geo
     if mt in ("roberta", "xlm-roberta"):
         return EncoderGeometry(
             family=FAMILY_ROBERTA, num_layers=int(cfg["num_hidden_layers"]), hidden=int(cfg["hidden_size"]),
@@ -371,7 +421,10 @@ def resolve_do_normalize(ssl_type: str, checkpoint: str = "") -> bool:
 
 
 def with_layers(geo: EncoderGeometry, layers: int) -> EncoderGeometry:
-    return replace(geo, num_layers=layers)
+    g = replace(geo, num_layers=layers)
+    if geo.decoder is not None:                             # replace() goes through __init__, which knows no decoder
+        object.__setattr__(g, "_decoder", geo.decoder)
+    return g
 
 
 # The four fixture geometries under tests/golden (head dims 64 / 120 / 80 / 64 and
@@ -380,6 +433,8 @@ TINY_WAVLM = tiny_geometry(FAMILY_WAVLM, hidden=128, heads=2, ffn=256, pos_group
 TINY_WAV2VEC2 = tiny_geometry(FAMILY_WAV2VEC2, hidden=960, heads=8, ffn=512, pos_groups=8)
 TINY_HUBERT = tiny_geometry(FAMILY_HUBERT, hidden=320, heads=4, ffn=384, pos_groups=4)
 TINY_WHISPER = tiny_geometry(FAMILY_WHISPER, hidden=128, heads=2, ffn=256)
+# ... with the decoder of tests/golden/tiny_whisper_dec_d128h2.npz: 522 = 51 866 mod 8 (+ 8 k), so the vocabulary padding is live
+TINY_WHISPER_DEC = with_decoder(replace(TINY_WHISPER, name="tiny-whisper-dec-d128h2"), 2, 2, 512, 522, 64)
 TINY_ROBERTA = tiny_geometry(FAMILY_ROBERTA, hidden=128, heads=2, ffn=256)
 TINY_DEBERTA = tiny_geometry(FAMILY_DEBERTA, hidden=128, heads=2, ffn=256)
 TINY_DEBERTA_CONV = tiny_geometry(FAMILY_DEBERTA, hidden=128, heads=2, ffn=256, text_conv_kernel=3)      # deberta-v2-xlarge style
@@ -391,3 +446,63 @@ TINY_HUBERT_BASE = tiny_geometry(FAMILY_HUBERT, hidden=128, heads=2, ffn=256, po
 # model's (768 / 16), not a multiple of 64, so the stack's GEMMs read the padded channels of pos_kc
 TINY_DATA2VEC_AUDIO = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=128, heads=2, ffn=256, pos_groups=2)
 TINY_DATA2VEC_AUDIO_G48 = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=192, heads=3, ffn=256, pos_groups=4, conv_bias=True)
+
+
+@dataclass(frozen=True)
+class GenerationSpec:
+    """What the short-form path of HF's ``WhisperGenerationMixin.generate`` reads from ``generation_config.json`` when it is called with
+    defaults (greedy, no timestamps): prompt ``[start, language, task, no_timestamps]``, ``suppress_tokens`` at every generated
+    position, ``begin_suppress_tokens`` at the first one too.  ``language`` None: detected per utterance (one step on ``[start]``,
+    logits restricted to ``lang_ids``, argmax)."""
+    decoder_start_token_id: int
+    eos_token_id: int
+    pad_token_id: int
+    suppress_tokens: Tuple[int, ...]
+    begin_suppress_tokens: Tuple[int, ...]
+    no_timestamps_token_id: int
+    lang_ids: Tuple[int, ...]
+    task_id: int
+    max_length: int = 448
+    language: object = None            # None, a token id, or a key of ``lang_to_id`` ("en" / "<|en|>") resolved by from_snapshot
+
+    PROMPT_LEN = 4
+
+    @staticmethod
+    def from_config(cfg: dict, language=None) -> "GenerationSpec":
+        lang_to_id = {str(k): int(v) for k, v in (cfg.get("lang_to_id") or {}).items()}
+        task_to_id = cfg.get("task_to_id") or {}
+        missing = [k for k in ("decoder_start_token_id", "eos_token_id", "no_timestamps_token_id") if cfg.get(k) is None]
+        if missing or not lang_to_id or "transcribe" not in task_to_id:
+            raise OSError("generation_config.json lacks " + ", ".join(missing + ["lang_to_id"] * (not lang_to_id)
+                                                                      + ["task_to_id.transcribe"] * ("transcribe" not in task_to_id)))
+        if language is not None and not isinstance(language, int):
+            key = str(language)
+            for cand in (key, f"<|{key}|>"):
+                if cand in lang_to_id:
+                    language = lang_to_id[cand]
+                    break
+            else:
+                raise ValueError(f"language '{key}' is not in the checkpoint's lang_to_id")
+        eos = cfg["eos_token_id"]
+        eos = int(eos[0] if isinstance(eos, (list, tuple)) else eos)
+        pad = cfg.get("pad_token_id")
+        return GenerationSpec(
+            decoder_start_token_id=int(cfg["decoder_start_token_id"]), eos_token_id=eos, pad_token_id=eos if pad is None else int(pad),
+            suppress_tokens=tuple(int(t) for t in cfg.get("suppress_tokens") or ()),
+            begin_suppress_tokens=tuple(int(t) for t in cfg.get("begin_suppress_tokens") or ()),
+            no_timestamps_token_id=int(cfg["no_timestamps_token_id"]), lang_ids=tuple(sorted(lang_to_id.values())),
+            task_id=int(task_to_id["transcribe"]), max_length=int(cfg.get("max_length", 448)), language=language)
+
+    @staticmethod
+    def from_snapshot(directory: str, language=None) -> "GenerationSpec":
+        """``generation_config.json`` of a local snapshot directory (or of the directory a checkpoint file lies in)."""
+        import json
+        import os
+        d = directory if os.path.isdir(directory) else os.path.dirname(os.path.abspath(directory))
+        path = os.path.join(d, "generation_config.json")
+        try:
+            with open(path, "r") as f:
+                cfg = json.load(f)
+        except (OSError, ValueError) as e:
+            raise OSError(f"cannot read {path}: {e}")
+        return GenerationSpec.from_config(cfg, language)

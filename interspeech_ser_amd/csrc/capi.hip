@@ -71,6 +71,18 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_pos_ln_v(&c.u.pos_ln, stream);
                 break;
             }
+            case SER_OP_DEC_EMBED: {
+                rc = ser_dec_embed_v(&c.u.dec_embed, stream);
+                break;
+            }
+            case SER_OP_DEC_ATTN: {
+                rc = ser_dec_attn_v(&c.u.dec_attn, stream);
+                break;
+            }
+            case SER_OP_DEC_SELECT: {
+                rc = ser_dec_select_v(&c.u.dec_select, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

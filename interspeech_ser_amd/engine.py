@@ -123,12 +123,12 @@ class Tape:
                 self.patches.append((view, field, value.name))
         self.n += 1
 
-    def subset(self, keep) -> "Tape":
+    def subset(self, keep, by_cmd: bool = False) -> "Tape":
         """Measurement aid (bench.py ``step_decomposition``): a command list holding copies of the recorded launches whose op
-        satisfies ``keep(op)``, with the sizes of the batch that ran last.  Same pointers, same shapes, same kernels -- replayed
+        satisfies ``keep(op)`` (or, with ``by_cmd``, ``keep(cmd)``: two uses of one op apart), with the sizes of the batch that ran last.  Same pointers, same shapes, same kernels -- replayed
         on its own it shows what ONE class of kernels (the GEMMs, the attention kernels, the row kernels) costs in the regime
         the step runs them in (two utterance groups on parallel graph branches)."""
-        picked = [i for i in range(self.n) if keep(self.cmds[i].op)]
+        picked = [i for i in range(self.n) if keep(self.cmds[i] if by_cmd else self.cmds[i].op)]
         t = Tape(max(1, len(picked)))
         for j, i in enumerate(picked):
             C.memmove(C.byref(t.cmds[j]), C.byref(self.cmds[i]), C.sizeof(_lib.Cmd))
@@ -2234,6 +2234,302 @@ class TrimodalHead(_FusionBase):
         if isinstance(x3, torch.Tensor) and x3.dim() == 3 and x3.shape[-1] == 1:
             x3 = x3.squeeze(-1)
         return self._forward((x1, x2, x3), (offs1, offs2, offs3), slot, range_flag)
+
+
+class DecodeResult:
+    """One batch of ``WhisperDecoder.generate``: ``sequences`` int64 [B, n] (prompt, generated ids, eos / pad tail; n = the length at which
+    every row had finished, else max_length), ``languages`` [B], ``lists`` (per utterance the generated ids without the prompt, up to and
+    excluding eos), ``margins`` fp32 [B, n - 1] (top-1 minus top-2 masked logit of position p's decision, +inf where nothing was decided),
+    ``range_bits`` (fp16 range guard) and ``err`` (ser_dec_select_v's error word): the batch failed when either is set."""
+
+    def __init__(self, sequences, languages, lists, margins, range_bits, err):
+        self.sequences, self.languages, self.lists, self.margins = sequences, languages, lists, margins
+        self.range_bits, self.err = int(range_bits), int(err)
+
+    @property
+    def failed(self) -> bool:
+        return bool(self.range_bits & 1) or self.err != 0
+
+
+class WhisperDecoder(_LaunchHost):
+    """Whisper decoder with greedy short-form generation (HF modeling_whisper.py WhisperDecoder, generation_whisper.py with defaults) behind
+    ``WhisperEncoder``: the reference's transcripts (test/Whisper transcriptions.ipynb).  Lock-step: all rows of a batch stand at the same
+    position; one step takes ids[:, pos] to ids[:, pos + 1] on the device -- ids, finished flags and the position live there, and the
+    host reads the count of unfinished rows back every ``CHECK_EVERY`` steps only.  A step is 11 launches per layer (3 LayerNorms, 6 GEMMs,
+    2 ser_dec_attn_v) + 4, recorded once per (slot, B) and replayed with ser_run; the host leaves the logits launches out at positions
+    whose next token is forced.  The cross keys / values of all layers are projected once per batch into an fp32 cache."""
+
+    DEC_MODES = ("f16x", "fp32x", "bf16")
+    CHECK_EVERY = 4
+    PHASE_STEADY, PHASE_FIRST, PHASE_LANG = 0, 1, 2
+
+    def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "f16x", spec=None):
+        if mode not in self.DEC_MODES:
+            print(f"WhisperDecoder: mode '{mode}' has no decoder form, using 'f16x'")
+            mode = "f16x"
+        m = MODES[mode]
+        super().__init__(device, mode, m, m, mode == "f16x" and _os.environ.get("SER_NO_RANGE_GUARD", "0") != "1")
+        if geo.family != FAMILY_WHISPER or geo.decoder_layers < 1:
+            raise ValueError("WhisperDecoder needs a whisper geometry with decoder_layers >= 1")
+        if geo.hidden != 64 * geo.decoder_attention_heads:
+            raise ValueError("the decoder attention kernel needs head dim 64 (every Whisper size)")
+        self.geo, self.spec = geo, spec
+        sd = state_dict
+        D, V = geo.hidden, geo.decoder_vocab_size
+        self.Vp = (V + 7) // 8 * 8                      # GEMM N: zero rows behind the vocabulary; their logits are never read
+        emb = torch.zeros((self.Vp, D), dtype=torch.float32)
+        emb[:V] = sd["decoder.embed_tokens.weight"].detach().float().cpu()
+        self.embed = self._dev_f32(emb)
+        self.proj = self._linear(emb, None, name="decoder.embed_tokens.weight")        # tied output projection, no bias
+        self.pos_emb = self._dev_f32(sd["decoder.embed_positions.weight"])
+        if self.pos_emb.shape[0] != geo.max_target_positions:
+            raise ValueError("decoder.embed_positions.weight does not have max_target_positions rows")
+        self.final_ln = self._ln(sd, "decoder.layer_norm")
+        self.layers = []
+        zeros = torch.zeros(D)
+        for i in range(geo.decoder_layers):
+            p = f"decoder.layers.{i}"
+            sa, ca = p + ".self_attn", p + ".encoder_attn"
+            cat = lambda names: torch.cat([sd[n].detach().float().cpu() for n in names], 0)
+            lay = dict(
+                ln1=self._ln(sd, p + ".self_attn_layer_norm"),
+                qkv=self._linear(cat([sa + ".q_proj.weight", sa + ".k_proj.weight", sa + ".v_proj.weight"]),       # k_proj has no bias
+                                 torch.cat([sd[sa + ".q_proj.bias"].float().cpu(), zeros, sd[sa + ".v_proj.bias"].float().cpu()]),
+                                 name=sa + ".{q,k,v}_proj.weight"),
+                out=self._linear(sd[sa + ".out_proj.weight"], sd[sa + ".out_proj.bias"], name=sa + ".out_proj.weight"),
+                ln2=self._ln(sd, p + ".encoder_attn_layer_norm"),
+                cq=self._linear(sd[ca + ".q_proj.weight"], sd[ca + ".q_proj.bias"], name=ca + ".q_proj.weight"),
+                ckv=self._linear(cat([ca + ".k_proj.weight", ca + ".v_proj.weight"]), torch.cat([zeros, sd[ca + ".v_proj.bias"].float().cpu()]),
+                                 name=ca + ".{k,v}_proj.weight"),
+                cout=self._linear(sd[ca + ".out_proj.weight"], sd[ca + ".out_proj.bias"], name=ca + ".out_proj.weight"),
+                ln3=self._ln(sd, p + ".final_layer_norm"),
+                fc1=self._linear(sd[p + ".fc1.weight"], sd[p + ".fc1.bias"], name=p + ".fc1.weight"),
+                fc2=self._linear(sd[p + ".fc2.weight"], sd[p + ".fc2.bias"], name=p + ".fc2.weight"))
+            self.layers.append(lay)
+        self._plans: Dict = {}
+        self._masks: Dict = {}
+        self._cache, self._cache_B = None, 0
+
+    def _ln(self, sd, prefix):
+        return (self._dev_f32(sd[prefix + ".weight"]), self._dev_f32(sd[prefix + ".bias"]))
+
+    # ------------------------------------------------------------------ buffers
+    def _plan(self, B: int, slot: int):
+        pl = self._plans.get((slot, B))
+        if pl is not None:
+            return pl
+        geo, dev = self.geo, self.device
+        D, L, T, S = geo.hidden, geo.decoder_layers, geo.max_target_positions, geo.max_source_positions
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        pl = dict(B=B, ids=i32(B, T), finished=i32(B), margin=f32(B, T), pos=i32(1), unfinished=i32(1), work=i32(2), err=i32(1),
+                  phase=i32(T), forced=i32(T), range_flag=i32(1) if self.fp16_planes else None,
+                  x=[f32(B, D), f32(B, D), f32(B, D)], qkv=f32(B, 3 * D), qc=f32(B, D), logits=f32(B, self.Vp),
+                  xa=self._new_act(B, D), ctx=self._new_act(B, D), ffn=self._new_act(B, geo.decoder_ffn_dim),
+                  enc_act=self._new_act(B * S, D))
+        # the K / V caches (at large-v3 geometry and B = 16: 2.3 GB self + 7.9 GB cross) belong to the decoder, not to the plan: generate()
+        # ends with a host synchronisation, so no two batches are ever in flight and every (slot, B) plan can read the same storage
+        ks, vs, cr = self._caches(B)
+        pl["kself"], pl["vself"] = ks[: L * B * T * D].view(L, B, T, D), vs[: L * B * T * D].view(L, B, T, D)
+        pl["cross"] = cr[: L * B * S * 2 * D].view(L, B * S, 2 * D)
+        pl["host"] = torch.empty(3, dtype=torch.int32).pin_memory()
+        self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
+        self._rec = tape = Tape()
+        try:
+            self._step_launches(pl)
+        finally:
+            self._rec = None
+        pl["tape"] = tape
+        if len(self._plans) >= 6:
+            self._plans.pop(next(iter(self._plans)))
+        self._plans[(slot, B)] = pl
+        return pl
+
+    def _caches(self, B: int):
+        """(self k, self v, cross k | v) flat fp32 storage for the largest batch seen.  A larger batch replaces it and drops every plan,
+        whose recorded commands point into the old storage."""
+        geo = self.geo
+        if B > self._cache_B:
+            self._plans.clear()
+            self._cache = None                          # free before allocating the larger one
+            n_self = geo.decoder_layers * B * geo.max_target_positions * geo.hidden
+            n_cross = geo.decoder_layers * B * geo.max_source_positions * 2 * geo.hidden
+            self._cache = tuple(torch.empty(n, dtype=torch.float32, device=self.device) for n in (n_self, n_self, n_cross))
+            self._cache_B = B
+        return self._cache
+
+    def _dec_attn(self, pl, q: torch.Tensor, ldq: int, kc: torch.Tensor, vc_ptr: int, ldc: int, batch_stride: int, max_len: int, *,
+                  new=None, lens=None, len_add: int) -> None:
+        geo = self.geo
+        a = self._cmd("dec_attn")
+        a.q, a.ldq = q.data_ptr(), ldq
+        if new is not None:
+            a.k_new, a.v_new, a.ld_new = new
+        a.kcache, a.vcache, a.ldc, a.batch_stride = kc.data_ptr(), vc_ptr, ldc, batch_stride
+        a.lens, a.lens_stride, a.len_add = _ptr(lens), 0, len_add
+        ctx = pl["ctx"]
+        a.out_act, a.ldo_act, a.out_plane_stride, a.range_flag = ctx.ptr, ctx.cols, ctx.plane_stride, self._flag
+        a.scale, a.B, a.H, a.dh, a.max_len, a.mode = 64 ** -0.5, pl["B"], geo.decoder_attention_heads, 64, max_len, self.mode
+        self._issue(_lib.OP_DEC_ATTN, a, "ser_dec_attn")
+
+    def _step_launches(self, pl) -> None:
+        """One decode step: ids[:, pos] -> logits -> ids[:, pos + 1].  pl["n_body"] / pl["n_logits"]: the command ranges of the layers and
+        of final LayerNorm + logits GEMM (left out when the next token is forced); ser_dec_select_v is the last command."""
+        geo = self.geo
+        B, D, T, S = pl["B"], geo.hidden, geo.max_target_positions, geo.max_source_positions
+        x0, x1, x2 = pl["x"]
+        e = self._cmd("dec_embed")
+        e.ids, e.ld_ids, e.pos = pl["ids"].data_ptr(), T, pl["pos"].data_ptr()
+        e.embed_tokens, e.embed_positions, e.out, e.ldo = self.embed.data_ptr(), self.pos_emb.data_ptr(), x0.data_ptr(), D
+        e.B, e.D, e.vocab, e.max_pos = B, D, geo.decoder_vocab_size, T
+        self._issue(_lib.OP_DEC_EMBED, e, "ser_dec_embed")
+        qkv, qc = pl["qkv"], pl["qc"]
+        for i, lay in enumerate(self.layers):
+            self._layernorm(x0, D, lay["ln1"], B, D, out_act=pl["xa"])
+            self._gemm(pl["xa"], lay["qkv"], B, out_f32=qkv, ldo_f32=3 * D)
+            self._dec_attn(pl, qkv, 3 * D, pl["kself"][i], pl["vself"][i].data_ptr(), D, T * D, T,
+                           new=(qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D, 3 * D), lens=pl["pos"], len_add=1)
+            self._gemm(pl["ctx"], lay["out"], B, residual=x0, ldr=D, out_f32=x1, ldo_f32=D)
+            self._layernorm(x1, D, lay["ln2"], B, D, out_act=pl["xa"])
+            self._gemm(pl["xa"], lay["cq"], B, out_f32=qc, ldo_f32=D)
+            cross = pl["cross"][i]
+            self._dec_attn(pl, qc, D, cross, cross.data_ptr() + 4 * D, 2 * D, S * 2 * D, S, len_add=S)
+            self._gemm(pl["ctx"], lay["cout"], B, residual=x1, ldr=D, out_f32=x2, ldo_f32=D)
+            self._layernorm(x2, D, lay["ln3"], B, D, out_act=pl["xa"])
+            self._gemm(pl["xa"], lay["fc1"], B, act=_lib.ACT_GELU, out_act=pl["ffn"])
+            self._gemm(pl["ffn"], lay["fc2"], B, residual=x2, ldr=D, out_f32=x0, ldo_f32=D)
+        pl["n_body"] = self._rec.n if self._rec is not None else None
+        self._layernorm(x0, D, self.final_ln, B, D, out_act=pl["xa"])
+        self._gemm(pl["xa"], self.proj, B, out_f32=pl["logits"], ldo_f32=self.Vp)
+        pl["n_logits"] = self._rec.n if self._rec is not None else None
+        s = self._cmd("dec_select")
+        s.logits, s.ldl = pl["logits"].data_ptr(), self.Vp
+        s.mask, s.ldm = 0, geo.decoder_vocab_size                      # the spec's masks: set per generate() call (_bind_spec)
+        s.phase, s.forced = pl["phase"].data_ptr(), pl["forced"].data_ptr()
+        s.ids, s.ld_ids, s.finished = pl["ids"].data_ptr(), T, pl["finished"].data_ptr()
+        s.margin, s.ld_margin = pl["margin"].data_ptr(), T
+        s.pos, s.unfinished, s.work, s.err = pl["pos"].data_ptr(), pl["unfinished"].data_ptr(), pl["work"].data_ptr(), pl["err"].data_ptr()
+        s.B, s.V, s.eos, s.pad, s.max_pos = B, geo.decoder_vocab_size, 0, 0, T
+        pl["select"] = s
+        self._issue(_lib.OP_DEC_SELECT, s, "ser_dec_select")
+
+    def _spec_masks(self, spec) -> torch.Tensor:
+        """fp32 [3, V] additive masks of a spec on the device: steady, first generated position, language set."""
+        key = (spec.suppress_tokens, spec.begin_suppress_tokens, spec.lang_ids)
+        m = self._masks.get(key)
+        if m is None:
+            V = self.geo.decoder_vocab_size
+            bad = [t for t in key[0] + key[1] + key[2] if not 0 <= t < V]
+            if bad:
+                raise ValueError(f"generation spec names token ids outside the vocabulary: {bad[:4]}")
+            h = torch.zeros((3, V), dtype=torch.float32)
+            h[0, list(spec.suppress_tokens)] = float("-inf")
+            h[1] = h[0]
+            h[1, list(spec.begin_suppress_tokens)] = float("-inf")
+            h[2] = float("-inf")
+            h[2, list(spec.lang_ids)] = 0.0
+            m = self._masks[key] = h.to(self.device)
+        return m
+
+    # ------------------------------------------------------------------ the batch
+    @_on_stream
+    def project_cross(self, pl, enc_last: torch.Tensor) -> None:
+        """Once per batch: the encoder's last hidden state [B * 1500, D] -> every layer's cross keys | values (one ser_gemm per layer, N = 2 D)
+        in the fp32 cache."""
+        geo = self.geo
+        B, D, S = pl["B"], geo.hidden, geo.max_source_positions
+        if tuple(enc_last.shape) != (B * S, D) or enc_last.dtype != torch.float32 or not enc_last.is_contiguous():
+            raise ValueError(f"the decoder needs the encoder's last hidden state as contiguous fp32 [{B * S}, {D}], got {tuple(enc_last.shape)}")
+        ea = pl["enc_act"]
+        check(lib.ser_pack_rows_flagged(enc_last.data_ptr(), D, 1, B * S, D, 0, ea.ptr, D, ea.plane_stride, self.mode, self._flag, self._s()),
+              "ser_pack_rows_flagged")
+        for i, lay in enumerate(self.layers):
+            self._gemm(ea, lay["ckv"], B * S, out_f32=pl["cross"][i], ldo_f32=2 * D)
+
+    def _run_step(self, pl, with_logits: bool) -> None:
+        tape = pl["tape"]
+        st = self._s()
+        if with_logits:
+            rc = lib.ser_run(tape.cmds, tape.n, C.byref(tape._failed), st)
+        else:
+            rc = lib.ser_run(tape.cmds, pl["n_body"], C.byref(tape._failed), st)
+            if rc == 0:
+                rc = lib.ser_run(C.byref(tape.cmds, pl["n_logits"] * C.sizeof(_lib.Cmd)), tape.n - pl["n_logits"], C.byref(tape._failed), st)
+        if rc != 0:
+            check(rc, f"ser_run (decoder step, command {tape._failed.value})")
+
+    def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None):
+        """Reset the slot's decoding state for a batch of B: ids[:, 0] = start, position 0, nothing finished.  ``forced_ids`` (tests:
+        teacher forcing): a whole id row to follow instead of the spec's prompt."""
+        spec = spec or self.spec
+        if spec is None:
+            raise ValueError("WhisperDecoder needs a GenerationSpec")
+        geo = self.geo
+        T = geo.max_target_positions
+        n_max = min(int(spec.max_length), T)
+        pl = self._plan(B, slot)
+        language = spec.language if language is None else language
+        forced = np.full(T, -1, dtype=np.int32)
+        phase = np.zeros(T, dtype=np.int32)
+        if forced_ids is not None:
+            forced[: len(forced_ids) - 1] = np.asarray(forced_ids[1:], dtype=np.int32)
+            start = int(forced_ids[0])
+        else:
+            start = spec.decoder_start_token_id
+            forced[1], forced[2] = spec.task_id, spec.no_timestamps_token_id
+            if language is not None:
+                forced[0] = int(language)
+            phase[0], phase[spec.PROMPT_LEN - 1] = self.PHASE_LANG, self.PHASE_FIRST
+        pl["forced_host"], pl["n_max"], pl["spec"] = forced, n_max, spec
+        pl["forced"].copy_(torch.from_numpy(forced))
+        pl["phase"].copy_(torch.from_numpy(phase))
+        for k in ("finished", "pos", "unfinished", "work", "err") + (("range_flag",) if pl["range_flag"] is not None else ()):
+            pl[k].zero_()
+        pl["ids"].zero_()
+        pl["ids"][:, 0] = start
+        pl["margin"].fill_(float("inf"))
+        s = pl["select"]
+        s.mask, s.eos, s.pad = self._spec_masks(spec).data_ptr(), spec.eos_token_id, spec.pad_token_id
+        self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
+        return pl
+
+    @_on_stream
+    def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0) -> DecodeResult:
+        """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``)."""
+        pl = self.begin(B, spec, language, slot)
+        spec = pl["spec"]
+        self.project_cross(pl, enc_last)
+        n_max, forced = pl["n_max"], pl["forced_host"]
+        host = pl["host"]
+        steps = 0
+        for pos in range(n_max - 1):
+            self._run_step(pl, with_logits=forced[pos] < 0)
+            steps += 1
+            if steps % self.CHECK_EVERY == 0 and pos >= spec.PROMPT_LEN - 1:
+                host[0:1].copy_(pl["unfinished"], non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                if int(host[0]) == 0:
+                    break
+        return self.result(pl, steps)
+
+    def result(self, pl, steps: int) -> DecodeResult:
+        spec = pl["spec"]
+        ids = pl["ids"][:, : steps + 1].cpu().numpy().astype(np.int64)
+        margins = pl["margin"][:, :steps].cpu().numpy()
+        err = int(pl["err"].item()) & 0xffffffff
+        bits = 0
+        if pl["range_flag"] is not None:
+            bits = int(pl["range_flag"].item())
+            pl["range_flag"].zero_()
+        P = spec.PROMPT_LEN
+        lists, ends = [], []
+        for row in ids:
+            gen = row[P:].tolist()
+            cut = gen.index(spec.eos_token_id) if spec.eos_token_id in gen else None
+            lists.append(gen if cut is None else gen[:cut])
+            ends.append(ids.shape[1] if cut is None else P + cut + 1)
+        n = max(ends)                                   # the length at which every row had finished (steps past it wrote pad only)
+        return DecodeResult(ids[:, :n], ids[:, 1].copy(), lists, margins[:, : n - 1], bits, err)
 
 
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):

@@ -31,6 +31,9 @@ class AudioStream:
 
     def __init__(self, enc, state: int = -1, average: bool = False):
         self.enc, self.state, self.average = enc, int(state), bool(average)
+        # (Whisper) set by ``FusionPredictor.transcribe_with``: the forward's HiddenStates, B -> (input_ids, attention_mask) of the
+        # batch's own transcripts; the forward then runs to its end and feeds the head's state and the decoder alike
+        self.tokens_from_states = None
 
 
 class TextStream:
@@ -117,6 +120,26 @@ class FusionPredictor:
             self.head = FusionHead(head_sd, *dims, self.device, mode)
         self.n_out = self.head.n_out
 
+    def transcribe_with(self, decoder, spec, tokenize, detokenize=None) -> None:
+        """Texts from the Whisper stream's own transcript instead of the caller's tokens: ``decoder`` (``engine.WhisperDecoder`` over the
+        Whisper stream's checkpoint) decodes greedily from the last state of that stream's forward, ``detokenize(ids) -> str`` (default:
+        the ids as decimal numbers, what preprocessing/transcribe_whisper.py writes without vocabulary files) and ``tokenize(texts) ->
+        (input_ids, attention_mask)`` turn the ids into the text stream's input.  A batch whose decoder error word or range guard is set
+        raises ``SerHipError``, like a failed forward."""
+        audio = [s for s in self.streams if isinstance(s, AudioStream) and isinstance(s.enc, WhisperEncoder)]
+        if not audio or not any(isinstance(s, TextStream) for s in self.streams):
+            raise ValueError("transcription needs a Whisper audio stream and a text stream")
+        detok = detokenize or (lambda ids: " ".join(str(t) for t in ids))
+
+        def tokens(hs, B):
+            res = decoder.generate(hs.states[-1], B, spec)
+            if res.failed:
+                hs.take_range_bits()                    # predict() will not get to it: a bit left set would fail the next batch's first forward
+                raise SerHipError(f"transcription failed: decoder error word {res.err:#x}, range-guard bits {res.range_bits:#x}")
+            self.last_texts = [detok(ids) for ids in res.lists]
+            return tokenize(self.last_texts)
+        audio[0].tokens_from_states = tokens
+
     @staticmethod
     def _source(s, hs, counts):
         """the stream's rows inside its forward's states, ``counts[b]`` of them from each utterance's first row"""
@@ -139,7 +162,8 @@ class FusionPredictor:
                 raise ValueError("an AudioStream needs waves")
             waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
             B = len(waves)
-        if any(isinstance(s, TextStream) for s in self.streams):
+        transcriber = next((s for s in self.streams if isinstance(s, AudioStream) and s.tokens_from_states is not None), None)
+        if any(isinstance(s, TextStream) for s in self.streams) and transcriber is None:
             if input_ids is None or attention_mask is None:
                 raise ValueError("a TextStream needs input_ids and attention_mask")
             if B is not None and input_ids.shape[0] != B:
@@ -151,10 +175,15 @@ class FusionPredictor:
             if len(rows) != B:
                 raise ValueError(f"{len(rows)} row matrices for {B} utterances")
         out = []
-        for s in self.streams:
+        # with a transcriber its stream goes first: the text stream's tokens come out of it
+        order = self.streams if transcriber is None else [transcriber] + [s for s in self.streams if s is not transcriber]
+        for s in order:
             if isinstance(s, AudioStream):
                 lengths = [len(w) for w in waves]
-                hs = s.enc.forward(s.enc.upload(waves), lengths, last_state=None if s.average else s.index)
+                full = s.average or s is transcriber            # the decoder reads the LAST state: that forward does not stop early
+                hs = s.enc.forward(s.enc.upload(waves), lengths, last_state=None if full else s.index)
+                if s is transcriber:
+                    input_ids, attention_mask = s.tokens_from_states(hs, B)
                 if isinstance(s.enc, WhisperEncoder):                      # the rows the reference keeps of each 1 500-row window
                     counts = [min(whisper_saved_rows(n, s.enc.geo.hidden), hs.frames(b)) for b, n in enumerate(lengths)]
                 else:
@@ -173,6 +202,8 @@ class FusionPredictor:
                         raise ValueError(f"rows must be [T >= 1, {s.dim}] matrices, got {tuple(r.shape)}")
                     mats.append(r.float().contiguous())
                 out.append((torch.cat(mats).to(self.device), [0] + [int(v) for v in np.cumsum([m.shape[0] for m in mats])], None))
+        if transcriber is not None:
+            out = [out[order.index(s)] for s in self.streams]
         return out
 
     def predict(self, waves: Optional[Sequence[np.ndarray]] = None, input_ids: Optional[torch.Tensor] = None,
@@ -224,7 +255,8 @@ def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[s
 def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Sequence[int]] = None, averages: Optional[Sequence[bool]] = None,
                    checkpoints: Optional[Sequence[str]] = None, test_csv: Optional[str] = None, mode: str = "f16mf", text_mode: str = "f16x",
                    head_mode: Optional[str] = None, batch_size: int = 16, num_workers: int = 4, tokenizer_path: str = "", max_len: int = 80,
-                   synthetic_weights: bool = False, seed: int = 7, device: Optional[str] = None, tokenize=None) -> Dict:
+                   synthetic_weights: bool = False, seed: int = 7, device: Optional[str] = None, tokenize=None, transcribe: bool = False,
+                   spec: Optional[C.GenerationSpec] = None, detokenize=None, language=None) -> Dict:
     """``head.score(engine="hip")`` from the corpus itself: the ``FileName`` column of ``test_csv``, wavs from ``config["wav_dir"]``
     (16 kHz), transcripts from the table ``config["txt_dir"]`` (columns FileName, transcription), the head's weights from
     ``<model_path>/multimodal_ser.pt`` -> ``<model_path>/results/test.csv`` in ``head.score``'s format.  ``encoders``: two or three
@@ -233,7 +265,9 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     or the mean.  ``mode`` / ``text_mode`` / ``head_mode``: numerics of the audio encoders, the text encoders and the head (default: the
     first encoder's).  ``tokenize``: texts -> (input_ids, attention_mask), default ``driver.hf_tokenize_fn``.  A file that cannot be
     decoded, has no transcript or is empty is printed and gets no row; a batch whose range-guard or GRU error word is set is retried file
-    by file.  Returns {"csv", "n", "failed"}."""
+    by file.  ``transcribe``: the texts are the Whisper stream's own transcripts (``FusionPredictor.transcribe_with``) and ``txt_dir`` is not
+    read; ``spec`` (default: the checkpoint's generation_config.json, with ``language``) and ``detokenize`` (default: the checkpoint's
+    tokenizer from local files, else the ids as numbers) belong to it.  Returns {"csv", "n", "failed"}."""
     from . import head as HD
     from .driver import _Extractor, find_weights, hf_tokenize_fn
     from .engine import build_encoder
@@ -257,6 +291,10 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     names = pd.read_csv(test_csv or HD.TEST_CSV)["FileName"].tolist()
     texts: Dict[str, str] = {}
     streams = []
+    decoder = None
+    if transcribe and not (any(g is not None and g.family == C.FAMILY_WHISPER and g.decoder_layers > 0 for g in geos)
+                           and any(g is not None and g.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA) for g in geos)):
+        raise ValueError("transcribe needs a Whisper encoder whose checkpoint has a decoder, and a text encoder")
     for i, (name, geo) in enumerate(zip(encoders, geos)):
         if geo is None:
             streams.append(RowsStream(int(config[f"feat{i + 1}_dim"])))
@@ -267,19 +305,37 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
         if text:
             if tokenize is None:
                 tokenize = hf_tokenize_fn(tokenizer_path or name, max_len, geo.family)
-            if not texts:
-                df = pd.read_csv(config["txt_dir"])
-                texts = {str(f): str(t) for f, t in zip(df.FileName.values, df.transcription.values)}
+            if not texts and not transcribe:
+                from .transcribe import read_table
+                texts = read_table(config["txt_dir"])
             enc = build_encoder(geo, sd, dev, text_mode)
             streams.append(TextStream(enc, averages[i]))
         else:
             m = _Extractor.supported_mode(geo, mode, whisper, name)
             enc = build_encoder(geo, sd, dev, m, normalize=True if whisper else C.resolve_do_normalize(name, checkpoints[i]))
             streams.append(AudioStream(enc, layers[i], averages[i]))
+            if transcribe and whisper and decoder is None and geo.decoder_layers > 0:
+                from .engine import WhisperDecoder
+                from .transcribe import load_tokenizer
+                if synthetic_weights:
+                    from .weights import synthetic_decoder_state_dict
+                    sd = dict(sd)
+                    sd.update(synthetic_decoder_state_dict(geo, seed))
+                if spec is None:
+                    cfg_json = C.find_config_json(name, checkpoints[i])
+                    if not cfg_json:
+                        raise OSError(f"no generation_config.json for {name} (it lies beside config.json in a local snapshot)")
+                    spec = C.GenerationSpec.from_snapshot(os.path.dirname(cfg_json), language)
+                decoder = WhisperDecoder(geo, sd, dev, m, spec)
+                if detokenize is None and not synthetic_weights:
+                    tok = load_tokenizer(tokenizer_path or name)
+                    detokenize = None if tok is None else (lambda ids, tok=tok: tok.decode(ids, skip_special_tokens=True))
         print(f"Stream {i + 1}: {name} ({src}; numerics mode {enc.mode_name})")
         del sd
     head_sd = torch.load(os.path.join(model_path, "multimodal_ser.pt"), map_location="cpu", weights_only=True)
     pred = FusionPredictor(streams, head_sd, head_mode)
+    if transcribe:
+        pred.transcribe_with(decoder, spec, tokenize, detokenize)
     has_text, has_rows = any(isinstance(s, TextStream) for s in streams), any(isinstance(s, RowsStream) for s in streams)
     log.info("Starting scoring test samples...")
     done, rows_out, failed = [], [], 0
@@ -296,7 +352,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
             if len(wave) < 1:
                 raise ValueError("empty waveform")
             text = None
-            if has_text:
+            if has_text and not transcribe:
                 if name not in texts:
                     raise KeyError(f"no transcript in {config['txt_dir']}")
                 text = texts[name]
@@ -314,7 +370,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     def run(items):
         """items: (index, name, waveform, transcript, rows) -> error message or None; appends the rows of a clean batch"""
         ids = mask = None
-        if has_text:
+        if has_text and not transcribe:
             ids, mask = tokenize([it[3] for it in items])
         out = pred.predict([it[2] for it in items], ids, mask, [it[4] for it in items] if has_rows else None)
         for it, row in zip(items, out):
@@ -388,6 +444,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--tokenizer_path", type=str, default="")
     p.add_argument("--max_len", type=int, default=80)
     p.add_argument("--synthetic_weights", action="store_true")
+    p.add_argument("--transcribe", action="store_true", help="texts from the Whisper stream's own transcripts (no txt_dir)")
+    p.add_argument("--language", type=str, default=None, help="with --transcribe: e.g. en; default: detected per utterance")
     a = p.parse_args(argv)
     with open(a.config_path, "r") as f:
         config = json.load(f)
@@ -395,5 +453,6 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     pick = lambda what: [getattr(a, f"{what}{i}") for i in range(1, k + 1)]
     score_from_wav(config, pick("encoder"), pick("layer"), pick("average"), pick("checkpoint"), test_csv=a.test_csv, mode=a.mode,
                    text_mode=a.text_mode, head_mode=a.head_mode, batch_size=a.batch_size, num_workers=a.num_workers,
-                   tokenizer_path=a.tokenizer_path, max_len=a.max_len, synthetic_weights=a.synthetic_weights, seed=a.seed)
+                   tokenizer_path=a.tokenizer_path, max_len=a.max_len, synthetic_weights=a.synthetic_weights, seed=a.seed,
+                   transcribe=a.transcribe, language=a.language)
     return 0

@@ -63,6 +63,32 @@ def whisper_sinusoids(length: int, channels: int) -> torch.Tensor:
     return torch.from_numpy(np.concatenate([np.sin(t), np.cos(t)], axis=1).astype(np.float32))
 
 
+def synthetic_decoder_state_dict(geo: EncoderGeometry, seed: int = 0, fast: bool = False) -> StateDict:
+    """Seeded ``decoder.*`` tensors of a Whisper checkpoint (HF names and shapes; ``proj_out`` is tied to ``embed_tokens``, so it has no
+    tensor).  Scales chosen so that greedy decoding carries signal: token embeddings of N(0, 0.08) and learned positions of N(0, 1), so
+    that a step's output follows the position and the attended context rather than repeating the token it was fed (tied embeddings make
+    a large E[t] . E[t] win the next argmax); q / k projections at gain 1.6 (peaky attention), v / out projections at 0.7 in both
+    attentions."""
+    r = _Rng(seed, fast)
+    sd: StateDict = {}
+    D, Fd = geo.hidden, geo.decoder_ffn_dim
+    sd["decoder.embed_tokens.weight"] = r.normal(geo.decoder_vocab_size, D, std=0.08)
+    sd["decoder.embed_positions.weight"] = r.normal(geo.max_target_positions, D, std=1.0)
+    for i in range(geo.decoder_layers):
+        p = f"decoder.layers.{i}"
+        for a in (".self_attn", ".encoder_attn"):
+            _layer_norm(sd, r, p + a + "_layer_norm", D)
+            _linear(sd, r, p + a + ".q_proj", D, D, gain=1.6)
+            _linear(sd, r, p + a + ".k_proj", D, D, gain=1.6, bias=False)
+            _linear(sd, r, p + a + ".v_proj", D, D)
+            _linear(sd, r, p + a + ".out_proj", D, D)
+        _layer_norm(sd, r, p + ".final_layer_norm", D)
+        _linear(sd, r, p + ".fc1", Fd, D)
+        _linear(sd, r, p + ".fc2", D, Fd)
+    _layer_norm(sd, r, "decoder.layer_norm", D)
+    return sd
+
+
 def synthetic_state_dict(geo: EncoderGeometry, seed: int = 0, fast: bool = False) -> StateDict:
     r = _Rng(seed, fast)
     sd: StateDict = {}
