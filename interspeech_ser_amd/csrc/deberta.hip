@@ -6,7 +6,7 @@
 //                         (HF modeling_deberta_v2.py DebertaV2Embeddings: no absolute positions / token types in v3)
 //   ser_deberta_attention disentangled attention (DisentangledSelfAttention.forward + disentangled_attention_bias):
 //                         softmax((Qc Kc^T + c2p + p2c) / sqrt(3 dh)) V with the "both tokens real" mask
-#include "ser_common.h"
+#include "row_common.h"
 
 // ---------------------------------------------------------------------------------------------- embeddings
 // f16 planes: the stored values are folded into the fp16 range guard (rflag, may be NULL); a padded row stores zeros, so whatever its
@@ -22,41 +22,11 @@ __global__ __launch_bounds__(256) void embed_ln_masked_kernel(const int32_t* __r
     if (row >= rows) return;
     const int seq = row / T, t = row - seq * T;
     const bool real = t < key_lens[seq];
-    const float* w = wemb + (int64_t)ids[row] * D;
     f32x4 v[8];
-    float s = 0.f, ramax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-            v[i] = *(const f32x4*)(w + c);
-            s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-        } else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-            const f32x4 gg = *(const f32x4*)(g + c), bb = *(const f32x4*)(b + c);
-            f32x4 y;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) y[j] = real ? (v[i][j] - mean) * rstd * gg[j] + bb[j] : 0.f;   // embeddings * mask
-            if (of) *(f32x4*)(of + (int64_t)row * D + c) = y;
-            if (oa) store_act4<MODE>(oa + (int64_t)row * D + c, plane, y[0], y[1], y[2], y[3]);
-            if constexpr (mode_traits<MODE>::f16) { if (oa) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); } }
-        }
-    }
+    const float mean = row_load(v, row_ptr{wemb + (int64_t)ids[row] * D}, lane, D);
+    const float rstd = row_rstd(v, mean, eps, lane, D);
+    const float ramax = row_ln_store<MODE>(v, mean, rstd, g, b, 0, real /* embeddings * mask */, of ? of + (int64_t)row * D : nullptr,
+                                           oa ? oa + (int64_t)row * D : nullptr, plane, lane, D);
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
 }
 
@@ -69,15 +39,10 @@ extern "C" int ser_embed_ln_masked_flagged(const int32_t* ids, const float* word
     if (mode != SER_MODE_BF16 && mode != SER_MODE_FP32X && mode != SER_MODE_FP16X) return ser_fail(-3, "ser_embed_ln_masked: bad mode");
     const int rows = B * T;
     dim3 grid((rows + 3) / 4), block(256);
-    if (mode == SER_MODE_FP32X)
-        hipLaunchKernelGGL(embed_ln_masked_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b,
-                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
-    else if (mode == SER_MODE_FP16X)
-        hipLaunchKernelGGL(embed_ln_masked_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b,
-                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
-    else
-        hipLaunchKernelGGL(embed_ln_masked_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b,
-                           eps, key_lens, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
+    ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(mode, [&](auto M) {
+        hipLaunchKernelGGL(embed_ln_masked_kernel<M()>, grid, block, 0, (hipStream_t)stream, ids, word_emb, ln_g, ln_b, eps, key_lens,
+                           out_f32, (unsigned short*)out_act, out_plane_stride, T, D, rows, range_flag);
+    });
     return ser_check_launch("ser_embed_ln_masked");
 }
 
@@ -201,16 +166,11 @@ extern "C" int ser_pack_rows_flagged(const float* x, int64_t ldx, int B, int T, 
         return ser_fail(-1, "ser_pack_rows: bad arguments");
     const int64_t total = (int64_t)B * T * (D / 4);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (mode == SER_MODE_FP32X)
-        hipLaunchKernelGGL(pack_rows_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo,
-                           (unsigned short*)out, ldo, out_plane_stride, total, range_flag);
-    else if (mode == SER_MODE_BF16)
-        hipLaunchKernelGGL(pack_rows_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo,
-                           (unsigned short*)out, ldo, out_plane_stride, total, range_flag);
-    else if (mode == SER_MODE_FP16X)
-        hipLaunchKernelGGL(pack_rows_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo,
-                           (unsigned short*)out, ldo, out_plane_stride, total, range_flag);
-    else return ser_fail(-2, "ser_pack_rows: bad mode %d", mode);
+    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16X>(mode, [&](auto M) {
+            hipLaunchKernelGGL(pack_rows_kernel<M()>, grid, block, 0, (hipStream_t)stream, x, ldx, T, D, halo, (unsigned short*)out, ldo,
+                               out_plane_stride, total, range_flag);
+        }))
+        return ser_fail(-2, "ser_pack_rows: bad mode %d", mode);
     return ser_check_launch("ser_pack_rows");
 }
 
@@ -239,16 +199,11 @@ extern "C" int ser_zero_padded_rows(float* x, int64_t ldx, void* act, int64_t ld
         return ser_fail(-1, "ser_zero_padded_rows: bad arguments");
     const int64_t total = (int64_t)B * T * (D / 4);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (mode == SER_MODE_FP32X)
-        hipLaunchKernelGGL(zero_padded_rows_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, x, ldx,
-                           (unsigned short*)act, lda, plane_stride, key_lens, T, D, total);
-    else if (mode == SER_MODE_BF16)
-        hipLaunchKernelGGL(zero_padded_rows_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, x, ldx,
-                           (unsigned short*)act, lda, plane_stride, key_lens, T, D, total);
-    else if (mode == SER_MODE_FP16X)
-        hipLaunchKernelGGL(zero_padded_rows_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, x, ldx,
-                           (unsigned short*)act, lda, plane_stride, key_lens, T, D, total);
-    else return ser_fail(-2, "ser_zero_padded_rows: bad mode %d", mode);
+    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16X>(mode, [&](auto M) {
+            hipLaunchKernelGGL(zero_padded_rows_kernel<M()>, grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned short*)act, lda,
+                               plane_stride, key_lens, T, D, total);
+        }))
+        return ser_fail(-2, "ser_zero_padded_rows: bad mode %d", mode);
     return ser_check_launch("ser_zero_padded_rows");
 }
 

@@ -1,7 +1,7 @@
 // HBM-bound row kernels: waveform normalisation (K1), conv layer 0 + LayerNorm + GELU (K2),
 // LayerNorm (K6), WavLM bias table / GRU gate (K8), state mean (K15), bf16 splitting.
 // One 64-lane wave owns one row; reductions are DPP/shuffle butterflies, loads/stores 16 B/lane.
-#include "ser_common.h"
+#include "row_common.h"
 
 // ------------------------------------------------------------------------------- K1
 // One 1024-thread block per utterance, three sweeps (sum, squared deviation, write).
@@ -127,13 +127,10 @@ extern "C" int ser_wave_frames_v(const ser_wave_frames_args* a, void* stream) {
     int blocks = ((total_rows + B - 1) / B + 31) / 32;
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
-#define SER_WF(M_) hipLaunchKernelGGL(wave_frames_kernel<M_>, dim3(blocks, B), dim3(256), 0, s, wav, sample_offs, frame_offs, \
-                                      (const double*)work, (unsigned short*)out, out_plane_stride, k, stride, a->range_flag, \
-                                      a->no_norm)
-    if (mode == SER_MODE_FP32X) SER_WF(SER_MODE_FP32X);
-    else if (mode == SER_MODE_FP16X) SER_WF(SER_MODE_FP16X);
-    else SER_WF(SER_MODE_BF16);
-#undef SER_WF
+    ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(mode, [&](auto M) {
+        hipLaunchKernelGGL(wave_frames_kernel<M()>, dim3(blocks, B), dim3(256), 0, s, wav, sample_offs, frame_offs, (const double*)work,
+                           (unsigned short*)out, out_plane_stride, k, stride, a->range_flag, a->no_norm);
+    });
     return ser_check_launch("ser_wave_frames");
 }
 
@@ -246,29 +243,23 @@ extern "C" int ser_conv0_ln_gelu(const float* wav_norm, const int64_t* sample_of
     dim3 grid(blocks, B), block(256);
     hipStream_t s = (hipStream_t)stream;
     unsigned short* o = (unsigned short*)out;
-#define LAUNCH2(CPL, KT)                                                                                        \
-    do {                                                                                                        \
-        if (mode == SER_MODE_BF16)                                                                              \
-            hipLaunchKernelGGL((conv0_kernel<CPL, KT, SER_MODE_BF16>), grid, block, 0, s, wav_norm, sample_offs, \
-                               frame_offs, w, bias, ln_g, ln_b, o, out_plane_stride, k, stride, rpg);          \
-        else                                                                                                    \
-            hipLaunchKernelGGL((conv0_kernel<CPL, KT, SER_MODE_FP32X>), grid, block, 0, s, wav_norm, sample_offs, \
-                               frame_offs, w, bias, ln_g, ln_b, o, out_plane_stride, k, stride, rpg);          \
-    } while (0)
-#define LAUNCH(CPL)                                  \
-    do {                                             \
-        if (k <= 10) LAUNCH2(CPL, 10);               \
-        else LAUNCH2(CPL, 16);                       \
-    } while (0)
+    auto launch = [&](auto CPL, auto KT) {                       // channels per lane, bound on the kernel width
+        ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X>(mode, [&](auto M) {
+            hipLaunchKernelGGL((conv0_kernel<CPL(), KT(), M()>), grid, block, 0, s, wav_norm, sample_offs, frame_offs, w, bias, ln_g, ln_b,
+                               o, out_plane_stride, k, stride, rpg);
+        });
+    };
+    auto launch_k = [&](auto CPL) {
+        if (k <= 10) launch(CPL, std::integral_constant<int, 10>{});
+        else launch(CPL, std::integral_constant<int, 16>{});
+    };
     switch (C) {
-        case 64: LAUNCH(1); break;
-        case 128: LAUNCH(2); break;
-        case 256: LAUNCH(4); break;
-        case 512: LAUNCH(8); break;
+        case 64: launch_k(std::integral_constant<int, 1>{}); break;
+        case 128: launch_k(std::integral_constant<int, 2>{}); break;
+        case 256: launch_k(std::integral_constant<int, 4>{}); break;
+        case 512: launch_k(std::integral_constant<int, 8>{}); break;
         default: return ser_fail(-4, "ser_conv0: C=%d unsupported (64/128/256/512)", C);
     }
-#undef LAUNCH
-#undef LAUNCH2
     return ser_check_launch("ser_conv0_ln_gelu");
 }
 
@@ -283,42 +274,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (int64_t)row * ldx;
     f32x4 v[8];
-    float s = 0.f, ramax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) { v[i] = *(const f32x4*)(xr + c); s += v[i][0] + v[i][1] + v[i][2] + v[i][3]; }
-        else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-            const f32x4 gg = *(const f32x4*)(g + c), bb = *(const f32x4*)(b + c);
-            f32x4 y;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float t = (v[i][j] - mean) * rstd * gg[j] + bb[j];
-                y[j] = gelu ? gelu_erf(t) : t;
-            }
-            if (of) *(f32x4*)(of + (int64_t)row * ldof + c) = y;
-            if (oa) store_act4<MODE>(oa + (int64_t)row * ldoa + c, plane, y[0], y[1], y[2], y[3]);
-            if constexpr (mode_traits<MODE>::f16) { if (oa) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); } }
-        }
-    }
+    const float mean = row_load(v, row_ptr{x + (int64_t)row * ldx}, lane, D);
+    const float rstd = row_rstd(v, mean, eps, lane, D);
+    const float ramax = row_ln_store<MODE>(v, mean, rstd, g, b, gelu, true, of ? of + (int64_t)row * ldof : nullptr,
+                                           oa ? oa + (int64_t)row * ldoa : nullptr, plane, lane, D);
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
 }
 
@@ -331,14 +291,11 @@ extern "C" int ser_layernorm_v(const ser_layernorm_args* a, void* stream) {
     if (D % 4 || D > 2048 || D <= 0 || rows <= 0) return ser_fail(-2, "ser_layernorm: D=%d rows=%d unsupported", D, rows);
     if ((ldx % 4) || (out_f32 && ldo_f32 % 4) || (out_act && ldo_act % 4)) return ser_fail(-3, "ser_layernorm: pitches must be multiples of 4");
     dim3 grid((rows + 3) / 4), block(256);
-#define SER_LN(M_) hipLaunchKernelGGL(layernorm_kernel<M_>, grid, block, 0, (hipStream_t)stream, x, ldx, g, b, eps, gelu, out_f32, ldo_f32, \
-                                      (unsigned short*)out_act, ldo_act, out_plane_stride, rows, D, a->range_flag)
-    if (mode == SER_MODE_FP32X) SER_LN(SER_MODE_FP32X);
-    else if (mode == SER_MODE_BF16) SER_LN(SER_MODE_BF16);
-    else if (mode == SER_MODE_FP16) SER_LN(SER_MODE_FP16);
-    else if (mode == SER_MODE_FP16X) SER_LN(SER_MODE_FP16X);
-    else return ser_fail(-4, "ser_layernorm: bad mode %d", mode);
-#undef SER_LN
+    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16, SER_MODE_FP16X>(mode, [&](auto M) {
+            hipLaunchKernelGGL(layernorm_kernel<M()>, grid, block, 0, (hipStream_t)stream, x, ldx, g, b, eps, gelu, out_f32, ldo_f32,
+                               (unsigned short*)out_act, ldo_act, out_plane_stride, rows, D, a->range_flag);
+        }))
+        return ser_fail(-4, "ser_layernorm: bad mode %d", mode);
     return ser_check_launch("ser_layernorm");
 }
 
@@ -364,30 +321,12 @@ __global__ __launch_bounds__(256) void pos_ln_kernel(const float* __restrict__ x
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (int64_t)row * ldx;
     f32x4 v[8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) { v[i] = *(const f32x4*)(xr + c); s += v[i][0] + v[i][1] + v[i][2] + v[i][3]; }
-        else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    float mean = wave_sum(s) / (float)D, q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
-        }
-    }
-    float rstd = rsqrtf(wave_sum(q) / (float)D + eps_pos);
+    float mean = row_load(v, row_ptr{x + (int64_t)row * ldx}, lane, D);
+    float rstd = row_rstd(v, mean, eps_pos, lane, D);
     // y = gelu(LN(x)) (+ residual) in place
-    s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
+    float s = 0.f, ramax = 0.f;
+    row_chunks(lane, [&](int i, int c) {
         if (c < D) {
             f32x4 r = (f32x4){0.f, 0.f, 0.f, 0.f};
             if constexpr (LAST) r = *(const f32x4*)(res + (int64_t)row * ldr + c);
@@ -395,45 +334,20 @@ __global__ __launch_bounds__(256) void pos_ln_kernel(const float* __restrict__ x
             for (int j = 0; j < 4; ++j) v[i][j] = gelu_erf((v[i][j] - mean) * rstd) + r[j];
             s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
         }
-    }
-    float ramax = 0.f;
+    });
     if constexpr (!LAST) {
         unsigned short* orow = oa + (int64_t)(rowmap ? rowmap[row] : row) * ldoa;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = i * 256 + lane * 4;
+        row_chunks(lane, [&](int i, int c) {
             if (c < D) {
                 store_act4<MODE>(orow + c, plane, v[i][0], v[i][1], v[i][2], v[i][3]);
                 if constexpr (mode_traits<MODE>::f16) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, v[i][j]); }
             }
-        }
+        });
     } else {
         mean = wave_sum(s) / (float)D;
-        q = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = i * 256 + lane * 4;
-            if (c < D) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
-            }
-        }
-        rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = i * 256 + lane * 4;
-            if (c < D) {
-                const f32x4 gg = *(const f32x4*)(g + c), bb = *(const f32x4*)(b + c);
-                f32x4 y;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * gg[j] + bb[j];
-                *(f32x4*)(of + (int64_t)row * ldof + c) = y;
-                if (oa) {
-                    store_act4<MODE>(oa + (int64_t)row * ldoa + c, plane, y[0], y[1], y[2], y[3]);
-                    if constexpr (mode_traits<MODE>::f16) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); }
-                }
-            }
-        }
+        rstd = row_rstd(v, mean, eps, lane, D);
+        ramax = row_ln_store<MODE>(v, mean, rstd, g, b, 0, true, of + (int64_t)row * ldof, oa ? oa + (int64_t)row * ldoa : nullptr, plane,
+                                   lane, D);
     }
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
 }
@@ -449,17 +363,13 @@ extern "C" int ser_pos_ln_v(const ser_pos_ln_args* a, void* stream) {
     if ((a->ldx % 4) || (a->out_act && a->ldo_act % 4) || (last && (a->ldr % 4 || a->ldo_f32 % 4)))
         return ser_fail(-3, "ser_pos_ln: pitches must be multiples of 4");
     dim3 grid((rows + 3) / 4), block(256);
-#define SER_PL(M_, L_) hipLaunchKernelGGL((pos_ln_kernel<M_, L_>), grid, block, 0, (hipStream_t)stream, a->x, a->ldx, \
-                                          (unsigned short*)a->out_act, a->ldo_act, a->out_plane_stride, a->out_rowmap, a->residual, a->ldr, \
-                                          a->g, a->b, a->out_f32, a->ldo_f32, a->eps_pos, a->eps, rows, D, a->range_flag)
-#define SER_PL2(M_) do { if (last) SER_PL(M_, true); else SER_PL(M_, false); } while (0)
-    if (mode == SER_MODE_FP32X) SER_PL2(SER_MODE_FP32X);
-    else if (mode == SER_MODE_BF16) SER_PL2(SER_MODE_BF16);
-    else if (mode == SER_MODE_FP16) SER_PL2(SER_MODE_FP16);
-    else if (mode == SER_MODE_FP16X) SER_PL2(SER_MODE_FP16X);
-    else return ser_fail(-4, "ser_pos_ln: bad mode %d", mode);
-#undef SER_PL2
-#undef SER_PL
+    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16, SER_MODE_FP16X>(mode, [&](auto M) {
+            auto kernel = last ? pos_ln_kernel<M(), true> : pos_ln_kernel<M(), false>;
+            hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a->x, a->ldx, (unsigned short*)a->out_act, a->ldo_act,
+                               a->out_plane_stride, a->out_rowmap, a->residual, a->ldr, a->g, a->b, a->out_f32, a->ldo_f32, a->eps_pos,
+                               a->eps, rows, D, a->range_flag);
+        }))
+        return ser_fail(-4, "ser_pos_ln: bad mode %d", mode);
     return ser_check_launch("ser_pos_ln");
 }
 
@@ -477,21 +387,10 @@ __global__ __launch_bounds__(256) void row_center_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    float ramax = 0.f;
-    const float* xr = x + (int64_t)row * ldx;
     f32x4 v[8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) { v[i] = *(const f32x4*)(xr + c); s += v[i][0] + v[i][1] + v[i][2] + v[i][3]; }
-        else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f, r1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
+    const float mean = row_load(v, row_ptr{x + (int64_t)row * ldx}, lane, D);
+    float q = 0.f, r1 = 0.f, ramax = 0.f;
+    row_chunks(lane, [&](int i, int c) {
         if (c < D) {
             f32x4 d;
 #pragma unroll
@@ -507,7 +406,7 @@ __global__ __launch_bounds__(256) void row_center_kernel(const float* __restrict
                                                      oscale + row, oscale_ld, false));
             }
         }
-    }
+    });
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
     q = wave_sum(q);
     r1 = wave_sum(r1);
@@ -528,15 +427,11 @@ extern "C" int ser_row_center_v(const ser_row_center_args* a, void* stream) {
     if (mode == SER_MODE_FP16M && (!a->out_scale || a->out_scale_ld < rows || (D % 64) || (ldo_act % 64)))
         return ser_fail(-5, "ser_row_center: FP16M needs out_scale (out_scale_ld >= rows), D %% 64 == 0, ldo_act %% 64 == 0");
     dim3 grid((rows + 3) / 4), block(256);
-#define SER_RC(M_) hipLaunchKernelGGL(row_center_kernel<M_>, grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned short*)out_act, ldo_act, \
-                                      out_plane_stride, stats, stat_groups, shift, rows, D, a->out_scale, a->out_scale_ld, a->range_flag)
-    if (mode == SER_MODE_FP32X) SER_RC(SER_MODE_FP32X);
-    else if (mode == SER_MODE_BF16) SER_RC(SER_MODE_BF16);
-    else if (mode == SER_MODE_FP16) SER_RC(SER_MODE_FP16);
-    else if (mode == SER_MODE_FP16X) SER_RC(SER_MODE_FP16X);
-    else if (mode == SER_MODE_FP16M) SER_RC(SER_MODE_FP16M);
-    else return ser_fail(-4, "ser_row_center: bad mode %d", mode);
-#undef SER_RC
+    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16, SER_MODE_FP16X, SER_MODE_FP16M>(mode, [&](auto M) {
+            hipLaunchKernelGGL(row_center_kernel<M()>, grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned short*)out_act, ldo_act,
+                               out_plane_stride, stats, stat_groups, shift, rows, D, a->out_scale, a->out_scale_ld, a->range_flag);
+        }))
+        return ser_fail(-4, "ser_row_center: bad mode %d", mode);
     return ser_check_launch("ser_row_center");
 }
 
@@ -571,40 +466,10 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
     const float* w = wemb + (int64_t)id * D;
     const float* pe = pemb + (int64_t)pos * D;
     f32x4 v[8];
-    float s = 0.f, ramax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-            const f32x4 a = *(const f32x4*)(w + c), p4 = *(const f32x4*)(pe + c), t4 = *(const f32x4*)(temb + c);
-            v[i] = (a + p4) + t4;
-            s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-        } else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; q += d * d; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = i * 256 + lane * 4;
-        if (c < D) {
-            const f32x4 gg = *(const f32x4*)(g + c), bb = *(const f32x4*)(b + c);
-            f32x4 y;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * gg[j] + bb[j];
-            if (of) *(f32x4*)(of + (int64_t)row * D + c) = y;
-            if (oa) store_act4<MODE>(oa + (int64_t)row * D + c, plane, y[0], y[1], y[2], y[3]);
-            if constexpr (mode_traits<MODE>::f16) { if (oa) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, y[j]); } }
-        }
-    }
+    const float mean = row_load(v, row_sum3{w, pe, temb}, lane, D);
+    const float rstd = row_rstd(v, mean, eps, lane, D);
+    const float ramax = row_ln_store<MODE>(v, mean, rstd, g, b, 0, true, of ? of + (int64_t)row * D : nullptr,
+                                           oa ? oa + (int64_t)row * D : nullptr, plane, lane, D);
     if constexpr (mode_traits<MODE>::f16) range_report(rflag, ramax);
 }
 
@@ -618,15 +483,10 @@ extern "C" int ser_embed_ln_flagged(const int32_t* ids, const float* word_emb, c
     if (mode != SER_MODE_BF16 && mode != SER_MODE_FP32X && mode != SER_MODE_FP16X) return ser_fail(-3, "ser_embed_ln: bad mode");
     const int rows = B * T;
     dim3 grid((rows + 3) / 4), block(256);
-    if (mode == SER_MODE_FP32X)
-        hipLaunchKernelGGL(embed_ln_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb,
-                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
-    else if (mode == SER_MODE_FP16X)
-        hipLaunchKernelGGL(embed_ln_kernel<SER_MODE_FP16X>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb,
-                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
-    else
-        hipLaunchKernelGGL(embed_ln_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb,
-                           ln_g, ln_b, eps, out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
+    ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(mode, [&](auto M) {
+        hipLaunchKernelGGL(embed_ln_kernel<M()>, grid, block, 0, (hipStream_t)stream, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps,
+                           out_f32, (unsigned short*)out_act, out_plane_stride, T, D, pad_id, rows, range_flag);
+    });
     return ser_check_launch("ser_embed_ln");
 }
 
@@ -715,12 +575,11 @@ extern "C" int ser_wavlm_gate(const void* x_ln, int64_t ldx, int64_t plane_strid
     if ((dh != 8 && dh != 16 && dh != 32 && dh != 64 && dh != 128) || rows <= 0 || (ldx % 8))
         return ser_fail(-2, "ser_wavlm_gate: dh=%d unsupported (8..128, power of two)", dh);
     dim3 grid((rows + 3) / 4), block(256);
-    if (mode == SER_MODE_FP32X)
-        hipLaunchKernelGGL(gate_kernel<SER_MODE_FP32X>, grid, block, 0, (hipStream_t)stream, (const unsigned short*)x_ln,
-                           ldx, plane_stride, w8, b8, gru_const, gate, rows, H, dh);
-    else
-        hipLaunchKernelGGL(gate_kernel<SER_MODE_BF16>, grid, block, 0, (hipStream_t)stream, (const unsigned short*)x_ln,
-                           ldx, plane_stride, w8, b8, gru_const, gate, rows, H, dh);
+    auto launch = [&](auto M) {
+        hipLaunchKernelGGL(gate_kernel<M()>, grid, block, 0, (hipStream_t)stream, (const unsigned short*)x_ln, ldx, plane_stride, w8, b8,
+                           gru_const, gate, rows, H, dh);
+    };
+    if (!ser_with_mode<SER_MODE_FP32X>(mode, launch)) launch(std::integral_constant<int, SER_MODE_BF16>{});   // any other mode: the bf16 plane
     return ser_check_launch("ser_wavlm_gate");
 }
 
@@ -804,10 +663,8 @@ extern "C" int ser_select_rows_v(const ser_select_rows_args* a, void* stream) {
     if (a->out_f32 && (a->ldo_f32 < a->D || (a->ldo_f32 % 4) || ((uintptr_t)a->out_f32 & 15)))
         return ser_fail(-6, "ser_select_rows: ldo_f32=%lld (>= D, multiple of 4, 16-byte aligned)", (long long)a->ldo_f32);
     if (a->max_rows <= 0) return ser_fail(-7, "ser_select_rows: max_rows=%d", a->max_rows);
-    if (a->mode == SER_MODE_FP32X) select_rows_launch<SER_MODE_FP32X>(a, stream);
-    else if (a->mode == SER_MODE_BF16) select_rows_launch<SER_MODE_BF16>(a, stream);
-    else if (a->mode == SER_MODE_FP16X) select_rows_launch<SER_MODE_FP16X>(a, stream);
-    else return ser_fail(-8, "ser_select_rows: bad mode %d", a->mode);
+    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16X>(a->mode, [&](auto M) { select_rows_launch<M()>(a, stream); }))
+        return ser_fail(-8, "ser_select_rows: bad mode %d", a->mode);
     return ser_check_launch("ser_select_rows_v");
 }
 
@@ -902,12 +759,10 @@ extern "C" int ser_pack_act_v(const ser_pack_act_args* a, void* stream) {
         return ser_fail(-2, "ser_pack_act: mode %d (SER_MODE_BF16, SER_MODE_FP32X or SER_MODE_FP16X)", mode);
     const int64_t total = (int64_t)B * (T + 2 * halo) * (C / 4);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define SER_PA(M_) hipLaunchKernelGGL(pack_act_kernel<M_>, grid, block, 0, (hipStream_t)stream, x, B, C, T, halo, (unsigned short*)out, ldo, \
-                                      out_plane_stride, a->range_flag)
-    if (mode == SER_MODE_FP32X) SER_PA(SER_MODE_FP32X);
-    else if (mode == SER_MODE_FP16X) SER_PA(SER_MODE_FP16X);
-    else if (mode == SER_MODE_BF16) SER_PA(SER_MODE_BF16);
-#undef SER_PA
+    ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(mode, [&](auto M) {
+        hipLaunchKernelGGL(pack_act_kernel<M()>, grid, block, 0, (hipStream_t)stream, x, B, C, T, halo, (unsigned short*)out, ldo,
+                           out_plane_stride, a->range_flag);
+    });
     return ser_check_launch("ser_pack_act");
 }
 
