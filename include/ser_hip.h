@@ -139,7 +139,10 @@ typedef struct ser_gemm_args {
     const float*   ln_gamma;       /* [N] or NULL */
     const float*   ln_beta;        /* [N] */
     float          ln_eps;
-    int32_t        tile_cfg;       /* 0 = auto; 1 = 128x128, 2 = 256x128, 3 = 256x256 block tile */
+    int32_t        tile_cfg;       /* 0 = auto; 1 = 128x128, 2 = 256x128, 3 = 256x256 block tile -- a request the mode families treat
+                                    * differently.  BF16 / FP16: honoured, unless ln_gamma is set (the row count alone picks the LayerNorm
+                                    * tile).  FP16M: 2 and 3 are honoured; 1 only switches the automatic choice off, which leaves 128x128.
+                                    * FP32X / FP16X: ignored, the automatic choice stands.  Values outside 0..3 are refused (-13). */
     /* DEFERRED LayerNorm of the A operand (encoder layers: LN -> Linear, HF modeling_wavlm.py:357-358,
      * 366): the LayerNorm kernel and its HBM round trip disappear.  With W' = W * gamma (folded at load),
      *   LN(x) W^T + b = rstd_m * (x W'^T - mu_m * colsum(W')_n) + (beta W^T + b)_n

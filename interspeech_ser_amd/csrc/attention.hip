@@ -27,6 +27,7 @@
 //     high-occupancy arm (OCC: one K/V buffer, fragments read just in time, 128 registers, four blocks per CU) that the launcher picks
 //     for single-plane 64-wide launches of 513 .. 1 024 blocks -- see the template's comment and DESIGN.md section 5.
 #include "attn_common.h"
+#include "launch_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <atomic>
@@ -672,16 +673,15 @@ void attention_kernel(const AttnParams p) {
     }
 }
 
-template <int DHP, int MODE, bool PRE, bool TBL, int NWV = 4, bool B2D = false, bool GB = false, bool OCC = false>
-static int launch_attention(const AttnParams& p, dim3 grid, size_t lds, hipStream_t s) {
-    auto k = attention_kernel<DHP, MODE, PRE, TBL, NWV, B2D, GB, OCC>;
-    static std::atomic<bool> ready{false};          // several host threads launch (see gemm.hip launch_mode)
-    if (lds > 65536 && !ready.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return ser_fail((int)e, "ser_attention: cannot raise dynamic LDS");
-        ready.store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, p);
+static_assert(ABKV == ATTN_BKV && ABQ == 32 * ATTN_NWV, "launch_plan.h plans for the kernel's tile sizes");
+
+template <int DHP, int MODE, bool PRE, bool TBL, bool B2D, bool GB, bool OCC>
+static int launch_attention(const AttnParams& p, const attn_launch& pl, hipStream_t s) {
+    auto k = attention_kernel<DHP, MODE, PRE, TBL, ATTN_NWV, B2D, GB, OCC>;
+    static std::atomic<bool> ready{false};          // per instantiation
+    if (pl.lds > 65536)
+        if (hipError_t e = ser_lds_optin(k, 160 * 1024, ready)) return ser_fail((int)e, "ser_attention: cannot raise dynamic LDS");
+    hipLaunchKernelGGL(k, dim3(pl.grid, 1, 1), dim3(64 * ATTN_NWV), pl.lds, s, p);
     return ser_check_launch("ser_attention");
 }
 
@@ -699,131 +699,35 @@ extern "C" int ser_attention(const void* qkv, int64_t ld, int64_t plane_stride, 
 }
 
 extern "C" int ser_attention_v(const ser_attention_args* args, void* stream) {
-    if (!args) return ser_fail(-1, "ser_attention: null pointer");
-    const void* qkv = args->qkv; const int64_t ld = args->ld, plane_stride = args->plane_stride;
-    const int q_col = args->q_col, k_col = args->k_col, v_col = args->v_col, B = args->B, max_frames = args->max_frames;
-    const int32_t* frame_offs = args->frame_offs; const float* table = args->table; const int table_T = args->table_T;
-    const float* gate = args->gate; void* out = args->out; const int64_t ldo = args->ldo, out_plane_stride = args->out_plane_stride;
-    const int H = args->H, dh = args->dh, mode = args->mode, gate_col = args->gate_col; const float scale = args->scale;
-    const float* gru_const = args->gru_const; const int32_t* key_lens = args->key_lens;
-    const float* bias2d = args->bias2d; const int64_t bias2d_ld = args->bias2d_ld;
-    if (!qkv || !frame_offs || !out) return ser_fail(-1, "ser_attention: null pointer");
-    if (args->gate_x) {
-        if (!table || !gru_const || gate || !args->gate_stat || !args->gate_w || !args->gate_cb)
-            return ser_fail(-13, "ser_attention: gate_x needs table, gru_const, gate_stat, gate_w, gate_cb and no gate[]");
-        const int np_ = (args->mode == SER_MODE_FP32X || args->mode == SER_MODE_FP16X || args->mode == SER_MODE_FP16Q) ? 2 : 1;
-        if ((args->gate_x_ld % 8) || (args->gate_x_plane_stride % 8) || (args->gate_w_plane_stride % 8) || args->gate_x_planes != np_ || (args->dh % 8))
-            return ser_fail(-13, "ser_attention: gate_x / gate_w pitch, or gate_x_planes != the planes of mode %d", args->mode);
-    }
-    if (args->out_mode && args->out_mode != SER_MODE_FP16M) return ser_fail(-14, "ser_attention: out_mode %d (0 or SER_MODE_FP16M)", args->out_mode);
-    if (args->out_mode == SER_MODE_FP16M &&
-        (args->mode != SER_MODE_FP16X || args->dh != 64 || !args->out_scale || (args->ldo % 64) || args->bias2d || args->out_scale_ld <= 0))
-        return ser_fail(-14, "ser_attention: SER_MODE_FP16M context rows need mode FP16X, head dim 64, out_scale, ldo %% 64 == 0 and no bias2d");
-    if (B <= 0 || H <= 0 || max_frames <= 0) return ser_fail(-2, "ser_attention: bad B/H/max_frames");
-    if (dh % 8 || dh < 8 || dh > 128) return ser_fail(-3, "ser_attention: head dim %d unsupported (multiple of 8, <= 128)", dh);
-    if ((ld % 8) || (ldo % 4) || (q_col % 8) || (k_col % 8) || (v_col % 8)) return ser_fail(-4, "ser_attention: misaligned pitches/columns");
-    if (mode < SER_MODE_BF16 || mode > SER_MODE_FP16Q) return ser_fail(-5, "ser_attention: bad mode %d", mode);
-    if ((table != nullptr) != (gate != nullptr || gru_const != nullptr))
-        return ser_fail(-6, "ser_attention: the bias table needs a gate (gate[] or gate_col + gru_const) and vice versa");
-    if (gate && gru_const) return ser_fail(-9, "ser_attention: give gate[] or gru_const, not both");
-    if (gru_const && !args->gate_x && (gate_col < 0 || (gate_col % 2))) return ser_fail(-10, "ser_attention: bad gate_col %d", gate_col);
-    if (table && table_T < max_frames) return ser_fail(-7, "ser_attention: bias table built for T=%d < max_frames=%d", table_T, max_frames);
-    if (bias2d) {
-        if (table || !key_lens || scale > 0.f || dh > 64 || mode == SER_MODE_FP16 || mode == SER_MODE_FP16Q)
-            return ser_fail(-11, "ser_attention: bias2d needs key_lens, a pre-scaled q (scale <= 0), dh <= 64, no table, bf16 / fp32x / fp16x");
-        if (bias2d_ld < max_frames || (bias2d_ld % ABKV))
-            return ser_fail(-12, "ser_attention: bias2d_ld=%lld must be a multiple of %d and >= max_frames", (long long)bias2d_ld, ABKV);
-    }
-    // padded head dim of the LDS images and MFMA loops: 64, 96 (head dims 72 .. 96: HuBERT-xlarge's 80 runs 6 + 6 k-steps and 3 output column
-    // blocks instead of the 8 + 8 and 4 of the 128-wide form it used through round 3) or 128
-    const int dhp = dh <= 64 ? 64 : (dh <= 96 ? 96 : 128);
-    const int np = (mode == SER_MODE_FP32X || mode == SER_MODE_FP16X || mode == SER_MODE_FP16Q) ? 2 : 1;      // planes of q / k
-    const int npv = (mode == SER_MODE_FP32X || mode == SER_MODE_FP16X) ? 2 : 1;                                 // planes of v
-    const int nwv = 4;
-    const int nch = ABKV * (dhp / 8) / (64 * nwv);
-    const int nq_tiles = (max_frames + 32 * nwv - 1) / (32 * nwv);
-    const unsigned nblocks = (unsigned)(((H * B + 7) / 8) * 8 * nq_tiles);
-    // high-occupancy form (see the kernel): single-plane 64-wide launches with more than two blocks per CU to place that fit ONE round at
-    // four per CU (measured: 16 x 16 heads x 300 / 499 frames and the ragged mix gain 8 - 11 %; Whisper's 1 920-block launches run several
-    // rounds either way and LOSE 1 - 3 % on their step with it: left on the low-occupancy form)
-    bool occ = dhp == 64 && np == 1 && !bias2d && nblocks > 2u * 256u && nblocks <= 4u * 256u;
-    int nbuf = (!occ && nch * (np + npv) <= 8) ? 2 : 1;
-    // copy stride == 16 (mod 64) floats: the 4 shifted copies x the 4 query phases of a ds_read_b128
-    // lane group then land on 16 distinct 4-bank slots (a multiple of 64 made them 2-way conflicts)
-    int bias_stride = 0;
-    if (table) {
-        bias_stride = ((max_frames + 32 * nwv + 2 * ABKV + 3 + 4) / 4) * 4;   // window of one query block (+ the 0..3 alignment slots), not all 2T-1 distances
-        bias_stride += (16 - (bias_stride & 63) + 64) & 63;
-    }
-    size_t lds = (size_t)nbuf * (np + npv) * ABKV * dhp * 2 + (size_t)4 * bias_stride * 4;
-    // ... and only while four blocks' LDS fit a CU: a long utterance's bias window (B = 1, ~8 000 frames: 1 008 blocks, 133 KiB of window) would
-    // otherwise take the single-buffer 128-register form at ONE block per CU, the slow combination
-    if (occ && lds > 40 * 1024) {
-        occ = false;
-        nbuf = (nch * (np + npv) <= 8) ? 2 : 1;
-        lds = (size_t)nbuf * (np + npv) * ABKV * dhp * 2 + (size_t)4 * bias_stride * 4;
-    }
-    // a bias window that does not fit (utterances beyond ~2 min; ~1.5 min in the two-plane modes): the table is read from global
-    // memory instead (GB forms: pre-scaled q, head dim <= 64 -- what the WavLM encoders use)
-    const bool gbias = table && lds > 160 * 1024 && scale <= 0.f && dhp == 64 && nwv == 4;
-    if (gbias) {                                                  // (the GB forms have no high-occupancy instantiation: double buffer)
-        occ = false;
-        nbuf = (nch * (np + npv) <= 8) ? 2 : 1;
-        bias_stride = 0;
-        lds = (size_t)nbuf * (np + npv) * ABKV * dhp * 2;
-    }
-    if (lds > 160 * 1024) return ser_fail(-8, "ser_attention: LDS need %zu > 160 KiB (max_frames=%d)", lds, max_frames);
+    attn_launch pl;
+    if (int rc = attn_plan(args, &pl)) return rc;
     AttnParams p;
-    p.qkv = (const unsigned short*)qkv; p.ld = ld; p.plane = plane_stride;
-    p.q_col = q_col; p.k_col = k_col; p.v_col = v_col;
-    p.frame_offs = frame_offs; p.key_lens = key_lens; p.table = table; p.table_T = table_T; p.gate = gate;
-    p.gru_const = gru_const; p.gate_col = gate_col;
+    p.qkv = (const unsigned short*)args->qkv; p.ld = args->ld; p.plane = args->plane_stride;
+    p.q_col = args->q_col; p.k_col = args->k_col; p.v_col = args->v_col;
+    p.frame_offs = args->frame_offs; p.key_lens = args->key_lens; p.table = args->table; p.table_T = args->table_T; p.gate = args->gate;
+    p.gru_const = args->gru_const; p.gate_col = args->gate_col;
     p.gx = (const unsigned short*)args->gate_x; p.gx_ld = args->gate_x_ld; p.gx_plane = args->gate_x_plane_stride;
     p.gx_planes = args->gate_x_planes; p.gstat = args->gate_stat; p.gw = (const unsigned short*)args->gate_w; p.gw_plane = args->gate_w_plane_stride;
     p.gcb = args->gate_cb;
-    p.out = (unsigned short*)out; p.ldo = ldo; p.out_plane = out_plane_stride;
-    p.H = H; p.dh = dh; p.bias_stride = bias_stride; p.scale = scale;
-    p.bias2d = bias2d; p.b2d_ld = bias2d_ld; p.b2d_T = max_frames;
+    p.out = (unsigned short*)args->out; p.ldo = args->ldo; p.out_plane = args->out_plane_stride;
+    p.H = args->H; p.dh = args->dh; p.bias_stride = pl.bias_stride; p.scale = args->scale;
+    p.bias2d = args->bias2d; p.b2d_ld = args->bias2d_ld; p.b2d_T = args->max_frames;
     p.out_scale = args->out_mode == SER_MODE_FP16M ? (unsigned*)args->out_scale : nullptr; p.out_scale_ld = args->out_scale_ld;
 #ifdef SER_ATTN_DBG
     p.dbg = (unsigned long long*)ser_attn_dbg_ptr;
 #endif
-    p.B = B; p.nq = (max_frames + 32 * nwv - 1) / (32 * nwv);
-    dim3 grid((unsigned)(((H * B + 7) / 8) * 8 * p.nq), 1, 1);
-    p.nitems = (int)grid.x;
+    p.B = args->B; p.nq = pl.nq;
+    p.nitems = (int)pl.grid;
     hipStream_t s = (hipStream_t)stream;
-    const bool pre = scale <= 0.f;
-#define SER_ATTN_O(D_, M_, O_) (pre ? (table ? launch_attention<D_, M_, true, true, 4, false, false, O_>(p, grid, lds, s) : launch_attention<D_, M_, true, false, 4, false, false, O_>(p, grid, lds, s)) \
-                                    : (table ? launch_attention<D_, M_, false, true, 4, false, false, O_>(p, grid, lds, s) : launch_attention<D_, M_, false, false, 4, false, false, O_>(p, grid, lds, s)))
-#define SER_ATTN(D_, M_) SER_ATTN_O(D_, M_, false)
-    if (gbias) {
-        switch (mode) {
-            case SER_MODE_BF16:  return launch_attention<64, SER_MODE_BF16, true, true, 4, false, true>(p, grid, lds, s);
-            case SER_MODE_FP16:  return launch_attention<64, SER_MODE_FP16, true, true, 4, false, true>(p, grid, lds, s);
-            case SER_MODE_FP32X: return launch_attention<64, SER_MODE_FP32X, true, true, 4, false, true>(p, grid, lds, s);
-            case SER_MODE_FP16X: return launch_attention<64, SER_MODE_FP16X, true, true, 4, false, true>(p, grid, lds, s);
-            default:             return launch_attention<64, SER_MODE_FP16Q, true, true, 4, false, true>(p, grid, lds, s);
-        }
-    }
-    if (bias2d)
-        return mode == SER_MODE_FP32X ? launch_attention<64, SER_MODE_FP32X, true, false, 4, true>(p, grid, lds, s)
-             : mode == SER_MODE_FP16X ? launch_attention<64, SER_MODE_FP16X, true, false, 4, true>(p, grid, lds, s)
-                                      : launch_attention<64, SER_MODE_BF16, true, false, 4, true>(p, grid, lds, s);
-#define SER_ATTN_D(M_) (dhp == 64 ? SER_ATTN(64, M_) : (dhp == 96 ? SER_ATTN(96, M_) : SER_ATTN(128, M_)))
-    if (occ) return mode == SER_MODE_FP16 ? SER_ATTN_O(64, SER_MODE_FP16, true) : SER_ATTN_O(64, SER_MODE_BF16, true);
-    if (mode == SER_MODE_FP16) return SER_ATTN_D(SER_MODE_FP16);
-    if (mode == SER_MODE_FP16X || mode == SER_MODE_FP16Q) {      // "f16a" / "f16q": the host always pre-scales q; only the PRE forms are built
-        if (!pre) return ser_fail(-13, "ser_attention: FP16X / FP16Q need a pre-scaled q (scale <= 0)");
-#define SER_ATTN_X(D_, M_) (table ? launch_attention<D_, M_, true, true>(p, grid, lds, s) : launch_attention<D_, M_, true, false>(p, grid, lds, s))
-#define SER_ATTN_XD(M_) (dhp == 64 ? SER_ATTN_X(64, M_) : (dhp == 96 ? SER_ATTN_X(96, M_) : SER_ATTN_X(128, M_)))
-        if (mode == SER_MODE_FP16X) return SER_ATTN_XD(SER_MODE_FP16X);
-        return SER_ATTN_XD(SER_MODE_FP16Q);
-#undef SER_ATTN_XD
-#undef SER_ATTN_X
-    }
-    if (np == 1) return SER_ATTN_D(SER_MODE_BF16);
-    return SER_ATTN_D(SER_MODE_FP32X);
-#undef SER_ATTN_D
-#undef SER_ATTN
-#undef SER_ATTN_O
+    int rc = -13;                                   // (never returned: attn_plan refuses the forms that are not built)
+    ser_with_mode<64, 96, 128>(pl.dhp, [&](auto D) {
+    ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16, SER_MODE_FP16X, SER_MODE_FP16Q>(pl.mode, [&](auto M) {
+    ser_with_bool(pl.pre, [&](auto PRE) { ser_with_bool(pl.tbl, [&](auto TBL) { ser_with_bool(pl.b2d, [&](auto B2D) {
+    ser_with_bool(pl.gb, [&](auto GB) { ser_with_bool(pl.occ, [&](auto OCC) {
+        constexpr int dhp = decltype(D)::value, mode = decltype(M)::value;
+        constexpr bool pre = decltype(PRE)::value, tbl = decltype(TBL)::value, b2d = decltype(B2D)::value, gb = decltype(GB)::value,
+                       occ = decltype(OCC)::value;
+        if constexpr (attn_form_built(dhp, mode, pre, tbl, b2d, gb, occ)) rc = launch_attention<dhp, mode, pre, tbl, b2d, gb, occ>(p, pl, s);
+    }); }); }); }); }); }); });
+    return rc;
 }

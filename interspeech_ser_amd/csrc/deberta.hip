@@ -262,10 +262,11 @@ extern "C" int ser_deberta_attention(const void* qkv, int64_t ld, int64_t plane_
     const size_t lds = (size_t)(2 * T * 64 + T * (T + 1)) * 4;
     const float scale = 1.0f / sqrtf(3.0f * (float)dh);
     auto k = mode == SER_MODE_FP32X ? deberta_attention_kernel<SER_MODE_FP32X> : deberta_attention_kernel<SER_MODE_BF16>;
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return ser_fail((int)e, "ser_deberta_attention: cannot raise dynamic LDS");
-    }
+    // raised once per kernel, so to what the longest sequence takes (T = 128: 128.5 KiB), not to this launch's bytes
+    static std::atomic<bool> ready[2] = {{false}, {false}};
+    if (lds > 65536)
+        if (hipError_t e = ser_lds_optin(k, (2 * 128 * 64 + 128 * 129) * 4, ready[mode == SER_MODE_FP32X]))
+            return ser_fail((int)e, "ser_deberta_attention: cannot raise dynamic LDS");
     hipLaunchKernelGGL(k, dim3((unsigned)(B * H)), dim3(128), lds, (hipStream_t)stream, (const unsigned short*)qkv, ld, plane_stride,
                        q_col, k_col, v_col, c2p, p2c, ldp, Nr, c2p_col, p2c_col, key_lens, (unsigned short*)out, ldo,
                        out_plane_stride, T, H, dh, scale);

@@ -5,7 +5,6 @@
 //   ser_xattn_v       ser_xattn_mh_v with heads = 1
 // The pooling and the classifier behind them (ser_attn_pool_v, ser_fusion_cls_v) share pool.hip's kernels.  ser_hip.h states the arithmetic.  No atomics on float data; every sum runs in an order fixed by the utterance alone.
 #include "ser_common.h"
-#include <atomic>
 
 // ================================================================================================ ser_gru_v
 // One block serves (group of <= 16 utterances, direction, cluster rank): it owns U = H / R hidden units (x 3 gates), i.e. 3 U rows of W_hh,
@@ -278,11 +277,7 @@ extern "C" int ser_gru_v(const ser_gru_args* a, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     auto k = R > 1 ? gru_kernel<true> : gru_kernel<false>;
     static std::atomic<bool> ready[2] = {{false}, {false}};
-    if (!ready[R > 1].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        if (e != hipSuccess) return ser_fail((int)e, "ser_gru: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready[R > 1].store(true, std::memory_order_release);
-    }
+    if (hipError_t e = ser_lds_optin(k, 160 * 1024 - 256, ready[R > 1])) return ser_fail((int)e, "ser_gru: hipFuncSetAttribute: %s", hipGetErrorString(e));
     gru_params p;
     p.gx = a->gx; p.ldgx = a->ldgx; p.whh = (const unsigned short*)a->whh; p.wplane = a->whh_plane_stride; p.bhh = a->bhh;
     p.offs = a->frame_offs; p.out = a->out; p.ldo = a->ldo;
@@ -460,20 +455,14 @@ static int xattn_run(const ser_xattn_mh_args* a, void* stream, const char* who) 
     const dim3 grid((unsigned)((a->max_q + XA_QT - 1) / XA_QT), (unsigned)a->B, (unsigned)a->heads);
     hipStream_t s = (hipStream_t)stream;
     static std::atomic<bool> ready[3] = {{false}, {false}, {false}};
-#define XA_LAUNCH(MODE, I)                                                                                                          \
-    {                                                                                                                               \
-        auto kern = xattn_kernel<MODE>;                                                                                             \
-        if (!ready[I].load(std::memory_order_acquire)) {                                                                            \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);          \
-            if (e != hipSuccess) return ser_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));                 \
-            ready[I].store(true, std::memory_order_release);                                                                        \
-        }                                                                                                                           \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);                                                                       \
-    }
-    if (a->mode == SER_MODE_BF16) XA_LAUNCH(SER_MODE_BF16, 0)
-    else if (a->mode == SER_MODE_FP32X) XA_LAUNCH(SER_MODE_FP32X, 1)
-    else XA_LAUNCH(SER_MODE_FP16X, 2)
-#undef XA_LAUNCH
+    const auto launch = [&](auto kern, std::atomic<bool>& rdy) {
+        const hipError_t e = ser_lds_optin(kern, 136 * 1024, rdy);
+        if (e == hipSuccess) hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
+        return e;
+    };
+    const hipError_t e = a->mode == SER_MODE_BF16 ? launch(xattn_kernel<SER_MODE_BF16>, ready[0])
+                       : a->mode == SER_MODE_FP32X ? launch(xattn_kernel<SER_MODE_FP32X>, ready[1]) : launch(xattn_kernel<SER_MODE_FP16X>, ready[2]);
+    if (e != hipSuccess) return ser_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
     return ser_check_launch(who);
 }
 

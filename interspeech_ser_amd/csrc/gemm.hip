@@ -3,11 +3,16 @@
 //   C[m,n] = sum_k A(m,k) * W[n,k]     A: act bf16 (1 or 2 planes), W: bf16 [N][K] (1 or 2 planes)
 //
 // gfx950 design
-//   * One kernel template, several tile configurations (host picks per shape):
+//   * One kernel template, twelve tile configurations (launch_plan.h: the table GEMM_TILE, and gemm_pick_tile chooses per shape):
+//     single-plane modes (BF16 / FP16 / FP16M), BM x BN x BK:
 //       128x128x64, 4 waves, 2-stage ring, 2 blocks/CU   -- small grids (N = 1024 projections)
-//       256x128x64, 8 waves, 3-stage ring                -- large grids
+//       256x128x64, 8 waves, 3-stage ring                -- deep-K launches too small for the square tile
 //       256x256x64, 8 waves, 2-stage ring                -- largest grids (half the L2->LDS bytes per FLOP)
-//       128x512x32, 8 waves, 3-stage ring, LayerNorm+GELU epilogue over the full 512-wide row
+//       128x64x64,  4 waves, 2-stage ring                -- grouped positional conv (<= 64 output channels per group)
+//       128x512x64 (8 waves), 64x512x64 (8 waves), 32x512x64 (4 waves), 2-stage ring -- LayerNorm+GELU epilogue over the full 512-wide
+//                                                           row; the fewer the rows, the shorter the tile
+//     two-plane modes (FP32X / FP16X: both planes of a K tile per stage), 8 waves but for the 4 of 128x64x32:
+//       128x128x64 2-stage, 256x128x32 3-stage, 256x256x32 2-stage, 128x64x32 2-stage, and the LayerNorm tile 128x512x32 2-stage
 //   * v_mfma_f32_16x16x32_bf16 with the WEIGHT tile as the MFMA A operand and the activation
 //     tile as the B operand: the accumulator then holds 4 consecutive output columns per register
 //     quad, and by permuting which weight row sits in which LDS row each lane ends up owning
@@ -26,13 +31,13 @@
 //   * blockIdx.x -> tile through a bijective XCD swizzle so each of the 8 L2s sees a contiguous run
 //     of tiles that share activation panels.
 #include "ser_common.h"
+#include "launch_plan.h"
 #ifndef SER_GEMM_PP
 #define SER_GEMM_PP 27        // ping-pong schedule, bit mask: 1 = 256x256, 2 = 256x128 / 64x512 (64x64 wave tiles), 4 = 128x512 LayerNorm tile, 8 = the FP32X 128x128 tile, 16 = the FP32X 128x512 LayerNorm tile; 0 = plain ring (A/B builds)
 #endif
 #include <stdlib.h>
 #include <stdio.h>
-#include <atomic>
-#include <type_traits>
+#include <utility>
 #ifdef SER_GEMM_DBG
 // diagnostic build only (tools/gemm_clock.py): wave 0 of every block stamps s_memtime / s_memrealtime around its K loop
 extern "C" { void* ser_gemm_dbg_ptr = nullptr; }
@@ -961,191 +966,27 @@ void ser_gemm_kernel(const ser_gemm_args p) {
 #endif
 }
 
-// Tile-selection thresholds are constants in the product build; `make EXPERIMENTS=1` turns them back into the environment knobs the
-// A/B scripts under tools/ set (SER_GEMM_T256_MIN, SER_GEMM_FORCE, ...).
-#ifdef SER_EXPERIMENTS
-#define SER_KNOB(name, dflt) ([] { const char* e_ = getenv(name); return e_ ? atol(e_) : (long)(dflt); }())
-#else
-#define SER_KNOB(name, dflt) ((long)(dflt))
-#endif
-
 // ------------------------------------------------------------------------------------------------
-enum { CFG_128x128 = 0, CFG_256x128 = 1, CFG_256x256 = 2, CFG_LN512 = 3, CFG_LN512_M64 = 4, CFG_LN512_M32 = 5, CFG_128x64 = 6 };
+// Host side: launch_plan.h checks the arguments and plans the launch (tile, (MODE, OM) pair, grid, LDS bytes); here the plan meets the
+// kernel template.  gemm_tile_serves guards the instantiation: exactly the (tile, pair) kernels it names are built.
+template <int... I, class F>
+static bool with_index(int i, std::integer_sequence<int, I...>, F&& f) { return ser_with_mode<I...>(i, f); }
 
-template <int WM, int WN, int TM, int TN, int BK, int ST, int MODE, bool LNEPI, int OM = MODE>
-static hipError_t launch_mode(const ser_gemm_args* a, dim3 grid, dim3 block, int LDS, hipStream_t s) {
-    auto k = ser_gemm_kernel<WM, WN, TM, TN, BK, ST, MODE, LNEPI, OM>;
-    // per instantiation; the drivers launch from several host threads: an atomic flag (two threads may both make the
-    // idempotent call, neither reads a half-written flag)
-    static std::atomic<bool> ready{false};
-    if (LDS > 65536 && !ready.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        ready.store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(k, grid, block, LDS, s, *a);
-    return hipSuccess;
-}
-
-// X32: the configuration serves the two-plane modes FP32X / FP16X (both planes per stage); otherwise the single-plane modes BF16 / FP16.
-template <int WM, int WN, int TM, int TN, int BK, int ST, bool LNEPI, bool X32 = false>
-static int launch_cfg(const ser_gemm_args* a, hipStream_t s) {
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    const int npl = (a->mode == SER_MODE_FP32X || a->mode == SER_MODE_FP16X) ? 2 : 1;
-    const int LDS = npl * ST * (BM + BN) * BK * 2 + (LNEPI ? 0 : BM * 8)    // ring (+ [BM][2] row statistics)
-                  + (a->mode == SER_MODE_FP16M ? ST * (BM + BN) * 4 : 0);   // FP16M: + the block-scale words of every stage
-    const int ntm = (a->M + BM - 1) / BM, ntn = (a->N + BN - 1) / BN;
-    dim3 grid((unsigned)(ntm * ntn), (unsigned)a->groups, 1), block(64 * WM * WN, 1, 1);
-    hipError_t e = hipSuccess;
-    if constexpr (X32) {
-        if constexpr (!LNEPI) {
-            if (a->mode == SER_MODE_FP16X && a->out_mode == SER_MODE_FP16M) {   // output projection of "f16m": 3 products on the attention kernel's hi + lo
-                if constexpr (BN >= 128)                                         // context rows, FP16M copy for FC1
-                    e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16X, LNEPI, SER_MODE_FP16M>(a, grid, block, LDS, s);
-                else return ser_fail(-22, "ser_gemm: FP16X -> FP16M output needs a dense tile (N > 64)");
-            } else
-            if (a->mode == SER_MODE_FP16X && a->out_mode == SER_MODE_FP16)      // output projection of "f16a": 3 products, one-plane copy for FC1
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16X, LNEPI, SER_MODE_FP16>(a, grid, block, LDS, s);
-            else if (a->mode == SER_MODE_FP16X)        // attention block ("f16a") / logit path ("f16q"): 3 products on the f16 MFMA
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16X, LNEPI>(a, grid, block, LDS, s);
-            else if (a->out_mode == SER_MODE_FP16)     // stem -> layers boundary of the "f16" numerics mode
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP32X, LNEPI, SER_MODE_FP16>(a, grid, block, LDS, s);
-            else
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP32X, LNEPI>(a, grid, block, LDS, s);
-        } else {
-            if (a->mode == SER_MODE_FP16X)             // conv stack of the f16 / f16q / f16a modes: fp16 hi + lo planes (22-bit operands)
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16X, LNEPI>(a, grid, block, LDS, s);
-            else
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP32X, LNEPI>(a, grid, block, LDS, s);
-        }
-    } else {
-        if (a->mode == SER_MODE_FP16M) {
-            if constexpr (!LNEPI && BN >= 128 && BK == 64) {
-                if (a->out_mode == SER_MODE_FP16X)     // packed projection of "f16m": q, k, v leave as fp16 hi + lo planes for ser_attention
-                    e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16M, LNEPI, SER_MODE_FP16X>(a, grid, block, LDS, s);
-                else
-                    e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16M, LNEPI>(a, grid, block, LDS, s);
-            } else return ser_fail(-22, "ser_gemm: FP16M needs a dense tile (N > 64, no LayerNorm epilogue)");
-        } else
-        if (a->mode == SER_MODE_FP16) {
-            if constexpr (!LNEPI && BN >= 128) {
-                if (a->out_mode == SER_MODE_FP16X)     // FC2 of the "f16q" mode: the next layer's q / k projection reads hi + lo planes
-                    e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16, LNEPI, SER_MODE_FP16X>(a, grid, block, LDS, s);
-                else
-                    e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16, LNEPI>(a, grid, block, LDS, s);
-            } else {
-                if (a->out_mode == SER_MODE_FP16X) return ser_fail(-22, "ser_gemm: FP16 -> FP16X output needs a dense tile (N > 64, no LayerNorm epilogue)");
-                e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_FP16, LNEPI>(a, grid, block, LDS, s);
-            }
-        }
-        else e = launch_mode<WM, WN, TM, TN, BK, ST, SER_MODE_BF16, LNEPI>(a, grid, block, LDS, s);
-    }
-    if (e != hipSuccess) return ser_fail((int)e, "ser_gemm: cannot raise dynamic LDS to %d", LDS);
+template <int TILE, int PAIR>
+static int launch_planned(const ser_gemm_args* a, const gemm_launch& pl, hipStream_t s) {
+    constexpr gemm_tile t = GEMM_TILE[TILE];
+    constexpr gemm_pair pr = GEMM_PAIR[PAIR];
+    auto k = ser_gemm_kernel<t.WM, t.WN, t.TM, t.TN, t.BK, t.ST, pr.mode, t.LNEPI, pr.om>;
+    static std::atomic<bool> ready{false};          // per instantiation
+    if (pl.lds > 65536)
+        if (hipError_t e = ser_lds_optin(k, pl.lds, ready)) return ser_fail((int)e, "ser_gemm: cannot raise dynamic LDS to %d", pl.lds);
+    hipLaunchKernelGGL(k, dim3(pl.grid_x, pl.grid_y, 1), dim3((unsigned)pl.block, 1, 1), pl.lds, s, *a);
     return ser_check_launch("ser_gemm");
 }
 
-static int pick_cfg(const ser_gemm_args* a) {
-    if (a->ln_gamma) {
-        // Row-complete LayerNorm tiles are BM x 512.  The last conv layers have few rows (M = 16k / 8k / 4k for eight
-        // 10 s utterances): 128-row tiles would leave half to 7/8 of the CUs idle, so the tile gets shorter until
-        // the grid covers the chip (measured per layer with tools/gemm_by_layer.py).
-        static const int force_bm = (int)SER_KNOB("SER_GEMM_LN_BM", 0);
-        const int bm = force_bm ? force_bm : (a->M >= 200 * 128 ? 128 : (a->M >= 200 * 64 ? 64 : 32));
-        return bm == 128 ? CFG_LN512 : (bm == 64 ? CFG_LN512_M64 : CFG_LN512_M32);
-    }
-    if (a->tile_cfg > 0) return a->tile_cfg - 1;
-    // Measured on MI355X (tools/gemm_sweep.py, M = 7984): the simple ring keeps the 128x128 tile
-    // (2 blocks/CU) ahead of 256x128 on every N <= 3072 shape; 256x256 wins once it has >= ~2 full
-    // rounds of blocks (N = 4096, conv layers) because it halves the L2->LDS bytes per FLOP.
-    // In the real step (two utterance groups in flight) 256x256 already pays from ~200 tiles (QKV and FC1
-    // at M = 3992): 9.6 -> 9.1 ms per step, A/B on one device.
-#ifdef SER_EXPERIMENTS
-    {   // experiments: SER_GEMM_FORCE="N:K:cfg[,N:K:cfg...]" pins the tile config of matching launches (tools/)
-        struct Rule { int n, k, cfg; };
-        static Rule rules[8];
-        static const int nrules = [] {
-            const char* e = getenv("SER_GEMM_FORCE");
-            int n = 0;
-            while (e && *e && n < 8) {
-                int a0, a1, a2, used = 0;
-                if (sscanf(e, "%d:%d:%d%n", &a0, &a1, &a2, &used) != 3) break;
-                rules[n++] = {a0, a1, a2};
-                e += used;
-                if (*e == ',') ++e;
-            }
-            return n;
-        }();
-        for (int i = 0; i < nrules; ++i)
-            if (rules[i].n == a->N && rules[i].k == a->K && rules[i].cfg >= 0 && rules[i].cfg <= CFG_256x256) return rules[i].cfg;
-    }
-#endif
-    const long t256x256 = (long)((a->M + 255) / 256) * ((a->N + 255) / 256) * a->groups;
-    static const long t256_min = SER_KNOB("SER_GEMM_T256_MIN", 150);      // 200 before the ping-pong schedule; XLS-R-2B's QKV (184 tiles at 4 x 10 s): +3.2 % on its step
-    if (a->N >= 256 && t256x256 >= t256_min) return CFG_256x256;
-    // grouped positional conv: 64 output channels per group -> a 128x64 tile wastes no MFMA columns
-    static const int n64 = (int)SER_KNOB("SER_GEMM_N64", 1);
-    if (n64 && a->N <= 64) return CFG_128x64;
-    // Deep-K, narrow-N GEMMs (FC2: N = D, K = 4D) that are too small for the 256x256 tile: 256x128 tiles are SLOWER
-    // in isolation (52 -> 64 us at M = 3992: only 128 blocks) but +1.5 % on the real step in five A/B pairs -- the
-    // launch then occupies half the CUs for its whole (long) K loop and the other utterance group's kernels own the
-    // other half, instead of both time-slicing every CU.  The shallow out-projection (K = D) loses with it.
-    static const int deepk = (int)SER_KNOB("SER_GEMM_DEEPK_256x128", 1);
-    if (deepk && a->groups == 1 && a->K >= 2048 && a->N >= 128 && a->M >= 512) return CFG_256x128;
-    return CFG_128x128;
-}
-
 extern "C" int ser_gemm(const ser_gemm_args* a, void* stream) {
-    if (!a || !a->A || !a->W) return ser_fail(-1, "ser_gemm: null operand");
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return ser_fail(-2, "ser_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
-    if (a->K % 64) return ser_fail(-3, "ser_gemm: K=%d must be a multiple of 64", a->K);
-    if (a->kc && (a->kc % 64 || a->K % a->kc)) return ser_fail(-4, "ser_gemm: kc=%d must divide K and be a multiple of 64", a->kc);
-    if (a->N % 8) return ser_fail(-5, "ser_gemm: N=%d must be a multiple of 8", a->N);
-    if (a->mode != SER_MODE_BF16 && a->mode != SER_MODE_FP32X && a->mode != SER_MODE_FP16 && a->mode != SER_MODE_FP16X && a->mode != SER_MODE_FP16M)
-        return ser_fail(-6, "ser_gemm: bad mode %d", a->mode);
-    if (a->mode == SER_MODE_FP16M) {
-        if (!a->a_scale || !a->w_scale || a->a_scale_ld < a->M || a->w_scale_ld < a->N)
-            return ser_fail(-23, "ser_gemm: FP16M needs a_scale / w_scale with *_scale_ld >= the row count");
-        if (a->a_rowoff || a->kc || a->groups != 1 || a->ln_gamma || (a->lda % 64))
-            return ser_fail(-23, "ser_gemm: FP16M takes plain row-major operands (no row map / conv chunks / groups / LayerNorm epilogue), lda %% 64 == 0");
-    }
-    if (a->out_mode == SER_MODE_FP16M || (a->mode == SER_MODE_FP16M && !a->out_mode && a->out_act)) {
-        if (!a->out_scale || (a->N % 64) || (a->ldo_act % 64) || a->groups != 1 || a->ln_gamma)
-            return ser_fail(-24, "ser_gemm: an FP16M out_act needs out_scale, N %% 64 == 0, ldo_act %% 64 == 0, groups == 1, no LayerNorm epilogue");
-    }
-    if (!a->a_rowoff && (a->lda % 8)) return ser_fail(-7, "ser_gemm: lda must be a multiple of 8");
-    if (a->groups < 1) return ser_fail(-8, "ser_gemm: groups=%d", a->groups);
-    if (!a->out_f32 && !a->out_act) return ser_fail(-9, "ser_gemm: no output");
-    if ((a->ldo_f32 % 4) || (a->ldo_act % 4) || (a->ldr % 4) || (a->c_group_stride % 4))
-        return ser_fail(-10, "ser_gemm: output/residual pitches must be multiples of 4");
-    if (a->ln_gamma) {
-        if (!a->ln_beta) return ser_fail(-11, "ser_gemm: ln_gamma without ln_beta");
-        if (a->N > 512 || a->groups != 1 || a->residual)
-            return ser_fail(-12, "ser_gemm: the LayerNorm epilogue needs N <= 512, groups == 1, no residual");
-    }
-    if (a->ln_stats_in) {
-        if (!a->ln_colsum || a->ln_groups < 2 || a->ln_groups > 32 || (a->ln_groups & 1) || a->ln_gamma)
-            return ser_fail(-14, "ser_gemm: deferred LayerNorm needs ln_colsum, an even ln_groups in [2,32] and no fused-LN epilogue");
-    }
-    if (a->stat_out && (a->ln_gamma || a->stat_groups < a->groups * ((a->N + 63) / 64)))
-        return ser_fail(-15, "ser_gemm: stat_out needs stat_groups >= groups*ceil(N/64) and no fused-LN epilogue");
-    if (a->shift_out && (!a->stat_out || a->ln_gamma)) return ser_fail(-19, "ser_gemm: shift_out needs stat_out and no fused-LN epilogue");
-    if (a->mean_out && !a->ln_stats_in) return ser_fail(-20, "ser_gemm: mean_out needs ln_stats_in");
-    if (a->lnstat_out && !a->ln_stats_in) return ser_fail(-20, "ser_gemm: lnstat_out needs ln_stats_in");
-    if (a->out_mode && a->out_mode != a->mode && !a->ln_gamma &&
-        !((a->mode == SER_MODE_FP32X && a->out_mode == SER_MODE_FP16) || (a->mode == SER_MODE_FP16 && a->out_mode == SER_MODE_FP16X) ||
-          (a->mode == SER_MODE_FP16X && a->out_mode == SER_MODE_FP16) || (a->mode == SER_MODE_FP16X && a->out_mode == SER_MODE_FP16M) ||
-          (a->mode == SER_MODE_FP16M && a->out_mode == SER_MODE_FP16X)))
-        return ser_fail(-21, "ser_gemm: out_mode %d with mode %d (FP32X -> FP16, FP16 <-> FP16X, FP16X <-> FP16M convert)", a->out_mode, a->mode);
-    if (a->out_mode && a->out_mode != a->mode && a->ln_gamma)
-        return ser_fail(-21, "ser_gemm: out_mode %d with the LayerNorm epilogue", a->out_mode);
-    if (a->col_scale_end % 4) return ser_fail(-17, "ser_gemm: col_scale_end must be a multiple of 4");
-    if (a->gn_scale && (!a->gn_shift || !a->gn_row_offs || a->gn_B < 1 || a->gn_ld < a->N || (a->gn_ld % 4) || a->groups != 1 ||
-                        a->ln_gamma || a->ln_stats_in))
-        return ser_fail(-25, "ser_gemm: gn_scale needs gn_shift, gn_row_offs, gn_B >= 1, gn_ld >= N (multiple of 4), groups == 1, "
-                             "no LayerNorm epilogue and no deferred LayerNorm");
-    if ((a->ldo_act % 8) || (a->c_group_stride % 8)) return ser_fail(-18, "ser_gemm: act pitch / group stride must be multiples of 8");
-    if (a->f32_col_begin < 0 || (a->f32_col_begin % 8)) return ser_fail(-16, "ser_gemm: f32_col_begin must be a non-negative multiple of 8");
-    if (a->tile_cfg < 0 || a->tile_cfg > 3) return ser_fail(-13, "ser_gemm: tile_cfg=%d (0 auto, 1..3)", a->tile_cfg);
+    gemm_launch pl;
+    if (int rc = gemm_plan(a, &pl)) return rc;
     hipStream_t s = (hipStream_t)stream;
 #ifdef SER_GEMM_DBG
     {
@@ -1156,55 +997,12 @@ extern "C" int ser_gemm(const ser_gemm_args* a, void* stream) {
         }
     }
 #endif
-    if (a->mode == SER_MODE_FP32X || a->mode == SER_MODE_FP16X) {
-        // both planes share a stage: the ring doubles, so FP32X uses the two configurations that still fit 160 KiB
-        if (a->ln_gamma) return launch_cfg<2, 4, 4, 8, 32, 2, true, true>(a, s);
-        // grouped positional conv (<= 64 output channels per group): 128x64 tiles of 32x64 wave tiles, like the bf16 path's -- the
-        // 128x128 tile below computes 64 dead columns per group (fp32x pos-conv: 360 us against 100 us in bf16)
-        static const int x32_n64 = (int)SER_KNOB("SER_GEMM_N64", 1);
-        if (x32_n64 && a->N <= 64) return launch_cfg<4, 1, 2, 4, 32, 2, false, true>(a, s);
-        // Large grids: 256x128 tiles of 64x64 wave tiles on a 32-deep, 3-stage ring (144 KiB): 16 fragments feed 48 MFMAs per
-        // k-step (0.33 LDS fragment reads per MFMA against 0.5 for the 32x64 wave tile below), one ping-pong phase per K tile
-        static const long x32_256_min = SER_KNOB("SER_GEMM_X32_256_MIN", 100);   // 100: M = 3992 out-proj / FC2 (128 tiles) gain, M = 1996 ones (64 tiles) lose
-        const long t256x128 = (long)((a->M + 255) / 256) * ((a->N + 127) / 128) * a->groups;
-        // Largest grids (round 3): 256x256 tiles of 64x128 wave tiles, both planes of a 32-deep K tile per stage, 2 stages (128 KiB):
-        // 24 fragments feed 96 MFMAs per K tile (0.25 LDS fragment reads per MFMA, half the L2 -> LDS bytes per product of the
-        // 256x128 tile), the weight fragments taken in two halves like the LayerNorm tile's (PPW).  From SER_GEMM_X32_SQ_MIN tiles.
-        static const long x32_sq_min = SER_KNOB("SER_GEMM_X32_SQ_MIN", 150);
-        const long t256sq = (long)((a->M + 255) / 256) * ((a->N + 255) / 256) * a->groups;
-        // Measured on the step (two A/B pairs, one box): the packed QKV projection on it f16a 1 110 / 1 114 -> 1 134 / 1 130 utt/s; FC1 too
-        // (its GELU epilogue on 128 accumulators + 64 spilled bias / column-sum registers) gives the gain back: fp32x 848 -> 846.
-        // Hence only launches without an activation take it.
-        // ... and only grids whose last round of 256 blocks is mostly full (round 4): WavLM-large's packed projection has 384 such tiles = 1.5 rounds
-        // (efficiency 0.75) and is 0.5 % faster on the f16x step as 768 tiles of 256x128 = 3 full rounds (XLS-R-2B at 8 x 10 s, 368 tiles: + 0.2 %), while
-        // HuBERT-xlarge's 480 (0.94) and Whisper's 705 (0.92) lose 2.7 % / 4.7 % of their steps without the square tile (same-box pairs, experiments build).
-        const long sq_rounds = (t256sq + 255) / 256;
-        const bool sq_full = t256sq * 100 >= sq_rounds * 256 * 85;
-        if (x32_sq_min > 0 && a->N >= 256 && t256sq >= x32_sq_min && sq_full && a->act == SER_ACT_NONE) return launch_cfg<4, 2, 4, 8, 32, 2, false, true>(a, s);
-        if (x32_256_min > 0 && a->N >= 128 && t256x128 >= x32_256_min) return launch_cfg<4, 2, 4, 4, 32, 3, false, true>(a, s);
-        return launch_cfg<4, 2, 2, 4, 64, 2, false, true>(a, s);      // 128x128 tile on 8 waves (32x64 each): 2 waves/SIMD hide the LDS reads
-    }
-    if (a->mode == SER_MODE_FP16M) {
-        // the single-plane tiles walked twice per K tile (H unit, E unit): 256x256 from 100 tiles up, 256x128 on a three-stage ring, 128x128 on four
-        // waves for small M.  Alone, one launch at a time, the 256x256 form is the SLOWER one at M = 7 984 (packed projection 139 us against 122 on
-        // 256x128, FC2 -- 128 tiles, half the chip -- 206 against 130: profiles/r05_gemm_f16m_bench.txt); on the step it is the FASTER one: 928 ->
-        // 973 utt/s with the packed projection and FC1 on it, 990 with FC2 and the output projection too (profiles/r05_f16m_tile_choice_step_ab.txt).
-        // The step runs at the board's power cap (profiles/r05_power_sample_bf16_step.txt): what counts is energy per FLOP, and the square tile
-        // moves 2/3 of the L2 -> LDS bytes per FLOP.  (The same threshold on the bf16 tiles LOSES 1.3 %: T256_MIN stays 150.)
-        const long t256sq = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
-        const long t256x128 = (long)((a->M + 255) / 256) * ((a->N + 127) / 128);
-        static const long m_sq_min = SER_KNOB("SER_GEMM_M16_SQ_MIN", 100), m_256_min = SER_KNOB("SER_GEMM_M16_256_MIN", 100);
-        if (a->tile_cfg == 3 || (!a->tile_cfg && a->N >= 256 && t256sq >= m_sq_min)) return launch_cfg<2, 4, 8, 4, 64, 2, false>(a, s);
-        if (a->tile_cfg == 2 || (!a->tile_cfg && a->N >= 128 && t256x128 >= m_256_min)) return launch_cfg<4, 2, 4, 4, 64, 3, false>(a, s);
-        return launch_cfg<2, 2, 4, 4, 64, 2, false>(a, s);
-    }
-    switch (pick_cfg(a)) {
-        case CFG_LN512:   return launch_cfg<2, 4, 4, 8, 64, 2, true>(a, s);     // 160 KiB ring, one barrier per 64-deep K tile
-        case CFG_LN512_M64: return launch_cfg<1, 8, 4, 4, 64, 2, true>(a, s);   // 64 x 512 tile, 8 waves of 64x64
-        case CFG_LN512_M32: return launch_cfg<1, 4, 2, 8, 64, 2, true>(a, s);   // 32 x 512 tile, 4 waves of 32x128
-        case CFG_128x64:  return launch_cfg<4, 1, 2, 4, 64, 2, false>(a, s);    // 4 waves of 32x64: a wave owns a whole 64-column stat group
-        case CFG_256x256: return launch_cfg<2, 4, 8, 4, 64, 2, false>(a, s);
-        case CFG_256x128: return launch_cfg<4, 2, 4, 4, 64, 3, false>(a, s);
-        default:          return launch_cfg<2, 2, 4, 4, 64, 2, false>(a, s);
-    }
+    int rc = -22;                                   // (never returned: gemm_plan refuses the (tile, pair) combinations that are not built)
+    with_index(pl.tile, std::make_integer_sequence<int, GEMM_TILES>{}, [&](auto T) {
+        with_index(pl.pair, std::make_integer_sequence<int, GEMM_PAIRS>{}, [&](auto P) {
+            constexpr int tile = decltype(T)::value, pair = decltype(P)::value;
+            if constexpr (gemm_tile_serves(GEMM_TILE[tile], GEMM_PAIR[pair])) rc = launch_planned<tile, pair>(a, pl, s);
+        });
+    });
+    return rc;
 }

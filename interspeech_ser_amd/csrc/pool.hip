@@ -243,13 +243,10 @@ __global__ __launch_bounds__(256) void tail_hidden_kernel(const float* __restric
 template <bool RELU>
 static void tail_hidden_launch(const float* p, int64_t ldp, const float* W1, const float* b1, float* hidden, int B, int K, int H, hipStream_t s) {
     const dim3 grid((unsigned)((H + 3) / 4)), block(256);
-#define TAIL_HIDDEN(KV) hipLaunchKernelGGL((tail_hidden_kernel<KV, RELU>), grid, block, 0, s, p, ldp, W1, b1, hidden, B, K, H)
-    if (K <= 256) TAIL_HIDDEN(1);
-    else if (K <= 512) TAIL_HIDDEN(2);
-    else if (K <= 1024) TAIL_HIDDEN(4);
-    else if (K <= 2048) TAIL_HIDDEN(8);
-    else TAIL_HIDDEN(16);
-#undef TAIL_HIDDEN
+    const int chunks = K <= 256 ? 1 : (K <= 512 ? 2 : (K <= 1024 ? 4 : (K <= 2048 ? 8 : 16)));
+    ser_with_mode<1, 2, 4, 8, 16>(chunks, [&](auto KV) {
+        hipLaunchKernelGGL((tail_hidden_kernel<KV(), RELU>), grid, block, 0, s, p, ldp, W1, b1, hidden, B, K, H);
+    });
 }
 
 // ------------------------------------------------------------------------------- outputs (second Linear)

@@ -1,15 +1,7 @@
-// Where a row kernel starts (rowops.hip, deberta.hip): the host's run-time mode -> template dispatch, and the wave-per-row pass
-// "row kept in registers (D <= 2048, D % 4 == 0), two-pass mean / variance, LayerNorm tail".
+// Where a row kernel starts (rowops.hip, deberta.hip): the wave-per-row pass "row kept in registers (D <= 2048, D % 4 == 0), two-pass
+// mean / variance, LayerNorm tail".  (The run-time mode -> template dispatch they start from, ser_with_mode, is in ser_common.h.)
 #pragma once
-#include <type_traits>
 #include "ser_common.h"
-
-// Calls f(std::integral_constant<int, M>) for the M of MODES that equals `mode`; false when none does (f is not called).
-//   ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X>(mode, [&](auto M) { hipLaunchKernelGGL(kernel<M()>, ...); })
-template <int... MODES, class F>
-static inline bool ser_with_mode(int mode, F&& f) {
-    return ((mode == MODES ? (f(std::integral_constant<int, MODES>{}), true) : false) || ...);
-}
 
 // A lane owns 4 consecutive columns of every 256-column chunk: f(i, c) for chunk i and the lane's first column c of it (may be >= D).
 template <class F>

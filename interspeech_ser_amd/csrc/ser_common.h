@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <type_traits>
 #include "../../include/ser_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -19,6 +21,29 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 // host-side error plumbing (capi.hip)
 int ser_fail(int code, const char* fmt, ...);
 int ser_check_launch(const char* what);
+
+// The host's run-time value -> template dispatch.  Calls f(std::integral_constant<int, M>) for the M of MODES that equals `mode`; false
+// when none does (f is not called).  Any int serves: a numerics mode, a padded head dim, an index into a constexpr table.
+//   ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X>(mode, [&](auto M) { hipLaunchKernelGGL(kernel<M()>, ...); })
+template <int... MODES, class F>
+static inline bool ser_with_mode(int mode, F&& f) {
+    return ((mode == MODES ? (f(std::integral_constant<int, MODES>{}), true) : false) || ...);
+}
+template <class F>
+static inline void ser_with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+// One-time opt-in of kernel `k` to `bytes` of dynamic LDS (beyond the 64 KiB a kernel gets unasked).  `ready` is the caller's flag for this
+// kernel (a function-local static per instantiation).  The drivers launch from several host threads: an atomic flag -- two threads may both
+// make the idempotent call, neither reads a half-written flag.  hipSuccess, or what hipFuncSetAttribute said (the caller words the failure).
+template <class K>
+static inline hipError_t ser_lds_optin(K k, int bytes, std::atomic<bool>& ready) {
+    if (ready.load(std::memory_order_acquire)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) ready.store(true, std::memory_order_release);
+    return e;
+}
 
 __device__ __forceinline__ unsigned short f2bf(float x) {
     return __builtin_bit_cast(unsigned short, (__bf16)x);      // v_cvt_pk_bf16_f32: RNE, NaN-safe

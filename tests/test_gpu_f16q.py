@@ -51,6 +51,24 @@ def test_gemm_two_plane_256x256_tile_integer_exact(L, mode, M, N, K):
     assert torch.equal(out.cpu().double(), ref)
 
 
+@pytest.mark.parametrize("mode", [2, 4])
+@pytest.mark.parametrize("M,N,K", [(12800, 256, 64), (3840, 3840, 64), (300, 64, 128)])
+def test_gemm_two_plane_tiles_write_one_fp16_plane_integer_exact(L, mode, M, N, K):
+    """FP32X / FP16X -> one fp16 plane (ser_gemm_args.out_mode = FP16) on the two-plane tiles that the conversion tests do not reach at
+    their 300 x 200 (the 128x128x64 tile): 100 tiles of 256x128 -> 256x128x32; 225 square tiles, 88 % of one round of 256 blocks, no
+    activation -> 256x256x32; N = 64 -> 128x64x32.  Small integers: the fp32 result and its fp16 copy are both exact."""
+    from test_gpu_kernels import to_act
+    g = torch.Generator().manual_seed(M + N + mode)
+    A = torch.randint(-3, 4, (M, K), generator=g).float()
+    W = torch.randint(-3, 4, (N, K), generator=g).float() + (torch.arange(N)[:, None] % 3).float()
+    bias = torch.randint(-4, 5, (N,), generator=g).float()
+    ref = A @ W.T + bias                                    # |ref| <= 15 K + 4 < 2048: exact in fp32 and in fp16
+    a, w = (split_h(A), split_h(W)) if mode == 4 else (to_act(A, 2), to_act(W, 2))
+    out, oact = run_gemm(L, a, w, M, N, K, mode, bias=bias.to(DEV), out_mode=FP16)
+    assert torch.equal(out.cpu(), ref)
+    assert oact.dtype == torch.float16 and oact.shape[0] == 1 and torch.equal(oact[0].cpu().float(), ref)
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 200, 192), (515, 392, 1024), (2561, 1288, 192), (3000, 1160, 320)])
 def test_gemm_fp16x_integer_exact(L, M, N, K):
     """Small integers are exact in fp16: any slip in the two-plane stage layout or the fragment order shows as a wrong
@@ -187,14 +205,14 @@ def _attention_case(L, dh, H, bias, sharp, mode, Ts=(70, 129, 5, 200), ramp=0.0)
     return (planes_value(out.cpu()) - ref).abs().max().item(), ref
 
 
-@pytest.mark.parametrize("dh,H,bias", [(64, 2, True), (64, 3, False), (80, 2, False), (120, 2, False), (128, 1, False)])
+@pytest.mark.parametrize("dh,H,bias", [(64, 2, True), (64, 3, False), (80, 2, False), (120, 2, False), (128, 1, False), (80, 2, True), (120, 2, True)])
 def test_attention_fp16q(L, dh, H, bias):
     """3-product S = K Q^T from fp16 hi + lo planes of q and k, single-product P V: every head-dim / bias path, ragged batch."""
     err, ref = _attention_case(L, dh, H, bias, 1.0, FP16Q)
     assert err < 3e-3, err                                # P and the output are fp16 (2^-11 relative); |v| up to ~4
 
 
-@pytest.mark.parametrize("dh,H,bias", [(64, 2, True), (64, 3, False), (80, 2, False), (120, 2, False), (128, 1, False)])
+@pytest.mark.parametrize("dh,H,bias", [(64, 2, True), (64, 3, False), (80, 2, False), (120, 2, False), (128, 1, False), (80, 2, True), (120, 2, True)])
 def test_attention_fp16x(L, dh, H, bias):
     """everything split ("f16a"): S, P V on 3 products, the context rows written as fp16 hi + lo planes -- fp32-grade"""
     err, ref = _attention_case(L, dh, H, bias, 1.0, FP16X)
@@ -208,6 +226,14 @@ def test_attention_two_plane_stale_running_maximum(L, mode, bound, dh, bias):
     two-plane forms: 11 key tiles of climbing scores"""
     err, ref = _attention_case(L, dh, 2, bias, 1.0, mode, Ts=(700, 65, 1, 130), ramp=100.0)
     assert err < bound, err
+
+
+def test_attention_fp16q_reads_a_long_table_from_global_memory(L):
+    """FP16Q's three operand planes leave the bias window 112 KiB of LDS: from 6 858 frames the table is read from global memory (the GB form
+    test_gpu_kernels.py::test_attention_unbounded_utterance_reads_the_table_from_global_memory launches in modes 1 - 3).  A short utterance
+    shares the launch."""
+    err, ref = _attention_case(L, 64, 1, True, 1.0, FP16Q, Ts=(6900, 150))
+    assert err < 3e-3, err
 
 
 def test_gemm_fp16x_writes_one_plane(L):

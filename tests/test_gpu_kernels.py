@@ -129,7 +129,9 @@ def test_gemm_integer_exact(L, mode, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(700, 520, 256), (257, 264, 64), (1030, 128, 640), (300, 136, 128), (140, 256, 192), (129, 8, 320)])
 def test_gemm_every_tile_config_integer_exact(L, mode, cfg, M, N, K):
     """128x128 / 256x128 / 256x256 block tiles (2- and 3-stage rings; K = 64..640 covers every ring fill / drain
-    length) forced through tile_cfg."""
+    length) forced through tile_cfg -- in modes 1 (BF16) and 3 (FP16), which honour it.  Mode 2 (FP32X) ignores tile_cfg, as FP16X does
+    (include/ser_hip.h): its three cfg cases run the automatically chosen two-plane tile three times (128x128x64 at these sizes, 128x64x32
+    at N = 8).  The two-plane 256x128x32 and 256x256x32 tiles are reached by size, in tests/test_gpu_f16q.py."""
     g = torch.Generator().manual_seed(M + N + cfg)
     A = torch.randint(-3, 4, (M, K), generator=g).float()
     W = torch.randint(-3, 4, (N, K), generator=g).float() + (torch.arange(N)[:, None] % 3).float()
@@ -588,7 +590,7 @@ def attention_reference(q, k, v, scale, table=None, gate=None):
 
 
 @pytest.mark.parametrize("mode", [1, 2, 3])
-@pytest.mark.parametrize("dh,H,bias", [(64, 2, True), (64, 3, False), (80, 2, False), (120, 2, False), (128, 1, False)])
+@pytest.mark.parametrize("dh,H,bias", [(64, 2, True), (64, 3, False), (80, 2, False), (120, 2, False), (128, 1, False), (80, 2, True), (120, 2, True)])
 def test_attention(L, mode, dh, H, bias):
     Ts = [70, 129, 5, 200]
     D = H * dh
@@ -896,7 +898,7 @@ def test_attention_prescaled_q(L, mode, dh, bias):
 
 
 @pytest.mark.parametrize("mode", [1, 2, 3])
-@pytest.mark.parametrize("dh,bias", [(64, True), (64, False), (80, False), (128, False)])
+@pytest.mark.parametrize("dh,bias", [(64, True), (64, False), (80, False), (128, False), (80, True), (120, True)])
 def test_attention_stale_running_maximum(L, mode, dh, bias):
     """Pre-scaled launches with a bias table keep a STALE row maximum in the accumulators' start value and only raise it when a tile
     exceeds it by 2^8 (csrc/attention.hip, LAZY); the others track the exact maximum.  Scores that climb ~50 exp2-units across 11 key
@@ -962,6 +964,15 @@ def test_attention_high_occupancy_arm_without_table(L, mode, pre_scaled):
     blocks, pre-scaled q (scores are exp2 exponents) and plain q with scale = dh^-0.5, bf16 and fp16, against the fp64 statement."""
     Ts = [499, 499, 149, 333, 250, 499, 64, 401, 499, 200, 450, 499, 97, 499, 310, 499]
     err = _prescaled_case(L, mode, 64, False, Ts, H=16, pre_scaled=pre_scaled, check=(0, 2, 6, 12, 15))
+    assert err < mode_tol(mode, 3e-2, 3e-4), err
+
+
+@pytest.mark.parametrize("mode", [1, 3])
+def test_attention_high_occupancy_arm_with_table_and_plain_q(L, mode):
+    """The OCC arm with the bias table + gate[] and scale = dh^-0.5 (q not pre-scaled): the one combination of the arm's four that
+    neither test_attention_full_batch_launch_shape (table, pre-scaled) nor the test above (no table) launches.  Same 1 024-block shape."""
+    Ts = [499, 499, 149, 333, 250, 499, 64, 401, 499, 200, 450, 499, 97, 499, 310, 499]
+    err = _prescaled_case(L, mode, 64, True, Ts, H=16, pre_scaled=False, check=(0, 2, 6, 12, 15))
     assert err < mode_tol(mode, 3e-2, 3e-4), err
 
 
