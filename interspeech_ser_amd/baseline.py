@@ -25,7 +25,6 @@ import json
 import os
 import pickle
 import time
-from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence
 
@@ -33,7 +32,8 @@ import numpy as np
 import torch
 
 from . import config as C
-from .driver import _Extractor, make_batches
+from .batchloop import SlotPipeline, make_batches, prefetch
+from .driver import _Extractor
 from .frontend import TARGET_SR, UnsupportedAudio, decode_wav
 
 MAX_SAMPLES = 12 * TARGET_SR                        # utils/dataset/dataset.py: min(longest file, 12 s)
@@ -280,39 +280,20 @@ def _run_eval(argv: Optional[Sequence[str]], kind: str, predictor_factory=None) 
         failed += 1
         print(f"Failed to process {os.path.join(wav_dir, name)}: {err}")
 
-    def one_by_one(good):
-        """A failed batch is retried per utterance so one bad file cannot drop its neighbours."""
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-        for name, wave in good:
-            try:
-                out = ex.extract([wave])
-                done.append(name)
-                logits.append(np.asarray(out[0]))
-            except Exception as e:                          # noqa: BLE001
-                fail(name, e)
-
-    def finish(ticket):
-        good = ticket["good"]
-        try:
-            out = ex.collect(ticket)
-        except Exception:                                   # noqa: BLE001
-            one_by_one(good)
-            return
+    def finished(good, out, ticket):
         for (name, _), row in zip(good, out):
             done.append(name)
             logits.append(np.asarray(row))
 
-    batches = make_batches(names, max(1, args.batch_size))
-    slots = getattr(ex, "SLOTS", 2)
+    # the extraction drivers' slot pipeline (batchloop: a failed batch is retried per utterance, a file that still fails costs itself)
+    pipe = SlotPipeline(submit=lambda good, slot: ex.submit([w for _, w in good], None, slot=slot), collect=ex.collect,
+                        extract=lambda good: ex.extract([w for _, w in good]), slots=getattr(ex, "SLOTS", 2), done=finished,
+                        fail=lambda item, err: fail(item[0], err),
+                        before_retry=torch.cuda.synchronize if torch.cuda.is_available() else None)
     t0 = time.perf_counter()
-    inflight = deque()
     with ThreadPoolExecutor(max_workers=max(1, args.num_workers)) as pool:
-        pending = pool.map(decode, batches[0]) if batches else []
-        for bi, batch in enumerate(batches):
-            decoded = list(pending)
-            if bi + 1 < len(batches):
-                pending = pool.map(decode, batches[bi + 1])          # decode the next batch while the GPU works
+        # the next batch is decoded while the GPU works
+        for bi, decoded in enumerate(prefetch(make_batches(names, max(1, args.batch_size)), pool, decode)):
             good = []
             for name, wave, err in decoded:
                 if err is not None:
@@ -320,18 +301,9 @@ def _run_eval(argv: Optional[Sequence[str]], kind: str, predictor_factory=None) 
                 else:
                     good.append((name, wave))
             if good:
-                try:
-                    ticket = ex.submit([w for _, w in good], None, slot=bi % slots)
-                    ticket["good"] = good
-                    inflight.append(ticket)
-                except Exception:                           # noqa: BLE001
-                    while inflight:
-                        finish(inflight.popleft())
-                    one_by_one(good)
-            while len(inflight) > slots - 1:
-                finish(inflight.popleft())
-        while inflight:
-            finish(inflight.popleft())
+                pipe.push(bi, good)
+            pipe.drain()
+        pipe.drain(0)
 
     dt = time.perf_counter() - t0
     print(f"{len(done)} utterances on 1 GPU(s) in {dt:.2f} s ({len(done) / max(dt, 1e-9):.1f} utt/s)")

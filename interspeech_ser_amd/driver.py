@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import config as C
+from .batchloop import SlotPipeline, make_batches, prefetch       # noqa: F401  (make_batches: tests and tools import it from here)
 from .frontend import (RESAMPLE_MAX_R, TARGET_SR, decode_wav, feature_path, host_resample, load_wav_16k, resample_ratio,
                        resampled_len, save_feature, whisper_saved_rows)
 
@@ -91,10 +92,6 @@ def build_parser(whisper: bool) -> argparse.ArgumentParser:
 
 
 from .dist import shard_files          # noqa: E402  (re-exported: the sharding rule lives in dist.py)
-
-
-def make_batches(files: Sequence[str], batch_size: int) -> List[List[str]]:
-    return [list(files[i:i + batch_size]) for i in range(0, len(files), batch_size)]
 
 
 def resolve_layer_index(n_layer: int, num_states: int) -> int:
@@ -473,54 +470,48 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
     done = 0
     audio_s = 0.0
     bar = tqdm(total=len(mine), desc="Extracting features", disable=(rank != 0))
-    from collections import deque
-    pipelined = getattr(ex, "pipelined", True)           # both encoder families run through the two-slot pipeline
     with ThreadPoolExecutor(max_workers=max(1, args.num_workers)) as pool:
-        pending = pool.map(decode, batches[0]) if batches else []
         writes = []
-        inflight = deque()
 
-        def run(fn, items, *a, **k):
-            """fn(waves, ...) of (samples, rate) items; the rates go along only where the GPU resamples."""
-            waves = [w for w, _ in items]
-            return fn(waves, *a, rates=[sr for _, sr in items], **k) if gpu_resample else fn(waves, *a, **k)
+        def run(fn, good, **k):
+            """fn(waves, layer_index, ...) of (path, (samples, rate)) items; the rates go along only where the GPU resamples."""
+            waves = [w for _, (w, _) in good]
+            return fn(waves, layer_index, rates=[sr for _, (_, sr) in good], **k) if gpu_resample else fn(waves, layer_index, **k)
 
-        def one_by_one(good):
-            """A failed batch is retried per utterance so one bad file cannot drop its neighbours."""
+        def finished(good, feats, ticket):
             nonlocal done, audio_s
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()                      # the synchronous path shares slot 0's arena with the pipeline
-            for path, (wave, sr) in good:
-                try:
-                    f = run(ex.extract, [(wave, sr)], layer_index)[0]
-                    writes.append(pool.submit(write, (path, f)))
-                    done += 1
-                    audio_s += resampled_len(len(wave), sr) / 16000.0
-                except Exception as e1:                       # noqa: BLE001
-                    print(f"Failed to process {path}: {e1}")
-
-        def finish(ticket):
-            nonlocal done, audio_s
-            good = ticket["good"]
-            try:
-                feats = ex.collect(ticket)
-            except Exception:                                 # noqa: BLE001
-                one_by_one(good)
-                return
             futs = [pool.submit(write, (path, f)) for (path, _), f in zip(good, feats)]
-            ex.hold(ticket["slot"], futs)
             writes.extend(futs)
             done += len(good)
-            audio_s += sum(resampled_len(len(w), sr) for _, (w, sr) in good) / 16000.0
+            samples = [resampled_len(len(w), sr) for _, (w, sr) in good]
+            if ticket is not None:
+                ex.hold(ticket["slot"], futs)                 # the slot's pinned buffer is not refilled under its writers
+                audio_s += sum(samples) / 16000.0
+            else:                                             # through extract: added file by file (the total's last digit
+                for n in samples:                             # follows the order of the additions, and SER_RUN rounds it)
+                    audio_s += n / 16000.0
 
         tm = dict(decode_wait=0.0, submit=0.0, finish=0.0)   # where the launching thread spends its time (--timing)
         clock = time.perf_counter
-        for bi, batch in enumerate(batches):
+
+        def submit(good, slot):
             t_a = clock()
-            decoded = list(pending)
+            ticket = run(ex.submit, good, slot=slot)
+            tm["submit"] += clock() - t_a
+            return ticket
+
+        # both encoder families run through the slot pipeline; the contract of a failed batch is batchloop's
+        # (an extractor with ``pipelined = False`` has no submit / collect / hold: they are looked up when called)
+        pipe = SlotPipeline(submit=submit, collect=lambda ticket: ex.collect(ticket), extract=lambda good: run(ex.extract, good),
+                            slots=getattr(ex, "SLOTS", 2), done=finished,
+                            fail=lambda item, err: print(f"Failed to process {item[0]}: {err}"),
+                            before_retry=torch.cuda.synchronize if torch.cuda.is_available() else None,
+                            pipelined=getattr(ex, "pipelined", True))
+        decoding = prefetch(batches, pool, decode)           # the next batch is decoded while the GPU works
+        for bi in range(len(batches)):
+            t_a = clock()
+            decoded = next(decoding)
             tm["decode_wait"] += clock() - t_a
-            if bi + 1 < len(batches):
-                pending = pool.map(decode, batches[bi + 1])          # decode the next batch while the GPU works
             good = []
             for path, item, err in decoded:                   # item: (samples, their rate)
                 if err is not None:
@@ -531,30 +522,12 @@ def _run(argv: Optional[Sequence[str]], whisper: bool, extractor_factory=None, l
                 for path, _ in good:
                     print(f"Failed to process {path}: tuple index out of range")
             elif good:
-                try:
-                    if pipelined:
-                        t_a = clock()
-                        ticket = run(ex.submit, [item for _, item in good], layer_index, slot=bi % ex.SLOTS)
-                        tm["submit"] += clock() - t_a
-                        ticket["good"] = good
-                        inflight.append(ticket)
-                    else:
-                        feats = run(ex.extract, [item for _, item in good], layer_index)
-                        for (path, (wave, sr)), f in zip(good, feats):
-                            writes.append(pool.submit(write, (path, f)))
-                            audio_s += resampled_len(len(wave), sr) / 16000.0
-                        done += len(good)
-                except Exception:                             # noqa: BLE001
-                    while inflight:                           # keep the per-slot order simple: drain, then retry singly
-                        finish(inflight.popleft())
-                    one_by_one(good)
+                pipe.push(bi, good)
             t_a = clock()
-            while len(inflight) > getattr(ex, "SLOTS", 2) - 1:   # all but one slot stay in flight while the next batch is prepared
-                finish(inflight.popleft())
+            pipe.drain()                                      # all but one slot stay in flight while the next batch is prepared
             tm["finish"] += clock() - t_a
-            bar.update(len(batch))
-        while inflight:
-            finish(inflight.popleft())
+            bar.update(len(decoded))
+        pipe.drain(0)
         for w in writes:
             w.result()
     bar.close()
@@ -699,9 +672,7 @@ def run_roberta(argv: Optional[Sequence[str]] = None, tokenize=None, family: str
     bar = tqdm(total=len(mine), desc="Extracting features", disable=(rank != 0))
     with ThreadPoolExecutor(max_workers=max(1, args.num_workers)) as pool:
         writes = []
-        bs = max(1, args.batch_size)
-        for i in range(0, len(mine), bs):
-            idx = mine[i:i + bs]
+        for idx in make_batches(mine, max(1, args.batch_size)):
             try:
                 feats = ex.extract([texts[j] for j in idx])
                 for j, f in zip(idx, feats):

@@ -13,7 +13,6 @@ repository are on the extraction side, which writes the files this module reads.
 """
 from __future__ import annotations
 
-import csv
 import json
 import logging
 import math
@@ -28,6 +27,8 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn.utils.rnn import pad_sequence
 from torch.utils.data import DataLoader, Dataset, WeightedRandomSampler
+
+from .batchloop import close_logger, run_or_each, write_result_csv
 
 CLASSES = ["Angry", "Sad", "Happy", "Surprise", "Fear", "Disgust", "Contempt", "Neutral"]      # train script :147
 CLASS_LETTERS = ["A", "S", "H", "U", "F", "D", "C", "N"]                                        # eval script :129
@@ -340,9 +341,7 @@ def train(config: Dict, seed: int = 7, device: Optional[str] = None, modalities:
             print("Save", epoch)
             print("Loss", float(dev_loss))
             torch.save(model.state_dict(), best["model_file"])
-    for h in list(log.handlers):
-        h.close()
-        log.removeHandler(h)
+    close_logger(log)
     return best
 
 
@@ -376,16 +375,8 @@ def evaluate(config: Dict, seed: int = 7, device: Optional[str] = None, engine: 
     loss = ce_weight_category(logits_all, labels_all, None)
     f1 = macro_f1(gold, preds)
     log.info(f"|Metrics| eval_loss = {loss} eval f1 = {f1}")
-    os.makedirs(os.path.join(model_path, "results"), exist_ok=True)
-    csv_file = os.path.join(model_path, "results", "dev.csv")
-    with open(csv_file, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(["Filename", "Prediction"] + [f"class_{i}_prob" for i in range(len(CLASSES))])
-        for row, utt in zip(logits_all.cpu().numpy(), utts):
-            w.writerow([utt, CLASS_LETTERS[int(np.argmax(row))]] + [f"{p:.4f}" for p in row.flatten()])
-    for h in list(log.handlers):
-        h.close()
-        log.removeHandler(h)
+    csv_file = write_result_csv(model_path, "dev", "Filename", utts, logits_all.cpu().numpy(), CLASS_LETTERS)
+    close_logger(log)
     return {"eval_loss": float(loss), "eval_f1": f1, "csv": csv_file, "n": len(utts)}
 
 
@@ -405,8 +396,8 @@ def _hip_head(config: Dict, dev, mode: str, modalities: int):
 
 def _run_hip(head, config: Dict, names: Sequence[str], dev, modalities: int):
     """``names`` through the head on the device, HIP_BATCH files per packed ragged batch -> (indices of the files done, their logit rows,
-    number of files failed).  A batch whose range-guard word or ser_gru_v error word is set is retried file by file; a file that still fails
-    gets a printed line and no row, as in the baseline driver."""
+    number of files failed).  A batch whose range-guard word or ser_gru_v error word is set, or whose forward raises, goes through
+    ``batchloop.run_or_each``: retried file by file, and a file that still fails gets a printed line and no row."""
     lazy = [config[f"lazy_dir{i + 1}"] for i in range(modalities)]
     done, rows, failed = [], [], 0
 
@@ -447,22 +438,8 @@ def _run_hip(head, config: Dict, names: Sequence[str], dev, modalities: int):
                 items.append((i + k, name, *[a.float().contiguous() for a in feats]))
             except Exception as e:                              # noqa: BLE001  (per-file failure, as in the extraction drivers)
                 fail(name, e)
-        if not items:
-            continue
-        try:
-            err = run(items)
-        except Exception as e:                                  # noqa: BLE001
-            err = e
-        if err is not None and len(items) > 1:                  # one bad file must not drop its neighbours
-            for it in items:
-                try:
-                    e1 = run([it])
-                except Exception as e:                          # noqa: BLE001
-                    e1 = e
-                if e1 is not None:
-                    fail(it[1], e1)
-        elif err is not None:
-            fail(items[0][1], err)
+        if items:
+            run_or_each(items, run, lambda it, e: fail(it[1], e))
     return done, rows, failed
 
 
@@ -490,17 +467,9 @@ def _evaluate_hip(config: Dict, seed: int, device: Optional[str], mode: str, mod
         loss = float(ce_weight_category(logits_all, labels_all, None))
         f1 = macro_f1(labels_all.max(dim=1)[1].numpy(), torch.argmax(logits_all, dim=1).numpy())
     log.info(f"|Metrics| eval_loss = {loss} eval f1 = {f1}")
-    os.makedirs(os.path.join(model_path, "results"), exist_ok=True)
-    csv_file = os.path.join(model_path, "results", "dev.csv")
-    with open(csv_file, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(["Filename", "Prediction"] + [f"class_{i}_prob" for i in range(len(CLASSES))])
-        for row, utt in zip(rows, done):
-            w.writerow([utt, CLASS_LETTERS[int(np.argmax(row))]] + [f"{p:.4f}" for p in row.flatten()])
+    csv_file = write_result_csv(model_path, "dev", "Filename", done, rows, CLASS_LETTERS)
     print(f"{len(done)} rows written, {failed} files failed")
-    for h in list(log.handlers):
-        h.close()
-        log.removeHandler(h)
+    close_logger(log)
     return {"eval_loss": loss, "eval_f1": f1, "csv": csv_file, "n": len(done), "failed": failed}
 
 
@@ -554,18 +523,10 @@ def score(config: Dict, seed: int = 7, device: Optional[str] = None, engine: str
                 logits = model(*_inputs(batch, dev))
             rows.extend(logits.cpu().numpy())
             done.extend(batch["utt"])
-    os.makedirs(os.path.join(model_path, "results"), exist_ok=True)
-    csv_file = os.path.join(model_path, "results", "test.csv")
-    with open(csv_file, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(["FileName", "Prediction"] + [f"class_{i}_prob" for i in range(len(CLASSES))])      # "FileName" here, "Filename" in dev.csv
-        for row, utt in zip(rows, done):
-            w.writerow([utt, CLASS_LETTERS[int(np.argmax(row))]] + [f"{p:.4f}" for p in np.asarray(row).flatten()])
+    csv_file = write_result_csv(model_path, "test", "FileName", done, rows, CLASS_LETTERS)      # "FileName" here, "Filename" in dev.csv
     if engine == "hip":
         print(f"{len(done)} rows written, {failed} files failed")
-    for h in list(log.handlers):
-        h.close()
-        log.removeHandler(h)
+    close_logger(log)
     return {"csv": csv_file, "n": len(done), "failed": failed}
 
 

@@ -10,7 +10,6 @@ ser_select_rows_v launch per stream): of a Whisper window only the ``min(ceil(le
 (bin/predict_cat_from_wav.py).  One GPU, 16 kHz input."""
 from __future__ import annotations
 
-import csv
 import ctypes as C_
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -20,6 +19,7 @@ import numpy as np
 import torch
 
 from . import config as C
+from .batchloop import close_logger, make_batches, prefetch, run_or_each, write_result_csv
 from ._lib import SelectRowsArgs, SerHipError, check, lib
 from .engine import FusionHead, RowSource, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
 from .frontend import whisper_saved_rows
@@ -265,7 +265,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     or the mean.  ``mode`` / ``text_mode`` / ``head_mode``: numerics of the audio encoders, the text encoders and the head (default: the
     first encoder's).  ``tokenize``: texts -> (input_ids, attention_mask), default ``driver.hf_tokenize_fn``.  A file that cannot be
     decoded, has no transcript or is empty is printed and gets no row; a batch whose range-guard or GRU error word is set is retried file
-    by file.  ``transcribe``: the texts are the Whisper stream's own transcripts (``FusionPredictor.transcribe_with``) and ``txt_dir`` is not
+    by file (``batchloop.run_or_each``).  ``transcribe``: the texts are the Whisper stream's own transcripts (``FusionPredictor.transcribe_with``) and ``txt_dir`` is not
     read; ``spec`` (default: the checkpoint's generation_config.json, with ``language``) and ``detokenize`` (default: the checkpoint's
     tokenizer from local files, else the ids as numbers) belong to it.  Returns {"csv", "n", "failed"}."""
     from . import head as HD
@@ -368,57 +368,29 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
             return name, None, None, None, e
 
     def run(items):
-        """items: (index, name, waveform, transcript, rows) -> error message or None; appends the rows of a clean batch"""
+        """items: (name, waveform, transcript, rows); appends the rows of a clean batch, raises what a failed one raises"""
         ids = mask = None
         if has_text and not transcribe:
-            ids, mask = tokenize([it[3] for it in items])
-        out = pred.predict([it[2] for it in items], ids, mask, [it[4] for it in items] if has_rows else None)
+            ids, mask = tokenize([it[2] for it in items])
+        out = pred.predict([it[1] for it in items], ids, mask, [it[3] for it in items] if has_rows else None)
         for it, row in zip(items, out):
-            done.append(it[1])
+            done.append(it[0])
             rows_out.append(row)
-        return None
 
-    bs = max(1, int(batch_size))
-    windows = [names[i:i + bs] for i in range(0, len(names), bs)]
     with ThreadPoolExecutor(max_workers=max(1, int(num_workers))) as pool:
-        pending = pool.map(load, windows[0]) if windows else []
-        for wi, window in enumerate(windows):
-            loaded = list(pending)
-            if wi + 1 < len(windows):
-                pending = pool.map(load, windows[wi + 1])               # decode the next batch while the GPU works
+        # the next batch is decoded while the GPU works
+        for loaded in prefetch(make_batches(names, max(1, int(batch_size))), pool, load):
             items = []
-            for k, (name, wave, text, third, err) in enumerate(loaded):
+            for name, wave, text, third, err in loaded:
                 if err is not None:
                     fail(name, err)
                 else:
-                    items.append((wi * bs + k, name, wave, text, third))
-            if not items:
-                continue
-            try:
-                err = run(items)
-            except Exception as e:                                      # noqa: BLE001
-                err = e
-            if err is not None and len(items) > 1:                      # one bad file must not drop its neighbours
-                for it in items:
-                    try:
-                        e1 = run([it])
-                    except Exception as e:                              # noqa: BLE001
-                        e1 = e
-                    if e1 is not None:
-                        fail(it[1], e1)
-            elif err is not None:
-                fail(items[0][1], err)
-    os.makedirs(os.path.join(model_path, "results"), exist_ok=True)
-    csv_file = os.path.join(model_path, "results", "test.csv")
-    with open(csv_file, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(["FileName", "Prediction"] + [f"class_{i}_prob" for i in range(len(HD.CLASSES))])
-        for row, utt in zip(rows_out, done):
-            w.writerow([utt, HD.CLASS_LETTERS[int(np.argmax(row))]] + [f"{p:.4f}" for p in np.asarray(row).flatten()])
+                    items.append((name, wave, text, third))
+            if items:
+                run_or_each(items, run, lambda it, e: fail(it[0], e))                         # one bad file must not drop its neighbours
+    csv_file = write_result_csv(model_path, "test", "FileName", done, rows_out, HD.CLASS_LETTERS)
     print(f"{len(done)} rows written, {failed} files failed")
-    for h in list(log.handlers):
-        h.close()
-        log.removeHandler(h)
+    close_logger(log)
     return {"csv": csv_file, "n": len(done), "failed": failed}
 
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import config as C
+from .batchloop import make_batches, run_or_each
 
 N_SAMPLES = 480000            # 30 s: WhisperFeatureExtractor cuts longer input, and so does this path
 BATCH = 16
@@ -23,8 +24,9 @@ BATCH = 16
 
 class WhisperTranscriber:
     """``transcribe(waves)``: per utterance the generated ids without the prompt, up to and excluding eos (None for a file that failed).
-    Batches of ``BATCH`` alternate between the encoder's and decoder's two slots.  Failure contract (the project's): a batch whose fp16
-    range-guard word or decoder error word is set is retried file by file; a file that still fails is printed and left out."""
+    Batches of ``BATCH`` alternate between the encoder's and decoder's two slots.  A batch whose fp16 range-guard word or decoder error
+    word is set goes through ``batchloop.run_or_each``: retried file by file, a file that still fails is printed and left out.  What
+    the encoder or the decoder raises is not caught."""
 
     def __init__(self, encoder, decoder, spec: C.GenerationSpec):
         self.enc, self.dec, self.spec = encoder, decoder, spec
@@ -45,22 +47,16 @@ class WhisperTranscriber:
         names = list(names) if names is not None else [f"utterance {i}" for i in range(len(waves))]
         out: List[Optional[List[int]]] = [None] * len(waves)
         self.last_languages = [None] * len(waves)
-        for n, i in enumerate(range(0, len(waves), BATCH), start=int(first_batch)):
-            idx = list(range(i, min(i + BATCH, len(waves))))
-            res, failed, _ = self._batch([waves[j] for j in idx], n % 2)
-            if failed and len(idx) > 1:
-                for j in idx:                               # retried file by file
-                    r1, f1, _ = self._batch([waves[j]], n % 2)
-                    if f1:
-                        print(f"Failed to process {names[j]}: decoder error word {r1.err:#x}, range-guard bits {r1.range_bits:#x}")
-                    else:
-                        out[j], self.last_languages[j] = r1.lists[0], int(r1.languages[0])
-                continue
-            if failed:
-                print(f"Failed to process {names[idx[0]]}: decoder error word {res.err:#x}, range-guard bits {res.range_bits:#x}")
-                continue
-            for k, j in enumerate(idx):
-                out[j], self.last_languages[j] = res.lists[k], int(res.languages[k])
+        for n, idx in enumerate(make_batches(range(len(waves)), BATCH), start=int(first_batch)):
+            def run(js):
+                res, failed, _ = self._batch([waves[j] for j in js], n % 2)
+                if failed:
+                    return res
+                for k, j in enumerate(js):
+                    out[j], self.last_languages[j] = res.lists[k], int(res.languages[k])
+
+            run_or_each(idx, run, lambda j, res: print(f"Failed to process {names[j]}: decoder error word {res.err:#x}, "
+                                                       f"range-guard bits {res.range_bits:#x}"), catch=())
         return out
 
     def texts(self, waves: Sequence[np.ndarray], tokenizer, names: Optional[Sequence[str]] = None) -> List[Optional[str]]:

@@ -85,6 +85,69 @@ def test_speech_driver_config0(tmp_path, capsys):
         assert float((got - ref).abs().max() / max(1.0, float(ref.abs().max()))) < 1e-3
 
 
+def test_speech_driver_failed_submit_costs_only_its_file(tmp_path, capsys):
+    """The slot pipeline with real streams and arenas (batchloop.SlotPipeline under driver._run): four batches of two, and the second
+    holds a file below the conv stack's receptive field, so its ``submit`` raises with the first batch in flight.  The driver finishes
+    what is in flight, extracts that batch file by file and goes on: the short file gets its one line, its neighbour and the files of
+    the batches before and after are written, and every file holds bit for bit what a forward of that file alone gives (a ragged
+    batch is arithmetically the batch-of-one loop: test_batched_equals_single)."""
+    import struct
+    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd import driver
+    from interspeech_ser_amd.frontend import load_wav_16k
+    wav_dir, out = tmp_path / "wav", tmp_path / "pt"
+    wav_dir.mkdir()
+    lengths = (700, 1234, 2501, 3333, 4800, 6001, 8000)                  # 700 samples: one frame, the smallest utterance the stack takes
+    for i, n in enumerate(lengths):
+        write_wav(wav_dir / f"u{i}.wav", synth(30 + i, n))
+    # 300 samples behind a 7 000-byte chunk the reader skips: the driver orders files by their size, which puts this one beside u4
+    pcm = (np.clip(synth(99, 300), -1, 1) * 32767).astype("<i2").tobytes()
+    chunks = b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, 16000, 32000, 2, 16) + b"junk" + struct.pack("<I", 7000) + bytes(7000) \
+        + b"data" + struct.pack("<I", len(pcm)) + pcm
+    (wav_dir / "short.wav").write_bytes(b"RIFF" + struct.pack("<I", 4 + len(chunks)) + b"WAVE" + chunks)
+    sizes = {f: os.path.getsize(wav_dir / f) for f in os.listdir(wav_dir)}
+    assert sizes["u4.wav"] > sizes["short.wav"] > sizes["u3.wav"] and len(load_wav_16k(str(wav_dir / "short.wav"))) == 300
+    made, submits, collected = [], [], []
+
+    class Watched(driver._Extractor):
+        def submit(self, waves, *a, **k):
+            submits.append([len(w) for w in waves])
+            try:
+                return super().submit(waves, *a, **k)
+            except Exception:
+                submits[-1].append("raised")
+                collected.append(None)                                   # how many batches had been collected when it raised
+                raise
+
+        def collect(self, ticket):
+            collected.append(len(ticket["lengths"]))
+            return super().collect(ticket)
+
+    def factory(args, whisper, device):
+        made.append(Watched(args, whisper, device))
+        return made[0]
+
+    C._REGISTRY["tiny-batchloop-test"] = C.TINY_WAVLM
+    try:
+        rc = driver.run_speech(["--ssl_type", "tiny-batchloop-test", "--wav_dir", str(wav_dir), "--save_path", str(out), "--synthetic_weights",
+                                "--mode", "f16x", "--batch_size", "2", "--use_n_layer", "--n_layer", "2"], extractor_factory=factory)
+    finally:
+        C._REGISTRY.pop("tiny-batchloop-test")
+    text = capsys.readouterr().out
+    assert rc == 0 and "7 utterances" in text
+    failures = [ln for ln in text.splitlines() if ln.startswith("Failed to process")]
+    assert len(failures) == 1 and "short.wav" in failures[0] and "receptive field" in failures[0], text
+    assert sorted(os.listdir(out)) == [f"u{i}.pt" for i in range(7)]                      # u4, the short file's batch neighbour, among them
+    # the path taken: the second submit raised, before the first batch had been collected (its ticket in flight), and nothing else did
+    assert submits == [[8000, 6001], [4800, 300, "raised"], [3333, 2501], [1234, 700]] and collected == [None, 2, 2, 2]
+    ex = made[0]
+    torch.cuda.synchronize()
+    for i, n in enumerate(lengths):
+        alone = ex.extract([load_wav_16k(str(wav_dir / f"u{i}.wav"))], 2)[0]
+        got = torch.load(out / f"u{i}.pt")
+        assert got.shape == (C.TINY_WAVLM.frames_for(n), C.TINY_WAVLM.hidden) and torch.equal(got, alone), f"u{i}.pt"
+
+
 def test_unknown_hub_name_resolves_through_the_snapshot_config_json(tmp_path, capsys, monkeypatch):
     """a3: ``AutoModel.from_pretrained(--ssl_type)`` works for any hub id because the snapshot carries its own config.json
     (preprocess_speech.py:111-112).  A fine-tune under a name the built-in table does not know -- offline HF cache layout
