@@ -718,6 +718,68 @@ typedef struct ser_dec_select_args {
 } ser_dec_select_args;
 int ser_dec_select_v(const ser_dec_select_args* args, void* stream);
 
+/* a26 (added under ABI 18: new entry points, ser_cmd members and SER_OP codes only; nothing existing changed)  The prosody stream: the
+ * NaturalSpeech 3 / FACodec feature the reference's three-stream heads read as their third input (preprocessing/preprocess_ns3_prosody.py;
+ * src/ns3/facodec.py get_prosody_feature / get_processed_style_embedding).  Of that model only a 20-bin log-mel, melspec_linear, the four
+ * pre-LayerNorm layers of melspec_encoder and the first quantizer reach the saved tensor.  Three kernels are its own; the layers run on
+ * ser_layernorm_v, ser_gemm and ser_attention_v.
+ *
+ * ser_prosody_mel_v: packed ragged waveforms -> log-mel rows and layer 0's input rows.  Utterance b (n = sample_offs[b + 1] - sample_offs[b]
+ * samples, n >= 400: the CALLER's check) has T = n / 200 + 1 = frame_offs[b + 1] - frame_offs[b] frames: the reference zero-pads to 200 T
+ * samples, reflect-pads 412 each side and runs torch.stft(n_fft 1024, hop 200, win 800, center=False), so frame t is the 800 samples
+ * 200 t - 300 .. 200 t + 499 of the zero-padded wave, mirrored at 0 and at 200 T - 1, under the periodic Hann window.  Per frame:
+ *   X[k] = sum_j x[j] dft[j][k]     dft [800][n_bins] pairs of float64 (w[j] cos, -w[j] sin)(2 pi k (j + 112) / 1024), built by the host
+ *   mel[m] = log(max(sum_k melw[m][k] sqrt(re^2 + im^2 + 1e-9), 1e-5))       melw fp32 [n_mels][n_bins]: rows of the Slaney basis over its
+ *                                                                             non-zero bins (n_bins <= 64, n_mels <= 32)
+ * all in float64 with ascending j / k, rounded to fp32 once -> mel_out [rows][n_mels] (may be NULL).  With out != NULL also
+ *   out[row][d] = lin_b[d] + sum_m lin_w[d][m] * mel[m]   (fp32 FMAs on the rounded log-mel, ascending m; lin_b carries the position-0
+ *   encoding the reference adds to every frame).  max_frames (the longest T) sizes the grid; B <= 65535.  A frame's result depends on its
+ *   own utterance alone. */
+typedef struct ser_prosody_mel_args {
+    const float* wav; const int64_t* sample_offs; const int32_t* frame_offs;
+    const double* dft; const float* mel;
+    const float* lin_w; const float* lin_b;
+    float* mel_out;
+    float* out; int64_t ldo;
+    int32_t B, max_frames, n_bins, n_mels, D, reserved0;
+} ser_prosody_mel_args;
+int ser_prosody_mel_v(const ser_prosody_mel_args* args, void* stream);
+
+/* ser_fvq_v: one factorized quantizer's lookup (src/ns3/quantize/fvq.py decode_latents + out_proj) on fp32 rows z [rows][ldz]:
+ *   z_e = w_in z + b_in (w_in fp32 [8][D], weight norm folded);  e = z_e / max(|z_e|, 1e-12);
+ *   idx = argmin_n |e|^2 - 2 e . codes[n] + |codes[n]|^2      codes fp32 [n_codes][8], L2-normalised by the host; the lowest n on a tie;
+ *   gap = second smallest distance - smallest (fp32; +inf with one code);  out row = table[idx]   table fp32 [n_codes][ld_table] =
+ *   out_proj of the RAW code, built once at load.
+ * One wave per row, float64 products and sums.  Writes idx (int32 [rows]), gap ([rows], may be NULL), the row as out_f32 and / or as
+ * operand planes out_act in `mode` (SER_MODE_BF16 / FP32X / FP16 / FP16X; the fp16 formats report into range_flag, may be NULL).  A row
+ * whose z_e is not finite ORs bit 0 into *err (may be NULL) and takes code 0: the batch fails, as with ser_dec_select_v's error word.
+ * D % 4 == 0, D <= 2048, code_dim == 8, pitches multiples of 4, everything 16-byte aligned. */
+typedef struct ser_fvq_args {
+    const float* z; int64_t ldz;
+    const float* w_in; const float* b_in;
+    const float* codes;
+    const float* table; int64_t ld_table;
+    int32_t* idx; float* gap;
+    float* out_f32; int64_t ldo_f32;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    uint32_t* range_flag; uint32_t* err;
+    int32_t rows, D, n_codes, code_dim, mode, reserved0;
+} ser_fvq_args;
+int ser_fvq_v(const ser_fvq_args* args, void* stream);
+
+/* ser_act_rows_v: fp32 rows x [rows][ldx] -> GEMM operand planes in `mode` (SER_MODE_BF16 / FP32X / FP16 / FP16X) at row out_rowmap[m]
+ * (NULL: m), with relu == 1 as max(x, 0): the ReLU between the prosody encoder's FC1 (a k = 5 convolution, run as an implicit ser_gemm)
+ * and FC2 (src/ns3/transformer.py TransformerFFNLayer), and LayerNorm 2's rows into that convolution's zero-halo'd operand copy.  Wave
+ * per row; D % 4 == 0, D <= 2048, pitches multiples of 4.  range_flag: the fp16 range guard, may be NULL. */
+typedef struct ser_act_rows_args {
+    const float* x; int64_t ldx;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    const int32_t* out_rowmap;
+    uint32_t* range_flag;
+    int32_t relu, mode, rows, D;
+} ser_act_rows_args;
+int ser_act_rows_v(const ser_act_rows_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -730,6 +792,9 @@ int ser_dec_select_v(const ser_dec_select_args* args, void* stream);
 #define SER_OP_DEC_EMBED 10
 #define SER_OP_DEC_ATTN 11
 #define SER_OP_DEC_SELECT 12
+#define SER_OP_PROSODY_MEL 13
+#define SER_OP_FVQ 14
+#define SER_OP_ACT_ROWS 15
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -745,6 +810,9 @@ typedef struct ser_cmd {
         ser_dec_embed_args   dec_embed;
         ser_dec_attn_args    dec_attn;
         ser_dec_select_args  dec_select;
+        ser_prosody_mel_args prosody_mel;
+        ser_fvq_args         fvq;
+        ser_act_rows_args    act_rows;
     } u;
 } ser_cmd;
 

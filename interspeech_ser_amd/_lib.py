@@ -271,6 +271,37 @@ class DecSelectArgs(C.Structure):
     ]
 
 
+class ProsodyMelArgs(C.Structure):
+    """Mirror of ``ser_prosody_mel_args``."""
+    _fields_ = [
+        ("wav", c_void_p), ("sample_offs", c_void_p), ("frame_offs", c_void_p),
+        ("dft", c_void_p), ("mel", c_void_p), ("lin_w", c_void_p), ("lin_b", c_void_p),
+        ("mel_out", c_void_p), ("out", c_void_p), ("ldo", c_i64),
+        ("B", C.c_int32), ("max_frames", C.c_int32), ("n_bins", C.c_int32), ("n_mels", C.c_int32), ("D", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class FvqArgs(C.Structure):
+    """Mirror of ``ser_fvq_args``."""
+    _fields_ = [
+        ("z", c_void_p), ("ldz", c_i64), ("w_in", c_void_p), ("b_in", c_void_p), ("codes", c_void_p),
+        ("table", c_void_p), ("ld_table", c_i64), ("idx", c_void_p), ("gap", c_void_p),
+        ("out_f32", c_void_p), ("ldo_f32", c_i64), ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64),
+        ("range_flag", c_void_p), ("err", c_void_p),
+        ("rows", C.c_int32), ("D", C.c_int32), ("n_codes", C.c_int32), ("code_dim", C.c_int32), ("mode", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class ActRowsArgs(C.Structure):
+    """Mirror of ``ser_act_rows_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64), ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64),
+        ("out_rowmap", c_void_p), ("range_flag", c_void_p),
+        ("relu", C.c_int32), ("mode", C.c_int32), ("rows", C.c_int32), ("D", C.c_int32),
+    ]
+
+
+FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
 DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked logit was not finite
 DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
 
@@ -278,7 +309,8 @@ DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
 class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
-                ("pos_ln", PosLnArgs), ("dec_embed", DecEmbedArgs), ("dec_attn", DecAttnArgs), ("dec_select", DecSelectArgs)]
+                ("pos_ln", PosLnArgs), ("dec_embed", DecEmbedArgs), ("dec_attn", DecAttnArgs), ("dec_select", DecSelectArgs),
+                ("prosody_mel", ProsodyMelArgs), ("fvq", FvqArgs), ("act_rows", ActRowsArgs)]
 
 
 class Cmd(C.Structure):
@@ -288,12 +320,14 @@ class Cmd(C.Structure):
 
 OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS, OP_POS_LN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_DEC_EMBED, OP_DEC_ATTN, OP_DEC_SELECT = 10, 11, 12
+OP_PROSODY_MEL, OP_FVQ, OP_ACT_ROWS = 13, 14, 15
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
                   "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_xattn_mh_args": XattnMhArgs, "ser_attn_pool_args": AttnPoolArgs,
                   "ser_fusion_cls_args": FusionClsArgs, "ser_select_rows_args": SelectRowsArgs, "ser_dec_embed_args": DecEmbedArgs, "ser_dec_attn_args": DecAttnArgs,
-                  "ser_dec_select_args": DecSelectArgs, "ser_cmd": Cmd}
+                  "ser_dec_select_args": DecSelectArgs, "ser_prosody_mel_args": ProsodyMelArgs, "ser_fvq_args": FvqArgs,
+                  "ser_act_rows_args": ActRowsArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -326,6 +360,9 @@ _SIGNATURES = {
     "ser_dec_embed_v": (c_int, [c_void_p, c_void_p]),
     "ser_dec_attn_v": (c_int, [c_void_p, c_void_p]),
     "ser_dec_select_v": (c_int, [c_void_p, c_void_p]),
+    "ser_prosody_mel_v": (c_int, [c_void_p, c_void_p]),
+    "ser_fvq_v": (c_int, [c_void_p, c_void_p]),
+    "ser_act_rows_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

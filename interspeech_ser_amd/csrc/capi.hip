@@ -83,6 +83,18 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_dec_select_v(&c.u.dec_select, stream);
                 break;
             }
+            case SER_OP_PROSODY_MEL: {
+                rc = ser_prosody_mel_v(&c.u.prosody_mel, stream);
+                break;
+            }
+            case SER_OP_FVQ: {
+                rc = ser_fvq_v(&c.u.fvq, stream);
+                break;
+            }
+            case SER_OP_ACT_ROWS: {
+                rc = ser_act_rows_v(&c.u.act_rows, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

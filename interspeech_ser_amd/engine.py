@@ -2532,6 +2532,225 @@ class WhisperDecoder(_LaunchHost):
         return DecodeResult(ids[:, :n], ids[:, 1].copy(), lists, margins[:, : n - 1], bits, err)
 
 
+class ProsodyFeatures(HiddenStates):
+    """What ``ProsodyEncoder.forward`` returns: ``rows`` [M, D] fp32 (the tensor the reference saves per file, packed), ``codes`` [M]
+    int32, ``gaps`` [M] fp32 (distance of the second-nearest code minus the nearest's) and ``z`` [M, D] (the encoder's last LayerNorm, the
+    quantizer's input), all on the device and valid until the slot's next forward; utterance b owns rows frame_offs[b]:frame_offs[b + 1]
+    with ``len_b // 200 + 1`` frames.  As ``HiddenStates`` it holds one state -- the rows -- so that a head reads them in place
+    (``RowSource``).  ``err``: ser_fvq_v's error word (a latent that was not finite)."""
+
+    def __init__(self, rows, codes, gaps, z, mel, frame_offs, range_flag, frame_offs_dev, err):
+        super().__init__(rows.unsqueeze(0), frame_offs, range_flag=range_flag, frame_offs_dev=frame_offs_dev)
+        self.rows, self.codes, self.gaps, self.z, self.mel, self.err = rows, codes, gaps, z, mel, err
+
+    def take_range_bits(self, pinned_out: Optional[torch.Tensor] = None):
+        """The guard bits of the forward, with bit 0 set as well when the quantizer's error word is: such a batch fails like a range-guard
+        hit.  Synchronous (the error word is read back); both words are cleared."""
+        bits = super().take_range_bits() | (1 if int(self.err.item()) else 0)
+        self.err.zero_()
+        if pinned_out is not None:
+            pinned_out.fill_(bits)
+            return None
+        return bits
+
+
+class ProsodyEncoder(_LaunchHost):
+    """The prosody stream of the reference's three-stream heads (preprocessing/preprocess_ns3_prosody.py) on libserhip: NS3 log-mel +
+    melspec_linear (ser_prosody_mel_v), melspec_encoder's pre-LayerNorm layers -- ser_layernorm_v, ser_gemm (FC1's k = 5 convolution as an
+    implicit GEMM over a zero-halo'd copy, two zero rows around each utterance), ser_attention_v, ser_act_rows_v for the ReLU -- and the
+    first quantizer's lookup (ser_fvq_v).  ``state_dict``: ns3_facodec_decoder_v2.bin's (``prosody.load_state_dict``); geometry from its
+    shapes, ``heads`` is not in them.  Every utterance alone, as the reference's batch of one; 16 kHz input of at least 400 samples."""
+
+    use_tape = True
+
+    def __init__(self, state_dict, device="cuda:0", mode: str = "f16x", heads: int = 4):
+        from . import prosody as P
+        from .frontend import prosody_dft_table, prosody_mel_filters
+        if mode not in POST_LN_MODES:
+            raise ValueError(f"the prosody encoder supports the {', '.join(POST_LN_MODES)} numerics modes")
+        fp16_planes = mode == "f16x" and _os.environ.get("SER_NO_RANGE_GUARD", "0") != "1"
+        super().__init__(device, mode, MODES[mode], MODES[mode], fp16_planes)
+        w = P.prepare(state_dict, heads)
+        self.spec = spec = w["spec"]
+        melw = prosody_mel_filters(spec.n_mels)
+        self.n_bins = int(melw.shape[1])
+        self.melw = self._dev_f32(torch.from_numpy(melw))
+        self.dft = torch.from_numpy(prosody_dft_table(self.n_bins)).to(self.device)
+        self.lin_w, self.lin_b = self._dev_f32(w["lin_w"]), self._dev_f32(w["lin_b"])
+        pair = lambda t: (self._dev_f32(t[0]), self._dev_f32(t[1]))
+        self.layers = []
+        for i, lw in enumerate(w["layers"]):
+            p = f"{P.ENC}.layers.{i}"
+            self.layers.append(dict(
+                ln1=pair(lw["ln1"]), ln2=pair(lw["ln2"]),
+                qkv=self._linear(*lw["qkv"], name=p + ".self_attn.in_proj_weight"), out=self._linear(*lw["out"], name=p + ".self_attn.out_proj.weight"),
+                fc1=self._linear(*lw["fc1"], name=p + ".ffn.ffn_1.weight"), fc2=self._linear(*lw["fc2"], name=p + ".ffn.ffn_2.weight")))
+        self.last_ln = pair(w["last_ln"])
+        self.w_in, self.b_in = self._dev_f32(w["w_in"]), self._dev_f32(w["b_in"])
+        self.codes, self.table = self._dev_f32(w["codes"]), self._dev_f32(w["table"])
+        self._arenas: Dict[int, dict] = {}
+
+    upload = SpeechEncoder.upload
+    download = SpeechEncoder.download
+
+    # ------------------------------------------------------------------ buffers
+    def _arena(self, slot: int, M: int, B: int) -> dict:
+        """grow-only buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena)"""
+        ar = self._arenas.get(slot)
+        if ar is not None and ar["cap_M"] >= M and ar["cap_B"] >= B:
+            return ar
+        M, B = max(M, ar["cap_M"] if ar else 0), max(B, ar["cap_B"] if ar else 0)
+        sp, dev = self.spec, self.device
+        D, F = sp.hidden, sp.ffn
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ar = dict(cap_M=M, cap_B=B, plan=None)
+        ar["x"], ar["h"], ar["tmp"], ar["z"], ar["rows"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D), f32(M, D)
+        ar["f1"], ar["mel"], ar["gaps"] = f32(M, F), f32(M, sp.n_mels), f32(M)
+        ar["codes"] = torch.empty(M, dtype=torch.int32, device=dev)
+        ar["xa"], ar["ctx"], ar["qkv"], ar["ffn"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, 3 * D), self._new_act(M, F)
+        ar["halo"] = self._new_act(M + (sp.kernel // 2) * (B + 1), D, zero=True)
+        ar["halo_rowmap"] = torch.empty(M, dtype=torch.int32, device=dev)
+        ar["fc1_rowoff"] = torch.empty(M, dtype=torch.int32, device=dev)
+        ar["sample_offs"] = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        ar["frame_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        ar["base"] = torch.empty((2, B), dtype=torch.int64, device=dev)
+        ar["err"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.fp16_planes:
+            ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._arenas[slot] = ar
+        return ar
+
+    def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
+        from .frontend import PROSODY_MIN_SAMPLES, prosody_frames
+        lengths = tuple(int(n) for n in lengths)
+        B = len(lengths)
+        if B == 0 or min(lengths) < PROSODY_MIN_SAMPLES:
+            raise ValueError(f"utterance shorter than {PROSODY_MIN_SAMPLES} samples: it cannot be reflect-padded (the reference fails such a file)")
+        T = [prosody_frames(n) for n in lengths]
+        offs = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+        M, Tmax, half = int(offs[-1]), max(T), self.spec.kernel // 2
+        ar = self._arena(slot, M, B)
+        if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
+            return ar["plan"]
+        st, D = _stream(), self.spec.hidden
+        ar["sample_offs"][: B + 1].copy_(torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))
+        ar["frame_offs_all"][: B + 1].copy_(torch.from_numpy(offs.astype(np.int32)))
+        # zero-halo'd copy of FC1's input: [half zero rows][utt 0][half zero rows][utt 1] ... [half zero rows]; frame t of utterance b sits at
+        # row half (b + 1) + offs[b] + t, and its k taps start ``half`` rows earlier
+        starts = np.array([half * (b + 1) + offs[b] for b in range(B)], dtype=np.int64)
+        ar["base"][:, :B].copy_(torch.from_numpy(np.stack([starts, starts - half])))
+        fo = ar["frame_offs_all"]
+        check(lib.ser_ragged_index(fo.data_ptr(), ar["base"][0].data_ptr(), B, 1, 1, 1, ar["halo_rowmap"].data_ptr(), M, st), "ser_ragged_index")
+        check(lib.ser_ragged_index(fo.data_ptr(), ar["base"][1].data_ptr(), B, 1, D, 8, ar["fc1_rowoff"].data_ptr(), M, st), "ser_ragged_index")
+        if ar["plan"] is not None:
+            ar["halo"].t.zero_()                                # the halo rows sit elsewhere than in the previous batch
+        pl = dict(ar)
+        pl.update(lengths=lengths, B=Sz(B, "B"), M=Sz(M, "M"), Tmax=Sz(Tmax, "Tmax"), sizes=dict(B=B, M=M, Tmax=Tmax),
+                  frame_offs=fo[: B + 1], frame_offs_host=[int(v) for v in offs])
+        ar["plan"] = pl
+        return pl
+
+    # ------------------------------------------------------------------ launches
+    def _mel(self, pl, packed_wave: torch.Tensor, with_linear: bool = True) -> None:
+        sp = self.spec
+        a = self._cmd("prosody_mel")
+        a.wav, a.sample_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["frame_offs"].data_ptr()
+        a.dft, a.mel, a.mel_out = self.dft.data_ptr(), self.melw.data_ptr(), pl["mel"].data_ptr()
+        if with_linear:
+            a.lin_w, a.lin_b, a.out, a.ldo, a.D = self.lin_w.data_ptr(), self.lin_b.data_ptr(), pl["x"].data_ptr(), sp.hidden, sp.hidden
+        a.B, a.max_frames, a.n_bins, a.n_mels = pl["B"], pl["Tmax"], self.n_bins, sp.n_mels
+        self._issue(_lib.OP_PROSODY_MEL, a, "ser_prosody_mel", input="wav", B=pl["B"], max_frames=pl["Tmax"])
+
+    def _act_rows(self, x: torch.Tensor, ldx: int, out: Act, rows: int, D: int, relu: bool, rowmap=None) -> None:
+        a = self._cmd("act_rows")
+        a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), ldx, out.ptr, out.cols, out.plane_stride
+        a.out_rowmap, a.range_flag = _ptr(rowmap), self._flag
+        a.relu, a.mode, a.rows, a.D = int(relu), self.mode, rows, D
+        self._issue(_lib.OP_ACT_ROWS, a, "ser_act_rows", rows=rows)
+
+    def _attn(self, pl) -> None:
+        sp, qkv, out = self.spec, pl["qkv"], pl["ctx"]
+        a = self._cmd("attention")
+        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
+        a.q_col, a.k_col, a.v_col, a.B = 0, sp.hidden, 2 * sp.hidden, pl["B"]
+        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
+        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
+        a.H, a.dh, a.scale, a.mode = sp.heads, sp.head_dim, -1.0, self.mode          # q is pre-scaled
+        self._issue(_lib.OP_ATTENTION, a, "ser_attention", B=pl["B"], max_frames=pl["Tmax"])
+
+    def _fvq(self, pl) -> None:
+        sp = self.spec
+        a = self._cmd("fvq")
+        a.z, a.ldz, a.w_in, a.b_in, a.codes = pl["z"].data_ptr(), sp.hidden, self.w_in.data_ptr(), self.b_in.data_ptr(), self.codes.data_ptr()
+        a.table, a.ld_table, a.idx, a.gap = self.table.data_ptr(), sp.hidden, pl["codes"].data_ptr(), pl["gaps"].data_ptr()
+        a.out_f32, a.ldo_f32, a.err = pl["rows"].data_ptr(), sp.hidden, pl["err"].data_ptr()
+        a.rows, a.D, a.n_codes, a.code_dim, a.mode = pl["M"], sp.hidden, sp.n_codes, sp.code_dim, self.mode
+        self._issue(_lib.OP_FVQ, a, "ser_fvq", rows=pl["M"])
+
+    def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
+        sp = self.spec
+        M, D, F = pl["M"], sp.hidden, sp.ffn
+        scale = sp.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
+        x, h = pl["x"], pl["h"]
+        self._mel(pl, packed_wave)
+        for lay in self.layers:
+            # x += MHA(LN1(x))
+            self._layernorm(x, D, lay["ln1"], M, D, out_act=pl["xa"], eps=1e-5)
+            self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
+            self._attn(pl)
+            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=h, ldo_f32=D)
+            # h += Linear(ReLU(Conv1d_k5(LN2(h)))): LN2's rows go to their halo'd positions, FC1 reads k consecutive rows per frame
+            self._layernorm(h, D, lay["ln2"], M, D, out_f32=pl["tmp"], eps=1e-5)
+            self._act_rows(pl["tmp"], D, pl["halo"], M, D, relu=False, rowmap=pl["halo_rowmap"])
+            self._gemm(pl["halo"], lay["fc1"], M, a_rowoff=pl["fc1_rowoff"], out_f32=pl["f1"], ldo_f32=F)
+            self._act_rows(pl["f1"], F, pl["ffn"], M, F, relu=True)
+            self._gemm(pl["ffn"], lay["fc2"], M, residual=h, ldr=D, out_f32=x, ldo_f32=D)
+        self._layernorm(x, D, self.last_ln, M, D, out_f32=pl["z"], eps=1e-5)
+        self._fvq(pl)
+
+    def _result(self, pl, flag) -> ProsodyFeatures:
+        M = int(pl["M"])
+        return ProsodyFeatures(pl["rows"][:M], pl["codes"][:M], pl["gaps"][:M], pl["z"][:M], pl["mel"][:M], pl["frame_offs_host"], flag,
+                               pl["frame_offs"], pl["err"])
+
+    def _ingest(self, waves, lengths, slot: int):
+        """(plan, packed samples on the device) of a list of raw waveforms, or of samples the caller packed (``lengths`` given)"""
+        if lengths is not None:
+            return self._plan(lengths, slot), waves
+        waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
+        pl = self._plan([len(w) for w in waves], slot)                # refuses a short wave before anything is uploaded
+        return pl, self.upload(waves, slot)
+
+    @_on_stream
+    def forward(self, waves, lengths: Optional[Sequence[int]] = None, slot: int = 0) -> ProsodyFeatures:
+        """``waves``: a list of raw 16 kHz fp32 waveforms (uploaded here), or with ``lengths`` their packed samples on the device."""
+        pl, waves = self._ingest(waves, lengths, slot)
+        ar = self._arenas[slot]
+        flag = pl.get("range_flag")
+        self._flag = None if flag is None else flag.data_ptr()
+        if not self.use_tape or self.gemm_trace is not None:
+            self._launches(pl, waves)
+        else:
+            tape = ar.get("tape")
+            if tape is None:
+                self._rec = tape = Tape()
+                try:
+                    self._launches(pl, waves)
+                finally:
+                    self._rec = None
+                ar["tape"] = tape
+            tape.inputs["wav"].wav = waves.data_ptr()
+            tape.run(pl["sizes"], self._s())
+        return self._result(pl, flag)
+
+    @_on_stream
+    def log_mel(self, waves, lengths: Optional[Sequence[int]] = None, slot: int = 0) -> torch.Tensor:
+        """the [M, 20] log-mel rows alone (ser_prosody_mel_v without melspec_linear)"""
+        pl, waves = self._ingest(waves, lengths, slot)
+        self._mel(pl, waves, with_linear=False)
+        return pl["mel"][: int(pl["M"])]
+
+
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):
     """``normalize``: the speech families' input normalisation (``do_normalize`` of the checkpoint's feature extractor)."""
     if geo.family == "deberta":

@@ -181,6 +181,36 @@ def whisper_mel_filters(n_mels: int = 128, n_fft: int = 400, sr: int = TARGET_SR
     return fb.astype(np.float32)
 
 
+PROSODY_HOP, PROSODY_WIN, PROSODY_NFFT, PROSODY_MELS = 200, 800, 1024, 20
+PROSODY_MIN_SAMPLES = 400          # a shorter wave cannot be reflect-padded by 412 after its zero padding: the reference fails that file
+
+
+def prosody_frames(num_samples: int) -> int:
+    """Frames of the prosody stream (80 Hz): the reference pads with ``200 - len % 200`` zeros -- a full 200 when the length is
+    already a multiple of 200 (preprocess_ns3_prosody.py:45) -- and its STFT keeps one frame per 200 padded samples."""
+    return int(num_samples) // PROSODY_HOP + 1
+
+
+def prosody_mel_filters(n_keep: int = PROSODY_MELS) -> np.ndarray:
+    """[n_keep, n_bins] fp32: rows 0..n_keep-1 of the 80-filter Slaney basis over 0-8 kHz at n_fft 1024 (``librosa.filters.mel`` as
+    src/ns3/melspec.py:64 calls it, restated: the same construction as ``whisper_mel_filters``), cut after their last non-zero bin
+    (52 of 513 for the 20 rows FACodecEncoderV2.get_prosody_feature keeps).  Checked against transformers' ``mel_filter_bank``; PARITY
+    UNPINNED against librosa's own table, which is not available offline (like the resampler's soxr note above)."""
+    fb = whisper_mel_filters(80, PROSODY_NFFT)[:, :n_keep]                  # [513, n_keep]
+    n_bins = int(np.nonzero(fb.any(axis=1))[0].max()) + 1
+    return np.ascontiguousarray(fb[:n_bins].T)
+
+
+def prosody_dft_table(n_bins: int) -> np.ndarray:
+    """[800, n_bins, 2] float64 (w[j] cos, -w[j] sin)(2 pi k (j + 112) / 1024): the periodic Hann window of 800 (fp32 values, as
+    torch.hann_window yields them) that torch.stft pads centrally to n_fft 1024, times the DFT twiddles of the first n_bins bins."""
+    w = torch.hann_window(PROSODY_WIN, periodic=True, dtype=torch.float32).double().numpy()
+    j = np.arange(PROSODY_WIN, dtype=np.int64) + (PROSODY_NFFT - PROSODY_WIN) // 2
+    r = (j[:, None] * np.arange(n_bins, dtype=np.int64)[None, :]) % PROSODY_NFFT      # exact argument reduction
+    ang = 2.0 * np.pi * r.astype(np.float64) / PROSODY_NFFT
+    return np.ascontiguousarray(np.stack([w[:, None] * np.cos(ang), -w[:, None] * np.sin(ang)], axis=-1))
+
+
 def whisper_saved_rows(num_samples: int, feat_dim: int) -> int:
     """Rows the reference keeps: min(ceil(len/320), feats.shape[1]) where feats is already
     [1500, D], so the cap is the hidden size (preprocess_whisper.py:49-50,75-76)."""

@@ -21,8 +21,9 @@ import torch
 from . import config as C
 from .batchloop import close_logger, make_batches, prefetch, run_or_each, write_result_csv
 from ._lib import SelectRowsArgs, SerHipError, check, lib
-from .engine import FusionHead, RowSource, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
+from .engine import FusionHead, ProsodyEncoder, RowSource, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
 from .frontend import whisper_saved_rows
+from .prosody import NS3_PROSODY
 
 
 class AudioStream:
@@ -45,10 +46,19 @@ class TextStream:
 
 
 class RowsStream:
-    """``[T, dim]`` rows per utterance handed in by the caller (the third stream's files: its extractor is not part of this library)."""
+    """``[T, dim]`` rows per utterance handed in by the caller: a third stream read from feature files (``--encoder3 files``), whatever
+    wrote them -- preprocessing/preprocess_ns3_prosody.py for the prosody stream, which ``ProsodyStream`` computes from the waveforms."""
 
     def __init__(self, dim: int):
         self.dim = int(dim)
+
+
+class ProsodyStream:
+    """The prosody encoder (``engine.ProsodyEncoder``) over the batch's waveforms: the ``[len // 200 + 1, D]`` rows the reference's
+    preprocess_ns3_prosody.py saves per file, read by the head where the quantizer's lookup left them."""
+
+    def __init__(self, enc):
+        self.enc = enc
 
 
 def gather_rows(src: RowSource, offs: Sequence[int]) -> torch.Tensor:
@@ -71,7 +81,7 @@ def gather_rows(src: RowSource, offs: Sequence[int]) -> torch.Tensor:
 
 class FusionPredictor:
     """``streams``: two (``engine.FusionHead``) or three (``engine.TrimodalHead``, ``heads`` = (1, 1, 2) unless given) of ``AudioStream`` /
-    ``TextStream`` / ``RowsStream``, in the order of the head's modalities; ``head_sd``: the head's state dict; ``head_mode``: its numerics
+    ``TextStream`` / ``ProsodyStream`` / ``RowsStream``, in the order of the head's modalities; ``head_sd``: the head's state dict; ``head_mode``: its numerics
     (default: the first encoder's ``mode_name``).  All encoders and the head live on one device.  Constructor errors are
     ``BimodalPredictor``'s: ``IndexError("tuple index out of range")`` for a state outside the tuple, ``ValueError`` for a mean over fewer
     than four states or a stream width the state dict contradicts."""
@@ -90,16 +100,22 @@ class FusionPredictor:
             if isinstance(s, RowsStream):
                 dims.append(s.dim)
                 continue
-            if isinstance(s, AudioStream):
+            if isinstance(s, ProsodyStream):
+                if not isinstance(s.enc, ProsodyEncoder):
+                    raise ValueError(f"stream {i + 1}: a ProsodyStream needs the prosody encoder")
+            elif isinstance(s, AudioStream):
                 if not isinstance(s.enc, (SpeechEncoder, WhisperEncoder)):
                     raise ValueError(f"stream {i + 1}: an AudioStream needs a speech encoder or Whisper")
             elif isinstance(s, TextStream):
                 if not isinstance(s.enc, _TextEncoderBase):
                     raise ValueError(f"stream {i + 1}: a TextStream needs a text encoder (RoBERTa / DeBERTa)")
             else:
-                raise ValueError(f"stream {i + 1}: expected an AudioStream, a TextStream or a RowsStream")
+                raise ValueError(f"stream {i + 1}: expected an AudioStream, a TextStream, a ProsodyStream or a RowsStream")
             if s.enc.device != encs[0].device:
                 raise ValueError(f"all encoders must live on one device, got {encs[0].device} and {s.enc.device}")
+            if isinstance(s, ProsodyStream):
+                dims.append(s.enc.spec.hidden)
+                continue
             L = s.enc.geo.num_layers
             if s.average:
                 if L + 1 < 4:
@@ -157,9 +173,9 @@ class FusionPredictor:
         states (nothing copied; valid until that encoder's next forward), or for a ``RowsStream`` the caller's rows packed on the device
         (and None for the HiddenStates).  The forwards run on the current stream in the order of the streams."""
         B = None
-        if any(isinstance(s, AudioStream) for s in self.streams):
+        if any(isinstance(s, (AudioStream, ProsodyStream)) for s in self.streams):
             if waves is None:
-                raise ValueError("an AudioStream needs waves")
+                raise ValueError("an AudioStream or a ProsodyStream needs waves")
             waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
             B = len(waves)
         transcriber = next((s for s in self.streams if isinstance(s, AudioStream) and s.tokens_from_states is not None), None)
@@ -192,6 +208,9 @@ class FusionPredictor:
             elif isinstance(s, TextStream):
                 hs = s.enc.forward(input_ids, attention_mask)
                 out.append(self._source(s, hs, [hs.frames(b) for b in range(B)]))
+            elif isinstance(s, ProsodyStream):
+                hs = s.enc.forward(waves)                                  # (a wave under 400 samples raises: the batch is retried file by file)
+                out.append((RowSource(hs.rows, hs.frame_offs[:-1]), list(hs.frame_offs), hs))
             else:
                 mats = []
                 for r in rows:
@@ -231,8 +250,9 @@ class FusionPredictor:
 FILES = "files"           # --encoder3 files: the third stream is read from config["lazy_dir3"]
 
 
-def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[str]):
-    """(geometry or None for "files") per stream, checked against the config's feat{i}_dim -- before any weight is loaded"""
+def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[str], synthetic: bool = False):
+    """(geometry, ``prosody.ProsodySpec`` for "ns3-prosody", or None for "files") per stream, checked against the config's feat{i}_dim
+    -- before any weight is loaded (the prosody checkpoint's shapes are read, mapped where the file allows)"""
     if len(encoders) not in (2, 3):
         raise ValueError(f"two or three encoders, got {len(encoders)}")
     geos = []
@@ -243,7 +263,11 @@ def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[s
                 raise ValueError("only the third stream can be read from files (--encoder3 files)")
             geos.append(None)
             continue
-        geo = C.resolve_geometry(name, checkpoints[i])
+        if name == NS3_PROSODY:
+            from .prosody import resolve_spec
+            geo = resolve_spec(checkpoints[i], synthetic)
+        else:
+            geo = C.resolve_geometry(name, checkpoints[i])
         if geo.hidden != want:
             raise ValueError(f"feat{i + 1}_dim = {want} in the config, but {name} has hidden size {geo.hidden}")
         geos.append(geo)
@@ -260,8 +284,9 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     """``head.score(engine="hip")`` from the corpus itself: the ``FileName`` column of ``test_csv``, wavs from ``config["wav_dir"]``
     (16 kHz), transcripts from the table ``config["txt_dir"]`` (columns FileName, transcription), the head's weights from
     ``<model_path>/multimodal_ser.pt`` -> ``<model_path>/results/test.csv`` in ``head.score``'s format.  ``encoders``: two or three
-    encoder ids (``config.resolve_geometry``; the family decides the stream kind), the third may be "files" (rows from
-    ``config["lazy_dir3"]``).  ``layers[i]`` / ``averages[i]``: the state an audio stream hands on; a text stream hands on its last state
+    encoder ids (``config.resolve_geometry``; the family decides the stream kind); "ns3-prosody" is the prosody stream
+    (``engine.ProsodyEncoder``, checkpoint: a directory holding ns3_facodec_decoder_v2.bin, or the file), and the third may be "files"
+    (rows from ``config["lazy_dir3"]``).  ``layers[i]`` / ``averages[i]``: the state an audio stream hands on; a text stream hands on its last state
     or the mean.  ``mode`` / ``text_mode`` / ``head_mode``: numerics of the audio encoders, the text encoders and the head (default: the
     first encoder's).  ``tokenize``: texts -> (input_ids, attention_mask), default ``driver.hf_tokenize_fn``.  A file that cannot be
     decoded, has no transcript or is empty is printed and gets no row; a batch whose range-guard or GRU error word is set is retried file
@@ -276,7 +301,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     layers = list(layers) if layers is not None else [-1] * n
     averages = list(averages) if averages is not None else [False] * n
     checkpoints = list(checkpoints) if checkpoints is not None else [""] * n
-    geos = _stream_kinds(config, encoders, checkpoints)
+    geos = _stream_kinds(config, encoders, checkpoints, synthetic_weights)
     if max_len > 512:
         raise ValueError(f"max_len {max_len}: the text encoders have 512 positions (the reference uses 80)")
     if not torch.cuda.is_available():
@@ -298,6 +323,17 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     for i, (name, geo) in enumerate(zip(encoders, geos)):
         if geo is None:
             streams.append(RowsStream(int(config[f"feat{i + 1}_dim"])))
+            continue
+        if geo.family == NS3_PROSODY:
+            from . import prosody as P
+            if synthetic_weights and not checkpoints[i]:
+                sd, src = P.synthetic_state_dict(geo, seed), f"synthetic weights (seed {seed})"
+            else:
+                sd, src = P.load_state_dict(checkpoints[i]), f"checkpoint {P.checkpoint_path(checkpoints[i])}"
+            enc = ProsodyEncoder(sd, dev, mode if mode in ("f16x", "fp32x", "bf16") else "f16x")      # the encoders' mode where it has it
+            streams.append(ProsodyStream(enc))
+            print(f"Stream {i + 1}: {name} ({src}; numerics mode {enc.mode_name})")
+            del sd
             continue
         text = geo.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA)
         whisper = geo.family == C.FAMILY_WHISPER
@@ -403,7 +439,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--config_path", type=str, default="./configs/config_cat.json")
     for i in (1, 2, 3):
         p.add_argument(f"--encoder{i}", type=str, default="" if i == 3 else None, required=i < 3,
-                       help="encoder id" + (' or "files" (rows from lazy_dir3); empty: two streams' if i == 3 else ""))
+                       help="encoder id" + (' or "ns3-prosody" (the prosody stream, --checkpoint3 <dir or .bin>) or "files" (rows from lazy_dir3); '
+                                           'empty: two streams' if i == 3 else ""))
         p.add_argument(f"--layer{i}", type=int, default=-1, help="audio stream: hidden_states[N]")
         p.add_argument(f"--average{i}", action="store_true", help="the mean of the last four hidden states")
         p.add_argument(f"--checkpoint{i}", type=str, default="")
