@@ -780,6 +780,73 @@ typedef struct ser_act_rows_args {
 } ser_act_rows_args;
 int ser_act_rows_v(const ser_act_rows_args* args, void* stream);
 
+/* a27 (added under ABI 18: new entry points, ser_cmd members and SER_OP codes only; nothing existing changed)  The speaker half of the
+ * reference's 512-wide third stream (preprocessing/preprocess_ns3_prosody_speaker.py:41-60 saves cat(prosody rows, timbre rows)):
+ * FACodecEncoderV2.block (src/ns3/facodec.py), the waveform-rate stack conv_in -> four EncoderBlocks (three ResidualUnits of dilation 1, 3, 9,
+ * an activation, a strided convolution C -> 2 C) -> activation -> k = 3 convolution, every convolution weight-normed with zero padding, every
+ * activation an alias-free SnakeBeta (src/ns3/alias_free_torch Activation1d).  On rows x[0 .. T-1] of one utterance, per channel c, with the
+ * 12 Kaiser-sinc taps f (`taps`, fp32 [12]), ea = e^alpha_c and ib = 1 / (e^beta_c + 1e-9) folded by the host:
+ *   u[m] = 2 sum_i xp[i] f[m + 15 - 2 i]                  xp = x replicate-padded by 5 a side, m = 0 .. 2 T - 1
+ *   s[m] = u[m] + sin(u[m] ea)^2 ib                       accurate sinf
+ *   Act(x)[t] = sum_k sp[2 t + k] f[k]                    sp = s replicate-padded by (5, 6), t = 0 .. T - 1
+ * Both clamps act at every utterance's own ends; Act(x)[t] reaches x[t - 6 .. t + 6].  Layout: channels-last fp32 rows of a packed ragged
+ * batch, utterance b = rows offs[b] .. offs[b + 1] - 1 (offsets on the device).  All three kernels use fp32 FMAs in a fixed order --
+ * ascending tap, then ascending input channel -- whatever the numerics mode, and tile each utterance from its own first row, so a batched
+ * run is bit-equal to a batch of one.  Routing is by input channels: a convolution with C_in % 64 == 0 is ser_snake_v + ser_gemm (its
+ * operand copy in a zero-halo'd layout supplies the padding), every narrower one (C_in 1, 8, 16, 32) goes through the two narrow kernels.
+ * Narrow weights are K-MAJOR: w[(tap * C_in + c) * C_out + n] -- the transpose of ser_gemm's [N][K] -- so that the 4 output channels a
+ * thread owns are one 16-byte load.
+ *
+ * ser_codec_unit_v: one whole ResidualUnit per launch,  y = x + W1 Act2(conv_k_d(Act1(x)) + b7) + b1,  C = 8, 16, 24 or 32, k odd <= 7,
+ * dilation d <= 9 (padding (k / 2) d).  A block takes SER_CODEC_TILE rows of one utterance; Act1(x), the convolution's output and
+ * Act2 of it exist only in LDS, on a halo of (k / 2) d + 12 rows a side: nothing between x and y goes to HBM.  y must not alias x.
+ * max_rows = the longest utterance (sizes the grid); rows = the row count of x and y (only validated: 0 <= max_rows <= rows). */
+#define SER_CODEC_TILE 128
+typedef struct ser_codec_unit_args {
+    const float* x; float* y;
+    const int32_t* row_offs;
+    const float* taps;
+    const float* ea1; const float* ib1;
+    const float* w7; const float* b7;
+    const float* ea2; const float* ib2;
+    const float* w1; const float* b1;
+    int32_t B, C, k, dilation, max_rows, rows;
+} ser_codec_unit_args;
+int ser_codec_unit_v(const ser_codec_unit_args* args, void* stream);
+
+/* ser_codec_conv_v: the narrow strided convolution, with Activation1d fused on its input when ea != NULL:
+ *   y[t][n] = bias[n] + sum_tap sum_c w[(tap C_in + c) C_out + n] v[t stride - pad + tap][c],   v = Act(x) or x, zero outside [0, L)
+ * for t < T_out = out_offs[b + 1] - out_offs[b] (the caller's count; the codec's levels divide exactly), where L = in_offs[b + 1] -
+ * in_offs[b] is the utterance's input length: the activation's clamps act at 0 and L - 1.  int64 input offsets: conv_in (no activation,
+ * C_in = 1) reads the packed, UNPADDED waveform and writes the padded length's rows -- the zeros the reference pads the wave with are the
+ * zeros beyond L.
+ * C_in 1, 8, 16 or 32; C_out % 8 == 0; k <= 16; stride <= 8.  A block takes SER_CODEC_TILE / stride output rows.  y fp32 [rows][ldy]. */
+typedef struct ser_codec_conv_args {
+    const float* x;
+    const int64_t* in_offs; const int32_t* out_offs;
+    const float* taps; const float* ea; const float* ib;
+    const float* w; const float* bias;
+    float* y; int64_t ldy;
+    int32_t B, C_in, C_out, k, stride, pad, max_out_rows, rows;
+} ser_codec_conv_args;
+int ser_codec_conv_v(const ser_codec_conv_args* args, void* stream);
+
+/* ser_snake_v: Activation1d for the wide levels (C % 64 == 0), as the producer of ser_gemm's operand copy: Act(x) of fp32 rows x [rows][ldx]
+ * -> operand planes out_act in `mode` (SER_MODE_BF16 / FP32X / FP16 / FP16X) at row out_rowmap[m] (NULL: m) -- a zero-halo'd layout whose
+ * rows between utterances are the caller's zeros and are never written -- and / or the fp32 value out_f32 at row m.  The fp16 formats
+ * report every value they round into range_flag (may be NULL; see ser_gemm_args.range_flag). */
+typedef struct ser_snake_args {
+    const float* x; int64_t ldx;
+    const int32_t* row_offs;
+    const float* taps; const float* ea; const float* ib;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    const int32_t* out_rowmap;
+    float* out_f32; int64_t ldo_f32;
+    uint32_t* range_flag;
+    int32_t B, C, max_rows, rows, mode, reserved0;
+} ser_snake_args;
+int ser_snake_v(const ser_snake_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -795,6 +862,9 @@ int ser_act_rows_v(const ser_act_rows_args* args, void* stream);
 #define SER_OP_PROSODY_MEL 13
 #define SER_OP_FVQ 14
 #define SER_OP_ACT_ROWS 15
+#define SER_OP_CODEC_UNIT 16
+#define SER_OP_CODEC_CONV 17
+#define SER_OP_SNAKE 18
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -813,6 +883,9 @@ typedef struct ser_cmd {
         ser_prosody_mel_args prosody_mel;
         ser_fvq_args         fvq;
         ser_act_rows_args    act_rows;
+        ser_codec_unit_args  codec_unit;
+        ser_codec_conv_args  codec_conv;
+        ser_snake_args       snake;
     } u;
 } ser_cmd;
 

@@ -301,6 +301,38 @@ class ActRowsArgs(C.Structure):
     ]
 
 
+class CodecUnitArgs(C.Structure):
+    """Mirror of ``ser_codec_unit_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("y", c_void_p), ("row_offs", c_void_p), ("taps", c_void_p),
+        ("ea1", c_void_p), ("ib1", c_void_p), ("w7", c_void_p), ("b7", c_void_p),
+        ("ea2", c_void_p), ("ib2", c_void_p), ("w1", c_void_p), ("b1", c_void_p),
+        ("B", C.c_int32), ("C", C.c_int32), ("k", C.c_int32), ("dilation", C.c_int32), ("max_rows", C.c_int32), ("rows", C.c_int32),
+    ]
+
+
+class CodecConvArgs(C.Structure):
+    """Mirror of ``ser_codec_conv_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("in_offs", c_void_p), ("out_offs", c_void_p),
+        ("taps", c_void_p), ("ea", c_void_p), ("ib", c_void_p), ("w", c_void_p), ("bias", c_void_p),
+        ("y", c_void_p), ("ldy", c_i64),
+        ("B", C.c_int32), ("C_in", C.c_int32), ("C_out", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
+        ("max_out_rows", C.c_int32), ("rows", C.c_int32),
+    ]
+
+
+class SnakeArgs(C.Structure):
+    """Mirror of ``ser_snake_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64), ("row_offs", c_void_p), ("taps", c_void_p), ("ea", c_void_p), ("ib", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("out_rowmap", c_void_p),
+        ("out_f32", c_void_p), ("ldo_f32", c_i64), ("range_flag", c_void_p),
+        ("B", C.c_int32), ("C", C.c_int32), ("max_rows", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+CODEC_TILE = 128                # SER_CODEC_TILE: output rows per block of ser_codec_unit_v
 FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
 DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked logit was not finite
 DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
@@ -310,7 +342,8 @@ class _CmdUnion(C.Union):
     _fields_ = [("gemm", GemmArgs), ("attention", AttentionArgs), ("layernorm", LayerNormArgs), ("wave_frames", WaveFramesArgs),
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
                 ("pos_ln", PosLnArgs), ("dec_embed", DecEmbedArgs), ("dec_attn", DecAttnArgs), ("dec_select", DecSelectArgs),
-                ("prosody_mel", ProsodyMelArgs), ("fvq", FvqArgs), ("act_rows", ActRowsArgs)]
+                ("prosody_mel", ProsodyMelArgs), ("fvq", FvqArgs), ("act_rows", ActRowsArgs),
+                ("codec_unit", CodecUnitArgs), ("codec_conv", CodecConvArgs), ("snake", SnakeArgs)]
 
 
 class Cmd(C.Structure):
@@ -321,13 +354,15 @@ class Cmd(C.Structure):
 OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, OP_PACK_ACT, OP_GN_STATS, OP_POS_LN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_DEC_EMBED, OP_DEC_ATTN, OP_DEC_SELECT = 10, 11, 12
 OP_PROSODY_MEL, OP_FVQ, OP_ACT_ROWS = 13, 14, 15
+OP_CODEC_UNIT, OP_CODEC_CONV, OP_SNAKE = 16, 17, 18
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
                   "ser_mlp_head_args": MlpHeadArgs, "ser_gru_args": GruArgs, "ser_xattn_args": XattnArgs, "ser_xattn_mh_args": XattnMhArgs, "ser_attn_pool_args": AttnPoolArgs,
                   "ser_fusion_cls_args": FusionClsArgs, "ser_select_rows_args": SelectRowsArgs, "ser_dec_embed_args": DecEmbedArgs, "ser_dec_attn_args": DecAttnArgs,
                   "ser_dec_select_args": DecSelectArgs, "ser_prosody_mel_args": ProsodyMelArgs, "ser_fvq_args": FvqArgs,
-                  "ser_act_rows_args": ActRowsArgs, "ser_cmd": Cmd}
+                  "ser_act_rows_args": ActRowsArgs, "ser_codec_unit_args": CodecUnitArgs, "ser_codec_conv_args": CodecConvArgs,
+                  "ser_snake_args": SnakeArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -363,6 +398,9 @@ _SIGNATURES = {
     "ser_prosody_mel_v": (c_int, [c_void_p, c_void_p]),
     "ser_fvq_v": (c_int, [c_void_p, c_void_p]),
     "ser_act_rows_v": (c_int, [c_void_p, c_void_p]),
+    "ser_codec_unit_v": (c_int, [c_void_p, c_void_p]),
+    "ser_codec_conv_v": (c_int, [c_void_p, c_void_p]),
+    "ser_snake_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -95,6 +95,18 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_act_rows_v(&c.u.act_rows, stream);
                 break;
             }
+            case SER_OP_CODEC_UNIT: {
+                rc = ser_codec_unit_v(&c.u.codec_unit, stream);
+                break;
+            }
+            case SER_OP_CODEC_CONV: {
+                rc = ser_codec_conv_v(&c.u.codec_conv, stream);
+                break;
+            }
+            case SER_OP_SNAKE: {
+                rc = ser_snake_v(&c.u.snake, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

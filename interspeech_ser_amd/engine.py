@@ -435,7 +435,8 @@ class _LaunchHost:
         trace.append((e0, e1, 2.0 * M * g.N * groups * k_real, nbytes, _PRODUCTS[g.mode]))
 
     def _layernorm(self, x: torch.Tensor, ldx: int, ln, rows: int, D: int, *, gelu=False, out_f32=None,
-                   out_act: Optional[Act] = None, eps=None, stem=False):
+                   out_act: Optional[Act] = None, eps=None, stem=False, ldo_f32: Optional[int] = None):
+        """``ldo_f32``: pitch of ``out_f32`` when its rows are a column block of a wider buffer (default: D)"""
         g, b = ln
         mode = self.stem_mode if stem else self.mode
         if mode == _lib.MODE_FP16M:                   # ser_layernorm writes no FP16M copy; the encoders only need its fp32 output in that mode
@@ -446,7 +447,7 @@ class _LaunchHost:
         o_act = None if out_act is None else out_act.ptr
         ldo_act = 0 if out_act is None else out_act.cols
         ops = 0 if out_act is None else out_act.plane_stride
-        ldo_f32 = D if out_f32 is not None else 0
+        ldo_f32 = (D if ldo_f32 is None else ldo_f32) if out_f32 is not None else 0
         a = self._cmd("layernorm")
         a.x, a.ldx, a.g, a.b, a.eps, a.gelu = x.data_ptr(), ldx, g.data_ptr(), b.data_ptr(), eps, int(gelu)
         a.out_f32, a.ldo_f32, a.out_act, a.ldo_act, a.out_plane_stride = _ptr(out_f32), ldo_f32, o_act, ldo_act, ops
@@ -2554,7 +2555,71 @@ class ProsodyFeatures(HiddenStates):
         return bits
 
 
-class ProsodyEncoder(_LaunchHost):
+class _PreLnStack(_LaunchHost):
+    """The pre-LayerNorm layers of src/ns3/transformer.py's TransformerEncoder (melspec_encoder, timbre_encoder) on libserhip:
+    ser_layernorm_v, ser_gemm (FC1's k = 5 convolution as an implicit GEMM over a zero-halo'd copy), ser_attention_v and ser_act_rows_v
+    for the ReLU.  ``pl``: the buffers of one slot -- xa, qkv, ctx, tmp, halo, f1, ffn, halo_rowmap, fc1_rowoff, frame_offs, B, M, Tmax."""
+
+    def _act_rows(self, x: torch.Tensor, ldx: int, out: Act, rows: int, D: int, relu: bool, rowmap=None) -> None:
+        a = self._cmd("act_rows")
+        a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), ldx, out.ptr, out.cols, out.plane_stride
+        a.out_rowmap, a.range_flag = _ptr(rowmap), self._flag
+        a.relu, a.mode, a.rows, a.D = int(relu), self.mode, rows, D
+        self._issue(_lib.OP_ACT_ROWS, a, "ser_act_rows", rows=rows)
+
+    def _attn(self, pl, sp=None) -> None:
+        sp = self.spec if sp is None else sp
+        qkv, out = pl["qkv"], pl["ctx"]
+        a = self._cmd("attention")
+        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
+        a.q_col, a.k_col, a.v_col, a.B = 0, sp.hidden, 2 * sp.hidden, pl["B"]
+        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
+        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
+        a.H, a.dh, a.scale, a.mode = sp.heads, sp.head_dim, -1.0, self.mode          # q is pre-scaled
+        self._issue(_lib.OP_ATTENTION, a, "ser_attention", B=pl["B"], max_frames=pl["Tmax"])
+
+    def _pre_ln_layers(self, pl, sp, layers, x: torch.Tensor, h: torch.Tensor, x_in: Optional[torch.Tensor] = None) -> None:
+        """the layers on the residual stream ``x`` (``h``: the stream between a layer's two halves); ``x_in``: where layer 0 reads its
+        input when that is not ``x`` itself"""
+        M, D, F = pl["M"], sp.hidden, sp.ffn
+        scale = sp.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
+        src = x if x_in is None else x_in
+        for lay in layers:
+            # x += MHA(LN1(x))
+            self._layernorm(src, D, lay["ln1"], M, D, out_act=pl["xa"], eps=1e-5)
+            self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
+            self._attn(pl, sp)
+            self._gemm(pl["ctx"], lay["out"], M, residual=src, ldr=D, out_f32=h, ldo_f32=D)
+            # h += Linear(ReLU(Conv1d_k5(LN2(h)))): LN2's rows go to their halo'd positions, FC1 reads k consecutive rows per frame
+            self._layernorm(h, D, lay["ln2"], M, D, out_f32=pl["tmp"], eps=1e-5)
+            self._act_rows(pl["tmp"], D, pl["halo"], M, D, relu=False, rowmap=pl["halo_rowmap"])
+            self._gemm(pl["halo"], lay["fc1"], M, a_rowoff=pl["fc1_rowoff"], out_f32=pl["f1"], ldo_f32=F)
+            self._act_rows(pl["f1"], F, pl["ffn"], M, F, relu=True)
+            self._gemm(pl["ffn"], lay["fc2"], M, residual=h, ldr=D, out_f32=x, ldo_f32=D)
+            src = x
+
+    def _upload_layers(self, layers, prefix: str) -> list:
+        pair = lambda t: (self._dev_f32(t[0]), self._dev_f32(t[1]))
+        out = []
+        for i, lw in enumerate(layers):
+            p = f"{prefix}.layers.{i}"
+            out.append(dict(
+                ln1=pair(lw["ln1"]), ln2=pair(lw["ln2"]),
+                qkv=self._linear(*lw["qkv"], name=p + ".self_attn.in_proj_weight"), out=self._linear(*lw["out"], name=p + ".self_attn.out_proj.weight"),
+                fc1=self._linear(*lw["fc1"], name=p + ".ffn.ffn_1.weight"), fc2=self._linear(*lw["fc2"], name=p + ".ffn.ffn_2.weight")))
+        return out
+
+    @staticmethod
+    def _halo_maps(frame_offs_dev, base, offs, B: int, M: int, half: int, D: int, halo_rowmap, fc1_rowoff, st: int) -> None:
+        """zero-halo'd copy of FC1's input: [half zero rows][utt 0][half zero rows][utt 1] ... [half zero rows]; frame t of utterance b sits
+        at row half (b + 1) + offs[b] + t, and its k taps start ``half`` rows earlier"""
+        starts = np.array([half * (b + 1) + offs[b] for b in range(B)], dtype=np.int64)
+        base[:, :B].copy_(torch.from_numpy(np.stack([starts, starts - half])))
+        check(lib.ser_ragged_index(frame_offs_dev.data_ptr(), base[0].data_ptr(), B, 1, 1, 1, halo_rowmap.data_ptr(), M, st), "ser_ragged_index")
+        check(lib.ser_ragged_index(frame_offs_dev.data_ptr(), base[1].data_ptr(), B, 1, D, 8, fc1_rowoff.data_ptr(), M, st), "ser_ragged_index")
+
+
+class ProsodyEncoder(_PreLnStack):
     """The prosody stream of the reference's three-stream heads (preprocessing/preprocess_ns3_prosody.py) on libserhip: NS3 log-mel +
     melspec_linear (ser_prosody_mel_v), melspec_encoder's pre-LayerNorm layers -- ser_layernorm_v, ser_gemm (FC1's k = 5 convolution as an
     implicit GEMM over a zero-halo'd copy, two zero rows around each utterance), ser_attention_v, ser_act_rows_v for the ReLU -- and the
@@ -2577,15 +2642,8 @@ class ProsodyEncoder(_LaunchHost):
         self.melw = self._dev_f32(torch.from_numpy(melw))
         self.dft = torch.from_numpy(prosody_dft_table(self.n_bins)).to(self.device)
         self.lin_w, self.lin_b = self._dev_f32(w["lin_w"]), self._dev_f32(w["lin_b"])
-        pair = lambda t: (self._dev_f32(t[0]), self._dev_f32(t[1]))
-        self.layers = []
-        for i, lw in enumerate(w["layers"]):
-            p = f"{P.ENC}.layers.{i}"
-            self.layers.append(dict(
-                ln1=pair(lw["ln1"]), ln2=pair(lw["ln2"]),
-                qkv=self._linear(*lw["qkv"], name=p + ".self_attn.in_proj_weight"), out=self._linear(*lw["out"], name=p + ".self_attn.out_proj.weight"),
-                fc1=self._linear(*lw["fc1"], name=p + ".ffn.ffn_1.weight"), fc2=self._linear(*lw["fc2"], name=p + ".ffn.ffn_2.weight")))
-        self.last_ln = pair(w["last_ln"])
+        self.layers = self._upload_layers(w["layers"], P.ENC)
+        self.last_ln = (self._dev_f32(w["last_ln"][0]), self._dev_f32(w["last_ln"][1]))
         self.w_in, self.b_in = self._dev_f32(w["w_in"]), self._dev_f32(w["b_in"])
         self.codes, self.table = self._dev_f32(w["codes"]), self._dev_f32(w["table"])
         self._arenas: Dict[int, dict] = {}
@@ -2635,13 +2693,8 @@ class ProsodyEncoder(_LaunchHost):
         st, D = _stream(), self.spec.hidden
         ar["sample_offs"][: B + 1].copy_(torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))
         ar["frame_offs_all"][: B + 1].copy_(torch.from_numpy(offs.astype(np.int32)))
-        # zero-halo'd copy of FC1's input: [half zero rows][utt 0][half zero rows][utt 1] ... [half zero rows]; frame t of utterance b sits at
-        # row half (b + 1) + offs[b] + t, and its k taps start ``half`` rows earlier
-        starts = np.array([half * (b + 1) + offs[b] for b in range(B)], dtype=np.int64)
-        ar["base"][:, :B].copy_(torch.from_numpy(np.stack([starts, starts - half])))
         fo = ar["frame_offs_all"]
-        check(lib.ser_ragged_index(fo.data_ptr(), ar["base"][0].data_ptr(), B, 1, 1, 1, ar["halo_rowmap"].data_ptr(), M, st), "ser_ragged_index")
-        check(lib.ser_ragged_index(fo.data_ptr(), ar["base"][1].data_ptr(), B, 1, D, 8, ar["fc1_rowoff"].data_ptr(), M, st), "ser_ragged_index")
+        self._halo_maps(fo, ar["base"], offs, B, M, half, D, ar["halo_rowmap"], ar["fc1_rowoff"], st)
         if ar["plan"] is not None:
             ar["halo"].t.zero_()                                # the halo rows sit elsewhere than in the previous batch
         pl = dict(ar)
@@ -2661,50 +2714,21 @@ class ProsodyEncoder(_LaunchHost):
         a.B, a.max_frames, a.n_bins, a.n_mels = pl["B"], pl["Tmax"], self.n_bins, sp.n_mels
         self._issue(_lib.OP_PROSODY_MEL, a, "ser_prosody_mel", input="wav", B=pl["B"], max_frames=pl["Tmax"])
 
-    def _act_rows(self, x: torch.Tensor, ldx: int, out: Act, rows: int, D: int, relu: bool, rowmap=None) -> None:
-        a = self._cmd("act_rows")
-        a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), ldx, out.ptr, out.cols, out.plane_stride
-        a.out_rowmap, a.range_flag = _ptr(rowmap), self._flag
-        a.relu, a.mode, a.rows, a.D = int(relu), self.mode, rows, D
-        self._issue(_lib.OP_ACT_ROWS, a, "ser_act_rows", rows=rows)
-
-    def _attn(self, pl) -> None:
-        sp, qkv, out = self.spec, pl["qkv"], pl["ctx"]
-        a = self._cmd("attention")
-        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
-        a.q_col, a.k_col, a.v_col, a.B = 0, sp.hidden, 2 * sp.hidden, pl["B"]
-        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
-        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
-        a.H, a.dh, a.scale, a.mode = sp.heads, sp.head_dim, -1.0, self.mode          # q is pre-scaled
-        self._issue(_lib.OP_ATTENTION, a, "ser_attention", B=pl["B"], max_frames=pl["Tmax"])
-
     def _fvq(self, pl) -> None:
         sp = self.spec
         a = self._cmd("fvq")
         a.z, a.ldz, a.w_in, a.b_in, a.codes = pl["z"].data_ptr(), sp.hidden, self.w_in.data_ptr(), self.b_in.data_ptr(), self.codes.data_ptr()
         a.table, a.ld_table, a.idx, a.gap = self.table.data_ptr(), sp.hidden, pl["codes"].data_ptr(), pl["gaps"].data_ptr()
-        a.out_f32, a.ldo_f32, a.err = pl["rows"].data_ptr(), sp.hidden, pl["err"].data_ptr()
+        a.out_f32, a.ldo_f32, a.err = pl["rows"].data_ptr(), pl.get("rows_ld", sp.hidden), pl["err"].data_ptr()   # rows_ld: a column block of a wider buffer
         a.rows, a.D, a.n_codes, a.code_dim, a.mode = pl["M"], sp.hidden, sp.n_codes, sp.code_dim, self.mode
         self._issue(_lib.OP_FVQ, a, "ser_fvq", rows=pl["M"])
 
     def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
         sp = self.spec
-        M, D, F = pl["M"], sp.hidden, sp.ffn
-        scale = sp.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
-        x, h = pl["x"], pl["h"]
+        M, D = pl["M"], sp.hidden
+        x = pl["x"]
         self._mel(pl, packed_wave)
-        for lay in self.layers:
-            # x += MHA(LN1(x))
-            self._layernorm(x, D, lay["ln1"], M, D, out_act=pl["xa"], eps=1e-5)
-            self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
-            self._attn(pl)
-            self._gemm(pl["ctx"], lay["out"], M, residual=x, ldr=D, out_f32=h, ldo_f32=D)
-            # h += Linear(ReLU(Conv1d_k5(LN2(h)))): LN2's rows go to their halo'd positions, FC1 reads k consecutive rows per frame
-            self._layernorm(h, D, lay["ln2"], M, D, out_f32=pl["tmp"], eps=1e-5)
-            self._act_rows(pl["tmp"], D, pl["halo"], M, D, relu=False, rowmap=pl["halo_rowmap"])
-            self._gemm(pl["halo"], lay["fc1"], M, a_rowoff=pl["fc1_rowoff"], out_f32=pl["f1"], ldo_f32=F)
-            self._act_rows(pl["f1"], F, pl["ffn"], M, F, relu=True)
-            self._gemm(pl["ffn"], lay["fc2"], M, residual=h, ldr=D, out_f32=x, ldo_f32=D)
+        self._pre_ln_layers(pl, sp, self.layers, x, pl["h"])
         self._layernorm(x, D, self.last_ln, M, D, out_f32=pl["z"], eps=1e-5)
         self._fvq(pl)
 
@@ -2749,6 +2773,270 @@ class ProsodyEncoder(_LaunchHost):
         pl, waves = self._ingest(waves, lengths, slot)
         self._mel(pl, waves, with_linear=False)
         return pl["mel"][: int(pl["M"])]
+
+
+class SpeakerProsodyFeatures(ProsodyFeatures):
+    """``ProsodyFeatures`` of the 512-wide stream: ``rows`` [M, 2 D] = prosody rows | timbre rows (what the reference saves per file,
+    packed); ``encoded`` [M, D] = the codec encoder's output (the timbre layers' input without the position-0 vector the final
+    convolution's bias carries: one fp32 subtraction, made when asked)."""
+
+    def __init__(self, rows, codes, gaps, z, mel, frame_offs, range_flag, frame_offs_dev, err, enc_x, pos0, levels=None):
+        super().__init__(rows, codes, gaps, z, mel, frame_offs, range_flag, frame_offs_dev, err)
+        self._enc_x, self._pos0, self.levels = enc_x, pos0, levels
+
+    @property
+    def encoded(self) -> torch.Tensor:
+        return self._enc_x - self._pos0
+
+
+class SpeakerProsodyEncoder(_PreLnStack):
+    """The reference's 512-wide third stream (preprocessing/preprocess_ns3_prosody_speaker.py) on libserhip: a ``ProsodyEncoder`` for the
+    first half and, for the second, FACodecEncoderV2.block -- narrow levels (C <= 32) on ser_codec_conv_v / ser_codec_unit_v, wide ones
+    (C % 64 == 0) on ser_snake_v + ser_gemm over a zero-halo'd operand copy (27 zero rows around each utterance) -- followed by
+    FACodecDecoderV2.timbre_encoder's pre-LayerNorm layers, all on one stream and one command list.  ser_fvq_v writes columns 0:D and the
+    timbre encoder's last LayerNorm columns D:2D of one [M, 2 D] buffer.  ``decoder_sd`` / ``encoder_sd``: the state dicts of
+    ns3_facodec_decoder_v2.bin / ns3_facodec_encoder_v2.bin; 16 kHz input of at least 400 samples, every utterance alone."""
+
+    use_tape = True
+
+    def __init__(self, decoder_sd, encoder_sd, device="cuda:0", mode: str = "f16x", heads: int = 4):
+        from . import prosody as P
+        if mode not in POST_LN_MODES:
+            raise ValueError(f"the prosody encoders support the {', '.join(POST_LN_MODES)} numerics modes")
+        w = P.prepare_codec(encoder_sd, decoder_sd, heads)               # refuses an unsupported geometry before anything is uploaded
+        self.prosody = ProsodyEncoder(decoder_sd, device, mode, heads)
+        if self.prosody.spec.hidden != w["spec"].out_channels:
+            raise ValueError(f"prosody rows are {self.prosody.spec.hidden} wide, timbre rows {w['spec'].out_channels}: not the halves of one tensor")
+        super().__init__(device, mode, MODES[mode], MODES[mode], self.prosody.fp16_planes)
+        self.spec = spec = w["spec"]
+        dev = self._dev_f32
+        kmajor = lambda t: dev(t.t().contiguous())                       # the narrow kernels read [k C_in][C_out]
+        act = lambda a: (dev(a[0]), dev(a[1]))
+        self.taps = dev(w["taps"])
+        self.conv_in = (kmajor(w["conv_in"][0]), dev(w["conv_in"][1]))
+        self.levels = []
+        for i, lv in enumerate(w["levels"], start=1):
+            narrow = lv["C"] <= P.NARROW_MAX
+            units = []
+            for j, u in enumerate(lv["units"]):
+                p = f"block.{i}.block.{j}.block"
+                if narrow:
+                    units.append(dict(d=u["d"], act1=act(u["act1"]), act2=act(u["act2"]), w7=kmajor(u["w7"]), b7=dev(u["b7"]),
+                                      w1=kmajor(u["w1"]), b1=dev(u["b1"])))
+                else:
+                    units.append(dict(d=u["d"], act1=act(u["act1"]), act2=act(u["act2"]), w7=self._linear(u["w7"], u["b7"], name=p + ".1.weight"),
+                                      w1=self._linear(u["w1"], u["b1"], name=p + ".3.weight")))
+            down = (kmajor(lv["down"][0]), dev(lv["down"][1])) if narrow else self._linear(*lv["down"], name=f"block.{i}.block.4.weight")
+            self.levels.append(dict(C=lv["C"], narrow=narrow, stride=lv["stride"], pad=lv["pad"], units=units, act=act(lv["act"]), down=down))
+        n = len(spec.strides)
+        self.final = dict(act=act(w["final"]["act"]), lin=self._linear(w["final"]["w"], w["final"]["b"], name=f"block.{n + 2}.weight"))
+        self.layers = self._upload_layers(w["layers"], P.TIMBRE)
+        self.last_ln = (dev(w["last_ln"][0]), dev(w["last_ln"][1]))
+        self.pos0 = dev(P.position0(spec.out_channels).float())
+        self.halo = P.WIDE_HALO
+        self._arenas: Dict[int, dict] = {}
+
+    upload = SpeechEncoder.upload
+    download = SpeechEncoder.download
+
+    # ------------------------------------------------------------------ buffers
+    def _arena(self, slot: int, M0: int, B: int) -> dict:
+        """grow-only buffer set of one slot, sized by the rows of level 0 (every other level's rows are its exact quotients)"""
+        ar = self._arenas.get(slot)
+        if ar is not None and ar["cap_M0"] >= M0 and ar["cap_B"] >= B:
+            return ar
+        M0, B = max(M0, ar["cap_M0"] if ar else 0), max(B, ar["cap_B"] if ar else 0)
+        sp, dev = self.spec, self.device
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        ar = dict(cap_M0=M0, cap_B=B, plan=None, lv=[])
+        rows = M0
+        for l, C in enumerate(sp.channels):
+            last = l == len(sp.strides)
+            lv = dict(cap=rows, xa=f32(rows, C), offs=i32(B + 1), offs64=torch.empty(B + 1, dtype=torch.int64, device=dev))
+            if not last:
+                lv["xb"] = f32(rows, C)
+            if C > 32:                                                   # a wide level: operand copies for ser_gemm
+                lv["halo"] = self._new_act(rows + self.halo * (B + 1), C, zero=True)
+                lv["rowmap"] = i32(rows)
+                lv["base"] = torch.empty((5, B), dtype=torch.int64, device=dev)
+                if last:
+                    lv["rowoff_k3"] = i32(rows)
+                else:
+                    lv["h"], lv["a2"] = f32(rows, C), self._new_act(rows, C)
+                    lv["rowoff"] = i32(3, rows)
+                    lv["down_rowoff"] = i32(rows // sp.strides[l])
+            ar["lv"].append(lv)
+            if not last:
+                rows //= sp.strides[l]
+        M, ts = rows, sp.timbre
+        D, F = ts.hidden, ts.ffn
+        ar["enc"], ar["x"], ar["h"], ar["tmp"], ar["f1"], ar["rows2"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D), f32(M, F), f32(M, 2 * D)
+        ar["xa"], ar["ctx"], ar["qkv"], ar["ffn"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, 3 * D), self._new_act(M, F)
+        ar["halo"] = self._new_act(M + (ts.kernel // 2) * (B + 1), D, zero=True)
+        ar["halo_rowmap"], ar["fc1_rowoff"] = i32(M), i32(M)
+        ar["base"] = torch.empty((2, B), dtype=torch.int64, device=dev)
+        self._arenas[slot] = ar
+        return ar
+
+    def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
+        ppl = self.prosody._plan(lengths, slot)                          # refuses a short wave before anything is uploaded
+        lengths, B, sp = ppl["lengths"], int(ppl["B"]), self.spec
+        lens = np.array([sp.level_lengths(n) for n in lengths], dtype=np.int64)        # [B, levels]
+        offs = np.concatenate([np.zeros((1, lens.shape[1]), dtype=np.int64), np.cumsum(lens, axis=0)]).T   # [levels, B + 1]
+        ar = self._arena(slot, int(offs[0, -1]), B)
+        old = ar["plan"]
+        if old is not None and old["ppl"] is ppl:
+            return old
+        assert int(offs[-1, -1]) == int(ppl["M"]) and lens[:, -1].tolist() == np.diff(ppl["frame_offs_host"]).tolist()
+        st, H = _stream(), self.halo
+        ridx = lambda row_offs, base, step, mult, div, out, total: check(
+            lib.ser_ragged_index(row_offs.data_ptr(), base.data_ptr(), B, step, mult, div, out.data_ptr(), total, st), "ser_ragged_index")
+        for l, lv in enumerate(ar["lv"]):                                # every level's offsets first: a level's row maps read the next one's
+            lv["offs"][: B + 1].copy_(torch.from_numpy(offs[l].astype(np.int32)))
+            lv["offs64"][: B + 1].copy_(torch.from_numpy(offs[l]))
+        for l, lv in enumerate(ar["lv"]):
+            if "halo" not in lv:
+                continue
+            # zero-halo'd copy of a wide level: [H zero rows][utt 0][H zero rows][utt 1] ... ; row t of utterance b sits at H (b + 1) + offs[b] + t
+            C, M_l = sp.channels[l], int(offs[l, -1])
+            starts = np.array([H * (b + 1) + offs[l, b] for b in range(B)], dtype=np.int64)
+            if "rowoff" in lv:
+                s, p = sp.strides[l], self.levels[l]["pad"]
+                lv["base"][:, :B].copy_(torch.from_numpy(np.stack([starts, starts - 3, starts - 9, starts - 27, starts - p])))
+                for j in range(3):                                       # the dilated k = 7 convolutions start 3 d rows earlier
+                    ridx(lv["offs"], lv["base"][1 + j], 1, C, 8, lv["rowoff"][j], M_l)
+                ridx(ar["lv"][l + 1]["offs"], lv["base"][4], s, C, 8, lv["down_rowoff"], int(offs[l + 1, -1]))
+            else:
+                lv["base"][:2, :B].copy_(torch.from_numpy(np.stack([starts, starts - 1])))
+                ridx(lv["offs"], lv["base"][1], 1, C, 8, lv["rowoff_k3"], M_l)
+            ridx(lv["offs"], lv["base"][0], 1, 1, 1, lv["rowmap"], M_l)
+            if old is not None:
+                lv["halo"].t.zero_()                                     # the halo rows sit elsewhere than in the previous batch
+        ts = sp.timbre
+        self._halo_maps(ppl["frame_offs_all"], ar["base"], ppl["frame_offs_host"], B, int(ppl["M"]), ts.kernel // 2, ts.hidden,
+                        ar["halo_rowmap"], ar["fc1_rowoff"], st)
+        if old is not None:
+            ar["halo"].t.zero_()
+        pl = dict(ar)
+        sizes = dict(ppl["sizes"])
+        for l in range(len(sp.channels)):
+            sizes[f"M{l}"], sizes[f"R{l}"] = int(offs[l, -1]), int(lens[:, l].max())
+        pp = dict(ppl)
+        pp["rows"], pp["rows_ld"] = ar["rows2"], 2 * ts.hidden           # ser_fvq_v writes the left half of the saved rows
+        pl.update(ppl=ppl, pp=pp, lengths=lengths, B=ppl["B"], M=ppl["M"], Tmax=ppl["Tmax"], frame_offs=ppl["frame_offs"], sizes=sizes,
+                  Ms=[Sz(sizes[f"M{l}"], f"M{l}") for l in range(len(sp.channels))],
+                  Rs=[Sz(sizes[f"R{l}"], f"R{l}") for l in range(len(sp.channels))])
+        ar["plan"] = pl
+        return pl
+
+    # ------------------------------------------------------------------ launches
+    def _unit(self, x, y, C: int, u, offs, B, rmax, rows) -> None:
+        a = self._cmd("codec_unit")
+        a.x, a.y, a.row_offs, a.taps = x.data_ptr(), y.data_ptr(), offs.data_ptr(), self.taps.data_ptr()
+        a.ea1, a.ib1, a.ea2, a.ib2 = u["act1"][0].data_ptr(), u["act1"][1].data_ptr(), u["act2"][0].data_ptr(), u["act2"][1].data_ptr()
+        a.w7, a.b7, a.w1, a.b1 = u["w7"].data_ptr(), u["b7"].data_ptr(), u["w1"].data_ptr(), u["b1"].data_ptr()
+        a.B, a.C, a.k, a.dilation, a.max_rows, a.rows = B, C, 7, u["d"], rmax, rows
+        self._issue(_lib.OP_CODEC_UNIT, a, "ser_codec_unit", B=B, max_rows=rmax, rows=rows)
+
+    def _conv(self, x, in_offs, out_offs, act, wb, y, C_in: int, C_out: int, k: int, stride: int, pad: int, B, rmax, rows, input=None) -> None:
+        a = self._cmd("codec_conv")
+        a.x, a.in_offs, a.out_offs = x.data_ptr(), in_offs.data_ptr(), out_offs.data_ptr()
+        if act is not None:
+            a.taps, a.ea, a.ib = self.taps.data_ptr(), act[0].data_ptr(), act[1].data_ptr()
+        a.w, a.bias, a.y, a.ldy = wb[0].data_ptr(), wb[1].data_ptr(), y.data_ptr(), C_out
+        a.B, a.C_in, a.C_out, a.k, a.stride, a.pad, a.max_out_rows, a.rows = B, C_in, C_out, k, stride, pad, rmax, rows
+        self._issue(_lib.OP_CODEC_CONV, a, "ser_codec_conv", input=input, B=B, max_out_rows=rmax, rows=rows)
+
+    def _snake(self, x, C: int, act, offs, out: Act, rowmap, B, rmax, rows) -> None:
+        a = self._cmd("snake")
+        a.x, a.ldx, a.row_offs, a.taps, a.ea, a.ib = x.data_ptr(), C, offs.data_ptr(), self.taps.data_ptr(), act[0].data_ptr(), act[1].data_ptr()
+        a.out_act, a.ldo_act, a.out_plane_stride, a.out_rowmap = out.ptr, out.cols, out.plane_stride, _ptr(rowmap)
+        a.range_flag = self._flag
+        a.B, a.C, a.max_rows, a.rows, a.mode = B, C, rmax, rows, self.mode
+        self._issue(_lib.OP_SNAKE, a, "ser_snake", B=B, max_rows=rmax, rows=rows)
+
+    def _keep_level(self, keep, name: str, x: torch.Tensor, rows) -> None:
+        """a test's copy of a level's output; when recording, where the level's commands end (tools/codec_bench.py times the parts)"""
+        if keep is not None:
+            keep[name] = x[: int(rows)].clone()
+        if self._rec is not None and not name.startswith("u"):
+            self._rec.__dict__.setdefault("parts", []).append((name, self._rec.n))
+
+    def _codec_launches(self, pl, packed_wave: torch.Tensor, keep: Optional[dict] = None) -> None:
+        sp, B, Ms, Rs, lvs = self.spec, pl["B"], pl["Ms"], pl["Rs"], pl["lv"]
+        x = lvs[0]["xa"]
+        self._conv(packed_wave, pl["ppl"]["sample_offs"], lvs[0]["offs"], None, self.conv_in, x, 1, sp.ngf, 7, 1, 3, B, Rs[0], Ms[0], input="wav_codec")
+        self._keep_level(keep, "conv_in", x, Ms[0])
+        for l, L in enumerate(self.levels):
+            lv, nxt, C, s = lvs[l], lvs[l + 1], L["C"], L["stride"]
+            y = lv["xb"]
+            for j, u in enumerate(L["units"]):
+                if L["narrow"]:
+                    self._unit(x, y, C, u, lv["offs"], B, Rs[l], Ms[l])
+                else:
+                    self._snake(x, C, u["act1"], lv["offs"], lv["halo"], lv["rowmap"], B, Rs[l], Ms[l])
+                    self._gemm(lv["halo"], u["w7"], Ms[l], a_rowoff=lv["rowoff"][j], kc=C, ldj=u["d"] * C, out_f32=lv["h"], ldo_f32=C)
+                    self._snake(lv["h"], C, u["act2"], lv["offs"], lv["a2"], None, B, Rs[l], Ms[l])
+                    self._gemm(lv["a2"], u["w1"], Ms[l], residual=x, ldr=C, out_f32=y, ldo_f32=C)
+                x, y = y, x
+                self._keep_level(keep, f"u{l + 1}_{j}", x, Ms[l])
+            if L["narrow"]:
+                self._conv(x, lv["offs64"], nxt["offs"], L["act"], L["down"], nxt["xa"], C, 2 * C, 2 * s, s, L["pad"], B, Rs[l + 1], Ms[l + 1])
+            else:
+                self._snake(x, C, L["act"], lv["offs"], lv["halo"], lv["rowmap"], B, Rs[l], Ms[l])
+                self._gemm(lv["halo"], L["down"], Ms[l + 1], a_rowoff=lv["down_rowoff"], out_f32=nxt["xa"], ldo_f32=2 * C)
+            x = nxt["xa"]
+            self._keep_level(keep, f"level_{l + 1}", x, Ms[l + 1])
+        n = len(self.levels)
+        lv, C, ts = lvs[n], sp.channels[n], sp.timbre
+        D, M = ts.hidden, pl["M"]
+        self._snake(x, C, self.final["act"], lv["offs"], lv["halo"], lv["rowmap"], B, Rs[n], Ms[n])
+        self._gemm(lv["halo"], self.final["lin"], Ms[n], a_rowoff=lv["rowoff_k3"], out_f32=pl["enc"], ldo_f32=D)
+        # the timbre encoder: its input is the codec's output plus the position-0 vector (in the final convolution's bias)
+        self._pre_ln_layers(pl, ts, self.layers, pl["x"], pl["h"], x_in=pl["enc"])
+        self._layernorm(pl["x"], D, self.last_ln, M, D, out_f32=pl["rows2"][:, D:], ldo_f32=2 * D, eps=1e-5)
+
+    def _launch_all(self, pl, packed_wave: torch.Tensor, keep: Optional[dict] = None) -> None:
+        self.prosody._launches(pl["pp"], packed_wave)
+        self._keep_level(None, "prosody", packed_wave, 0)
+        self._codec_launches(pl, packed_wave, keep)
+
+    @_on_stream
+    def forward(self, waves, lengths: Optional[Sequence[int]] = None, slot: int = 0, keep_levels: bool = False) -> SpeakerProsodyFeatures:
+        """``waves``: a list of raw 16 kHz fp32 waveforms (uploaded here), or with ``lengths`` their packed samples on the device.
+        ``keep_levels`` (tests): launch one by one and keep a copy of conv_in's, every unit's and every level's output in ``.levels``."""
+        if lengths is None:
+            waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
+            pl = self._plan([len(w) for w in waves], slot)
+            waves = self.upload(waves, slot)
+        else:
+            pl = self._plan(lengths, slot)
+        ar, pro = self._arenas[slot], self.prosody
+        flag = pl["ppl"].get("range_flag")
+        self._flag = pro._flag = None if flag is None else flag.data_ptr()
+        prev, pro._st = pro._st, self._st
+        keep = {} if keep_levels else None
+        try:
+            if keep_levels or not self.use_tape:
+                self._launch_all(pl, waves, keep)
+            else:
+                tape = ar.get("tape")
+                if tape is None or ar.get("tape_for") is not pro._arenas[slot]:      # (the prosody arena grew: its pointers moved)
+                    self._rec = pro._rec = tape = Tape()
+                    try:
+                        self._launch_all(pl, waves)
+                    finally:
+                        self._rec = pro._rec = None
+                    ar["tape"], ar["tape_for"] = tape, pro._arenas[slot]
+                tape.inputs["wav"].wav = waves.data_ptr()
+                tape.inputs["wav_codec"].x = waves.data_ptr()
+                tape.run(pl["sizes"], self._s())
+        finally:
+            pro._st = prev
+        M, pp = int(pl["M"]), pl["pp"]
+        return SpeakerProsodyFeatures(pl["rows2"][:M], pp["codes"][:M], pp["gaps"][:M], pp["z"][:M], pp["mel"][:M], pp["frame_offs_host"], flag,
+                                      pp["frame_offs"], pp["err"], pl["enc"][:M], self.pos0, keep)
 
 
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):

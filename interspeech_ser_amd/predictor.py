@@ -21,9 +21,9 @@ import torch
 from . import config as C
 from .batchloop import close_logger, make_batches, prefetch, run_or_each, write_result_csv
 from ._lib import SelectRowsArgs, SerHipError, check, lib
-from .engine import FusionHead, ProsodyEncoder, RowSource, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
+from .engine import FusionHead, ProsodyEncoder, RowSource, SpeakerProsodyEncoder, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
 from .frontend import whisper_saved_rows
-from .prosody import NS3_PROSODY
+from .prosody import NS3_PROSODY, NS3_PROSODY_SPEAKER
 
 
 class AudioStream:
@@ -101,7 +101,7 @@ class FusionPredictor:
                 dims.append(s.dim)
                 continue
             if isinstance(s, ProsodyStream):
-                if not isinstance(s.enc, ProsodyEncoder):
+                if not isinstance(s.enc, (ProsodyEncoder, SpeakerProsodyEncoder)):
                     raise ValueError(f"stream {i + 1}: a ProsodyStream needs the prosody encoder")
             elif isinstance(s, AudioStream):
                 if not isinstance(s.enc, (SpeechEncoder, WhisperEncoder)):
@@ -114,7 +114,7 @@ class FusionPredictor:
             if s.enc.device != encs[0].device:
                 raise ValueError(f"all encoders must live on one device, got {encs[0].device} and {s.enc.device}")
             if isinstance(s, ProsodyStream):
-                dims.append(s.enc.spec.hidden)
+                dims.append(s.enc.spec.hidden)                            # (the speaker encoder's spec: both halves, 2 D)
                 continue
             L = s.enc.geo.num_layers
             if s.average:
@@ -266,6 +266,9 @@ def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[s
         if name == NS3_PROSODY:
             from .prosody import resolve_spec
             geo = resolve_spec(checkpoints[i], synthetic)
+        elif name == NS3_PROSODY_SPEAKER:
+            from .prosody import resolve_codec_spec
+            geo = resolve_codec_spec(checkpoints[i], synthetic)
         else:
             geo = C.resolve_geometry(name, checkpoints[i])
         if geo.hidden != want:
@@ -334,6 +337,20 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
             streams.append(ProsodyStream(enc))
             print(f"Stream {i + 1}: {name} ({src}; numerics mode {enc.mode_name})")
             del sd
+            continue
+        if geo.family == NS3_PROSODY_SPEAKER:
+            from . import prosody as P
+            if synthetic_weights and not checkpoints[i]:
+                sd, enc_sd = P.synthetic_state_dict(geo.timbre, seed), P.synthetic_codec_state_dict(geo, seed)
+                sd.update(P.synthetic_timbre_state_dict(geo.timbre, seed))
+                src = f"synthetic weights (seed {seed})"
+            else:
+                sd, enc_sd = P.load_state_dict(checkpoints[i]), P.load_encoder_state_dict(checkpoints[i])
+                src = f"checkpoints {P.checkpoint_path(checkpoints[i])}, {P.encoder_checkpoint_path(checkpoints[i])}"
+            enc = SpeakerProsodyEncoder(sd, enc_sd, dev, mode if mode in ("f16x", "fp32x", "bf16") else "f16x")
+            streams.append(ProsodyStream(enc))
+            print(f"Stream {i + 1}: {name} ({src}; numerics mode {enc.mode_name})")
+            del sd, enc_sd
             continue
         text = geo.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA)
         whisper = geo.family == C.FAMILY_WHISPER
@@ -439,7 +456,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--config_path", type=str, default="./configs/config_cat.json")
     for i in (1, 2, 3):
         p.add_argument(f"--encoder{i}", type=str, default="" if i == 3 else None, required=i < 3,
-                       help="encoder id" + (' or "ns3-prosody" (the prosody stream, --checkpoint3 <dir or .bin>) or "files" (rows from lazy_dir3); '
+                       help="encoder id" + (' or "ns3-prosody" (the prosody stream, --checkpoint3 <dir or .bin>), "ns3-prosody-speaker" (prosody | timbre rows, '
+                                           '--checkpoint3 <dir with both FACodec files>) or "files" (rows from lazy_dir3); '
                                            'empty: two streams' if i == 3 else ""))
         p.add_argument(f"--layer{i}", type=int, default=-1, help="audio stream: hidden_states[N]")
         p.add_argument(f"--average{i}", action="store_true", help="the mean of the last four hidden states")
