@@ -847,6 +847,89 @@ typedef struct ser_snake_args {
 } ser_snake_args;
 int ser_snake_v(const ser_snake_args* args, void* stream);
 
+/* a28 (added under ABI 18: new entry points, ser_cmd members and SER_OP codes only; nothing existing changed)  w2v-BERT 2.0
+ * (HF Wav2Vec2BertModel behind SeamlessM4TFeatureExtractor), an encoder the reference does not ship but its heads take like any other
+ * [T, D] stream: a Kaldi fbank front end, conformer layers, a relative-key attention bias.  Five kernels are its own; everything else runs on
+ * ser_layernorm_v and ser_gemm.  Every kernel is a plain grid (no inter-block waits, no atomics on float data), every sum runs in an order
+ * fixed by the utterance alone (a batched run is bit-equal to a batch of one), every fp16 operand plane reports into range_flag.
+ *
+ * ser_fbank_v: packed ragged waveforms -> normalised, stacked fp32 rows.  Utterance b (n = sample_offs[b + 1] - sample_offs[b] >= 400
+ * samples: the CALLER's check) has F = 1 + (n - 400) / 160 = mel_offs[b + 1] - mel_offs[b] frames (400 samples, hop 160, no centring) and
+ * T = F / stride = frame_offs[b + 1] - frame_offs[b] rows.  Per frame, with x = 2^15 wav:
+ *   y[j] = x[j] - mean(x);   z[j] = y[j] - 0.97 y[j - 1],  z[0] = (1 - 0.97) y[0];
+ *   X[k] = sum_j z[j] dft[j][k]       dft [400][257] pairs of float64 (w[j] cos, -w[j] sin)(2 pi k j / 512), w = the Povey window (host)
+ *   mel[m] = log(max(sum_k melw[m][k] |X[k]|^2, 1.192092955078125e-07))   melw float64 [n_mels][257], summed over k in mel_range[m][0 .. 1)
+ * all in float64 with ascending j / k, rounded to fp32 once -> work [total frames][n_mels].  A second launch takes, per utterance and mel
+ * bin, the mean and the unbiased variance over ALL F frames (float64, a fixed order) and writes
+ *   out[row][s n_mels + m] = (mel[stride row + s][m] - mean_m) / sqrt(var_m + 1e-7),     s < stride, row < T
+ * (an odd last frame counts for the statistics and has no row).  n_mels <= 128, 1 <= stride <= 4, ldo >= stride n_mels; B <= 65535;
+ * max_mel_frames (the longest F) sizes the grids. */
+typedef struct ser_fbank_args {
+    const float* wav; const int64_t* sample_offs; const int32_t* mel_offs; const int32_t* frame_offs;
+    const double* dft; const double* melw; const int32_t* mel_range;
+    float* work;
+    float* out; int64_t ldo;
+    int32_t B, max_mel_frames, n_mels, stride;
+} ser_fbank_args;
+int ser_fbank_v(const ser_fbank_args* args, void* stream);
+
+/* ser_relkey_table_v: the query side of the relative-key bias (HF Wav2Vec2BertSelfAttention, position_embeddings_type "relative_key"):
+ *   qe[(m H + h) ld_qe + p] = sum_d q_h[m][d] E[p][d],    p < P = left_max + right_max + 1
+ * in fp32 FMAs with ascending d, q read where the packed projection left it (column block q_col of the operand planes qkv in `mode`:
+ * hi, or hi + lo, as fp32) -- so qe carries the dh^-0.5 log2 e the projection's epilogue gave q.  E fp32 [P][dh]: distance_embedding, shared
+ * by all heads.  Modes SER_MODE_BF16 / FP32X / FP16X; dh % 8 == 0, dh <= 128, P <= 128, H dh <= 2048, ld_qe >= P. */
+typedef struct ser_relkey_table_args {
+    const void* qkv; int64_t ld; int64_t plane_stride;
+    const float* E;
+    float* qe; int64_t ld_qe;
+    int32_t q_col, rows, H, dh, P, mode;
+} ser_relkey_table_args;
+int ser_relkey_table_v(const ser_relkey_table_args* args, void* stream);
+
+/* ser_attention_rk_v: ser_attention_v's tiled attention with the relative-key bias added to every logit,
+ *   out[q, :] = softmax_k( q.k + qe[(q H + h) ld_qe + clamp(k - q, -left_max, right_max) + left_max] ) v,
+ * as further instantiations of the same kernel: `base` is an ser_attention_args with a pre-scaled q (scale <= 0), head dim 64, no table,
+ * gate, key_lens, bias2d or FP16M output; modes SER_MODE_BF16 / FP32X / FP16X.  The S accumulators start at the bias instead of at zero,
+ * so with E = 0 the result is bit-equal to ser_attention_v's low-occupancy form on the same operands.  A key tile wholly left of q - left_max
+ * or wholly right of q + right_max for all 32 queries of a wave adds one constant per query; only tiles that cross the band gather. */
+typedef struct ser_attention_rk_args {
+    ser_attention_args base;
+    const float* qe; int64_t ld_qe;
+    int32_t left_max, right_max;
+} ser_attention_rk_args;
+int ser_attention_rk_v(const ser_attention_rk_args* args, void* stream);
+
+/* ser_conformer_conv_v: the middle of the conformer convolution module (HF Wav2Vec2BertConvModule) between its two pointwise GEMMs:
+ *   g[t][c] = y[t][c] sigmoid(y[t][D + c])                                  GLU of pointwise-1's fp32 output y [rows][ldy >= 2 D]
+ *   u[t][c] = sum_k w[k][c] g[t - (K - 1) + k][c]                           causal depthwise convolution: rows before the utterance's
+ *                                                                           first (frame_offs) are zeros, never the previous utterance's
+ *   out[t]  = swish(LayerNorm_D(u[t]) gamma + beta)                         -> operand planes of pointwise-2's input, in `mode`
+ * fp32 FMAs in ascending k, accurate expf, two-pass LayerNorm statistics in a fixed order.  w fp32 [K][D] (the checkpoint's [D][1][K]
+ * transposed by the host).  A block takes SER_CCONV_TILE rows of one utterance and computes the GLU of each input row once.
+ * D % 4 == 0, D <= 2048, K odd <= 31; pitches multiples of 4.  Modes SER_MODE_BF16 / FP32X / FP16 / FP16X. */
+#define SER_CCONV_TILE 8
+typedef struct ser_conformer_conv_args {
+    const float* y; int64_t ldy;
+    const float* w; const float* gamma; const float* beta;
+    const int32_t* frame_offs;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    uint32_t* range_flag;
+    float eps;
+    int32_t B, D, K, max_frames, rows, mode, reserved0;
+} ser_conformer_conv_args;
+int ser_conformer_conv_v(const ser_conformer_conv_args* args, void* stream);
+
+/* ser_swish_rows_v: fp32 rows x [rows][ldx] -> x sigmoid(x) as GEMM operand planes in `mode` (SER_MODE_BF16 / FP32X / FP16 / FP16X): the
+ * activation between the two GEMMs of a conformer feed-forward block, ser_act_rows_v's counterpart.  Wave per row; D % 4 == 0, D <= 2048 per
+ * 2048-column slab (wider rows take further slabs: D <= 8192), pitches multiples of 4.  range_flag: the fp16 range guard, may be NULL. */
+typedef struct ser_swish_rows_args {
+    const float* x; int64_t ldx;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    uint32_t* range_flag;
+    int32_t mode, rows, D, reserved0;
+} ser_swish_rows_args;
+int ser_swish_rows_v(const ser_swish_rows_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -865,6 +948,11 @@ int ser_snake_v(const ser_snake_args* args, void* stream);
 #define SER_OP_CODEC_UNIT 16
 #define SER_OP_CODEC_CONV 17
 #define SER_OP_SNAKE 18
+#define SER_OP_FBANK 19
+#define SER_OP_RELKEY_TABLE 20
+#define SER_OP_ATTENTION_RK 21
+#define SER_OP_CONFORMER_CONV 22
+#define SER_OP_SWISH_ROWS 23
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -886,6 +974,11 @@ typedef struct ser_cmd {
         ser_codec_unit_args  codec_unit;
         ser_codec_conv_args  codec_conv;
         ser_snake_args       snake;
+        ser_fbank_args       fbank;
+        ser_relkey_table_args relkey_table;
+        ser_attention_rk_args attention_rk;
+        ser_conformer_conv_args conformer_conv;
+        ser_swish_rows_args  swish_rows;
     } u;
 } ser_cmd;
 

@@ -332,6 +332,47 @@ class SnakeArgs(C.Structure):
     ]
 
 
+class FbankArgs(C.Structure):
+    """Mirror of ``ser_fbank_args``."""
+    _fields_ = [
+        ("wav", c_void_p), ("sample_offs", c_void_p), ("mel_offs", c_void_p), ("frame_offs", c_void_p),
+        ("dft", c_void_p), ("melw", c_void_p), ("mel_range", c_void_p), ("work", c_void_p), ("out", c_void_p), ("ldo", c_i64),
+        ("B", C.c_int32), ("max_mel_frames", C.c_int32), ("n_mels", C.c_int32), ("stride", C.c_int32),
+    ]
+
+
+class RelkeyTableArgs(C.Structure):
+    """Mirror of ``ser_relkey_table_args``."""
+    _fields_ = [
+        ("qkv", c_void_p), ("ld", c_i64), ("plane_stride", c_i64), ("E", c_void_p), ("qe", c_void_p), ("ld_qe", c_i64),
+        ("q_col", C.c_int32), ("rows", C.c_int32), ("H", C.c_int32), ("dh", C.c_int32), ("P", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
+class AttentionRkArgs(C.Structure):
+    """Mirror of ``ser_attention_rk_args``."""
+    _fields_ = [("base", AttentionArgs), ("qe", c_void_p), ("ld_qe", c_i64), ("left_max", C.c_int32), ("right_max", C.c_int32)]
+
+
+class ConformerConvArgs(C.Structure):
+    """Mirror of ``ser_conformer_conv_args``."""
+    _fields_ = [
+        ("y", c_void_p), ("ldy", c_i64), ("w", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("frame_offs", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("range_flag", c_void_p), ("eps", c_float),
+        ("B", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("max_frames", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class SwishRowsArgs(C.Structure):
+    """Mirror of ``ser_swish_rows_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64), ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("range_flag", c_void_p),
+        ("mode", C.c_int32), ("rows", C.c_int32), ("D", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+CCONV_TILE = 8                  # SER_CCONV_TILE: rows per block of ser_conformer_conv_v
 CODEC_TILE = 128                # SER_CODEC_TILE: output rows per block of ser_codec_unit_v
 FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
 DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked logit was not finite
@@ -343,7 +384,9 @@ class _CmdUnion(C.Union):
                 ("row_center", RowCenterArgs), ("logmel", LogmelArgs), ("pack_act", PackActArgs), ("gn_stats", GnStatsArgs),
                 ("pos_ln", PosLnArgs), ("dec_embed", DecEmbedArgs), ("dec_attn", DecAttnArgs), ("dec_select", DecSelectArgs),
                 ("prosody_mel", ProsodyMelArgs), ("fvq", FvqArgs), ("act_rows", ActRowsArgs),
-                ("codec_unit", CodecUnitArgs), ("codec_conv", CodecConvArgs), ("snake", SnakeArgs)]
+                ("codec_unit", CodecUnitArgs), ("codec_conv", CodecConvArgs), ("snake", SnakeArgs),
+                ("fbank", FbankArgs), ("relkey_table", RelkeyTableArgs), ("attention_rk", AttentionRkArgs),
+                ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs)]
 
 
 class Cmd(C.Structure):
@@ -355,6 +398,7 @@ OP_GEMM, OP_ATTENTION, OP_LAYERNORM, OP_WAVE_FRAMES, OP_ROW_CENTER, OP_LOGMEL, O
 OP_DEC_EMBED, OP_DEC_ATTN, OP_DEC_SELECT = 10, 11, 12
 OP_PROSODY_MEL, OP_FVQ, OP_ACT_ROWS = 13, 14, 15
 OP_CODEC_UNIT, OP_CODEC_CONV, OP_SNAKE = 16, 17, 18
+OP_FBANK, OP_RELKEY_TABLE, OP_ATTENTION_RK, OP_CONFORMER_CONV, OP_SWISH_ROWS = 19, 20, 21, 22, 23
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -362,7 +406,9 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_fusion_cls_args": FusionClsArgs, "ser_select_rows_args": SelectRowsArgs, "ser_dec_embed_args": DecEmbedArgs, "ser_dec_attn_args": DecAttnArgs,
                   "ser_dec_select_args": DecSelectArgs, "ser_prosody_mel_args": ProsodyMelArgs, "ser_fvq_args": FvqArgs,
                   "ser_act_rows_args": ActRowsArgs, "ser_codec_unit_args": CodecUnitArgs, "ser_codec_conv_args": CodecConvArgs,
-                  "ser_snake_args": SnakeArgs, "ser_cmd": Cmd}
+                  "ser_snake_args": SnakeArgs, "ser_fbank_args": FbankArgs, "ser_relkey_table_args": RelkeyTableArgs,
+                  "ser_attention_rk_args": AttentionRkArgs, "ser_conformer_conv_args": ConformerConvArgs,
+                  "ser_swish_rows_args": SwishRowsArgs, "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -401,6 +447,11 @@ _SIGNATURES = {
     "ser_codec_unit_v": (c_int, [c_void_p, c_void_p]),
     "ser_codec_conv_v": (c_int, [c_void_p, c_void_p]),
     "ser_snake_v": (c_int, [c_void_p, c_void_p]),
+    "ser_fbank_v": (c_int, [c_void_p, c_void_p]),
+    "ser_relkey_table_v": (c_int, [c_void_p, c_void_p]),
+    "ser_attention_rk_v": (c_int, [c_void_p, c_void_p]),
+    "ser_conformer_conv_v": (c_int, [c_void_p, c_void_p]),
+    "ser_swish_rows_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -21,6 +21,7 @@ FAMILY_WHISPER = "whisper"
 FAMILY_ROBERTA = "roberta"      # text side of the bimodal heads (next row 8f-1)
 FAMILY_DEBERTA = "deberta"      # DeBERTa-v2/v3 variant of the text side (engine.DebertaEncoder, csrc/deberta.hip)
 FAMILY_DATA2VEC_AUDIO = "data2vec-audio"   # layer-norm conv stem, post-LN encoder, a stack of LayerNorm'd positional convs
+FAMILY_W2V_BERT = "wav2vec2-bert"          # Kaldi fbank front end, conformer layers with a relative-key attention bias (engine.W2vBertEncoder)
 
 SPEECH_FAMILIES = (FAMILY_WAVLM, FAMILY_WAV2VEC2, FAMILY_HUBERT, FAMILY_DATA2VEC_AUDIO)
 
@@ -64,6 +65,13 @@ class EncoderGeometry:
     position_buckets: int = 256
     # DeBERTa-v2 xlarge / xxlarge: ConvLayer after encoder layer 0 (HF modeling_deberta_v2.py ConvLayer; 0 = none, as in v3)
     text_conv_kernel: int = 0
+    # w2v-BERT 2.0 (HF Wav2Vec2BertModel): stacked log-mel rows in (fbank_mels x fbank_stride = feature_projection_input_dim), the causal
+    # depthwise kernel of the conformer convolution module, and the clamp of the relative-key distance embedding
+    fbank_mels: int = 80
+    fbank_stride: int = 2
+    conv_depthwise_kernel: int = 31
+    left_max_positions: int = 64
+    right_max_positions: int = 8
     name: str = ""
 
     @property
@@ -105,9 +113,20 @@ class EncoderGeometry:
         """Integer frame count of the conv stack: floor((L-k)/s)+1 per layer
         (HF modeling_wavlm.py:633-652).  Bit-exact gate of SURVEY 8a row a8."""
         n = int(num_samples)
+        if self.family == FAMILY_W2V_BERT:
+            # 400-sample frames every 160 (center=False), stacked fbank_stride at a time; HF's extra masked row of an odd count is not a row here
+            return max(0, 1 + (n - 400) // 160) // self.fbank_stride if n >= 400 else 0
         for k, s in zip(self.conv_kernel, self.conv_stride):
             n = (n - k) // s + 1
         return n
+
+    @property
+    def fbank_dim(self) -> int:
+        return self.fbank_mels * self.fbank_stride
+
+    @property
+    def distance_positions(self) -> int:
+        return self.left_max_positions + self.right_max_positions + 1
 
     def frame_chain(self, num_samples: int):
         out = []
@@ -200,6 +219,11 @@ DATA2VEC_AUDIO_LARGE = EncoderGeometry(
     family=FAMILY_DATA2VEC_AUDIO, num_layers=24, hidden=1024, heads=16, ffn=4096, conv_bias=False, stable_layer_norm=False,
     pos_conv_kernel=19, pos_conv_groups=16, pos_conv_layers=5, pos_conv_norm="layer", name="facebook/data2vec-audio-large")
 
+# w2v-BERT 2.0: transformers' Wav2Vec2BertConfig() defaults are the checkpoint's (24 conformer layers, 16 heads of 64, 600 M parameters)
+W2V_BERT_2 = EncoderGeometry(
+    family=FAMILY_W2V_BERT, num_layers=24, hidden=1024, heads=16, ffn=4096, fbank_mels=80, fbank_stride=2, conv_depthwise_kernel=31,
+    left_max_positions=64, right_max_positions=8, layer_norm_eps=1e-5, name="facebook/w2v-bert-2.0")
+
 _REGISTRY = {
     "microsoft/deberta-v3-large": DEBERTA_V3_LARGE,
     "microsoft/deberta-v2-xlarge": DEBERTA_V2_XLARGE,
@@ -222,12 +246,14 @@ _REGISTRY = {
     "facebook/data2vec-audio-base-960h": replace(DATA2VEC_AUDIO_BASE, name="facebook/data2vec-audio-base-960h"),
     "facebook/data2vec-audio-large": DATA2VEC_AUDIO_LARGE,
     "facebook/data2vec-audio-large-960h": replace(DATA2VEC_AUDIO_LARGE, name="facebook/data2vec-audio-large-960h"),
+    "facebook/w2v-bert-2.0": W2V_BERT_2,
 }
 
 
 def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int = 2,
                   ffn: int = 256, conv_dim: int = 64, pos_groups: int = 2, text_conv_kernel: int = 0,
-                  base: bool = False, conv_bias: bool = False) -> EncoderGeometry:
+                  base: bool = False, conv_bias: bool = False, depthwise_kernel: int = 31, left_max: int = 64,
+                  right_max: int = 8) -> EncoderGeometry:
     """Small geometries with the real kernel/stride tuples; used by the parity
     fixtures under tests/golden (SURVEY 8c item 1).  ``hidden // heads`` selects
     the head-dim code path (64 WavLM/Whisper, 80 HuBERT-XL, 120 XLS-R-2B) and
@@ -246,6 +272,10 @@ def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int
         return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads,
                                ffn=ffn, n_mels=128, max_source_positions=1500,
                                name=f"tiny-{family}-d{hidden}h{heads}")
+    if family == FAMILY_W2V_BERT:
+        return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn, conv_depthwise_kernel=depthwise_kernel,
+                               left_max_positions=left_max, right_max_positions=right_max,
+                               name=f"tiny-w2v-bert-d{hidden}h{heads}")
     if family == FAMILY_DATA2VEC_AUDIO:
         return EncoderGeometry(
             family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn, conv_dim=(conv_dim,) * 7, conv_bias=conv_bias,
@@ -356,8 +386,33 @@ def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
             pos_conv_kernel=k, pos_conv_groups=int(cfg.get("num_conv_pos_embedding_groups", 16)),
             pos_conv_layers=int(cfg.get("num_conv_pos_embeddings", 5)), pos_conv_norm="layer",
             layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), name=name)
+    if mt == FAMILY_W2V_BERT:
+        # HF Wav2Vec2BertConfig.  Built: relative-key positions, the swish activation, no adapter (facebook/w2v-bert-2.0's settings).
+        pos = cfg.get("position_embeddings_type", "relative_key")
+        if pos != "relative_key":
+            raise OSError(f"{name}: position_embeddings_type='{pos}' is not supported (the path implements relative_key)")
+        if cfg.get("add_adapter", False):
+            raise OSError(f"{name}: add_adapter=True (an adapter stack after the encoder) is not supported")
+        if str(cfg.get("hidden_act", "swish")) not in ("swish", "silu"):
+            raise OSError(f"{name}: hidden_act='{cfg.get('hidden_act')}' is not supported (the path implements swish)")
+        k = int(cfg.get("conv_depthwise_kernel_size", 31))
+        if k % 2 == 0:
+            raise OSError(f"{name}: an even conv_depthwise_kernel_size ({k}) is not supported")
+        if k > 31:
+            raise OSError(f"{name}: conv_depthwise_kernel_size {k} is beyond the 31 taps the convolution-module kernel holds")
+        lm, rm = int(cfg.get("left_max_position_embeddings", 64)), int(cfg.get("right_max_position_embeddings", 8))
+        if lm < 0 or rm < 0 or lm + rm + 1 > 128:
+            raise OSError(f"{name}: left_max_position_embeddings + right_max_position_embeddings + 1 = {lm + rm + 1} is beyond 128 distances")
+        fdim, stride = int(cfg.get("feature_projection_input_dim", 160)), int(cfg.get("fbank_stride", 2))
+        if stride < 1 or fdim % stride:
+            raise OSError(f"{name}: feature_projection_input_dim {fdim} is not a multiple of the frame stacking {stride}")
+        return EncoderGeometry(
+            family=FAMILY_W2V_BERT, num_layers=int(cfg["num_hidden_layers"]), hidden=int(cfg["hidden_size"]),
+            heads=int(cfg["num_attention_heads"]), ffn=int(cfg["intermediate_size"]), fbank_mels=fdim // stride, fbank_stride=stride,
+            conv_depthwise_kernel=k, left_max_positions=lm, right_max_positions=rm,
+            layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), name=name)
     raise OSError(f"{name}: model_type '{mt}' is not an encoder this path implements "
-                  "(wavlm / wav2vec2 / hubert / data2vec-audio / whisper / roberta / deberta-v2)")
+                  "(wavlm / wav2vec2 / hubert / data2vec-audio / wav2vec2-bert / whisper / roberta / deberta-v2)")
 
 
 def find_config_json(ssl_type: str, checkpoint: str = "") -> str:
@@ -420,6 +475,28 @@ def resolve_do_normalize(ssl_type: str, checkpoint: str = "") -> bool:
     return bool(cfg.get("do_normalize", True))
 
 
+def resolve_fbank(geo: EncoderGeometry, ssl_type: str, checkpoint: str = "") -> EncoderGeometry:
+    """A w2v-BERT geometry with the front end's mel count and frame stacking taken from the snapshot's ``preprocessor_config.json``
+    (HF SeamlessM4TFeatureExtractor: ``num_mel_bins`` / ``feature_size`` and ``stride``); 80 and 2 when there is no such file.  Their
+    product must be the model's ``feature_projection_input_dim``."""
+    import json
+    if geo.family != FAMILY_W2V_BERT:
+        return geo
+    path = find_preprocessor_config(ssl_type, checkpoint)
+    mels, stride = 80, 2
+    if path:
+        try:
+            with open(path, "r") as f:
+                cfg = json.load(f)
+        except (OSError, ValueError) as e:
+            raise OSError(f"cannot read {path}: {e}")
+        mels, stride = int(cfg.get("num_mel_bins", cfg.get("feature_size", 80))), int(cfg.get("stride", 2))
+    if mels * stride != geo.fbank_dim:
+        raise OSError(f"{ssl_type}: the feature extractor stacks {stride} frames of {mels} mel bins, the model's feature projection "
+                      f"reads {geo.fbank_dim} columns")
+    return replace(geo, fbank_mels=mels, fbank_stride=stride)
+
+
 def with_layers(geo: EncoderGeometry, layers: int) -> EncoderGeometry:
     g = replace(geo, num_layers=layers)
     if geo.decoder is not None:                             # replace() goes through __init__, which knows no decoder
@@ -446,6 +523,10 @@ TINY_HUBERT_BASE = tiny_geometry(FAMILY_HUBERT, hidden=128, heads=2, ffn=256, po
 # model's (768 / 16), not a multiple of 64, so the stack's GEMMs read the padded channels of pos_kc
 TINY_DATA2VEC_AUDIO = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=128, heads=2, ffn=256, pos_groups=2)
 TINY_DATA2VEC_AUDIO_G48 = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=192, heads=3, ffn=256, pos_groups=4, conv_bias=True)
+# w2v-BERT fixture geometries (tests/golden/tiny_w2v_bert_*.npz): the checkpoint's kernel and clamp, and a second set (7 taps, clamp -5 .. 3,
+# three heads) that no constant of the first survives
+TINY_W2V_BERT = tiny_geometry(FAMILY_W2V_BERT, hidden=128, heads=2, ffn=256)
+TINY_W2V_BERT_H3 = tiny_geometry(FAMILY_W2V_BERT, hidden=192, heads=3, ffn=384, depthwise_kernel=7, left_max=5, right_max=3)
 
 
 @dataclass(frozen=True)

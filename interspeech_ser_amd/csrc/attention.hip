@@ -50,12 +50,16 @@ extern "C" { void* ser_attn_dbg_ptr = nullptr; }
 // 16-utterance x 16-head x 499-frame launch are resident in ONE round instead of two (40.5 -> 37.0 us; ragged 64..499 frames 34.3 -> 30.5).
 // With at most two blocks per CU to place (8-utterance launches: 512 blocks) the low-occupancy form -- double buffer, all LDS reads of a phase
 // up front, 198 registers -- is the faster one (23.0 against 24.4 us): the launcher picks by grid size.
-template <int DHP, int MODE, bool PRE, bool TBL, int NWV = 4, bool B2D = false, bool GB = false, bool OCC = false>
+// RK (ser_attention_rk_v: w2v-BERT's relative-key bias; needs PRE, excludes TBL / B2D / GB / OCC): the S accumulators start at
+// qe[query][head][clamp(key - query, -Lm, Rm) + Lm], read from global memory per lane -- one constant per query for a key tile wholly outside
+// the band of all 32 queries of the wave, a gather for the tiles that cross it.  Every RK line sits under `if constexpr (RK)`: the other
+// instantiations compile what they compiled before.
+template <int DHP, int MODE, bool PRE, bool TBL, int NWV = 4, bool B2D = false, bool GB = false, bool OCC = false, bool RK = false>
 // waves per SIMD the registers leave room for: two everywhere (round 4: the 96-wide two-plane forms and the 128-wide ones WITHOUT a bias table
 // fit 256 registers unspilled -- head dim 80 in the 3-product modes 98.9 -> 49.9 us per 8 x 499 frames) except the 128-wide two-plane form
 // with a bias table (208 spilled registers at two; no encoder uses it: WavLM's head dim is 64)
 __global__ __launch_bounds__(64 * NWV, (DHP == 128 && mode_traits<MODE>::planes == 2 && TBL) ? 1 : (OCC ? 4 : 2))
-void attention_kernel(const AttnParams p) {
+void attention_kernel(const std::conditional_t<RK, AttnParamsRK, AttnParams> p) {
     constexpr int NT = 64 * NWV;                // threads per block
     // NP: planes of Q and K (the logit path S = K Q^T: 3 products when 2), NPV: planes of V and P.  FP16Q (the "f16q" numerics
     // mode) keeps the logits fp32-grade -- q, k arrive as fp16 hi + lo planes -- and runs P V on single fp16 products; its
@@ -308,6 +312,19 @@ void attention_kernel(const AttnParams p) {
         }
     };
 
+    // RK: the relative-key bias of keys kb..kb+3 for this lane's query; side -1 / +1: the tile lies wholly left / right of the band
+    auto rk_quad = [&](int kb, int side) -> f32x4 {
+        if constexpr (RK) {
+            const float* qerow = p.qe + ((int64_t)(row0 + qc) * p.H + h) * p.qe_ld;
+            if (side) { const float c = qerow[side < 0 ? 0 : p.Lm + p.Rm]; return (f32x4){c, c, c, c}; }
+            f32x4 r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = qerow[min(max(kb + e - qc, -p.Lm), p.Rm) + p.Lm];
+            return r;
+        } else {
+            return (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+    };
     f32x16 ot[DSUB];
 #pragma unroll
     for (int i = 0; i < DSUB; ++i)
@@ -349,6 +366,11 @@ void attention_kernel(const AttnParams p) {
 #endif
         DBG_T(0);
         if (DB && kt + 1 < nkt) stage_load(kt + 1, padded || kt + 1 >= nfull);   // issue early: lands under the MFMAs below
+        int rk_side = 0;                                             // RK, wave-uniform: where the tile lies for queries qlo .. qlo + 31
+        if constexpr (RK) {
+            const int qlo = q0 + wave * 32, k0 = kt * ABKV;
+            rk_side = (k0 + ABKV - 1 <= qlo - p.Lm) ? -1 : ((k0 >= qlo + 31 + p.Rm) ? 1 : 0);
+        }
 
         // ---- S^T = K Q^T  (rows = keys in registers, col = query on the lane)
         // PRE (q pre-scaled by dh^-0.5*log2e in the projection epilogue): the accumulators START at the
@@ -371,6 +393,13 @@ void attention_kernel(const AttnParams p) {
                     for (int g4 = 0; g4 < 4; ++g4)
                         bvv[sub][g4] = *(const f32x4*)(brow + kt * ABKV + sub * 32 + 8 * g4 + 4 * hh);
             }
+            if constexpr (RK) {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4)
+                        bvv[sub][g4] = rk_quad(kt * ABKV + sub * 32 + 8 * g4 + 4 * hh, rk_side);
+            }
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 const int key = sub * 32 + l31;
@@ -386,7 +415,7 @@ void attention_kernel(const AttnParams p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         st[sub][4 * g4 + r] = (PRE && TBL) ? (LAZY ? fmaf(gq2, bvv[sub][g4][r], -m_run) : gq2 * bvv[sub][g4][r])
-                                                           : ((PRE && B2D) ? bvv[sub][g4][r] : 0.f);
+                                                           : (((PRE && B2D) || RK) ? bvv[sub][g4][r] : 0.f);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)                          // the two key halves are independent chains
 #pragma unroll
@@ -407,6 +436,13 @@ void attention_kernel(const AttnParams p) {
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
                         const f32x4 bv = *(const f32x4*)(brow + kt * ABKV + sub * 32 + 8 * g4 + 4 * hh);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) st[sub][4 * g4 + r] = bv[r];
+                    }
+                } else if (RK) {
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        const f32x4 bv = rk_quad(kt * ABKV + sub * 32 + 8 * g4 + 4 * hh, rk_side);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) st[sub][4 * g4 + r] = bv[r];
                     }
@@ -683,6 +719,42 @@ static int launch_attention(const AttnParams& p, const attn_launch& pl, hipStrea
         if (hipError_t e = ser_lds_optin(k, 160 * 1024, ready)) return ser_fail((int)e, "ser_attention: cannot raise dynamic LDS");
     hipLaunchKernelGGL(k, dim3(pl.grid, 1, 1), dim3(64 * ATTN_NWV), pl.lds, s, p);
     return ser_check_launch("ser_attention");
+}
+
+// ser_attention_rk_v: the base arguments are planned as ser_attention_v plans them, then moved to the low-occupancy form (the RK forms have
+// no high-occupancy instantiation: the bias registers would not fit its 128).
+extern "C" int ser_attention_rk_v(const ser_attention_rk_args* ra, void* stream) {
+    if (!ra || !ra->qe) return ser_fail(-1, "ser_attention_rk: null pointer");
+    const ser_attention_args* args = &ra->base;
+    if (args->table || args->gate || args->gru_const || args->gate_x || args->key_lens || args->bias2d || args->out_mode)
+        return ser_fail(-2, "ser_attention_rk: takes no table, gate, key_lens, bias2d or FP16M output");
+    if (args->scale > 0.f || args->dh != 64) return ser_fail(-2, "ser_attention_rk: needs a pre-scaled q (scale <= 0) and head dim 64");
+    if (args->mode != SER_MODE_BF16 && args->mode != SER_MODE_FP32X && args->mode != SER_MODE_FP16X)
+        return ser_fail(-5, "ser_attention_rk: bad mode %d (bf16 / fp32x / fp16x)", args->mode);
+    if (ra->left_max < 0 || ra->right_max < 0 || ra->left_max + ra->right_max + 1 > 128 || ra->ld_qe < ra->left_max + ra->right_max + 1)
+        return ser_fail(-2, "ser_attention_rk: left_max=%d right_max=%d ld_qe=%lld unsupported", ra->left_max, ra->right_max, (long long)ra->ld_qe);
+    attn_launch pl;
+    if (int rc = attn_plan(args, &pl)) return rc;
+    if (pl.occ) {                                   // the double-buffered form's LDS: two K + V buffers, no bias window
+        pl.occ = false;
+        pl.nbuf = 2;
+        pl.lds = (size_t)2 * (attn_qk_planes(pl.mode) + attn_v_planes(pl.mode)) * ATTN_BKV * pl.dhp * 2;
+    }
+    AttnParamsRK p = {};
+    p.qkv = (const unsigned short*)args->qkv; p.ld = args->ld; p.plane = args->plane_stride;
+    p.q_col = args->q_col; p.k_col = args->k_col; p.v_col = args->v_col;
+    p.frame_offs = args->frame_offs;
+    p.out = (unsigned short*)args->out; p.ldo = args->ldo; p.out_plane = args->out_plane_stride;
+    p.H = args->H; p.dh = args->dh; p.scale = args->scale; p.b2d_T = args->max_frames;
+    p.B = args->B; p.nq = pl.nq; p.nitems = (int)pl.grid;
+    p.qe = ra->qe; p.qe_ld = ra->ld_qe; p.Lm = ra->left_max; p.Rm = ra->right_max;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(pl.mode, [&](auto M) {
+            hipLaunchKernelGGL((attention_kernel<64, M(), true, false, ATTN_NWV, false, false, false, true>), dim3(pl.grid, 1, 1), dim3(64 * ATTN_NWV),
+                               pl.lds, s, p);
+        }))
+        return ser_fail(-5, "ser_attention_rk: bad mode %d", pl.mode);
+    return ser_check_launch("ser_attention_rk");
 }
 
 extern "C" int ser_attention(const void* qkv, int64_t ld, int64_t plane_stride, int q_col, int k_col, int v_col,

@@ -44,6 +44,12 @@ struct AttnParams {
     unsigned long long* dbg;   // phase timestamps of one wave (tools/attn_phases.py; never in the product build)
 #endif
 };
+// ser_attention_rk_v's forms (RK) take the block with the relative-key table behind it; the other forms' argument block stays as it is.
+struct AttnParamsRK : AttnParams {
+    const float* qe;      // [rows][H][qe_ld] fp32, exp2 domain (built from the pre-scaled q)
+    int64_t qe_ld;
+    int Lm, Rm;           // clamp of key - query
+};
 #ifdef SER_ATTN_DBG
 extern "C" { extern void* ser_attn_dbg_ptr; }
 #define DBG_P(i) do { __builtin_amdgcn_sched_barrier(0); dbg_p[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)

@@ -107,6 +107,26 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_snake_v(&c.u.snake, stream);
                 break;
             }
+            case SER_OP_FBANK: {
+                rc = ser_fbank_v(&c.u.fbank, stream);
+                break;
+            }
+            case SER_OP_RELKEY_TABLE: {
+                rc = ser_relkey_table_v(&c.u.relkey_table, stream);
+                break;
+            }
+            case SER_OP_ATTENTION_RK: {
+                rc = ser_attention_rk_v(&c.u.attention_rk, stream);
+                break;
+            }
+            case SER_OP_CONFORMER_CONV: {
+                rc = ser_conformer_conv_v(&c.u.conformer_conv, stream);
+                break;
+            }
+            case SER_OP_SWISH_ROWS: {
+                rc = ser_swish_rows_v(&c.u.swish_rows, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

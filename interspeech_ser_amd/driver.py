@@ -130,6 +130,7 @@ class _Extractor:
         from .engine import build_encoder
         self.args, self.whisper = args, whisper
         self.geo = C.resolve_geometry(args.ssl_type, args.checkpoint)      # config.json of the checkpoint, else the built-in table
+        self.geo = C.resolve_fbank(self.geo, args.ssl_type, args.checkpoint)   # w2v-BERT: mel count and stacking of preprocessor_config.json
         if whisper != (self.geo.family == C.FAMILY_WHISPER):
             raise OSError(f"{args.ssl_type} is not a {'whisper' if whisper else 'wav2vec2-style'} encoder")
         from . import dist as D
@@ -165,6 +166,10 @@ class _Extractor:
         if not whisper and not geo.stable_layer_norm and mode not in POST_LN_MODES:
             # the post-LayerNorm (*-base) encoders run the text encoders' modes; the others need FP16M copies out of ser_layernorm
             print(f"--mode {mode} is not implemented for post-LayerNorm encoders ({name}): using f16x")
+            mode = "f16x"
+        if geo.family == C.FAMILY_W2V_BERT and mode not in POST_LN_MODES:
+            # the conformer layers run ser_layernorm between their GEMMs, like the post-LayerNorm encoders: the same three modes
+            print(f"--mode {mode} is not implemented for the conformer encoder ({name}): using f16x")
             mode = "f16x"
         return mode
 

@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import check, lib
 from .weights import check_f16_weight
-from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_WAVLM, FAMILY_WHISPER
+from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_WAVLM, FAMILY_WHISPER
 
 MODES = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X, "f16": _lib.MODE_FP16, "f16q": _lib.MODE_FP16, "f16a": _lib.MODE_FP16,
          "f16x": _lib.MODE_FP16X, "f16m": _lib.MODE_FP16M, "f16mf": _lib.MODE_FP16M}
@@ -3039,6 +3039,217 @@ class SpeakerProsodyEncoder(_PreLnStack):
                                       pp["frame_offs"], pp["err"], pl["enc"][:M], self.pos0, keep)
 
 
+class W2vBertEncoder(_EncoderBase):
+    """w2v-BERT 2.0 (HF Wav2Vec2BertModel behind SeamlessM4TFeatureExtractor; not in the reference, whose heads take any [T, D] stream) on
+    libserhip: the Kaldi fbank front end (ser_fbank_v), the feature projection, and per conformer layer
+        x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(LN x);  x += FFN2(LN x) / 2;  x = LN x
+    on ser_layernorm_v and ser_gemm, with ser_swish_rows_v between a feed-forward block's GEMMs, ser_relkey_table_v + ser_attention_rk_v for
+    the relative-key attention and ser_conformer_conv_v between the convolution module's pointwise GEMMs.  The two 1/2 factors are folded
+    into the blocks' output Linears at load.  Every utterance alone: ``frames(n) = (1 + (n - 400) // 160) // stride`` rows, at least one."""
+
+    use_tape = True
+    upload = SpeechEncoder.upload
+    upload_resampled = SpeechEncoder.upload_resampled
+    _resample_bank = SpeechEncoder._resample_bank
+    download = SpeechEncoder.download
+
+    def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "f16x"):
+        from .frontend import w2vbert_dft_table, w2vbert_mel_filters
+        from .weights import fold_w2v_bert_ffn
+        super().__init__(geo, device, mode, post_ln=True)
+        sd = state_dict
+        D, dh, K = geo.hidden, geo.head_dim, geo.conv_depthwise_kernel
+        if dh != 64:
+            raise ValueError(f"the relative-key attention is built for heads of 64 (hidden {D} / {geo.heads} heads = {dh})")
+        if D % 64 or geo.ffn % 64 or D > 2048:
+            raise ValueError(f"hidden {D} / intermediate {geo.ffn} must be multiples of 64, hidden <= 2048")
+        if not (K & 1) or K > 31 or geo.distance_positions > 128:
+            raise ValueError(f"depthwise kernel {K} (odd, <= 31) / {geo.distance_positions} distances (<= 128) unsupported")
+        melw, rng = w2vbert_mel_filters(geo.fbank_mels)
+        self.melw = torch.from_numpy(melw).to(self.device)
+        self.mel_range = torch.from_numpy(rng).to(self.device)
+        self.dft = torch.from_numpy(w2vbert_dft_table()).to(self.device)
+        # feature projection: LayerNorm(160) -> Linear(160 -> D); K is padded with zero columns to the GEMM's 64-deep tiles
+        self.fdim = geo.fbank_dim
+        self.fpad = ((self.fdim + 63) // 64) * 64
+        self.proj_ln = self._ln_pair(sd, "feature_projection.layer_norm")
+        w = torch.zeros(D, self.fpad)
+        w[:, : self.fdim] = sd["feature_projection.projection.weight"].detach().float().cpu()
+        self.proj = self._linear(w, sd["feature_projection.projection.bias"], name="feature_projection.projection.weight")
+        self.qe_ld = ((geo.distance_positions + 3) // 4) * 4
+        self.layers = []
+        for i in range(geo.num_layers):
+            p = f"encoder.layers.{i}"
+            a, c = p + ".self_attn", p + ".conv_module"
+            lay = {}
+            for f in ("ffn1", "ffn2"):
+                lay[f + "_ln"] = self._ln_pair(sd, f"{p}.{f}_layer_norm")
+                lay[f + "_fc1"] = self._linear(sd[f"{p}.{f}.intermediate_dense.weight"], sd[f"{p}.{f}.intermediate_dense.bias"],
+                                               name=f"{p}.{f}.intermediate_dense.weight")
+                lay[f + "_fc2"] = self._linear(*fold_w2v_bert_ffn(sd[f"{p}.{f}.output_dense.weight"], sd[f"{p}.{f}.output_dense.bias"]),
+                                               name=f"{p}.{f}.output_dense.weight")
+            lay["attn_ln"] = self._ln_pair(sd, p + ".self_attn_layer_norm")
+            lay["qkv"] = self._linear(torch.cat([sd[f"{a}.linear_{n}.weight"] for n in "qkv"], 0), torch.cat([sd[f"{a}.linear_{n}.bias"] for n in "qkv"], 0),
+                                      name=a + ".linear_{q,k,v}.weight")
+            lay["out"] = self._linear(sd[a + ".linear_out.weight"], sd[a + ".linear_out.bias"], name=a + ".linear_out.weight")
+            lay["E"] = self._dev_f32(sd[a + ".distance_embedding.weight"])
+            lay["conv_ln"] = self._ln_pair(sd, c + ".layer_norm")
+            lay["pw1"] = self._linear(sd[c + ".pointwise_conv1.weight"].reshape(2 * D, D), None, name=c + ".pointwise_conv1.weight")
+            lay["dw"] = self._dev_f32(sd[c + ".depthwise_conv.weight"].reshape(D, K).t())        # [K][D]: a thread's 4 channels are one load
+            lay["dw_ln"] = self._ln_pair(sd, c + ".depthwise_layer_norm")
+            lay["pw2"] = self._linear(sd[c + ".pointwise_conv2.weight"].reshape(D, D), None, name=c + ".pointwise_conv2.weight")
+            lay["final_ln"] = self._ln_pair(sd, p + ".final_layer_norm")
+            self.layers.append(lay)
+        self._arenas: Dict[int, dict] = {}
+
+    def frames(self, num_samples: int) -> int:
+        return self.geo.frames_for(num_samples)
+
+    # ------------------------------------------------------------------ buffers
+    def _arena(self, slot: int, M: int, B: int, Fr: int) -> dict:
+        """grow-only buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena)"""
+        ar = self._arenas.get(slot)
+        if ar is not None and ar["cap_M"] >= M and ar["cap_B"] >= B and ar["cap_F"] >= Fr:
+            return ar
+        M, B, Fr = max(M, ar["cap_M"] if ar else 0), max(B, ar["cap_B"] if ar else 0), max(Fr, ar["cap_F"] if ar else 0)
+        geo, dev = self.geo, self.device
+        D, F, H = geo.hidden, geo.ffn, geo.heads
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ar = dict(cap_M=M, cap_B=B, cap_F=Fr, plan=None)
+        ar["mel"], ar["fb"] = f32(Fr, geo.fbank_mels), f32(M, self.fdim)
+        ar["fb_act"] = self._new_act(M, self.fpad, zero=True)                 # columns past 160 stay zero
+        ar["states"] = f32(geo.num_layers + 1, M, D)
+        ar["r1"], ar["r2"], ar["r3"], ar["r4"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D)
+        ar["f1"], ar["pw"], ar["qe"] = f32(M, F), f32(M, 2 * D), f32(M * H, self.qe_ld)
+        ar["xa"], ar["ctx"], ar["cv"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
+        ar["qkv"], ar["ffn"] = self._new_act(M, 3 * D), self._new_act(M, F)
+        ar["sample_offs"] = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        ar["mel_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        ar["frame_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        if self.fp16_planes:
+            ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._arenas[slot] = ar
+        return ar
+
+    def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
+        from .frontend import W2VBERT_MIN_SAMPLES, w2vbert_mel_frames
+        lengths = tuple(int(n) for n in lengths)
+        B, stride = len(lengths), self.geo.fbank_stride
+        Fr = [w2vbert_mel_frames(n) for n in lengths]
+        if B == 0 or min(Fr) < max(2, stride):
+            raise ValueError(f"utterance shorter than {W2VBERT_MIN_SAMPLES} samples: it has no stacked fbank row")
+        T = [f // stride for f in Fr]
+        offs = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+        moffs = np.concatenate([[0], np.cumsum(Fr)]).astype(np.int64)
+        M, Tmax, Fmax = int(offs[-1]), max(T), max(Fr)
+        ar = self._arena(slot, M, B, int(moffs[-1]))
+        if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
+            return ar["plan"]
+        ar["sample_offs"][: B + 1].copy_(torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))
+        ar["mel_offs_all"][: B + 1].copy_(torch.from_numpy(moffs.astype(np.int32)))
+        ar["frame_offs_all"][: B + 1].copy_(torch.from_numpy(offs.astype(np.int32)))
+        pl = dict(ar)
+        pl.update(lengths=lengths, B=Sz(B, "B"), M=Sz(M, "M"), MH=Sz(M * self.geo.heads, "MH"), Tmax=Sz(Tmax, "Tmax"), Fmax=Sz(Fmax, "Fmax"),
+                  sizes=dict(B=B, M=M, MH=M * self.geo.heads, Tmax=Tmax, Fmax=Fmax), frame_offs=ar["frame_offs_all"][: B + 1],
+                  mel_offs=ar["mel_offs_all"][: B + 1], frame_offs_host=[int(v) for v in offs], states=ar["states"][:, :M])
+        ar["plan"] = pl
+        return pl
+
+    # ------------------------------------------------------------------ launches
+    def _fbank(self, pl, packed_wave: torch.Tensor) -> None:
+        geo = self.geo
+        a = self._cmd("fbank")
+        a.wav, a.sample_offs, a.mel_offs, a.frame_offs = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), pl["mel_offs"].data_ptr(), pl["frame_offs"].data_ptr()
+        a.dft, a.melw, a.mel_range, a.work = self.dft.data_ptr(), self.melw.data_ptr(), self.mel_range.data_ptr(), pl["mel"].data_ptr()
+        a.out, a.ldo = pl["fb"].data_ptr(), self.fdim
+        a.B, a.max_mel_frames, a.n_mels, a.stride = pl["B"], pl["Fmax"], geo.fbank_mels, geo.fbank_stride
+        self._issue(_lib.OP_FBANK, a, "ser_fbank", input="wav", B=pl["B"], max_mel_frames=pl["Fmax"])
+
+    def _swish_rows(self, x: torch.Tensor, out: Act, rows: int, D: int) -> None:
+        a = self._cmd("swish_rows")
+        a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), D, out.ptr, out.cols, out.plane_stride
+        a.range_flag, a.mode, a.rows, a.D = self._flag, self.mode, rows, D
+        self._issue(_lib.OP_SWISH_ROWS, a, "ser_swish_rows", rows=rows)
+
+    def _relkey_attention(self, pl, lay) -> None:
+        geo = self.geo
+        D, H, P = geo.hidden, geo.heads, geo.distance_positions
+        qkv, out = pl["qkv"], pl["ctx"]
+        t = self._cmd("relkey_table")
+        t.qkv, t.ld, t.plane_stride, t.E, t.qe, t.ld_qe = qkv.ptr, qkv.cols, qkv.plane_stride, lay["E"].data_ptr(), pl["qe"].data_ptr(), self.qe_ld
+        t.q_col, t.rows, t.H, t.dh, t.P, t.mode = 0, pl["M"], H, geo.head_dim, P, self.mode
+        self._issue(_lib.OP_RELKEY_TABLE, t, "ser_relkey_table", rows=pl["M"])
+        r = self._cmd("attention_rk")
+        a = r.base
+        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
+        a.q_col, a.k_col, a.v_col, a.B = 0, D, 2 * D, pl["B"]
+        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
+        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
+        a.H, a.dh, a.scale, a.mode = H, geo.head_dim, -1.0, self.mode          # q is pre-scaled
+        r.qe, r.ld_qe, r.left_max, r.right_max = pl["qe"].data_ptr(), self.qe_ld, geo.left_max_positions, geo.right_max_positions
+        if self._rec is not None:                                               # the per-batch sizes live in the embedded base struct
+            self._rec.patches += [(a, "B", "B"), (a, "max_frames", "Tmax")]
+        self._issue(_lib.OP_ATTENTION_RK, r, "ser_attention_rk")
+
+    def _conv_mid(self, pl, lay) -> None:
+        geo = self.geo
+        out = pl["cv"]
+        a = self._cmd("conformer_conv")
+        a.y, a.ldy, a.w, a.gamma, a.beta = pl["pw"].data_ptr(), 2 * geo.hidden, lay["dw"].data_ptr(), lay["dw_ln"][0].data_ptr(), lay["dw_ln"][1].data_ptr()
+        a.frame_offs, a.out_act, a.ldo_act, a.out_plane_stride = pl["frame_offs"].data_ptr(), out.ptr, out.cols, out.plane_stride
+        a.range_flag, a.eps = self._flag, float(geo.layer_norm_eps)
+        a.B, a.D, a.K, a.max_frames, a.rows, a.mode = pl["B"], geo.hidden, geo.conv_depthwise_kernel, pl["Tmax"], pl["M"], self.mode
+        self._issue(_lib.OP_CONFORMER_CONV, a, "ser_conformer_conv", B=pl["B"], max_frames=pl["Tmax"], rows=pl["M"])
+
+    def _ffn_half(self, pl, lay, f: str, x: torch.Tensor, out: torch.Tensor) -> None:
+        """out = x + FFN(LN x) / 2 (the half sits in the output Linear)"""
+        M, D, F = pl["M"], self.geo.hidden, self.geo.ffn
+        self._layernorm(x, D, lay[f + "_ln"], M, D, out_act=pl["xa"])
+        self._gemm(pl["xa"], lay[f + "_fc1"], M, out_f32=pl["f1"], ldo_f32=F)
+        self._swish_rows(pl["f1"], pl["ffn"], M, F)
+        self._gemm(pl["ffn"], lay[f + "_fc2"], M, residual=x, ldr=D, out_f32=out, ldo_f32=D)
+
+    def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
+        geo = self.geo
+        M, D = pl["M"], geo.hidden
+        states = pl["states"]
+        scale = geo.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
+        self._fbank(pl, packed_wave)
+        self._layernorm(pl["fb"], self.fdim, self.proj_ln, M, self.fdim, out_act=pl["fb_act"])
+        self._gemm(pl["fb_act"], self.proj, M, out_f32=states[0], ldo_f32=D)
+        if self._state_done(0, last_state):
+            return
+        for i, lay in enumerate(self.layers):
+            x = states[i]
+            self._ffn_half(pl, lay, "ffn1", x, pl["r1"])
+            self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_act=pl["xa"])
+            self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
+            self._relkey_attention(pl, lay)
+            self._gemm(pl["ctx"], lay["out"], M, residual=pl["r1"], ldr=D, out_f32=pl["r2"], ldo_f32=D)
+            self._layernorm(pl["r2"], D, lay["conv_ln"], M, D, out_act=pl["xa"])
+            self._gemm(pl["xa"], lay["pw1"], M, out_f32=pl["pw"], ldo_f32=2 * D)
+            self._conv_mid(pl, lay)
+            self._gemm(pl["cv"], lay["pw2"], M, residual=pl["r2"], ldr=D, out_f32=pl["r3"], ldo_f32=D)
+            self._ffn_half(pl, lay, "ffn2", pl["r3"], pl["r4"])
+            self._layernorm(pl["r4"], D, lay["final_ln"], M, D, out_f32=states[i + 1])
+            if self._state_done(i + 1, last_state):
+                return
+
+    @_on_stream
+    def forward(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0,
+                last_state: Optional[int] = None) -> HiddenStates:
+        """packed 16 kHz samples [sum(lengths)] fp32 on the device -> L + 1 hidden states"""
+        pl = self._plan(lengths, slot)
+        return self._launch_or_replay(self._arenas[slot], pl, packed_wave, self._check_last_state(last_state))
+
+    @_on_stream
+    def fbank(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0) -> torch.Tensor:
+        """the stacked, normalised fbank rows [M, 160] alone (ser_fbank_v)"""
+        pl = self._plan(lengths, slot)
+        self._fbank(pl, packed_wave)
+        return pl["fb"][: int(pl["M"])]
+
+
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):
     """``normalize``: the speech families' input normalisation (``do_normalize`` of the checkpoint's feature extractor)."""
     if geo.family == "deberta":
@@ -3047,4 +3258,6 @@ def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16"
         return TextEncoder(geo, state_dict, device, mode)
     if geo.family == FAMILY_WHISPER:
         return WhisperEncoder(geo, state_dict, device, mode)
+    if geo.family == FAMILY_W2V_BERT:
+        return W2vBertEncoder(geo, state_dict, device, mode)
     return SpeechEncoder(geo, state_dict, device, mode, normalize=normalize)

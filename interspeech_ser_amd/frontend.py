@@ -211,6 +211,49 @@ def prosody_dft_table(n_bins: int) -> np.ndarray:
     return np.ascontiguousarray(np.stack([w[:, None] * np.cos(ang), -w[:, None] * np.sin(ang)], axis=-1))
 
 
+# ---- w2v-BERT 2.0's front end (HF SeamlessM4TFeatureExtractor; kernels: csrc/fbank.hip) ---------------------------------------------------
+W2VBERT_WIN, W2VBERT_HOP, W2VBERT_NFFT, W2VBERT_BINS = 400, 160, 512, 257
+W2VBERT_MIN_SAMPLES = 560                  # two frames: one stacked row (and an unbiased variance that exists)
+
+
+def w2vbert_mel_frames(num_samples: int) -> int:
+    """frames of 400 samples every 160, no centring"""
+    n = int(num_samples)
+    return 1 + (n - W2VBERT_WIN) // W2VBERT_HOP if n >= W2VBERT_WIN else 0
+
+
+def w2vbert_frames(num_samples: int, stride: int = 2) -> int:
+    """rows the encoder sees: whole groups of ``stride`` frames (HF's further, masked row of an odd frame count is not one)"""
+    return w2vbert_mel_frames(num_samples) // stride
+
+
+def w2vbert_mel_filters(n_mels: int = 80):
+    """(weights [n_mels, 257] float64, ranges [n_mels, 2] int32): Kaldi-scale triangular filters from 20 Hz to 8 kHz, triangular in mel
+    space (mel = 1127 ln(1 + f / 700)), no normalisation, over the 257 bins of a 512-point DFT at 16 kHz; a filter's non-zero bins are
+    ``ranges[m, 0] .. ranges[m, 1] - 1``."""
+    mel = lambda f: 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+    edges = np.linspace(mel(20.0), mel(8000.0), n_mels + 2)
+    bins = mel(np.arange(W2VBERT_BINS, dtype=np.float64) * (16000.0 / W2VBERT_NFFT))
+    down = (edges[None, 2:] - bins[:, None]) / (edges[2:] - edges[1:-1])[None, :]
+    up = (bins[:, None] - edges[None, :-2]) / (edges[1:-1] - edges[:-2])[None, :]
+    w = np.maximum(0.0, np.minimum(down, up)).T                                   # [n_mels, 257]
+    rng = np.zeros((n_mels, 2), dtype=np.int32)
+    for m in range(n_mels):
+        nz = np.nonzero(w[m])[0]
+        rng[m] = (nz[0], nz[-1] + 1) if nz.size else (0, 0)
+    return np.ascontiguousarray(w), rng
+
+
+def w2vbert_dft_table() -> np.ndarray:
+    """[400, 257, 2] float64 (w[j] cos, -w[j] sin)(2 pi k j / 512): the Povey window (a symmetric Hann window to the power 0.85) times the
+    twiddles of a 512-point DFT whose input is the 400-sample frame followed by zeros."""
+    j = np.arange(W2VBERT_WIN, dtype=np.int64)
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * j.astype(np.float64) / (W2VBERT_WIN - 1))) ** 0.85
+    r = (j[:, None] * np.arange(W2VBERT_BINS, dtype=np.int64)[None, :]) % W2VBERT_NFFT        # exact argument reduction
+    ang = 2.0 * np.pi * r.astype(np.float64) / W2VBERT_NFFT
+    return np.ascontiguousarray(np.stack([w[:, None] * np.cos(ang), -w[:, None] * np.sin(ang)], axis=-1))
+
+
 def whisper_saved_rows(num_samples: int, feat_dim: int) -> int:
     """Rows the reference keeps: min(ceil(len/320), feats.shape[1]) where feats is already
     [1500, D], so the cap is the hidden size (preprocess_whisper.py:49-50,75-76)."""

@@ -21,7 +21,8 @@ import torch
 from . import config as C
 from .batchloop import close_logger, make_batches, prefetch, run_or_each, write_result_csv
 from ._lib import SelectRowsArgs, SerHipError, check, lib
-from .engine import FusionHead, ProsodyEncoder, RowSource, SpeakerProsodyEncoder, SpeechEncoder, TrimodalHead, WhisperEncoder, _TextEncoderBase, _stream
+from .engine import (FusionHead, ProsodyEncoder, RowSource, SpeakerProsodyEncoder, SpeechEncoder, TrimodalHead, W2vBertEncoder, WhisperEncoder,
+                     _TextEncoderBase, _stream)
 from .frontend import whisper_saved_rows
 from .prosody import NS3_PROSODY, NS3_PROSODY_SPEAKER
 
@@ -104,7 +105,7 @@ class FusionPredictor:
                 if not isinstance(s.enc, (ProsodyEncoder, SpeakerProsodyEncoder)):
                     raise ValueError(f"stream {i + 1}: a ProsodyStream needs the prosody encoder")
             elif isinstance(s, AudioStream):
-                if not isinstance(s.enc, (SpeechEncoder, WhisperEncoder)):
+                if not isinstance(s.enc, (SpeechEncoder, WhisperEncoder, W2vBertEncoder)):
                     raise ValueError(f"stream {i + 1}: an AudioStream needs a speech encoder or Whisper")
             elif isinstance(s, TextStream):
                 if not isinstance(s.enc, _TextEncoderBase):
@@ -270,7 +271,7 @@ def _stream_kinds(config: Dict, encoders: Sequence[str], checkpoints: Sequence[s
             from .prosody import resolve_codec_spec
             geo = resolve_codec_spec(checkpoints[i], synthetic)
         else:
-            geo = C.resolve_geometry(name, checkpoints[i])
+            geo = C.resolve_fbank(C.resolve_geometry(name, checkpoints[i]), name, checkpoints[i])
         if geo.hidden != want:
             raise ValueError(f"feat{i + 1}_dim = {want} in the config, but {name} has hidden size {geo.hidden}")
         geos.append(geo)

@@ -21,7 +21,7 @@ from typing import Dict
 import numpy as np
 import torch
 
-from .config import EncoderGeometry, FAMILY_DEBERTA, FAMILY_ROBERTA, FAMILY_WAVLM, FAMILY_WHISPER
+from .config import EncoderGeometry, FAMILY_DEBERTA, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_WAVLM, FAMILY_WHISPER
 
 StateDict = Dict[str, torch.Tensor]
 
@@ -149,6 +149,32 @@ def synthetic_state_dict(geo: EncoderGeometry, seed: int = 0, fast: bool = False
         _layer_norm(sd, r, "encoder.layer_norm", D)
         return sd
 
+    if geo.family == FAMILY_W2V_BERT:      # HF Wav2Vec2BertModel names; a branch of its own, the other families' streams stay as they were
+        K, P = geo.conv_depthwise_kernel, geo.distance_positions
+        _layer_norm(sd, r, "feature_projection.layer_norm", geo.fbank_dim)
+        _linear(sd, r, "feature_projection.projection", D, geo.fbank_dim)
+        for i in range(geo.num_layers):
+            p = f"encoder.layers.{i}"
+            for f in ("ffn1", "ffn2"):
+                _layer_norm(sd, r, f"{p}.{f}_layer_norm", D)
+                _linear(sd, r, f"{p}.{f}.intermediate_dense", Fd, D)
+                _linear(sd, r, f"{p}.{f}.output_dense", D, Fd)
+            _layer_norm(sd, r, p + ".self_attn_layer_norm", D)
+            _linear(sd, r, p + ".self_attn.linear_q", D, D, gain=1.6)
+            _linear(sd, r, p + ".self_attn.linear_k", D, D, gain=1.6)
+            _linear(sd, r, p + ".self_attn.linear_v", D, D)
+            _linear(sd, r, p + ".self_attn.linear_out", D, D)
+            # q rows have |q| ~ 1.6 sqrt(dh) / ... ; N(0, 0.3) entries make the bias a logit term of the size of q . k's spread
+            sd[p + ".self_attn.distance_embedding.weight"] = r.normal(P, dh, std=0.3)
+            c = p + ".conv_module"
+            _layer_norm(sd, r, c + ".layer_norm", D)
+            sd[c + ".pointwise_conv1.weight"] = r.normal(2 * D, D, 1, std=1.0 / math.sqrt(D))
+            sd[c + ".depthwise_conv.weight"] = r.normal(D, 1, K, std=1.0 / math.sqrt(K))
+            _layer_norm(sd, r, c + ".depthwise_layer_norm", D)
+            sd[c + ".pointwise_conv2.weight"] = r.normal(D, D, 1, std=0.7 / math.sqrt(D))
+            _layer_norm(sd, r, p + ".final_layer_norm", D)
+        return sd
+
     cin = 1
     for i, (c, k) in enumerate(zip(geo.conv_dim, geo.conv_kernel)):
         p = f"feature_extractor.conv_layers.{i}"
@@ -249,7 +275,7 @@ def apply_stress(sd: StateDict, geo: EncoderGeometry, kind: str) -> StateDict:
     return sd
 
 
-_STRIP_PREFIXES = ("wavlm.", "wav2vec2.", "hubert.", "data2vec_audio.", "model.", "roberta.", "deberta.")
+_STRIP_PREFIXES = ("wavlm.", "wav2vec2_bert.", "wav2vec2.", "hubert.", "data2vec_audio.", "model.", "roberta.", "deberta.")
 
 
 def normalize_names(sd: StateDict) -> StateDict:
@@ -341,6 +367,12 @@ def fold_wavlm_gate(w8: torch.Tensor, b8: torch.Tensor, gamma: torch.Tensor, bet
     wg = (gam * wab[None]).reshape(2 * heads, head_dim)
     t = (bet * wab[None]).sum(2) + torch.stack([b8[:4].sum(), b8[4:].sum()])[None]
     return wg, t
+
+
+def fold_w2v_bert_ffn(w: torch.Tensor, b: torch.Tensor):
+    """The conformer layer adds HALF of each feed-forward block to the residual stream (HF Wav2Vec2BertEncoderLayer: ``x * 0.5 + residual``).
+    The factor goes into the block's output Linear at load: 0.5 is a power of two, so every product and sum keeps its rounding."""
+    return w.detach().to(torch.float32) * 0.5, b.detach().to(torch.float32) * 0.5
 
 
 F16_MAX = 65504.0
