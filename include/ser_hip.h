@@ -537,6 +537,50 @@ typedef struct ser_mlp_head_args {
 } ser_mlp_head_args;
 int ser_mlp_head_v(const ser_mlp_head_args* args, void* stream);
 
+/* a29 (added under ABI 18: new entry points only)  The head the hub's audio-classification checkpoints share (HF
+ * WavLMForSequenceClassification.forward and its wav2vec2 / HuBERT / data2vec-audio / w2v-BERT twins, WhisperForAudioClassification):
+ *   x = sum_l softmax(layer_weights)[l] hs[l]  (use_weighted_layer_sum; else the last state)  ->  projector  ->  mean over the frames  ->  classifier.
+ * Projector and mean are linear, so the mean is taken first: the [M, D] weighted sum and the M-row projection are never formed.
+ * Neither launcher is a command-list op: they run after the recorded forward.  Both accumulate every sum in float64, in an order fixed by
+ * the utterance alone (its frame count and the widths, never what else is in the batch: no atomics), and round once to fp32 at each store.
+ *
+ * ser_layer_pool_v: per utterance b with rows r0 = frame_offs[b] .. frame_offs[b+1]-1 (T_b of them):
+ *   out[b, d] = (1 / T_b) sum_t sum_l w[l] s[l, r0 + t, d]
+ * s: n_states fp32 planes [rows, lds], state l at s + l * state_stride (floats); n_states = 1 with w = {1.0} and s at the last state is
+ * the form without the weighted sum.  w: float64 [n_states] on the device.  The frames are cut into chunks of SER_LAYER_POOL_FC counted
+ * from the utterance's first row; two launches: one block per (256-column slab, chunk, utterance) adds its terms frame by frame, within
+ * a frame in ascending state, into the float64 workspace work [B, ceil(max_frames / SER_LAYER_POOL_FC), D] (a chunk past the
+ * utterance's end leaves at once), then one thread per (utterance, column) adds the chunk partials in ascending chunk, divides by T_b and
+ * rounds.  s is read once, 16 bytes at a time.  frame_offs int32 [B + 1] on the device and the same numbers at frame_offs_host, which the
+ * launcher validates.  out fp32 [B, ldo], ldo >= D; columns beyond D are not written.
+ * Refused before the launch: -1 null pointer; -2 D % 4 != 0, n_states < 1, an empty utterance, offsets outside [0, rows] or descending,
+ * an utterance longer than max_frames, max_frames > rows, B > 65535, lds / state_stride not multiples of 4, s not 16-byte aligned, a
+ * workspace smaller than B * ceil(max_frames / SER_LAYER_POOL_FC) * D doubles. */
+#define SER_LAYER_POOL_FC 32
+typedef struct ser_layer_pool_args {
+    const float* s; int64_t state_stride; int64_t lds;
+    const double* w;
+    const int32_t* frame_offs;
+    const int32_t* frame_offs_host;
+    double* work; int64_t work_elems;
+    float* out; int64_t ldo;
+    int32_t n_states, B, D, rows, max_frames, reserved0;
+} ser_layer_pool_args;
+int ser_layer_pool_v(const ser_layer_pool_args* args, void* stream);
+
+/* ser_cls_tail_v: out[b] = C (P pooled[b] + bp) + bc on B rows: Linear(D, proj) then Linear(proj, n_labels), nothing between them (HF's
+ * projector and classifier).  pooled [B, ldp], P [proj, D], bp [proj], C [n_labels, proj], bc [n_labels], out [B, ldo], all fp32.  One
+ * block per row: a wave per projector unit (products added per lane in ascending column, then the butterfly; the unit is kept in
+ * float64, not rounded), then a wave per label.  D % 4 == 0, 1 <= proj <= 2048, 1 <= n_labels <= 2048 (n_labels = 1: regression),
+ * pooled and P 16-byte aligned, ldp a multiple of 4, ldo >= n_labels, B <= 65535. */
+typedef struct ser_cls_tail_args {
+    const float* pooled; int64_t ldp;
+    const float* P; const float* bp; const float* C; const float* bc;
+    float* out; int64_t ldo;
+    int32_t B, D, proj, n_labels;
+} ser_cls_tail_args;
+int ser_cls_tail_v(const ser_cls_tail_args* args, void* stream);
+
 /* a23 (added under ABI 18: new entry points only)  The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334,
  * MultiModalEmotionClassifier) on packed ragged batches: every utterance alone, as the reference's evaluation runs it (batch_size = 1,
  * bin/eval_cat_bimodal_lazy_1head.py:292) -- no pad frame enters the recurrence, the attention or a pooling softmax.  None of the four is a

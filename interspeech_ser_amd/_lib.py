@@ -180,6 +180,25 @@ class MlpHeadArgs(C.Structure):
     ]
 
 
+class LayerPoolArgs(C.Structure):
+    """Mirror of ``ser_layer_pool_args``."""
+    _fields_ = [
+        ("s", c_void_p), ("state_stride", c_i64), ("lds", c_i64), ("w", c_void_p),
+        ("frame_offs", c_void_p), ("frame_offs_host", c_void_p),
+        ("work", c_void_p), ("work_elems", c_i64), ("out", c_void_p), ("ldo", c_i64),
+        ("n_states", C.c_int32), ("B", C.c_int32), ("D", C.c_int32), ("rows", C.c_int32), ("max_frames", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class ClsTailArgs(C.Structure):
+    """Mirror of ``ser_cls_tail_args``."""
+    _fields_ = [
+        ("pooled", c_void_p), ("ldp", c_i64), ("P", c_void_p), ("bp", c_void_p), ("C", c_void_p), ("bc", c_void_p),
+        ("out", c_void_p), ("ldo", c_i64),
+        ("B", C.c_int32), ("D", C.c_int32), ("proj", C.c_int32), ("n_labels", C.c_int32),
+    ]
+
+
 class GruArgs(C.Structure):
     """Mirror of ``ser_gru_args``."""
     _fields_ = [
@@ -372,6 +391,8 @@ class SwishRowsArgs(C.Structure):
     ]
 
 
+LAYER_POOL_FC = 32              # SER_LAYER_POOL_FC: frames per chunk of ser_layer_pool_v
+CLS_TAIL_MAX = 2048             # widest projector / most labels of ser_cls_tail_v
 CCONV_TILE = 8                  # SER_CCONV_TILE: rows per block of ser_conformer_conv_v
 CODEC_TILE = 128                # SER_CODEC_TILE: output rows per block of ser_codec_unit_v
 FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
@@ -408,7 +429,8 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_act_rows_args": ActRowsArgs, "ser_codec_unit_args": CodecUnitArgs, "ser_codec_conv_args": CodecConvArgs,
                   "ser_snake_args": SnakeArgs, "ser_fbank_args": FbankArgs, "ser_relkey_table_args": RelkeyTableArgs,
                   "ser_attention_rk_args": AttentionRkArgs, "ser_conformer_conv_args": ConformerConvArgs,
-                  "ser_swish_rows_args": SwishRowsArgs, "ser_cmd": Cmd}
+                  "ser_swish_rows_args": SwishRowsArgs, "ser_layer_pool_args": LayerPoolArgs, "ser_cls_tail_args": ClsTailArgs,
+                  "ser_cmd": Cmd}
 
 _SIGNATURES = {
     "ser_version": (c_int, []),
@@ -431,6 +453,8 @@ _SIGNATURES = {
     "ser_resample_v": (c_int, [c_void_p, c_void_p]),
     "ser_asp_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_mlp_head_v": (c_int, [c_void_p, c_void_p]),
+    "ser_layer_pool_v": (c_int, [c_void_p, c_void_p]),
+    "ser_cls_tail_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),

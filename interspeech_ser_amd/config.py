@@ -587,3 +587,62 @@ class GenerationSpec:
         except (OSError, ValueError) as e:
             raise OSError(f"cannot read {path}: {e}")
         return GenerationSpec.from_config(cfg, language)
+
+
+# The six hub classes that share one head (HF *ForSequenceClassification of the speech families, WhisperForAudioClassification):
+# optional softmax-weighted sum of the hidden states -> projector -> mean over the frames -> classifier (engine.ClassifierHead).
+AUDIO_CLASSIFICATION_ARCHITECTURES = (
+    "Wav2Vec2ForSequenceClassification", "WavLMForSequenceClassification", "HubertForSequenceClassification",
+    "Data2VecAudioForSequenceClassification", "Wav2Vec2BertForSequenceClassification", "WhisperForAudioClassification")
+
+
+@dataclass(frozen=True)
+class ClassifierSpec:
+    """What ``AutoModelForAudioClassification`` reads from ``config.json`` for that head.  ``labels``: ``id2label`` in index order
+    (``LABEL_i`` where the config has none, as ``PretrainedConfig`` names them)."""
+    use_weighted_layer_sum: bool
+    classifier_proj_size: int
+    num_labels: int
+    labels: Tuple[str, ...]
+    architecture: str = ""
+
+    @staticmethod
+    def from_config(cfg: dict, name: str = "") -> Optional["ClassifierSpec"]:
+        """The spec of a snapshot whose ``architectures[0]`` is one of the six classes, else None (such a snapshot runs as a bare
+        encoder, as before)."""
+        arch = cfg.get("architectures") or []
+        arch = arch[0] if isinstance(arch, (list, tuple)) and arch else (arch if isinstance(arch, str) else "")
+        if arch not in AUDIO_CLASSIFICATION_ARCHITECTURES:
+            return None
+        name = name or str(cfg.get("_name_or_path", "")) or arch
+        if cfg.get("add_adapter", False):
+            # HF: "Sequence classification does not support the use of <model> adapters (config.add_adapter=True)"
+            raise OSError(f"{name}: {arch} does not support adapters (add_adapter=True)")
+        id2label = cfg.get("id2label")
+        if id2label:
+            by_index = {int(k): str(v) for k, v in id2label.items()}
+            n = len(by_index)
+            if sorted(by_index) != list(range(n)):
+                raise OSError(f"{name}: id2label does not number its labels 0..{n - 1}")
+            labels = tuple(by_index[i] for i in range(n))
+        else:
+            n = int(cfg.get("num_labels", 2))
+            labels = tuple(f"LABEL_{i}" for i in range(n))
+        if n < 1:
+            raise OSError(f"{name}: no labels")
+        return ClassifierSpec(use_weighted_layer_sum=bool(cfg.get("use_weighted_layer_sum", False)),
+                              classifier_proj_size=int(cfg.get("classifier_proj_size", 256)), num_labels=n, labels=labels, architecture=arch)
+
+
+def resolve_classifier(ssl_type: str, checkpoint: str = "") -> Optional[ClassifierSpec]:
+    """``ClassifierSpec`` of the ``config.json`` that ``find_config_json`` picks; None when there is no such file or it names another class."""
+    import json
+    path = find_config_json(ssl_type, checkpoint)
+    if not path:
+        return None
+    try:
+        with open(path, "r") as f:
+            cfg = json.load(f)
+    except (OSError, ValueError) as e:
+        raise OSError(f"cannot read {path}: {e}")
+    return ClassifierSpec.from_config(cfg, name=ssl_type)

@@ -4,6 +4,9 @@
 //   ser_mlp_head_v    its 2D -> H -> n_out head (benchmark/net/ser.py EmotionRegression)
 //   ser_attn_pool_v   fusion heads (bin/train_cat_bimodal_lazy_1head.py MultiModalEmotionClassifier): softmax attention pooling of (a + b)
 //   ser_fusion_cls_v  their LayerNorm -> Linear -> ReLU -> Linear on the pooled rows
+//   ser_layer_pool_v  hub audio-classification heads (HF *ForSequenceClassification / WhisperForAudioClassification): softmax-weighted
+//                     sum of the hidden states and the mean over an utterance's frames, in one pass over the states
+//   ser_cls_tail_v    their projector and classifier on the pooled rows
 // ser_hip.h states the arithmetic.  Every sum accumulates in float64 in an order that depends on the utterance alone (its frame count and
 // the widths), never on the batch; one rounding to fp32 at each store.  No atomics.
 #include "ser_common.h"
@@ -317,4 +320,138 @@ extern "C" int ser_fusion_cls_v(const ser_fusion_cls_args* a, void* stream) {
     hipLaunchKernelGGL(tail_out_kernel<false>, dim3((unsigned)a->B), dim3(256), 0, s, a->hidden, nullptr, nullptr, 0.f, a->W2, a->b2, a->out,
                        a->H1, a->n_out);
     return ser_check_launch("ser_fusion_cls");
+}
+
+// ------------------------------------------------------------------------------- layer-weighted frame mean
+// pooled[b, d] = (1 / T_b) sum_t sum_l w_l s[l, r0_b + t, d].  The utterance's frames are cut into chunks of SER_LAYER_POOL_FC counted from
+// its first row.  Block (256-column slab, chunk, utterance): wave g owns the chunk's frames g, g + 4, ... and lane q the columns
+// 4 q .. 4 q + 3 of the slab (one 1 KiB row segment per wave and load); a thread adds its terms frame by frame, within a frame in ascending
+// state, then the four waves are merged in ascending g and the chunk's partial goes to work[b, chunk, :] in float64.  Every element of s
+// is read once, 16 bytes at a time.  A chunk past the utterance's last frame leaves at once.
+__global__ __launch_bounds__(256) void layer_pool_chunk_kernel(const float* __restrict__ s, int64_t state_stride, int64_t lds,
+                                                               const double* __restrict__ w, const int32_t* __restrict__ frame_offs,
+                                                               double* __restrict__ work, int n_states, int D, int rows, int n_chunks) {
+    __shared__ double red[4][256];
+    const int b = blockIdx.z, chunk = blockIdx.y, tid = threadIdx.x;
+    int r0 = frame_offs[b], r1 = frame_offs[b + 1];
+    if (r0 < 0) r0 = 0;                                           // the launcher checked the host copy; never read outside [0, rows)
+    if (r1 > rows) r1 = rows;
+    const int t0 = chunk * SER_LAYER_POOL_FC;
+    if (t0 >= r1 - r0) return;                                    // block-uniform
+    const int t1 = min(t0 + SER_LAYER_POOL_FC, r1 - r0);
+    const int g = tid >> 6, q = tid & 63;
+    const int col = blockIdx.x * 256 + q * 4;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (col < D) {                                                // D % 4 == 0: a quad is inside or outside as a whole
+        for (int t = t0 + g; t < t1; t += 4) {
+            const float* row = s + (int64_t)(r0 + t) * lds + col;
+#pragma unroll 5
+            for (int l = 0; l < n_states; ++l) {
+                const f32x4 v = *(const f32x4*)(row + (int64_t)l * state_stride);
+                const double wl = w[l];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = fma(wl, (double)v[j], acc[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[g][q * 4 + j] = acc[j];
+    __syncthreads();
+    const int c = blockIdx.x * 256 + tid;                         // one thread per column of the slab
+    if (c < D) work[((int64_t)b * n_chunks + chunk) * D + c] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// One thread per (utterance, column): the chunk partials in ascending chunk, the division by the frame count, one rounding.
+__global__ __launch_bounds__(256) void layer_pool_finish_kernel(const double* __restrict__ work, const int32_t* __restrict__ frame_offs,
+                                                                float* __restrict__ out, int64_t ldo, int D, int rows, int n_chunks) {
+    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= D) return;
+    int r0 = frame_offs[b], r1 = frame_offs[b + 1];
+    if (r0 < 0) r0 = 0;
+    if (r1 > rows) r1 = rows;
+    const int T = r1 - r0;
+    if (T <= 0) { out[(int64_t)b * ldo + c] = 0.f; return; }
+    const int used = min((T + SER_LAYER_POOL_FC - 1) / SER_LAYER_POOL_FC, n_chunks);
+    const double* p = work + (int64_t)b * n_chunks * D + c;
+    double sum = 0.0;
+    for (int k = 0; k < used; ++k) sum += p[(int64_t)k * D];
+    out[(int64_t)b * ldo + c] = (float)(sum / (double)T);
+}
+
+extern "C" int ser_layer_pool_v(const ser_layer_pool_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_layer_pool: null pointer");
+    if (!a->s || !a->w || !a->frame_offs || !a->frame_offs_host || !a->work || !a->out) return ser_fail(-1, "ser_layer_pool: null pointer");
+    if (a->n_states < 1) return ser_fail(-2, "ser_layer_pool: n_states=%d (at least 1)", a->n_states);
+    if (a->B <= 0 || a->B > 65535 || a->D <= 0 || (a->D % 4) || a->rows <= 0 || a->max_frames <= 0 || a->max_frames > a->rows)
+        return ser_fail(-2, "ser_layer_pool: bad B=%d (1..65535) D=%d (D %% 4 == 0) rows=%d max_frames=%d (<= rows)", a->B, a->D, a->rows,
+                        a->max_frames);
+    const int64_t n_chunks = ((int64_t)a->max_frames + SER_LAYER_POOL_FC - 1) / SER_LAYER_POOL_FC;
+    if (n_chunks > 65535) return ser_fail(-2, "ser_layer_pool: max_frames=%d is beyond %d chunks of %d frames", a->max_frames, 65535, SER_LAYER_POOL_FC);
+    if (a->lds < a->D || (a->lds % 4) || (a->state_stride % 4) || a->ldo < a->D || (a->n_states > 1 && a->state_stride <= 0))
+        return ser_fail(-2, "ser_layer_pool: bad pitches lds=%lld (>= D, multiple of 4) state_stride=%lld (multiple of 4) ldo=%lld (>= D)",
+                        (long long)a->lds, (long long)a->state_stride, (long long)a->ldo);
+    if ((((uintptr_t)a->s) & 15) != 0 || (((uintptr_t)a->w | (uintptr_t)a->work) & 7) != 0)
+        return ser_fail(-2, "ser_layer_pool: s must be 16-byte aligned, w and work 8-byte aligned");
+    if (a->work_elems < (int64_t)a->B * n_chunks * a->D)
+        return ser_fail(-2, "ser_layer_pool: work holds %lld doubles, B * ceil(max_frames / %d) * D = %lld are needed", (long long)a->work_elems,
+                        SER_LAYER_POOL_FC, (long long)((int64_t)a->B * n_chunks * a->D));
+    for (int b = 0; b < a->B; ++b) {                              // the host copy of the offsets: what the grid and the reads rely on
+        const int64_t r0 = a->frame_offs_host[b], r1 = a->frame_offs_host[b + 1];
+        if (r0 < 0 || r1 > a->rows || r1 < r0) return ser_fail(-2, "ser_layer_pool: utterance %d owns rows %lld..%lld outside [0, %d]", b, (long long)r0, (long long)r1, a->rows);
+        if (r1 == r0) return ser_fail(-2, "ser_layer_pool: utterance %d is empty (no frame to average)", b);
+        if (r1 - r0 > a->max_frames) return ser_fail(-2, "ser_layer_pool: utterance %d has %lld frames, max_frames=%d", b, (long long)(r1 - r0), a->max_frames);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned slabs = (unsigned)((a->D + 255) / 256);
+    hipLaunchKernelGGL(layer_pool_chunk_kernel, dim3(slabs, (unsigned)n_chunks, (unsigned)a->B), dim3(256), 0, st, a->s, a->state_stride, a->lds, a->w,
+                       a->frame_offs, a->work, a->n_states, a->D, a->rows, (int)n_chunks);
+    hipLaunchKernelGGL(layer_pool_finish_kernel, dim3(slabs, (unsigned)a->B), dim3(256), 0, st, a->work, a->frame_offs, a->out, a->ldo, a->D, a->rows,
+                       (int)n_chunks);
+    return ser_check_launch("ser_layer_pool");
+}
+
+// ------------------------------------------------------------------------------- projector and classifier on the pooled rows
+// One block of 1024 threads per utterance.  Hidden unit j (wave v owns j = v, v + 16, ...): lane l adds pooled[b, c] P[j, c] over its
+// columns 4 l + 256 i in ascending i (16-byte loads), then the butterfly, + bp[j]; the unit stays in LDS in float64.  Label n (same wave
+// rule): lane l adds hid[k] C[n, k] over k = l, l + 64, ... ascending, the butterfly, + bc[n], one rounding at the store.
+#define CLS_TAIL_MAX 2048
+__global__ __launch_bounds__(1024) void cls_tail_kernel(const float* __restrict__ pooled, int64_t ldp, const float* __restrict__ P,
+                                                        const float* __restrict__ bp, const float* __restrict__ Cw, const float* __restrict__ bc,
+                                                        float* __restrict__ out, int64_t ldo, int D, int proj, int n_labels) {
+    __shared__ double hid[CLS_TAIL_MAX];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* x = pooled + (int64_t)b * ldp;
+    for (int j = wave; j < proj; j += 16) {
+        const float* pr = P + (int64_t)j * D;
+        double acc = 0.0;
+        for (int c = lane * 4; c < D; c += 256) {
+            const f32x4 v = *(const f32x4*)(x + c), u = *(const f32x4*)(pr + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = fma((double)v[e], (double)u[e], acc);
+        }
+        acc = wave_sum_f64(acc);
+        if (lane == 0) hid[j] = acc + (double)bp[j];
+    }
+    __syncthreads();
+    for (int n = wave; n < n_labels; n += 16) {
+        const float* cr = Cw + (int64_t)n * proj;
+        double acc = 0.0;
+        for (int k = lane; k < proj; k += 64) acc = fma(hid[k], (double)cr[k], acc);
+        acc = wave_sum_f64(acc);
+        if (lane == 0) out[(int64_t)b * ldo + n] = (float)(acc + (double)bc[n]);
+    }
+}
+
+extern "C" int ser_cls_tail_v(const ser_cls_tail_args* a, void* stream) {
+    if (!a) return ser_fail(-1, "ser_cls_tail: null pointer");
+    if (!a->pooled || !a->P || !a->bp || !a->C || !a->bc || !a->out) return ser_fail(-1, "ser_cls_tail: null pointer");
+    if (a->proj < 1 || a->proj > CLS_TAIL_MAX || a->n_labels < 1 || a->n_labels > CLS_TAIL_MAX)
+        return ser_fail(-2, "ser_cls_tail: proj=%d n_labels=%d (1..%d each)", a->proj, a->n_labels, CLS_TAIL_MAX);
+    if (a->B <= 0 || a->B > 65535 || a->D <= 0 || (a->D % 4) || a->ldp < a->D || (a->ldp % 4) || a->ldo < a->n_labels)
+        return ser_fail(-2, "ser_cls_tail: bad B=%d D=%d (D %% 4 == 0) ldp=%lld (>= D, multiple of 4) ldo=%lld (>= n_labels)", a->B, a->D,
+                        (long long)a->ldp, (long long)a->ldo);
+    if ((((uintptr_t)a->pooled | (uintptr_t)a->P) & 15) != 0) return ser_fail(-2, "ser_cls_tail: pooled and P must be 16-byte aligned");
+    hipLaunchKernelGGL(cls_tail_kernel, dim3((unsigned)a->B), dim3(1024), 0, (hipStream_t)stream, a->pooled, a->ldp, a->P, a->bp, a->C, a->bc, a->out,
+                       a->ldo, a->D, a->proj, a->n_labels);
+    return ser_check_launch("ser_cls_tail");
 }

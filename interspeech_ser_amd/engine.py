@@ -1916,6 +1916,85 @@ class PoolHead(_HeadBase):
         return bf["out"][:B]
 
 
+class ClassifierHead(_HeadBase):
+    """The head of the hub's audio-classification checkpoints on the device (HF WavLMForSequenceClassification.forward and its five twins):
+    ``hidden_states`` -> softmax(layer_weights)-weighted sum (``use_weighted_layer_sum``; else the last state) -> projector -> mean over
+    the utterance's frames -> classifier -> ``[B, num_labels]`` logits.  Projector and mean commute, so ``forward`` enqueues two steps on
+    the current stream behind the encoder's recorded forward (no command-list op, the tapes stay as they are):
+      ser_layer_pool_v (one pass over the fp32 states: [B, D] weighted frame means) -> ser_cls_tail_v (projector and classifier per row).
+    Both read fp32 and sum in float64: no operand copies, so no range guard.  Behind Whisper the utterance's frames are the whole
+    1 500-row window, HF's unmasked mean.  ``head_sd``: the tensors of ``weights.split_classifier_head``; ``spec``: ``config.ClassifierSpec``."""
+
+    def __init__(self, enc: "_EncoderBase", head_sd, spec):
+        from .weights import check_classifier_head
+        if not isinstance(enc, (SpeechEncoder, W2vBertEncoder, WhisperEncoder)):
+            raise ValueError("ClassifierHead runs behind the speech, w2v-BERT and Whisper encoders")
+        geo = enc.geo
+        D, L1 = geo.hidden, geo.num_layers + 1
+        self.enc, self.D, self.device = enc, D, enc.device
+        self.proj, self.n_out, self.weighted = int(spec.classifier_proj_size), int(spec.num_labels), bool(spec.use_weighted_layer_sum)
+        if D % 4:
+            raise ValueError(f"ClassifierHead needs a hidden width that is a multiple of 4 (16-byte loads), got {D}")
+        if not 1 <= self.proj <= _lib.CLS_TAIL_MAX or not 1 <= self.n_out <= _lib.CLS_TAIL_MAX:
+            raise ValueError(f"classifier_proj_size {self.proj} / num_labels {self.n_out}: ser_cls_tail_v takes 1..{_lib.CLS_TAIL_MAX} each")
+        check_classifier_head(head_sd, D, self.proj, self.n_out, L1, self.weighted)
+        self.P, self.bp = enc._dev_f32(head_sd["projector.weight"]), enc._dev_f32(head_sd["projector.bias"])
+        self.C, self.bc = enc._dev_f32(head_sd["classifier.weight"]), enc._dev_f32(head_sd["classifier.bias"])
+        # softmax(layer_weights), once, in float64 from the fp32 parameter
+        w = torch.softmax(head_sd["layer_weights"].detach().to(torch.float32).double(), dim=-1) if self.weighted else torch.ones(1, dtype=torch.float64)
+        self.n_states = int(w.numel())
+        self.w = w.contiguous().to(self.device)
+        self._bufs: Dict[int, dict] = {}
+
+    def _buffers(self, slot: int, B: int, chunks: int) -> dict:
+        """grow-only buffers of one pipeline slot (slots run on streams of their own, so they share nothing)"""
+        need = B * chunks * self.D
+        bf = self._bufs.get(slot)
+        if bf is not None and bf["B"] >= B and bf["work"].numel() >= need:
+            return bf
+        B, need = max(B, bf["B"] if bf else 0), max(need, bf["work"].numel() if bf else 0)
+        dev = self.device
+        bf = dict(B=B, work=torch.empty(need, dtype=torch.float64, device=dev),
+                  pooled=torch.empty((B, self.D), dtype=torch.float32, device=dev),
+                  out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
+                  offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
+        self._bufs[slot] = bf
+        return bf
+
+    def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
+        """``[B, num_labels]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``);
+        ``hs.states`` is only read."""
+        if hs.computed < len(hs):
+            raise IndexError(f"the head needs {'every hidden state' if self.weighted else 'the last hidden state'} (run the forward without "
+                             f"last_state: states 0..{hs.computed - 1} of {len(hs)} were computed)")
+        s = hs.states
+        M, B, D = int(hs.frame_offs[-1]), hs.batch, self.D
+        if s.dim() != 3 or s.shape[0] != self.enc.geo.num_layers + 1 or s.shape[2] != D or s.stride(2) != 1 or s.shape[1] < M \
+                or s.dtype != torch.float32:
+            raise ValueError(f"hidden states {tuple(s.shape)} do not match the head ({self.enc.geo.num_layers + 1} states of width {D}, {M} rows)")
+        max_frames = max(hs.frames(b) for b in range(B))
+        chunks = -(-max_frames // _lib.LAYER_POOL_FC)
+        bf = self._buffers(slot, B, chunks)
+        st = _stream()
+        offs = hs.frame_offs_dev
+        if offs is None:
+            offs = bf["offs"][: B + 1]
+            offs.copy_(torch.tensor(hs.frame_offs, dtype=torch.int32))
+        offs_host = (C.c_int32 * (B + 1))(*hs.frame_offs)
+        first = s if self.weighted else s[-1:]
+        p = _lib.LayerPoolArgs()
+        p.s, p.state_stride, p.lds, p.w = first.data_ptr(), s.stride(0), s.stride(1), self.w.data_ptr()
+        p.frame_offs, p.frame_offs_host = offs.data_ptr(), C.cast(offs_host, C.c_void_p)
+        p.work, p.work_elems, p.out, p.ldo = bf["work"].data_ptr(), bf["work"].numel(), bf["pooled"].data_ptr(), D
+        p.n_states, p.B, p.D, p.rows, p.max_frames = self.n_states, B, D, M, max_frames
+        self._step("layer_pool", lambda: check(lib.ser_layer_pool_v(C.byref(p), st), "ser_layer_pool_v"))
+        t = _lib.ClsTailArgs()
+        t.pooled, t.ldp, t.P, t.bp, t.C, t.bc = bf["pooled"].data_ptr(), D, self.P.data_ptr(), self.bp.data_ptr(), self.C.data_ptr(), self.bc.data_ptr()
+        t.out, t.ldo, t.B, t.D, t.proj, t.n_labels = bf["out"].data_ptr(), self.n_out, B, D, self.proj, self.n_out
+        self._step("cls_tail", lambda: check(lib.ser_cls_tail_v(C.byref(t), st), "ser_cls_tail_v"))
+        return bf["out"][:B]
+
+
 def _fusion_keys(names) -> Dict[str, tuple]:
     """state-dict keys and symbolic shapes of the reference's fusion head over the modalities ``names`` (feature width of modality i: "d<i+1>")"""
     keys = {"classifier.0.weight": ("h1", "ne"), "classifier.0.bias": ("h1",), "classifier.3.weight": ("n", "h1"), "classifier.3.bias": ("n",),

@@ -295,6 +295,32 @@ def normalize_names(sd: StateDict) -> StateDict:
     return out
 
 
+CLASSIFIER_HEAD_KEYS = ("projector.weight", "projector.bias", "classifier.weight", "classifier.bias", "layer_weights")
+
+
+def split_classifier_head(sd: StateDict):
+    """(encoder tensors, head tensors) of a normalised state dict (``normalize_names`` / ``load_checkpoint``) of an audio-classification
+    checkpoint.  The head's are the five of ``CLASSIFIER_HEAD_KEYS`` that are present (``layer_weights`` exists only with
+    ``use_weighted_layer_sum``); every other tensor stays with the encoder, so a snapshot without a head comes back whole."""
+    enc = {k: v for k, v in sd.items() if k not in CLASSIFIER_HEAD_KEYS}
+    head = {k: sd[k] for k in CLASSIFIER_HEAD_KEYS if k in sd}
+    return enc, head
+
+
+def check_classifier_head(head_sd: StateDict, D: int, proj: int, num_labels: int, num_states: int, weighted: bool) -> None:
+    """Names and shapes of the head tensors against the encoder width, ``classifier_proj_size``, the label count and L + 1."""
+    want = {"projector.weight": (proj, D), "projector.bias": (proj,), "classifier.weight": (num_labels, proj),
+            "classifier.bias": (num_labels,)}
+    if weighted:
+        want["layer_weights"] = (num_states,)
+    for k, shape in want.items():
+        if k not in head_sd:
+            raise ValueError(f"{k} is missing from the checkpoint (an audio-classification head needs {', '.join(want)})")
+        if tuple(head_sd[k].shape) != shape:
+            raise ValueError(f"{k}: shape {tuple(head_sd[k].shape)}, expected {shape} (hidden width {D}, classifier_proj_size {proj}, "
+                             f"{num_labels} labels, {num_states} hidden states)")
+
+
 def merge_lora(sd: StateDict, lora_alpha: float = 16.0) -> StateDict:
     """Fold PEFT LoRA adapters into their base weights (next row 8f-4).  The reference fine-tunes WavLM with
     ``LoraConfig(r=8, lora_alpha=16, target_modules=['q_proj','v_proj'])`` inside a classifier wrapper and extracts
