@@ -17,6 +17,7 @@ exist, so no attention / conv masking is needed) and waste no FLOPs on padding.
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import ctypes as C
 import math
@@ -28,6 +29,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
+from .arena import SlotArenas
 from .weights import check_f16_weight
 from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_WAVLM, FAMILY_WHISPER
 
@@ -107,8 +109,10 @@ class Tape:
         self.cmds = (_lib.Cmd * capacity)()
         self.n = 0
         self.patches = []                    # (struct view inside cmds, field name, size name)
-        self.inputs: Dict[str, tuple] = {}   # named per-batch pointers, e.g. the uploaded waveform
+        self.inputs: List[tuple] = []        # (struct view inside cmds, field name) of every launch that reads the per-batch waveform
         self.marks: Dict[int, int] = {}      # hidden state index -> number of leading commands that produce states[0..index]
+        self.parts: List[tuple] = []         # (name, number of leading commands) where a recorder marks the end of a part (tools/codec_bench.py)
+        self.over: tuple = ()                # the dicts beyond its keeper's that the recorded pointers lie in (_LaunchHost._replay)
         self._failed = C.c_int32(-1)
 
     def slot(self, union_field: str):
@@ -135,10 +139,14 @@ class Tape:
         t.n = len(picked)
         return t
 
-    def run(self, sizes: Dict[str, int], stream: int, last_state: Optional[int] = None) -> None:
-        """Replay the list; with ``last_state`` only the leading commands that produce hidden states 0..last_state."""
+    def run(self, sizes: Dict[str, int], stream: int, last_state: Optional[int] = None, wave: Optional[int] = None) -> None:
+        """Replay the list with this batch's ``sizes`` and waveform (``wave``: its device address); with ``last_state`` only the leading
+        commands that produce hidden states 0..last_state."""
         for view, field, name in self.patches:
             setattr(view, field, sizes[name])
+        if wave is not None:
+            for view, field in self.inputs:
+                setattr(view, field, wave)
         n = self.n if last_state is None else self.marks.get(last_state, self.n)
         rc = lib.ser_run(self.cmds, n, C.byref(self._failed), stream)
         if rc != 0:
@@ -260,8 +268,11 @@ def _operand_mode(mode_name: str) -> int:
 
 
 class _LaunchHost:
-    """Weight and launch helpers (``_linear`` / ``_dev_f32`` / ``_gemm`` / ``_layernorm``): the base of every encoder, and used as it is by
-    the fusion heads -- one operand format for every GEMM, launches issued at once (nothing is recorded)."""
+    """Weight and launch helpers (``_linear`` / ``_dev_f32`` / ``_gemm`` / ``_layernorm``) and the one record-or-replay path (``_replay``):
+    the base of every encoder, and used as it is by the fusion heads -- one operand format for every GEMM, launches issued at once
+    (nothing is recorded)."""
+
+    use_tape = True          # replay recorded command lists (one foreign call per forward); False = launch one by one
 
     def __init__(self, device, mode_name: str, mode: int, stem_mode: int, fp16_planes: bool):
         if not torch.cuda.is_available():
@@ -274,6 +285,9 @@ class _LaunchHost:
         # when a list, every ser_gemm launch appends (start_event, end_event, algorithmic_flops):
         # bench.py uses it for the live roofline figure of the dominant kernel
         self.gemm_trace: Optional[list] = None
+        # when a list, every encoder layer appends (start_event, end_event, utterances) around its attention block
+        # (packed QKV projection -> attention -> output projection): bench.py's "attention_block" figure
+        self.block_trace: Optional[list] = None
         self._flag: Optional[int] = None    # device address of the range-guard word of the slot being launched / recorded
         self._st: Optional[int] = None      # launch stream of the forward in progress (looked up once per forward)
         self._rec: Optional[Tape] = None    # when set, _issue records the launch helpers' commands into it instead of launching them
@@ -349,16 +363,60 @@ class _LaunchHost:
         return view
 
     def _issue(self, op: int, view, what: str, input: Optional[str] = None, **sizes) -> None:
-        """Recording: commit the filled command (``Sz`` sizes become patches, ``input`` names it as a reader of the per-batch waveform
-        pointer); else launch it now, alone, through the dispatcher the list goes through."""
+        """Recording: commit the filled command (``Sz`` sizes become patches, ``input`` names the field of ``view`` that takes the
+        per-batch waveform pointer); else launch it now, alone, through the dispatcher the list goes through."""
         rec = self._rec
         if rec is not None:
             if input is not None:
-                rec.inputs[input] = view
+                rec.inputs.append((view, input))
             rec.commit(op, view, **sizes)
             return
         view.cmd.op = op
         check(lib.ser_run(C.byref(view.cmd), 1, None, self._s()), what)
+
+    # ------------------------------------------------------------------ record once, then patch and replay
+    @contextlib.contextmanager
+    def _launching(self, tape: Optional[Tape], hosts: Sequence["_LaunchHost"] = ()):
+        """Inside, this host and ``hosts`` (further hosts whose helpers the same forward calls) issue on this host's stream with its
+        guard word: into ``tape`` when one is given, else at once."""
+        hosts = (self,) + tuple(hosts)
+        saved = [(h._rec, h._st, h._flag) for h in hosts]
+        for h in hosts:
+            h._rec, h._st, h._flag = tape, self._st, self._flag
+        try:
+            yield
+        finally:
+            for h, old in zip(hosts, saved):
+                h._rec, h._st, h._flag = old
+
+    def _replay(self, owners: Sequence[dict], sizes: Dict[str, int], launch, wave: Optional[int] = None,
+                last_state: Optional[int] = None, hosts: Sequence["_LaunchHost"] = ()) -> None:
+        """One forward of ``launch(last_state)``.  Launched one by one when ``use_tape`` is off or a trace list is set; else the command
+        list kept in ``owners[0]["tape"]`` is replayed with this batch's ``sizes`` and waveform address, and ``launch(None)`` records it
+        first (launching nothing) when there is none yet.  ``owners``: the arena / plan dicts the launches' pointers lie in.  A list is
+        valid only over the very dicts it was recorded over: a grown arena is a new dict (arena.SlotArenas) and so has none, and one
+        that also points into another host's arena (``owners[1:]``) is recorded again when that arena was replaced."""
+        if not self.use_tape or self.gemm_trace is not None or self.block_trace is not None:
+            with self._launching(None, hosts):
+                launch(last_state)
+            return
+        tape, rest = owners[0].get("tape"), tuple(owners[1:])
+        if tape is None or len(tape.over) != len(rest) or any(a is not b for a, b in zip(tape.over, rest)):
+            tape = Tape()
+            with self._launching(tape, hosts):
+                launch(None)
+            tape.over = rest
+            owners[0]["tape"] = tape
+        tape.run(sizes, self._s(), last_state, wave=wave)
+
+    def recorded_tape(self, lengths: Sequence[int], slot: int) -> Tape:
+        """the command list the slot's last forward over ``lengths`` replayed (kept per arena; Whisper encoder and decoder: per plan)"""
+        pl = self._plan(lengths, slot)
+        arenas = getattr(self, "_arenas", None)
+        tape = (pl if arenas is None else arenas[slot]).get("tape")
+        if tape is None:
+            raise _lib.SerHipError("no recorded command list for this slot yet (run a forward first)")
+        return tape
 
     def _gemm(self, a: Act, lin: Linear, M: int, *, a_rowoff=None, lda=None, kc=0, ldj=0, groups=1,
               a_group_stride=0, w_group_stride=0, c_group_stride=0, N=None, K=None, act=_lib.ACT_NONE,
@@ -417,7 +475,7 @@ class _LaunchHost:
             if out_col % 64:
                 raise ValueError("an FP16M output must start on a 64-column tile")
             g.out_scale, g.out_scale_ld = out_act.scale.data_ptr() + 4 * (out_col // 64) * out_act.scale_ld, out_act.scale_ld
-        trace = self.gemm_trace                 # (never on while a list is recorded: _launch_or_replay)
+        trace = self.gemm_trace                 # (never on while a list is recorded: _replay)
         if trace is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -491,9 +549,6 @@ class _EncoderBase(_LaunchHost):
             self.qkv_m_from = None if v < 0 else v
         self.planes, self.stem_planes = _PLANES[self.mode], _PLANES[self.stem_mode]
         self._cache: Dict = {}
-        # when a list, every encoder layer appends (start_event, end_event, utterances) around its attention block
-        # (packed QKV projection -> attention -> output projection): bench.py's "attention_block" figure
-        self.block_trace: Optional[list] = None
 
     def _guard_word(self, pl) -> Optional[torch.Tensor]:
         """the slot's range-guard word (allocated with the plan); launch helpers pick its address up from ``self._flag``"""
@@ -708,35 +763,11 @@ class _EncoderBase(_LaunchHost):
         self._layernorm(pl["last"], D, self.enc_ln, M, D, out_f32=states[L])
 
     def _launch_or_replay(self, owner: dict, pl, packed_wave: torch.Tensor, last_state: Optional[int]) -> HiddenStates:
-        """One forward of ``self._launches``: launched one by one (``use_tape`` off, or a trace on), else the command list kept in
-        ``owner["tape"]`` (SpeechEncoder: the slot's arena; Whisper: the plan) replayed with this batch's sizes and waveform -- the
-        first forward over ``owner`` records it, launching nothing."""
+        """One forward of ``self._launches`` over ``owner`` (the slot's arena; Whisper: the plan), through ``_replay``"""
         flag = self._guard_word(pl)
-        if not self.use_tape or self.gemm_trace is not None or self.block_trace is not None:
-            self._launches(pl, packed_wave, last_state)      # one by one: a one-command ser_run per kernel
-        else:
-            tape = owner.get("tape")
-            if tape is None:
-                self._rec = tape = Tape()
-                try:
-                    self._launches(pl, packed_wave)
-                finally:
-                    self._rec = None
-                owner["tape"] = tape
-            for key in ("wav", "wav_gn"):                   # the launches that read the waveform
-                if key in tape.inputs:
-                    tape.inputs[key].wav = packed_wave.data_ptr()
-            tape.run(pl.get("sizes", {}), self._s(), last_state)
+        self._replay((owner,), pl.get("sizes", {}), lambda last: self._launches(pl, packed_wave, last), packed_wave.data_ptr(), last_state)
         return HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1, range_flag=flag,
                             frame_offs_dev=pl.get("frame_offs"))
-
-    def recorded_tape(self, lengths: Sequence[int], slot: int) -> Tape:
-        """the command list the slot's last forward over ``lengths`` replayed (SpeechEncoder: per arena; Whisper: per plan)"""
-        pl = self._plan(lengths, slot)
-        tape = pl.get("tape") or getattr(self, "_arenas", {}).get(slot, {}).get("tape")
-        if tape is None:
-            raise _lib.SerHipError("no recorded command list for this slot yet (run a forward first)")
-        return tape
 
     @_on_stream
     def attention_blocks_only(self, lengths: Sequence[int], slot: int) -> int:
@@ -923,7 +954,129 @@ def _fold_weight_norm(sd) -> torch.Tensor:
     return v * (g / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())
 
 
-class SpeechEncoder(_EncoderBase):
+class _WaveIO:
+    """Waveform I/O of the encoders that take raw samples: ``upload`` / ``upload_resampled`` (host -> packed device buffer) and ``download``.
+    A mixin in front of a ``_LaunchHost`` (it reads ``self.device``)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._pin_in: Dict[int, tuple] = {}                 # slot -> (pinned staging buffer, event behind its last copy)
+        self._rs_tab: Dict[int, tuple] = {}                 # slot -> (pinned blob, device blob, event) of ser_resample_v's O(B) tables
+        self._rs_banks = dict(buf=None, used=0, offs={}, retired=[])      # the polyphase banks met so far, one float64 device buffer
+
+    def upload(self, waves: Sequence[np.ndarray], slot: int = 0) -> torch.Tensor:
+        """Pack raw fp32 waveforms into slot ``slot``'s (reused, grow-only) pinned host buffer and copy H2D.
+        The copy is enqueued on the current stream; the staging buffer is reused only after an event
+        recorded behind its previous copy has completed."""
+        total = int(sum(len(w) for w in waves))
+        if total and all(isinstance(w, np.ndarray) and w.dtype == np.float32 and w.flags.c_contiguous for w in waves):
+            srcs = [torch.from_numpy(w) for w in waves]
+            if all(t.is_pinned() for t in srcs):
+                # every utterance already sits in page-locked memory (driver: frontend.load_wav_16k(pinned=True)): one async copy each,
+                # no packing pass here; torch's host allocator keeps a block from being re-issued until the copy from it has run
+                dev = torch.empty(total, dtype=torch.float32, device=self.device)
+                o = 0
+                for t in srcs:
+                    dev[o:o + t.numel()].copy_(t, non_blocking=True)
+                    o += t.numel()
+                return dev
+        pin, evt = self._pin_in.get(slot, (None, None))
+        if pin is None or pin.numel() < total:
+            pin, evt = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory(), None
+        elif evt is not None:
+            evt.synchronize()
+        host = pin[:total]
+        view = host.numpy()
+        o = 0
+        for w in waves:
+            n = len(w)
+            view[o:o + n] = w
+            o += n
+        dev = host.to(self.device, non_blocking=True)
+        evt = torch.cuda.Event()
+        evt.record()
+        self._pin_in[slot] = (pin, evt)
+        return dev
+
+    def _resample_bank(self, up: int, down: int):
+        """(element offset, half) of the (up, down) polyphase bank inside this encoder's float64 bank buffer on the device; a ratio met
+        for the first time is appended (one blocking copy per ratio and encoder).  Appending never moves what launches in flight read: a
+        buffer that runs out of room is succeeded by a larger one and kept alive beside it."""
+        from .frontend import polyphase_bank
+        rs = self._rs_banks
+        hit = rs["offs"].get((up, down))
+        if hit is not None:
+            return hit
+        h, half = polyphase_bank(up, down)
+        if rs["buf"] is None or rs["used"] + len(h) > rs["buf"].numel():
+            grown = torch.empty(max(1 << 16, 2 * (rs["used"] + len(h))), dtype=torch.float64, device=self.device)
+            if rs["buf"] is not None:
+                grown[: rs["used"]].copy_(rs["buf"][: rs["used"]])
+                rs["retired"].append(rs["buf"])
+            rs["buf"] = grown
+        off = rs["used"]
+        rs["buf"][off: off + len(h)].copy_(torch.from_numpy(h.copy()))      # the cached bank is read-only
+        torch.cuda.current_stream().synchronize()           # every slot's stream may read the bank from now on
+        rs["used"] = off + len(h)
+        rs["offs"][(up, down)] = (off, half)
+        return off, half
+
+    def upload_resampled(self, waves: Sequence[np.ndarray], rates: Sequence[int], slot: int = 0):
+        """``upload`` for utterances at their files' own sample rates: stages the raw samples like ``upload`` does, and enqueues ONE
+        ``ser_resample_v`` launch on the current stream that brings the ragged, mixed-rate batch to 16 kHz (Kaiser beta 14 polyphase
+        FIR, the ``--resample`` filter of frontend.load_wav_16k; parity with librosa's soxr_hq unpinned).  Returns (packed 16 kHz
+        device buffer, lengths) for ``forward``.  A batch that is all 16 kHz goes through plain ``upload``."""
+        from .frontend import TARGET_SR, resample_ratio
+        rates = [int(r) for r in rates]
+        if len(rates) != len(waves):
+            raise ValueError("one sample rate per utterance")
+        if all(r == TARGET_SR for r in rates):
+            return self.upload(waves, slot), [len(w) for w in waves]
+        B = len(waves)
+        ratios = [resample_ratio(r) for r in rates]
+        n_in = [len(w) for w in waves]
+        n_out = [(n * u + d - 1) // d for n, (u, d) in zip(n_in, ratios)]
+        banks = [(0, 0) if u == d == 1 else self._resample_bank(u, d) for u, d in ratios]
+        raw = self.upload(waves, slot)
+        # ---- O(B) tables -> this slot's pinned blob (int64 words: in_offs, out_offs, bank_off; then int32: up, down, half), one async copy
+        words = 3 * B + 2 + (3 * B + 1) // 2
+        host, dev, evt = self._rs_tab.get(slot, (None, None, None))
+        if host is None or host.numel() < words:
+            host = torch.empty(max(words, 256), dtype=torch.int64).pin_memory()
+            dev, evt = torch.empty(host.numel(), dtype=torch.int64, device=self.device), None
+        elif evt is not None:
+            evt.synchronize()                                 # the previous batch's copy out of the blob has finished
+        h64 = host.numpy()
+        h64[0: B + 1] = np.concatenate([[0], np.cumsum(n_in)])
+        h64[B + 1: 2 * B + 2] = np.concatenate([[0], np.cumsum(n_out)])
+        h64[2 * B + 2: 3 * B + 2] = [o for o, _ in banks]
+        h32 = h64[3 * B + 2:].view(np.int32)
+        h32[0: B] = [u for u, _ in ratios]
+        h32[B: 2 * B] = [d for _, d in ratios]
+        h32[2 * B: 3 * B] = [hf for _, hf in banks]
+        dev[:words].copy_(host[:words], non_blocking=True)
+        evt = torch.cuda.Event()
+        evt.record()
+        self._rs_tab[slot] = (host, dev, evt)
+        out = torch.empty(int(sum(n_out)), dtype=torch.float32, device=self.device)
+        a = _lib.ResampleArgs()
+        base, i32 = dev.data_ptr(), dev.data_ptr() + 8 * (3 * B + 2)
+        a.wav, a.in_offs, a.out_offs, a.bank_off = raw.data_ptr(), base, base + 8 * (B + 1), base + 8 * (2 * B + 2)
+        a.up, a.down, a.half = i32, i32 + 4 * B, i32 + 8 * B
+        a.bank, a.out = self._rs_banks["buf"].data_ptr(), out.data_ptr()
+        a.total_in, a.total_out, a.max_out, a.B = int(sum(n_in)), int(sum(n_out)), int(max(n_out)), B
+        check(lib.ser_resample_v(C.byref(a), _stream()), "ser_resample_v")
+        return out, n_out
+
+    def download(self, t: torch.Tensor) -> torch.Tensor:
+        """Device fp32 tensor -> fresh pinned host tensor (async D2H + one synchronisation)."""
+        host = torch.empty(t.shape, dtype=t.dtype).pin_memory()
+        host.copy_(t, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host
+
+
+class SpeechEncoder(_WaveIO, _EncoderBase):
     """WavLM / wav2vec2 / HuBERT on libserhip: the *-large / xlarge / XLS-R form (layer-norm conv stack, stable-LayerNorm encoder) and
     the *-base form (GroupNorm-over-time conv layer 0, post-LayerNorm encoder; ``geo.stable_layer_norm`` False).  data2vec-audio: the
     layer-norm conv stack with a post-LayerNorm encoder, and a stack of LayerNorm'd positional convs (``geo.pos_conv_norm == "layer"``).
@@ -1013,22 +1166,16 @@ class SpeechEncoder(_EncoderBase):
                 k_bias=True, gate=(geo.family == FAMILY_WAVLM), index=i))
         if geo.family == FAMILY_WAVLM:
             self.rel_embed = self._dev_f32(sd["encoder.layers.0.attention.rel_attn_embed.weight"])
+        self._arenas = SlotArenas(self._build_arena)          # per slot; ar["plan"]: (lengths, plan) currently laid out in it
 
-    # ------------------------------------------------------------------ batch plan
     # ------------------------------------------------------------------ per-slot arenas + plans
-    def _arena(self, slot: int, need: Dict[str, int]):
-        """Grow-only buffer set of one slot, sized by the largest batch seen so far: a stream of ragged batches
-        re-uses the same HBM instead of allocating ~25 tensors per batch.  ``need``: rows after conv 0 / conv 1,
-        frames M, halo'd rows, utterances B, longest utterance Tmax."""
-        arenas = self.__dict__.setdefault("_arenas", {})
-        ar = arenas.get(slot)
-        if ar is not None and all(ar["cap"][k] >= v for k, v in need.items()):
-            return ar
-        cap = {k: max(int(v), ar["cap"][k] if ar else 0) for k, v in need.items()}
+    def _build_arena(self, cap: Dict[str, int]) -> dict:
+        """Buffer set of one slot (arena.SlotArenas): a stream of ragged batches re-uses the same HBM instead of allocating ~25 tensors
+        per batch.  ``cap``: rows after conv 0 / conv 1, frames M, halo'd rows, utterances B, longest utterance Tmax."""
         geo, dev = self.geo, self.device
         C0, D = geo.conv_dim[0], geo.hidden
         nl = len(geo.conv_dim)
-        ar = dict(cap=cap)
+        ar = {}
         ar["frames"] = self._new_act(cap["rows0"], 64, stem=True)
         ar["wave_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_WAVE_FRAMES, cap["B"], 0, 0, 0, self.stem_mode),
                                       dtype=torch.uint8, device=dev)
@@ -1061,8 +1208,6 @@ class SpeechEncoder(_EncoderBase):
         ar["tab_host"] = torch.empty(words, dtype=torch.int64).pin_memory()
         ar["tab_dev"] = torch.empty(words, dtype=torch.int64, device=dev)
         ar["tab_evt"] = None
-        ar["plan"] = None                                   # (lengths, plan) currently laid out in this arena
-        arenas[slot] = ar
         return ar
 
     def _plan(self, lengths: Sequence[int], slot: int = 0):
@@ -1082,8 +1227,7 @@ class SpeechEncoder(_EncoderBase):
         M, Tmax = int(offs[-1][-1]), max(T)
         half = geo.pos_conv_kernel // 2
         halo_rows = int(M + half * (B + 1))
-        ar = self._arena(slot, dict(rows0=int(offs[0][-1]), rows1=int(offs[1][-1]) if nl > 1 else 1, M=M,
-                                    halo=halo_rows, B=B, Tmax=Tmax))
+        ar = self._arenas.fit(slot, rows0=int(offs[0][-1]), rows1=int(offs[1][-1]) if nl > 1 else 1, M=M, halo=halo_rows, B=B, Tmax=Tmax)
         if ar["plan"] is not None and ar["plan"][0] == lengths:
             return ar["plan"][1]
         st = _stream()
@@ -1153,121 +1297,6 @@ class SpeechEncoder(_EncoderBase):
         return pl
 
     # ------------------------------------------------------------------ forward
-    def upload(self, waves: Sequence[np.ndarray], slot: int = 0) -> torch.Tensor:
-        """Pack raw fp32 waveforms into slot ``slot``'s (reused, grow-only) pinned host buffer and copy H2D.
-        The copy is enqueued on the current stream; the staging buffer is reused only after an event
-        recorded behind its previous copy has completed."""
-        total = int(sum(len(w) for w in waves))
-        if total and all(isinstance(w, np.ndarray) and w.dtype == np.float32 and w.flags.c_contiguous for w in waves):
-            srcs = [torch.from_numpy(w) for w in waves]
-            if all(t.is_pinned() for t in srcs):
-                # every utterance already sits in page-locked memory (driver: frontend.load_wav_16k(pinned=True)): one async copy each,
-                # no packing pass here; torch's host allocator keeps a block from being re-issued until the copy from it has run
-                dev = torch.empty(total, dtype=torch.float32, device=self.device)
-                o = 0
-                for t in srcs:
-                    dev[o:o + t.numel()].copy_(t, non_blocking=True)
-                    o += t.numel()
-                return dev
-        pins = self.__dict__.setdefault("_pin_in", {})
-        pin, evt = pins.get(slot, (None, None))
-        if pin is None or pin.numel() < total:
-            pin, evt = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory(), None
-        elif evt is not None:
-            evt.synchronize()
-        host = pin[:total]
-        view = host.numpy()
-        o = 0
-        for w in waves:
-            n = len(w)
-            view[o:o + n] = w
-            o += n
-        dev = host.to(self.device, non_blocking=True)
-        evt = torch.cuda.Event()
-        evt.record()
-        pins[slot] = (pin, evt)
-        return dev
-
-    def _resample_bank(self, up: int, down: int):
-        """(element offset, half) of the (up, down) polyphase bank inside this encoder's float64 bank buffer on the device; a ratio met
-        for the first time is appended (one blocking copy per ratio and encoder).  Appending never moves what launches in flight read: a
-        buffer that runs out of room is succeeded by a larger one and kept alive beside it."""
-        from .frontend import polyphase_bank
-        rs = self.__dict__.setdefault("_rs_banks", dict(buf=None, used=0, offs={}, retired=[]))
-        hit = rs["offs"].get((up, down))
-        if hit is not None:
-            return hit
-        h, half = polyphase_bank(up, down)
-        if rs["buf"] is None or rs["used"] + len(h) > rs["buf"].numel():
-            grown = torch.empty(max(1 << 16, 2 * (rs["used"] + len(h))), dtype=torch.float64, device=self.device)
-            if rs["buf"] is not None:
-                grown[: rs["used"]].copy_(rs["buf"][: rs["used"]])
-                rs["retired"].append(rs["buf"])
-            rs["buf"] = grown
-        off = rs["used"]
-        rs["buf"][off: off + len(h)].copy_(torch.from_numpy(h.copy()))      # the cached bank is read-only
-        torch.cuda.current_stream().synchronize()           # every slot's stream may read the bank from now on
-        rs["used"] = off + len(h)
-        rs["offs"][(up, down)] = (off, half)
-        return off, half
-
-    def upload_resampled(self, waves: Sequence[np.ndarray], rates: Sequence[int], slot: int = 0):
-        """``upload`` for utterances at their files' own sample rates: stages the raw samples like ``upload`` does, and enqueues ONE
-        ``ser_resample_v`` launch on the current stream that brings the ragged, mixed-rate batch to 16 kHz (Kaiser beta 14 polyphase
-        FIR, the ``--resample`` filter of frontend.load_wav_16k; parity with librosa's soxr_hq unpinned).  Returns (packed 16 kHz
-        device buffer, lengths) for ``forward``.  A batch that is all 16 kHz goes through plain ``upload``."""
-        from .frontend import TARGET_SR, resample_ratio
-        rates = [int(r) for r in rates]
-        if len(rates) != len(waves):
-            raise ValueError("one sample rate per utterance")
-        if all(r == TARGET_SR for r in rates):
-            return self.upload(waves, slot), [len(w) for w in waves]
-        B = len(waves)
-        ratios = [resample_ratio(r) for r in rates]
-        n_in = [len(w) for w in waves]
-        n_out = [(n * u + d - 1) // d for n, (u, d) in zip(n_in, ratios)]
-        banks = [(0, 0) if u == d == 1 else self._resample_bank(u, d) for u, d in ratios]
-        raw = self.upload(waves, slot)
-        # ---- O(B) tables -> this slot's pinned blob (int64 words: in_offs, out_offs, bank_off; then int32: up, down, half), one async copy
-        words = 3 * B + 2 + (3 * B + 1) // 2
-        tabs = self.__dict__.setdefault("_rs_tab", {})
-        host, dev, evt = tabs.get(slot, (None, None, None))
-        if host is None or host.numel() < words:
-            host = torch.empty(max(words, 256), dtype=torch.int64).pin_memory()
-            dev, evt = torch.empty(host.numel(), dtype=torch.int64, device=self.device), None
-        elif evt is not None:
-            evt.synchronize()                                 # the previous batch's copy out of the blob has finished
-        h64 = host.numpy()
-        h64[0: B + 1] = np.concatenate([[0], np.cumsum(n_in)])
-        h64[B + 1: 2 * B + 2] = np.concatenate([[0], np.cumsum(n_out)])
-        h64[2 * B + 2: 3 * B + 2] = [o for o, _ in banks]
-        h32 = h64[3 * B + 2:].view(np.int32)
-        h32[0: B] = [u for u, _ in ratios]
-        h32[B: 2 * B] = [d for _, d in ratios]
-        h32[2 * B: 3 * B] = [hf for _, hf in banks]
-        dev[:words].copy_(host[:words], non_blocking=True)
-        evt = torch.cuda.Event()
-        evt.record()
-        tabs[slot] = (host, dev, evt)
-        out = torch.empty(int(sum(n_out)), dtype=torch.float32, device=self.device)
-        a = _lib.ResampleArgs()
-        base, i32 = dev.data_ptr(), dev.data_ptr() + 8 * (3 * B + 2)
-        a.wav, a.in_offs, a.out_offs, a.bank_off = raw.data_ptr(), base, base + 8 * (B + 1), base + 8 * (2 * B + 2)
-        a.up, a.down, a.half = i32, i32 + 4 * B, i32 + 8 * B
-        a.bank, a.out = self._rs_banks["buf"].data_ptr(), out.data_ptr()
-        a.total_in, a.total_out, a.max_out, a.B = int(sum(n_in)), int(sum(n_out)), int(max(n_out)), B
-        check(lib.ser_resample_v(C.byref(a), _stream()), "ser_resample_v")
-        return out, n_out
-
-    def download(self, t: torch.Tensor) -> torch.Tensor:
-        """Device fp32 tensor -> fresh pinned host tensor (async D2H + one synchronisation)."""
-        host = torch.empty(t.shape, dtype=t.dtype).pin_memory()
-        host.copy_(t, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return host
-
-    use_tape = True          # replay recorded command lists (one foreign call per forward); False = launch one by one
-
     @_on_stream
     def forward(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0,
                 last_state: Optional[int] = None) -> HiddenStates:
@@ -1388,7 +1417,7 @@ class SpeechEncoder(_EncoderBase):
         a.scale, a.shift, a.stat_out, a.work = pl["gn_scale"].data_ptr(), pl["gn_shift"].data_ptr(), None, pl["gn_work"].data_ptr()
         a.B, a.C, a.k, a.stride, a.ld = B, C0, geo.conv_kernel[0], geo.conv_stride[0], C0
         a.no_norm, a.eps = 0 if self.normalize else 1, 1e-5      # nn.GroupNorm's default eps (HF WavLMGroupNormConvLayer)
-        self._issue(_lib.OP_GN_STATS, a, "ser_gn_stats", input="wav_gn", B=B)
+        self._issue(_lib.OP_GN_STATS, a, "ser_gn_stats", input="wav", B=B)
         self._gemm(pl["frames"], self.conv0, pl["rows"][0], act=_lib.ACT_GELU, out_act=pl["conv_act"][0], k_algo=geo.conv_kernel[0],
                    stem=True, gn=(pl["gn_scale"], pl["gn_shift"], pl["frame_offs0"], B))
 
@@ -1415,7 +1444,7 @@ class SpeechEncoder(_EncoderBase):
                 return
 
 
-class WhisperEncoder(_EncoderBase):
+class WhisperEncoder(_WaveIO, _EncoderBase):
     """Whisper encoder (log-mel front end + stem convs + pre-LN layers) on libserhip."""
 
     N_SAMPLES = 480000
@@ -1497,11 +1526,6 @@ class WhisperEncoder(_EncoderBase):
         self._cache[key_full] = pl
         return pl
 
-    upload = SpeechEncoder.upload
-    _resample_bank = SpeechEncoder._resample_bank
-    upload_resampled = SpeechEncoder.upload_resampled
-    download = SpeechEncoder.download
-
     def _logmel(self, pl, packed_wave: torch.Tensor) -> None:
         a = self._cmd("logmel")
         a.wav, a.sample_offs, a.mel = packed_wave.data_ptr(), pl["sample_offs"].data_ptr(), self.mel.data_ptr()
@@ -1514,8 +1538,6 @@ class WhisperEncoder(_EncoderBase):
         pl = self._plan(lengths, slot)
         self._logmel(pl, packed_wave)
         return pl["mel"]
-
-    use_tape = True          # replay a recorded command list (one foreign call per forward), like SpeechEncoder
 
     @_on_stream
     def forward(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0,
@@ -1863,25 +1885,18 @@ class PoolHead(_HeadBase):
         self.ln_g, self.ln_b = enc._dev_f32(ser_sd["fc.0.1.weight"]), enc._dev_f32(ser_sd["fc.0.1.bias"])
         self.w2, self.b2 = enc._dev_f32(w2), enc._dev_f32(ser_sd["out.0.bias"])
         self.ln_eps = 1e-5                                        # nn.LayerNorm's default (ser.py builds it without an eps)
-        self._bufs: Dict[int, dict] = {}
+        self._bufs = SlotArenas(self._build_buffers)
 
-    def _buffers(self, slot: int, M: int, B: int) -> dict:
-        """grow-only buffers of one pipeline slot (slots run on streams of their own, so they share nothing)"""
-        bf = self._bufs.get(slot)
-        if bf is not None and bf["M"] >= M and bf["B"] >= B:
-            return bf
-        M, B = max(M, bf["M"] if bf else 0), max(B, bf["B"] if bf else 0)
-        D, dev = self.D, self.device
-        bf = dict(M=M, B=B,
-                  xa=Act(M, D, _PLANES[self.op_mode], dev, dtype=_DTYPE[self.op_mode]),
-                  hlin=torch.empty((M, D), dtype=torch.float32, device=dev),
-                  scores=torch.empty(M, dtype=torch.float32, device=dev),
-                  pooled=torch.empty((B, 2 * D), dtype=torch.float32, device=dev),
-                  hidden=torch.empty((B, self.H), dtype=torch.float32, device=dev),
-                  out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
-                  offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
-        self._bufs[slot] = bf
-        return bf
+    def _build_buffers(self, cap: Dict[str, int]) -> dict:
+        """buffers of one pipeline slot (slots run on streams of their own, so they share nothing)"""
+        M, B, D, dev = cap["M"], cap["B"], self.D, self.device
+        return dict(xa=Act(M, D, _PLANES[self.op_mode], dev, dtype=_DTYPE[self.op_mode]),
+                    hlin=torch.empty((M, D), dtype=torch.float32, device=dev),
+                    scores=torch.empty(M, dtype=torch.float32, device=dev),
+                    pooled=torch.empty((B, 2 * D), dtype=torch.float32, device=dev),
+                    hidden=torch.empty((B, self.H), dtype=torch.float32, device=dev),
+                    out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
+                    offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
 
     def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
         """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``).  The range
@@ -1892,7 +1907,7 @@ class PoolHead(_HeadBase):
         M, B, D = int(hs.frame_offs[-1]), hs.batch, self.D
         if x.shape[0] != M or x.shape[1] != D or x.stride(0) != D:
             raise ValueError("hidden states do not match the head's width")
-        bf = self._buffers(slot, M, B)
+        bf = self._bufs.fit(slot, M=M, B=B)
         st = _stream()
         offs = hs.frame_offs_dev
         if offs is None:
@@ -1944,22 +1959,15 @@ class ClassifierHead(_HeadBase):
         w = torch.softmax(head_sd["layer_weights"].detach().to(torch.float32).double(), dim=-1) if self.weighted else torch.ones(1, dtype=torch.float64)
         self.n_states = int(w.numel())
         self.w = w.contiguous().to(self.device)
-        self._bufs: Dict[int, dict] = {}
+        self._bufs = SlotArenas(self._build_buffers)
 
-    def _buffers(self, slot: int, B: int, chunks: int) -> dict:
-        """grow-only buffers of one pipeline slot (slots run on streams of their own, so they share nothing)"""
-        need = B * chunks * self.D
-        bf = self._bufs.get(slot)
-        if bf is not None and bf["B"] >= B and bf["work"].numel() >= need:
-            return bf
-        B, need = max(B, bf["B"] if bf else 0), max(need, bf["work"].numel() if bf else 0)
-        dev = self.device
-        bf = dict(B=B, work=torch.empty(need, dtype=torch.float64, device=dev),
-                  pooled=torch.empty((B, self.D), dtype=torch.float32, device=dev),
-                  out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
-                  offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
-        self._bufs[slot] = bf
-        return bf
+    def _build_buffers(self, cap: Dict[str, int]) -> dict:
+        """buffers of one pipeline slot (slots run on streams of their own, so they share nothing); ``work``: float64 words of ser_layer_pool_v"""
+        B, dev = cap["B"], self.device
+        return dict(work=torch.empty(cap["work"], dtype=torch.float64, device=dev),
+                    pooled=torch.empty((B, self.D), dtype=torch.float32, device=dev),
+                    out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
+                    offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
 
     def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
         """``[B, num_labels]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``);
@@ -1974,7 +1982,7 @@ class ClassifierHead(_HeadBase):
             raise ValueError(f"hidden states {tuple(s.shape)} do not match the head ({self.enc.geo.num_layers + 1} states of width {D}, {M} rows)")
         max_frames = max(hs.frames(b) for b in range(B))
         chunks = -(-max_frames // _lib.LAYER_POOL_FC)
-        bf = self._buffers(slot, B, chunks)
+        bf = self._bufs.fit(slot, B=B, work=B * chunks * self.D)
         st = _stream()
         offs = hs.frame_offs_dev
         if offs is None:
@@ -2125,16 +2133,12 @@ class _FusionBase(_HeadBase):
             raise ValueError(f"cluster={cluster} does not divide H / 16 = {h // 16}")
         self.R = r.value
         self._epoch = 1
-        self._bufs: Dict[int, dict] = {}
+        self._bufs = SlotArenas(self._build_buffers)
 
-    def _buffers(self, slot: int, Ms: Sequence[int], B: int) -> dict:
-        """grow-only buffers of one pipeline slot"""
-        bf = self._bufs.get(slot)
-        if bf is not None and all(a >= b for a, b in zip(bf["M"], Ms)) and bf["B"] >= B:
-            return bf
-        if bf is not None:
-            Ms, B = [max(a, b) for a, b in zip(bf["M"], Ms)], max(B, bf["B"])
+    def _build_buffers(self, cap: Dict[str, int]) -> dict:
+        """buffers of one pipeline slot; ``cap``: utterances B and the rows M1, M2 (, M3) of each side"""
         dev, h, E, om, n = self.device, self.h, self.E, self.op_mode, len(self.NAMES)
+        B, Ms = cap["B"], [cap[f"M{i + 1}"] for i in range(n)]
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         act = lambda rows, cols: Act(rows, cols, _PLANES[om], dev, dtype=_DTYPE[om])
         side = []
@@ -2145,11 +2149,9 @@ class _FusionBase(_HeadBase):
             if n > 2:
                 sb["att_first"] = f(M, E)                         # the first out-projection of a module with two key sides (distinct from `att`)
             side.append(sb)
-        bf = dict(M=tuple(Ms), B=B, side=side, pooled=f(B, n * E), xn=f(B, n * E), hidden=f(B, self.h1), out=f(B, self.n_out),
-                  err=torch.zeros(1, dtype=torch.int32, device=dev), flag=torch.zeros(1, dtype=torch.int32, device=dev),
-                  work=torch.zeros(max(self.work_bytes, 16), dtype=torch.uint8, device=dev))
-        self._bufs[slot] = bf
-        return bf
+        return dict(side=side, pooled=f(B, n * E), xn=f(B, n * E), hidden=f(B, self.h1), out=f(B, self.n_out),
+                    err=torch.zeros(1, dtype=torch.int32, device=dev), flag=torch.zeros(1, dtype=torch.int32, device=dev),
+                    work=torch.zeros(max(self.work_bytes, 16), dtype=torch.uint8, device=dev))
 
     def _gru(self, bf, sb, w, B: int, M: int, max_frames: int, st: int) -> None:
         g = _lib.GruArgs()
@@ -2177,7 +2179,7 @@ class _FusionBase(_HeadBase):
             if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != D or x.shape[0] < Ms[i] or x.stride(1) != 1 or x.stride(0) % 4 \
                     or x.data_ptr() % 16 or x.device != self.device:
                 raise ValueError(f"{what} rows must be an fp32 [>= {Ms[i]}, {D}] tensor on {self.device} (16-byte aligned, row pitch a multiple of 4)")
-        bf = self._buffers(slot, Ms, B)
+        bf = self._bufs.fit(slot, B=B, **{f"M{i + 1}": M for i, M in enumerate(Ms)})
         st = _stream()
         flag_t = range_flag if range_flag is not None else bf["flag"]
         bf["flag_used"] = flag_t
@@ -2414,12 +2416,9 @@ class WhisperDecoder(_LaunchHost):
         pl["cross"] = cr[: L * B * S * 2 * D].view(L, B * S, 2 * D)
         pl["host"] = torch.empty(3, dtype=torch.int32).pin_memory()
         self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
-        self._rec = tape = Tape()
-        try:
+        pl["tape"] = tape = Tape()
+        with self._launching(tape):
             self._step_launches(pl)
-        finally:
-            self._rec = None
-        pl["tape"] = tape
         if len(self._plans) >= 6:
             self._plans.pop(next(iter(self._plans)))
         self._plans[(slot, B)] = pl
@@ -2698,14 +2697,12 @@ class _PreLnStack(_LaunchHost):
         check(lib.ser_ragged_index(frame_offs_dev.data_ptr(), base[1].data_ptr(), B, 1, D, 8, fc1_rowoff.data_ptr(), M, st), "ser_ragged_index")
 
 
-class ProsodyEncoder(_PreLnStack):
+class ProsodyEncoder(_WaveIO, _PreLnStack):
     """The prosody stream of the reference's three-stream heads (preprocessing/preprocess_ns3_prosody.py) on libserhip: NS3 log-mel +
     melspec_linear (ser_prosody_mel_v), melspec_encoder's pre-LayerNorm layers -- ser_layernorm_v, ser_gemm (FC1's k = 5 convolution as an
     implicit GEMM over a zero-halo'd copy, two zero rows around each utterance), ser_attention_v, ser_act_rows_v for the ReLU -- and the
     first quantizer's lookup (ser_fvq_v).  ``state_dict``: ns3_facodec_decoder_v2.bin's (``prosody.load_state_dict``); geometry from its
     shapes, ``heads`` is not in them.  Every utterance alone, as the reference's batch of one; 16 kHz input of at least 400 samples."""
-
-    use_tape = True
 
     def __init__(self, state_dict, device="cuda:0", mode: str = "f16x", heads: int = 4):
         from . import prosody as P
@@ -2725,22 +2722,15 @@ class ProsodyEncoder(_PreLnStack):
         self.last_ln = (self._dev_f32(w["last_ln"][0]), self._dev_f32(w["last_ln"][1]))
         self.w_in, self.b_in = self._dev_f32(w["w_in"]), self._dev_f32(w["b_in"])
         self.codes, self.table = self._dev_f32(w["codes"]), self._dev_f32(w["table"])
-        self._arenas: Dict[int, dict] = {}
-
-    upload = SpeechEncoder.upload
-    download = SpeechEncoder.download
+        self._arenas = SlotArenas(self._build_arena)
 
     # ------------------------------------------------------------------ buffers
-    def _arena(self, slot: int, M: int, B: int) -> dict:
-        """grow-only buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena)"""
-        ar = self._arenas.get(slot)
-        if ar is not None and ar["cap_M"] >= M and ar["cap_B"] >= B:
-            return ar
-        M, B = max(M, ar["cap_M"] if ar else 0), max(B, ar["cap_B"] if ar else 0)
-        sp, dev = self.spec, self.device
+    def _build_arena(self, cap: Dict[str, int]) -> dict:
+        """buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena)"""
+        M, B, sp, dev = cap["M"], cap["B"], self.spec, self.device
         D, F = sp.hidden, sp.ffn
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        ar = dict(cap_M=M, cap_B=B, plan=None)
+        ar = {}
         ar["x"], ar["h"], ar["tmp"], ar["z"], ar["rows"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D), f32(M, D)
         ar["f1"], ar["mel"], ar["gaps"] = f32(M, F), f32(M, sp.n_mels), f32(M)
         ar["codes"] = torch.empty(M, dtype=torch.int32, device=dev)
@@ -2754,7 +2744,6 @@ class ProsodyEncoder(_PreLnStack):
         ar["err"] = torch.zeros(1, dtype=torch.int32, device=dev)
         if self.fp16_planes:
             ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._arenas[slot] = ar
         return ar
 
     def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
@@ -2766,7 +2755,7 @@ class ProsodyEncoder(_PreLnStack):
         T = [prosody_frames(n) for n in lengths]
         offs = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
         M, Tmax, half = int(offs[-1]), max(T), self.spec.kernel // 2
-        ar = self._arena(slot, M, B)
+        ar = self._arenas.fit(slot, M=M, B=B)
         if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
             return ar["plan"]
         st, D = _stream(), self.spec.hidden
@@ -2828,22 +2817,9 @@ class ProsodyEncoder(_PreLnStack):
     def forward(self, waves, lengths: Optional[Sequence[int]] = None, slot: int = 0) -> ProsodyFeatures:
         """``waves``: a list of raw 16 kHz fp32 waveforms (uploaded here), or with ``lengths`` their packed samples on the device."""
         pl, waves = self._ingest(waves, lengths, slot)
-        ar = self._arenas[slot]
         flag = pl.get("range_flag")
         self._flag = None if flag is None else flag.data_ptr()
-        if not self.use_tape or self.gemm_trace is not None:
-            self._launches(pl, waves)
-        else:
-            tape = ar.get("tape")
-            if tape is None:
-                self._rec = tape = Tape()
-                try:
-                    self._launches(pl, waves)
-                finally:
-                    self._rec = None
-                ar["tape"] = tape
-            tape.inputs["wav"].wav = waves.data_ptr()
-            tape.run(pl["sizes"], self._s())
+        self._replay((self._arenas[slot],), pl["sizes"], lambda last: self._launches(pl, waves), waves.data_ptr())
         return self._result(pl, flag)
 
     @_on_stream
@@ -2868,15 +2844,13 @@ class SpeakerProsodyFeatures(ProsodyFeatures):
         return self._enc_x - self._pos0
 
 
-class SpeakerProsodyEncoder(_PreLnStack):
+class SpeakerProsodyEncoder(_WaveIO, _PreLnStack):
     """The reference's 512-wide third stream (preprocessing/preprocess_ns3_prosody_speaker.py) on libserhip: a ``ProsodyEncoder`` for the
     first half and, for the second, FACodecEncoderV2.block -- narrow levels (C <= 32) on ser_codec_conv_v / ser_codec_unit_v, wide ones
     (C % 64 == 0) on ser_snake_v + ser_gemm over a zero-halo'd operand copy (27 zero rows around each utterance) -- followed by
     FACodecDecoderV2.timbre_encoder's pre-LayerNorm layers, all on one stream and one command list.  ser_fvq_v writes columns 0:D and the
     timbre encoder's last LayerNorm columns D:2D of one [M, 2 D] buffer.  ``decoder_sd`` / ``encoder_sd``: the state dicts of
     ns3_facodec_decoder_v2.bin / ns3_facodec_encoder_v2.bin; 16 kHz input of at least 400 samples, every utterance alone."""
-
-    use_tape = True
 
     def __init__(self, decoder_sd, encoder_sd, device="cuda:0", mode: str = "f16x", heads: int = 4):
         from . import prosody as P
@@ -2913,23 +2887,16 @@ class SpeakerProsodyEncoder(_PreLnStack):
         self.last_ln = (dev(w["last_ln"][0]), dev(w["last_ln"][1]))
         self.pos0 = dev(P.position0(spec.out_channels).float())
         self.halo = P.WIDE_HALO
-        self._arenas: Dict[int, dict] = {}
-
-    upload = SpeechEncoder.upload
-    download = SpeechEncoder.download
+        self._arenas = SlotArenas(self._build_arena)
 
     # ------------------------------------------------------------------ buffers
-    def _arena(self, slot: int, M0: int, B: int) -> dict:
-        """grow-only buffer set of one slot, sized by the rows of level 0 (every other level's rows are its exact quotients)"""
-        ar = self._arenas.get(slot)
-        if ar is not None and ar["cap_M0"] >= M0 and ar["cap_B"] >= B:
-            return ar
-        M0, B = max(M0, ar["cap_M0"] if ar else 0), max(B, ar["cap_B"] if ar else 0)
-        sp, dev = self.spec, self.device
+    def _build_arena(self, cap: Dict[str, int]) -> dict:
+        """buffer set of one slot, sized by the rows of level 0 (every other level's rows are its exact quotients)"""
+        B, sp, dev = cap["B"], self.spec, self.device
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-        ar = dict(cap_M0=M0, cap_B=B, plan=None, lv=[])
-        rows = M0
+        ar = dict(lv=[])
+        rows = cap["M0"]
         for l, C in enumerate(sp.channels):
             last = l == len(sp.strides)
             lv = dict(cap=rows, xa=f32(rows, C), offs=i32(B + 1), offs64=torch.empty(B + 1, dtype=torch.int64, device=dev))
@@ -2955,7 +2922,6 @@ class SpeakerProsodyEncoder(_PreLnStack):
         ar["halo"] = self._new_act(M + (ts.kernel // 2) * (B + 1), D, zero=True)
         ar["halo_rowmap"], ar["fc1_rowoff"] = i32(M), i32(M)
         ar["base"] = torch.empty((2, B), dtype=torch.int64, device=dev)
-        self._arenas[slot] = ar
         return ar
 
     def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
@@ -2963,7 +2929,7 @@ class SpeakerProsodyEncoder(_PreLnStack):
         lengths, B, sp = ppl["lengths"], int(ppl["B"]), self.spec
         lens = np.array([sp.level_lengths(n) for n in lengths], dtype=np.int64)        # [B, levels]
         offs = np.concatenate([np.zeros((1, lens.shape[1]), dtype=np.int64), np.cumsum(lens, axis=0)]).T   # [levels, B + 1]
-        ar = self._arena(slot, int(offs[0, -1]), B)
+        ar = self._arenas.fit(slot, M0=int(offs[0, -1]), B=B)
         old = ar["plan"]
         if old is not None and old["ppl"] is ppl:
             return old
@@ -3040,12 +3006,12 @@ class SpeakerProsodyEncoder(_PreLnStack):
         if keep is not None:
             keep[name] = x[: int(rows)].clone()
         if self._rec is not None and not name.startswith("u"):
-            self._rec.__dict__.setdefault("parts", []).append((name, self._rec.n))
+            self._rec.parts.append((name, self._rec.n))
 
     def _codec_launches(self, pl, packed_wave: torch.Tensor, keep: Optional[dict] = None) -> None:
         sp, B, Ms, Rs, lvs = self.spec, pl["B"], pl["Ms"], pl["Rs"], pl["lv"]
         x = lvs[0]["xa"]
-        self._conv(packed_wave, pl["ppl"]["sample_offs"], lvs[0]["offs"], None, self.conv_in, x, 1, sp.ngf, 7, 1, 3, B, Rs[0], Ms[0], input="wav_codec")
+        self._conv(packed_wave, pl["ppl"]["sample_offs"], lvs[0]["offs"], None, self.conv_in, x, 1, sp.ngf, 7, 1, 3, B, Rs[0], Ms[0], input="x")
         self._keep_level(keep, "conv_in", x, Ms[0])
         for l, L in enumerate(self.levels):
             lv, nxt, C, s = lvs[l], lvs[l + 1], L["C"], L["stride"]
@@ -3091,46 +3057,29 @@ class SpeakerProsodyEncoder(_PreLnStack):
             waves = self.upload(waves, slot)
         else:
             pl = self._plan(lengths, slot)
-        ar, pro = self._arenas[slot], self.prosody
+        pro = self.prosody
         flag = pl["ppl"].get("range_flag")
-        self._flag = pro._flag = None if flag is None else flag.data_ptr()
-        prev, pro._st = pro._st, self._st
+        self._flag = None if flag is None else flag.data_ptr()
         keep = {} if keep_levels else None
-        try:
-            if keep_levels or not self.use_tape:
+        if keep_levels:
+            with self._launching(None, (pro,)):
                 self._launch_all(pl, waves, keep)
-            else:
-                tape = ar.get("tape")
-                if tape is None or ar.get("tape_for") is not pro._arenas[slot]:      # (the prosody arena grew: its pointers moved)
-                    self._rec = pro._rec = tape = Tape()
-                    try:
-                        self._launch_all(pl, waves)
-                    finally:
-                        self._rec = pro._rec = None
-                    ar["tape"], ar["tape_for"] = tape, pro._arenas[slot]
-                tape.inputs["wav"].wav = waves.data_ptr()
-                tape.inputs["wav_codec"].x = waves.data_ptr()
-                tape.run(pl["sizes"], self._s())
-        finally:
-            pro._st = prev
+        else:
+            # the list points into the prosody encoder's arena as well: recorded again when either arena was replaced
+            self._replay((self._arenas[slot], pro._arenas[slot]), pl["sizes"], lambda last: self._launch_all(pl, waves), waves.data_ptr(),
+                         hosts=(pro,))
         M, pp = int(pl["M"]), pl["pp"]
         return SpeakerProsodyFeatures(pl["rows2"][:M], pp["codes"][:M], pp["gaps"][:M], pp["z"][:M], pp["mel"][:M], pp["frame_offs_host"], flag,
                                       pp["frame_offs"], pp["err"], pl["enc"][:M], self.pos0, keep)
 
 
-class W2vBertEncoder(_EncoderBase):
+class W2vBertEncoder(_WaveIO, _EncoderBase):
     """w2v-BERT 2.0 (HF Wav2Vec2BertModel behind SeamlessM4TFeatureExtractor; not in the reference, whose heads take any [T, D] stream) on
     libserhip: the Kaldi fbank front end (ser_fbank_v), the feature projection, and per conformer layer
         x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(LN x);  x += FFN2(LN x) / 2;  x = LN x
     on ser_layernorm_v and ser_gemm, with ser_swish_rows_v between a feed-forward block's GEMMs, ser_relkey_table_v + ser_attention_rk_v for
     the relative-key attention and ser_conformer_conv_v between the convolution module's pointwise GEMMs.  The two 1/2 factors are folded
     into the blocks' output Linears at load.  Every utterance alone: ``frames(n) = (1 + (n - 400) // 160) // stride`` rows, at least one."""
-
-    use_tape = True
-    upload = SpeechEncoder.upload
-    upload_resampled = SpeechEncoder.upload_resampled
-    _resample_bank = SpeechEncoder._resample_bank
-    download = SpeechEncoder.download
 
     def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "f16x"):
         from .frontend import w2vbert_dft_table, w2vbert_mel_filters
@@ -3179,22 +3128,19 @@ class W2vBertEncoder(_EncoderBase):
             lay["pw2"] = self._linear(sd[c + ".pointwise_conv2.weight"].reshape(D, D), None, name=c + ".pointwise_conv2.weight")
             lay["final_ln"] = self._ln_pair(sd, p + ".final_layer_norm")
             self.layers.append(lay)
-        self._arenas: Dict[int, dict] = {}
+        self._arenas = SlotArenas(self._build_arena)
 
     def frames(self, num_samples: int) -> int:
         return self.geo.frames_for(num_samples)
 
     # ------------------------------------------------------------------ buffers
-    def _arena(self, slot: int, M: int, B: int, Fr: int) -> dict:
-        """grow-only buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena)"""
-        ar = self._arenas.get(slot)
-        if ar is not None and ar["cap_M"] >= M and ar["cap_B"] >= B and ar["cap_F"] >= Fr:
-            return ar
-        M, B, Fr = max(M, ar["cap_M"] if ar else 0), max(B, ar["cap_B"] if ar else 0), max(Fr, ar["cap_F"] if ar else 0)
-        geo, dev = self.geo, self.device
+    def _build_arena(self, cap: Dict[str, int]) -> dict:
+        """buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena); ``cap``: frames M,
+        utterances B, mel frames F"""
+        M, B, Fr, geo, dev = cap["M"], cap["B"], cap["F"], self.geo, self.device
         D, F, H = geo.hidden, geo.ffn, geo.heads
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        ar = dict(cap_M=M, cap_B=B, cap_F=Fr, plan=None)
+        ar = {}
         ar["mel"], ar["fb"] = f32(Fr, geo.fbank_mels), f32(M, self.fdim)
         ar["fb_act"] = self._new_act(M, self.fpad, zero=True)                 # columns past 160 stay zero
         ar["states"] = f32(geo.num_layers + 1, M, D)
@@ -3207,7 +3153,6 @@ class W2vBertEncoder(_EncoderBase):
         ar["frame_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
         if self.fp16_planes:
             ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._arenas[slot] = ar
         return ar
 
     def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
@@ -3221,7 +3166,7 @@ class W2vBertEncoder(_EncoderBase):
         offs = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
         moffs = np.concatenate([[0], np.cumsum(Fr)]).astype(np.int64)
         M, Tmax, Fmax = int(offs[-1]), max(T), max(Fr)
-        ar = self._arena(slot, M, B, int(moffs[-1]))
+        ar = self._arenas.fit(slot, M=M, B=B, F=int(moffs[-1]))
         if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
             return ar["plan"]
         ar["sample_offs"][: B + 1].copy_(torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))

@@ -200,6 +200,10 @@ def test_predict_matches_hf_float64(name, mode):
     alone = np.stack([clf.predict([w])[0] for w in waves])
     assert ragged.shape == (3, fx.spec().num_labels) and not clf.failed
     assert np.array_equal(ragged.view(np.uint32), alone.view(np.uint32))
+    for batch, want in ((waves[:1], ragged[:1]), (waves, ragged)):       # a slot of the head that meets the smaller batch first and grows
+        dev, lengths = clf.upload_resampled(batch, None)
+        got = clf.head.forward(clf.enc.forward(dev, lengths), slot=2).cpu().numpy()
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     eps, wide = EPS[name][mode], 0
     for j in range(3):
         bound = fx.logit_bound(eps, j)

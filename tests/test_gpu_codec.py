@@ -335,18 +335,37 @@ def test_full_geometry_on_two_short_waves(built_library):
 
 
 def test_replay_equals_a_fresh_eager_forward(fx):
+    from interspeech_ser_amd import _lib
     from interspeech_ser_amd.engine import SpeakerProsodyEncoder
     waves = fx["waves"]
     eager = SpeakerProsodyEncoder(fx["dec_full"], fx["enc"], DEV, "f16x", heads=HEADS)
     eager.use_tape = False
     taped = _encoder(fx, "f16x")
-    for batch in (waves, [waves[3], waves[0]], [waves[1]], waves):                  # recorded once, sizes patched for the others
-        a, b = eager.forward(batch), taped.forward(batch)
-        assert "tape" in taped._arenas[0] and "tape" not in eager._arenas[0]
-        for name in ("rows", "encoded", "z", "gaps", "mel"):
-            assert np.array_equal(_bits(getattr(a, name).cpu().numpy()), _bits(getattr(b, name).cpu().numpy())), name
-        assert torch.equal(a.codes, b.codes) and a.frame_offs == b.frame_offs
-        assert a.take_range_bits() == 0 and b.take_range_bits() == 0
+    # slot 0: recorded once, on the largest batch, sizes patched for the others.  Slot 1 starts small: the arena grows under a recorded list
+    # (which must be recorded again over the new buffers), then holds a subset and the full batch again
+    runs = [(batch, 0) for batch in (waves, [waves[3], waves[0]], [waves[1]], waves)]
+    runs += [(batch, 1) for batch in ([waves[1]], waves, [waves[3], waves[0]], waves)]
+    for batch, slot in runs:
+        a, b = eager.forward(batch, slot=slot), taped.forward(batch, slot=slot)
+        lens = [len(w) for w in batch]
+        assert taped.recorded_tape(lens, slot).n > 0
+        with pytest.raises(_lib.SerHipError, match="no recorded command list"):
+            eager.recorded_tape(lens, slot)
+        _same_features(a, b)
+    # only the INNER prosody encoder's arena grows between two forwards of the outer one: the outer list points into it as well
+    small, larger = [waves[1]], waves
+    want = eager.forward(small, slot=2)
+    first = taped.forward(small, slot=2)
+    _same_features(want, first)
+    taped.prosody.forward(larger, slot=2)
+    _same_features(eager.forward(small, slot=2), taped.forward(small, slot=2))
+
+
+def _same_features(a, b):
+    for name in ("rows", "encoded", "z", "gaps", "mel"):
+        assert np.array_equal(_bits(getattr(a, name).cpu().numpy()), _bits(getattr(b, name).cpu().numpy())), name
+    assert torch.equal(a.codes, b.codes) and a.frame_offs == b.frame_offs
+    assert a.take_range_bits() == 0 and b.take_range_bits() == 0
 
 
 def test_short_wave_fails_alone(fx):

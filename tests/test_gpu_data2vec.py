@@ -253,7 +253,7 @@ def test_command_list_replay_equals_eager(case):
                 enc.use_tape = use_tape
                 hs = enc.forward(dev, list(lens), last_state=n)
                 assert torch.equal(hs.states[: n + 1], ref[: n + 1]), (n, use_tape)
-    tape = enc._arenas[0]["tape"]
+    tape = enc.recorded_tape(list(lens), 0)
     from interspeech_ser_amd import _lib
     assert sum(tape.cmds[i].op == _lib.OP_POS_LN for i in range(tape.n)) == geo.pos_conv_layers
 

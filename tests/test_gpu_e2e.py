@@ -661,7 +661,7 @@ def test_pipelined_slots_equal_synchronous_path():
 def test_command_list_replay_equals_launch_by_launch():
     """A forward replayed from its recorded command list (ser_run, sizes patched per batch) is bit-identical to the
     same forward launched kernel by kernel, across growing / shrinking ragged batches that re-use one arena."""
-    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd import _lib, config as C
     from interspeech_ser_amd.engine import SpeechEncoder
     from interspeech_ser_amd.weights import synthetic_state_dict
     geo = C.TINY_HUBERT
@@ -678,7 +678,9 @@ def test_command_list_replay_equals_launch_by_launch():
         torch.cuda.synchronize()
         assert a.frame_offs == b.frame_offs
         assert torch.equal(a.states, b.states), k
-    assert taped._arenas[0].get("tape") is not None and eager._arenas[0].get("tape") is None
+    assert taped.recorded_tape(lens, 0).n > 0
+    with pytest.raises(_lib.SerHipError, match="no recorded command list"):
+        eager.recorded_tape(lens, 0)
 
 
 @pytest.mark.parametrize("family", ["wavlm", "hubert", "whisper"])
@@ -711,7 +713,7 @@ def test_whisper_command_list_and_pipeline_equal_eager():
     """Whisper is first-class on the host side too: the recorded command list (log-mel -> stem -> layers in one ser_run)
     is bit-identical to launching kernel by kernel, and the two-slot pipeline (streams, pinned D2H, the reference's
     crop applied on collect) is bit-identical to the synchronous path -- across batches of different sizes and lengths."""
-    from interspeech_ser_amd import config as C
+    from interspeech_ser_amd import _lib, config as C
     from interspeech_ser_amd.driver import _Extractor
     from interspeech_ser_amd.engine import WhisperEncoder
     from interspeech_ser_amd.frontend import whisper_saved_rows
@@ -733,7 +735,9 @@ def test_whisper_command_list_and_pipeline_equal_eager():
         b = eager.forward(eager.upload(waves), lens)
         torch.cuda.synchronize()
         assert torch.equal(a.states, b.states)
-    assert any("tape" in pl for pl in taped._cache.values()) and not any("tape" in pl for pl in eager._cache.values())
+    assert taped.recorded_tape(lens, 0).n > 0
+    with pytest.raises(_lib.SerHipError, match="no recorded command list"):
+        eager.recorded_tape(lens, 0)
     ex = _Extractor.__new__(_Extractor)
     ex.whisper, ex.average, ex.geo, ex.enc = True, False, geo, taped
     want = [[t.clone() for t in ex.extract(b, 2)] for b in batches]

@@ -345,10 +345,10 @@ def test_fusion_classifier_padded_rows_are_bit_equal(built_library):
 
 
 # ------------------------------------------------------------------------------- engine.FusionHead
-def _head_forward(head, xs1, xs2):
+def _head_forward(head, xs1, xs2, slot=0):
     x1, x2 = _dev(np.concatenate(xs1)), _dev(np.concatenate(xs2))
-    out = head.forward(x1, _offs([len(x) for x in xs1]), x2, _offs([len(x) for x in xs2])).cpu().numpy().copy()
-    assert head.status() == (0, 0)
+    out = head.forward(x1, _offs([len(x) for x in xs1]), x2, _offs([len(x) for x in xs2]), slot=slot).cpu().numpy().copy()
+    assert head.status(slot) == (0, 0)
     return out
 
 
@@ -367,6 +367,9 @@ def test_fusion_head_against_the_float64_statement(built_library, mode):
         for i in range(3):                                               # one at a time: bit-equal logits
             one = _head_forward(head, xs1[i:i + 1], xs2[i:i + 1])
             assert np.array_equal(one[0].view(np.uint32), got[i].view(np.uint32)), i
+        # a slot that meets the smallest utterance first and grows for the batch
+        assert np.array_equal(_head_forward(head, xs1[:1], xs2[:1], slot=1)[0].view(np.uint32), got[0].view(np.uint32))
+        assert np.array_equal(_head_forward(head, xs1, xs2, slot=1).view(np.uint32), got.view(np.uint32))
     assert worst <= gate, (worst, gate)
 
 

@@ -270,6 +270,11 @@ def test_pool_head_on_encoder_output(built_library, geo_name, mode, n_out):
         hs1 = enc.forward(enc.upload([w]), [len(w)])
         one = head.forward(hs1).cpu().numpy()
         assert np.array_equal(one[0].view(np.uint32), got[i].view(np.uint32)), i
+        if i == 0:
+            first = head.forward(hs1, slot=1).cpu().numpy()   # a slot of the head that meets the smaller batch first ...
+            assert np.array_equal(first.view(np.uint32), one.view(np.uint32))
+    grown = head.forward(enc.forward(enc.upload(waves), lengths), slot=1).cpu().numpy()    # ... and grows for the ragged one
+    assert np.array_equal(grown.view(np.uint32), got.view(np.uint32))
 
 
 def test_pool_head_refuses_what_it_cannot_run(built_library):

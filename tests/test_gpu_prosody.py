@@ -288,14 +288,22 @@ def test_full_geometry_on_two_short_waves(built_library):
 
 
 def test_replay_equals_a_fresh_eager_forward(fx):
+    from interspeech_ser_amd import _lib
     from interspeech_ser_amd.engine import ProsodyEncoder
     waves = fx["waves"]
     eager = ProsodyEncoder(fx["sd"], DEV, "f16x", heads=HEADS)
     eager.use_tape = False
     taped = ProsodyEncoder(fx["sd"], DEV, "f16x", heads=HEADS)
-    for batch in (waves, [waves[3], waves[0]], [waves[1]], waves):            # recorded on the first, sizes patched for the others
-        a, b = eager.forward(batch), taped.forward(batch)
-        assert "tape" in taped._arenas[0] and "tape" not in eager._arenas[0]
+    # slot 0: recorded on the first batch, the largest, sizes patched for the others.  Slot 1 starts small: the arena grows under a recorded
+    # list (which must be recorded again over the new buffers), then holds a subset and the full batch again
+    runs = [(batch, 0) for batch in (waves, [waves[3], waves[0]], [waves[1]], waves)]
+    runs += [(batch, 1) for batch in ([waves[1]], waves, [waves[3], waves[0]], waves)]
+    for batch, slot in runs:
+        a, b = eager.forward(batch, slot=slot), taped.forward(batch, slot=slot)
+        lens = [len(w) for w in batch]
+        assert taped.recorded_tape(lens, slot).n > 0
+        with pytest.raises(_lib.SerHipError, match="no recorded command list"):
+            eager.recorded_tape(lens, slot)
         for name in ("mel", "z", "rows", "gaps"):
             assert np.array_equal(_bits(getattr(a, name).cpu().numpy()), _bits(getattr(b, name).cpu().numpy())), name
         assert torch.equal(a.codes, b.codes) and a.frame_offs == b.frame_offs

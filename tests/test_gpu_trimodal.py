@@ -159,12 +159,12 @@ def test_xattn_mh_range_guard(built_library):
 
 
 # ------------------------------------------------------------------------------- engine.TrimodalHead
-def _forward(head, xs1, xs2, xs3, third_axis=False):
+def _forward(head, xs1, xs2, xs3, third_axis=False, slot=0):
     x1, x2, x3 = (_dev(np.concatenate(x)) for x in (xs1, xs2, xs3))
     if third_axis:
         x3 = x3[..., None]
-    out = head.forward(x1, _offs([len(x) for x in xs1]), x2, _offs([len(x) for x in xs2]), x3, _offs([len(x) for x in xs3])).cpu().numpy().copy()
-    assert head.status() == (0, 0)
+    out = head.forward(x1, _offs([len(x) for x in xs1]), x2, _offs([len(x) for x in xs2]), x3, _offs([len(x) for x in xs3]), slot=slot).cpu().numpy().copy()
+    assert head.status(slot) == (0, 0)
     return out
 
 
@@ -188,6 +188,9 @@ def test_trimodal_head_against_the_float64_statement(built_library, mode):
         for i in range(3):                                               # one at a time: bit-equal logits
             one = _forward(head, xs1[i:i + 1], xs2[i:i + 1], xs3[i:i + 1], third_axis=(i == 1))
             assert np.array_equal(one[0].view(np.uint32), got[i].view(np.uint32)), i
+        # a slot that meets one utterance first and grows, on every side, for the batch
+        assert np.array_equal(_forward(head, xs1[1:2], xs2[1:2], xs3[1:2], slot=1)[0].view(np.uint32), got[1].view(np.uint32))
+        assert np.array_equal(_forward(head, xs1, xs2, xs3, slot=1).view(np.uint32), got.view(np.uint32))
         one_head = _forward(TrimodalHead(sd, *SMALL_DIMS, DEV, mode, heads=(1, 1, 1)), xs1, xs2, xs3)
         assert not np.array_equal(one_head, got)                         # the head count reaches the kernel
     assert worst <= gate, (worst, gate)

@@ -366,6 +366,12 @@ def test_end_to_end_against_hf(fixtures, case, mode):
     for b, w in enumerate(waves):
         one = enc.forward(enc.upload([w]), [lengths[b]], slot=1)
         assert torch.equal(_bits(one.states), _bits(eager_states[:, offs[b]: offs[b + 1]])), b
+    # a slot that starts small: its arena grows under a recorded list (recorded again over the new buffers), then holds a subset and the
+    # full batch again; every batch is its utterances' rows of the eager forward
+    for pick in ([1], [0, 1, 2], [2, 0], [0, 1, 2]):
+        hs = enc.forward(enc.upload([waves[b] for b in pick]), [lengths[b] for b in pick], slot=2)
+        want = torch.cat([eager_states[:, offs[b]: offs[b + 1]] for b in pick], dim=1)
+        assert hs.take_range_bits() == 0 and torch.equal(_bits(hs.states), _bits(want)), pick
     # a state asked for alone stops the replay there and is the full forward's
     part = enc.forward(enc.upload(waves), lengths, last_state=1)
     assert part.computed == 2 and torch.equal(_bits(part.states[1]), _bits(eager_states[1]))

@@ -80,7 +80,7 @@ for mode in ("f16x", "fp32x", "bf16"):
         out = enc.forward(packed, lengths)
     assert out.take_range_bits() == 0
     t_fwd = timed(lambda: enc.forward(packed, lengths), reps)
-    tape = enc._arenas[0]["tape"]
+    tape = enc.recorded_tape(lengths, 0)
     st = torch.cuda.current_stream().cuda_stream
     marks = [("start", 0)] + list(tape.parts) + [("final + timbre", tape.n)]
     lines.append(f"  mode {mode:5s}: forward (replayed command list, {tape.n} commands) {t_fwd:9.1f} us = {B * 1e6 / t_fwd:7.0f} utt/s")

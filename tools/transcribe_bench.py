@@ -117,7 +117,7 @@ def main():
             dec._run_step(pl, True)
         torch.cuda.synchronize()
         assert int(pl["pos"].item()) == a.warm and int(pl["err"].item()) == 0, (int(pl["pos"].item()), int(pl["err"].item()))
-        tape = pl["tape"]
+        tape = dec.recorded_tape(B, 0)
 
         def run(t, n, resets_pos):
             def fn(before):
