@@ -29,7 +29,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .arena import SlotArenas
+from .arena import Pinned, SlotArenas, TableBlob
 from .weights import check_f16_weight
 from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_WAVLM, FAMILY_WHISPER
 
@@ -954,14 +954,33 @@ def _fold_weight_norm(sd) -> torch.Tensor:
     return v * (g / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())
 
 
+def _halo_layout(tab: TableBlob, offs, offs_dev, half: int, width: int, rowmap, rowoffs, halo: Act, taps=None):
+    """The zero-halo'd copy of a ragged batch: [half zero rows][utt 0][half zero rows][utt 1] ... [half zero rows]; row t of utterance b
+    sits at ``starts[b] + t``, starts[b] = half (b + 1) + offs[b], and a convolution's taps begin ``taps[j]`` (default: half) rows
+    earlier.  Puts the O(B) base rows into ``tab`` and returns (starts, the function that builds the O(rows) tables once ``tab`` is
+    sent): the row map into ``rowmap``, the tap offsets (16-byte units of ``width``-column rows) into ``rowoffs[j]``, and zeroes ``halo``
+    when an earlier plan left rows where this one's halo lies."""
+    B, M = len(offs) - 1, int(offs[-1])
+    starts = half * np.arange(1, B + 1, dtype=np.int64) + np.asarray(offs[:B], dtype=np.int64)
+    bases = [tab.put64(starts)] + [tab.put64(starts - t) for t in (taps or (half,))]
+
+    def index(st: int, rezero: bool) -> None:
+        check(lib.ser_ragged_index(offs_dev.data_ptr(), bases[0].data_ptr(), B, 1, 1, 1, rowmap.data_ptr(), M, st), "ser_ragged_index")
+        for base, out in zip(bases[1:], rowoffs):
+            check(lib.ser_ragged_index(offs_dev.data_ptr(), base.data_ptr(), B, 1, width, 8, out.data_ptr(), M, st), "ser_ragged_index")
+        if rezero:
+            halo.t.zero_()
+    return starts, index
+
+
 class _WaveIO:
     """Waveform I/O of the encoders that take raw samples: ``upload`` / ``upload_resampled`` (host -> packed device buffer) and ``download``.
     A mixin in front of a ``_LaunchHost`` (it reads ``self.device``)."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self._pin_in: Dict[int, tuple] = {}                 # slot -> (pinned staging buffer, event behind its last copy)
-        self._rs_tab: Dict[int, tuple] = {}                 # slot -> (pinned blob, device blob, event) of ser_resample_v's O(B) tables
+        self._pin_in: Dict[int, Pinned] = {}                # slot -> pinned staging buffer of ``upload``
+        self._rs_tabs: Dict[int, TableBlob] = {}            # slot -> ser_resample_v's O(B) tables
         self._rs_banks = dict(buf=None, used=0, offs={}, retired=[])      # the polyphase banks met so far, one float64 device buffer
 
     def upload(self, waves: Sequence[np.ndarray], slot: int = 0) -> torch.Tensor:
@@ -980,12 +999,11 @@ class _WaveIO:
                     dev[o:o + t.numel()].copy_(t, non_blocking=True)
                     o += t.numel()
                 return dev
-        pin, evt = self._pin_in.get(slot, (None, None))
-        if pin is None or pin.numel() < total:
-            pin, evt = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory(), None
-        elif evt is not None:
-            evt.synchronize()
-        host = pin[:total]
+        pin = self._pin_in.get(slot)
+        if pin is None or pin.host.numel() < total:
+            pin = self._pin_in[slot] = Pinned(max(total, 1 << 20), torch.float32)
+        pin.wait()
+        host = pin.host[:total]
         view = host.numpy()
         o = 0
         for w in waves:
@@ -993,9 +1011,7 @@ class _WaveIO:
             view[o:o + n] = w
             o += n
         dev = host.to(self.device, non_blocking=True)
-        evt = torch.cuda.Event()
-        evt.record()
-        self._pin_in[slot] = (pin, evt)
+        pin.sent()
         return dev
 
     def _resample_bank(self, up: int, down: int):
@@ -1038,31 +1054,18 @@ class _WaveIO:
         n_out = [(n * u + d - 1) // d for n, (u, d) in zip(n_in, ratios)]
         banks = [(0, 0) if u == d == 1 else self._resample_bank(u, d) for u, d in ratios]
         raw = self.upload(waves, slot)
-        # ---- O(B) tables -> this slot's pinned blob (int64 words: in_offs, out_offs, bank_off; then int32: up, down, half), one async copy
-        words = 3 * B + 2 + (3 * B + 1) // 2
-        host, dev, evt = self._rs_tab.get(slot, (None, None, None))
-        if host is None or host.numel() < words:
-            host = torch.empty(max(words, 256), dtype=torch.int64).pin_memory()
-            dev, evt = torch.empty(host.numel(), dtype=torch.int64, device=self.device), None
-        elif evt is not None:
-            evt.synchronize()                                 # the previous batch's copy out of the blob has finished
-        h64 = host.numpy()
-        h64[0: B + 1] = np.concatenate([[0], np.cumsum(n_in)])
-        h64[B + 1: 2 * B + 2] = np.concatenate([[0], np.cumsum(n_out)])
-        h64[2 * B + 2: 3 * B + 2] = [o for o, _ in banks]
-        h32 = h64[3 * B + 2:].view(np.int32)
-        h32[0: B] = [u for u, _ in ratios]
-        h32[B: 2 * B] = [d for _, d in ratios]
-        h32[2 * B: 3 * B] = [hf for _, hf in banks]
-        dev[:words].copy_(host[:words], non_blocking=True)
-        evt = torch.cuda.Event()
-        evt.record()
-        self._rs_tab[slot] = (host, dev, evt)
+        # ---- O(B) tables -> this slot's blob, replaced by a larger one when B outgrows it
+        tab = self._rs_tabs.get(slot)
+        if tab is None or tab.layout.region < B + 2:
+            tab = self._rs_tabs[slot] = TableBlob(max(B, 16), 6, self.device)
+        tab.begin()
+        tabs = [tab.put64(np.concatenate([[0], np.cumsum(n)])) for n in (n_in, n_out)] + [tab.put64([o for o, _ in banks])]
+        tabs += [tab.put32(v) for v in ([u for u, _ in ratios], [d for _, d in ratios], [hf for _, hf in banks])]
+        tab.send()
         out = torch.empty(int(sum(n_out)), dtype=torch.float32, device=self.device)
         a = _lib.ResampleArgs()
-        base, i32 = dev.data_ptr(), dev.data_ptr() + 8 * (3 * B + 2)
-        a.wav, a.in_offs, a.out_offs, a.bank_off = raw.data_ptr(), base, base + 8 * (B + 1), base + 8 * (2 * B + 2)
-        a.up, a.down, a.half = i32, i32 + 4 * B, i32 + 8 * B
+        a.wav = raw.data_ptr()
+        a.in_offs, a.out_offs, a.bank_off, a.up, a.down, a.half = (t.data_ptr() for t in tabs)
         a.bank, a.out = self._rs_banks["buf"].data_ptr(), out.data_ptr()
         a.total_in, a.total_out, a.max_out, a.B = int(sum(n_in)), int(sum(n_out)), int(max(n_out)), B
         check(lib.ser_resample_v(C.byref(a), _stream()), "ser_resample_v")
@@ -1166,7 +1169,7 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
                 k_bias=True, gate=(geo.family == FAMILY_WAVLM), index=i))
         if geo.family == FAMILY_WAVLM:
             self.rel_embed = self._dev_f32(sd["encoder.layers.0.attention.rel_attn_embed.weight"])
-        self._arenas = SlotArenas(self._build_arena)          # per slot; ar["plan"]: (lengths, plan) currently laid out in it
+        self._arenas = SlotArenas(self._build_arena)          # per slot; ar["plan"]: the plan currently laid out in it
 
     # ------------------------------------------------------------------ per-slot arenas + plans
     def _build_arena(self, cap: Dict[str, int]) -> dict:
@@ -1200,14 +1203,8 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
             self._layer_buffers(ar, cap["M"], ar["first_groups"])
         if geo.family == FAMILY_WAVLM:
             ar["table"] = torch.empty(geo.heads * (2 * cap["Tmax"] - 1), dtype=torch.float32, device=dev)
-        # small per-batch tables: one pinned host blob -> one async H2D into one device blob (int64 words)
-        # fixed regions of cap B + 2 words each (pointers into the blob must not move from batch to batch):
-        # sample_offs | offs[0..nl) (int32, two per word) | conv bases [1..nl) | halo base | pos base
-        ar["tab_region"] = cap["B"] + 2
-        words = (1 + nl + (nl - 1) + 2) * ar["tab_region"]
-        ar["tab_host"] = torch.empty(words, dtype=torch.int64).pin_memory()
-        ar["tab_dev"] = torch.empty(words, dtype=torch.int64, device=dev)
-        ar["tab_evt"] = None
+        # the O(B) tables: sample_offs | offs[0..nl) (int32) | conv bases [1..nl) | halo base | pos base
+        ar["tab"] = TableBlob(cap["B"], 1 + nl + (nl - 1) + 2, dev)
         return ar
 
     def _plan(self, lengths: Sequence[int], slot: int = 0):
@@ -1228,49 +1225,25 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
         half = geo.pos_conv_kernel // 2
         halo_rows = int(M + half * (B + 1))
         ar = self._arenas.fit(slot, rows0=int(offs[0][-1]), rows1=int(offs[1][-1]) if nl > 1 else 1, M=M, halo=halo_rows, B=B, Tmax=Tmax)
-        if ar["plan"] is not None and ar["plan"][0] == lengths:
-            return ar["plan"][1]
+        if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
+            return ar["plan"]
         st = _stream()
         C0, D = geo.conv_dim[0], geo.hidden
-        # ---- O(B) tables -> pinned blob (int64 words; int32 tables packed two per word)
-        if ar["tab_evt"] is not None:
-            ar["tab_evt"].synchronize()                     # the previous batch's copy out of the blob has finished
-        host64 = ar["tab_host"].numpy()
-        host32 = host64.view(np.int32)
-        dev64 = ar["tab_dev"]
-        dev32 = dev64.view(torch.int32)
-        region = [0]                                        # next fixed region (int64 words)
-
-        def put64(a):
-            a = np.asarray(a, dtype=np.int64)
-            w = region[0] * ar["tab_region"]
-            region[0] += 1
-            host64[w:w + len(a)] = a
-            return dev64[w:w + len(a)]
-
-        def put32(a):
-            a = np.asarray(a, dtype=np.int32)
-            w = region[0] * ar["tab_region"]
-            region[0] += 1
-            host32[2 * w:2 * w + len(a)] = a
-            return dev32[2 * w:2 * w + len(a)]
-
+        tab = ar["tab"].begin()
         pl = dict(ar)                                       # arena buffers + this batch's views / numbers
         pl["rows"] = [Sz(int(o[-1]), f"rows{i}") for i, o in enumerate(offs)]
         pl["sizes"] = {f"rows{i}": int(r) for i, r in enumerate(pl["rows"])}
         pl["sizes"].update(M=M, B=B, Tmax=Tmax)
         pl.update(B=Sz(B, "B"), lengths=lengths, T=T, M=Sz(M, "M"), Tmax=Sz(Tmax, "Tmax"), halo_rows=halo_rows)
-        pl["sample_offs"] = put64(np.concatenate([[0], np.cumsum(lengths)]))
-        offs_dev = [put32(o) for o in offs]                 # offs[i][b] = first row of utterance b after conv layer i
+        pl["sample_offs"] = tab.put64(np.concatenate([[0], np.cumsum(lengths)]))
+        offs_dev = [tab.put32(o) for o in offs]             # offs[i][b] = first row of utterance b after conv layer i
         pl["frame_offs0"] = offs_dev[0]
         pl["frame_offs"] = offs_dev[-1]
         pl["frame_offs_host"] = [int(x) for x in offs[-1]]
-        starts = np.array([half * (b + 1) + offs[-1][b] for b in range(B)], dtype=np.int64)
-        base_conv = [put64(offs[i - 1][:B]) for i in range(1, nl)]
-        base_halo, base_pos = put64(starts), put64(starts - half)
-        dev64.copy_(ar["tab_host"], non_blocking=True)
-        ar["tab_evt"] = torch.cuda.Event()
-        ar["tab_evt"].record()
+        base_conv = [tab.put64(offs[i - 1][:B]) for i in range(1, nl)]
+        # halo'd layout of the positional-conv input: [64 zero rows][utt 0][64 zero rows][utt 1] ... [64 zero rows]
+        _, halo_index = _halo_layout(tab, offs[-1], offs_dev[-1], half, D, ar["halo_rowmap"], [ar["pos_rowoff"]], ar["halo_act"])
+        tab.send()
         # ---- O(rows) tables on the device
         rowoffs = []
         for i in range(1, nl):
@@ -1279,13 +1252,7 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
                                        out.data_ptr(), pl["rows"][i], st), "ser_ragged_index")
             rowoffs.append(out)
         pl["conv_rowoff"] = rowoffs
-        # halo'd layout of the positional-conv input: [64 zero rows][utt 0][64 zero rows][utt 1] ... [64 zero rows]
-        check(lib.ser_ragged_index(offs_dev[-1].data_ptr(), base_halo.data_ptr(), B, 1, 1, 1,
-                                   ar["halo_rowmap"].data_ptr(), M, st), "ser_ragged_index")
-        check(lib.ser_ragged_index(offs_dev[-1].data_ptr(), base_pos.data_ptr(), B, 1, D, 8,
-                                   ar["pos_rowoff"].data_ptr(), M, st), "ser_ragged_index")
-        if ar["plan"] is not None:
-            ar["halo_act"].t.zero_()                        # the halo rows sit elsewhere than in the previous batch
+        halo_index(st, ar["plan"] is not None)
         pl["states"] = ar["states"][:, :M]
         if geo.family == FAMILY_WAVLM:
             pl["table"] = ar["table"][: geo.heads * (2 * Tmax - 1)].view(geo.heads, 2 * Tmax - 1)
@@ -1293,7 +1260,7 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
                 check(lib.ser_wavlm_bias_table(self.rel_embed.data_ptr(), pl["table"].data_ptr(), Tmax, geo.heads,
                                                geo.num_buckets, geo.max_bucket_distance, st), "ser_wavlm_bias_table")
                 ar["table_T"] = Tmax
-        ar["plan"] = (lengths, pl)
+        ar["plan"] = pl
         return pl
 
     # ------------------------------------------------------------------ forward
@@ -1482,12 +1449,8 @@ class WhisperEncoder(_WaveIO, _EncoderBase):
             self._cache[(slot, len(lengths))] = pl      # re-insert: the dict is kept in least-recently-USED order, the hot
             #                                             full-batch plans of the pipeline slots are never the ones evicted
         if pl["lengths"] != lengths:
-            if pl["offs_evt"] is not None:
-                pl["offs_evt"].synchronize()
-            pl["offs_host"].numpy()[:] = np.concatenate([[0], np.cumsum(lengths)])
-            pl["sample_offs"].copy_(pl["offs_host"], non_blocking=True)
-            pl["offs_evt"] = torch.cuda.Event()
-            pl["offs_evt"].record()
+            pl["sample_offs"] = pl["tab"].begin().put64(np.concatenate([[0], np.cumsum(lengths)]))
+            pl["tab"].send()
             pl["lengths"] = lengths
         return pl
 
@@ -1500,9 +1463,7 @@ class WhisperEncoder(_WaveIO, _EncoderBase):
             raise ValueError("max_source_positions must be 1500 (3000 mel frames / 2)")
         Tp = T1 + 2
         M = B * T2
-        pl = dict(B=B, M=M, lengths=None, offs_evt=None)
-        pl["offs_host"] = torch.empty(B + 1, dtype=torch.int64).pin_memory()
-        pl["sample_offs"] = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        pl = dict(B=B, M=M, lengths=None, tab=TableBlob(B, 1, dev))
         pl["mel"] = torch.empty((B, nm, T1), dtype=torch.float32, device=dev)
         ws = lib.ser_workspace_bytes(_lib.WS_LOGMEL, B, 0, 0, 0, self.stem_mode)
         pl["work"] = torch.empty(ws, dtype=torch.uint8, device=dev)
@@ -1851,6 +1812,13 @@ class _HeadBase:
         self.trace.append((name, e0, e1))
 
 
+def _head_offs(tab: TableBlob, frame_offs) -> torch.Tensor:
+    """the frame offsets of a batch that came without them on the device, through the slot's blob"""
+    offs = tab.begin().put32(frame_offs)
+    tab.send()
+    return offs
+
+
 class PoolHead(_HeadBase):
     """The organiser baseline's utterance-level tail on the device (benchmark/train_eval_files/eval_cat_ser.py:164-177):
     ``last_hidden_state`` -> AttentiveStatisticsPooling -> EmotionRegression -> ``[B, n_out]`` logits, so a waveform -> prediction run
@@ -1895,8 +1863,7 @@ class PoolHead(_HeadBase):
                     scores=torch.empty(M, dtype=torch.float32, device=dev),
                     pooled=torch.empty((B, 2 * D), dtype=torch.float32, device=dev),
                     hidden=torch.empty((B, self.H), dtype=torch.float32, device=dev),
-                    out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
-                    offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
+                    out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev), tab=TableBlob(B, 1, dev))
 
     def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
         """``[B, n_out]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``).  The range
@@ -1909,10 +1876,7 @@ class PoolHead(_HeadBase):
             raise ValueError("hidden states do not match the head's width")
         bf = self._bufs.fit(slot, M=M, B=B)
         st = _stream()
-        offs = hs.frame_offs_dev
-        if offs is None:
-            offs = bf["offs"][: B + 1]
-            offs.copy_(torch.tensor(hs.frame_offs, dtype=torch.int32))
+        offs = hs.frame_offs_dev if hs.frame_offs_dev is not None else _head_offs(bf["tab"], hs.frame_offs)
         xa = bf["xa"].first_rows(M)
         flag = hs.range_flag.data_ptr() if (hs.range_flag is not None and self.op_mode == _lib.MODE_FP16X) else None
         self._step("pack", lambda: check(lib.ser_pack_rows_flagged(x.data_ptr(), D, 1, M, D, 0, xa.ptr, D, xa.plane_stride, self.op_mode,
@@ -1966,8 +1930,7 @@ class ClassifierHead(_HeadBase):
         B, dev = cap["B"], self.device
         return dict(work=torch.empty(cap["work"], dtype=torch.float64, device=dev),
                     pooled=torch.empty((B, self.D), dtype=torch.float32, device=dev),
-                    out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev),
-                    offs=torch.empty(B + 1, dtype=torch.int32, device=dev))
+                    out=torch.empty((B, self.n_out), dtype=torch.float32, device=dev), tab=TableBlob(B, 1, dev))
 
     def forward(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
         """``[B, num_labels]`` fp32 logits on the device (a view of the slot's buffer: valid until the slot's next ``forward``);
@@ -1984,10 +1947,7 @@ class ClassifierHead(_HeadBase):
         chunks = -(-max_frames // _lib.LAYER_POOL_FC)
         bf = self._bufs.fit(slot, B=B, work=B * chunks * self.D)
         st = _stream()
-        offs = hs.frame_offs_dev
-        if offs is None:
-            offs = bf["offs"][: B + 1]
-            offs.copy_(torch.tensor(hs.frame_offs, dtype=torch.int32))
+        offs = hs.frame_offs_dev if hs.frame_offs_dev is not None else _head_offs(bf["tab"], hs.frame_offs)
         offs_host = (C.c_int32 * (B + 1))(*hs.frame_offs)
         first = s if self.weighted else s[-1:]
         p = _lib.LayerPoolArgs()
@@ -2144,12 +2104,11 @@ class _FusionBase(_HeadBase):
         side = []
         for M, D in zip(Ms, self.dims_in):
             sb = dict(xa=act(M, D), proj=f(M, h), sa=act(M, h), gx=f(M, 6 * h), gh=f(M, E), gha=act(M, E), q=f(M, E), kv=f(M, 2 * E * (n - 1)),
-                      ctx=[act(M, E) for _ in range(n - 1)], att=f(M, E), scores=f(M), offs=torch.empty(B + 1, dtype=torch.int32, device=dev),
-                      src=torch.empty(B, dtype=torch.int32, device=dev))
+                      ctx=[act(M, E) for _ in range(n - 1)], att=f(M, E), scores=f(M))
             if n > 2:
                 sb["att_first"] = f(M, E)                         # the first out-projection of a module with two key sides (distinct from `att`)
             side.append(sb)
-        return dict(side=side, pooled=f(B, n * E), xn=f(B, n * E), hidden=f(B, self.h1), out=f(B, self.n_out),
+        return dict(side=side, tab=TableBlob(B, 2 * n, dev), pooled=f(B, n * E), xn=f(B, n * E), hidden=f(B, self.h1), out=f(B, self.n_out),
                     err=torch.zeros(1, dtype=torch.int32, device=dev), flag=torch.zeros(1, dtype=torch.int32, device=dev),
                     work=torch.zeros(max(self.work_bytes, 16), dtype=torch.uint8, device=dev))
 
@@ -2187,14 +2146,16 @@ class _FusionBase(_HeadBase):
         host._flag = flag
         bf["err"].zero_()
         maxf = [max(b - a for a, b in zip(o[:-1], o[1:])) for o in offs]
+        tab = bf["tab"].begin()
+        for sb, o, x in zip(bf["side"], offs, xs):                # per side: its offsets, and its source rows where it is a RowSource
+            sb["offs"], sb["src"] = tab.put32(o), tab.put32(x.src_offs if isinstance(x, RowSource) else ())
+        tab.send()
         for i in range(n):
             sb, w, x, M = bf["side"][i], self.mod[i], xs[i], Ms[i]
-            sb["offs"][: B + 1].copy_(torch.tensor(offs[i], dtype=torch.int32))
             D = self.dims_in[i]
             xa, sa = sb["xa"].first_rows(M), sb["sa"].first_rows(M)
             tag = names[i]
             if isinstance(x, RowSource):                          # the utterances' rows where they lie: one ragged gather into the same operand copy
-                sb["src"][:B].copy_(torch.tensor(x.src_offs, dtype=torch.int32))
                 g = _lib.SelectRowsArgs()
                 for k, s_ in enumerate(x.states):
                     g.src[k] = s_.data_ptr()
@@ -2687,15 +2648,6 @@ class _PreLnStack(_LaunchHost):
                 fc1=self._linear(*lw["fc1"], name=p + ".ffn.ffn_1.weight"), fc2=self._linear(*lw["fc2"], name=p + ".ffn.ffn_2.weight")))
         return out
 
-    @staticmethod
-    def _halo_maps(frame_offs_dev, base, offs, B: int, M: int, half: int, D: int, halo_rowmap, fc1_rowoff, st: int) -> None:
-        """zero-halo'd copy of FC1's input: [half zero rows][utt 0][half zero rows][utt 1] ... [half zero rows]; frame t of utterance b sits
-        at row half (b + 1) + offs[b] + t, and its k taps start ``half`` rows earlier"""
-        starts = np.array([half * (b + 1) + offs[b] for b in range(B)], dtype=np.int64)
-        base[:, :B].copy_(torch.from_numpy(np.stack([starts, starts - half])))
-        check(lib.ser_ragged_index(frame_offs_dev.data_ptr(), base[0].data_ptr(), B, 1, 1, 1, halo_rowmap.data_ptr(), M, st), "ser_ragged_index")
-        check(lib.ser_ragged_index(frame_offs_dev.data_ptr(), base[1].data_ptr(), B, 1, D, 8, fc1_rowoff.data_ptr(), M, st), "ser_ragged_index")
-
 
 class ProsodyEncoder(_WaveIO, _PreLnStack):
     """The prosody stream of the reference's three-stream heads (preprocessing/preprocess_ns3_prosody.py) on libserhip: NS3 log-mel +
@@ -2738,9 +2690,7 @@ class ProsodyEncoder(_WaveIO, _PreLnStack):
         ar["halo"] = self._new_act(M + (sp.kernel // 2) * (B + 1), D, zero=True)
         ar["halo_rowmap"] = torch.empty(M, dtype=torch.int32, device=dev)
         ar["fc1_rowoff"] = torch.empty(M, dtype=torch.int32, device=dev)
-        ar["sample_offs"] = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        ar["frame_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
-        ar["base"] = torch.empty((2, B), dtype=torch.int64, device=dev)
+        ar["tab"] = TableBlob(B, 4, dev)                        # sample_offs | frame_offs (int32) | halo base | FC1 tap base
         ar["err"] = torch.zeros(1, dtype=torch.int32, device=dev)
         if self.fp16_planes:
             ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -2758,16 +2708,14 @@ class ProsodyEncoder(_WaveIO, _PreLnStack):
         ar = self._arenas.fit(slot, M=M, B=B)
         if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
             return ar["plan"]
-        st, D = _stream(), self.spec.hidden
-        ar["sample_offs"][: B + 1].copy_(torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))
-        ar["frame_offs_all"][: B + 1].copy_(torch.from_numpy(offs.astype(np.int32)))
-        fo = ar["frame_offs_all"]
-        self._halo_maps(fo, ar["base"], offs, B, M, half, D, ar["halo_rowmap"], ar["fc1_rowoff"], st)
-        if ar["plan"] is not None:
-            ar["halo"].t.zero_()                                # the halo rows sit elsewhere than in the previous batch
+        tab = ar["tab"].begin()
+        so, fo = tab.put64(np.concatenate([[0], np.cumsum(lengths)])), tab.put32(offs)
+        _, halo_index = _halo_layout(tab, offs, fo, half, self.spec.hidden, ar["halo_rowmap"], [ar["fc1_rowoff"]], ar["halo"])
+        tab.send()
+        halo_index(_stream(), ar["plan"] is not None)
         pl = dict(ar)
         pl.update(lengths=lengths, B=Sz(B, "B"), M=Sz(M, "M"), Tmax=Sz(Tmax, "Tmax"), sizes=dict(B=B, M=M, Tmax=Tmax),
-                  frame_offs=fo[: B + 1], frame_offs_host=[int(v) for v in offs])
+                  sample_offs=so, frame_offs=fo, frame_offs_host=[int(v) for v in offs])
         ar["plan"] = pl
         return pl
 
@@ -2899,13 +2847,12 @@ class SpeakerProsodyEncoder(_WaveIO, _PreLnStack):
         rows = cap["M0"]
         for l, C in enumerate(sp.channels):
             last = l == len(sp.strides)
-            lv = dict(cap=rows, xa=f32(rows, C), offs=i32(B + 1), offs64=torch.empty(B + 1, dtype=torch.int64, device=dev))
+            lv = dict(cap=rows, xa=f32(rows, C))
             if not last:
                 lv["xb"] = f32(rows, C)
             if C > 32:                                                   # a wide level: operand copies for ser_gemm
                 lv["halo"] = self._new_act(rows + self.halo * (B + 1), C, zero=True)
                 lv["rowmap"] = i32(rows)
-                lv["base"] = torch.empty((5, B), dtype=torch.int64, device=dev)
                 if last:
                     lv["rowoff_k3"] = i32(rows)
                 else:
@@ -2921,7 +2868,8 @@ class SpeakerProsodyEncoder(_WaveIO, _PreLnStack):
         ar["xa"], ar["ctx"], ar["qkv"], ar["ffn"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, 3 * D), self._new_act(M, F)
         ar["halo"] = self._new_act(M + (ts.kernel // 2) * (B + 1), D, zero=True)
         ar["halo_rowmap"], ar["fc1_rowoff"] = i32(M), i32(M)
-        ar["base"] = torch.empty((2, B), dtype=torch.int64, device=dev)
+        # per level offs (int32) and offs64; a wide level's halo base and tap bases (3 + the downsampling's, or 1); the timbre layers' two
+        ar["tab"] = TableBlob(B, sum(2 + (0 if C <= 32 else 2 if l == len(sp.strides) else 5) for l, C in enumerate(sp.channels)) + 2, dev)
         return ar
 
     def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
@@ -2934,35 +2882,28 @@ class SpeakerProsodyEncoder(_WaveIO, _PreLnStack):
         if old is not None and old["ppl"] is ppl:
             return old
         assert int(offs[-1, -1]) == int(ppl["M"]) and lens[:, -1].tolist() == np.diff(ppl["frame_offs_host"]).tolist()
-        st, H = _stream(), self.halo
-        ridx = lambda row_offs, base, step, mult, div, out, total: check(
-            lib.ser_ragged_index(row_offs.data_ptr(), base.data_ptr(), B, step, mult, div, out.data_ptr(), total, st), "ser_ragged_index")
-        for l, lv in enumerate(ar["lv"]):                                # every level's offsets first: a level's row maps read the next one's
-            lv["offs"][: B + 1].copy_(torch.from_numpy(offs[l].astype(np.int32)))
-            lv["offs64"][: B + 1].copy_(torch.from_numpy(offs[l]))
+        st, ts, tab = _stream(), sp.timbre, ar["tab"].begin()
+        for l, lv in enumerate(ar["lv"]):
+            lv["offs"], lv["offs64"] = tab.put32(offs[l]), tab.put64(offs[l])
+        index, downs = [], []
         for l, lv in enumerate(ar["lv"]):
             if "halo" not in lv:
                 continue
-            # zero-halo'd copy of a wide level: [H zero rows][utt 0][H zero rows][utt 1] ... ; row t of utterance b sits at H (b + 1) + offs[b] + t
-            C, M_l = sp.channels[l], int(offs[l, -1])
-            starts = np.array([H * (b + 1) + offs[l, b] for b in range(B)], dtype=np.int64)
-            if "rowoff" in lv:
-                s, p = sp.strides[l], self.levels[l]["pad"]
-                lv["base"][:, :B].copy_(torch.from_numpy(np.stack([starts, starts - 3, starts - 9, starts - 27, starts - p])))
-                for j in range(3):                                       # the dilated k = 7 convolutions start 3 d rows earlier
-                    ridx(lv["offs"], lv["base"][1 + j], 1, C, 8, lv["rowoff"][j], M_l)
-                ridx(ar["lv"][l + 1]["offs"], lv["base"][4], s, C, 8, lv["down_rowoff"], int(offs[l + 1, -1]))
-            else:
-                lv["base"][:2, :B].copy_(torch.from_numpy(np.stack([starts, starts - 1])))
-                ridx(lv["offs"], lv["base"][1], 1, C, 8, lv["rowoff_k3"], M_l)
-            ridx(lv["offs"], lv["base"][0], 1, 1, 1, lv["rowmap"], M_l)
-            if old is not None:
-                lv["halo"].t.zero_()                                     # the halo rows sit elsewhere than in the previous batch
-        ts = sp.timbre
-        self._halo_maps(ppl["frame_offs_all"], ar["base"], ppl["frame_offs_host"], B, int(ppl["M"]), ts.kernel // 2, ts.hidden,
-                        ar["halo_rowmap"], ar["fc1_rowoff"], st)
-        if old is not None:
-            ar["halo"].t.zero_()
+            # a wide level's halo'd copy: the dilated k = 7 convolutions start 3 d rows earlier, the last level's k = 3 one row earlier
+            wide = "rowoff" in lv
+            starts, ix = _halo_layout(tab, offs[l], lv["offs"], self.halo, sp.channels[l], lv["rowmap"],
+                                      lv["rowoff"] if wide else [lv["rowoff_k3"]], lv["halo"], taps=(3, 9, 27) if wide else (1,))
+            index.append(ix)
+            if wide:                                                     # the strided convolution into the next level: that level's rows
+                downs.append((l, tab.put64(starts - self.levels[l]["pad"])))
+        index.append(_halo_layout(tab, ppl["frame_offs_host"], ppl["frame_offs"], ts.kernel // 2, ts.hidden, ar["halo_rowmap"],
+                                  [ar["fc1_rowoff"]], ar["halo"])[1])
+        tab.send()
+        for ix in index:
+            ix(st, old is not None)
+        for l, base in downs:
+            check(lib.ser_ragged_index(ar["lv"][l + 1]["offs"].data_ptr(), base.data_ptr(), B, sp.strides[l], sp.channels[l], 8,
+                                       ar["lv"][l]["down_rowoff"].data_ptr(), int(offs[l + 1, -1]), st), "ser_ragged_index")
         pl = dict(ar)
         sizes = dict(ppl["sizes"])
         for l in range(len(sp.channels)):
@@ -3148,9 +3089,7 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         ar["f1"], ar["pw"], ar["qe"] = f32(M, F), f32(M, 2 * D), f32(M * H, self.qe_ld)
         ar["xa"], ar["ctx"], ar["cv"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
         ar["qkv"], ar["ffn"] = self._new_act(M, 3 * D), self._new_act(M, F)
-        ar["sample_offs"] = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        ar["mel_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
-        ar["frame_offs_all"] = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        ar["tab"] = TableBlob(B, 3, dev)                                     # sample_offs | mel_offs (int32) | frame_offs (int32)
         if self.fp16_planes:
             ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
         return ar
@@ -3169,13 +3108,13 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         ar = self._arenas.fit(slot, M=M, B=B, F=int(moffs[-1]))
         if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
             return ar["plan"]
-        ar["sample_offs"][: B + 1].copy_(torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))
-        ar["mel_offs_all"][: B + 1].copy_(torch.from_numpy(moffs.astype(np.int32)))
-        ar["frame_offs_all"][: B + 1].copy_(torch.from_numpy(offs.astype(np.int32)))
+        tab = ar["tab"].begin()
+        so, mo, fo = tab.put64(np.concatenate([[0], np.cumsum(lengths)])), tab.put32(moffs), tab.put32(offs)
+        tab.send()
         pl = dict(ar)
         pl.update(lengths=lengths, B=Sz(B, "B"), M=Sz(M, "M"), MH=Sz(M * self.geo.heads, "MH"), Tmax=Sz(Tmax, "Tmax"), Fmax=Sz(Fmax, "Fmax"),
-                  sizes=dict(B=B, M=M, MH=M * self.geo.heads, Tmax=Tmax, Fmax=Fmax), frame_offs=ar["frame_offs_all"][: B + 1],
-                  mel_offs=ar["mel_offs_all"][: B + 1], frame_offs_host=[int(v) for v in offs], states=ar["states"][:, :M])
+                  sizes=dict(B=B, M=M, MH=M * self.geo.heads, Tmax=Tmax, Fmax=Fmax), sample_offs=so, frame_offs=fo,
+                  mel_offs=mo, frame_offs_host=[int(v) for v in offs], states=ar["states"][:, :M])
         ar["plan"] = pl
         return pl
 

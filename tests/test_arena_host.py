@@ -56,3 +56,25 @@ def test_a_key_met_for_the_first_time_counts_as_capacity_zero():
     assert grown is first and len(made) == 1
     grown = ar.fit(0, B=1, work=6)
     assert grown is not first and grown["cap"] == dict(B=2, work=6) and made[-1] == dict(B=2, work=6)
+
+
+# ---------------------------------------------------------------------------------------------------------- the table blob's layout
+@pytest.mark.parametrize("cap_b", [1, 2, 17])
+def test_table_layout_regions_are_disjoint_aligned_and_independent_of_the_batch(cap_b):
+    from interspeech_ser_amd.arena import TableLayout
+    lay = TableLayout(cap_b, 5)
+    assert lay.region == cap_b + 2 and lay.words == 5 * (cap_b + 2)
+    spans = []
+    for r in range(5):
+        w = lay.offset(r, cap_b + 1)                          # a 64-bit table of B + 1 entries fits ...
+        e = lay.offset(r, 2 * cap_b + 2, 2)                   # ... and so does a 32-bit table of 2 B + 2 entries
+        assert e == 2 * w                                     # an int32 table starts on its region's first word: 8-byte aligned
+        spans.append((w, w + max(cap_b + 1, (2 * cap_b + 2 + 1) // 2)))
+        for b in range(1, cap_b + 1):                         # the batch's own B moves nothing
+            assert lay.offset(r, b + 1) == w and lay.offset(r, b, 2) == e and lay.offset(r, 0) == w
+    assert spans[0][0] == 0 and spans[-1][1] <= lay.words
+    assert all(a[1] <= b[0] for a, b in zip(spans[:-1], spans[1:]))          # no region reaches into the next
+    assert lay.offset(0, cap_b + 2) == 0 and lay.offset(0, 2 * cap_b + 4, 2) == 0
+    for bad in ((0, cap_b + 3, 1), (0, 2 * cap_b + 5, 2), (5, 1, 1), (-1, 1, 1)):
+        with pytest.raises(ValueError):
+            lay.offset(*bad)
