@@ -581,6 +581,72 @@ typedef struct ser_cls_tail_args {
 } ser_cls_tail_args;
 int ser_cls_tail_v(const ser_cls_tail_args* args, void* stream);
 
+/* a30 (added under ABI 18: new entry points only)  The x-vector head of the hub's speaker-verification checkpoints (HF
+ * WavLMForXVector.forward; the wav2vec2 / data2vec-audio / w2v-BERT classes are the same text), one utterance of T frames:
+ *   x = sum_l softmax(layer_weights)[l] hs[l]  (use_weighted_layer_sum; else the last state)                      [T, D]
+ *   x = projector(x)                                                                                               [T, tdnn_dim[0]]
+ *   TDNN layer i:  y[t] = ReLU(b + sum_{j < k_i} W_j x[t + j d_i]),  t < T_i = T_{i-1} - d_i (k_i - 1);  kernel.weight [out, k in], tap-major
+ *   stats = cat(mean_t y, std_t y) over the T' rows of the last layer, std unbiased (divided by T' - 1)
+ *   embeddings = feature_extractor(stats);  logits = classifier(embeddings)
+ * A ReLU follows the projector's successors, so projector and mean do not commute: the [T, D] mix is formed.  The projector and every TDNN
+ * layer are ser_gemm launches (a layer: kc = its padded input width, ldj = d_i * the operand pitch, a_rowoff from ser_ragged_index over
+ * the per-layer offsets, so no window crosses an utterance; ser_act_rows_v(relu = 1) makes the next operand).  The three launchers below
+ * are the rest.  None is a command-list op; none uses a float atomic; every sum runs in an order fixed by the utterance alone.
+ *
+ * ser_layer_mix_v: out[m, d] = sum_l w[l] s[l, m, d] over n_states fp32 planes [rows, lds] (state l at s + l * state_stride floats), each
+ * element ONE float64 sum -- products rounded to float64, added in ascending l, no fused multiply-add -- rounded once to fp32; that fp32
+ * value goes to the operand planes out_act in `mode` (SER_MODE_BF16 / FP32X / FP16 / FP16X) and, when out_f32 is not NULL, to out_f32
+ * [rows, ldo_f32].  w: float64 [n_states] on the device; n_states = 1 with w = {1.0} is the form without the weighted sum.  Wave per row;
+ * D % 4 == 0, D <= 2048, pitches multiples of 4, s 16-byte aligned.  range_flag: the fp16 range guard, reported as ser_act_rows_v does;
+ * may be NULL.  Refused: -1 null pointer, -2 sizes, -3 pitches / alignment, -4 mode. */
+typedef struct ser_layer_mix_args {
+    const float* s; int64_t state_stride; int64_t lds;
+    const double* w;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    float* out_f32; int64_t ldo_f32;
+    uint32_t* range_flag;
+    int32_t n_states, mode, rows, D;
+} ser_layer_mix_args;
+int ser_layer_mix_v(const ser_layer_mix_args* args, void* stream);
+
+/* ser_stat_pool_v: statistics pooling.  Per utterance b with rows r0 = frame_offs[b] .. frame_offs[b+1]-1 (T_b >= 2 of them) of the fp32
+ * rows x [rows, ldx], with relu == 1 read as max(x, 0):
+ *   out[b, d] = mean_t x[r0 + t, d];   out[b, D + d] = sqrt( sum_t (x[r0 + t, d] - mean)^2 / (T_b - 1) )
+ * in float64, one rounding at each store.  The frames are cut into chunks of SER_STAT_POOL_FC counted from the utterance's first row.  One
+ * block per (256-column slab, chunk, utterance) takes the chunk's mean and then, in a second pass over the chunk, its CENTRED second
+ * moment sum_t (x - chunk mean)^2 into work [B, chunks, 2, D]; one thread per (utterance, column) then merges the chunks in ascending
+ * order (Chan et al.: M2 += M2_c + delta^2 n n_c / (n + n_c)).  No sum of raw squares is ever formed, so a column whose mean is 10^5
+ * times its deviation keeps its std.  Columns beyond D of x (ldx > D: the zero padding of a GEMM's output width) are never read.
+ * frame_offs int32 [B + 1] on the device and the same numbers at frame_offs_host, which the launcher validates.  out fp32 [B, ldo],
+ * ldo >= 2 D.  Refused before the launch: -1 null pointer; -2 D % 4 != 0, relu not 0 / 1, an utterance with fewer than 2 rows (named by
+ * its index), offsets outside [0, rows] or descending, an utterance longer than max_frames, max_frames > rows, B > 65535, ldx not a
+ * multiple of 4 or < D, x not 16-byte aligned, a workspace smaller than B * ceil(max_frames / SER_STAT_POOL_FC) * 2 * D doubles. */
+#define SER_STAT_POOL_FC 32
+typedef struct ser_stat_pool_args {
+    const float* x; int64_t ldx;
+    const int32_t* frame_offs;
+    const int32_t* frame_offs_host;
+    double* work; int64_t work_elems;
+    float* out; int64_t ldo;
+    int32_t B, D, rows, max_frames, relu, reserved0;
+} ser_stat_pool_args;
+int ser_stat_pool_v(const ser_stat_pool_args* args, void* stream);
+
+/* ser_xvec_tail_v: ser_cls_tail_v's kernel with the intermediate written too:
+ *   emb[b] = fp32(F stats[b] + bf)   (HF's `embeddings`; rounded ONCE, and the classifier reads that fp32 value, as HF's does)
+ *   logits[b] = C emb[b] + bc
+ * stats [B, lds], F [dim, D], bf [dim], C [n_labels, dim], bc [n_labels], emb [B, lde], logits [B, ldo], all fp32; sums in float64 in
+ * ser_cls_tail_v's order.  D % 4 == 0, 1 <= dim <= 2048, 1 <= n_labels <= 2048, stats and F 16-byte aligned, lds a multiple of 4 and
+ * >= D, lde >= dim, ldo >= n_labels, B <= 65535. */
+typedef struct ser_xvec_tail_args {
+    const float* stats; int64_t lds;
+    const float* F; const float* bf; const float* C; const float* bc;
+    float* emb; int64_t lde;
+    float* logits; int64_t ldo;
+    int32_t B, D, dim, n_labels;
+} ser_xvec_tail_args;
+int ser_xvec_tail_v(const ser_xvec_tail_args* args, void* stream);
+
 /* a23 (added under ABI 18: new entry points only)  The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334,
  * MultiModalEmotionClassifier) on packed ragged batches: every utterance alone, as the reference's evaluation runs it (batch_size = 1,
  * bin/eval_cat_bimodal_lazy_1head.py:292) -- no pad frame enters the recurrence, the attention or a pooling softmax.  None of the four is a
@@ -1039,6 +1105,9 @@ int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void* stream);
  *     torch's zip archive format. */
 int64_t ser_wav_read_f32(const char* path, float* host_dst, int64_t capacity, int32_t* sample_rate, int32_t* channels);
 int     ser_pt_write_f32(const char* path, const float* host_data, int64_t rows, int64_t cols);
+/* ser_pt_write_f32_vec (added under ABI 18: a new entry point only): the same archive through the same writer for a 1-D [n] float32 tensor,
+ * what torch.save(embeddings[0], "<utt>.pt") leaves of one utterance's x-vector (a30). */
+int     ser_pt_write_f32_vec(const char* path, const float* host_data, int64_t n);
 
 #define SER_WS_LOGMEL 1
 #define SER_WS_WAVE_FRAMES 2

@@ -199,6 +199,34 @@ class ClsTailArgs(C.Structure):
     ]
 
 
+class LayerMixArgs(C.Structure):
+    """Mirror of ``ser_layer_mix_args``."""
+    _fields_ = [
+        ("s", c_void_p), ("state_stride", c_i64), ("lds", c_i64), ("w", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("out_f32", c_void_p), ("ldo_f32", c_i64),
+        ("range_flag", c_void_p),
+        ("n_states", C.c_int32), ("mode", C.c_int32), ("rows", C.c_int32), ("D", C.c_int32),
+    ]
+
+
+class StatPoolArgs(C.Structure):
+    """Mirror of ``ser_stat_pool_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64), ("frame_offs", c_void_p), ("frame_offs_host", c_void_p),
+        ("work", c_void_p), ("work_elems", c_i64), ("out", c_void_p), ("ldo", c_i64),
+        ("B", C.c_int32), ("D", C.c_int32), ("rows", C.c_int32), ("max_frames", C.c_int32), ("relu", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class XvecTailArgs(C.Structure):
+    """Mirror of ``ser_xvec_tail_args``."""
+    _fields_ = [
+        ("stats", c_void_p), ("lds", c_i64), ("F", c_void_p), ("bf", c_void_p), ("C", c_void_p), ("bc", c_void_p),
+        ("emb", c_void_p), ("lde", c_i64), ("logits", c_void_p), ("ldo", c_i64),
+        ("B", C.c_int32), ("D", C.c_int32), ("dim", C.c_int32), ("n_labels", C.c_int32),
+    ]
+
+
 class GruArgs(C.Structure):
     """Mirror of ``ser_gru_args``."""
     _fields_ = [
@@ -392,7 +420,8 @@ class SwishRowsArgs(C.Structure):
 
 
 LAYER_POOL_FC = 32              # SER_LAYER_POOL_FC: frames per chunk of ser_layer_pool_v
-CLS_TAIL_MAX = 2048             # widest projector / most labels of ser_cls_tail_v
+CLS_TAIL_MAX = 2048             # widest projector / most labels of ser_cls_tail_v (and widest embedding / most labels of ser_xvec_tail_v)
+STAT_POOL_FC = 32               # SER_STAT_POOL_FC: frames per chunk of ser_stat_pool_v
 CCONV_TILE = 8                  # SER_CCONV_TILE: rows per block of ser_conformer_conv_v
 CODEC_TILE = 128                # SER_CODEC_TILE: output rows per block of ser_codec_unit_v
 FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
@@ -430,6 +459,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_snake_args": SnakeArgs, "ser_fbank_args": FbankArgs, "ser_relkey_table_args": RelkeyTableArgs,
                   "ser_attention_rk_args": AttentionRkArgs, "ser_conformer_conv_args": ConformerConvArgs,
                   "ser_swish_rows_args": SwishRowsArgs, "ser_layer_pool_args": LayerPoolArgs, "ser_cls_tail_args": ClsTailArgs,
+                  "ser_layer_mix_args": LayerMixArgs, "ser_stat_pool_args": StatPoolArgs, "ser_xvec_tail_args": XvecTailArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -455,6 +485,9 @@ _SIGNATURES = {
     "ser_mlp_head_v": (c_int, [c_void_p, c_void_p]),
     "ser_layer_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_cls_tail_v": (c_int, [c_void_p, c_void_p]),
+    "ser_layer_mix_v": (c_int, [c_void_p, c_void_p]),
+    "ser_stat_pool_v": (c_int, [c_void_p, c_void_p]),
+    "ser_xvec_tail_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),
@@ -508,6 +541,7 @@ _SIGNATURES = {
     "ser_workspace_bytes": (C.c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ser_wav_read_f32": (c_i64, [C.c_char_p, c_void_p, c_i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ser_pt_write_f32": (c_int, [C.c_char_p, c_void_p, c_i64, c_i64]),
+    "ser_pt_write_f32_vec": (c_int, [C.c_char_p, c_void_p, c_i64]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -646,3 +646,107 @@ def resolve_classifier(ssl_type: str, checkpoint: str = "") -> Optional[Classifi
     except (OSError, ValueError) as e:
         raise OSError(f"cannot read {path}: {e}")
     return ClassifierSpec.from_config(cfg, name=ssl_type)
+
+
+# The hub classes that share the x-vector head (HF *ForXVector, what ``AutoModelForAudioXVector`` loads): optional softmax-weighted sum of
+# the hidden states -> projector -> ReLU TDNN layers -> statistics pooling -> feature_extractor -> classifier (engine.XVectorHead).
+XVECTOR_ARCHITECTURES = ("Wav2Vec2ForXVector", "WavLMForXVector", "Data2VecAudioForXVector", "Wav2Vec2BertForXVector")
+# ... and the two whose encoders this path does not build
+XVECTOR_UNBUILT_ARCHITECTURES = ("UniSpeechSatForXVector", "Wav2Vec2ConformerForXVector")
+
+
+@dataclass(frozen=True)
+class TdnnLayout:
+    """Where the rows of a ragged batch lie at every level of a TDNN stack: ``offs[0]`` the [B + 1] input frame offsets, ``offs[i]`` those
+    of layer i's packed output rows (T_i = T_{i-1} - d_i (k_i - 1) per utterance)."""
+    offs: Tuple[Tuple[int, ...], ...]
+    kernel: Tuple[int, ...]
+    dilation: Tuple[int, ...]
+
+    def first_rows(self, i: int):
+        """numpy int64 [rows of layer i]: the input row (in layer i - 1's packed rows) under tap 0 of every output row of layer i
+        (1 <= i <= len(kernel)); tap j reads ``dilation[i - 1] * j`` rows further.  What ser_ragged_index builds on the device."""
+        import numpy as np
+        src, dst = self.offs[i - 1], self.offs[i]
+        return np.concatenate([src[b] + np.arange(dst[b + 1] - dst[b], dtype=np.int64) for b in range(len(dst) - 1)]
+                              + [np.zeros(0, dtype=np.int64)])
+
+
+@dataclass(frozen=True)
+class XVectorSpec:
+    """What ``AutoModelForAudioXVector`` reads from ``config.json`` for that head."""
+    tdnn_dim: Tuple[int, ...]
+    tdnn_kernel: Tuple[int, ...]
+    tdnn_dilation: Tuple[int, ...]
+    xvector_output_dim: int
+    use_weighted_layer_sum: bool
+    num_labels: int = 2                # sizes ``objective.weight`` (training) only: HF's classifier is Linear(xvector_output_dim, xvector_output_dim)
+    architecture: str = ""
+
+    @property
+    def context(self) -> int:
+        """frames the TDNN stack consumes: T' = T - context"""
+        return sum(d * (k - 1) for k, d in zip(self.tdnn_kernel, self.tdnn_dilation))
+
+    @property
+    def min_frames(self) -> int:
+        """fewest encoder frames with T' >= 2, what the unbiased std needs"""
+        return self.context + 2
+
+    @staticmethod
+    def from_config(cfg: dict, name: str = "") -> Optional["XVectorSpec"]:
+        """The spec of a snapshot whose ``architectures[0]`` is one of ``XVECTOR_ARCHITECTURES``, else None.  ``OSError``: an x-vector
+        class over an encoder that is not built, ``add_adapter``, TDNN lists of unequal length."""
+        arch = cfg.get("architectures") or []
+        arch = arch[0] if isinstance(arch, (list, tuple)) and arch else (arch if isinstance(arch, str) else "")
+        name = name or str(cfg.get("_name_or_path", "")) or arch
+        if arch in XVECTOR_UNBUILT_ARCHITECTURES:
+            raise OSError(f"{name}: {arch} is not supported (its encoder is not built; the x-vector head runs behind "
+                          + ", ".join(XVECTOR_ARCHITECTURES) + ")")
+        if arch not in XVECTOR_ARCHITECTURES:
+            return None
+        if cfg.get("add_adapter", False):
+            raise OSError(f"{name}: {arch} with add_adapter=True (an adapter stack after the encoder) is not supported")
+        dim = tuple(int(v) for v in cfg.get("tdnn_dim", (512, 512, 512, 512, 1500)))
+        kernel = tuple(int(v) for v in cfg.get("tdnn_kernel", (5, 3, 3, 1, 1)))
+        dilation = tuple(int(v) for v in cfg.get("tdnn_dilation", (1, 2, 3, 1, 1)))
+        if not (len(dim) == len(kernel) == len(dilation)) or not dim:
+            raise OSError(f"{name}: tdnn_dim, tdnn_kernel and tdnn_dilation have {len(dim)}, {len(kernel)} and {len(dilation)} entries "
+                          "(one per TDNN layer each)")
+        if min(dim) < 1 or min(kernel) < 1 or min(dilation) < 1:
+            raise OSError(f"{name}: tdnn_dim {dim}, tdnn_kernel {kernel} and tdnn_dilation {dilation} must be positive")
+        id2label = cfg.get("id2label")
+        n = len(id2label) if id2label else int(cfg.get("num_labels", 2))
+        return XVectorSpec(tdnn_dim=dim, tdnn_kernel=kernel, tdnn_dilation=dilation, xvector_output_dim=int(cfg.get("xvector_output_dim", 512)),
+                           use_weighted_layer_sum=bool(cfg.get("use_weighted_layer_sum", False)), num_labels=n, architecture=arch)
+
+    def layout(self, frame_offs) -> TdnnLayout:
+        """The per-layer packed offsets of a batch whose utterance b owns encoder rows ``frame_offs[b] .. frame_offs[b + 1] - 1``.
+        ``ValueError`` naming the first utterance (by index) that keeps fewer than two rows: it has no unbiased std."""
+        offs = [tuple(int(o) for o in frame_offs)]
+        frames = [offs[0][b + 1] - offs[0][b] for b in range(len(offs[0]) - 1)]
+        for b, t in enumerate(frames):
+            if t < self.min_frames:
+                raise ValueError(f"utterance {b}: {t} encoder frames leave {max(t - self.context, 0)} TDNN output rows; the unbiased std of "
+                                 f"the statistics pooling needs 2 (at least {self.min_frames} frames)")
+        for k, d in zip(self.tdnn_kernel, self.tdnn_dilation):
+            frames = [t - d * (k - 1) for t in frames]
+            acc = [0]
+            for t in frames:
+                acc.append(acc[-1] + t)
+            offs.append(tuple(acc))
+        return TdnnLayout(offs=tuple(offs), kernel=self.tdnn_kernel, dilation=self.tdnn_dilation)
+
+
+def resolve_xvector(ssl_type: str, checkpoint: str = "") -> Optional[XVectorSpec]:
+    """``XVectorSpec`` of the ``config.json`` that ``find_config_json`` picks; None when there is no such file or it names another class."""
+    import json
+    path = find_config_json(ssl_type, checkpoint)
+    if not path:
+        return None
+    try:
+        with open(path, "r") as f:
+            cfg = json.load(f)
+    except (OSError, ValueError) as e:
+        raise OSError(f"cannot read {path}: {e}")
+    return XVectorSpec.from_config(cfg, name=ssl_type)

@@ -183,7 +183,8 @@ std::string local_header(const std::string& name, uint32_t crc, uint32_t size, s
     return h;
 }
 
-std::string pickle_f32_matrix(int64_t rows, int64_t cols) {
+// vec: the 1-D tensor [cols] (rows == 1) instead of the matrix [rows, cols]
+std::string pickle_f32_matrix(int64_t rows, int64_t cols, bool vec = false) {
     auto J = [](std::string& s, int64_t v) {                          // BININT (4 bytes): valid for any value < 2^31
         s.push_back('J');
         for (int i = 0; i < 4; ++i) s.push_back((char)((v >> (8 * i)) & 0xff));
@@ -193,17 +194,22 @@ std::string pickle_f32_matrix(int64_t rows, int64_t cols) {
                             "ctorch\nFloatStorage\nq\x02X\x01\x00\x00\x00" "0q\x03X\x03\x00\x00\x00" "cpuq\x04");
     J(p, rows * cols);
     p += SER_LIT("tq\x05QK\x00");
-    J(p, rows); J(p, cols);
-    p += SER_LIT("\x86q\x06");
-    J(p, cols);
-    p += SER_LIT("K\x01\x86q\x07\x89" "ccollections\nOrderedDict\nq\x08)Rq\x09tq\x0aRq\x0b.");
+    if (vec) {
+        J(p, cols);
+        p += SER_LIT("\x85q\x06K\x01\x85q\x07\x89" "ccollections\nOrderedDict\nq\x08)Rq\x09tq\x0aRq\x0b.");
+    } else {
+        J(p, rows); J(p, cols);
+        p += SER_LIT("\x86q\x06");
+        J(p, cols);
+        p += SER_LIT("K\x01\x86q\x07\x89" "ccollections\nOrderedDict\nq\x08)Rq\x09tq\x0aRq\x0b.");
+    }
 #undef SER_LIT
     return p;
 }
 
 }  // namespace
 
-static int pt_write_f32(const char* path, const float* host_data, int64_t rows, int64_t cols) {
+static int pt_write_f32(const char* path, const float* host_data, int64_t rows, int64_t cols, bool vec = false) {
     if (!path || rows < 0 || cols <= 0 || (!host_data && rows > 0)) return ser_fail(-1, "ser_pt_write_f32: bad arguments");
     if (rows >= (1LL << 29) || cols >= (1LL << 29) || rows * cols >= (1LL << 29))       // (each factor first: the product cannot wrap)
         return ser_fail(-2, "ser_pt_write_f32: tensor too large for a 32-bit zip member");
@@ -222,7 +228,7 @@ static int pt_write_f32(const char* path, const float* host_data, int64_t rows, 
     if (dot != std::string::npos && dot > 0) stem = stem.substr(0, dot);
     if (stem.empty()) stem = "archive";
 
-    const std::string pkl = pickle_f32_matrix(rows, cols);
+    const std::string pkl = pickle_f32_matrix(rows, cols, vec);
     struct Part { std::string name; const void* data; size_t size; bool align; };
     const Part parts[4] = {
         {stem + "/data.pkl", pkl.data(), pkl.size(), false},
@@ -266,6 +272,15 @@ static int pt_write_f32(const char* path, const float* host_data, int64_t rows, 
 extern "C" int ser_pt_write_f32(const char* path, const float* host_data, int64_t rows, int64_t cols) {
     try {                                                             // no C++ exception may cross the C ABI (std::string / vector growth)
         return pt_write_f32(path, host_data, rows, cols);
+    } catch (const std::bad_alloc&) {
+        return ser_fail(-ENOMEM, "ser_pt_write_f32: out of memory");
+    }
+}
+
+extern "C" int ser_pt_write_f32_vec(const char* path, const float* host_data, int64_t n) {
+    try {
+        if (n <= 0) return ser_fail(-1, "ser_pt_write_f32: bad arguments");
+        return pt_write_f32(path, host_data, 1, n, true);
     } catch (const std::bad_alloc&) {
         return ser_fail(-ENOMEM, "ser_pt_write_f32: out of memory");
     }

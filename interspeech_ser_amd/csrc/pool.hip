@@ -9,13 +9,8 @@
 //   ser_cls_tail_v    their projector and classifier on the pooled rows
 // ser_hip.h states the arithmetic.  Every sum accumulates in float64 in an order that depends on the utterance alone (its frame count and
 // the widths), never on the batch; one rounding to fp32 at each store.  No atomics.
-#include "ser_common.h"
+#include "tail_common.h"
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // sum over the 4 waves of a 256-thread block, fixed order; every thread gets the result.  red: 4 doubles of LDS per call site in flight.
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
     v = wave_sum_f64(v);
@@ -411,37 +406,7 @@ extern "C" int ser_layer_pool_v(const ser_layer_pool_args* a, void* stream) {
 }
 
 // ------------------------------------------------------------------------------- projector and classifier on the pooled rows
-// One block of 1024 threads per utterance.  Hidden unit j (wave v owns j = v, v + 16, ...): lane l adds pooled[b, c] P[j, c] over its
-// columns 4 l + 256 i in ascending i (16-byte loads), then the butterfly, + bp[j]; the unit stays in LDS in float64.  Label n (same wave
-// rule): lane l adds hid[k] C[n, k] over k = l, l + 64, ... ascending, the butterfly, + bc[n], one rounding at the store.
-#define CLS_TAIL_MAX 2048
-__global__ __launch_bounds__(1024) void cls_tail_kernel(const float* __restrict__ pooled, int64_t ldp, const float* __restrict__ P,
-                                                        const float* __restrict__ bp, const float* __restrict__ Cw, const float* __restrict__ bc,
-                                                        float* __restrict__ out, int64_t ldo, int D, int proj, int n_labels) {
-    __shared__ double hid[CLS_TAIL_MAX];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* x = pooled + (int64_t)b * ldp;
-    for (int j = wave; j < proj; j += 16) {
-        const float* pr = P + (int64_t)j * D;
-        double acc = 0.0;
-        for (int c = lane * 4; c < D; c += 256) {
-            const f32x4 v = *(const f32x4*)(x + c), u = *(const f32x4*)(pr + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = fma((double)v[e], (double)u[e], acc);
-        }
-        acc = wave_sum_f64(acc);
-        if (lane == 0) hid[j] = acc + (double)bp[j];
-    }
-    __syncthreads();
-    for (int n = wave; n < n_labels; n += 16) {
-        const float* cr = Cw + (int64_t)n * proj;
-        double acc = 0.0;
-        for (int k = lane; k < proj; k += 64) acc = fma(hid[k], (double)cr[k], acc);
-        acc = wave_sum_f64(acc);
-        if (lane == 0) out[(int64_t)b * ldo + n] = (float)(acc + (double)bc[n]);
-    }
-}
-
+// cls_tail_kernel (tail_common.h, shared with ser_xvec_tail_v) in the form that never rounds the projector unit.
 extern "C" int ser_cls_tail_v(const ser_cls_tail_args* a, void* stream) {
     if (!a) return ser_fail(-1, "ser_cls_tail: null pointer");
     if (!a->pooled || !a->P || !a->bp || !a->C || !a->bc || !a->out) return ser_fail(-1, "ser_cls_tail: null pointer");
@@ -451,7 +416,7 @@ extern "C" int ser_cls_tail_v(const ser_cls_tail_args* a, void* stream) {
         return ser_fail(-2, "ser_cls_tail: bad B=%d D=%d (D %% 4 == 0) ldp=%lld (>= D, multiple of 4) ldo=%lld (>= n_labels)", a->B, a->D,
                         (long long)a->ldp, (long long)a->ldo);
     if ((((uintptr_t)a->pooled | (uintptr_t)a->P) & 15) != 0) return ser_fail(-2, "ser_cls_tail: pooled and P must be 16-byte aligned");
-    hipLaunchKernelGGL(cls_tail_kernel, dim3((unsigned)a->B), dim3(1024), 0, (hipStream_t)stream, a->pooled, a->ldp, a->P, a->bp, a->C, a->bc, a->out,
-                       a->ldo, a->D, a->proj, a->n_labels);
+    hipLaunchKernelGGL(cls_tail_kernel<false>, dim3((unsigned)a->B), dim3(1024), 0, (hipStream_t)stream, a->pooled, a->ldp, a->P, a->bp, a->C, a->bc,
+                       a->out, a->ldo, a->D, a->proj, a->n_labels, (float*)nullptr, (int64_t)0);
     return ser_check_launch("ser_cls_tail");
 }

@@ -1963,6 +1963,163 @@ class ClassifierHead(_HeadBase):
         return bf["out"][:B]
 
 
+def _pad_to(n: int, m: int) -> int:
+    return -(-int(n) // m) * m
+
+
+class XVectorHead(_HeadBase):
+    """The x-vector head of the hub's speaker-verification checkpoints on the device (HF WavLMForXVector.forward and its wav2vec2 /
+    data2vec-audio / w2v-BERT twins): ``hidden_states`` -> softmax(layer_weights)-weighted sum (``use_weighted_layer_sum``; else the last
+    state) -> projector -> ReLU TDNN layers (dilated, unpadded: T shrinks) -> statistics pooling (mean | unbiased std) ->
+    feature_extractor (``embeddings``) -> classifier (``logits``).  A ReLU follows the projector, so nothing commutes with the mean and
+    the [T, D] mix is formed.  ``forward`` enqueues on the current stream behind the encoder's recorded forward (no command-list op, the
+    tapes stay as they are):
+      ser_layer_mix_v (the mix as the projector's operand) -> ser_gemm (projector, operand out)
+      -> per TDNN layer: ser_ragged_index (tap-0 row of every output row) -> ser_gemm (kc = the padded input width, ldj = dilation x
+         pitch, fp32 out, rows packed at the layer's own offsets) -> ser_act_rows_v(relu) (the next operand; not after the last layer)
+      -> ser_stat_pool_v (relu on read) -> ser_xvec_tail_v.
+    Every utterance alone: no window crosses an utterance, every sum's order depends on the utterance alone.  Widths ser_gemm does not
+    take are zero-padded at load -- a layer's input width to a multiple of 64 (zero weight columns, and the producer's zero weight rows
+    and biases make the operand's padding columns exact zeros), the last layer's output width to a multiple of 8 -- and the statistics
+    read the true width only.  GEMM operand format: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo otherwise; the fp16
+    copies report to ``hs.range_flag``.  ``head_sd``: the tensors of ``weights.split_xvector_head``; ``spec``: ``config.XVectorSpec``."""
+
+    def __init__(self, enc: "_EncoderBase", head_sd, spec):
+        from .weights import check_xvector_head
+        if not isinstance(enc, (SpeechEncoder, W2vBertEncoder)):
+            raise ValueError("XVectorHead runs behind the speech and w2v-BERT encoders")
+        geo = enc.geo
+        D, L1 = geo.hidden, geo.num_layers + 1
+        self.enc, self.D, self.device, self.spec = enc, D, enc.device, spec
+        self.op_mode = _operand_mode(enc.mode_name)
+        self.weighted = bool(spec.use_weighted_layer_sum)
+        check_xvector_head(head_sd, D, spec, L1)
+        dims, n = tuple(int(d) for d in spec.tdnn_dim), len(spec.tdnn_dim)
+        self.dim, self.n_out = int(spec.xvector_output_dim), int(head_sd["classifier.weight"].shape[0])
+        if D % 64 or D > 2048:
+            raise ValueError(f"XVectorHead needs a hidden width that is a multiple of 64 and at most 2048 (ser_gemm's K rule, ser_layer_mix_v's row), got {D}")
+        if dims[-1] % 4:
+            raise ValueError(f"tdnn_dim[-1] = {dims[-1]} is not a multiple of 4 (ser_stat_pool_v's 16-byte loads)")
+        if not 1 <= self.dim <= _lib.CLS_TAIL_MAX or not 1 <= self.n_out <= _lib.CLS_TAIL_MAX:
+            raise ValueError(f"xvector_output_dim {self.dim} / {self.n_out} labels: ser_xvec_tail_v takes 1..{_lib.CLS_TAIL_MAX} each")
+        # padded widths: what a later GEMM reads as K chunks is a multiple of 64, the last layer's output a multiple of 8
+        self.widths = [_pad_to(d, 64) for d in dims[:-1]] + [_pad_to(dims[-1], 8)]
+        if max(self.widths[:-1], default=0) > 2048:
+            raise ValueError(f"tdnn_dim {dims}: ser_act_rows_v takes rows of at most 2048 columns")
+        f32 = lambda t: t.detach().to(torch.float32)                     # noqa: E731
+        P0 = self.widths[0]
+        w = torch.zeros((P0, D), dtype=torch.float32)
+        b = torch.zeros(P0, dtype=torch.float32)
+        w[: dims[0]], b[: dims[0]] = f32(head_sd["projector.weight"]), f32(head_sd["projector.bias"])
+        self.projector = enc._linear(w, b, mode=self.op_mode, name="projector.weight")
+        self.tdnn = []
+        for i in range(n):
+            k, d_in, p_in = int(spec.tdnn_kernel[i]), dims[i - 1] if i else dims[0], self.widths[i - 1] if i else P0
+            w = torch.zeros((self.widths[i], k, p_in), dtype=torch.float32)
+            b = torch.zeros(self.widths[i], dtype=torch.float32)
+            w[: dims[i], :, :d_in] = f32(head_sd[f"tdnn.{i}.kernel.weight"]).reshape(dims[i], k, d_in)       # tap-major
+            b[: dims[i]] = f32(head_sd[f"tdnn.{i}.kernel.bias"])
+            self.tdnn.append(dict(lin=enc._linear(w.reshape(self.widths[i], k * p_in), b, mode=self.op_mode, name=f"tdnn.{i}.kernel.weight"),
+                                  k=k, d=int(spec.tdnn_dilation[i]), p_in=p_in, N=self.widths[i]))
+        self.Dl = dims[-1]
+        self.F, self.bf = enc._dev_f32(head_sd["feature_extractor.weight"]), enc._dev_f32(head_sd["feature_extractor.bias"])
+        self.C, self.bc = enc._dev_f32(head_sd["classifier.weight"]), enc._dev_f32(head_sd["classifier.bias"])
+        # softmax(layer_weights), once, in float64 from the fp32 parameter
+        sw = torch.softmax(head_sd["layer_weights"].detach().to(torch.float32).double(), dim=-1) if self.weighted else torch.ones(1, dtype=torch.float64)
+        self.n_states = int(sw.numel())
+        self.w = sw.contiguous().to(self.device)
+        self._bufs = SlotArenas(self._build_buffers)
+
+    def _build_buffers(self, cap: Dict[str, int]) -> dict:
+        """buffers of one pipeline slot, sized by the encoder rows M (every later level has fewer): the operand of the projector, one per
+        TDNN layer's input, one fp32 GEMM output and one tap-0 row table that the layers take turns with (one stream), and the tail's"""
+        M, B, dev = cap["M"], cap["B"], self.device
+        planes, dt = _PLANES[self.op_mode], _DTYPE[self.op_mode]
+        ops = [Act(M, self.D, planes, dev, dtype=dt)] + [Act(M, t["p_in"], planes, dev, dtype=dt) for t in self.tdnn]
+        return dict(ops=ops, y=torch.empty((M, max(self.widths)), dtype=torch.float32, device=dev),
+                    rowoff=torch.empty(M, dtype=torch.int32, device=dev),
+                    work=torch.empty(cap["work"], dtype=torch.float64, device=dev),
+                    stats=torch.empty((B, 2 * self.Dl), dtype=torch.float32, device=dev),
+                    rows=torch.empty((B, self.dim + self.n_out), dtype=torch.float32, device=dev),      # [embeddings | logits]
+                    # the encoder's frame offsets when they came without a device copy, then per layer its [B + 1] offsets and [B] base rows
+                    tab=TableBlob(B, 1 + 2 * len(self.tdnn), dev))
+
+    def forward(self, hs: HiddenStates, slot: int = 0):
+        """(``[B, xvector_output_dim]`` fp32 embeddings, ``[B, num_labels]`` fp32 logits): the two column blocks of ``forward_rows``"""
+        rows = self.forward_rows(hs, slot)
+        return rows[:, : self.dim], rows[:, self.dim:]
+
+    def forward_rows(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
+        """``[B, xvector_output_dim + num_labels]`` fp32 on the device, embeddings then logits (a view of the slot's buffer: valid until
+        the slot's next ``forward``).  ``hs.states`` is only read.  ``ValueError`` naming the utterance (by index) whose TDNN output has
+        fewer than two rows, before anything is launched."""
+        if hs.computed < len(hs):
+            raise IndexError(f"the head needs {'every hidden state' if self.weighted else 'the last hidden state'} (run the forward without "
+                             f"last_state: states 0..{hs.computed - 1} of {len(hs)} were computed)")
+        s = hs.states
+        M, B, D = int(hs.frame_offs[-1]), hs.batch, self.D
+        if s.dim() != 3 or s.shape[0] != self.enc.geo.num_layers + 1 or s.shape[2] != D or s.stride(2) != 1 or s.shape[1] < M \
+                or s.dtype != torch.float32:
+            raise ValueError(f"hidden states {tuple(s.shape)} do not match the head ({self.enc.geo.num_layers + 1} states of width {D}, {M} rows)")
+        lay = self.spec.layout(hs.frame_offs)                             # refuses a short utterance by index
+        offs = lay.offs
+        max_out = max(offs[-1][b + 1] - offs[-1][b] for b in range(B))
+        chunks = -(-max_out // _lib.STAT_POOL_FC)
+        bf = self._bufs.fit(slot, M=M, B=B, work=B * chunks * 2 * self.Dl)
+        st = _stream()
+        tab = bf["tab"].begin()
+        offs_dev = [hs.frame_offs_dev if hs.frame_offs_dev is not None else tab.put32(offs[0])]
+        bases = []
+        for i in range(len(self.tdnn)):
+            offs_dev.append(tab.put32(offs[i + 1]))
+            bases.append(tab.put64(offs[i][:B]))
+        tab.send()
+        flag = hs.range_flag.data_ptr() if (hs.range_flag is not None and self.op_mode == _lib.MODE_FP16X) else None
+        ops, y, enc = bf["ops"], bf["y"], self.enc
+        first = s if self.weighted else s[-1:]
+        x0 = ops[0].first_rows(M)
+        m = _lib.LayerMixArgs()
+        m.s, m.state_stride, m.lds, m.w = first.data_ptr(), s.stride(0), s.stride(1), self.w.data_ptr()
+        m.out_act, m.ldo_act, m.out_plane_stride, m.range_flag = x0.ptr, x0.cols, x0.plane_stride, flag
+        m.n_states, m.mode, m.rows, m.D = self.n_states, self.op_mode, M, D
+        self._step("layer_mix", lambda: check(lib.ser_layer_mix_v(C.byref(m), st), "ser_layer_mix_v"))
+        prev_flag, prev_st = enc._flag, enc._st
+        enc._flag, enc._st = flag, st                                     # the GEMMs' guard word and stream (launched at once, never recorded)
+        try:
+            self._step("projector", lambda: enc._gemm(x0, self.projector, M, out_act=ops[1].first_rows(M), mode=self.op_mode))
+            for i, t in enumerate(self.tdnn):
+                Mi, last = int(offs[i + 1][-1]), i == len(self.tdnn) - 1
+                a_in, p_in, N = ops[i + 1].first_rows(int(offs[i][-1])), t["p_in"], t["N"]
+
+                def layer(i=i, t=t, Mi=Mi, a_in=a_in, p_in=p_in, N=N):
+                    check(lib.ser_ragged_index(offs_dev[i + 1].data_ptr(), bases[i].data_ptr(), B, 1, p_in, 8, bf["rowoff"].data_ptr(), Mi, st),
+                          "ser_ragged_index")
+                    enc._gemm(a_in, t["lin"], Mi, a_rowoff=bf["rowoff"], kc=p_in, ldj=t["d"] * p_in, out_f32=y, ldo_f32=N, mode=self.op_mode)
+                self._step(f"tdnn{i}", layer)
+                if not last:
+                    nxt = ops[i + 2].first_rows(Mi)
+                    r = _lib.ActRowsArgs()
+                    r.x, r.ldx, r.out_act, r.ldo_act, r.out_plane_stride = y.data_ptr(), N, nxt.ptr, nxt.cols, nxt.plane_stride
+                    r.range_flag, r.relu, r.mode, r.rows, r.D = flag, 1, self.op_mode, Mi, N
+                    self._step(f"relu{i}", lambda r=r: check(lib.ser_act_rows_v(C.byref(r), st), "ser_act_rows_v"))
+        finally:
+            enc._flag, enc._st = prev_flag, prev_st
+        Ml, Nl = int(offs[-1][-1]), self.widths[-1]
+        offs_host = (C.c_int32 * (B + 1))(*offs[-1])
+        p = _lib.StatPoolArgs()
+        p.x, p.ldx, p.frame_offs, p.frame_offs_host = y.data_ptr(), Nl, offs_dev[-1].data_ptr(), C.cast(offs_host, C.c_void_p)
+        p.work, p.work_elems, p.out, p.ldo = bf["work"].data_ptr(), bf["work"].numel(), bf["stats"].data_ptr(), 2 * self.Dl
+        p.B, p.D, p.rows, p.max_frames, p.relu = B, self.Dl, Ml, max_out, 1
+        self._step("stat_pool", lambda: check(lib.ser_stat_pool_v(C.byref(p), st), "ser_stat_pool_v"))
+        t = _lib.XvecTailArgs()
+        t.stats, t.lds, t.F, t.bf, t.C, t.bc = bf["stats"].data_ptr(), 2 * self.Dl, self.F.data_ptr(), self.bf.data_ptr(), self.C.data_ptr(), self.bc.data_ptr()
+        ld = self.dim + self.n_out
+        t.emb, t.lde, t.logits, t.ldo = bf["rows"].data_ptr(), ld, bf["rows"].data_ptr() + 4 * self.dim, ld
+        t.B, t.D, t.dim, t.n_labels = B, 2 * self.Dl, self.dim, self.n_out
+        self._step("xvec_tail", lambda: check(lib.ser_xvec_tail_v(C.byref(t), st), "ser_xvec_tail_v"))
+        return bf["rows"][:B]
+
+
 def _fusion_keys(names) -> Dict[str, tuple]:
     """state-dict keys and symbolic shapes of the reference's fusion head over the modalities ``names`` (feature width of modality i: "d<i+1>")"""
     keys = {"classifier.0.weight": ("h1", "ne"), "classifier.0.bias": ("h1",), "classifier.3.weight": ("n", "h1"), "classifier.3.bias": ("n",),

@@ -321,6 +321,51 @@ def check_classifier_head(head_sd: StateDict, D: int, proj: int, num_labels: int
                              f"{num_labels} labels, {num_states} hidden states)")
 
 
+def xvector_head_keys(num_tdnn: int, weighted: bool) -> tuple:
+    """the head tensors of an x-vector checkpoint under normalised names (HF *ForXVector; ``feature_extractor.weight`` is the head's
+    Linear, not the encoder's ``feature_extractor.conv_layers.*``)"""
+    keys = ["projector.weight", "projector.bias"]
+    for i in range(num_tdnn):
+        keys += [f"tdnn.{i}.kernel.weight", f"tdnn.{i}.kernel.bias"]
+    keys += ["feature_extractor.weight", "feature_extractor.bias", "classifier.weight", "classifier.bias"]
+    return tuple(keys + (["layer_weights"] if weighted else []))
+
+
+def split_xvector_head(sd: StateDict):
+    """(encoder tensors, head tensors) of a normalised state dict of an x-vector checkpoint.  ``objective.*`` (the AMSoftmax training
+    weight) is dropped; a snapshot without a head comes back whole."""
+    def is_head(k: str) -> bool:
+        return k in ("projector.weight", "projector.bias", "feature_extractor.weight", "feature_extractor.bias", "classifier.weight",
+                     "classifier.bias", "layer_weights") or (k.startswith("tdnn.") and ".kernel." in k)
+    enc = {k: v for k, v in sd.items() if not is_head(k) and not k.startswith("objective.")}
+    head = {k: v for k, v in sd.items() if is_head(k)}
+    return enc, head
+
+
+def check_xvector_head(head_sd: StateDict, D: int, spec, num_states: int) -> None:
+    """Names and shapes of the head tensors against the encoder width, the TDNN lists, ``xvector_output_dim`` and L + 1; the label count
+    is the classifier's own (``ValueError`` naming the key)."""
+    dims, n = tuple(spec.tdnn_dim), len(spec.tdnn_dim)
+    want = {"projector.weight": (dims[0], D), "projector.bias": (dims[0],)}
+    for i in range(n):
+        d_in = dims[i - 1] if i > 0 else dims[0]
+        want[f"tdnn.{i}.kernel.weight"] = (dims[i], d_in * spec.tdnn_kernel[i])
+        want[f"tdnn.{i}.kernel.bias"] = (dims[i],)
+    want["feature_extractor.weight"] = (spec.xvector_output_dim, 2 * dims[-1])
+    want["feature_extractor.bias"] = (spec.xvector_output_dim,)
+    labels = int(head_sd["classifier.weight"].shape[0]) if "classifier.weight" in head_sd and head_sd["classifier.weight"].dim() == 2 else 0
+    want["classifier.weight"] = (labels, spec.xvector_output_dim)
+    want["classifier.bias"] = (labels,)
+    if spec.use_weighted_layer_sum:
+        want["layer_weights"] = (num_states,)
+    for k, shape in want.items():
+        if k not in head_sd:
+            raise ValueError(f"{k} is missing from the checkpoint (an x-vector head needs {', '.join(want)})")
+        if tuple(head_sd[k].shape) != shape or 0 in shape:
+            raise ValueError(f"{k}: shape {tuple(head_sd[k].shape)}, expected {shape} (hidden width {D}, tdnn_dim {dims}, tdnn_kernel "
+                             f"{tuple(spec.tdnn_kernel)}, xvector_output_dim {spec.xvector_output_dim}, {num_states} hidden states)")
+
+
 def merge_lora(sd: StateDict, lora_alpha: float = 16.0) -> StateDict:
     """Fold PEFT LoRA adapters into their base weights (next row 8f-4).  The reference fine-tunes WavLM with
     ``LoraConfig(r=8, lora_alpha=16, target_modules=['q_proj','v_proj'])`` inside a classifier wrapper and extracts
