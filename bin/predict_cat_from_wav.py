@@ -5,7 +5,9 @@ families, w2v-BERT 2.0 (``--encoder1 facebook/w2v-bert-2.0``), RoBERTa / DeBERTa
 the 512-wide prosody | timbre stream of the reference's trimodal ``*_ns3`` configurations, or ``--encoder3 files`` for rows
 from ``lazy_dir3``) and ``multimodal_ser.pt`` into ``results/test.csv`` -- the
 file bin/test_cat_{bi,tri}modal_lazy_stacking_1head.py write, with no feature file in between (interspeech_ser_amd/predictor.py,
-``score_from_wav``).  One GPU, 16 kHz input."""
+``score_from_wav``).  ``--transcribe`` takes the texts from the Whisper stream's own transcripts, ``--transcribe_ctc`` from the greedy CTC
+transcripts of the audio encoder whose snapshot is a CTC checkpoint (``--encoder1 facebook/hubert-xlarge-ls960-ft --encoder2 roberta-large
+--transcribe_ctc``); ``txt_dir`` is then not read.  One GPU, 16 kHz input."""
 import os
 import sys
 

@@ -647,6 +647,52 @@ typedef struct ser_xvec_tail_args {
 } ser_xvec_tail_args;
 int ser_xvec_tail_v(const ser_xvec_tail_args* args, void* stream);
 
+/* a31 (added under ABI 18: new entry points only)  Greedy CTC decoding behind the lm_head of the hub's CTC checkpoints (HF *ForCTC:
+ * logits = lm_head(last_hidden_state); predicted_ids = argmax(logits, -1); Wav2Vec2CTCTokenizer.decode groups equal neighbours and drops
+ * the blank).  The lm_head is a ser_gemm launch with fp32 output (its weight zero-padded to a multiple of 8 rows); ser_ctc_greedy_v is
+ * the rest.  Not a command-list op.
+ *
+ * z: fp32 logits [rows, ldz], the packed ragged rows of a batch; the true width is V, and columns V .. ldz - 1 (the GEMM's padding) are
+ * NEVER read, so nothing there can win.  Utterance b owns frames r0 = frame_offs[b] .. frame_offs[b + 1] - 1 (int32 [B + 1] on the
+ * device).  Per frame t of it:
+ *   tok[t]    = argmax_v z[r0 + t, v], v < V; on a tie the lowest index wins (torch.argmax; ser_dec_select_v's rule)
+ *   margin[t] = top1 - top2, one fp32 subtraction (+inf when V == 1, or when every other column is -inf)
+ *   t is KEPT when tok[t] != blank and (t == 0 or tok[t] != tok[t - 1]) -- the previous frame of the SAME utterance only
+ * The kept tokens in order go to ids[b, 0 .. n_b - 1], counts[b] = n_b; starts[b, j] is the frame index (inside the utterance) of kept
+ * token j and ends[b, j] one past the last frame of its run: HF's char_offsets in frames.  ids / starts / ends are int32 [B, ld_tok],
+ * ld_tok >= max_frames; entries at j >= n_b are not written.  An utterance longer than max_frames is cut there (never a write past the
+ * pitch).  Optional outputs, each skipped when NULL: frame_ids [rows] (HF's predicted_ids, before the collapse), frame_margin [rows],
+ * min_margin [B] (the smallest margin of the utterance's frames; +inf for an utterance without frames).
+ * err: a frame whose winning value is not finite -- all -inf, a +inf, or a NaN among its V columns (a NaN is read as +inf, so it wins) --
+ * ORs SER_CTC_ERR_NONFINITE into *err, which the caller zeroes; the batch then fails like a range-guard hit.  This is
+ * ser_dec_select_v's rule.  The other frames' and utterances' outputs are what they would be without that frame.
+ * work: int32 words, work_elems >= 2 * rows of them (the per-frame tokens and margins between the two kernels).
+ *
+ * Two kernels.  Argmax: a grid over all rows; G lanes of a wave (8 .. 64, from V) take one frame with 16-byte loads and reduce
+ * (top1, its index, top2) triples.  Collapse: one block per utterance walks its frames in chunks of SER_CTC_CHUNK, a block-wide exclusive
+ * scan of the keep flags per chunk, the running count carried from chunk to chunk.
+ * Determinism: there is no floating-point sum and no atomic on data.  max, the lowest index of the max and the second value are
+ * functions of a row's multiset of (value, index) pairs, so the merge of two triples is associative and commutative and no split of V
+ * over lanes, no lane count and no shuffle order can change a result; the margin is one subtraction of two such values; min_margin is
+ * a min, exact in any order; the scan adds integers.  Every output is therefore a pure function of (the utterance's rows of z, blank) and
+ * bit-identical whatever else shares the batch.
+ * Refused before any launch: -1 null pointer (z, frame_offs, work, ids, starts, ends, counts, err); -2 sizes (B < 1 or > 65535, V < 1,
+ * rows < 1, blank outside [0, V), max_frames < 1, work_elems < 2 * rows); -3 pitches / alignment (ldz < V or not a multiple of 4,
+ * ld_tok < max_frames, z not 16-byte aligned). */
+#define SER_CTC_CHUNK 256
+#define SER_CTC_ERR_NONFINITE 1
+typedef struct ser_ctc_greedy_args {
+    const float* z; int64_t ldz;
+    const int32_t* frame_offs;
+    int32_t* work; int64_t work_elems;
+    int32_t* ids; int32_t* starts; int32_t* ends; int64_t ld_tok;
+    int32_t* counts;
+    int32_t* frame_ids; float* frame_margin; float* min_margin;
+    uint32_t* err;
+    int32_t B, V, rows, blank, max_frames, reserved0;
+} ser_ctc_greedy_args;
+int ser_ctc_greedy_v(const ser_ctc_greedy_args* args, void* stream);
+
 /* a23 (added under ABI 18: new entry points only)  The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334,
  * MultiModalEmotionClassifier) on packed ragged batches: every utterance alone, as the reference's evaluation runs it (batch_size = 1,
  * bin/eval_cat_bimodal_lazy_1head.py:292) -- no pad frame enters the recurrence, the attention or a pooling softmax.  None of the four is a

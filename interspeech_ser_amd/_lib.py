@@ -227,6 +227,16 @@ class XvecTailArgs(C.Structure):
     ]
 
 
+class CtcGreedyArgs(C.Structure):
+    """Mirror of ``ser_ctc_greedy_args``."""
+    _fields_ = [
+        ("z", c_void_p), ("ldz", c_i64), ("frame_offs", c_void_p), ("work", c_void_p), ("work_elems", c_i64),
+        ("ids", c_void_p), ("starts", c_void_p), ("ends", c_void_p), ("ld_tok", c_i64), ("counts", c_void_p),
+        ("frame_ids", c_void_p), ("frame_margin", c_void_p), ("min_margin", c_void_p), ("err", c_void_p),
+        ("B", C.c_int32), ("V", C.c_int32), ("rows", C.c_int32), ("blank", C.c_int32), ("max_frames", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class GruArgs(C.Structure):
     """Mirror of ``ser_gru_args``."""
     _fields_ = [
@@ -427,6 +437,8 @@ CODEC_TILE = 128                # SER_CODEC_TILE: output rows per block of ser_c
 FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
 DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked logit was not finite
 DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
+CTC_CHUNK = 256                 # SER_CTC_CHUNK: frames per chunk of ser_ctc_greedy_v's collapse
+CTC_ERR_NONFINITE = 1           # ser_ctc_greedy_v *err bit 0: a frame's winning logit was not finite
 
 
 class _CmdUnion(C.Union):
@@ -460,6 +472,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_attention_rk_args": AttentionRkArgs, "ser_conformer_conv_args": ConformerConvArgs,
                   "ser_swish_rows_args": SwishRowsArgs, "ser_layer_pool_args": LayerPoolArgs, "ser_cls_tail_args": ClsTailArgs,
                   "ser_layer_mix_args": LayerMixArgs, "ser_stat_pool_args": StatPoolArgs, "ser_xvec_tail_args": XvecTailArgs,
+                  "ser_ctc_greedy_args": CtcGreedyArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -488,6 +501,7 @@ _SIGNATURES = {
     "ser_layer_mix_v": (c_int, [c_void_p, c_void_p]),
     "ser_stat_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_xvec_tail_v": (c_int, [c_void_p, c_void_p]),
+    "ser_ctc_greedy_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),

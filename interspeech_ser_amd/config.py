@@ -750,3 +750,56 @@ def resolve_xvector(ssl_type: str, checkpoint: str = "") -> Optional[XVectorSpec
     except (OSError, ValueError) as e:
         raise OSError(f"cannot read {path}: {e}")
     return XVectorSpec.from_config(cfg, name=ssl_type)
+
+
+# The hub classes that put a CTC head on the encoders built here (HF *ForCTC, what ``AutoModelForCTC`` loads): dropout ->
+# lm_head(last_hidden_state) -> argmax per frame -> equal neighbours merged, blanks dropped (engine.CTCHead).
+CTC_ARCHITECTURES = ("Wav2Vec2ForCTC", "HubertForCTC", "WavLMForCTC", "Data2VecAudioForCTC", "Wav2Vec2BertForCTC")
+# ... and those whose encoders this path does not build
+CTC_UNBUILT_ARCHITECTURES = ("UniSpeechForCTC", "UniSpeechSatForCTC", "Wav2Vec2ConformerForCTC", "SEWForCTC", "SEWDForCTC")
+
+
+@dataclass(frozen=True)
+class CTCSpec:
+    """What ``AutoModelForCTC`` reads from ``config.json`` for that head.  ``blank``: ``pad_token_id``, the id
+    ``Wav2Vec2CTCTokenizer`` drops after grouping."""
+    vocab_size: int
+    blank: int
+    architecture: str = ""
+
+    @staticmethod
+    def from_config(cfg: dict, name: str = "") -> Optional["CTCSpec"]:
+        """The spec of a snapshot whose ``architectures[0]`` is one of ``CTC_ARCHITECTURES``, else None.  ``OSError`` naming the class: a
+        CTC class over an encoder that is not built, ``add_adapter``, a missing ``vocab_size`` or ``pad_token_id``."""
+        arch = cfg.get("architectures") or []
+        arch = arch[0] if isinstance(arch, (list, tuple)) and arch else (arch if isinstance(arch, str) else "")
+        name = name or str(cfg.get("_name_or_path", "")) or arch
+        if arch in CTC_UNBUILT_ARCHITECTURES:
+            raise OSError(f"{name}: {arch} is not supported (its encoder is not built; the CTC head runs behind " + ", ".join(CTC_ARCHITECTURES) + ")")
+        if arch not in CTC_ARCHITECTURES:
+            return None
+        if cfg.get("add_adapter", False):
+            raise OSError(f"{name}: {arch} with add_adapter=True (an adapter stack after the encoder) is not supported")
+        if cfg.get("vocab_size") is None:
+            # HF: "You are trying to instantiate <class> with a configuration that does not define the vocabulary size of the language model head"
+            raise OSError(f"{name}: {arch} without vocab_size (the width of lm_head) in config.json")
+        if cfg.get("pad_token_id") is None:
+            raise OSError(f"{name}: {arch} without pad_token_id (the CTC blank) in config.json")
+        V, blank = int(cfg["vocab_size"]), int(cfg["pad_token_id"])
+        if V < 1 or not 0 <= blank < V:
+            raise OSError(f"{name}: {arch} with vocab_size {V} and pad_token_id {blank} (the blank must be one of the vocabulary)")
+        return CTCSpec(vocab_size=V, blank=blank, architecture=arch)
+
+
+def resolve_ctc(ssl_type: str, checkpoint: str = "") -> Optional[CTCSpec]:
+    """``CTCSpec`` of the ``config.json`` that ``find_config_json`` picks; None when there is no such file or it names another class."""
+    import json
+    path = find_config_json(ssl_type, checkpoint)
+    if not path:
+        return None
+    try:
+        with open(path, "r") as f:
+            cfg = json.load(f)
+    except (OSError, ValueError) as e:
+        raise OSError(f"cannot read {path}: {e}")
+    return CTCSpec.from_config(cfg, name=ssl_type)

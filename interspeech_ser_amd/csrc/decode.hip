@@ -3,6 +3,7 @@
 // append of the step's own k / v row.  ser_dec_select_v: masked greedy choice, end-of-sequence bookkeeping, and the advance of the position.
 // The position lives in device memory and no pointer changes between steps, so a recorded step is replayed as it is (ser_run).
 #include "ser_common.h"
+#include "top2_common.h"
 #include <math.h>
 
 // ---------------------------------------------------------------------------------------------------------------- embed
@@ -151,17 +152,7 @@ extern "C" int ser_dec_attn_v(const ser_dec_attn_args* a, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- select
-// (top-1 value, its index, top-2 value) of a set; NaN was mapped to +inf on the way in, so plain comparisons order everything.
-struct Top2 { float v1; int i1; float v2; };
-__device__ __forceinline__ Top2 top2_merge(Top2 x, Top2 y) {
-    const bool xw = x.v1 > y.v1 || (x.v1 == y.v1 && x.i1 < y.i1);             // the lowest index wins a tie (torch.argmax)
-    Top2 r;
-    r.v1 = xw ? x.v1 : y.v1;
-    r.i1 = xw ? x.i1 : y.i1;
-    r.v2 = xw ? fmaxf(x.v2, y.v1) : fmaxf(y.v2, x.v1);
-    return r;
-}
-
+// Top2 / top2_merge: top2_common.h (shared with ctc.hip)
 __global__ __launch_bounds__(256) void dec_select_kernel(ser_dec_select_args a) {
     __shared__ Top2 part[4];
     const int b = blockIdx.x, tid = threadIdx.x;

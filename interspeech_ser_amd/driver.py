@@ -102,14 +102,15 @@ def resolve_layer_index(n_layer: int, num_states: int) -> int:
 
 
 # ------------------------------------------------------------------------ weights
-def find_weights(ssl_type: str, checkpoint: str, synthetic: bool, seed: int, geo, lora_alpha: float = 16.0):
+def find_weights(ssl_type: str, checkpoint: str, synthetic: bool, seed: int, geo, lora_alpha: float = 16.0, keep: tuple = ()):
     """Rank 0 only: the other ranks receive the tensors by broadcast (dist.broadcast_state_dict).
-    A checkpoint that carries PEFT LoRA adapters (preprocess_speech_pretrained.py:108-177) is merged at load."""
+    A checkpoint that carries PEFT LoRA adapters (preprocess_speech_pretrained.py:108-177) is merged at load.
+    ``keep``: name prefixes ``weights.normalize_names`` leaves in (the CTC drivers' ``lm_head.``)."""
     from .weights import load_checkpoint, synthetic_state_dict
     if checkpoint:
-        return load_checkpoint(checkpoint, lora_alpha), f"checkpoint {checkpoint}"
+        return load_checkpoint(checkpoint, lora_alpha, keep), f"checkpoint {checkpoint}"
     if not synthetic and os.path.isdir(ssl_type):         # --ssl_type may be a local snapshot directory, as with from_pretrained
-        return load_checkpoint(ssl_type, lora_alpha), f"snapshot {ssl_type}"
+        return load_checkpoint(ssl_type, lora_alpha, keep), f"snapshot {ssl_type}"
     if not synthetic:
         # offline HF cache layout: $HF_HOME/hub/models--org--name/snapshots/<rev>/
         home = os.environ.get("HF_HOME", os.path.join(os.path.expanduser("~"), ".cache", "huggingface"))
@@ -117,7 +118,7 @@ def find_weights(ssl_type: str, checkpoint: str, synthetic: bool, seed: int, geo
         if os.path.isdir(snap):
             for rev in sorted(os.listdir(snap)):
                 try:
-                    return load_checkpoint(os.path.join(snap, rev)), f"HF cache {rev}"
+                    return load_checkpoint(os.path.join(snap, rev), keep=keep), f"HF cache {rev}"
                 except OSError:
                     continue
         raise OSError(f"no local checkpoint for {ssl_type} (pass --checkpoint or --synthetic_weights)")

@@ -2120,6 +2120,112 @@ class XVectorHead(_HeadBase):
         return bf["rows"][:B]
 
 
+class CTCHead(_HeadBase):
+    """The head of the hub's CTC checkpoints on the device (HF Wav2Vec2ForCTC.forward and its HuBERT / WavLM / data2vec-audio / w2v-BERT
+    twins, then ``argmax(-1)`` and what ``Wav2Vec2CTCTokenizer`` does to the ids): ``last_hidden_state`` -> lm_head -> per frame the
+    winning id -> equal neighbours merged, blanks dropped.  ``forward_tokens`` enqueues three steps on the current stream behind the
+    encoder's recorded forward (no command-list op, the tapes stay as they are):
+      ser_layer_mix_v (one state, weight 1: the identity in fp32, the last state as the GEMM's operand planes)
+      -> ser_gemm (lm_head, fp32 out; ``lm_head.weight`` zero-padded at load to a multiple of 8 rows)
+      -> ser_ctc_greedy_v with the TRUE vocabulary width: it never reads the padded columns, so their zeros cannot win.
+    Every utterance alone: the collapse compares a frame with the previous frame of its own utterance only, and nothing is summed.  GEMM
+    operand format: bf16 in mode "bf16", bf16 hi + lo in "fp32x", fp16 hi + lo otherwise; the fp16 copies report to ``hs.range_flag``.
+    ``head_sd``: the tensors of ``weights.split_ctc_head``; ``spec``: ``config.CTCSpec``."""
+
+    def __init__(self, enc: "_EncoderBase", head_sd, spec):
+        from .weights import check_ctc_head
+        if not isinstance(enc, (SpeechEncoder, W2vBertEncoder)):
+            raise ValueError("CTCHead runs behind the speech and w2v-BERT encoders")
+        D = enc.geo.hidden
+        self.enc, self.D, self.device, self.spec = enc, D, enc.device, spec
+        self.op_mode = _operand_mode(enc.mode_name)
+        self.V, self.blank = int(spec.vocab_size), int(spec.blank)
+        if D % 64 or D > 2048:
+            raise ValueError(f"CTCHead needs a hidden width that is a multiple of 64 and at most 2048 (ser_gemm's K rule, ser_layer_mix_v's row), got {D}")
+        check_ctc_head(head_sd, D, self.V)
+        self.Vp = _pad_to(self.V, 8)
+        w = torch.zeros((self.Vp, D), dtype=torch.float32)
+        b = torch.zeros(self.Vp, dtype=torch.float32)
+        w[: self.V], b[: self.V] = head_sd["lm_head.weight"].detach().to(torch.float32), head_sd["lm_head.bias"].detach().to(torch.float32)
+        self.lm_head = enc._linear(w, b, mode=self.op_mode, name="lm_head.weight")
+        self.w = torch.ones(1, dtype=torch.float64, device=self.device)
+        self._bufs = SlotArenas(self._build_buffers)
+        self._last: Dict[int, tuple] = {}                                 # slot -> (M, B, max_frames) of its last forward
+
+    @staticmethod
+    def blob_words(B: int, max_frames: int) -> int:
+        """int32 words of a batch's result: counts [B] | ids [B, Tm] | starts [B, Tm] | ends [B, Tm] | min_margin [B] (fp32 bits) | err [1]"""
+        return 2 * B + 3 * B * max_frames + 1
+
+    @staticmethod
+    def unpack(words, B: int, max_frames: int) -> dict:
+        """The host copy of ``forward_tokens``'s buffer (numpy int32 [blob_words]) as its parts (views)"""
+        import numpy as np
+        w = np.asarray(words).reshape(-1).view(np.int32)
+        n = B * max_frames
+        part = lambda i: w[B + i * n: B + (i + 1) * n].reshape(B, max_frames)      # noqa: E731
+        return dict(counts=w[:B], ids=part(0), starts=part(1), ends=part(2), min_margin=w[B + 3 * n: 2 * B + 3 * n].view(np.float32),
+                    err=int(w[2 * B + 3 * n]))
+
+    def _build_buffers(self, cap: Dict[str, int]) -> dict:
+        """buffers of one pipeline slot: the operand copy of the last state, the fp32 logits, the kernel's per-frame words, the result"""
+        M, dev = cap["M"], self.device
+        return dict(xa=Act(M, self.D, _PLANES[self.op_mode], dev, dtype=_DTYPE[self.op_mode]),
+                    z=torch.empty((M, self.Vp), dtype=torch.float32, device=dev),
+                    work=torch.empty(2 * M, dtype=torch.int32, device=dev),
+                    blob=torch.empty(cap["blob"], dtype=torch.int32, device=dev), tab=TableBlob(cap["B"], 1, dev))
+
+    def forward_tokens(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
+        """int32 [blob_words(B, max_frames)] on the device (``unpack`` names its parts; a view of the slot's buffer, valid until the slot's
+        next forward): one D2H copy brings a batch's counts, ids, offsets, smallest margins and error word back.  ``hs.states`` is only read."""
+        if hs.computed < len(hs):
+            raise IndexError(f"the head needs the last hidden state (run the forward without last_state: states 0..{hs.computed - 1} of "
+                             f"{len(hs)} were computed)")
+        s = hs.states
+        M, B, D = int(hs.frame_offs[-1]), hs.batch, self.D
+        if s.dim() != 3 or s.shape[2] != D or s.stride(2) != 1 or s.shape[1] < M or s.dtype != torch.float32:
+            raise ValueError(f"hidden states {tuple(s.shape)} do not match the head (states of width {D}, {M} rows)")
+        Tm = max(hs.frames(b) for b in range(B))
+        if M < 1 or Tm < 1:
+            raise ValueError("the batch has no frames")
+        n = self.blob_words(B, Tm)
+        bf = self._bufs.fit(slot, M=M, B=B, blob=n)
+        st = _stream()
+        offs = hs.frame_offs_dev if hs.frame_offs_dev is not None else _head_offs(bf["tab"], hs.frame_offs)
+        flag = hs.range_flag.data_ptr() if (hs.range_flag is not None and self.op_mode == _lib.MODE_FP16X) else None
+        enc, xa, z, blob = self.enc, bf["xa"].first_rows(M), bf["z"], bf["blob"]
+        m = _lib.LayerMixArgs()
+        m.s, m.state_stride, m.lds, m.w = s[-1].data_ptr(), 0, s.stride(1), self.w.data_ptr()
+        m.out_act, m.ldo_act, m.out_plane_stride, m.range_flag = xa.ptr, xa.cols, xa.plane_stride, flag
+        m.n_states, m.mode, m.rows, m.D = 1, self.op_mode, M, D
+        self._step("operand", lambda: check(lib.ser_layer_mix_v(C.byref(m), st), "ser_layer_mix_v"))
+        prev_flag, prev_st = enc._flag, enc._st
+        enc._flag, enc._st = flag, st                                     # the GEMM's guard word and stream (launched at once, never recorded)
+        try:
+            self._step("lm_head", lambda: enc._gemm(xa, self.lm_head, M, out_f32=z, ldo_f32=self.Vp, mode=self.op_mode))
+        finally:
+            enc._flag, enc._st = prev_flag, prev_st
+        blob[n - 1: n].zero_()                                            # the error word
+        p0, nt = blob.data_ptr(), 4 * B * Tm
+        g = _lib.CtcGreedyArgs()
+        g.z, g.ldz, g.frame_offs, g.work, g.work_elems = z.data_ptr(), self.Vp, offs.data_ptr(), bf["work"].data_ptr(), bf["work"].numel()
+        g.counts, g.ids, g.starts, g.ends, g.ld_tok = p0, p0 + 4 * B, p0 + 4 * B + nt, p0 + 4 * B + 2 * nt, Tm
+        g.min_margin, g.err = p0 + 4 * B + 3 * nt, p0 + 4 * (n - 1)
+        g.B, g.V, g.rows, g.blank, g.max_frames = B, self.V, M, self.blank, Tm
+        self._step("ctc_greedy", lambda: check(lib.ser_ctc_greedy_v(C.byref(g), st), "ser_ctc_greedy_v"))
+        self._last[slot] = (M, B, Tm)
+        return blob[:n]
+
+    def logits(self, slot: int = 0) -> torch.Tensor:
+        """fp32 [rows, vocab_size] logits of the slot's last forward (a view of its buffer), for tests and tools"""
+        return self._bufs[slot]["z"][: self._last[slot][0], : self.V]
+
+    def status(self, slot: int = 0) -> int:
+        """the error word of the slot's last forward (synchronous): ``_lib.CTC_ERR_NONFINITE`` when a frame's winning logit was not finite"""
+        M, B, Tm = self._last[slot]
+        return int(self._bufs[slot]["blob"][self.blob_words(B, Tm) - 1].item())
+
+
 def _fusion_keys(names) -> Dict[str, tuple]:
     """state-dict keys and symbolic shapes of the reference's fusion head over the modalities ``names`` (feature width of modality i: "d<i+1>")"""
     keys = {"classifier.0.weight": ("h1", "ne"), "classifier.0.bias": ("h1",), "classifier.3.weight": ("n", "h1"), "classifier.3.bias": ("n",),

@@ -157,6 +157,31 @@ class FusionPredictor:
             return tokenize(self.last_texts)
         audio[0].tokens_from_states = tokens
 
+    def transcribe_with_ctc(self, head, detokenize=None, tokenize=None) -> None:
+        """Texts from a CTC checkpoint's greedy transcript: ``head`` (``engine.CTCHead``) sits behind the encoder of one of the speech
+        ``AudioStream``s, whose snapshot is the CTC checkpoint's.  One forward of that stream then feeds both the fusion head (its selected
+        state) and the text stream (the last state, through the head): ``detokenize(ids) -> str`` (default: the ids as decimal numbers,
+        what preprocessing/transcribe_ctc.py writes without vocabulary files) and ``tokenize(texts) -> (input_ids, attention_mask)`` turn
+        the ids into the text stream's input.  A batch whose error word is set raises ``SerHipError``, like a failed forward."""
+        audio = [s for s in self.streams if isinstance(s, AudioStream) and s.enc is head.enc]
+        if not audio or not any(isinstance(s, TextStream) for s in self.streams):
+            raise ValueError("CTC transcription needs the audio stream whose encoder the CTC head sits behind, and a text stream")
+        if tokenize is None:
+            raise ValueError("CTC transcription needs tokenize(texts) -> (input_ids, attention_mask)")
+        detok = detokenize or (lambda ids: " ".join(str(t) for t in ids))
+
+        def tokens(hs, B):
+            from .engine import CTCHead
+            words = head.forward_tokens(hs).cpu().numpy()
+            part = CTCHead.unpack(words, B, max(hs.frames(b) for b in range(B)))
+            if part["err"]:
+                hs.take_range_bits()                    # predict() will not get to it: a bit left set would fail the next batch's first forward
+                raise SerHipError(f"transcription failed: CTC error word {part['err']:#x} (a frame's winning logit was not finite)")
+            self.last_ids = [[int(t) for t in part["ids"][b, : int(part["counts"][b])]] for b in range(B)]
+            self.last_texts = [detok(ids) for ids in self.last_ids]
+            return tokenize(self.last_texts)
+        audio[0].tokens_from_states = tokens
+
     @staticmethod
     def _source(s, hs, counts):
         """the stream's rows inside its forward's states, ``counts[b]`` of them from each utterance's first row"""
@@ -284,7 +309,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
                    checkpoints: Optional[Sequence[str]] = None, test_csv: Optional[str] = None, mode: str = "f16mf", text_mode: str = "f16x",
                    head_mode: Optional[str] = None, batch_size: int = 16, num_workers: int = 4, tokenizer_path: str = "", max_len: int = 80,
                    synthetic_weights: bool = False, seed: int = 7, device: Optional[str] = None, tokenize=None, transcribe: bool = False,
-                   spec: Optional[C.GenerationSpec] = None, detokenize=None, language=None) -> Dict:
+                   spec: Optional[C.GenerationSpec] = None, detokenize=None, language=None, transcribe_ctc: bool = False) -> Dict:
     """``head.score(engine="hip")`` from the corpus itself: the ``FileName`` column of ``test_csv``, wavs from ``config["wav_dir"]``
     (16 kHz), transcripts from the table ``config["txt_dir"]`` (columns FileName, transcription), the head's weights from
     ``<model_path>/multimodal_ser.pt`` -> ``<model_path>/results/test.csv`` in ``head.score``'s format.  ``encoders``: two or three
@@ -296,7 +321,9 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     decoded, has no transcript or is empty is printed and gets no row; a batch whose range-guard or GRU error word is set is retried file
     by file (``batchloop.run_or_each``).  ``transcribe``: the texts are the Whisper stream's own transcripts (``FusionPredictor.transcribe_with``) and ``txt_dir`` is not
     read; ``spec`` (default: the checkpoint's generation_config.json, with ``language``) and ``detokenize`` (default: the checkpoint's
-    tokenizer from local files, else the ids as numbers) belong to it.  Returns {"csv", "n", "failed"}."""
+    tokenizer from local files, else the ids as numbers) belong to it.  ``transcribe_ctc``: the texts are the greedy CTC transcripts of the
+    first speech stream whose snapshot is a CTC checkpoint (``FusionPredictor.transcribe_with_ctc``; ``detokenize`` default: the
+    snapshot's vocab.json, else the ids as numbers) and ``txt_dir`` is not read.  Returns {"csv", "n", "failed"}."""
     from . import head as HD
     from .driver import _Extractor, find_weights, hf_tokenize_fn
     from .engine import build_encoder
@@ -324,6 +351,16 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     if transcribe and not (any(g is not None and g.family == C.FAMILY_WHISPER and g.decoder_layers > 0 for g in geos)
                            and any(g is not None and g.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA) for g in geos)):
         raise ValueError("transcribe needs a Whisper encoder whose checkpoint has a decoder, and a text encoder")
+    ctc_head, ctc_at = None, -1
+    if transcribe_ctc:
+        if transcribe:
+            raise ValueError("transcribe and transcribe_ctc are two sources of the same texts: choose one")
+        speech = C.SPEECH_FAMILIES + (C.FAMILY_W2V_BERT,)
+        ctc_at = next((i for i, g in enumerate(geos) if g is not None and g.family in speech and C.resolve_ctc(encoders[i], checkpoints[i]) is not None), -1)
+        if ctc_at < 0 or not any(g is not None and g.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA) for g in geos):
+            raise ValueError("transcribe_ctc needs an audio encoder whose snapshot is a CTC checkpoint (config.json names one of "
+                             + ", ".join(C.CTC_ARCHITECTURES) + "), and a text encoder")
+    own_text = transcribe or transcribe_ctc               # the texts come out of an audio stream: txt_dir is not read
     for i, (name, geo) in enumerate(zip(encoders, geos)):
         if geo is None:
             streams.append(RowsStream(int(config[f"feat{i + 1}_dim"])))
@@ -355,11 +392,16 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
             continue
         text = geo.family in (C.FAMILY_ROBERTA, C.FAMILY_DEBERTA)
         whisper = geo.family == C.FAMILY_WHISPER
-        sd, src = find_weights(name, checkpoints[i], synthetic_weights, seed, geo)
+        if i == ctc_at:
+            from .weights import CTC_HEAD_PREFIXES, split_ctc_head
+            sd, src = find_weights(name, checkpoints[i], False, seed, geo, keep=CTC_HEAD_PREFIXES)      # never synthetic: they have no lm_head
+            sd, ctc_sd = split_ctc_head(sd)
+        else:
+            sd, src = find_weights(name, checkpoints[i], synthetic_weights, seed, geo)
         if text:
             if tokenize is None:
                 tokenize = hf_tokenize_fn(tokenizer_path or name, max_len, geo.family)
-            if not texts and not transcribe:
+            if not texts and not own_text:
                 from .transcribe import read_table
                 texts = read_table(config["txt_dir"])
             enc = build_encoder(geo, sd, dev, text_mode)
@@ -368,6 +410,14 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
             m = _Extractor.supported_mode(geo, mode, whisper, name)
             enc = build_encoder(geo, sd, dev, m, normalize=True if whisper else C.resolve_do_normalize(name, checkpoints[i]))
             streams.append(AudioStream(enc, layers[i], averages[i]))
+            if i == ctc_at:
+                from .ctc import load_vocab
+                from .engine import CTCHead
+                ctc_head = CTCHead(enc, ctc_sd, C.resolve_ctc(name, checkpoints[i]))
+                if detokenize is None:
+                    cfg_json = C.find_config_json(name, checkpoints[i])
+                    vocab = load_vocab(os.path.dirname(cfg_json) if cfg_json else name)
+                    detokenize = None if vocab is None else vocab.text
             if transcribe and whisper and decoder is None and geo.decoder_layers > 0:
                 from .engine import WhisperDecoder
                 from .transcribe import load_tokenizer
@@ -390,6 +440,8 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     pred = FusionPredictor(streams, head_sd, head_mode)
     if transcribe:
         pred.transcribe_with(decoder, spec, tokenize, detokenize)
+    if transcribe_ctc:
+        pred.transcribe_with_ctc(ctc_head, detokenize, tokenize)
     has_text, has_rows = any(isinstance(s, TextStream) for s in streams), any(isinstance(s, RowsStream) for s in streams)
     log.info("Starting scoring test samples...")
     done, rows_out, failed = [], [], 0
@@ -406,7 +458,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
             if len(wave) < 1:
                 raise ValueError("empty waveform")
             text = None
-            if has_text and not transcribe:
+            if has_text and not own_text:
                 if name not in texts:
                     raise KeyError(f"no transcript in {config['txt_dir']}")
                 text = texts[name]
@@ -424,7 +476,7 @@ def score_from_wav(config: Dict, encoders: Sequence[str], layers: Optional[Seque
     def run(items):
         """items: (name, waveform, transcript, rows); appends the rows of a clean batch, raises what a failed one raises"""
         ids = mask = None
-        if has_text and not transcribe:
+        if has_text and not own_text:
             ids, mask = tokenize([it[2] for it in items])
         out = pred.predict([it[1] for it in items], ids, mask, [it[3] for it in items] if has_rows else None)
         for it, row in zip(items, out):
@@ -474,6 +526,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--synthetic_weights", action="store_true")
     p.add_argument("--transcribe", action="store_true", help="texts from the Whisper stream's own transcripts (no txt_dir)")
     p.add_argument("--language", type=str, default=None, help="with --transcribe: e.g. en; default: detected per utterance")
+    p.add_argument("--transcribe_ctc", action="store_true",
+                   help="texts from the greedy CTC transcripts of the audio encoder whose snapshot is a CTC checkpoint (no txt_dir)")
     a = p.parse_args(argv)
     with open(a.config_path, "r") as f:
         config = json.load(f)
@@ -482,5 +536,5 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     score_from_wav(config, pick("encoder"), pick("layer"), pick("average"), pick("checkpoint"), test_csv=a.test_csv, mode=a.mode,
                    text_mode=a.text_mode, head_mode=a.head_mode, batch_size=a.batch_size, num_workers=a.num_workers,
                    tokenizer_path=a.tokenizer_path, max_len=a.max_len, synthetic_weights=a.synthetic_weights, seed=a.seed,
-                   transcribe=a.transcribe, language=a.language)
+                   transcribe=a.transcribe, language=a.language, transcribe_ctc=a.transcribe_ctc)
     return 0

@@ -278,17 +278,18 @@ def apply_stress(sd: StateDict, geo: EncoderGeometry, kind: str) -> StateDict:
 _STRIP_PREFIXES = ("wavlm.", "wav2vec2_bert.", "wav2vec2.", "hubert.", "data2vec_audio.", "model.", "roberta.", "deberta.")
 
 
-def normalize_names(sd: StateDict) -> StateDict:
+def normalize_names(sd: StateDict, keep: tuple = ()) -> StateDict:
     """Strip task-head wrappers (``wav2vec2.`` / ``data2vec_audio.`` in *ForCTC checkpoints, ``model.``
     in WhisperForConditionalGeneration) and drop everything off the encoder path
-    (decoder, lm_head, quantizer, masked_spec_embed)."""
+    (decoder, lm_head, quantizer, masked_spec_embed).  ``keep``: name prefixes that stay all the same
+    (``CTC_HEAD_PREFIXES`` for the CTC drivers, which read ``lm_head``)."""
     out: StateDict = {}
     for k, v in sd.items():
         for p in _STRIP_PREFIXES:
             if k.startswith(p):
                 k = k[len(p):]
                 break
-        if k.startswith(("decoder.", "lm_head", "proj_out", "quantizer", "project_", "masked_spec_embed", "pooler.",
+        if not (keep and k.startswith(tuple(keep))) and k.startswith(("decoder.", "lm_head", "proj_out", "quantizer", "project_", "masked_spec_embed", "pooler.",
                          "embeddings.position_ids")):
             continue
         out[k] = v.detach().to(torch.float32).contiguous()
@@ -366,6 +367,28 @@ def check_xvector_head(head_sd: StateDict, D: int, spec, num_states: int) -> Non
                              f"{tuple(spec.tdnn_kernel)}, xvector_output_dim {spec.xvector_output_dim}, {num_states} hidden states)")
 
 
+CTC_HEAD_KEYS = ("lm_head.weight", "lm_head.bias")
+CTC_HEAD_PREFIXES = ("lm_head.",)
+
+
+def split_ctc_head(sd: StateDict):
+    """(encoder tensors, head tensors) of a state dict of a CTC checkpoint normalised with ``keep=CTC_HEAD_PREFIXES`` (plain
+    ``normalize_names`` drops ``lm_head``).  A snapshot without a head comes back whole."""
+    enc = {k: v for k, v in sd.items() if k not in CTC_HEAD_KEYS}
+    head = {k: sd[k] for k in CTC_HEAD_KEYS if k in sd}
+    return enc, head
+
+
+def check_ctc_head(head_sd: StateDict, D: int, vocab_size: int) -> None:
+    """Names and shapes of the head tensors against the encoder width and ``vocab_size`` (``ValueError`` naming the key)."""
+    want = {"lm_head.weight": (vocab_size, D), "lm_head.bias": (vocab_size,)}
+    for k, shape in want.items():
+        if k not in head_sd:
+            raise ValueError(f"{k} is missing from the checkpoint (a CTC head needs {', '.join(want)})")
+        if tuple(head_sd[k].shape) != shape:
+            raise ValueError(f"{k}: shape {tuple(head_sd[k].shape)}, expected {shape} (hidden width {D}, vocab_size {vocab_size})")
+
+
 def merge_lora(sd: StateDict, lora_alpha: float = 16.0) -> StateDict:
     """Fold PEFT LoRA adapters into their base weights (next row 8f-4).  The reference fine-tunes WavLM with
     ``LoraConfig(r=8, lora_alpha=16, target_modules=['q_proj','v_proj'])`` inside a classifier wrapper and extracts
@@ -402,10 +425,10 @@ def merge_lora(sd: StateDict, lora_alpha: float = 16.0) -> StateDict:
     return out
 
 
-def load_checkpoint(path: str, lora_alpha: float = 16.0) -> StateDict:
+def load_checkpoint(path: str, lora_alpha: float = 16.0, keep: tuple = ()) -> StateDict:
     """Read a local checkpoint file or directory.  Raises ``OSError`` when nothing
     loadable is found -- the error class the reference's driver reports as
-    "No pretrained model found" (preprocess_speech.py:115-117)."""
+    "No pretrained model found" (preprocess_speech.py:115-117).  ``keep``: ``normalize_names``'s."""
     candidates = []
     if os.path.isdir(path):
         for fn in sorted(os.listdir(path)):
@@ -422,7 +445,7 @@ def load_checkpoint(path: str, lora_alpha: float = 16.0) -> StateDict:
             sd.update(load_file(fn, device="cpu"))
         else:
             sd.update(torch.load(fn, map_location="cpu", weights_only=True))
-    return normalize_names(merge_lora(sd, lora_alpha))
+    return normalize_names(merge_lora(sd, lora_alpha), keep)
 
 
 def fold_wavlm_gate(w8: torch.Tensor, b8: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, heads: int, head_dim: int):
