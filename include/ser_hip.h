@@ -693,6 +693,67 @@ typedef struct ser_ctc_greedy_args {
 } ser_ctc_greedy_args;
 int ser_ctc_greedy_v(const ser_ctc_greedy_args* args, void* stream);
 
+/* a32 (added under ABI 18: new entry points only)  CTC forced alignment: the single best CTC path that spells a GIVEN target, per
+ * utterance of a packed ragged batch of a31's logits.  Not a command-list op.
+ *
+ * The rule, one utterance: fp32 logits z[T, V] (rows frame_offs[b] .. frame_offs[b + 1] - 1 of z), the blank id, a target y[0 .. L-1]
+ * (targets[tgt_offs[b] .. tgt_offs[b + 1] - 1], int32 on the device), every y[j] in [0, V) and != blank.
+ *   states     S = 2 L + 1; state s emits the blank when s is even and y[s / 2] when s is odd
+ *   emission   e(t, s) = (double) z[t, label(s)]: RAW logits (a frame's log-sum-exp shifts every path alike and stays out)
+ *   alpha      float64.  alpha[0][0] = e(0, 0), alpha[0][1] = e(0, 1), the rest -inf;
+ *              alpha[t][s] = max(alpha[t-1][s], alpha[t-1][s-1], alpha[t-1][s-2]) + e(t, s), the third term only for odd s >= 3 with
+ *              y[s/2] != y[s/2 - 1].  One max of exact values and one float64 addition per cell, every fp32 -> double conversion exact,
+ *              nothing to contract: a numpy float64 loop reproduces every alpha bit for bit (tests/ctc_align_ref.py).
+ *   ties       the smaller jump wins (stay, then step, then skip: a candidate replaces the current one only when strictly greater); the
+ *              path ends in state S - 1 only when alpha[T-1][S-1] > alpha[T-1][S-2], else in S - 2.  L == 0: state 0, every frame blank.
+ *   feasible   iff T >= 1 and T >= L + #{j : y[j] == y[j-1]}
+ * Outputs per utterance: pos[t] (optional, [rows]) the target index whose state frame t is in, -1 for a blank frame; starts[b, j] /
+ * ends[b, j] the first frame of token j and one past its last (contiguous by construction); path_logit[b] the final alpha (float64);
+ * frame_score[t] (optional, [rows]) = fp32((double) z[t, c_t] - lse64[t]), c_t the emitted label and lse64[t] the float64 log-sum-exp of
+ * row t's V columns (max subtracted first): the path's log-probability per frame; tok_score[b, j] = fp32 of the float64 mean of
+ * frame_score over the token's frames, summed in frame order.  starts / ends / tok_score are [B, ld_tok], ld_tok >= max_tokens; entries
+ * at j >= L_b are not written.  Columns V .. ldz - 1 are NEVER read.
+ * status[b] (always written), 0 or ONE of, checked in this order:
+ *   SER_CTC_ALIGN_BAD_TARGET  a target id outside [0, V) or equal to the blank, L_b > max_tokens (or > SER_CTC_ALIGN_MAX_TOKENS), more
+ *                             than max_frames frames, or offsets that leave [0, rows] / [0, n_targets]
+ *   SER_CTC_ALIGN_INFEASIBLE  too few frames (the feasibility rule above)
+ *   SER_CTC_ALIGN_NONFINITE   a logit in a column of {blank} U y, at any of the utterance's frames, is NaN or +inf, or the best score
+ *                             is not finite (-inf is a legal logit; a NaN in any OTHER column sets no status: that frame's lse64, and
+ *                             with it frame_score and its token's tok_score, are then NaN)
+ * A non-zero status leaves the utterance's other outputs unspecified (path_logit may be written); every other utterance's outputs are
+ * exactly what they would be without it.
+ * work: 8-byte aligned, work_bytes >= ser_ctc_align_work_bytes(rows, B, max_frames, max_tokens) = 16 rows (lse64, the path's states and
+ * the frame scores) + B * max_frames * 16 * ceil((2 max_tokens + 1) / 64) (the back pointers); -1 for arguments ser_ctc_align_v refuses.
+ *
+ * Two kernels.  lse64: a grid over all rows on a31's lane-group split.  Alignment: ONE block of SER_CTC_ALIGN_THREADS threads per
+ * utterance, state s on thread s % THREADS, frames the serial loop: three reads of the previous alpha row (two float64 rows in LDS, so one
+ * barrier per frame), one max, one add, one write; the next frame's emissions are loaded before the barrier; the back pointers are two
+ * bits per cell, packed by two wave ballots per 64 states.  The backtrack (T dependent reads, once) runs on one thread over chunks of
+ * back pointers the block copies into LDS; pos, frame_score, the spans and the token means are parallel passes.
+ * Determinism: no atomics; max and compare are exact; the lse's sum order is a function of V alone and a token's mean is one thread's
+ * sum in frame order.  Every output is a pure function of (the utterance's rows of z, its target, blank), whatever shares the batch.
+ * Refused before any launch: -1 null pointer (z, frame_offs, targets, tgt_offs, work, starts, ends, tok_score, status, path_logit);
+ * -2 sizes (B < 1 or > 65535, V < 1, rows < 1, max_frames < 1, n_targets < 0, max_tokens outside [0, SER_CTC_ALIGN_MAX_TOKENS], blank
+ * outside [0, V), work_bytes too small); -3 pitches / alignment (ldz < V, ld_tok < max_tokens, z not 4-byte, work or path_logit not
+ * 8-byte aligned). */
+#define SER_CTC_ALIGN_THREADS 512
+#define SER_CTC_ALIGN_MAX_TOKENS 1023
+#define SER_CTC_ALIGN_INFEASIBLE 1
+#define SER_CTC_ALIGN_NONFINITE 2
+#define SER_CTC_ALIGN_BAD_TARGET 4
+typedef struct ser_ctc_align_args {
+    const float* z; int64_t ldz;
+    const int32_t* frame_offs;
+    const int32_t* targets; const int32_t* tgt_offs;
+    void* work; int64_t work_bytes;
+    int32_t* starts; int32_t* ends; float* tok_score; int64_t ld_tok;
+    int32_t* status; double* path_logit;
+    int32_t* pos; float* frame_score;
+    int32_t B, V, rows, blank, max_frames, max_tokens, n_targets, reserved0;
+} ser_ctc_align_args;
+int ser_ctc_align_v(const ser_ctc_align_args* args, void* stream);
+int64_t ser_ctc_align_work_bytes(int32_t rows, int32_t B, int32_t max_frames, int32_t max_tokens);
+
 /* a23 (added under ABI 18: new entry points only)  The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334,
  * MultiModalEmotionClassifier) on packed ragged batches: every utterance alone, as the reference's evaluation runs it (batch_size = 1,
  * bin/eval_cat_bimodal_lazy_1head.py:292) -- no pad frame enters the recurrence, the attention or a pooling softmax.  None of the four is a

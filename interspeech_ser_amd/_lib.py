@@ -237,6 +237,18 @@ class CtcGreedyArgs(C.Structure):
     ]
 
 
+class CtcAlignArgs(C.Structure):
+    """Mirror of ``ser_ctc_align_args``."""
+    _fields_ = [
+        ("z", c_void_p), ("ldz", c_i64), ("frame_offs", c_void_p), ("targets", c_void_p), ("tgt_offs", c_void_p),
+        ("work", c_void_p), ("work_bytes", c_i64),
+        ("starts", c_void_p), ("ends", c_void_p), ("tok_score", c_void_p), ("ld_tok", c_i64), ("status", c_void_p), ("path_logit", c_void_p),
+        ("pos", c_void_p), ("frame_score", c_void_p),
+        ("B", C.c_int32), ("V", C.c_int32), ("rows", C.c_int32), ("blank", C.c_int32), ("max_frames", C.c_int32), ("max_tokens", C.c_int32),
+        ("n_targets", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class GruArgs(C.Structure):
     """Mirror of ``ser_gru_args``."""
     _fields_ = [
@@ -439,6 +451,12 @@ DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked 
 DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
 CTC_CHUNK = 256                 # SER_CTC_CHUNK: frames per chunk of ser_ctc_greedy_v's collapse
 CTC_ERR_NONFINITE = 1           # ser_ctc_greedy_v *err bit 0: a frame's winning logit was not finite
+WAVE = 64                       # lanes of a wave: a ballot of ser_ctc_align_v packs the back pointers of 64 consecutive states
+CTC_ALIGN_THREADS = 512         # SER_CTC_ALIGN_THREADS: threads of ser_ctc_align_v's block (state s on thread s % THREADS)
+CTC_ALIGN_MAX_TOKENS = 1023     # SER_CTC_ALIGN_MAX_TOKENS: the longest target of ser_ctc_align_v
+CTC_ALIGN_INFEASIBLE = 1        # ser_ctc_align_v status: too few frames for the target
+CTC_ALIGN_NONFINITE = 2         # a NaN or +inf in a column the trellis reads, or a best score that is not finite
+CTC_ALIGN_BAD_TARGET = 4        # a target id outside [0, V) or equal to the blank, or a target / utterance over the limits
 
 
 class _CmdUnion(C.Union):
@@ -472,7 +490,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_attention_rk_args": AttentionRkArgs, "ser_conformer_conv_args": ConformerConvArgs,
                   "ser_swish_rows_args": SwishRowsArgs, "ser_layer_pool_args": LayerPoolArgs, "ser_cls_tail_args": ClsTailArgs,
                   "ser_layer_mix_args": LayerMixArgs, "ser_stat_pool_args": StatPoolArgs, "ser_xvec_tail_args": XvecTailArgs,
-                  "ser_ctc_greedy_args": CtcGreedyArgs,
+                  "ser_ctc_greedy_args": CtcGreedyArgs, "ser_ctc_align_args": CtcAlignArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -502,6 +520,8 @@ _SIGNATURES = {
     "ser_stat_pool_v": (c_int, [c_void_p, c_void_p]),
     "ser_xvec_tail_v": (c_int, [c_void_p, c_void_p]),
     "ser_ctc_greedy_v": (c_int, [c_void_p, c_void_p]),
+    "ser_ctc_align_v": (c_int, [c_void_p, c_void_p]),
+    "ser_ctc_align_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),

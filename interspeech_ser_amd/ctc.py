@@ -8,6 +8,10 @@ behind it (engine.CTCHead), so what comes back per batch is one buffer of token 
 Semantics: every utterance alone.  The ids of a file are those of the HF class given that file at batch size 1 with no padding and no
 attention mask, then ``argmax(-1)``, whatever else shares its ragged batch.  Greedy only: no beams, no language model.  A CTC transcript
 is not Whisper's: the 960h models write upper-case letters without punctuation.
+
+Forced alignment (``CTCAligner``, ``run_align``) rides on the same forward: given an utterance and its KNOWN text (Whisper's transcript),
+the best CTC path that spells it, found on the device (engine.CTCHead.forward_align, ser_ctc_align_v): where each character and word
+starts and ends, and the mean log-probability the acoustic model gives it.
 """
 from __future__ import annotations
 
@@ -154,6 +158,151 @@ class CTCTranscriber(_Extractor):
         return ids
 
 
+class Alignment:
+    """One utterance's forced alignment: the target ``ids``, per id its ``spans`` (first frame, one past the last) and ``tok_scores`` (the
+    mean log-probability of its frames), ``score`` (the float64 mean of ALL frames' log-probabilities on the path, blanks included),
+    ``path_logit`` (the best path's sum of raw logits), and per frame ``pos`` (the index into ``ids``, -1 for a blank frame) and
+    ``frame_scores``."""
+    __slots__ = ("ids", "spans", "tok_scores", "score", "path_logit", "pos", "frame_scores")
+
+    def __init__(self, ids, spans, tok_scores, score, path_logit, pos, frame_scores):
+        self.ids, self.spans, self.tok_scores, self.score, self.path_logit = ids, spans, tok_scores, score, path_logit
+        self.pos, self.frame_scores = pos, frame_scores
+
+
+class AlignmentError(ValueError):
+    """an utterance's non-zero status word (``_lib.CTC_ALIGN_*``)"""
+
+    def __init__(self, status: int, frames: int, tokens: int):
+        from . import _lib
+        why = {_lib.CTC_ALIGN_INFEASIBLE: f"{frames} frames are too few for a target of {tokens} tokens",
+               _lib.CTC_ALIGN_NONFINITE: "a logit on the target's columns is NaN or +Inf, or no path has a finite score",
+               _lib.CTC_ALIGN_BAD_TARGET: f"the target ({tokens} tokens, at most {_lib.CTC_ALIGN_MAX_TOKENS}) holds the blank or an id outside the vocabulary"}
+        super().__init__(why.get(status, f"alignment status {status:#x}"))
+        self.status = status
+
+
+def split_align_blob(words: np.ndarray, frame_offs: Sequence[int], targets: Sequence[Sequence[int]]) -> list:
+    """per utterance the ``Alignment`` of one batch's host copy (engine.CTCHead.unpack_align's layout, frames included), or the
+    ``AlignmentError`` of its status word: an utterance fails alone"""
+    from . import _lib
+    from .engine import CTCHead
+    B, rows = len(targets), int(frame_offs[-1])
+    Lm = min(max(len(y) for y in targets), _lib.CTC_ALIGN_MAX_TOKENS)
+    p = CTCHead.unpack_align(words, B, Lm, rows)
+    out = []
+    for b, y in enumerate(targets):
+        r0, r1, L = int(frame_offs[b]), int(frame_offs[b + 1]), len(y)
+        if int(p["status"][b]):
+            out.append(AlignmentError(int(p["status"][b]), r1 - r0, L))
+            continue
+        fs = p["frame_score"][r0:r1].copy()
+        out.append(Alignment([int(t) for t in y], [(int(s), int(e)) for s, e in zip(p["starts"][b, :L], p["ends"][b, :L])],
+                             [float(v) for v in p["tok_score"][b, :L]], float(fs.astype(np.float64).mean()), float(p["path_logit"][b]),
+                             p["pos"][r0:r1].copy(), fs))
+    return out
+
+
+class CTCAligner(CTCTranscriber):
+    """Encoder + CTC head + forced alignment on one GPU: ``CTCTranscriber`` whose ``submit`` / ``collect`` / ``extract`` carry one target
+    (a sequence of token ids) per utterance.  The slot's D2H copy is ``engine.CTCHead.forward_align``'s buffer.  ``collect`` and ``extract``
+    return per utterance an ``Alignment`` or the ``AlignmentError`` of its status word."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.vocab: Optional["CTCVocab"] = None                          # ``align``'s default for text targets
+        self._targets: Dict[int, list] = {}                              # slot -> the targets ``select`` aligns (set ahead of the forward)
+
+    def select(self, hs, layer_index, slot: int = 0) -> torch.Tensor:
+        return self.head.forward_align(hs, self._targets[slot], slot=slot, frames=True).view(torch.float32).view(-1, 1)
+
+    def extract(self, waves: List[np.ndarray], targets=None, rates=None) -> list:
+        """One ragged batch and its targets -> one result per utterance, synchronously (slot 0)."""
+        self._targets[0] = targets = [list(y) for y in targets]
+        dev, lengths = self.upload_resampled(waves, rates)
+        hs = self.enc.forward(dev, lengths)
+        out = self.select(hs, None)
+        bits = hs.take_range_bits()
+        host = out.cpu().numpy().copy()
+        self._check_range(bits)
+        return split_align_blob(host.reshape(-1).view(np.int32), hs.frame_offs, targets)
+
+    def submit(self, waves: List[np.ndarray], targets=None, slot: int = 0, rates=None):
+        self._targets[slot] = targets = [list(y) for y in targets]
+        ticket = _Extractor.submit(self, waves, None, slot, rates)
+        ticket["targets"] = targets
+        return ticket
+
+    def collect(self, ticket) -> list:
+        ticket["event"].synchronize()
+        if ticket.get("watch") is not None:
+            self._check_range(int(ticket["watch"][0]))
+        return split_align_blob(ticket["host"].numpy().copy().reshape(-1).view(np.int32), ticket["frame_offs"], ticket["targets"])
+
+    def align(self, waves: Sequence[np.ndarray], targets: Sequence, vocab: Optional["CTCVocab"] = None) -> List[Optional[Alignment]]:
+        """16 kHz mono waveforms and per item a target (token ids, or a text that ``vocab.encode`` turns into ids) -> per item an
+        ``Alignment`` or None, through the two-slot pipeline.  A batch that fails as a whole (the fp16 range guard, an utterance too
+        short for the stem) is retried item by item; an item whose status word is set fails ALONE: it is printed, listed in
+        ``self.failed`` as (index, error) and gets None, and its batch mates are not run again."""
+        waves = [np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w in waves]
+        if len(targets) != len(waves):
+            raise ValueError(f"{len(targets)} targets for {len(waves)} waveforms")
+        vocab = vocab or self.vocab
+        if any(isinstance(y, str) for y in targets) and vocab is None:
+            raise ValueError("a text target needs the vocabulary (vocab=, or the aligner's .vocab)")
+        tg = [vocab.encode(y) if isinstance(y, str) else [int(t) for t in y] for y in targets]
+        out: List[Optional[Alignment]] = [None] * len(waves)
+        self.failed = []
+
+        def fail(item, err):
+            self.failed.append((item[0], err))
+            print(f"Failed to process item {item[0]}: {err}")
+
+        def done(good, got, ticket):
+            for item, r in zip(good, got):
+                if isinstance(r, Exception):
+                    fail(item, r)
+                else:
+                    out[item[0]] = r
+
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()                          # slot 0's arena is shared with the synchronous path
+        pipe = SlotPipeline(submit=lambda good, slot: self.submit([w for _, w, _ in good], [y for _, _, y in good], slot=slot),
+                            collect=self.collect, extract=lambda good: self.extract([w for _, w, _ in good], [y for _, _, y in good]),
+                            slots=self.SLOTS, done=done, fail=fail,
+                            before_retry=torch.cuda.synchronize if torch.cuda.is_available() else None)
+        for bi, batch in enumerate(make_batches([(i, w, y) for i, (w, y) in enumerate(zip(waves, tg))], self.batch_size)):
+            pipe.push(bi, batch)
+            pipe.drain()
+        pipe.drain(0)
+        return out
+
+
+def words(alignment: Alignment, encoded_words) -> List[tuple]:
+    """[(word, start frame, end frame, score)] of an alignment whose target was ``CTCVocab.join(encoded_words)``: a word's span runs from
+    its first id's first frame to one past its last id's last frame, its score is the float64 mean of its frames' log-probabilities
+    (the token means weighted by their span lengths, on the host).  An unalignable word (no ids) gets None times and score."""
+    n_ids = sum(len(ids) for _, ids in encoded_words)
+    n_words = sum(1 for _, ids in encoded_words if ids)
+    gap = 1 if n_words > 1 and len(alignment.ids) == n_ids + n_words - 1 else 0          # a word delimiter between two alignable words
+    if len(alignment.ids) != n_ids + gap * (n_words - 1):
+        raise ValueError(f"the alignment has {len(alignment.ids)} ids, the words {n_ids}")
+    out, j = [], 0
+    for word, ids in encoded_words:
+        if not ids:
+            out.append((word, None, None, None))
+            continue
+        n = len(ids)
+        if alignment.ids[j:j + n] != [int(t) for t in ids]:
+            raise ValueError(f"the alignment's ids do not spell the words (at {word!r})")
+        spans, sc = alignment.spans[j:j + n], alignment.tok_scores[j:j + n]
+        total = sum(e - s for s, e in spans)
+        score = sum(np.float64(v) * (e - s) for v, (s, e) in zip(sc, spans)) / np.float64(total)
+        out.append((word, spans[0][0], spans[-1][1], float(score)))
+        j += n + gap
+    return out
+
+
 # ------------------------------------------------------------------------------- vocabulary
 def _token(v, default):
     """a special token of tokenizer_config.json / special_tokens_map.json: a string, or an AddedToken dict with ``content``"""
@@ -210,6 +359,44 @@ class CTCVocab:
                 offs.append((int(offsets[j][0]), int(offsets[j][1])))
         return out, offs
 
+    def _specials(self) -> set:
+        """tokens that never spell a character: pad, unk, the word delimiter, and every multi-character token (<s>, </s>, ...)"""
+        return {self.pad_token, self.unk_token, self.word_delimiter_token} | {t for t in self.encoder if len(t) != 1}
+
+    def encode_words(self, text: str) -> List[Tuple[str, List[int]]]:
+        """[(word, [ids])] of a text that did not come from this vocabulary (Whisper's transcript): the inverse of ``chars``.  The text is
+        split on whitespace; per character the first of c, c.upper(), c.lower() whose every character is a vocabulary token is taken
+        (so "ß" against an upper-case vocabulary is "SS"); everything else is dropped (digits, punctuation).  A word left with no
+        ids is UNALIGNABLE."""
+        special = self._specials()
+        ok = lambda t: t in self.encoder and t not in special                     # noqa: E731
+        out = []
+        for word in str(text).split():
+            ids: List[int] = []
+            for c in word:
+                for form in (c, c.upper(), c.lower()):
+                    if form and all(ok(t) for t in form):
+                        ids.extend(self.encoder[t] for t in form)
+                        break
+            out.append((word, ids))
+        return out
+
+    def join(self, encoded_words) -> List[int]:
+        """the alignment target of ``encode_words``'s result: the alignable words' ids joined by the word-delimiter id (where the
+        vocabulary has one), no delimiter at either end and none doubled around an unalignable word"""
+        delim = self.encoder.get(self.word_delimiter_token)
+        out: List[int] = []
+        for _, ids in encoded_words:
+            if not ids:
+                continue
+            if out and delim is not None:
+                out.append(delim)
+            out.extend(ids)
+        return out
+
+    def encode(self, text: str) -> List[int]:
+        return self.join(self.encode_words(text))
+
     def text(self, ids: Sequence[int]) -> str:
         s = "".join(self.chars(ids)[0]).strip()
         return s.lower() if self.do_lower_case else s
@@ -257,7 +444,7 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _build_transcriber(args, device: str) -> CTCTranscriber:
+def _build_transcriber(args, device: str, cls=None) -> "CTCTranscriber":
     """The shared load path of the drivers: config.json -> geometry and head spec, weights by ``find_weights`` with ``lm_head`` kept."""
     from .weights import CTC_HEAD_PREFIXES
     spec = C.resolve_ctc(args.model, args.checkpoint)                 # first: a CTC class over an unbuilt encoder is named as such
@@ -266,40 +453,42 @@ def _build_transcriber(args, device: str) -> CTCTranscriber:
     geo = C.resolve_geometry(args.model, args.checkpoint)
     geo = C.resolve_fbank(geo, args.model, args.checkpoint)
     sd, source = find_weights(args.model, args.checkpoint, False, 0, geo, keep=CTC_HEAD_PREFIXES)
-    tr = CTCTranscriber(geo, spec, sd, device, args.mode, args.batch_size, normalize=C.resolve_do_normalize(args.model, args.checkpoint))
+    tr = (cls or CTCTranscriber)(geo, spec, sd, device, args.mode, args.batch_size, normalize=C.resolve_do_normalize(args.model, args.checkpoint))
     tr.weight_source = source
     return tr
 
 
-def run(argv: Optional[Sequence[str]] = None, transcriber_factory=None, vocab: Optional[CTCVocab] = None) -> int:
-    """``transcriber_factory(args, device)`` replaces the model (the host tests hand in a stub with ``submit`` / ``collect`` / ``extract``
-    / ``hop``): everything around the model call then runs without a GPU.  ``vocab`` replaces the vocabulary files."""
-    args = build_parser().parse_args(argv)
+def _build_aligner(args, device: str) -> "CTCAligner":
+    return _build_transcriber(args, device, CTCAligner)
+
+
+def _open(args, factory):
+    """The set-up both command lines share: (sorted file names, the model object), or None after the printed error (exit code 0, as the
+    extraction drivers do)."""
     device = "cuda:0" if torch.cuda.is_available() else "cpu"
     try:
         names = sorted(fn for fn in os.listdir(args.wav_dir) if os.path.isfile(os.path.join(args.wav_dir, fn)))
     except OSError as e:
         print(f"Error reading {args.wav_dir}: {e}")
         print("Something went wrong, make sure everything is correct before running again!")
-        return 0
+        return None
     print(f"{len(names)} file are going to be processed...")
-    if device == "cpu" and transcriber_factory is None:
+    if device == "cpu" and factory in (_build_transcriber, _build_aligner):
         print("Error: no MI355X visible -- this build has no CPU path (the CPU oracle under oracle/ is test-only)")
         print("Something went wrong, make sure everything is correct before running again!")
-        return 0
+        return None
     try:
-        tr = (transcriber_factory or _build_transcriber)(args, device)
+        tr = factory(args, device)
     except (OSError, NotImplementedError) as e:
         print(f"Error: No pretrained model found with the name {args.model}")
         print(f"  ({e})")
         print("Something went wrong, make sure everything is correct before running again!")
-        return 0
+        return None
     print(f"Weights: {getattr(tr, 'weight_source', 'caller')}; numerics mode {getattr(tr, 'mode', args.mode)}")
-    if vocab is None:
-        vocab = load_vocab(args.tokenizer_path or args.model)
-    gpu_resample = args.resample and hasattr(tr, "upload_resampled")
-    seconds = float(getattr(tr, "hop", 320)) / TARGET_SR
+    return names, tr
 
+
+def _decoder(args, gpu_resample: bool):
     def decode(name):
         """(name, (samples, their rate), None) or (name, None, error)."""
         path = os.path.join(args.wav_dir, name)
@@ -313,6 +502,22 @@ def run(argv: Optional[Sequence[str]] = None, transcriber_factory=None, vocab: O
             return name, (x, sr), None
         except Exception as e:                              # noqa: BLE001  (per-file failure, as in the extraction drivers)
             return name, None, e
+    return decode
+
+
+def run(argv: Optional[Sequence[str]] = None, transcriber_factory=None, vocab: Optional[CTCVocab] = None) -> int:
+    """``transcriber_factory(args, device)`` replaces the model (the host tests hand in a stub with ``submit`` / ``collect`` / ``extract``
+    / ``hop``): everything around the model call then runs without a GPU.  ``vocab`` replaces the vocabulary files."""
+    args = build_parser().parse_args(argv)
+    opened = _open(args, transcriber_factory or _build_transcriber)
+    if opened is None:
+        return 0
+    names, tr = opened
+    if vocab is None:
+        vocab = load_vocab(args.tokenizer_path or args.model)
+    gpu_resample = args.resample and hasattr(tr, "upload_resampled")
+    seconds = float(getattr(tr, "hop", 320)) / TARGET_SR
+    decode = _decoder(args, gpu_resample)
 
     rows: Dict[str, str] = {}
     offsets: Dict[str, list] = {}
@@ -362,4 +567,106 @@ def run(argv: Optional[Sequence[str]] = None, transcriber_factory=None, vocab: O
             json.dump({n: offsets[n] for n in done}, f)
     print(f"{len(done)} utterances on 1 GPU(s) in {dt:.2f} s ({len(done) / max(dt, 1e-9):.1f} utt/s)")
     print(f"Wrote {len(done)} of {len(names)} transcripts to {args.out_csv}; {failed} files failed")
+    return 0
+
+
+# ------------------------------------------------------------------------------- CLI: forced alignment
+def build_align_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="word times and acoustic scores of a transcript table, by CTC forced alignment with a hub AutoModelForCTC checkpoint")
+    p.add_argument("--model", type=str, required=True, help="hub id (offline HF cache) or local snapshot directory")
+    p.add_argument("--wav_dir", type=str, required=True)
+    p.add_argument("--df_path", type=str, required=True, help="FileName,transcription: the table transcribe_whisper.py / transcribe_ctc.py write")
+    p.add_argument("--out_json", type=str, required=True, help='{file: {"score": mean frame log-prob, "words": [[word, start_s, end_s, score], ...]}}')
+    p.add_argument("--mode", type=str, default="f16x", choices=list(MODES))
+    p.add_argument("--batch_size", type=int, default=16)
+    p.add_argument("--resample", action="store_true", help="accept non-16 kHz wav files (resampled on the GPU ahead of the forward)")
+    p.add_argument("--checkpoint", type=str, default="", help="local *.safetensors / pytorch_model.bin (or directory) instead of --model's weights")
+    p.add_argument("--tokenizer_path", type=str, default="", help="directory of vocab.json (default: --model's)")
+    p.add_argument("--chars", action="store_true", help='add "chars": [[char, start_s, end_s, score], ...] per file')
+    p.add_argument("--num_workers", type=int, default=4)
+    return p
+
+
+def _read_texts(path: str) -> Dict[str, str]:
+    """FileName -> transcription of the transcript table, an empty transcription as the empty string"""
+    import csv
+    with open(path, newline="", encoding="utf-8") as f:
+        return {str(r["FileName"]): str(r.get("transcription") or "") for r in csv.DictReader(f)}
+
+
+def run_align(argv: Optional[Sequence[str]] = None, aligner_factory=None, vocab: Optional[CTCVocab] = None) -> int:
+    """``aligner_factory(args, device)`` replaces the model (the host tests hand in a stub with ``submit`` / ``collect`` / ``extract`` /
+    ``hop``, whose results are ``Alignment`` or exception objects); ``vocab`` replaces the vocabulary files."""
+    args = build_align_parser().parse_args(argv)
+    if vocab is None:
+        vocab = load_vocab(args.tokenizer_path or args.model)
+    if vocab is None:                                               # (load_vocab has said which files are missing)
+        print("Error: forced alignment needs the checkpoint's vocabulary (vocab.json) to turn the transcripts into token ids")
+        print("Something went wrong, make sure everything is correct before running again!")
+        return 0
+    try:
+        texts = _read_texts(args.df_path)
+    except (OSError, KeyError, ValueError) as e:
+        print(f"Error reading {args.df_path}: {e}")
+        print("Something went wrong, make sure everything is correct before running again!")
+        return 0
+    opened = _open(args, aligner_factory or _build_aligner)
+    if opened is None:
+        return 0
+    names, tr = opened
+    gpu_resample = args.resample and hasattr(tr, "upload_resampled")
+    seconds = float(getattr(tr, "hop", 320)) / TARGET_SR
+    decode = _decoder(args, gpu_resample)
+    result: Dict[str, dict] = {}
+    failed = 0
+
+    def fail(name, err):
+        nonlocal failed
+        failed += 1
+        print(f"Failed to process {os.path.join(args.wav_dir, name)}: {err}")
+
+    def finished(good, out, ticket):
+        for (name, _, enc), r in zip(good, out):
+            if isinstance(r, Exception):
+                fail(name, r)
+                continue
+            entry = {"score": r.score,
+                     "words": [[w, None if s is None else s * seconds, None if e is None else e * seconds, sc] for w, s, e, sc in words(r, enc)]}
+            if args.chars:
+                ch, offs = vocab.chars(r.ids, r.spans)
+                entry["chars"] = [[c, s * seconds, e * seconds, sc] for c, (s, e), sc in zip(ch, offs, r.tok_scores)]
+            result[name] = entry
+
+    def go(fn, good, **k):
+        waves, tg = [w for _, (w, _), _ in good], [vocab.join(enc) for _, _, enc in good]
+        return fn(waves, tg, rates=[sr for _, (_, sr), _ in good], **k) if gpu_resample else fn(waves, tg, **k)
+
+    pipe = SlotPipeline(submit=lambda good, slot: go(tr.submit, good, slot=slot), collect=tr.collect, extract=lambda good: go(tr.extract, good),
+                        slots=getattr(tr, "SLOTS", 2), done=finished, fail=lambda item, err: fail(item[0], err),
+                        before_retry=torch.cuda.synchronize if torch.cuda.is_available() else None)
+    t0 = time.perf_counter()
+    with ThreadPoolExecutor(max_workers=max(1, args.num_workers)) as pool:
+        for bi, decoded in enumerate(prefetch(make_batches(names, max(1, args.batch_size)), pool, decode)):
+            good = []
+            for name, item, err in decoded:
+                if err is None and name not in texts:
+                    err = KeyError(f"no row for it in {args.df_path}")
+                enc = vocab.encode_words(texts[name]) if err is None else None
+                if err is None and not any(ids for _, ids in enc):
+                    err = ValueError(f"its transcription {texts[name]!r} has no word the vocabulary can spell")
+                if err is not None:
+                    fail(name, err)
+                else:
+                    good.append((name, item, enc))
+            if good:
+                pipe.push(bi, good)
+            pipe.drain()
+        pipe.drain(0)
+    dt = time.perf_counter() - t0
+    done = [n for n in names if n in result]
+    os.makedirs(os.path.dirname(os.path.abspath(args.out_json)), exist_ok=True)
+    with open(args.out_json, "w", encoding="utf-8") as f:
+        json.dump({n: result[n] for n in done}, f)
+    print(f"{len(done)} utterances on 1 GPU(s) in {dt:.2f} s ({len(done) / max(dt, 1e-9):.1f} utt/s)")
+    print(f"Wrote {len(done)} of {len(names)} alignments to {args.out_json}; {failed} files failed")
     return 0

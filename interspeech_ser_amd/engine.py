@@ -22,7 +22,7 @@ import copy
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -2150,6 +2150,7 @@ class CTCHead(_HeadBase):
         self.lm_head = enc._linear(w, b, mode=self.op_mode, name="lm_head.weight")
         self.w = torch.ones(1, dtype=torch.float64, device=self.device)
         self._bufs = SlotArenas(self._build_buffers)
+        self._abufs = SlotArenas(self._build_align_buffers)
         self._last: Dict[int, tuple] = {}                                 # slot -> (M, B, max_frames) of its last forward
 
     @staticmethod
@@ -2175,9 +2176,10 @@ class CTCHead(_HeadBase):
                     work=torch.empty(2 * M, dtype=torch.int32, device=dev),
                     blob=torch.empty(cap["blob"], dtype=torch.int32, device=dev), tab=TableBlob(cap["B"], 1, dev))
 
-    def forward_tokens(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
-        """int32 [blob_words(B, max_frames)] on the device (``unpack`` names its parts; a view of the slot's buffer, valid until the slot's
-        next forward): one D2H copy brings a batch's counts, ids, offsets, smallest margins and error word back.  ``hs.states`` is only read."""
+    def _lm_head(self, hs: HiddenStates, slot: int, blob: Callable[[int, int], int]):
+        """The part ``forward_tokens`` and ``forward_align`` share: the operand copy of the last state and the lm_head GEMM into the slot's
+        fp32 logits.  Returns (the slot's buffers, the device frame offsets, rows, B, the longest utterance's frames, the stream);
+        ``blob(B, frames)``: the words the caller needs of the slot's token blob."""
         if hs.computed < len(hs):
             raise IndexError(f"the head needs the last hidden state (run the forward without last_state: states 0..{hs.computed - 1} of "
                              f"{len(hs)} were computed)")
@@ -2188,12 +2190,11 @@ class CTCHead(_HeadBase):
         Tm = max(hs.frames(b) for b in range(B))
         if M < 1 or Tm < 1:
             raise ValueError("the batch has no frames")
-        n = self.blob_words(B, Tm)
-        bf = self._bufs.fit(slot, M=M, B=B, blob=n)
+        bf = self._bufs.fit(slot, M=M, B=B, blob=blob(B, Tm))
         st = _stream()
         offs = hs.frame_offs_dev if hs.frame_offs_dev is not None else _head_offs(bf["tab"], hs.frame_offs)
         flag = hs.range_flag.data_ptr() if (hs.range_flag is not None and self.op_mode == _lib.MODE_FP16X) else None
-        enc, xa, z, blob = self.enc, bf["xa"].first_rows(M), bf["z"], bf["blob"]
+        enc, xa, z = self.enc, bf["xa"].first_rows(M), bf["z"]
         m = _lib.LayerMixArgs()
         m.s, m.state_stride, m.lds, m.w = s[-1].data_ptr(), 0, s.stride(1), self.w.data_ptr()
         m.out_act, m.ldo_act, m.out_plane_stride, m.range_flag = xa.ptr, xa.cols, xa.plane_stride, flag
@@ -2205,6 +2206,15 @@ class CTCHead(_HeadBase):
             self._step("lm_head", lambda: enc._gemm(xa, self.lm_head, M, out_f32=z, ldo_f32=self.Vp, mode=self.op_mode))
         finally:
             enc._flag, enc._st = prev_flag, prev_st
+        self._last[slot] = (M, B, Tm)
+        return bf, offs, M, B, Tm, st
+
+    def forward_tokens(self, hs: HiddenStates, slot: int = 0) -> torch.Tensor:
+        """int32 [blob_words(B, max_frames)] on the device (``unpack`` names its parts; a view of the slot's buffer, valid until the slot's
+        next forward): one D2H copy brings a batch's counts, ids, offsets, smallest margins and error word back.  ``hs.states`` is only read."""
+        bf, offs, M, B, Tm, st = self._lm_head(hs, slot, self.blob_words)
+        n = self.blob_words(B, Tm)
+        z, blob = bf["z"], bf["blob"]
         blob[n - 1: n].zero_()                                            # the error word
         p0, nt = blob.data_ptr(), 4 * B * Tm
         g = _lib.CtcGreedyArgs()
@@ -2213,7 +2223,75 @@ class CTCHead(_HeadBase):
         g.min_margin, g.err = p0 + 4 * B + 3 * nt, p0 + 4 * (n - 1)
         g.B, g.V, g.rows, g.blank, g.max_frames = B, self.V, M, self.blank, Tm
         self._step("ctc_greedy", lambda: check(lib.ser_ctc_greedy_v(C.byref(g), st), "ser_ctc_greedy_v"))
-        self._last[slot] = (M, B, Tm)
+        return blob[:n]
+
+    # ---- forced alignment (ser_ctc_align_v): the same logits, a given target per utterance
+    @staticmethod
+    def align_words(B: int, max_tokens: int, rows: int = 0) -> int:
+        """int32 words of a batch's alignment: status [B] | starts [B, Lm] | ends [B, Lm] | tok_score [B, Lm] (fp32 bits) | one pad word
+        when that many are odd | path_logit [B] (float64 bits, two words each) | with ``rows``: pos [rows] | frame_score [rows] (fp32 bits);
+        Lm = max(max_tokens, 1)"""
+        return CTCHead._align_tail(B, max(int(max_tokens), 1)) + 2 * B + 2 * rows
+
+    @staticmethod
+    def _align_tail(B: int, Lm: int) -> int:
+        """the word offset of path_logit: behind status and the three [B, Lm] tables, rounded up to an even word (8-byte aligned)"""
+        n = B + 3 * B * Lm
+        return n + (n & 1)
+
+    @staticmethod
+    def unpack_align(words, B: int, max_tokens: int, rows: int = 0) -> dict:
+        """The host copy of ``forward_align``'s buffer (numpy int32 [align_words]) as its parts (views)"""
+        import numpy as np
+        w = np.asarray(words).reshape(-1).view(np.int32)
+        Lm = max(int(max_tokens), 1)
+        n = B * Lm
+        part = lambda i: w[B + i * n: B + (i + 1) * n].reshape(B, Lm)             # noqa: E731
+        o = CTCHead._align_tail(B, Lm)
+        out = dict(status=w[:B], starts=part(0), ends=part(1), tok_score=part(2).view(np.float32), path_logit=w[o: o + 2 * B].view(np.float64))
+        if rows:
+            out["pos"] = w[o + 2 * B: o + 2 * B + rows]
+            out["frame_score"] = w[o + 2 * B + rows: o + 2 * B + 2 * rows].view(np.float32)
+        return out
+
+    def _build_align_buffers(self, cap: Dict[str, int]) -> dict:
+        """buffers of one slot's alignment: the kernel's work bytes, the result, and the blob that carries tgt_offs | targets up (one
+        region each: ``tab`` regions hold 2 cap + 4 int32 words)"""
+        dev = self.device
+        return dict(work=torch.empty((cap["work"] + 7) // 8, dtype=torch.int64, device=dev),
+                    blob=torch.empty(cap["blob"], dtype=torch.int32, device=dev), tab=TableBlob(cap["tab"], 2, dev))
+
+    def forward_align(self, hs: HiddenStates, targets, slot: int = 0, frames: bool = False) -> torch.Tensor:
+        """int32 [align_words(B, max tokens, rows if frames)] on the device (``unpack_align`` names its parts; a view of the slot's
+        buffer, valid until the slot's next ``forward_align``): the best CTC path of utterance b that spells ``targets[b]`` (a sequence
+        of token ids), behind the same operand copy and lm_head as ``forward_tokens``.  A target the kernel refuses (an id outside the
+        vocabulary, the blank, more than ``_lib.CTC_ALIGN_MAX_TOKENS`` ids) or cannot place comes back in that utterance's status word."""
+        B = hs.batch
+        if len(targets) != B:
+            raise ValueError(f"{len(targets)} targets for a batch of {B}")
+        tgt_offs = [0]
+        for y in targets:
+            tgt_offs.append(tgt_offs[-1] + len(y))
+        flat = [int(v) for y in targets for v in y]
+        nt = len(flat)
+        Lm = min(max(len(y) for y in targets), _lib.CTC_ALIGN_MAX_TOKENS)          # a longer target is the kernel's BAD_TARGET
+        bf, offs, M, B, Tm, st = self._lm_head(hs, slot, lambda B, Tm: 1)        # (the token blob is forward_tokens')
+        n = self.align_words(B, Lm, M if frames else 0)
+        wb = int(lib.ser_ctc_align_work_bytes(M, B, Tm, Lm))
+        ab = self._abufs.fit(slot, work=wb, blob=n, tab=max(B, (nt + 1) // 2))
+        tab = ab["tab"].begin()
+        d_offs, d_tgt = tab.put32(tgt_offs), tab.put32(flat or [0])       # (never an empty view: its address is an argument)
+        tab.send()
+        blob, Lp = ab["blob"], max(Lm, 1)
+        p0, o = blob.data_ptr(), self._align_tail(B, Lp)
+        a = _lib.CtcAlignArgs()
+        a.z, a.ldz, a.frame_offs, a.targets, a.tgt_offs = bf["z"].data_ptr(), self.Vp, offs.data_ptr(), d_tgt.data_ptr(), d_offs.data_ptr()
+        a.work, a.work_bytes = ab["work"].data_ptr(), 8 * ab["work"].numel()
+        a.status, a.starts, a.ends, a.tok_score, a.ld_tok = p0, p0 + 4 * B, p0 + 4 * (B + B * Lp), p0 + 4 * (B + 2 * B * Lp), Lp
+        a.path_logit = p0 + 4 * o
+        a.pos, a.frame_score = (p0 + 4 * (o + 2 * B), p0 + 4 * (o + 2 * B + M)) if frames else (None, None)
+        a.B, a.V, a.rows, a.blank, a.max_frames, a.max_tokens, a.n_targets = B, self.V, M, self.blank, Tm, Lm, nt
+        self._step("ctc_align", lambda: check(lib.ser_ctc_align_v(C.byref(a), st), "ser_ctc_align_v"))
         return blob[:n]
 
     def logits(self, slot: int = 0) -> torch.Tensor:
