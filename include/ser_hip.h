@@ -754,6 +754,103 @@ typedef struct ser_ctc_align_args {
 int ser_ctc_align_v(const ser_ctc_align_args* args, void* stream);
 int64_t ser_ctc_align_work_bytes(int32_t rows, int32_t B, int32_t max_frames, int32_t max_tokens);
 
+/* a33 (added under ABI 18: new entry points, one ser_cmd member and one SER_OP code only)  Whisper token timestamps from the decoder's
+ * cross-attention: HF's WhisperGenerationMixin._extract_token_timestamps for EVERY UTTERANCE ALONE (batch 1, greedy short-form generate,
+ * return_token_timestamps=True, num_frames = len(samples) / 160), restated.  P = 4 prompt positions; an utterance whose generated tokens are
+ * g_0 .. g_{n-1} (the last one eos, or the token at the length cap) has R = n - 1 token rows: the cross-attention of the steps that FEED
+ * g_0 .. g_{n-2}, positions P .. P + n - 2.  F = (len / 160) / 2 frames.  What shares the batch changes nothing.
+ *
+ * The rule, one utterance, alignment heads (layer_k, head_k), k < A, in list order:
+ *   weights  w_k[r][s] = softmax over ALL n_keys keys s of scale * <q_k[P + r], K_k[s]> (float64 dot and softmax over the fp32 queries and
+ *            the fp32 cross cache, as HF's softmax runs over max_source_positions), rounded to fp32; frames s < F are kept
+ *   z-score  per (k, f): mean and BIASED std over the utterance's R rows, float64, sums in ascending row order (two passes);
+ *            z = (w - mean) / std
+ *   median   per (k, r): the median of `width` (odd; 7) along the frames with reflect padding; F <= width / 2 leaves z as it is.  A
+ *            selection: exact
+ *   mean     over the heads, added in list order, divided by A; ONE rounding to fp32: matrix[R][F]
+ *   DTW      HF's _dynamic_time_warping on -matrix.  cost is fp32 [R + 1][F + 1], +inf but cost[0][0] = 0.  Frames j ascending, rows i
+ *            ascending: c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1]; c = c0 (trace 0) if c0 < c1 and c0 < c2, else c1
+ *            (trace 1) if c1 < c0 and c1 < c2, else c2 (trace 2); cost[i][j] = fp32(double(-matrix[i-1][j-1]) + double(c)).  One exact
+ *            conversion each, one float64 add, one rounding: a numpy loop reproduces every cell bit for bit (tests/whisper_ts_ref.py).
+ *            Backtrace from (R, F) while i > 0 or j > 0: emit (i - 1, j - 1); row 0 is forced left (trace 2), column 0 up (trace 1).
+ *            first_frame[r] = the frame of the path's earliest cell in row r (HF's jump times / time_precision)
+ *   times    token k < n - 1: first_frame[k] * 0.02 s; the last token repeats the one before it (HF has no cross-attention row for it)
+ * Edge cases, settled against HF (tools/make_whisper_timestamps_golden.py):
+ *   n = 1   R = 0: no rows, the time is 0; nothing is launched for the utterance's rows
+ *   n = 2   R = 1: the std over one row is 0, the row is NaN, every comparison of the DTW is false and the path runs along row 0: time 0.
+ *           ser_ts_matrix_v sets no status for R = 1; ser_dtw_v follows the rule through the NaNs (its status is SER_TS_NONFINITE, which
+ *           the caller ignores for R = 1)
+ *   F <= 3  (width 7) the median filter returns its input
+ *   F = 0   with R >= 1: SER_TS_NO_FRAMES; the file fails alone
+ *   any other non-finite matrix entry or z-score (a column whose std is 0 with R >= 2): SER_TS_NONFINITE for that utterance alone, never a
+ *   silent time
+ *
+ * ser_dec_keep_q_v (SER_OP_DEC_KEEP_Q): the capture of one decode step and one layer: copies the layer's alignment heads' cross queries
+ * q[b][head[h] * 64 .. + 64] (fp32, the output of the cross q projection, before the scale) to keep[*pos][b][slot0 + h][0 .. 64];
+ * keep is [max_pos][B][n_align][64] fp32.  A position outside [0, max_pos) writes nothing.  One launch of n_heads x B waves.
+ * ser_ts_weights_v: keep, the cross cache (K of layer l, utterance b, key s, head h at cross + l layer_stride + b batch_stride + s ldc +
+ * 64 h), n_rows[b] = R_b and n_frames[b] = F_b on the device -> w [B][n_align][max_rows][ld_w] fp32; entries at r >= R_b or s >= F_b are
+ * not written.  A block takes 4 token rows of one (utterance, head): each key is read once for the four.  The softmax sum: a thread adds
+ * keys t, t + 256, .. in order, the lanes meet by xor shuffles, the four waves are added in wave order: a function of n_keys alone.
+ * ser_ts_matrix_v: w -> matrix [B][max_rows][ld_m] fp32 and status[b] (always written: 0, SER_TS_BAD_SHAPE for R_b outside [0, max_rows]
+ * or F_b outside [0, max_frames], SER_TS_NO_FRAMES, SER_TS_NONFINITE); stats is work of B * n_align * max_frames * 16 bytes.
+ * ser_dtw_v: matrix -> first_frame [B][ld_t] int32 (entries r < R_b), status[b] (always written; SER_TS_NONFINITE when the final cost is not
+ * finite -- the outputs still follow the rule), optionally the path in BACKTRACE order (path_text / path_time [B][max_rows + max_frames],
+ * path_len[b]; all three or none).  One block of SER_TS_THREADS threads per utterance, thread = token row (max_rows <= SER_TS_THREADS),
+ * anti-diagonal wavefront: three diagonals of fp32 costs in LDS, one barrier per diagonal (R + F - 1 of them); a thread reads its matrix
+ * row a block of 8 diagonals ahead and packs its 2-bit back pointers 32 to a 64-bit word of work (work_bytes >= ser_dtw_work_bytes(B, max_rows,
+ * max_frames) = 8 B max_rows ceil(max_frames / 32); -1 for sizes ser_dtw_v refuses).  The backtrack runs on one thread over bands of
+ * SER_TS_BAND frames the block stages in LDS.
+ * Determinism: no atomics on data; every output of an utterance is a pure function of its own queries, keys, R and F.
+ * Refused before any launch: -1 null pointer, -2 sizes, -3 pitches / alignment, each naming the argument. */
+#define SER_TS_THREADS 512
+#define SER_TS_BAND 256
+#define SER_TS_MAX_KEYS 1536
+#define SER_TS_MAX_HEADS 32
+#define SER_TS_KEEP_HEADS 16
+#define SER_TS_NONFINITE 1
+#define SER_TS_BAD_SHAPE 2
+#define SER_TS_NO_FRAMES 4
+typedef struct ser_dec_keep_q_args {
+    const float* q; int64_t ldq;
+    const int32_t* pos;
+    float* keep;
+    int32_t head[SER_TS_KEEP_HEADS];
+    int32_t n_heads, slot0, n_align, B, H, max_pos;
+} ser_dec_keep_q_args;
+int ser_dec_keep_q_v(const ser_dec_keep_q_args* args, void* stream);
+typedef struct ser_ts_weights_args {
+    const float* keep;
+    const float* cross; int64_t layer_stride; int64_t batch_stride; int64_t ldc;
+    const int32_t* n_rows; const int32_t* n_frames;
+    float* w; int64_t ld_w;
+    float scale;
+    int32_t B, n_align, n_keys, pos0, max_rows, max_pos, n_layers, H, reserved0;
+    int32_t head_layer[SER_TS_MAX_HEADS];
+    int32_t head_index[SER_TS_MAX_HEADS];
+} ser_ts_weights_args;
+int ser_ts_weights_v(const ser_ts_weights_args* args, void* stream);
+typedef struct ser_ts_matrix_args {
+    const float* w; int64_t ld_w;
+    const int32_t* n_rows; const int32_t* n_frames;
+    double* stats;
+    float* matrix; int64_t ld_m;
+    int32_t* status;
+    int32_t B, n_align, max_rows, max_frames, width, reserved0;
+} ser_ts_matrix_args;
+int ser_ts_matrix_v(const ser_ts_matrix_args* args, void* stream);
+typedef struct ser_dtw_args {
+    const float* matrix; int64_t ld_m;
+    const int32_t* n_rows; const int32_t* n_frames;
+    void* work; int64_t work_bytes;
+    int32_t* first_frame; int64_t ld_t;
+    int32_t* status;
+    int32_t* path_text; int32_t* path_time; int32_t* path_len;
+    int32_t B, max_rows, max_frames, reserved0;
+} ser_dtw_args;
+int ser_dtw_v(const ser_dtw_args* args, void* stream);
+int64_t ser_dtw_work_bytes(int32_t B, int32_t max_rows, int32_t max_frames);
+
 /* a23 (added under ABI 18: new entry points only)  The reference's bimodal fusion head (bin/train_cat_bimodal_lazy_1head.py:236-334,
  * MultiModalEmotionClassifier) on packed ragged batches: every utterance alone, as the reference's evaluation runs it (batch_size = 1,
  * bin/eval_cat_bimodal_lazy_1head.py:292) -- no pad frame enters the recurrence, the attention or a pooling softmax.  None of the four is a
@@ -1170,6 +1267,7 @@ int ser_swish_rows_v(const ser_swish_rows_args* args, void* stream);
 #define SER_OP_ATTENTION_RK 21
 #define SER_OP_CONFORMER_CONV 22
 #define SER_OP_SWISH_ROWS 23
+#define SER_OP_DEC_KEEP_Q 24
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -1196,6 +1294,7 @@ typedef struct ser_cmd {
         ser_attention_rk_args attention_rk;
         ser_conformer_conv_args conformer_conv;
         ser_swish_rows_args  swish_rows;
+        ser_dec_keep_q_args  dec_keep_q;
     } u;
 } ser_cmd;
 

@@ -249,6 +249,44 @@ class CtcAlignArgs(C.Structure):
     ]
 
 
+class DecKeepQArgs(C.Structure):
+    """Mirror of ``ser_dec_keep_q_args``."""
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_i64), ("pos", c_void_p), ("keep", c_void_p), ("head", C.c_int32 * 16),
+        ("n_heads", C.c_int32), ("slot0", C.c_int32), ("n_align", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("max_pos", C.c_int32),
+    ]
+
+
+class TsWeightsArgs(C.Structure):
+    """Mirror of ``ser_ts_weights_args``."""
+    _fields_ = [
+        ("keep", c_void_p), ("cross", c_void_p), ("layer_stride", c_i64), ("batch_stride", c_i64), ("ldc", c_i64),
+        ("n_rows", c_void_p), ("n_frames", c_void_p), ("w", c_void_p), ("ld_w", c_i64), ("scale", c_float),
+        ("B", C.c_int32), ("n_align", C.c_int32), ("n_keys", C.c_int32), ("pos0", C.c_int32), ("max_rows", C.c_int32), ("max_pos", C.c_int32),
+        ("n_layers", C.c_int32), ("H", C.c_int32), ("reserved0", C.c_int32),
+        ("head_layer", C.c_int32 * 32), ("head_index", C.c_int32 * 32),
+    ]
+
+
+class TsMatrixArgs(C.Structure):
+    """Mirror of ``ser_ts_matrix_args``."""
+    _fields_ = [
+        ("w", c_void_p), ("ld_w", c_i64), ("n_rows", c_void_p), ("n_frames", c_void_p), ("stats", c_void_p),
+        ("matrix", c_void_p), ("ld_m", c_i64), ("status", c_void_p),
+        ("B", C.c_int32), ("n_align", C.c_int32), ("max_rows", C.c_int32), ("max_frames", C.c_int32), ("width", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class DtwArgs(C.Structure):
+    """Mirror of ``ser_dtw_args``."""
+    _fields_ = [
+        ("matrix", c_void_p), ("ld_m", c_i64), ("n_rows", c_void_p), ("n_frames", c_void_p), ("work", c_void_p), ("work_bytes", c_i64),
+        ("first_frame", c_void_p), ("ld_t", c_i64), ("status", c_void_p),
+        ("path_text", c_void_p), ("path_time", c_void_p), ("path_len", c_void_p),
+        ("B", C.c_int32), ("max_rows", C.c_int32), ("max_frames", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class GruArgs(C.Structure):
     """Mirror of ``ser_gru_args``."""
     _fields_ = [
@@ -457,6 +495,14 @@ CTC_ALIGN_MAX_TOKENS = 1023     # SER_CTC_ALIGN_MAX_TOKENS: the longest target o
 CTC_ALIGN_INFEASIBLE = 1        # ser_ctc_align_v status: too few frames for the target
 CTC_ALIGN_NONFINITE = 2         # a NaN or +inf in a column the trellis reads, or a best score that is not finite
 CTC_ALIGN_BAD_TARGET = 4        # a target id outside [0, V) or equal to the blank, or a target / utterance over the limits
+TS_THREADS = 512                # SER_TS_THREADS: threads of ser_dtw_v's block = its most token rows
+TS_BAND = 256                   # SER_TS_BAND: frames per band of ser_dtw_v's backtrack
+TS_MAX_KEYS = 1536              # SER_TS_MAX_KEYS: the most cross keys ser_ts_weights_v takes (Whisper: 1500)
+TS_MAX_HEADS = 32               # SER_TS_MAX_HEADS: the most alignment heads
+TS_KEEP_HEADS = 16              # SER_TS_KEEP_HEADS: the most heads of one ser_dec_keep_q_v launch
+TS_NONFINITE = 1                # ser_ts_matrix_v / ser_dtw_v status: a z-score, matrix entry or final cost that is not finite
+TS_BAD_SHAPE = 2                # a row or frame count outside the buffers
+TS_NO_FRAMES = 4                # token rows but no frame
 
 
 class _CmdUnion(C.Union):
@@ -466,7 +512,7 @@ class _CmdUnion(C.Union):
                 ("prosody_mel", ProsodyMelArgs), ("fvq", FvqArgs), ("act_rows", ActRowsArgs),
                 ("codec_unit", CodecUnitArgs), ("codec_conv", CodecConvArgs), ("snake", SnakeArgs),
                 ("fbank", FbankArgs), ("relkey_table", RelkeyTableArgs), ("attention_rk", AttentionRkArgs),
-                ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs)]
+                ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs), ("dec_keep_q", DecKeepQArgs)]
 
 
 class Cmd(C.Structure):
@@ -479,6 +525,7 @@ OP_DEC_EMBED, OP_DEC_ATTN, OP_DEC_SELECT = 10, 11, 12
 OP_PROSODY_MEL, OP_FVQ, OP_ACT_ROWS = 13, 14, 15
 OP_CODEC_UNIT, OP_CODEC_CONV, OP_SNAKE = 16, 17, 18
 OP_FBANK, OP_RELKEY_TABLE, OP_ATTENTION_RK, OP_CONFORMER_CONV, OP_SWISH_ROWS = 19, 20, 21, 22, 23
+OP_DEC_KEEP_Q = 24
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -491,6 +538,8 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_swish_rows_args": SwishRowsArgs, "ser_layer_pool_args": LayerPoolArgs, "ser_cls_tail_args": ClsTailArgs,
                   "ser_layer_mix_args": LayerMixArgs, "ser_stat_pool_args": StatPoolArgs, "ser_xvec_tail_args": XvecTailArgs,
                   "ser_ctc_greedy_args": CtcGreedyArgs, "ser_ctc_align_args": CtcAlignArgs,
+                  "ser_dec_keep_q_args": DecKeepQArgs, "ser_ts_weights_args": TsWeightsArgs, "ser_ts_matrix_args": TsMatrixArgs,
+                  "ser_dtw_args": DtwArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -522,6 +571,11 @@ _SIGNATURES = {
     "ser_ctc_greedy_v": (c_int, [c_void_p, c_void_p]),
     "ser_ctc_align_v": (c_int, [c_void_p, c_void_p]),
     "ser_ctc_align_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ser_dec_keep_q_v": (c_int, [c_void_p, c_void_p]),
+    "ser_ts_weights_v": (c_int, [c_void_p, c_void_p]),
+    "ser_ts_matrix_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dtw_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dtw_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.c_int32]),
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),

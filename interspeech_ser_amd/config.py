@@ -545,8 +545,17 @@ class GenerationSpec:
     task_id: int
     max_length: int = 448
     language: object = None            # None, a token id, or a key of ``lang_to_id`` ("en" / "<|en|>") resolved by from_snapshot
+    alignment_heads: Tuple[Tuple[int, int], ...] = ()   # (decoder layer, head) pairs whose cross-attention carries the token times; () = absent
+    median_filter_width: int = 7       # config.json's (not generation_config.json's): the transcriber fills it in
 
     PROMPT_LEN = 4
+    TIME_PRECISION = 0.02              # seconds per encoder frame
+
+    def require_alignment_heads(self) -> Tuple[Tuple[int, int], ...]:
+        """The alignment heads, or the error that names what is missing: token times were asked of a checkpoint that has none."""
+        if not self.alignment_heads:
+            raise ValueError("token times need `alignment_heads` in generation_config.json, and this checkpoint's has none")
+        return self.alignment_heads
 
     @staticmethod
     def from_config(cfg: dict, language=None) -> "GenerationSpec":
@@ -567,12 +576,16 @@ class GenerationSpec:
         eos = cfg["eos_token_id"]
         eos = int(eos[0] if isinstance(eos, (list, tuple)) else eos)
         pad = cfg.get("pad_token_id")
+        heads = cfg.get("alignment_heads") or ()
+        if any(not isinstance(h, (list, tuple)) or len(h) != 2 or int(h[0]) < 0 or int(h[1]) < 0 for h in heads):
+            raise OSError("generation_config.json: alignment_heads must be a list of [layer, head] pairs")
         return GenerationSpec(
             decoder_start_token_id=int(cfg["decoder_start_token_id"]), eos_token_id=eos, pad_token_id=eos if pad is None else int(pad),
             suppress_tokens=tuple(int(t) for t in cfg.get("suppress_tokens") or ()),
             begin_suppress_tokens=tuple(int(t) for t in cfg.get("begin_suppress_tokens") or ()),
             no_timestamps_token_id=int(cfg["no_timestamps_token_id"]), lang_ids=tuple(sorted(lang_to_id.values())),
-            task_id=int(task_to_id["transcribe"]), max_length=int(cfg.get("max_length", 448)), language=language)
+            task_id=int(task_to_id["transcribe"]), max_length=int(cfg.get("max_length", 448)), language=language,
+            alignment_heads=tuple((int(l), int(h)) for l, h in heads), median_filter_width=int(cfg.get("median_filter_width", 7)))
 
     @staticmethod
     def from_snapshot(directory: str, language=None) -> "GenerationSpec":

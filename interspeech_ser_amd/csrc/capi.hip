@@ -127,6 +127,10 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_swish_rows_v(&c.u.swish_rows, stream);
                 break;
             }
+            case SER_OP_DEC_KEEP_Q: {
+                rc = ser_dec_keep_q_v(&c.u.dec_keep_q, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

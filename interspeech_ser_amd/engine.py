@@ -2624,7 +2624,13 @@ class DecodeResult:
     """One batch of ``WhisperDecoder.generate``: ``sequences`` int64 [B, n] (prompt, generated ids, eos / pad tail; n = the length at which
     every row had finished, else max_length), ``languages`` [B], ``lists`` (per utterance the generated ids without the prompt, up to and
     excluding eos), ``margins`` fp32 [B, n - 1] (top-1 minus top-2 masked logit of position p's decision, +inf where nothing was decided),
-    ``range_bits`` (fp16 range guard) and ``err`` (ser_dec_select_v's error word): the batch failed when either is set."""
+    ``range_bits`` (fp16 range guard) and ``err`` (ser_dec_select_v's error word): the batch failed when either is set.
+    After ``generate(..., token_times=True)`` also ``token_times`` (per utterance fp32 seconds of its n generated tokens, the closing eos
+    included: HF's ``token_timestamps`` behind the prompt; None where ``ts_status`` is set), ``token_frames`` (the n - 1 first frames) and
+    ``ts_status`` (int32 [B]: ser_ts_matrix_v's status, SER_TS_NO_FRAMES, or ser_dtw_v's for an utterance of two rows or more): an
+    utterance whose word is set fails ALONE.  ``ts_matrix``: the fp32 matrices on the device, [B, rows, pitch], until the next call."""
+
+    token_times = token_frames = ts_status = ts_matrix = None
 
     def __init__(self, sequences, languages, lists, margins, range_bits, err):
         self.sequences, self.languages, self.lists, self.margins = sequences, languages, lists, margins
@@ -2698,8 +2704,11 @@ class WhisperDecoder(_LaunchHost):
         return (self._dev_f32(sd[prefix + ".weight"]), self._dev_f32(sd[prefix + ".bias"]))
 
     # ------------------------------------------------------------------ buffers
-    def _plan(self, B: int, slot: int):
-        pl = self._plans.get((slot, B))
+    def _plan(self, B: int, slot: int, heads=None):
+        """``heads``: the alignment heads of the capture variant of the step (``generate(token_times=True)``), part of the plan's key; the
+        default plan (None) records exactly the launches it always did."""
+        key = (slot, B) if heads is None else (slot, B, tuple(heads))
+        pl = self._plans.get(key)
         if pl is not None:
             return pl
         geo, dev = self.geo, self.device
@@ -2717,14 +2726,48 @@ class WhisperDecoder(_LaunchHost):
         pl["kself"], pl["vself"] = ks[: L * B * T * D].view(L, B, T, D), vs[: L * B * T * D].view(L, B, T, D)
         pl["cross"] = cr[: L * B * S * 2 * D].view(L, B * S, 2 * D)
         pl["host"] = torch.empty(3, dtype=torch.int32).pin_memory()
+        pl["heads"] = None
+        if heads is not None:
+            heads = tuple((int(l), int(h)) for l, h in heads)
+            if not 1 <= len(heads) <= _lib.TS_MAX_HEADS or any(not (0 <= l < L and 0 <= h < geo.decoder_attention_heads) for l, h in heads):
+                raise ValueError(f"alignment_heads {heads} do not fit {L} decoder layers of {geo.decoder_attention_heads} heads "
+                                 f"(at most {_lib.TS_MAX_HEADS} pairs)")
+            if T - 1 > _lib.TS_THREADS or S > _lib.TS_MAX_KEYS:
+                raise ValueError(f"token times take up to {_lib.TS_THREADS} token rows and {_lib.TS_MAX_KEYS} keys")
+            pl["heads"] = heads
+            pl["keep"] = f32(T, B, len(heads), 64)              # the alignment heads' cross queries of every position
+            pl["ts_tab"] = TableBlob(B, 2, dev)                 # token rows | frames (int32)
+            pl["ts_out"] = i32(2 * B + B * T)                   # matrix status | DTW status | first frames [B, T]: one copy back
+            pl["ts_host"] = torch.empty(2 * B + B * T, dtype=torch.int32).pin_memory()
         self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
         pl["tape"] = tape = Tape()
         with self._launching(tape):
             self._step_launches(pl)
         if len(self._plans) >= 6:
             self._plans.pop(next(iter(self._plans)))
-        self._plans[(slot, B)] = pl
+        self._plans[key] = pl
         return pl
+
+    def _keep_q(self, pl, layer: int, qc: torch.Tensor) -> None:
+        """The capture of the step (ser_dec_keep_q_v): one launch per run of alignment heads that lie in ``layer``, after its cross q
+        projection."""
+        heads = pl["heads"]
+        geo = self.geo
+        k = 0
+        while k < len(heads):
+            if heads[k][0] != layer:
+                k += 1
+                continue
+            e = k
+            while e < len(heads) and heads[e][0] == layer and e - k < _lib.TS_KEEP_HEADS:
+                e += 1
+            a = self._cmd("dec_keep_q")
+            a.q, a.ldq, a.pos, a.keep = qc.data_ptr(), geo.hidden, pl["pos"].data_ptr(), pl["keep"].data_ptr()
+            for j in range(k, e):
+                a.head[j - k] = heads[j][1]
+            a.n_heads, a.slot0, a.n_align, a.B, a.H, a.max_pos = e - k, k, len(heads), pl["B"], geo.decoder_attention_heads, geo.max_target_positions
+            self._issue(_lib.OP_DEC_KEEP_Q, a, "ser_dec_keep_q")
+            k = e
 
     def _caches(self, B: int):
         """(self k, self v, cross k | v) flat fp32 storage for the largest batch seen.  A larger batch replaces it and drops every plan,
@@ -2773,6 +2816,8 @@ class WhisperDecoder(_LaunchHost):
             self._gemm(pl["ctx"], lay["out"], B, residual=x0, ldr=D, out_f32=x1, ldo_f32=D)
             self._layernorm(x1, D, lay["ln2"], B, D, out_act=pl["xa"])
             self._gemm(pl["xa"], lay["cq"], B, out_f32=qc, ldo_f32=D)
+            if pl["heads"] is not None:
+                self._keep_q(pl, i, qc)
             cross = pl["cross"][i]
             self._dec_attn(pl, qc, D, cross, cross.data_ptr() + 4 * D, 2 * D, S * 2 * D, S, len_add=S)
             self._gemm(pl["ctx"], lay["cout"], B, residual=x1, ldr=D, out_f32=x2, ldo_f32=D)
@@ -2839,16 +2884,16 @@ class WhisperDecoder(_LaunchHost):
         if rc != 0:
             check(rc, f"ser_run (decoder step, command {tape._failed.value})")
 
-    def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None):
+    def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None, token_times: bool = False):
         """Reset the slot's decoding state for a batch of B: ids[:, 0] = start, position 0, nothing finished.  ``forced_ids`` (tests:
-        teacher forcing): a whole id row to follow instead of the spec's prompt."""
+        teacher forcing): a whole id row to follow instead of the spec's prompt.  ``token_times``: the capture variant of the step."""
         spec = spec or self.spec
         if spec is None:
             raise ValueError("WhisperDecoder needs a GenerationSpec")
         geo = self.geo
         T = geo.max_target_positions
         n_max = min(int(spec.max_length), T)
-        pl = self._plan(B, slot)
+        pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None)
         language = spec.language if language is None else language
         forced = np.full(T, -1, dtype=np.int32)
         phase = np.zeros(T, dtype=np.int32)
@@ -2875,9 +2920,14 @@ class WhisperDecoder(_LaunchHost):
         return pl
 
     @_on_stream
-    def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0) -> DecodeResult:
-        """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``)."""
-        pl = self.begin(B, spec, language, slot)
+    def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0, token_times: bool = False,
+                 lengths: Optional[Sequence[int]] = None) -> DecodeResult:
+        """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``).
+        ``token_times``: also HF's ``token_timestamps`` of every utterance given alone (``DecodeResult.token_times``), from the alignment
+        heads' cross-attention; needs ``lengths``, the utterances' sample counts (HF's ``num_frames`` = length // 160)."""
+        if token_times and (lengths is None or len(lengths) != B):
+            raise ValueError("token times need the sample count of every utterance (lengths)")
+        pl = self.begin(B, spec, language, slot, token_times=token_times)
         spec = pl["spec"]
         self.project_cross(pl, enc_last)
         n_max, forced = pl["n_max"], pl["forced_host"]
@@ -2891,7 +2941,100 @@ class WhisperDecoder(_LaunchHost):
                 torch.cuda.current_stream().synchronize()
                 if int(host[0]) == 0:
                     break
-        return self.result(pl, steps)
+        res = self.result(pl, steps)
+        if token_times:
+            self._token_times(pl, res, lengths)
+        return res
+
+    def _ts_buffer(self, name: str, numel: int, dtype) -> torch.Tensor:
+        """Grow-only storage of the timestamp stages, the decoder's (like the caches: no two batches are in flight)."""
+        bufs = self.__dict__.setdefault("_ts_bufs", {})
+        t = bufs.get(name)
+        if t is None or t.numel() < numel:
+            bufs[name] = None
+            t = bufs[name] = torch.empty(numel, dtype=dtype, device=self.device)
+        return t
+
+    def _token_times(self, pl, res: DecodeResult, lengths: Sequence[int]) -> None:
+        """After the loop: weights (ser_ts_weights_v), matrix (ser_ts_matrix_v) and DTW (ser_dtw_v) of the whole batch on the forward's
+        stream, then ONE copy back: two status words and the first frames per utterance."""
+        geo, spec, heads = self.geo, pl["spec"], pl["heads"]
+        B, T, S, D, A = pl["B"], geo.max_target_positions, geo.max_source_positions, geo.hidden, len(heads)
+        P = spec.PROMPT_LEN
+        n_tok = []
+        for b in range(B):
+            gen = res.sequences[b, P:].tolist()
+            n_tok.append(gen.index(spec.eos_token_id) + 1 if spec.eos_token_id in gen else len(gen))
+        rows = [max(n - 1, 0) for n in n_tok]
+        frames = [min((int(l) // 160) // 2, S) for l in lengths]
+        R = max(1, max(rows))
+        ld = (S + 3) // 4 * 4
+        tab = pl["ts_tab"].begin()
+        d_rows, d_frames = tab.put32(np.asarray(rows, dtype=np.int32)), tab.put32(np.asarray(frames, dtype=np.int32))
+        tab.send()
+        w = self._ts_buffer("w", B * A * R * ld, torch.float32)
+        stats = self._ts_buffer("stats", B * A * S * 2, torch.float64)
+        mat = self._ts_buffer("matrix", B * R * ld, torch.float32)
+        work_bytes = int(lib.ser_dtw_work_bytes(B, R, S))
+        work = self._ts_buffer("work", work_bytes // 8, torch.int64)
+        out = pl["ts_out"]
+        st = self._s()
+        cross = pl["cross"]
+        trace = getattr(self, "ts_trace", None)             # when a list: (stage, start event, end event) per stage (tools/whisper_timestamps_bench.py)
+
+        def mark():
+            if trace is None:
+                return None
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            return e
+
+        t0 = mark()
+        wa = _lib.TsWeightsArgs()
+        wa.keep, wa.cross = pl["keep"].data_ptr(), cross.data_ptr()
+        wa.layer_stride, wa.batch_stride, wa.ldc = cross.stride(0), S * 2 * D, 2 * D
+        wa.n_rows, wa.n_frames, wa.w, wa.ld_w, wa.scale = d_rows.data_ptr(), d_frames.data_ptr(), w.data_ptr(), ld, 64 ** -0.5
+        wa.B, wa.n_align, wa.n_keys, wa.pos0, wa.max_rows, wa.max_pos = B, A, S, P, R, T
+        wa.n_layers, wa.H = geo.decoder_layers, geo.decoder_attention_heads
+        for k, (l, h) in enumerate(heads):
+            wa.head_layer[k], wa.head_index[k] = l, h
+        check(lib.ser_ts_weights_v(C.byref(wa), st), "ser_ts_weights")
+        t1 = mark()
+        ma = _lib.TsMatrixArgs()
+        ma.w, ma.ld_w, ma.n_rows, ma.n_frames, ma.stats = w.data_ptr(), ld, d_rows.data_ptr(), d_frames.data_ptr(), stats.data_ptr()
+        ma.matrix, ma.ld_m, ma.status = mat.data_ptr(), ld, out.data_ptr()
+        ma.B, ma.n_align, ma.max_rows, ma.max_frames, ma.width = B, A, R, S, int(spec.median_filter_width)
+        check(lib.ser_ts_matrix_v(C.byref(ma), st), "ser_ts_matrix")
+        t2 = mark()
+        da = _lib.DtwArgs()
+        da.matrix, da.ld_m, da.n_rows, da.n_frames = mat.data_ptr(), ld, d_rows.data_ptr(), d_frames.data_ptr()
+        da.work, da.work_bytes = work.data_ptr(), work_bytes
+        da.first_frame, da.ld_t, da.status = out.data_ptr() + 4 * 2 * B, T, out.data_ptr() + 4 * B
+        da.B, da.max_rows, da.max_frames = B, R, S
+        check(lib.ser_dtw_v(C.byref(da), st), "ser_dtw")
+        if trace is not None:
+            trace.extend((("weights", t0, t1), ("matrix", t1, t2), ("dtw", t2, mark())))
+        host = pl["ts_host"]
+        host.copy_(out, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        h = host.numpy()
+        first = h[2 * B:].reshape(B, T)
+        status = h[:B].copy()
+        res.token_frames, res.token_times = [], []
+        for b in range(B):
+            if rows[b] >= 1 and frames[b] < 1:
+                status[b] |= _lib.TS_NO_FRAMES
+            if rows[b] >= 2:
+                status[b] |= h[B + b]
+            fr = first[b, : rows[b]].astype(np.int64)
+            t = np.zeros(n_tok[b], dtype=np.float32)
+            if rows[b] >= 1:
+                t[: rows[b]] = (fr.astype(np.float64) * spec.TIME_PRECISION).astype(np.float32)
+                t[rows[b]] = t[rows[b] - 1]
+            res.token_frames.append(None if status[b] else fr)
+            res.token_times.append(None if status[b] else t)
+        res.ts_status = status
+        res.ts_matrix = mat[: B * R * ld].view(B, R, ld)
 
     def result(self, pl, steps: int) -> DecodeResult:
         spec = pl["spec"]

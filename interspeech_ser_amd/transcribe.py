@@ -4,11 +4,16 @@ The reference makes its transcript table with ``AutoModelForSpeechSeq2Seq.genera
 ``whisper_transcripts.csv``, columns FileName, transcription); ``preprocess_roberta.py --df_path`` and the heads' ``txt_dir`` read it.
 ``WhisperTranscriber.transcribe`` returns the generated token ids, ``.texts`` what ``batch_decode(skip_special_tokens=True)`` makes of them,
 ``run`` (preprocessing/transcribe_whisper.py) writes the table.
+
+``transcribe(..., token_times=True)`` also keeps HF's ``token_timestamps`` of every file given alone (``.token_times``), read from the
+alignment heads' cross-attention by the decoder itself (engine.WhisperDecoder.generate); ``token_words`` groups tokens into words as HF's
+``_combine_tokens_into_words`` does, and ``--times_json`` writes both.
 """
 from __future__ import annotations
 
 import argparse
 import csv
+import json
 import os
 from typing import List, Optional, Sequence
 
@@ -31,32 +36,53 @@ class WhisperTranscriber:
     def __init__(self, encoder, decoder, spec: C.GenerationSpec):
         self.enc, self.dec, self.spec = encoder, decoder, spec
         self.last_languages: List[Optional[int]] = []
+        self.token_times: List[Optional[List[float]]] = []      # per item of the last transcribe(token_times=True)
+        self.failed: List[str] = []                             # names of the files the last transcribe() left out
 
-    def _batch(self, waves: Sequence[np.ndarray], slot: int):
+    def _batch(self, waves: Sequence[np.ndarray], slot: int, token_times: bool = False):
         """(DecodeResult, failed) of one batch; one encoder forward serves the decoder (its LAST state: the forward does not stop early)."""
         lengths = [len(w) for w in waves]
         hs = self.enc.forward(self.enc.upload(waves, slot), lengths, slot=slot)
-        res = self.dec.generate(hs.states[-1], len(waves), self.spec, slot=slot)
+        extra = dict(token_times=True, lengths=lengths) if token_times else {}       # the default call is the one it always was
+        res = self.dec.generate(hs.states[-1], len(waves), self.spec, slot=slot, **extra)
         bits = hs.take_range_bits()
         return res, res.failed or bool(bits & 1), hs
 
-    def transcribe(self, waves: Sequence[np.ndarray], names: Optional[Sequence[str]] = None, first_batch: int = 0) -> List[Optional[List[int]]]:
+    def transcribe(self, waves: Sequence[np.ndarray], names: Optional[Sequence[str]] = None, first_batch: int = 0,
+                   token_times: bool = False) -> List[Optional[List[int]]]:
         """``first_batch``: the index of the first batch in the caller's own sequence of calls (a driver that hands over 16 files at a time
-        keeps the slots alternating with it)."""
+        keeps the slots alternating with it).  ``token_times``: ``self.token_times[i]`` becomes the seconds of item i's generated non-eos
+        tokens.  A file whose times have a status word set (no frame, a matrix entry that is not finite) fails ALONE: it is printed,
+        named in ``self.failed`` and has no times (its ids stay: the transcript table does not depend on the flag), and its batch mates are
+        neither touched nor run again."""
+        if token_times:
+            self.spec.require_alignment_heads()
         waves = [np.ascontiguousarray(w[:N_SAMPLES], dtype=np.float32) for w in waves]
         names = list(names) if names is not None else [f"utterance {i}" for i in range(len(waves))]
         out: List[Optional[List[int]]] = [None] * len(waves)
         self.last_languages = [None] * len(waves)
+        self.token_times = [None] * len(waves)
+        self.failed = []
+
+        def fail(j, res):
+            self.failed.append(names[j])
+            print(f"Failed to process {names[j]}: decoder error word {res.err:#x}, range-guard bits {res.range_bits:#x}")
+
         for n, idx in enumerate(make_batches(range(len(waves)), BATCH), start=int(first_batch)):
             def run(js):
-                res, failed, _ = self._batch([waves[j] for j in js], n % 2)
+                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times)
                 if failed:
                     return res
                 for k, j in enumerate(js):
                     out[j], self.last_languages[j] = res.lists[k], int(res.languages[k])
+                    if token_times and int(res.ts_status[k]) != 0:
+                        self.failed.append(names[j])
+                        print(f"Failed to process {names[j]}: token times status {int(res.ts_status[k]):#x} "
+                              f"({len(waves[j])} samples, {len(res.lists[k])} tokens)")
+                    elif token_times:
+                        self.token_times[j] = [float(t) for t in res.token_times[k][: len(res.lists[k])]]
 
-            run_or_each(idx, run, lambda j, res: print(f"Failed to process {names[j]}: decoder error word {res.err:#x}, "
-                                                       f"range-guard bits {res.range_bits:#x}"), catch=())
+            run_or_each(idx, run, fail, catch=())
         return out
 
     def texts(self, waves: Sequence[np.ndarray], tokenizer, names: Optional[Sequence[str]] = None) -> List[Optional[str]]:
@@ -72,6 +98,100 @@ def load_tokenizer(name_or_path: str):
     except Exception as e:                                  # noqa: BLE001
         print(f"No tokenizer files for {name_or_path} ({type(e).__name__}): writing token ids instead of text")
         return None
+
+
+_NO_SPACE_LANGUAGES = ("chinese", "japanese", "thai", "lao", "myanmar", "cantonese")
+_PREPEND = "\"'\u201c\u00a1\u00bf([{-"
+_APPEND = "\"'.\u3002,\uff0c!\uff01?\uff1f:\uff1a\u201d)]}\u3001"
+_PUNCTUATION = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"
+
+
+def _decode(tokenizer, ids):
+    try:
+        return tokenizer.decode(ids, decode_with_timestamps=True)
+    except TypeError:                                       # a tokenizer without Whisper's keyword
+        return tokenizer.decode(ids)
+
+
+def combine_tokens_into_words(tokenizer, tokens: Sequence[int], language: Optional[str] = None):
+    """HF's ``_combine_tokens_into_words`` (tokenization_whisper.py) restated over a tokenizer's ``decode``: (words, the token ids of each
+    word, the token indices of each word).  Tokens join until their text decodes without a dangling replacement character; the pieces
+    join into words at a leading space, a punctuation piece or a special token -- or stay as they are for the languages HF lists as
+    written without spaces --; then punctuation merges into its neighbour."""
+    tokens = [int(t) for t in tokens]
+    if language is None:
+        language = getattr(tokenizer, "language", None) or "english"
+    full = _decode(tokenizer, tokens)
+    pieces = []                                             # (text, ids, indices)
+    cur, cur_idx, offset = [], [], 0
+    for i, t in enumerate(tokens):
+        cur.append(t)
+        cur_idx.append(i)
+        text = _decode(tokenizer, cur)
+        at = text.find("\ufffd")
+        if at < 0 or offset + at >= len(full) or full[offset + at] == "\ufffd":
+            pieces.append((text, cur, cur_idx))
+            cur, cur_idx = [], []
+            offset += len(text)
+    if language in _NO_SPACE_LANGUAGES:
+        words = [[t, list(i), list(x)] for t, i, x in pieces]
+    else:
+        eos = getattr(tokenizer, "eos_token_id", None)
+        words = []
+        for text, ids, idx in pieces:
+            special = eos is not None and ids[0] >= eos
+            if special or text.startswith(" ") or text.strip() in _PUNCTUATION or not words:
+                words.append([text, list(ids), list(idx)])
+            else:
+                words[-1][0] += text
+                words[-1][1].extend(ids)
+                words[-1][2].extend(idx)
+    j = len(words) - 1                                      # punctuation that opens a word: right to left
+    for i in range(len(words) - 2, -1, -1):
+        if words[i][0].startswith(" ") and words[i][0].strip() in _PREPEND:
+            words[j] = [words[i][0] + words[j][0], words[i][1] + words[j][1], words[i][2] + words[j][2]]
+            words[i] = ["", [], []]
+        else:
+            j = i
+    i = 0                                                   # punctuation that closes a word: left to right
+    for j in range(1, len(words)):
+        if not words[i][0].endswith(" ") and words[j][0] in _APPEND:
+            words[i] = [words[i][0] + words[j][0], words[i][1] + words[j][1], words[i][2] + words[j][2]]
+            words[j] = ["", [], []]
+        else:
+            i = j
+    words = [w for w in words if w[0]]
+    return [w[0] for w in words], [w[1] for w in words if w[1]], [w[2] for w in words if w[2]]
+
+
+def token_spans(times: Sequence[float]):
+    """(start, end) per token: its own time, and the time of the token behind it -- the last token ends where it starts (its time is the
+    one HF repeats for the closing token)."""
+    t = [float(x) for x in times]
+    return [(t[k], t[k + 1] if k + 1 < len(t) else t[k]) for k in range(len(t))]
+
+
+def token_words(tokenizer, ids: Sequence[int], times: Sequence[float], language: Optional[str] = None):
+    """[(word, start_s, end_s)]: a word starts with its first token and ends where the token behind its last one starts."""
+    spans = token_spans(times)
+    words, _, indices = combine_tokens_into_words(tokenizer, ids, language)
+    return [(w, spans[idx[0]][0], spans[idx[-1]][1]) for w, idx in zip(words, indices)]
+
+
+def write_times_json(path: str, entries: dict) -> None:
+    """``{file: {"text": s, "tokens": [[id, start_s, end_s], ...], "words": [[word, start_s, end_s], ...]}}``; ``words`` only where an
+    entry has them (vocabulary files were found)."""
+    with open(path, "w") as f:
+        json.dump(entries, f, ensure_ascii=False, indent=1)
+        f.write("\n")
+
+
+def times_entry(ids: Sequence[int], times: Sequence[float], text: str, tokenizer=None) -> dict:
+    r = lambda x: round(float(x), 2)
+    e = {"text": text, "tokens": [[int(t), r(a), r(b)] for t, (a, b) in zip(ids, token_spans(times))]}
+    if tokenizer is not None:
+        e["words"] = [[w, r(a), r(b)] for w, a, b in token_words(tokenizer, ids, times)]
+    return e
 
 
 def write_table(path: str, names: Sequence[str], texts: Sequence[str]) -> None:
@@ -103,6 +223,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resample", action="store_true", help="accept wav files that are not 16 kHz")
     p.add_argument("--synthetic_weights", action="store_true", help="seeded weights (benchmarks and tests; the generation spec then comes from run(spec=...) or a generation_config.json beside --checkpoint)")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--times_json", type=str, default="", help="also write token (and, with vocabulary files, word) times to this JSON file")
     return p
 
 
@@ -123,6 +244,14 @@ def build(args, device: str = "cuda:0", spec: Optional[C.GenerationSpec] = None,
         if not cfg:
             raise OSError(f"no generation_config.json for {args.ssl_type} (it lies beside config.json in a local snapshot)")
         spec = C.GenerationSpec.from_snapshot(os.path.dirname(cfg), args.language)
+        try:
+            with open(cfg, "r") as f:
+                width = json.load(f).get("median_filter_width")
+        except (OSError, ValueError):
+            width = None
+        if width is not None:                               # config.json's, where HF reads it
+            import dataclasses
+            spec = dataclasses.replace(spec, median_filter_width=int(width))
     enc_mode = args.mode if args.mode in ("f16x", "fp32x", "bf16") else "f16x"
     enc = WhisperEncoder(geo, sd, device, enc_mode)
     dec = WhisperDecoder(geo, sd, device, args.mode, spec)
@@ -145,6 +274,14 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
     tok = tokenizer or tok
     names = sorted(f for f in os.listdir(args.wav_dir) if f.lower().endswith(".wav"))
     rows = []
+    want_times = bool(args.times_json)
+    if want_times:
+        try:
+            tr.spec.require_alignment_heads()
+        except ValueError as e:
+            print(f"Error: {e}")
+            return 0
+    entries = {}
     for i in range(0, len(names), BATCH):
         chunk, waves = [], []
         for n in names[i:i + BATCH]:
@@ -153,9 +290,14 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
                 chunk.append(n)
             except Exception as e:                          # noqa: BLE001
                 print(f"Failed to process {n}: {e}")
-        for n, ids in zip(chunk, tr.transcribe(waves, chunk, first_batch=i // BATCH)):
+        for k, (n, ids) in enumerate(zip(chunk, tr.transcribe(waves, chunk, first_batch=i // BATCH, token_times=want_times))):
             if ids is not None:
                 rows.append((n, tok.decode(ids, skip_special_tokens=True) if tok is not None else " ".join(str(t) for t in ids)))
+                if want_times and tr.token_times[k] is not None:
+                    entries[n] = times_entry(ids, tr.token_times[k], rows[-1][1], tok)
+    if want_times:
+        write_times_json(args.times_json, entries)
+        print(f"Wrote the token times of {len(entries)} files to {args.times_json}")
     write_table(args.out_csv, [r[0] for r in rows], [r[1] for r in rows])
     print(f"Wrote {len(rows)} of {len(names)} transcripts to {args.out_csv}")
     return 0
