@@ -1244,6 +1244,78 @@ typedef struct ser_swish_rows_args {
 } ser_swish_rows_args;
 int ser_swish_rows_v(const ser_swish_rows_args* args, void* stream);
 
+/* a34 (added under ABI 18: new entry points, two ser_cmd members and two SER_OP codes only; ser_dec_attn_v, ser_dec_select_v and every
+ * existing layout are unchanged)  Whisper beam search: HF's GenerationMixin._beam_search for do_sample = False, early_stopping = False,
+ * num_return_sequences = 1 and one eos token, restated with masks (tests/whisper_beam_ref.py is the float64 statement).  K beams of B
+ * utterances are the B K rows of one decode step; row b K + k is beam k of utterance b.
+ *
+ * ser_dec_attn_beam_v (SER_OP_DEC_ATTN_BEAM): ser_dec_attn_v's arithmetic, statement for statement, with the cache row of a key found
+ * through a table or a divisor.  `base` is read as by ser_dec_attn_v except that kcache / vcache + r * batch_stride is PHYSICAL row r:
+ *   src != NULL  (self-attention) key j < len - 1 of logical row b lies in physical row src[parity][b][j], parity = (len - 1) & 1; int32
+ *                [2][B][ld_src >= max_len], the halves src_parity_stride words apart; an entry outside [0, B) is clamped.  Row b appends
+ *                its step's k / v at ITS OWN physical row b, position len - 1, and reads them from k_new / v_new.  With the identity table
+ *                the result equals ser_dec_attn_v's bit for bit.
+ *   src == NULL  (cross-attention) row b reads physical row b / row_div: K beams share their utterance's cross cache; nothing is appended.
+ * Keys and values never move: what a step reorders is the table (ser_beam_select_v), B K p small integers.
+ *
+ * ser_beam_select_v (SER_OP_BEAM_SELECT): one step of the rule for every utterance.  With p = *pos, cur = p + 1 tokens per row:
+ *   scores   logp = z - logsumexp(z) over the RAW logits z (fp32) of a row, float64: suppressed tokens count in the normaliser.  Then the
+ *            mask row mask[phase[p]] (0 / -inf, as ser_dec_select_v's); then + run[b][k], the running score (-inf: a dead beam; the first
+ *            step starts from [0, -inf, ...], HF's [0, -1e9, ...]).
+ *   top 2K   of the K V scores; the larger first, on a tie the lower flat index k V + token.  parent = index / V, token = index % V.
+ *   hit      token == eos, or cur + 1 >= max_length.
+ *   running  the best K candidates that did not hit, in rank order; missing ones are dead rows (parent = own index, token = pad).
+ *   finished only candidates of rank < K that hit, and only while the flag is up: score / lenpow[cur + 1 - prompt_len], merged into the
+ *            K best kept in descending order (an older entry wins a tie); handle = (p, rank) into the trace.
+ *   flag     sticky AND: with K finished, run'[0] / lenpow[cur + 1 - prompt_len] > the worst finished score; untouched before that.
+ *   done     the flag dropped, or every candidate hit.  A done utterance is frozen: its rows keep stepping with identity parents and pad.
+ * lenpow [max_pos + 1] float64: n ^ length_penalty, tabulated by the host so that the device divides by the very number numpy does.
+ * State (device, across steps; the host zeroes it and sets run and flag = 1): run, fin_score [B][K] float64, fin_handle [B][K][2],
+ * state [B][4] = (n finished, flag, done, the position at which done was set).  Per step, indexed by p: trace_run [max_pos][B][K][2]
+ * (parent, token) of the new running rows (parent -1 where the utterance was frozen), trace_cand [max_pos][B][2K][2] and cand_score
+ * [max_pos][B][2K] of the candidates (-1 where there was none), gaps [max_pos][B] float64: the smallest gap of a comparison that decided
+ * the step (the cut at rank 2K, the cut behind the K-th candidate that did not hit, rank K - 1 against K when either hit, the finished
+ * merge against the worst kept, both sides of the flag's comparison; +inf where none applied).  Also writes ids[b K + r][p + 1], the
+ * ancestor table's other half (src'[r][j] = src[parent(r)][j] for j < p, src'[r][p] = parent(r); src may be NULL), *unfinished = the count
+ * of utterances not done, and advances *pos last (ser_dec_select_v's tickets; `ticket` int32 [2], zero before the first launch).
+ * *err (ORed): bit 0 a winning score that is not finite (a NaN logit wins), bit 2 p + 1 >= max_pos (nothing is written), bit 3 fewer
+ * than 2K finite candidates.  After an error bit only the error word is specified: the batch fails.
+ * Two launches.  Scan, blocks (chunk, beam, utterance) over SER_BEAM_CHUNK columns: the chunk's (max, sum exp) in float64 and its top 2K + 1
+ * masked logits (inside a row the order of the logits is the order of the scores).  Merge, one block per utterance: log-sum-exp from the
+ * partials in chunk order, the best 2K + 1 scores, the bookkeeping on one thread, the table copy on all.  Every order of a sum is a
+ * function of V alone; no atomics on data: an utterance's bits do not depend on B or on what shares the batch.  Every index read from
+ * device memory is clamped before use and every loop is bounded by a launch argument.  work: ser_beam_work_bytes(B, K, V) bytes, 8-byte
+ * aligned (-1 for sizes ser_beam_select_v refuses: K outside 2..SER_BEAM_MAX_K, V < 2 K or beyond SER_BEAM_MAX_CHUNKS chunks). */
+#define SER_BEAM_MAX_K 8
+#define SER_BEAM_MAX_CAND 17
+#define SER_BEAM_CHUNK 4096
+#define SER_BEAM_MAX_CHUNKS 13
+#define SER_BEAM_ERR_NONFINITE 1
+#define SER_BEAM_ERR_POSITION 4
+#define SER_BEAM_ERR_CANDIDATES 8
+typedef struct ser_dec_attn_beam_args {
+    ser_dec_attn_args base;
+    const int32_t* src; int64_t src_parity_stride;
+    int32_t ld_src, row_div;
+} ser_dec_attn_beam_args;
+int ser_dec_attn_beam_v(const ser_dec_attn_beam_args* args, void* stream);
+typedef struct ser_beam_select_args {
+    const float* logits; int64_t ldl;
+    const float* mask; int64_t ldm;
+    const int32_t* phase;
+    const double* lenpow;
+    int32_t* ids; int64_t ld_ids;
+    int32_t* src; int64_t src_parity_stride;
+    double* run; double* fin_score; int32_t* fin_handle; int32_t* state;
+    int32_t* trace_run; int32_t* trace_cand; double* cand_score; double* gaps;
+    void* work; int64_t work_bytes;
+    int32_t* pos; int32_t* unfinished; int32_t* ticket;
+    uint32_t* err;
+    int32_t B, K, V, eos, pad, max_pos, max_length, prompt_len, ld_src, reserved0;
+} ser_beam_select_args;
+int ser_beam_select_v(const ser_beam_select_args* args, void* stream);
+int64_t ser_beam_work_bytes(int32_t B, int32_t K, int32_t V);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -1268,6 +1340,8 @@ int ser_swish_rows_v(const ser_swish_rows_args* args, void* stream);
 #define SER_OP_CONFORMER_CONV 22
 #define SER_OP_SWISH_ROWS 23
 #define SER_OP_DEC_KEEP_Q 24
+#define SER_OP_DEC_ATTN_BEAM 25
+#define SER_OP_BEAM_SELECT 26
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -1295,6 +1369,8 @@ typedef struct ser_cmd {
         ser_conformer_conv_args conformer_conv;
         ser_swish_rows_args  swish_rows;
         ser_dec_keep_q_args  dec_keep_q;
+        ser_dec_attn_beam_args dec_attn_beam;
+        ser_beam_select_args beam_select;
     } u;
 } ser_cmd;
 

@@ -378,6 +378,24 @@ class DecSelectArgs(C.Structure):
     ]
 
 
+class DecAttnBeamArgs(C.Structure):
+    """Mirror of ``ser_dec_attn_beam_args``."""
+    _fields_ = [("base", DecAttnArgs), ("src", c_void_p), ("src_parity_stride", c_i64), ("ld_src", C.c_int32), ("row_div", C.c_int32)]
+
+
+class BeamSelectArgs(C.Structure):
+    """Mirror of ``ser_beam_select_args``."""
+    _fields_ = [
+        ("logits", c_void_p), ("ldl", c_i64), ("mask", c_void_p), ("ldm", c_i64), ("phase", c_void_p), ("lenpow", c_void_p),
+        ("ids", c_void_p), ("ld_ids", c_i64), ("src", c_void_p), ("src_parity_stride", c_i64),
+        ("run", c_void_p), ("fin_score", c_void_p), ("fin_handle", c_void_p), ("state", c_void_p),
+        ("trace_run", c_void_p), ("trace_cand", c_void_p), ("cand_score", c_void_p), ("gaps", c_void_p),
+        ("work", c_void_p), ("work_bytes", c_i64), ("pos", c_void_p), ("unfinished", c_void_p), ("ticket", c_void_p), ("err", c_void_p),
+        ("B", C.c_int32), ("K", C.c_int32), ("V", C.c_int32), ("eos", C.c_int32), ("pad", C.c_int32), ("max_pos", C.c_int32),
+        ("max_length", C.c_int32), ("prompt_len", C.c_int32), ("ld_src", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 class ProsodyMelArgs(C.Structure):
     """Mirror of ``ser_prosody_mel_args``."""
     _fields_ = [
@@ -487,6 +505,9 @@ CODEC_TILE = 128                # SER_CODEC_TILE: output rows per block of ser_c
 FVQ_ERR_NONFINITE = 1           # ser_fvq_v *err bit 0: a row's projected latent was not finite
 DEC_ERR_NONFINITE = 1           # ser_dec_select_v *err bit 0: a winning masked logit was not finite
 DEC_ERR_POSITION = 4            # bit 2: the position left the ids buffer
+BEAM_ERR_CANDIDATES = 8         # ser_beam_select_v *err bit 3: fewer than 2K finite candidates (bits 0 and 2 as ser_dec_select_v's)
+BEAM_MAX_K = 8                  # SER_BEAM_MAX_K: the most beams
+BEAM_CHUNK = 4096               # SER_BEAM_CHUNK: vocabulary columns per block of ser_beam_select_v's scan
 CTC_CHUNK = 256                 # SER_CTC_CHUNK: frames per chunk of ser_ctc_greedy_v's collapse
 CTC_ERR_NONFINITE = 1           # ser_ctc_greedy_v *err bit 0: a frame's winning logit was not finite
 WAVE = 64                       # lanes of a wave: a ballot of ser_ctc_align_v packs the back pointers of 64 consecutive states
@@ -512,7 +533,8 @@ class _CmdUnion(C.Union):
                 ("prosody_mel", ProsodyMelArgs), ("fvq", FvqArgs), ("act_rows", ActRowsArgs),
                 ("codec_unit", CodecUnitArgs), ("codec_conv", CodecConvArgs), ("snake", SnakeArgs),
                 ("fbank", FbankArgs), ("relkey_table", RelkeyTableArgs), ("attention_rk", AttentionRkArgs),
-                ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs), ("dec_keep_q", DecKeepQArgs)]
+                ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs), ("dec_keep_q", DecKeepQArgs),
+                ("dec_attn_beam", DecAttnBeamArgs), ("beam_select", BeamSelectArgs)]
 
 
 class Cmd(C.Structure):
@@ -526,6 +548,7 @@ OP_PROSODY_MEL, OP_FVQ, OP_ACT_ROWS = 13, 14, 15
 OP_CODEC_UNIT, OP_CODEC_CONV, OP_SNAKE = 16, 17, 18
 OP_FBANK, OP_RELKEY_TABLE, OP_ATTENTION_RK, OP_CONFORMER_CONV, OP_SWISH_ROWS = 19, 20, 21, 22, 23
 OP_DEC_KEEP_Q = 24
+OP_DEC_ATTN_BEAM, OP_BEAM_SELECT = 25, 26
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -539,7 +562,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_layer_mix_args": LayerMixArgs, "ser_stat_pool_args": StatPoolArgs, "ser_xvec_tail_args": XvecTailArgs,
                   "ser_ctc_greedy_args": CtcGreedyArgs, "ser_ctc_align_args": CtcAlignArgs,
                   "ser_dec_keep_q_args": DecKeepQArgs, "ser_ts_weights_args": TsWeightsArgs, "ser_ts_matrix_args": TsMatrixArgs,
-                  "ser_dtw_args": DtwArgs,
+                  "ser_dtw_args": DtwArgs, "ser_dec_attn_beam_args": DecAttnBeamArgs, "ser_beam_select_args": BeamSelectArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -576,6 +599,9 @@ _SIGNATURES = {
     "ser_ts_matrix_v": (c_int, [c_void_p, c_void_p]),
     "ser_dtw_v": (c_int, [c_void_p, c_void_p]),
     "ser_dtw_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.c_int32]),
+    "ser_dec_attn_beam_v": (c_int, [c_void_p, c_void_p]),
+    "ser_beam_select_v": (c_int, [c_void_p, c_void_p]),
+    "ser_beam_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.c_int32]),
     "ser_gru_v": (c_int, [c_void_p, c_void_p]),
     "ser_gru_work_bytes": (c_i64, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ser_xattn_v": (c_int, [c_void_p, c_void_p]),

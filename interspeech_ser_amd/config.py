@@ -547,8 +547,11 @@ class GenerationSpec:
     language: object = None            # None, a token id, or a key of ``lang_to_id`` ("en" / "<|en|>") resolved by from_snapshot
     alignment_heads: Tuple[Tuple[int, int], ...] = ()   # (decoder layer, head) pairs whose cross-attention carries the token times; () = absent
     median_filter_width: int = 7       # config.json's (not generation_config.json's): the transcriber fills it in
+    num_beams: int = 1                 # 1: greedy; 2..8: HF's beam search with early_stopping = False (engine.WhisperDecoder.generate)
+    length_penalty: float = 1.0        # the exponent of the generated length a finished beam's score is divided by
 
     PROMPT_LEN = 4
+    MAX_BEAMS = 8
     TIME_PRECISION = 0.02              # seconds per encoder frame
 
     def require_alignment_heads(self) -> Tuple[Tuple[int, int], ...]:
@@ -579,7 +582,19 @@ class GenerationSpec:
         heads = cfg.get("alignment_heads") or ()
         if any(not isinstance(h, (list, tuple)) or len(h) != 2 or int(h[0]) < 0 or int(h[1]) < 0 for h in heads):
             raise OSError("generation_config.json: alignment_heads must be a list of [layer, head] pairs")
+        early = cfg.get("early_stopping")
+        if early not in (None, False):
+            raise OSError(f"generation_config.json: early_stopping={early!r} is not built (beam search runs HF's early_stopping=false only)")
+        beams = cfg.get("num_beams")
+        beams = 1 if beams is None else beams
+        if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= GenerationSpec.MAX_BEAMS:
+            raise OSError(f"generation_config.json: num_beams={beams!r} (1..{GenerationSpec.MAX_BEAMS})")
+        penalty = cfg.get("length_penalty")
+        penalty = 1.0 if penalty is None else penalty
+        if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or penalty != penalty or abs(penalty) == float("inf"):
+            raise OSError(f"generation_config.json: length_penalty={penalty!r} (a finite number)")
         return GenerationSpec(
+            num_beams=beams, length_penalty=float(penalty),
             decoder_start_token_id=int(cfg["decoder_start_token_id"]), eos_token_id=eos, pad_token_id=eos if pad is None else int(pad),
             suppress_tokens=tuple(int(t) for t in cfg.get("suppress_tokens") or ()),
             begin_suppress_tokens=tuple(int(t) for t in cfg.get("begin_suppress_tokens") or ()),

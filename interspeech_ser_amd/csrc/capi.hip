@@ -131,6 +131,14 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_dec_keep_q_v(&c.u.dec_keep_q, stream);
                 break;
             }
+            case SER_OP_DEC_ATTN_BEAM: {
+                rc = ser_dec_attn_beam_v(&c.u.dec_attn_beam, stream);
+                break;
+            }
+            case SER_OP_BEAM_SELECT: {
+                rc = ser_beam_select_v(&c.u.beam_select, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

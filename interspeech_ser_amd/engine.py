@@ -2628,9 +2628,17 @@ class DecodeResult:
     After ``generate(..., token_times=True)`` also ``token_times`` (per utterance fp32 seconds of its n generated tokens, the closing eos
     included: HF's ``token_timestamps`` behind the prompt; None where ``ts_status`` is set), ``token_frames`` (the n - 1 first frames) and
     ``ts_status`` (int32 [B]: ser_ts_matrix_v's status, SER_TS_NO_FRAMES, or ser_dtw_v's for an utterance of two rows or more): an
-    utterance whose word is set fails ALONE.  ``ts_matrix``: the fp32 matrices on the device, [B, rows, pitch], until the next call."""
+    utterance whose word is set fails ALONE.  ``ts_matrix``: the fp32 matrices on the device, [B, rows, pitch], until the next call.
+    After a beam run (``generate(..., num_beams=K)``, K >= 2) ``sequences`` / ``lists`` / ``languages`` hold the best finished hypothesis
+    of every utterance (its length comes from its own history), and also: ``nbest`` (per utterance up to K ``(generated ids, score)`` pairs,
+    best first, the closing eos included), ``beam_scores`` float64 [B] (the best one's), ``beam_trace`` (dict: ``first`` = the position of the
+    first beam step, ``run`` int32 [n, B, K, 2] and ``cand`` int32 [n, B, 2K, 2] = (parent, token) of the running rows and of the candidates
+    of every position, ``cand_scores`` float64 [n, B, 2K], ``fin_scores`` / ``fin_handles`` / ``n_fin`` / ``flags`` / ``done_step``: the
+    finished sets and flags as the device left them, ``run_scores`` float64 [B, K]) and ``beam_gaps`` float64 [n, B] (per position the
+    smallest gap of a comparison that decided the step, +inf where none did).  ``margins`` then covers the prompt positions only."""
 
     token_times = token_frames = ts_status = ts_matrix = None
+    nbest = beam_scores = beam_trace = beam_gaps = beam_logits = None
 
     def __init__(self, sequences, languages, lists, margins, range_bits, err):
         self.sequences, self.languages, self.lists, self.margins = sequences, languages, lists, margins
@@ -2698,15 +2706,17 @@ class WhisperDecoder(_LaunchHost):
             self.layers.append(lay)
         self._plans: Dict = {}
         self._masks: Dict = {}
-        self._cache, self._cache_B = None, 0
+        self._cache, self._cache_B, self._cache_rows = None, 0, 0
 
     def _ln(self, sd, prefix):
         return (self._dev_f32(sd[prefix + ".weight"]), self._dev_f32(sd[prefix + ".bias"]))
 
     # ------------------------------------------------------------------ buffers
-    def _plan(self, B: int, slot: int, heads=None):
+    def _plan(self, B: int, slot: int, heads=None, beams: int = 1):
         """``heads``: the alignment heads of the capture variant of the step (``generate(token_times=True)``), part of the plan's key; the
-        default plan (None) records exactly the launches it always did."""
+        default plan (None) records exactly the launches it always did.  ``beams`` K >= 2: the beam plan, keyed (slot, B, "beam", K)."""
+        if beams > 1:
+            return self._beam_plan(B, slot, beams)
         key = (slot, B) if heads is None else (slot, B, tuple(heads))
         pl = self._plans.get(key)
         if pl is not None:
@@ -2748,6 +2758,60 @@ class WhisperDecoder(_LaunchHost):
         self._plans[key] = pl
         return pl
 
+    def _beam_plan(self, Bu: int, slot: int, K: int):
+        """The plan of a beam run: B K rows (row b K + k is beam k of utterance b) over a self cache of B K physical rows read through the
+        ancestor table, the B utterances' cross cache shared by their K rows, and the beam state in ONE device blob that comes back
+        with one copy.  pl["B"] is the row count, as every launch of the step reads it; pl["Bu"] the utterances."""
+        key = (slot, Bu, "beam", K)
+        pl = self._plans.get(key)
+        if pl is not None:
+            return pl
+        geo, dev = self.geo, self.device
+        D, L, T, S, V = geo.hidden, geo.decoder_layers, geo.max_target_positions, geo.max_source_positions, geo.decoder_vocab_size
+        B = Bu * K
+        work_bytes = int(lib.ser_beam_work_bytes(Bu, K, V))
+        if work_bytes < 0:
+            raise ValueError(f"beam search takes 2..{_lib.BEAM_MAX_K} beams over a vocabulary of at least 2 K tokens (K={K}, V={V})")
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        pl = dict(B=B, Bu=Bu, K=K, ids=i32(B, T), finished=i32(B), margin=f32(B, T), pos=i32(1), unfinished=i32(1), work=i32(2), err=i32(1),
+                  phase=i32(T), forced=i32(T), range_flag=i32(1) if self.fp16_planes else None,
+                  x=[f32(B, D), f32(B, D), f32(B, D)], qkv=f32(B, 3 * D), qc=f32(B, D), logits=f32(B, self.Vp),
+                  xa=self._new_act(B, D), ctx=self._new_act(B, D), ffn=self._new_act(B, geo.decoder_ffn_dim),
+                  enc_act=self._new_act(Bu * S, D))
+        ks, vs, cr = self._caches(Bu, B)
+        pl["kself"], pl["vself"] = ks[: L * B * T * D].view(L, B, T, D), vs[: L * B * T * D].view(L, B, T, D)
+        pl["cross"] = cr[: L * Bu * S * 2 * D].view(L, Bu * S, 2 * D)
+        pl["heads"] = None
+        # the beam state: float64 parts first, then int32 ones, each 8-byte aligned: ONE blob, so that one copy brings all of it back
+        parts = (("run", np.float64, (Bu, K)), ("fin_score", np.float64, (Bu, K)), ("cand_score", np.float64, (T, Bu, 2 * K)),
+                 ("gaps", np.float64, (T, Bu)), ("fin_handle", np.int32, (Bu, K, 2)), ("state", np.int32, (Bu, 4)),
+                 ("trace_run", np.int32, (T, Bu, K, 2)), ("trace_cand", np.int32, (T, Bu, 2 * K, 2)))
+        off, lay = 0, {}
+        for name, dt, shape in parts:
+            n = int(np.prod(shape)) * np.dtype(dt).itemsize
+            lay[name] = (off, dt, shape)
+            off += (n + 7) // 8 * 8
+        pl["beam_layout"], pl["beam_bytes"] = lay, off
+        pl["beam_blob"] = torch.zeros(off, dtype=torch.uint8, device=dev)
+        pl["beam_host"] = torch.empty(off, dtype=torch.uint8).pin_memory()
+        pl["beam_init"] = torch.empty(off, dtype=torch.uint8).pin_memory()         # what begin() uploads: zeros, run = [0, -inf ..], flag = 1
+        pl["src"] = i32(2, B, T)                        # the ancestor table, both halves
+        pl["src_init"] = torch.arange(B, dtype=torch.int32, device=dev).view(1, B, 1).expand(2, B, T).contiguous()
+        pl["lenpow"] = torch.zeros(T + 1, dtype=torch.float64, device=dev)
+        pl["beam_ticket"] = i32(2)
+        pl["beam_work"] = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        pl["beam_work_bytes"] = work_bytes
+        pl["host"] = torch.empty(3, dtype=torch.int32).pin_memory()
+        self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
+        pl["tape"] = tape = Tape()
+        with self._launching(tape):
+            self._step_launches(pl)
+        if len(self._plans) >= 6:
+            self._plans.pop(next(iter(self._plans)))
+        self._plans[key] = pl
+        return pl
+
     def _keep_q(self, pl, layer: int, qc: torch.Tensor) -> None:
         """The capture of the step (ser_dec_keep_q_v): one launch per run of alignment heads that lie in ``layer``, after its cross q
         projection."""
@@ -2769,23 +2833,34 @@ class WhisperDecoder(_LaunchHost):
             self._issue(_lib.OP_DEC_KEEP_Q, a, "ser_dec_keep_q")
             k = e
 
-    def _caches(self, B: int):
+    def _caches(self, B: int, rows: Optional[int] = None):
         """(self k, self v, cross k | v) flat fp32 storage for the largest batch seen.  A larger batch replaces it and drops every plan,
-        whose recorded commands point into the old storage."""
+        whose recorded commands point into the old storage.  ``rows``: the rows of the self cache when they are not the B utterances (a
+        beam plan's B K); the cross cache is per utterance."""
         geo = self.geo
-        if B > self._cache_B:
+        rows = B if rows is None else rows
+        if B > self._cache_B or rows > self._cache_rows:
             self._plans.clear()
             self._cache = None                          # free before allocating the larger one
-            n_self = geo.decoder_layers * B * geo.max_target_positions * geo.hidden
+            B, rows = max(B, self._cache_B), max(rows, self._cache_rows)
+            n_self = geo.decoder_layers * rows * geo.max_target_positions * geo.hidden
             n_cross = geo.decoder_layers * B * geo.max_source_positions * 2 * geo.hidden
             self._cache = tuple(torch.empty(n, dtype=torch.float32, device=self.device) for n in (n_self, n_self, n_cross))
-            self._cache_B = B
+            self._cache_B, self._cache_rows = B, rows
         return self._cache
 
     def _dec_attn(self, pl, q: torch.Tensor, ldq: int, kc: torch.Tensor, vc_ptr: int, ldc: int, batch_stride: int, max_len: int, *,
                   new=None, lens=None, len_add: int) -> None:
         geo = self.geo
-        a = self._cmd("dec_attn")
+        if pl.get("K"):                                 # a beam plan: the same arguments behind the ancestor table or the row divisor
+            x = self._cmd("dec_attn_beam")
+            a = x.base
+            if new is not None:
+                x.src, x.src_parity_stride, x.ld_src = pl["src"].data_ptr(), pl["src"].stride(0), pl["src"].shape[2]
+            x.row_div = 1 if new is not None else pl["K"]
+        else:
+            x = None
+            a = self._cmd("dec_attn")
         a.q, a.ldq = q.data_ptr(), ldq
         if new is not None:
             a.k_new, a.v_new, a.ld_new = new
@@ -2794,6 +2869,9 @@ class WhisperDecoder(_LaunchHost):
         ctx = pl["ctx"]
         a.out_act, a.ldo_act, a.out_plane_stride, a.range_flag = ctx.ptr, ctx.cols, ctx.plane_stride, self._flag
         a.scale, a.B, a.H, a.dh, a.max_len, a.mode = 64 ** -0.5, pl["B"], geo.decoder_attention_heads, 64, max_len, self.mode
+        if x is not None:
+            self._issue(_lib.OP_DEC_ATTN_BEAM, x, "ser_dec_attn_beam")
+            return
         self._issue(_lib.OP_DEC_ATTN, a, "ser_dec_attn")
 
     def _step_launches(self, pl) -> None:
@@ -2838,6 +2916,24 @@ class WhisperDecoder(_LaunchHost):
         s.B, s.V, s.eos, s.pad, s.max_pos = B, geo.decoder_vocab_size, 0, 0, T
         pl["select"] = s
         self._issue(_lib.OP_DEC_SELECT, s, "ser_dec_select")
+        if pl.get("K"):
+            # the second tail of a beam plan: from the first generated position the step ends with ser_beam_select_v instead
+            # (_run_step replays the tail the position needs)
+            pl["n_select"] = self._rec.n if self._rec is not None else None
+            K, Bu, lay = pl["K"], pl["Bu"], pl["beam_layout"]
+            at = lambda name: pl["beam_blob"].data_ptr() + lay[name][0]
+            g = self._cmd("beam_select")
+            g.logits, g.ldl, g.mask, g.ldm = pl["logits"].data_ptr(), self.Vp, 0, geo.decoder_vocab_size
+            g.phase, g.lenpow, g.ids, g.ld_ids = pl["phase"].data_ptr(), pl["lenpow"].data_ptr(), pl["ids"].data_ptr(), T
+            g.src, g.src_parity_stride, g.ld_src = pl["src"].data_ptr(), pl["src"].stride(0), T
+            g.run, g.fin_score, g.fin_handle, g.state = at("run"), at("fin_score"), at("fin_handle"), at("state")
+            g.trace_run, g.trace_cand, g.cand_score, g.gaps = at("trace_run"), at("trace_cand"), at("cand_score"), at("gaps")
+            g.work, g.work_bytes = pl["beam_work"].data_ptr(), pl["beam_work_bytes"]
+            g.pos, g.unfinished, g.ticket, g.err = pl["pos"].data_ptr(), pl["unfinished"].data_ptr(), pl["beam_ticket"].data_ptr(), pl["err"].data_ptr()
+            g.B, g.K, g.V, g.eos, g.pad, g.max_pos = Bu, K, geo.decoder_vocab_size, 0, 0, T
+            g.max_length, g.prompt_len = T, 1                                 # the spec's: set per generate() call (begin)
+            pl["beam_select"] = g
+            self._issue(_lib.OP_BEAM_SELECT, g, "ser_beam_select")
 
     def _spec_masks(self, spec) -> torch.Tensor:
         """fp32 [3, V] additive masks of a spec on the device: steady, first generated position, language set."""
@@ -2863,7 +2959,7 @@ class WhisperDecoder(_LaunchHost):
         """Once per batch: the encoder's last hidden state [B * 1500, D] -> every layer's cross keys | values (one ser_gemm per layer, N = 2 D)
         in the fp32 cache."""
         geo = self.geo
-        B, D, S = pl["B"], geo.hidden, geo.max_source_positions
+        B, D, S = pl.get("Bu", pl["B"]), geo.hidden, geo.max_source_positions      # a beam plan's rows share their utterance's cross cache
         if tuple(enc_last.shape) != (B * S, D) or enc_last.dtype != torch.float32 or not enc_last.is_contiguous():
             raise ValueError(f"the decoder needs the encoder's last hidden state as contiguous fp32 [{B * S}, {D}], got {tuple(enc_last.shape)}")
         ea = pl["enc_act"]
@@ -2872,9 +2968,22 @@ class WhisperDecoder(_LaunchHost):
         for i, lay in enumerate(self.layers):
             self._gemm(ea, lay["ckv"], B * S, out_f32=pl["cross"][i], ldo_f32=2 * D)
 
-    def _run_step(self, pl, with_logits: bool) -> None:
+    def _run_step(self, pl, with_logits: bool, beam: bool = False) -> None:
         tape = pl["tape"]
         st = self._s()
+        if pl.get("K"):
+            # a beam plan ends with two tails, [.. logits | ser_dec_select_v | ser_beam_select_v]: the prompt steps take the first (all B K
+            # rows are identical and choose alike), the generated positions the second
+            cmd_at = lambda i: C.byref(tape.cmds, i * C.sizeof(_lib.Cmd))
+            rc = lib.ser_run(tape.cmds, pl["n_logits"] if with_logits or beam else pl["n_body"], C.byref(tape._failed), st)
+            if rc == 0:
+                first = pl["n_select"] if beam else pl["n_logits"]
+                rc = lib.ser_run(cmd_at(first), 1, C.byref(tape._failed), st)
+                if rc != 0:
+                    tape._failed.value += first
+            if rc != 0:
+                check(rc, f"ser_run (decoder beam step, command {tape._failed.value})")
+            return
         if with_logits:
             rc = lib.ser_run(tape.cmds, tape.n, C.byref(tape._failed), st)
         else:
@@ -2884,16 +2993,19 @@ class WhisperDecoder(_LaunchHost):
         if rc != 0:
             check(rc, f"ser_run (decoder step, command {tape._failed.value})")
 
-    def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None, token_times: bool = False):
+    def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None, token_times: bool = False, num_beams: int = 1,
+              length_penalty: float = 1.0):
         """Reset the slot's decoding state for a batch of B: ids[:, 0] = start, position 0, nothing finished.  ``forced_ids`` (tests:
-        teacher forcing): a whole id row to follow instead of the spec's prompt.  ``token_times``: the capture variant of the step."""
+        teacher forcing): a whole id row to follow instead of the spec's prompt.  ``token_times``: the capture variant of the step.
+        ``num_beams`` K >= 2: the beam plan (B K rows) with its state reset: running scores [0, -inf, ..], empty finished sets, flags up,
+        the identity ancestor table."""
         spec = spec or self.spec
         if spec is None:
             raise ValueError("WhisperDecoder needs a GenerationSpec")
         geo = self.geo
         T = geo.max_target_positions
         n_max = min(int(spec.max_length), T)
-        pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None)
+        pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None, beams=num_beams)
         language = spec.language if language is None else language
         forced = np.full(T, -1, dtype=np.int32)
         phase = np.zeros(T, dtype=np.int32)
@@ -2917,14 +3029,46 @@ class WhisperDecoder(_LaunchHost):
         s = pl["select"]
         s.mask, s.eos, s.pad = self._spec_masks(spec).data_ptr(), spec.eos_token_id, spec.pad_token_id
         self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
+        if pl.get("K"):
+            from .beam import lenpow_table
+            if n_max <= spec.PROMPT_LEN:
+                raise ValueError(f"beam search needs max_length > {spec.PROMPT_LEN} (the prompt)")
+            K, lay = pl["K"], pl["beam_layout"]
+            g = pl["beam_select"]
+            g.mask, g.eos, g.pad, g.max_length, g.prompt_len = s.mask, spec.eos_token_id, spec.pad_token_id, n_max, spec.PROMPT_LEN
+            init = pl["beam_init"].numpy()
+            init[:] = 0
+            view = lambda name: init[lay[name][0]: lay[name][0] + int(np.prod(lay[name][2])) * np.dtype(lay[name][1]).itemsize].view(lay[name][1]).reshape(lay[name][2])
+            run = view("run")
+            run[:], run[:, 0] = -np.inf, 0.0
+            view("state")[:, 1] = 1
+            view("gaps")[:] = np.inf
+            pl["beam_blob"].copy_(pl["beam_init"], non_blocking=True)
+            pl["lenpow"].copy_(torch.from_numpy(lenpow_table(T + 1, length_penalty)))
+            pl["src"].copy_(pl["src_init"])
+            pl["beam_ticket"].zero_()
+            pl["length_penalty"] = float(length_penalty)
         return pl
 
     @_on_stream
     def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0, token_times: bool = False,
-                 lengths: Optional[Sequence[int]] = None) -> DecodeResult:
+                 lengths: Optional[Sequence[int]] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
+                 keep_logits: bool = False) -> DecodeResult:
         """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``).
         ``token_times``: also HF's ``token_timestamps`` of every utterance given alone (``DecodeResult.token_times``), from the alignment
-        heads' cross-attention; needs ``lengths``, the utterances' sample counts (HF's ``num_frames`` = length // 160)."""
+        heads' cross-attention; needs ``lengths``, the utterances' sample counts (HF's ``num_frames`` = length // 160).
+        ``num_beams`` / ``length_penalty``: None takes the spec's; 1 is the greedy path and its plan, untouched; K >= 2 is HF's beam search
+        (early_stopping = False) on the device.  ``keep_logits`` (tests): a beam run keeps the fp32 logits of every beam step in
+        ``DecodeResult.beam_logits`` [n, B K, V] on the device."""
+        sp = spec or self.spec
+        K = int(getattr(sp, "num_beams", 1) if num_beams is None else num_beams)
+        if not 1 <= K <= _lib.BEAM_MAX_K:
+            raise ValueError(f"num_beams={K} (1..{_lib.BEAM_MAX_K})")
+        if K > 1:
+            if token_times:
+                raise ValueError("token times with beam search are not built: run with num_beams=1")
+            lp = float(getattr(sp, "length_penalty", 1.0) if length_penalty is None else length_penalty)
+            return self._generate_beams(enc_last, B, spec, language, slot, K, lp, keep_logits)
         if token_times and (lengths is None or len(lengths) != B):
             raise ValueError("token times need the sample count of every utterance (lengths)")
         pl = self.begin(B, spec, language, slot, token_times=token_times)
@@ -2944,6 +3088,68 @@ class WhisperDecoder(_LaunchHost):
         res = self.result(pl, steps)
         if token_times:
             self._token_times(pl, res, lengths)
+        return res
+
+    def _generate_beams(self, enc_last, B: int, spec, language, slot: int, K: int, length_penalty: float, keep_logits: bool) -> DecodeResult:
+        """The beam run: the prompt steps through ser_dec_select_v on all B K rows, then ser_beam_select_v as the last command of every
+        step; the host reads the count of utterances not done every CHECK_EVERY steps, and one buffer after the loop."""
+        pl = self.begin(B, spec, language, slot, num_beams=K, length_penalty=length_penalty)
+        spec = pl["spec"]
+        self.project_cross(pl, enc_last)
+        n_max, forced, host, P = pl["n_max"], pl["forced_host"], pl["host"], spec.PROMPT_LEN
+        V = self.geo.decoder_vocab_size
+        kept = [] if keep_logits else None
+        steps = 0
+        for pos in range(n_max - 1):
+            beam = pos >= P - 1
+            self._run_step(pl, with_logits=forced[pos] < 0, beam=beam)
+            steps += 1
+            if beam and kept is not None:
+                kept.append(pl["logits"][:, :V].clone())
+            if beam and steps % self.CHECK_EVERY == 0:
+                host[0:1].copy_(pl["unfinished"], non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                if int(host[0]) == 0:
+                    break
+        return self._beam_result(pl, steps, kept)
+
+    def _beam_result(self, pl, steps: int, kept) -> DecodeResult:
+        from . import beam as BM
+        spec, K, Bu, lay = pl["spec"], pl["K"], pl["Bu"], pl["beam_layout"]
+        P = spec.PROMPT_LEN
+        pl["beam_host"].copy_(pl["beam_blob"], non_blocking=True)
+        head = pl["ids"][::K, :P].cpu().numpy().astype(np.int64)               # the prompt (rows of an utterance are identical there)
+        margins = pl["margin"][::K, : P - 1].cpu().numpy()
+        err = int(pl["err"].item()) & 0xffffffff
+        bits = 0
+        if pl["range_flag"] is not None:
+            bits = int(pl["range_flag"].item())
+            pl["range_flag"].zero_()
+        torch.cuda.current_stream().synchronize()
+        raw = pl["beam_host"].numpy()
+        view = lambda name: raw[lay[name][0]: lay[name][0] + int(np.prod(lay[name][2])) * np.dtype(lay[name][1]).itemsize].view(lay[name][1]).reshape(lay[name][2]).copy()
+        state, n = view("state"), steps + 1
+        trace = dict(first=P - 1, run=view("trace_run")[:n], cand=view("trace_cand")[:n], cand_scores=view("cand_score")[:n],
+                     fin_scores=view("fin_score"), fin_handles=view("fin_handle"), n_fin=state[:, 0].copy(), flags=state[:, 1].copy(),
+                     done=state[:, 2].copy(), done_step=state[:, 3].copy(), run_scores=view("run"))
+        failed = bool(bits & 1) or err != 0
+        nbest = [[] for _ in range(Bu)]
+        if not failed:
+            nbest = BM.nbest(trace["run"], trace["cand"], trace["fin_scores"], trace["fin_handles"], trace["n_fin"], P - 1)
+        rows = [nb[0][0] if nb else [] for nb in nbest]
+        width = P + max([len(r) for r in rows] + [0])
+        seqs = np.full((Bu, width), spec.pad_token_id, dtype=np.int64)
+        seqs[:, :P] = head
+        lists = []
+        for b, r in enumerate(rows):
+            seqs[b, P: P + len(r)] = r
+            lists.append(r[: r.index(spec.eos_token_id)] if spec.eos_token_id in r else list(r))
+        res = DecodeResult(seqs, head[:, 1].copy(), lists, margins, bits, err)
+        res.nbest = nbest
+        res.beam_scores = np.array([nb[0][1] if nb else np.nan for nb in nbest], dtype=np.float64)
+        res.beam_trace, res.beam_gaps = trace, view("gaps")[:n]
+        if kept is not None:
+            res.beam_logits = torch.stack(kept) if kept else None
         return res
 
     def _ts_buffer(self, name: str, numel: int, dtype) -> torch.Tensor:

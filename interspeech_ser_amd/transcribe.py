@@ -39,24 +39,32 @@ class WhisperTranscriber:
         self.token_times: List[Optional[List[float]]] = []      # per item of the last transcribe(token_times=True)
         self.failed: List[str] = []                             # names of the files the last transcribe() left out
 
-    def _batch(self, waves: Sequence[np.ndarray], slot: int, token_times: bool = False):
+    def _batch(self, waves: Sequence[np.ndarray], slot: int, token_times: bool = False, num_beams: Optional[int] = None,
+               length_penalty: Optional[float] = None):
         """(DecodeResult, failed) of one batch; one encoder forward serves the decoder (its LAST state: the forward does not stop early)."""
         lengths = [len(w) for w in waves]
         hs = self.enc.forward(self.enc.upload(waves, slot), lengths, slot=slot)
         extra = dict(token_times=True, lengths=lengths) if token_times else {}       # the default call is the one it always was
+        if num_beams is not None:
+            extra["num_beams"] = int(num_beams)
+        if length_penalty is not None:
+            extra["length_penalty"] = float(length_penalty)
         res = self.dec.generate(hs.states[-1], len(waves), self.spec, slot=slot, **extra)
         bits = hs.take_range_bits()
         return res, res.failed or bool(bits & 1), hs
 
     def transcribe(self, waves: Sequence[np.ndarray], names: Optional[Sequence[str]] = None, first_batch: int = 0,
-                   token_times: bool = False) -> List[Optional[List[int]]]:
+                   token_times: bool = False, num_beams: Optional[int] = None, length_penalty: Optional[float] = None
+                   ) -> List[Optional[List[int]]]:
         """``first_batch``: the index of the first batch in the caller's own sequence of calls (a driver that hands over 16 files at a time
         keeps the slots alternating with it).  ``token_times``: ``self.token_times[i]`` becomes the seconds of item i's generated non-eos
         tokens.  A file whose times have a status word set (no frame, a matrix entry that is not finite) fails ALONE: it is printed,
         named in ``self.failed`` and has no times (its ids stay: the transcript table does not depend on the flag), and its batch mates are
-        neither touched nor run again."""
+        neither touched nor run again.  ``num_beams`` / ``length_penalty``: None takes the spec's; K >= 2 returns the best beam's ids
+        (``self.last_scores[i]``: its score) and does not go with ``token_times``."""
         if token_times:
             self.spec.require_alignment_heads()
+        self.last_scores: List[Optional[float]] = [None] * len(waves)
         waves = [np.ascontiguousarray(w[:N_SAMPLES], dtype=np.float32) for w in waves]
         names = list(names) if names is not None else [f"utterance {i}" for i in range(len(waves))]
         out: List[Optional[List[int]]] = [None] * len(waves)
@@ -70,11 +78,13 @@ class WhisperTranscriber:
 
         for n, idx in enumerate(make_batches(range(len(waves)), BATCH), start=int(first_batch)):
             def run(js):
-                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times)
+                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times, num_beams, length_penalty)
                 if failed:
                     return res
                 for k, j in enumerate(js):
                     out[j], self.last_languages[j] = res.lists[k], int(res.languages[k])
+                    if getattr(res, "beam_scores", None) is not None:
+                        self.last_scores[j] = float(res.beam_scores[k])
                     if token_times and int(res.ts_status[k]) != 0:
                         self.failed.append(names[j])
                         print(f"Failed to process {names[j]}: token times status {int(res.ts_status[k]):#x} "
@@ -224,7 +234,21 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--synthetic_weights", action="store_true", help="seeded weights (benchmarks and tests; the generation spec then comes from run(spec=...) or a generation_config.json beside --checkpoint)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--times_json", type=str, default="", help="also write token (and, with vocabulary files, word) times to this JSON file")
+    p.add_argument("--num_beams", type=int, default=None, choices=range(1, C.GenerationSpec.MAX_BEAMS + 1), metavar="K",
+                   help="beam search with K beams (HF's early_stopping=false); default: generation_config.json's num_beams, else greedy")
+    p.add_argument("--length_penalty", type=float, default=None, help="with beams: the exponent of the length a finished score is divided by")
     return p
+
+
+def parse_args(argv: Optional[Sequence[str]] = None):
+    """The command line, with the combinations that are not built refused as argparse errors."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.num_beams is not None and args.num_beams > 1 and args.times_json:
+        p.error("--num_beams with --times_json: token times with beam search are not built")
+    if args.length_penalty is not None and (args.num_beams is None or args.num_beams < 2):
+        p.error("--length_penalty needs --num_beams K with K >= 2")
+    return args
 
 
 def build(args, device: str = "cuda:0", spec: Optional[C.GenerationSpec] = None, geo=None):
@@ -261,7 +285,7 @@ def build(args, device: str = "cuda:0", spec: Optional[C.GenerationSpec] = None,
 
 def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] = None, geo=None, tokenizer=None) -> int:
     from .frontend import load_wav_16k
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         print("Error: no MI355X visible -- this build has no CPU path")
         return 0
@@ -290,7 +314,8 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
                 chunk.append(n)
             except Exception as e:                          # noqa: BLE001
                 print(f"Failed to process {n}: {e}")
-        for k, (n, ids) in enumerate(zip(chunk, tr.transcribe(waves, chunk, first_batch=i // BATCH, token_times=want_times))):
+        beams = {} if args.num_beams is None else dict(num_beams=args.num_beams, length_penalty=args.length_penalty)
+        for k, (n, ids) in enumerate(zip(chunk, tr.transcribe(waves, chunk, first_batch=i // BATCH, token_times=want_times, **beams))):
             if ids is not None:
                 rows.append((n, tok.decode(ids, skip_special_tokens=True) if tok is not None else " ".join(str(t) for t in ids)))
                 if want_times and tr.token_times[k] is not None:
