@@ -96,9 +96,10 @@ __device__ __forceinline__ void mfma_scale_drain() {
 
 // WM x WN waves, each TM x TN MFMA tiles of 16x16; BK = K tile; ST = ring stages.
 // OM: format of the out_act copy (== MODE unless the launch converts, e.g. an FP32X stem GEMM feeding FP16 layers).
+// EPI: epilogue class of the dense epilogue (launch_plan.h: gemm_epi_id), which optional epilogue features are compiled in.
 // (Round 3's persistent form -- only the resident blocks are launched and each walks several tiles -- measured -8 % on the step and was
 // removed from the kernel in round 4; DESIGN.md section 10 keeps the record.)
-template <int WM, int WN, int TM, int TN, int BK, int ST, int MODE, bool LNEPI, int OM = MODE>
+template <int WM, int WN, int TM, int TN, int BK, int ST, int MODE, bool LNEPI, int OM = MODE, int EPI = GEMM_EPI_GENERIC>
 __global__ __launch_bounds__(64 * WM * WN, 2)
 void ser_gemm_kernel(const ser_gemm_args p) {
     constexpr int NW = WM * WN, NT = 64 * NW;
@@ -115,6 +116,7 @@ void ser_gemm_kernel(const ser_gemm_args p) {
     constexpr int NPL = M16 ? 1 : mode_traits<MODE>::planes;     // FP32X (bf16 hi/lo) and FP16X (fp16 hi/lo)
     constexpr int A_BYTES = BM * ROWB, W_BYTES = BN * ROWB, STAGE = NPL * (A_BYTES + W_BYTES);
     static_assert(!M16 || (BK == 64 && !LNEPI && (BM + BN) % 64 == 0), "FP16M: 64-deep K tiles, dense epilogue");
+    static_assert(EPI == GEMM_EPI_GENERIC || !LNEPI, "epilogue classes: dense epilogue only");
     constexpr int SCW = BM + BN;                  // FP16M: scale words per unit (one per A row and W row of the tile)
     constexpr int LA = BM / RPP / NW, LW = BN / RPP / NW;       // DMA pieces per wave per K tile
     constexpr int LPT = NPL * (LA + LW);
@@ -788,7 +790,7 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                 }
             }
         }
-    } else {
+    } else if constexpr (EPI == GEMM_EPI_GENERIC) {
         // wave-uniform feature flags: the column scale and the row partial sums cost 2 VALU each per element, and
         // most launches use neither (the epilogue is VALU-bound where it carries a GELU)
         const bool do_scale = p.col_scale_end > 0;
@@ -953,6 +955,191 @@ void ser_gemm_kernel(const ser_gemm_args p) {
                 }
             }
         }
+    } else {
+        // The specialised epilogue classes (launch_plan.h, gemm_pick_epi): the GENERIC body above with the features a class never has taken
+        // out at compile time and the ones it always has without their test.  Left as run-time tests, hipcc turns the cheap features into
+        // unconditional instructions + v_cndmask per element and wraps the lane-dependent ones in exec-mask branches that cut the GELU chains
+        // into 8-element scheduling regions -- in every launch, also those (FC1, the packed projection) that use none of them.  What a taken
+        // path computes per element is the GENERIC body's arithmetic in the same order: results are bit-identical
+        // (tests/test_gpu_gemm_epilogue_classes.py).
+        //   LN_ACT: deferred-LayerNorm transform, column scale / GELU decided per block, operand copy only;
+        //   RESID:  acc + bias (the transform with mu = 0, rstd = 1, exactly), residual, fp32 output at column 0; the operand copy, its
+        //           shift and the row partials stay wave-uniform run-time tests.
+        constexpr bool LNA = EPI == GEMM_EPI_LN_ACT, RES = EPI == GEMM_EPI_RESID;
+        static_assert(LNA || RES, "epilogue class");
+        // the 64-bit output column is formed here, behind the K loop: at 256 registers (256x256 tile) hipcc otherwise spills it across the loop
+        int ncol_e = ncol0;
+        asm volatile("" : "+v"(ncol_e));
+        const int64_t gcol = (int64_t)g * p.c_group_stride + ncol_e;
+        const bool do_scale = p.col_scale_end > 0;
+        const bool f_copy = LNA || p.out_act;
+        const bool f_shift = RES && p.shift_out;
+        const bool do_stat = RES && p.stat_out != nullptr;
+        float cs[TM];
+#pragma unroll
+        for (int mi = 0; mi < TM; ++mi) {
+            cs[mi] = 0.f;
+            if (f_shift) {
+                int m = m0 + wm * TM * 16 + mi * 16 + frow;
+                m = m < p.M ? m : p.M - 1;
+                cs[mi] = p.shift_const + (p.shift_in ? p.shift_in[m] : 0.f);
+            }
+        }
+        constexpr int RB = (TM * TN > 16) ? 2 : (TM < 4 ? TM : 4);          // the batched residual request, as above
+        // The rows of the tile.  ACT (GELU) and SCL (column scale) are 0 = off, 1 = on for every element, 2 = the GENERIC body's run-time
+        // test per fragment / per lane: both are decided ONCE per block, below, and the variant without the test runs.
+        auto rows = [&](auto act_tag, auto scl_tag) {
+            constexpr int ACT = decltype(act_tag)::value, SCL = decltype(scl_tag)::value;
+            f32x4 rres[RB][TN];
+#pragma unroll
+            for (int mi = 0; mi < TM; ++mi) {
+                if (RES && mi % RB == 0) {
+#pragma unroll
+                    for (int u = 0; u < RB; ++u) {
+                        int mr = m0 + wm * TM * 16 + (mi + u) * 16 + frow;
+                        mr = mr < p.M ? mr : p.M - 1;
+                        const int rr_ = p.res_row_mod ? (mr % p.res_row_mod) : mr;
+#pragma unroll
+                        for (int ni = 0; ni < TN; ++ni) {
+                            f32x4 r = {0.f, 0.f, 0.f, 0.f};
+                            if (ncol0 + ni * 16 < p.N) r = *(const f32x4*)(p.residual + (int64_t)rr_ * p.ldr + gcol + ni * 16);
+                            rres[u][ni] = r;
+                        }
+                    }
+                }
+                const int m = m0 + wm * TM * 16 + mi * 16 + frow;
+                if (m >= p.M) continue;
+                const int64_t orow = p.out_rowmap ? (int64_t)p.out_rowmap[m] : (int64_t)m;
+                float mu = 0.f, rs = 1.f;
+                if (LNA) {
+                    mu = lnst[2 * (wm * TM * 16 + mi * 16 + frow)];
+                    rs = lnst[2 * (wm * TM * 16 + mi * 16 + frow) + 1];
+                }
+                const float cshift = cs[mi];
+                if (f_shift && nt == 0 && g == 0 && wn == 0 && fq == 0) p.shift_out[m] = cshift;
+                // the row's output addresses, once per fragment row
+                float* const f32row = RES ? p.out_f32 + (int64_t)m * p.ldo_f32 + gcol : nullptr;
+                unsigned short* const actrow = f_copy ? (unsigned short*)p.out_act + orow * p.ldo_act + gcol : nullptr;
+                float st1 = 0.f, st2 = 0.f;
+                unsigned mcode[2] = {0u, 0u};                             // FP16M out copy: (P, Q) codes of the two blocks of a 64-column tile
+#pragma unroll
+                for (int ni = 0; ni < TN; ni += 2) {                      // fragment column blocks ni, ni+1: 4 + 4 columns
+                    const bool ok0 = ncol0 + ni * 16 < p.N, ok1 = ncol0 + ni * 16 + 16 < p.N;
+                    float v[8];
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const int nj = ni + (r >> 2), rr = r & 3;
+                        // LN(x) W^T = rstd * (x W'^T - mu * colsum(W')) + (beta W^T + b)
+                        float x = RES ? acc[nj][mi][rr] + bias[nj * 4 + rr] : fmaf(rs, acc[nj][mi][rr] - mu * csum[nj * 4 + rr], bias[nj * 4 + rr]);
+                        if (SCL == 2 && do_scale && ncol0 + nj * 16 < p.col_scale_end) x *= p.col_scale;   // e.g. q *= dh^-0.5 * log2(e)
+                        if constexpr (SCL == 1) {
+                            // the ROUNDED product, as the conditional form above gives it: left visible, hipcc fuses this multiply into the
+                            // v - hi of the two-plane / FP16M copies (one rounding instead of two: another lo plane than GENERIC's)
+                            x *= p.col_scale;
+                            asm("" : "+v"(x));
+                        }
+                        v[r] = x;
+                    }
+                    if (ACT == 1 || (ACT == 2 && p.act == SER_ACT_GELU)) {
+#pragma unroll
+                        for (int r = 0; r < 8; r += 2) {
+                            const f32x2 y = gelu2<MODE == SER_MODE_BF16>((f32x2){v[r], v[r + 1]});
+                            v[r] = y[0]; v[r + 1] = y[1];
+                        }
+                    }
+                    if constexpr (RES) {
+                        const f32x4 r0 = rres[mi % RB][ni], r1 = rres[mi % RB][ni + 1];
+                        v[0] += r0[0]; v[1] += r0[1]; v[2] += r0[2]; v[3] += r0[3];
+                        v[4] += r1[0]; v[5] += r1[1]; v[6] += r1[2]; v[7] += r1[3];
+                    }
+                    if constexpr (RES) {
+                        float* op = f32row + ni * 16;
+                        f32x4 o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
+                        if (ok0) *(f32x4*)op = o0;
+                        if (ok1) *(f32x4*)(op + 16) = o1;
+                    }
+                    if (f_shift) {                                        // wave-uniform; the fp32 output above stays unshifted
+#pragma unroll
+                        for (int r = 0; r < 8; ++r) v[r] -= cshift;
+                    }
+                    if (do_stat && ok0) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { st1 += v[r]; st2 += v[r] * v[r]; }
+                    }
+                    if (do_stat && ok1) {
+#pragma unroll
+                        for (int r = 4; r < 8; ++r) { st1 += v[r]; st2 += v[r] * v[r]; }
+                    }
+                    if (f_copy) {
+                        const int c8 = ni * 16 + ((fq & 1) ? 12 : 0);     // after the swap this lane holds columns c8..c8+7
+                        if constexpr (OM == SER_MODE_FP16M) {
+                            // hi plane = the fp16 copy; cross-term plane: P = v - hi, Q = v as e4m3 with one power-of-two scale per 32 columns
+                            // (this fragment pair = one block: the four lanes of the row hold 8 of its columns each)
+                            store_act8_swap<SER_MODE_FP16>(actrow + c8, 0, ncol0 + c8 < p.N, v);
+                            float lo[8], ax = 0.f, al = 0.f;
+#pragma unroll
+                            for (int r = 0; r < 8; r += 2) {
+                                const unsigned h2 = pack_h2(v[r], v[r + 1]);
+                                lo[r] = v[r] - h2f((unsigned short)(h2 & 0xffffu));
+                                lo[r + 1] = v[r + 1] - h2f((unsigned short)(h2 >> 16));
+                                ax = fmaxf(ax, fmaxf(fabsf(v[r]), fabsf(v[r + 1])));
+                                al = fmaxf(al, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
+                            }
+                            // range guard: stored columns only (N % 64 == 0: a block is stored whole or not at all, so its scales see no tail)
+                            if (p.range_flag) range_fold8(ramax, v, ok0, ok1);
+                            ax = max_rowquad(ax); al = max_rowquad(al);
+                            const unsigned cx = mx_code(ax), cl = mx_code(al);
+                            const float ix = mx_inv(cx), il = mx_inv(cl);
+                            unsigned q4[4] = {mx_pack4(lo[0] * il, lo[1] * il, lo[2] * il, lo[3] * il), mx_pack4(lo[4] * il, lo[5] * il, lo[6] * il, lo[7] * il),
+                                              mx_pack4(v[0] * ix, v[1] * ix, v[2] * ix, v[3] * ix), mx_pack4(v[4] * ix, v[5] * ix, v[6] * ix, v[7] * ix)};
+                            transpose_rowquad(q4);        // lane group fq now holds 16 consecutive bytes: P cols 0-15 | P 16-31 | Q 0-15 | Q 16-31 of the block
+                            const int64_t bcol = gcol - fq * 4 + ni * 16;                    // the block's first output column
+                            unsigned char* seg = (unsigned char*)((unsigned short*)p.out_act + p.out_plane_stride) + (orow * p.ldo_act + (bcol & ~(int64_t)63)) * 2;
+                            if (ok0) *(u32x4*)(seg + (fq >> 1) * 64 + (bcol & 63) + (fq & 1) * 16) = (u32x4){q4[0], q4[1], q4[2], q4[3]};
+                            mcode[(ni >> 1) & 1] = cl | (cx << 16);
+                            if (((ni >> 1) & 1) && fq == 0 && ok0)                            // second block of a 64-column tile: its scale word
+                                p.out_scale[(bcol >> 6) * p.out_scale_ld + orow] = (mcode[0] & 0xffu) | ((mcode[1] & 0xffu) << 8) | (mcode[0] & 0xff0000u) | ((mcode[1] & 0xff0000u) << 8);
+                        } else {
+                            store_act8_swap<OM>(actrow + c8, p.out_plane_stride, ncol0 + c8 < p.N, v);
+                            if constexpr (mode_traits<OM>::f16) {             // fp16 range guard (ser_hip.h range_flag): stored columns only
+                                if (p.range_flag) range_fold8(ramax, v, ok0, ok1);
+                            }
+                        }
+                    }
+                }
+                if (do_stat) {
+                    // row partials over this wave's columns (deterministic: one slot per 64-column group).  A 128-column wave tile (the
+                    // 3-product 256x256 tile) puts its partials in the first of its two slots and ZEROES in the second: every slot of the
+                    // columns a launch covers is written.  When it left the second slot alone, a buffer whose rows another launch shape had
+                    // filled before (the output projection's partials of "f16mf" with SER_F16M_OUT_M=1: FP16X layers, then FP16M layers,
+                    // then the next forward's FP16X layers) fed those stale values to the consumer's LayerNorm.
+                    st1 += __shfl_xor(st1, 16, 64); st2 += __shfl_xor(st2, 16, 64);
+                    st1 += __shfl_xor(st1, 32, 64); st2 += __shfl_xor(st2, 32, 64);
+                    const int cstart = n0 + wn * (TN * 16);
+                    const int grp = g * ((p.N + 63) >> 6) + (cstart >> 6);
+                    if (fq == 0 && cstart < p.N && grp < p.stat_groups) {
+                        float* d = p.stat_out + ((int64_t)m * p.stat_groups + grp) * 2;
+                        d[0] = st1; d[1] = st2;
+                        if constexpr (TN * 16 > 64) {
+                            if (cstart + 64 < p.N) { d[2] = 0.f; d[3] = 0.f; }     // (a second half past N: a padding slot, never written)
+                        }
+                    }
+                }
+            }
+        };
+        using std::integral_constant;
+        if constexpr (LNA) {
+            // block-uniform: GELU or not, and the tile wholly inside / outside the scaled columns [0, col_scale_end) -- a 256-wide tile of
+            // the 3 x 1024-wide packed projection always is; a tile that straddles the boundary keeps the per-lane test
+            const bool gelu = p.act == SER_ACT_GELU;
+            const bool scl_all = n0 + BN <= p.col_scale_end, scl_none = p.col_scale_end <= n0;
+            if (gelu && scl_none) rows(integral_constant<int, 1>{}, integral_constant<int, 0>{});             // FC1
+            else if (!gelu && scl_all) rows(integral_constant<int, 0>{}, integral_constant<int, 1>{});        // q columns
+            else if (!gelu && scl_none) rows(integral_constant<int, 0>{}, integral_constant<int, 0>{});       // k, v (, gate) columns
+            else rows(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+        } else {
+            rows(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+        }
     }
     if constexpr (mode_traits<OM>::f16) range_report(p.range_flag, ramax);
 #ifdef SER_GEMM_DBG
@@ -968,15 +1155,15 @@ void ser_gemm_kernel(const ser_gemm_args p) {
 
 // ------------------------------------------------------------------------------------------------
 // Host side: launch_plan.h checks the arguments and plans the launch (tile, (MODE, OM) pair, grid, LDS bytes); here the plan meets the
-// kernel template.  gemm_tile_serves guards the instantiation: exactly the (tile, pair) kernels it names are built.
+// kernel template.  gemm_epi_built guards the instantiation: exactly the (tile, pair, epilogue class) kernels it names are built.
 template <int... I, class F>
 static bool with_index(int i, std::integer_sequence<int, I...>, F&& f) { return ser_with_mode<I...>(i, f); }
 
-template <int TILE, int PAIR>
+template <int TILE, int PAIR, int EPI>
 static int launch_planned(const ser_gemm_args* a, const gemm_launch& pl, hipStream_t s) {
     constexpr gemm_tile t = GEMM_TILE[TILE];
     constexpr gemm_pair pr = GEMM_PAIR[PAIR];
-    auto k = ser_gemm_kernel<t.WM, t.WN, t.TM, t.TN, t.BK, t.ST, pr.mode, t.LNEPI, pr.om>;
+    auto k = ser_gemm_kernel<t.WM, t.WN, t.TM, t.TN, t.BK, t.ST, pr.mode, t.LNEPI, pr.om, EPI>;
     static std::atomic<bool> ready{false};          // per instantiation
     if (pl.lds > 65536)
         if (hipError_t e = ser_lds_optin(k, pl.lds, ready)) return ser_fail((int)e, "ser_gemm: cannot raise dynamic LDS to %d", pl.lds);
@@ -1001,7 +1188,10 @@ extern "C" int ser_gemm(const ser_gemm_args* a, void* stream) {
     with_index(pl.tile, std::make_integer_sequence<int, GEMM_TILES>{}, [&](auto T) {
         with_index(pl.pair, std::make_integer_sequence<int, GEMM_PAIRS>{}, [&](auto P) {
             constexpr int tile = decltype(T)::value, pair = decltype(P)::value;
-            if constexpr (gemm_tile_serves(GEMM_TILE[tile], GEMM_PAIR[pair])) rc = launch_planned<tile, pair>(a, pl, s);
+            with_index(pl.epi, std::make_integer_sequence<int, GEMM_EPIS>{}, [&](auto E) {
+                constexpr int epi = decltype(E)::value;
+                if constexpr (gemm_epi_built(tile, GEMM_PAIR[pair], epi)) rc = launch_planned<tile, pair, epi>(a, pl, s);
+            });
         });
     });
     return rc;

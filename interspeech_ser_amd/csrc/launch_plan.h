@@ -191,10 +191,37 @@ static inline int gemm_pick_tile(const ser_gemm_args* a) {
     return GEMM_128x128;
 }
 
+// Epilogue class of the dense (non-LayerNorm) epilogue: which of its optional features a kernel is COMPILED with.  The features a class
+// names as absent are not tested per element, they are not in the code.
+//   LN_ACT   deferred-LayerNorm transform, optional column scale, optional GELU, out_act only: the packed projection and FC1;
+//   RESID    residual + fp32 output, optional operand copy (shifted or not) with row partials, no activation: output projection and FC2;
+//   GENERIC  every feature behind its run-time test: all other launches.
+enum gemm_epi_id { GEMM_EPI_GENERIC, GEMM_EPI_LN_ACT, GEMM_EPI_RESID, GEMM_EPIS };
+constexpr const char* GEMM_EPI_NAME[GEMM_EPIS] = {"GENERIC", "LN_ACT", "RESID"};
+// Which (tile, pair) kernels exist in a specialised class: the three single-plane hot tiles of the encoder layers, and per class the pairs
+// the layers launch it with -- LN_ACT: the packed projection and FC1 (BF16, FP16, FP16M, FP16M -> FP16X); RESID: the output projection and
+// FC2 (the same and FP16 -> FP16X).  (The positional conv's 128x64 tile -- GELU + residual, one launch per forward -- and the two-plane
+// tiles stay on GENERIC: every further kernel is compile time of gemm.hip.)
+constexpr bool gemm_epi_built(int tile, gemm_pair p, int epi) {
+    if (epi == GEMM_EPI_GENERIC) return gemm_tile_serves(GEMM_TILE[tile], p);
+    if (tile != GEMM_128x128 && tile != GEMM_256x128 && tile != GEMM_256x256) return false;
+    if (!gemm_tile_serves(GEMM_TILE[tile], p) || gemm_two_plane(p.mode)) return false;
+    return epi == GEMM_EPI_RESID || !(p.mode == SER_MODE_FP16 && p.om == SER_MODE_FP16X);
+}
+// The class of a launch that passed gemm_plan's checks: exact predicates on the fields the kernel's epilogue tests.
+static inline int gemm_pick_epi(const ser_gemm_args* a, int tile, int pair) {
+    int epi = GEMM_EPI_GENERIC;
+    if (a->gn_scale) return epi;
+    if (a->ln_stats_in && a->out_act && !a->residual && !a->out_f32 && !a->shift_out && !a->stat_out) epi = GEMM_EPI_LN_ACT;
+    else if (a->residual && a->out_f32 && !a->f32_col_begin && a->col_scale_end <= 0 && !a->ln_stats_in && a->act != SER_ACT_GELU) epi = GEMM_EPI_RESID;
+    return gemm_epi_built(tile, GEMM_PAIR[pair], epi) ? epi : GEMM_EPI_GENERIC;
+}
+
 struct gemm_launch {
     int tile, pair;                    // indices into GEMM_TILE / GEMM_PAIR
     unsigned grid_x, grid_y;           // (row tiles x column tiles, groups)
     int block, lds;
+    int epi;                           // gemm_epi_id
 };
 
 // Checks the arguments (codes and texts of ser_gemm) and plans the launch.  0, or the code ser_fail was given.
@@ -258,6 +285,7 @@ static inline int gemm_plan(const ser_gemm_args* a, gemm_launch* out) {
     const int BM = t.BM(), BN = t.BN();
     out->tile = tile;
     out->pair = pair;
+    out->epi = gemm_pick_epi(a, tile, pair);
     out->grid_x = (unsigned)(((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN));
     out->grid_y = (unsigned)a->groups;
     out->block = t.threads();

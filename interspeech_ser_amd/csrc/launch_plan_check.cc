@@ -8,6 +8,7 @@
 //   gemm <tile> <MODE>><OM> grid=<x>x<y> block=<threads> lds=<bytes>
 //   attn <dhp> <mode> <PTBGO> nbuf=.. bias_stride=.. lds=.. grid=..      (a letter of PRE, TBL, B2D, GB, OCC where the flag is set, else '-')
 //   gemm err <code>   |   attn err <code>
+// With the argument --epi a gemm line also ends in ` epi=<class>`, the epilogue class of the launch (GEMM_EPI_NAME).
 #include "launch_plan.h"
 #include <string.h>
 #include <iostream>
@@ -68,7 +69,8 @@ static bool parse(std::istringstream& in, void* args, const field (&fields)[N]) 
     return true;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    const bool show_epi = argc > 1 && !strcmp(argv[1], "--epi");
     std::string line;
     int lineno = 0;
     while (std::getline(std::cin, line)) {
@@ -83,8 +85,11 @@ int main() {
             if ((ok = parse(in, &a, GEMM_FIELDS))) {
                 const int rc = gemm_plan(&a, &pl);
                 if (rc) printf("gemm err %d\n", rc);
-                else printf("gemm %s %d>%d grid=%ux%u block=%d lds=%d\n", GEMM_TILE[pl.tile].name, GEMM_PAIR[pl.pair].mode, GEMM_PAIR[pl.pair].om,
-                            pl.grid_x, pl.grid_y, pl.block, pl.lds);
+                else {
+                    printf("gemm %s %d>%d grid=%ux%u block=%d lds=%d", GEMM_TILE[pl.tile].name, GEMM_PAIR[pl.pair].mode, GEMM_PAIR[pl.pair].om,
+                           pl.grid_x, pl.grid_y, pl.block, pl.lds);
+                    printf(show_epi ? " epi=%s\n" : "\n", GEMM_EPI_NAME[pl.epi]);
+                }
             }
         } else if (what == "attn") {
             ser_attention_args a = {};
