@@ -1316,6 +1316,86 @@ typedef struct ser_beam_select_args {
 int ser_beam_select_v(const ser_beam_select_args* args, void* stream);
 int64_t ser_beam_work_bytes(int32_t B, int32_t K, int32_t V);
 
+/* a35 (added under ABI 18: new entry points, four ser_cmd members and four SER_OP codes only; every existing layout and kernel is
+ * unchanged)  The wav2vec2-conformer encoders (HF Wav2Vec2ConformerModel: facebook/wav2vec2-conformer-{rope,rel-pos}-large): wav2vec2's
+ * convolutional stem and feature projection, then conformer layers
+ *   x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(x);  x += FFN2(LN x) / 2;  x = LN x
+ * with hidden_states[i < L] = the input of layer i and hidden_states[L] = encoder.layer_norm of the last layer's output; no positional
+ * convolution.  Two position schemes and a convolution module of their own; the rest runs on a28's kernels, ser_layernorm_v, ser_gemm and
+ * ser_attention_v.  Every kernel is a plain grid, every sum runs in an order fixed by the utterance alone (a batched run is bit-equal to a
+ * batch of one), every fp16 operand plane reports into range_flag.  tests/w2vconf_ref.py is the float64 statement.
+ *
+ * Rotary ("rotary").  The layer-normed rows are rotated BEFORE linear_q and linear_k; linear_v reads the un-rotated rows.  With t = the
+ * row's frame index INSIDE its utterance, dh the head dim and c a channel of a head,
+ *   x'[c] = x[c] cos[t][c] + (c < dh / 2 ? -x[c + dh / 2] : x[c - dh / 2]) sin[t][c]
+ *   cos[t][c] = cos(t inv_freq[c mod dh / 2]),  inv_freq[i] = 1 / base^(2 i / dh) held in fp32 (HF's buffer)
+ * The tables are built by the HOST: float64 products of t with the fp32 inv_freq, cos / sin in float64, rounded once to fp32.
+ * ser_rope_rows_v: fp32 rows x [rows][ldx] -- the OUTPUT of ser_layernorm_v, which also writes the plain operand planes linear_v reads; the
+ * kernel applies no norm -- to the rotated rows as operand planes in `mode` (SER_MODE_BF16 / FP32X / FP16 / FP16X).  One product, one FMA
+ * per element: x' = fma(x_pair, sin, x cos).  Wave per row; the row's utterance b is found by bisection of frame_offs [B + 1], the
+ * position is row - frame_offs[b] < table_T (a position beyond the table is an argument error of the caller: max_frames <= table_T is
+ * checked, and the kernel clamps).  D % dh == 0, dh % 8 == 0, D % 4 == 0, D <= 2048; pitches multiples of 4. */
+typedef struct ser_rope_rows_args {
+    const float* x; int64_t ldx;
+    const float* cos_t; const float* sin_t;
+    const int32_t* frame_offs;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    uint32_t* range_flag;
+    int32_t B, rows, D, dh, table_T, max_frames, mode, reserved0;
+} ser_rope_rows_args;
+int ser_rope_rows_v(const ser_rope_rows_args* args, void* stream);
+
+/* ser_conformer_conv_bn_v: the middle of this family's convolution module (HF Wav2Vec2ConformerConvolutionModule) between its two
+ * pointwise GEMMs -- ser_conformer_conv_v's block shape with a CENTRED window and BatchNorm1d in eval in LayerNorm's place:
+ *   g[t][c] = y[t][c] sigmoid(y[t][D + c])                                  GLU of pointwise-1's fp32 output y [rows][ldy >= 2 D]
+ *   u[t][c] = sum_k w[k][c] g[t - (K - 1) / 2 + k][c]                       rows outside the utterance (frame_offs) are zeros on BOTH
+ *                                                                           sides, never a neighbouring utterance's
+ *   out[t]  = swish(fma(u[t][c], scale[c], shift[c]))                       -> operand planes of pointwise-2's input, in `mode`
+ * scale = gamma / sqrt(running_var + eps), shift = beta - running_mean scale: folded by the host in float64, rounded once.  fp32 FMAs in
+ * ascending k, accurate expf.  w fp32 [K][D].  D % 4 == 0, D <= 2048, K odd <= 31; pitches multiples of 4.  Modes BF16 / FP32X / FP16 / FP16X. */
+typedef struct ser_conformer_conv_bn_args {
+    const float* y; int64_t ldy;
+    const float* w; const float* scale; const float* shift;
+    const int32_t* frame_offs;
+    void* out_act; int64_t ldo_act; int64_t out_plane_stride;
+    uint32_t* range_flag;
+    int32_t B, D, K, max_frames, rows, mode;
+} ser_conformer_conv_bn_args;
+int ser_conformer_conv_bn_v(const ser_conformer_conv_bn_args* args, void* stream);
+
+/* Relative ("relative", Transformer-XL).  With i, j the frame indices of query and key inside their utterance,
+ *   scores[i][j] = ((q_i + u_h) . k_j + (q_i + v_h) . P_h(i - j)) / sqrt(dh),     P(r) = linear_pos(pe(r)) (no bias),
+ *   pe(r)[0::2] = sin(r div), pe(r)[1::2] = cos(r div), div = exp(arange(0, D, 2) (-ln 10000 / D));   r > 0: the key is to the left
+ * (HF's zero-pad / view / slice "shift" is exactly this index).  P depends on the distance alone.  The host folds u into linear_q's bias
+ * (the projection emits q + u, scaled by dh^-0.5 log2 e through ser_gemm's col_scale) and passes off_h = (v_h - u_h) dh^-0.5 log2 e.
+ * ser_relpos_bias_v: for every row m of utterance b (i = m - frame_offs[b], T = the utterance's frames) and head h
+ *   pb[(m H + h) ld_pb + j] = sum_d (q_h[m][d] + off_h[d]) P[(P_T + i - j) ldp + h dh + d]       j < T;      0 for T <= j < 64 ceil(T / 64)
+ * fp32 in the exp2 domain (q carries the scale), q read from the packed projection's planes as fp32 (hi, or hi + lo: ser_relkey_table_v's
+ * arithmetic), one rounding of q + off, fp32 FMAs in ascending d.  P fp32 [2 P_T][ldp], row P_T + r = P(r) for -P_T <= r < P_T;
+ * max_frames <= P_T.  A block takes 32 query rows x 64 keys of one (utterance, head) and stages the 95 rows of P_h they need in LDS.
+ * dh == 64, B H <= 65535, ld_pb % 64 == 0 and >= 64 ceil(max_frames / 64).  Modes SER_MODE_BF16 / FP32X / FP16X. */
+typedef struct ser_relpos_bias_args {
+    const void* qkv; int64_t ld; int64_t plane_stride;
+    const float* P; int64_t ldp;
+    const float* off;
+    const int32_t* frame_offs;
+    float* pb; int64_t ld_pb;
+    int32_t q_col, B, H, dh, P_T, max_frames, rows, mode;
+} ser_relpos_bias_args;
+int ser_relpos_bias_v(const ser_relpos_bias_args* args, void* stream);
+
+/* ser_attention_rb_v: ser_attention_rk_v's kernel with a per-(query row, head) bias ROW indexed by the key's index in its utterance,
+ *   out[q, :] = softmax_k( q.k + pb[(q H + h) ld_pb + k] ) v,
+ * a further instantiation of the same kernel behind `base` (as ser_attention_rk_v reads it: pre-scaled q, head dim 64, no table, gate,
+ * key_lens, bias2d or FP16M output; modes BF16 / FP32X / FP16X).  The S accumulators start at the bias, so with pb = 0 the result is
+ * bit-equal to ser_attention_v's low-occupancy form.  pb 16-byte aligned, ld_pb % 64 == 0 and >= 64 ceil(max_frames / 64); a row is read
+ * up to 64 ceil(T / 64) entries, which ser_relpos_bias_v leaves finite. */
+typedef struct ser_attention_rb_args {
+    ser_attention_args base;
+    const float* pb; int64_t ld_pb;
+} ser_attention_rb_args;
+int ser_attention_rb_v(const ser_attention_rb_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -1342,6 +1422,10 @@ int64_t ser_beam_work_bytes(int32_t B, int32_t K, int32_t V);
 #define SER_OP_DEC_KEEP_Q 24
 #define SER_OP_DEC_ATTN_BEAM 25
 #define SER_OP_BEAM_SELECT 26
+#define SER_OP_ROPE_ROWS 27
+#define SER_OP_CONFORMER_CONV_BN 28
+#define SER_OP_RELPOS_BIAS 29
+#define SER_OP_ATTENTION_RB 30
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -1371,6 +1455,10 @@ typedef struct ser_cmd {
         ser_dec_keep_q_args  dec_keep_q;
         ser_dec_attn_beam_args dec_attn_beam;
         ser_beam_select_args beam_select;
+        ser_rope_rows_args   rope_rows;
+        ser_conformer_conv_bn_args conformer_conv_bn;
+        ser_relpos_bias_args relpos_bias;
+        ser_attention_rb_args attention_rb;
     } u;
 } ser_cmd;
 

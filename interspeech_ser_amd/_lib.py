@@ -497,6 +497,40 @@ class SwishRowsArgs(C.Structure):
     ]
 
 
+class RopeRowsArgs(C.Structure):
+    """Mirror of ``ser_rope_rows_args``."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_i64), ("cos_t", c_void_p), ("sin_t", c_void_p), ("frame_offs", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("range_flag", c_void_p),
+        ("B", C.c_int32), ("rows", C.c_int32), ("D", C.c_int32), ("dh", C.c_int32), ("table_T", C.c_int32), ("max_frames", C.c_int32),
+        ("mode", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class ConformerConvBnArgs(C.Structure):
+    """Mirror of ``ser_conformer_conv_bn_args``."""
+    _fields_ = [
+        ("y", c_void_p), ("ldy", c_i64), ("w", c_void_p), ("scale", c_void_p), ("shift", c_void_p), ("frame_offs", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_i64), ("out_plane_stride", c_i64), ("range_flag", c_void_p),
+        ("B", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("max_frames", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
+class RelposBiasArgs(C.Structure):
+    """Mirror of ``ser_relpos_bias_args``."""
+    _fields_ = [
+        ("qkv", c_void_p), ("ld", c_i64), ("plane_stride", c_i64), ("P", c_void_p), ("ldp", c_i64), ("off", c_void_p),
+        ("frame_offs", c_void_p), ("pb", c_void_p), ("ld_pb", c_i64),
+        ("q_col", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("dh", C.c_int32), ("P_T", C.c_int32), ("max_frames", C.c_int32),
+        ("rows", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
+class AttentionRbArgs(C.Structure):
+    """Mirror of ``ser_attention_rb_args``."""
+    _fields_ = [("base", AttentionArgs), ("pb", c_void_p), ("ld_pb", c_i64)]
+
+
 LAYER_POOL_FC = 32              # SER_LAYER_POOL_FC: frames per chunk of ser_layer_pool_v
 CLS_TAIL_MAX = 2048             # widest projector / most labels of ser_cls_tail_v (and widest embedding / most labels of ser_xvec_tail_v)
 STAT_POOL_FC = 32               # SER_STAT_POOL_FC: frames per chunk of ser_stat_pool_v
@@ -534,7 +568,9 @@ class _CmdUnion(C.Union):
                 ("codec_unit", CodecUnitArgs), ("codec_conv", CodecConvArgs), ("snake", SnakeArgs),
                 ("fbank", FbankArgs), ("relkey_table", RelkeyTableArgs), ("attention_rk", AttentionRkArgs),
                 ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs), ("dec_keep_q", DecKeepQArgs),
-                ("dec_attn_beam", DecAttnBeamArgs), ("beam_select", BeamSelectArgs)]
+                ("dec_attn_beam", DecAttnBeamArgs), ("beam_select", BeamSelectArgs),
+                ("rope_rows", RopeRowsArgs), ("conformer_conv_bn", ConformerConvBnArgs), ("relpos_bias", RelposBiasArgs),
+                ("attention_rb", AttentionRbArgs)]
 
 
 class Cmd(C.Structure):
@@ -549,6 +585,7 @@ OP_CODEC_UNIT, OP_CODEC_CONV, OP_SNAKE = 16, 17, 18
 OP_FBANK, OP_RELKEY_TABLE, OP_ATTENTION_RK, OP_CONFORMER_CONV, OP_SWISH_ROWS = 19, 20, 21, 22, 23
 OP_DEC_KEEP_Q = 24
 OP_DEC_ATTN_BEAM, OP_BEAM_SELECT = 25, 26
+OP_ROPE_ROWS, OP_CONFORMER_CONV_BN, OP_RELPOS_BIAS, OP_ATTENTION_RB = 27, 28, 29, 30
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -563,6 +600,8 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_ctc_greedy_args": CtcGreedyArgs, "ser_ctc_align_args": CtcAlignArgs,
                   "ser_dec_keep_q_args": DecKeepQArgs, "ser_ts_weights_args": TsWeightsArgs, "ser_ts_matrix_args": TsMatrixArgs,
                   "ser_dtw_args": DtwArgs, "ser_dec_attn_beam_args": DecAttnBeamArgs, "ser_beam_select_args": BeamSelectArgs,
+                  "ser_rope_rows_args": RopeRowsArgs, "ser_conformer_conv_bn_args": ConformerConvBnArgs,
+                  "ser_relpos_bias_args": RelposBiasArgs, "ser_attention_rb_args": AttentionRbArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -623,6 +662,10 @@ _SIGNATURES = {
     "ser_attention_rk_v": (c_int, [c_void_p, c_void_p]),
     "ser_conformer_conv_v": (c_int, [c_void_p, c_void_p]),
     "ser_swish_rows_v": (c_int, [c_void_p, c_void_p]),
+    "ser_rope_rows_v": (c_int, [c_void_p, c_void_p]),
+    "ser_conformer_conv_bn_v": (c_int, [c_void_p, c_void_p]),
+    "ser_relpos_bias_v": (c_int, [c_void_p, c_void_p]),
+    "ser_attention_rb_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -39,7 +39,7 @@ class AudioClassifier(_Extractor):
         from .weights import split_classifier_head
         if spec is None:
             raise ValueError("not an audio-classification checkpoint (config.json names none of " + ", ".join(C.AUDIO_CLASSIFICATION_ARCHITECTURES) + ")")
-        if geo.family not in C.SPEECH_FAMILIES + (C.FAMILY_W2V_BERT, C.FAMILY_WHISPER):
+        if geo.family not in C.SPEECH_FAMILIES + (C.FAMILY_W2V_BERT, C.FAMILY_W2V_CONFORMER, C.FAMILY_WHISPER):
             raise ValueError(f"{geo.name}: the {geo.family} encoder has no audio-classification head")
         self.geo, self.spec, self.whisper = geo, spec, geo.family == C.FAMILY_WHISPER
         self.average, self.layer_index = False, geo.num_layers           # the extraction pipeline's selection: the full forward

@@ -22,8 +22,12 @@ FAMILY_ROBERTA = "roberta"      # text side of the bimodal heads (next row 8f-1)
 FAMILY_DEBERTA = "deberta"      # DeBERTa-v2/v3 variant of the text side (engine.DebertaEncoder, csrc/deberta.hip)
 FAMILY_DATA2VEC_AUDIO = "data2vec-audio"   # layer-norm conv stem, post-LN encoder, a stack of LayerNorm'd positional convs
 FAMILY_W2V_BERT = "wav2vec2-bert"          # Kaldi fbank front end, conformer layers with a relative-key attention bias (engine.W2vBertEncoder)
+# wav2vec2's conv stem, conformer layers with rotary or Transformer-XL relative positions, a centred BatchNorm convolution module
+# (engine.ConformerSpeechEncoder)
+FAMILY_W2V_CONFORMER = "wav2vec2-conformer"
 
 SPEECH_FAMILIES = (FAMILY_WAVLM, FAMILY_WAV2VEC2, FAMILY_HUBERT, FAMILY_DATA2VEC_AUDIO)
+W2V_CONFORMER_POSITION_TYPES = ("rotary", "relative")
 
 
 @dataclass(frozen=True)
@@ -72,6 +76,11 @@ class EncoderGeometry:
     conv_depthwise_kernel: int = 31
     left_max_positions: int = 64
     right_max_positions: int = 8
+    # wav2vec2-conformer (HF Wav2Vec2ConformerModel): "rotary" or "relative" (Transformer-XL); "" for every other family.  ``rotary_base``:
+    # rotary_embedding_base.  (``max_source_positions`` above is also this family's key: the length HF pre-computes its relative table for;
+    # the table here grows with the longest utterance, so the value is recorded and nothing reads it.)
+    position_type: str = ""
+    rotary_base: int = 10000
     name: str = ""
 
     @property
@@ -224,6 +233,15 @@ W2V_BERT_2 = EncoderGeometry(
     family=FAMILY_W2V_BERT, num_layers=24, hidden=1024, heads=16, ffn=4096, fbank_mels=80, fbank_stride=2, conv_depthwise_kernel=31,
     left_max_positions=64, right_max_positions=8, layer_norm_eps=1e-5, name="facebook/w2v-bert-2.0")
 
+# wav2vec2-conformer large (fairseq's conformer models, LV-60 pre-training; the -960h-ft fine-tunes share the encoder): the wav2vec2-large
+# stem (layer norm, conv bias), 24 conformer layers, K = 31.  Written from the public hub configs, which cannot be fetched offline to be
+# checked here: a snapshot's config.json takes precedence over these entries (resolve_geometry).
+W2V_CONFORMER_ROPE_LARGE = EncoderGeometry(
+    family=FAMILY_W2V_CONFORMER, num_layers=24, hidden=1024, heads=16, ffn=4096, conv_bias=True, feat_extract_norm="layer",
+    conv_depthwise_kernel=31, position_type="rotary", rotary_base=10000, max_source_positions=5000,
+    name="facebook/wav2vec2-conformer-rope-large")
+W2V_CONFORMER_REL_LARGE = replace(W2V_CONFORMER_ROPE_LARGE, position_type="relative", name="facebook/wav2vec2-conformer-rel-pos-large")
+
 _REGISTRY = {
     "microsoft/deberta-v3-large": DEBERTA_V3_LARGE,
     "microsoft/deberta-v2-xlarge": DEBERTA_V2_XLARGE,
@@ -247,13 +265,17 @@ _REGISTRY = {
     "facebook/data2vec-audio-large": DATA2VEC_AUDIO_LARGE,
     "facebook/data2vec-audio-large-960h": replace(DATA2VEC_AUDIO_LARGE, name="facebook/data2vec-audio-large-960h"),
     "facebook/w2v-bert-2.0": W2V_BERT_2,
+    "facebook/wav2vec2-conformer-rope-large": W2V_CONFORMER_ROPE_LARGE,
+    "facebook/wav2vec2-conformer-rope-large-960h-ft": replace(W2V_CONFORMER_ROPE_LARGE, name="facebook/wav2vec2-conformer-rope-large-960h-ft"),
+    "facebook/wav2vec2-conformer-rel-pos-large": W2V_CONFORMER_REL_LARGE,
+    "facebook/wav2vec2-conformer-rel-pos-large-960h-ft": replace(W2V_CONFORMER_REL_LARGE, name="facebook/wav2vec2-conformer-rel-pos-large-960h-ft"),
 }
 
 
 def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int = 2,
                   ffn: int = 256, conv_dim: int = 64, pos_groups: int = 2, text_conv_kernel: int = 0,
                   base: bool = False, conv_bias: bool = False, depthwise_kernel: int = 31, left_max: int = 64,
-                  right_max: int = 8) -> EncoderGeometry:
+                  right_max: int = 8, position_type: str = "rotary") -> EncoderGeometry:
     """Small geometries with the real kernel/stride tuples; used by the parity
     fixtures under tests/golden (SURVEY 8c item 1).  ``hidden // heads`` selects
     the head-dim code path (64 WavLM/Whisper, 80 HuBERT-XL, 120 XLS-R-2B) and
@@ -276,6 +298,10 @@ def tiny_geometry(family: str, *, hidden: int = 128, heads: int = 2, layers: int
         return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn, conv_depthwise_kernel=depthwise_kernel,
                                left_max_positions=left_max, right_max_positions=right_max,
                                name=f"tiny-w2v-bert-d{hidden}h{heads}")
+    if family == FAMILY_W2V_CONFORMER:
+        return EncoderGeometry(family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn, conv_dim=(conv_dim,) * 7,
+                               conv_bias=conv_bias, conv_depthwise_kernel=depthwise_kernel, position_type=position_type,
+                               max_source_positions=5000, name=f"tiny-w2v-conformer-{position_type}-d{hidden}h{heads}")
     if family == FAMILY_DATA2VEC_AUDIO:
         return EncoderGeometry(
             family=family, num_layers=layers, hidden=hidden, heads=heads, ffn=ffn, conv_dim=(conv_dim,) * 7, conv_bias=conv_bias,
@@ -411,8 +437,42 @@ def geometry_from_config(cfg: dict, name: str = "") -> EncoderGeometry:
             heads=int(cfg["num_attention_heads"]), ffn=int(cfg["intermediate_size"]), fbank_mels=fdim // stride, fbank_stride=stride,
             conv_depthwise_kernel=k, left_max_positions=lm, right_max_positions=rm,
             layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), name=name)
+    if mt == FAMILY_W2V_CONFORMER:
+        # HF Wav2Vec2ConformerConfig.  Built: the layer-norm stem, rotary or relative positions, swish, no adapter (the settings of
+        # facebook/wav2vec2-conformer-{rope,rel-pos}-large and their -960h-ft fine-tunes).  The class defaults are NOT those settings
+        # (feat_extract_norm "group", hidden_act "gelu"), so a missing key is refused like the value it stands for.
+        if cfg.get("add_adapter", False):
+            raise OSError(f"{name}: add_adapter=True (an adapter stack after the encoder) is not supported")
+        norm = cfg.get("feat_extract_norm", "group")
+        if norm != "layer":
+            raise OSError(f"{name}: feat_extract_norm='{norm}' is not supported (the path implements the layer-norm feature extractor "
+                          "of the published wav2vec2-conformer checkpoints)")
+        act = str(cfg.get("hidden_act", "gelu"))
+        if act not in ("swish", "silu"):
+            raise OSError(f"{name}: hidden_act='{act}' is not supported (the path implements swish)")
+        k = int(cfg.get("conv_depthwise_kernel_size", 31))
+        if k % 2 == 0:
+            raise OSError(f"{name}: an even conv_depthwise_kernel_size ({k}) is not supported")
+        if k > 31:
+            raise OSError(f"{name}: conv_depthwise_kernel_size {k} is beyond the 31 taps the convolution-module kernel holds")
+        hidden, heads = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+        if heads < 1 or hidden % heads or hidden // heads != 64:
+            raise OSError(f"{name}: hidden_size {hidden} / num_attention_heads {heads} is not a head dim of 64, the one the conformer "
+                          "attention is built for")
+        pos = cfg.get("position_embeddings_type", "relative")
+        if pos not in W2V_CONFORMER_POSITION_TYPES:
+            raise OSError(f"{name}: position_embeddings_type='{pos}' is not supported (the path implements "
+                          + " / ".join(W2V_CONFORMER_POSITION_TYPES) + ")")
+        return EncoderGeometry(
+            family=FAMILY_W2V_CONFORMER, num_layers=int(cfg["num_hidden_layers"]), hidden=hidden, heads=heads,
+            ffn=int(cfg["intermediate_size"]), conv_dim=tuple(int(c) for c in cfg.get("conv_dim", (512,) * 7)),
+            conv_kernel=tuple(int(c) for c in cfg.get("conv_kernel", (10, 3, 3, 3, 3, 2, 2))),
+            conv_stride=tuple(int(c) for c in cfg.get("conv_stride", (5, 2, 2, 2, 2, 2, 2))),
+            conv_bias=bool(cfg.get("conv_bias", False)), feat_extract_norm="layer", conv_depthwise_kernel=k, position_type=pos,
+            rotary_base=int(cfg.get("rotary_embedding_base", 10000)), max_source_positions=int(cfg.get("max_source_positions", 5000)),
+            layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-5)), name=name)
     raise OSError(f"{name}: model_type '{mt}' is not an encoder this path implements "
-                  "(wavlm / wav2vec2 / hubert / data2vec-audio / wav2vec2-bert / whisper / roberta / deberta-v2)")
+                  "(wavlm / wav2vec2 / hubert / data2vec-audio / wav2vec2-bert / wav2vec2-conformer / whisper / roberta / deberta-v2)")
 
 
 def find_config_json(ssl_type: str, checkpoint: str = "") -> str:
@@ -527,6 +587,9 @@ TINY_DATA2VEC_AUDIO_G48 = tiny_geometry(FAMILY_DATA2VEC_AUDIO, hidden=192, heads
 # three heads) that no constant of the first survives
 TINY_W2V_BERT = tiny_geometry(FAMILY_W2V_BERT, hidden=128, heads=2, ffn=256)
 TINY_W2V_BERT_H3 = tiny_geometry(FAMILY_W2V_BERT, hidden=192, heads=3, ffn=384, depthwise_kernel=7, left_max=5, right_max=3)
+# wav2vec2-conformer fixture geometries (tests/golden/tiny_w2v_conformer_*.npz): one per position type, two and three heads of 64
+TINY_W2V_CONFORMER_ROPE = tiny_geometry(FAMILY_W2V_CONFORMER, hidden=128, heads=2, ffn=256, conv_bias=True, position_type="rotary")
+TINY_W2V_CONFORMER_REL = tiny_geometry(FAMILY_W2V_CONFORMER, hidden=192, heads=3, ffn=384, conv_bias=True, position_type="relative")
 
 
 @dataclass(frozen=True)
@@ -617,11 +680,12 @@ class GenerationSpec:
         return GenerationSpec.from_config(cfg, language)
 
 
-# The six hub classes that share one head (HF *ForSequenceClassification of the speech families, WhisperForAudioClassification):
+# The seven hub classes that share one head (HF *ForSequenceClassification of the speech families, WhisperForAudioClassification):
 # optional softmax-weighted sum of the hidden states -> projector -> mean over the frames -> classifier (engine.ClassifierHead).
 AUDIO_CLASSIFICATION_ARCHITECTURES = (
     "Wav2Vec2ForSequenceClassification", "WavLMForSequenceClassification", "HubertForSequenceClassification",
-    "Data2VecAudioForSequenceClassification", "Wav2Vec2BertForSequenceClassification", "WhisperForAudioClassification")
+    "Data2VecAudioForSequenceClassification", "Wav2Vec2BertForSequenceClassification", "WhisperForAudioClassification",
+    "Wav2Vec2ConformerForSequenceClassification")
 
 
 @dataclass(frozen=True)
@@ -679,7 +743,7 @@ def resolve_classifier(ssl_type: str, checkpoint: str = "") -> Optional[Classifi
 # The hub classes that share the x-vector head (HF *ForXVector, what ``AutoModelForAudioXVector`` loads): optional softmax-weighted sum of
 # the hidden states -> projector -> ReLU TDNN layers -> statistics pooling -> feature_extractor -> classifier (engine.XVectorHead).
 XVECTOR_ARCHITECTURES = ("Wav2Vec2ForXVector", "WavLMForXVector", "Data2VecAudioForXVector", "Wav2Vec2BertForXVector")
-# ... and the two whose encoders this path does not build
+# ... and the two it does not run behind: UniSpeech-SAT's encoder is not built, the conformer encoders' x-vector head is not wired
 XVECTOR_UNBUILT_ARCHITECTURES = ("UniSpeechSatForXVector", "Wav2Vec2ConformerForXVector")
 
 
@@ -783,7 +847,7 @@ def resolve_xvector(ssl_type: str, checkpoint: str = "") -> Optional[XVectorSpec
 # The hub classes that put a CTC head on the encoders built here (HF *ForCTC, what ``AutoModelForCTC`` loads): dropout ->
 # lm_head(last_hidden_state) -> argmax per frame -> equal neighbours merged, blanks dropped (engine.CTCHead).
 CTC_ARCHITECTURES = ("Wav2Vec2ForCTC", "HubertForCTC", "WavLMForCTC", "Data2VecAudioForCTC", "Wav2Vec2BertForCTC")
-# ... and those whose encoders this path does not build
+# ... and those it does not run behind: encoders that are not built, and the conformer encoders, whose CTC head is not wired
 CTC_UNBUILT_ARCHITECTURES = ("UniSpeechForCTC", "UniSpeechSatForCTC", "Wav2Vec2ConformerForCTC", "SEWForCTC", "SEWDForCTC")
 
 

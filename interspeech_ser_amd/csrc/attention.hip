@@ -54,7 +54,9 @@ extern "C" { void* ser_attn_dbg_ptr = nullptr; }
 // qe[query][head][clamp(key - query, -Lm, Rm) + Lm], read from global memory per lane -- one constant per query for a key tile wholly outside
 // the band of all 32 queries of the wave, a gather for the tiles that cross it.  Every RK line sits under `if constexpr (RK)`: the other
 // instantiations compile what they compiled before.
-template <int DHP, int MODE, bool PRE, bool TBL, int NWV = 4, bool B2D = false, bool GB = false, bool OCC = false, bool RK = false>
+// RB (ser_attention_rb_v: the wav2vec2-conformer's Transformer-XL positional term; an RK form): the bias of key k is qe[query][head][k],
+// a row indexed by the key's index in its utterance (ser_relpos_bias_v), so every quad is one aligned 16-byte load and no tile has a side.
+template <int DHP, int MODE, bool PRE, bool TBL, int NWV = 4, bool B2D = false, bool GB = false, bool OCC = false, bool RK = false, bool RB = false>
 // waves per SIMD the registers leave room for: two everywhere (round 4: the 96-wide two-plane forms and the 128-wide ones WITHOUT a bias table
 // fit 256 registers unspilled -- head dim 80 in the 3-product modes 98.9 -> 49.9 us per 8 x 499 frames) except the 128-wide two-plane form
 // with a bias table (208 spilled registers at two; no encoder uses it: WavLM's head dim is 64)
@@ -316,6 +318,7 @@ void attention_kernel(const std::conditional_t<RK, AttnParamsRK, AttnParams> p) 
     auto rk_quad = [&](int kb, int side) -> f32x4 {
         if constexpr (RK) {
             const float* qerow = p.qe + ((int64_t)(row0 + qc) * p.H + h) * p.qe_ld;
+            if constexpr (RB) return *(const f32x4*)(qerow + kb);        // kb + 3 < 64 ceil(T / 64) <= qe_ld: the row's own, finite
             if (side) { const float c = qerow[side < 0 ? 0 : p.Lm + p.Rm]; return (f32x4){c, c, c, c}; }
             f32x4 r;
 #pragma unroll
@@ -367,7 +370,7 @@ void attention_kernel(const std::conditional_t<RK, AttnParamsRK, AttnParams> p) 
         DBG_T(0);
         if (DB && kt + 1 < nkt) stage_load(kt + 1, padded || kt + 1 >= nfull);   // issue early: lands under the MFMAs below
         int rk_side = 0;                                             // RK, wave-uniform: where the tile lies for queries qlo .. qlo + 31
-        if constexpr (RK) {
+        if constexpr (RK && !RB) {
             const int qlo = q0 + wave * 32, k0 = kt * ABKV;
             rk_side = (k0 + ABKV - 1 <= qlo - p.Lm) ? -1 : ((k0 >= qlo + 31 + p.Rm) ? 1 : 0);
         }
@@ -755,6 +758,43 @@ extern "C" int ser_attention_rk_v(const ser_attention_rk_args* ra, void* stream)
         }))
         return ser_fail(-5, "ser_attention_rk: bad mode %d", pl.mode);
     return ser_check_launch("ser_attention_rk");
+}
+
+// ser_attention_rb_v: ser_attention_rk_v's plan and argument block; the table is a bias row per (query row, head), indexed by the key.
+extern "C" int ser_attention_rb_v(const ser_attention_rb_args* ra, void* stream) {
+    if (!ra || !ra->pb) return ser_fail(-1, "ser_attention_rb: null pointer");
+    const ser_attention_args* args = &ra->base;
+    if (args->table || args->gate || args->gru_const || args->gate_x || args->key_lens || args->bias2d || args->out_mode)
+        return ser_fail(-2, "ser_attention_rb: takes no table, gate, key_lens, bias2d or FP16M output");
+    if (args->scale > 0.f || args->dh != 64) return ser_fail(-2, "ser_attention_rb: needs a pre-scaled q (scale <= 0) and head dim 64");
+    if (args->mode != SER_MODE_BF16 && args->mode != SER_MODE_FP32X && args->mode != SER_MODE_FP16X)
+        return ser_fail(-5, "ser_attention_rb: bad mode %d (bf16 / fp32x / fp16x)", args->mode);
+    if (args->max_frames <= 0 || (ra->ld_pb % ATTN_BKV) || ra->ld_pb < ((int64_t)args->max_frames + ATTN_BKV - 1) / ATTN_BKV * ATTN_BKV ||
+        ((uintptr_t)ra->pb & 15))
+        return ser_fail(-2, "ser_attention_rb: ld_pb=%lld must be a multiple of %d and >= max_frames rounded up to it; pb 16-byte aligned",
+                        (long long)ra->ld_pb, ATTN_BKV);
+    attn_launch pl;
+    if (int rc = attn_plan(args, &pl)) return rc;
+    if (pl.occ) {                                   // as ser_attention_rk_v: the double-buffered form's LDS
+        pl.occ = false;
+        pl.nbuf = 2;
+        pl.lds = (size_t)2 * (attn_qk_planes(pl.mode) + attn_v_planes(pl.mode)) * ATTN_BKV * pl.dhp * 2;
+    }
+    AttnParamsRK p = {};
+    p.qkv = (const unsigned short*)args->qkv; p.ld = args->ld; p.plane = args->plane_stride;
+    p.q_col = args->q_col; p.k_col = args->k_col; p.v_col = args->v_col;
+    p.frame_offs = args->frame_offs;
+    p.out = (unsigned short*)args->out; p.ldo = args->ldo; p.out_plane = args->out_plane_stride;
+    p.H = args->H; p.dh = args->dh; p.scale = args->scale; p.b2d_T = args->max_frames;
+    p.B = args->B; p.nq = pl.nq; p.nitems = (int)pl.grid;
+    p.qe = ra->pb; p.qe_ld = ra->ld_pb; p.Lm = 0; p.Rm = 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(pl.mode, [&](auto M) {
+            hipLaunchKernelGGL((attention_kernel<64, M(), true, false, ATTN_NWV, false, false, false, true, true>), dim3(pl.grid, 1, 1),
+                               dim3(64 * ATTN_NWV), pl.lds, s, p);
+        }))
+        return ser_fail(-5, "ser_attention_rb: bad mode %d", pl.mode);
+    return ser_check_launch("ser_attention_rb");
 }
 
 extern "C" int ser_attention(const void* qkv, int64_t ld, int64_t plane_stride, int q_col, int k_col, int v_col,

@@ -139,6 +139,22 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_beam_select_v(&c.u.beam_select, stream);
                 break;
             }
+            case SER_OP_ROPE_ROWS: {
+                rc = ser_rope_rows_v(&c.u.rope_rows, stream);
+                break;
+            }
+            case SER_OP_CONFORMER_CONV_BN: {
+                rc = ser_conformer_conv_bn_v(&c.u.conformer_conv_bn, stream);
+                break;
+            }
+            case SER_OP_RELPOS_BIAS: {
+                rc = ser_relpos_bias_v(&c.u.relpos_bias, stream);
+                break;
+            }
+            case SER_OP_ATTENTION_RB: {
+                rc = ser_attention_rb_v(&c.u.attention_rb, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

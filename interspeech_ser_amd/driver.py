@@ -168,7 +168,7 @@ class _Extractor:
             # the post-LayerNorm (*-base) encoders run the text encoders' modes; the others need FP16M copies out of ser_layernorm
             print(f"--mode {mode} is not implemented for post-LayerNorm encoders ({name}): using f16x")
             mode = "f16x"
-        if geo.family == C.FAMILY_W2V_BERT and mode not in POST_LN_MODES:
+        if geo.family in (C.FAMILY_W2V_BERT, C.FAMILY_W2V_CONFORMER) and mode not in POST_LN_MODES:
             # the conformer layers run ser_layernorm between their GEMMs, like the post-LayerNorm encoders: the same three modes
             print(f"--mode {mode} is not implemented for the conformer encoder ({name}): using f16x")
             mode = "f16x"

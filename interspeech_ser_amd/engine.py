@@ -31,7 +31,8 @@ from . import _lib
 from ._lib import check, lib
 from .arena import Pinned, SlotArenas, TableBlob
 from .weights import check_f16_weight
-from .config import EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_WAVLM, FAMILY_WHISPER
+from .config import (EncoderGeometry, FAMILY_DATA2VEC_AUDIO, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_W2V_CONFORMER, FAMILY_WAVLM,
+                     FAMILY_WHISPER)
 
 MODES = {"bf16": _lib.MODE_BF16, "fp32x": _lib.MODE_FP32X, "f16": _lib.MODE_FP16, "f16q": _lib.MODE_FP16, "f16a": _lib.MODE_FP16,
          "f16x": _lib.MODE_FP16X, "f16m": _lib.MODE_FP16M, "f16mf": _lib.MODE_FP16M}
@@ -1101,33 +1102,8 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
         if not geo.feat_proj_layer_norm:
             raise NotImplementedError("feat_proj_layer_norm=False checkpoints are not supported")
         sd = state_dict
-        D, C0 = geo.hidden, geo.conv_dim[0]
-        if any(c != C0 for c in geo.conv_dim):
-            raise NotImplementedError("conv_dim must be uniform")
-        # conv stack
-        p0 = "feature_extractor.conv_layers.0"
-        self.conv0_w = self._dev_f32(sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]))
-        self.conv0_b = self._dev_f32(sd[p0 + ".conv.bias"]) if geo.conv_bias else None
-        # matrix-core form of conv layer 0: taps zero-padded to K = 64 (frames come from ser_wave_frames)
-        if geo.conv_kernel[0] > 64:
-            raise NotImplementedError("conv layer 0 kernel wider than 64 taps")
-        w0 = torch.zeros((C0, 64), dtype=torch.float32)
-        w0[:, : geo.conv_kernel[0]] = sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]).float()
-        self.conv0 = self._linear(w0, sd[p0 + ".conv.bias"] if geo.conv_bias else None, stem=True, name=p0 + ".conv.weight")
-        if self.gn_stem:        # GroupNorm(C, C) of conv layer 0 (its affine); layers 1..6 have no norm
-            self.gn0 = self._ln_pair(sd, p0 + ".layer_norm")
-            self.conv_ln = [None] * len(geo.conv_dim)
-        else:
-            self.conv_ln = [self._ln_pair(sd, f"feature_extractor.conv_layers.{i}.layer_norm") for i in range(len(geo.conv_dim))]
-        self.convs: List[Linear] = []
-        for i in range(1, len(geo.conv_dim)):
-            p = f"feature_extractor.conv_layers.{i}.conv"
-            w = sd[p + ".weight"].float()                                  # [Cout, Cin, k]
-            w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)                # K index = tap*Cin + c
-            self.convs.append(self._linear(w2, sd[p + ".bias"] if geo.conv_bias else None, stem=True, name=p + ".weight"))
-        self.proj_ln = self._ln_pair(sd, "feature_projection.layer_norm")
-        self.proj = self._linear(sd["feature_projection.projection.weight"], sd["feature_projection.projection.bias"], stem=True,
-                                 name="feature_projection.projection.weight")
+        D = geo.hidden
+        self._init_stem(sd)
         # positional conv: per group [Cg out][tap][Cg in padded to a multiple of 64]
         G, k = geo.pos_conv_groups, geo.pos_conv_kernel
         Cg = D // G
@@ -1171,6 +1147,41 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
             self.rel_embed = self._dev_f32(sd["encoder.layers.0.attention.rel_attn_embed.weight"])
         self._arenas = SlotArenas(self._build_arena)          # per slot; ar["plan"]: the plan currently laid out in it
 
+    def _init_stem(self, sd) -> None:
+        """The convolutional waveform encoder and the feature projection (HF *FeatureEncoder / *FeatureProjection): weights of the wav2vec2-style
+        stem every family of this class -- and the conformer encoders behind it -- shares."""
+        geo = self.geo
+        self.gn_stem = geo.feat_extract_norm == "group"
+        if not geo.feat_proj_layer_norm:
+            raise NotImplementedError("feat_proj_layer_norm=False checkpoints are not supported")
+        C0 = geo.conv_dim[0]
+        if any(c != C0 for c in geo.conv_dim):
+            raise NotImplementedError("conv_dim must be uniform")
+        # conv stack
+        p0 = "feature_extractor.conv_layers.0"
+        self.conv0_w = self._dev_f32(sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]))
+        self.conv0_b = self._dev_f32(sd[p0 + ".conv.bias"]) if geo.conv_bias else None
+        # matrix-core form of conv layer 0: taps zero-padded to K = 64 (frames come from ser_wave_frames)
+        if geo.conv_kernel[0] > 64:
+            raise NotImplementedError("conv layer 0 kernel wider than 64 taps")
+        w0 = torch.zeros((C0, 64), dtype=torch.float32)
+        w0[:, : geo.conv_kernel[0]] = sd[p0 + ".conv.weight"].reshape(C0, geo.conv_kernel[0]).float()
+        self.conv0 = self._linear(w0, sd[p0 + ".conv.bias"] if geo.conv_bias else None, stem=True, name=p0 + ".conv.weight")
+        if self.gn_stem:        # GroupNorm(C, C) of conv layer 0 (its affine); layers 1..6 have no norm
+            self.gn0 = self._ln_pair(sd, p0 + ".layer_norm")
+            self.conv_ln = [None] * len(geo.conv_dim)
+        else:
+            self.conv_ln = [self._ln_pair(sd, f"feature_extractor.conv_layers.{i}.layer_norm") for i in range(len(geo.conv_dim))]
+        self.convs: List[Linear] = []
+        for i in range(1, len(geo.conv_dim)):
+            p = f"feature_extractor.conv_layers.{i}.conv"
+            w = sd[p + ".weight"].float()                                  # [Cout, Cin, k]
+            w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)                # K index = tap*Cin + c
+            self.convs.append(self._linear(w2, sd[p + ".bias"] if geo.conv_bias else None, stem=True, name=p + ".weight"))
+        self.proj_ln = self._ln_pair(sd, "feature_projection.layer_norm")
+        self.proj = self._linear(sd["feature_projection.projection.weight"], sd["feature_projection.projection.bias"], stem=True,
+                                 name="feature_projection.projection.weight")
+
     # ------------------------------------------------------------------ per-slot arenas + plans
     def _build_arena(self, cap: Dict[str, int]) -> dict:
         """Buffer set of one slot (arena.SlotArenas): a stream of ragged batches re-uses the same HBM instead of allocating ~25 tensors
@@ -1179,24 +1190,13 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
         C0, D = geo.conv_dim[0], geo.hidden
         nl = len(geo.conv_dim)
         ar = {}
-        ar["frames"] = self._new_act(cap["rows0"], 64, stem=True)
-        ar["wave_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_WAVE_FRAMES, cap["B"], 0, 0, 0, self.stem_mode),
-                                      dtype=torch.uint8, device=dev)
-        ar["conv_act"] = [self._new_act(cap["rows0"], C0, stem=True), self._new_act(cap["rows1"], C0, stem=True)]       # ping-pong
-        ar["conv_rowoff"] = [torch.empty(cap["rows1"], dtype=torch.int32, device=dev) for _ in range(1, nl)]
+        self._stem_arena(ar, cap)
         ar["halo_rowmap"] = torch.empty(cap["M"], dtype=torch.int32, device=dev)
         ar["pos_rowoff"] = torch.empty(cap["M"], dtype=torch.int32, device=dev)
-        ar["feat_f32"] = torch.empty((cap["M"], C0), dtype=torch.float32, device=dev)
-        ar["feat_act"] = self._new_act(cap["M"], C0, stem=True)
         ar["proj_f32"] = torch.empty((cap["M"], D), dtype=torch.float32, device=dev)
         ar["halo_act"] = self._new_act(cap["halo"], D, zero=True, extra_rows=1, stem=self.pos_in_stem)
         ar["states"] = torch.empty((geo.num_layers + 1, cap["M"], D), dtype=torch.float32, device=dev)
         ar["first_groups"] = 2                               # ser_row_center writes one (sum, sum^2) slot + one zero slot
-        if self.gn_stem:
-            # the GroupNorm stem's per-(utterance, channel) affine + its workspace
-            ar["gn_scale"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
-            ar["gn_shift"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
-            ar["gn_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_GN_STATS, cap["B"], 0, 0, 0, self.stem_mode), dtype=torch.uint8, device=dev)
         if self.post_ln:
             self._post_ln_buffers(ar, cap["M"], 3 * D + (self._gate_width() if geo.family == FAMILY_WAVLM else 0))
         else:
@@ -1207,6 +1207,55 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
         ar["tab"] = TableBlob(cap["B"], 1 + nl + (nl - 1) + 2, dev)
         return ar
 
+    def _stem_arena(self, ar: dict, cap: Dict[str, int]) -> None:
+        """the stem's buffers of one slot: ``cap`` rows after conv 0 / conv 1, frames M, utterances B"""
+        geo, dev = self.geo, self.device
+        C0, nl = geo.conv_dim[0], len(geo.conv_dim)
+        ar["frames"] = self._new_act(cap["rows0"], 64, stem=True)
+        ar["wave_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_WAVE_FRAMES, cap["B"], 0, 0, 0, self.stem_mode),
+                                      dtype=torch.uint8, device=dev)
+        ar["conv_act"] = [self._new_act(cap["rows0"], C0, stem=True), self._new_act(cap["rows1"], C0, stem=True)]       # ping-pong
+        ar["conv_rowoff"] = [torch.empty(cap["rows1"], dtype=torch.int32, device=dev) for _ in range(1, nl)]
+        ar["feat_f32"] = torch.empty((cap["M"], C0), dtype=torch.float32, device=dev)
+        ar["feat_act"] = self._new_act(cap["M"], C0, stem=True)
+        if self.gn_stem:
+            # the GroupNorm stem's per-(utterance, channel) affine + its workspace
+            ar["gn_scale"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
+            ar["gn_shift"] = torch.empty((cap["B"], C0), dtype=torch.float32, device=dev)
+            ar["gn_work"] = torch.empty(lib.ser_workspace_bytes(_lib.WS_GN_STATS, cap["B"], 0, 0, 0, self.stem_mode), dtype=torch.uint8, device=dev)
+
+    def _stem_offsets(self, lengths: Sequence[int]):
+        """per conv layer i the [B + 1] first rows of every utterance after it (int64); the last one's are the frame offsets"""
+        chains = [self.geo.frame_chain(n) for n in lengths]
+        if len(lengths) == 0 or min(c[-1] for c in chains) < 1:
+            raise ValueError("utterance shorter than the conv stack's receptive field (400 samples)")
+        return [np.concatenate([[0], np.cumsum([c[i] for c in chains])]).astype(np.int64) for i in range(len(self.geo.conv_dim))]
+
+    def _stem_tables(self, pl: dict, tab: TableBlob, lengths: Sequence[int], offs):
+        """the stem's O(B) tables into the blob (sample offsets, the per-layer offsets, the conv layers' base rows: 2 nl regions) and the
+        sizes a recorded list patches; returns (device offsets per layer, base rows per conv layer 1..)"""
+        B, nl = len(lengths), len(offs)
+        pl["rows"] = [Sz(int(o[-1]), f"rows{i}") for i, o in enumerate(offs)]
+        pl["sizes"] = {f"rows{i}": int(r) for i, r in enumerate(pl["rows"])}
+        pl["sample_offs"] = tab.put64(np.concatenate([[0], np.cumsum(lengths)]))
+        offs_dev = [tab.put32(o) for o in offs]             # offs[i][b] = first row of utterance b after conv layer i
+        pl["frame_offs0"] = offs_dev[0]
+        pl["frame_offs"] = offs_dev[-1]
+        pl["frame_offs_host"] = [int(x) for x in offs[-1]]
+        return offs_dev, [tab.put64(offs[i - 1][:B]) for i in range(1, nl)]
+
+    def _stem_index(self, pl: dict, ar: dict, offs_dev, base_conv, st: int) -> None:
+        """the conv layers' O(rows) row tables, on the device (after the blob was sent)"""
+        geo = self.geo
+        B, C0 = len(pl["lengths"]), geo.conv_dim[0]
+        rowoffs = []
+        for i in range(1, len(geo.conv_dim)):
+            out = ar["conv_rowoff"][i - 1][: pl["rows"][i]]
+            check(lib.ser_ragged_index(offs_dev[i].data_ptr(), base_conv[i - 1].data_ptr(), B, geo.conv_stride[i], C0, 8,
+                                       out.data_ptr(), pl["rows"][i], st), "ser_ragged_index")
+            rowoffs.append(out)
+        pl["conv_rowoff"] = rowoffs
+
     def _plan(self, lengths: Sequence[int], slot: int = 0):
         """Row bookkeeping of one ragged batch in slot ``slot``'s arena.  Only O(B) integers are computed on the
         host and uploaded (one pinned blob, one async copy); the O(rows) row tables are built on the device by
@@ -1216,11 +1265,8 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
         geo, dev = self.geo, self.device
         B = len(lengths)
         nl = len(geo.conv_dim)
-        chains = [geo.frame_chain(n) for n in lengths]
-        if B == 0 or min(c[-1] for c in chains) < 1:
-            raise ValueError("utterance shorter than the conv stack's receptive field (400 samples)")
-        offs = [np.concatenate([[0], np.cumsum([c[i] for c in chains])]).astype(np.int64) for i in range(nl)]
-        T = [c[-1] for c in chains]
+        offs = self._stem_offsets(lengths)
+        T = [int(t) for t in np.diff(offs[-1])]
         M, Tmax = int(offs[-1][-1]), max(T)
         half = geo.pos_conv_kernel // 2
         halo_rows = int(M + half * (B + 1))
@@ -1231,27 +1277,14 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
         C0, D = geo.conv_dim[0], geo.hidden
         tab = ar["tab"].begin()
         pl = dict(ar)                                       # arena buffers + this batch's views / numbers
-        pl["rows"] = [Sz(int(o[-1]), f"rows{i}") for i, o in enumerate(offs)]
-        pl["sizes"] = {f"rows{i}": int(r) for i, r in enumerate(pl["rows"])}
+        offs_dev, base_conv = self._stem_tables(pl, tab, lengths, offs)
         pl["sizes"].update(M=M, B=B, Tmax=Tmax)
         pl.update(B=Sz(B, "B"), lengths=lengths, T=T, M=Sz(M, "M"), Tmax=Sz(Tmax, "Tmax"), halo_rows=halo_rows)
-        pl["sample_offs"] = tab.put64(np.concatenate([[0], np.cumsum(lengths)]))
-        offs_dev = [tab.put32(o) for o in offs]             # offs[i][b] = first row of utterance b after conv layer i
-        pl["frame_offs0"] = offs_dev[0]
-        pl["frame_offs"] = offs_dev[-1]
-        pl["frame_offs_host"] = [int(x) for x in offs[-1]]
-        base_conv = [tab.put64(offs[i - 1][:B]) for i in range(1, nl)]
         # halo'd layout of the positional-conv input: [64 zero rows][utt 0][64 zero rows][utt 1] ... [64 zero rows]
         _, halo_index = _halo_layout(tab, offs[-1], offs_dev[-1], half, D, ar["halo_rowmap"], [ar["pos_rowoff"]], ar["halo_act"])
         tab.send()
         # ---- O(rows) tables on the device
-        rowoffs = []
-        for i in range(1, nl):
-            out = ar["conv_rowoff"][i - 1][: pl["rows"][i]]
-            check(lib.ser_ragged_index(offs_dev[i].data_ptr(), base_conv[i - 1].data_ptr(), B, geo.conv_stride[i], C0, 8,
-                                       out.data_ptr(), pl["rows"][i], st), "ser_ragged_index")
-            rowoffs.append(out)
-        pl["conv_rowoff"] = rowoffs
+        self._stem_index(pl, ar, offs_dev, base_conv, st)
         halo_index(st, ar["plan"] is not None)
         pl["states"] = ar["states"][:, :M]
         if geo.family == FAMILY_WAVLM:
@@ -1274,31 +1307,9 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
 
     def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
         geo = self.geo
-        B, M, D, C0 = pl["B"], pl["M"], geo.hidden, geo.conv_dim[0]
-        # a6 + a7 (layer 0): zero-mean / unit-variance per utterance fused with framing, then
-        # Conv1d(1,C,10,5)+LayerNorm+GELU on the matrix cores (K padded to 64, LayerNorm epilogue)
-        self._wave_frames(pl, packed_wave)
-        a_in = pl["conv_act"][0]
-        if self.gn_stem:
-            self._groupnorm_stem(pl, packed_wave)
-        else:
-            self._gemm(pl["frames"], self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
-                       k_algo=geo.conv_kernel[0], stem=True)
-        # a7: conv layers 1..6 as implicit GEMMs with LayerNorm(C)+GELU fused into the epilogue
-        # (the 512-wide output row lives in one block tile, so the pre-LN activations never touch HBM)
-        nl = len(geo.conv_dim)
-        for i in range(1, nl):
-            rows = pl["rows"][i]
-            if i < nl - 1:
-                a_view = pl["conv_act"][i % 2].first_rows(rows)
-                self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
-                           ln=self.conv_ln[i], ln_eps=1e-5, out_act=a_view, stem=True)     # (ln None: *-base, GELU only)
-                a_in = a_view
-            else:
-                self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
-                           ln=self.conv_ln[i], ln_eps=1e-5, out_f32=pl["feat_f32"], ldo_f32=C0, stem=True)
-        # a9: feature projection (LN -> Linear); also scatter into the zero-halo'd pos-conv input
-        self._layernorm(pl["feat_f32"], C0, self.proj_ln, M, C0, out_act=pl["feat_act"], stem=True)
+        B, M, D = pl["B"], pl["M"], geo.hidden
+        self._conv_stack(pl, packed_wave)
+        # a9 (its Linear): the feature projection; also scatter into the zero-halo'd pos-conv input
         self._gemm(pl["feat_act"], self.proj, M, out_f32=pl["proj_f32"], ldo_f32=D,
                    out_act=pl["halo_act"], out_rowmap=pl["halo_rowmap"], stem=True,
                    out_mode=self.stem_mode if self.pos_in_stem else self.mode)
@@ -1321,6 +1332,35 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
             return
         # a11/a12: stable-LayerNorm encoder layers (LayerNorms deferred into the GEMMs)
         self._run_layers(pl, states, pl["first_groups"], B, pl["Tmax"], last_state)
+
+    def _conv_stack(self, pl, packed_wave: torch.Tensor) -> None:
+        """packed samples -> the feature projection's LayerNorm'd operand rows ``feat_act`` [M, C0]"""
+        geo = self.geo
+        M, C0 = pl["M"], geo.conv_dim[0]
+        # a6 + a7 (layer 0): zero-mean / unit-variance per utterance fused with framing, then
+        # Conv1d(1,C,10,5)+LayerNorm+GELU on the matrix cores (K padded to 64, LayerNorm epilogue)
+        self._wave_frames(pl, packed_wave)
+        a_in = pl["conv_act"][0]
+        if self.gn_stem:
+            self._groupnorm_stem(pl, packed_wave)
+        else:
+            self._gemm(pl["frames"], self.conv0, pl["rows"][0], act=_lib.ACT_GELU, ln=self.conv_ln[0], ln_eps=1e-5, out_act=a_in,
+                       k_algo=geo.conv_kernel[0], stem=True)
+        # a7: conv layers 1..6 as implicit GEMMs with LayerNorm(C)+GELU fused into the epilogue
+        # (the 512-wide output row lives in one block tile, so the pre-LN activations never touch HBM)
+        nl = len(geo.conv_dim)
+        for i in range(1, nl):
+            rows = pl["rows"][i]
+            if i < nl - 1:
+                a_view = pl["conv_act"][i % 2].first_rows(rows)
+                self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
+                           ln=self.conv_ln[i], ln_eps=1e-5, out_act=a_view, stem=True)     # (ln None: *-base, GELU only)
+                a_in = a_view
+            else:
+                self._gemm(a_in, self.convs[i - 1], rows, a_rowoff=pl["conv_rowoff"][i - 1], act=_lib.ACT_GELU,
+                           ln=self.conv_ln[i], ln_eps=1e-5, out_f32=pl["feat_f32"], ldo_f32=C0, stem=True)
+        # a9 (its LayerNorm): the feature projection's input
+        self._layernorm(pl["feat_f32"], C0, self.proj_ln, M, C0, out_act=pl["feat_act"], stem=True)
 
     def _wave_frames(self, pl, packed_wave: torch.Tensor) -> None:
         """ser_wave_frames: every utterance's samples normalised (``normalize``) and framed into conv layer 0's operand rows."""
@@ -3854,10 +3894,10 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         a.B, a.D, a.K, a.max_frames, a.rows, a.mode = pl["B"], geo.hidden, geo.conv_depthwise_kernel, pl["Tmax"], pl["M"], self.mode
         self._issue(_lib.OP_CONFORMER_CONV, a, "ser_conformer_conv", B=pl["B"], max_frames=pl["Tmax"], rows=pl["M"])
 
-    def _ffn_half(self, pl, lay, f: str, x: torch.Tensor, out: torch.Tensor) -> None:
-        """out = x + FFN(LN x) / 2 (the half sits in the output Linear)"""
+    def _ffn_half(self, pl, lay, f: str, x: torch.Tensor, out: torch.Tensor, eps=None) -> None:
+        """out = x + FFN(LN x) / 2 (the half sits in the output Linear); ``eps``: the LayerNorm's, default the geometry's"""
         M, D, F = pl["M"], self.geo.hidden, self.geo.ffn
-        self._layernorm(x, D, lay[f + "_ln"], M, D, out_act=pl["xa"])
+        self._layernorm(x, D, lay[f + "_ln"], M, D, out_act=pl["xa"], eps=eps)
         self._gemm(pl["xa"], lay[f + "_fc1"], M, out_f32=pl["f1"], ldo_f32=F)
         self._swish_rows(pl["f1"], pl["ffn"], M, F)
         self._gemm(pl["ffn"], lay[f + "_fc2"], M, residual=x, ldr=D, out_f32=out, ldo_f32=D)
@@ -3903,6 +3943,238 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         return pl["fb"][: int(pl["M"])]
 
 
+class ConformerSpeechEncoder(SpeechEncoder):
+    """The wav2vec2-conformer encoders (HF Wav2Vec2ConformerModel; not in the reference, whose heads take any [T, D] stream) on libserhip:
+    ``SpeechEncoder``'s layer-norm conv stem and feature projection -- hidden_states[0], there is no positional convolution -- and per
+    conformer layer
+        x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(x);  x += FFN2(LN x) / 2;  x = LN x
+    on ser_layernorm_v, ser_gemm and ser_swish_rows_v as ``W2vBertEncoder`` runs it, with ser_conformer_conv_bn_v (centred window, BatchNorm
+    in eval folded to a per-channel affine at load) between the convolution module's pointwise GEMMs and one of two position schemes
+    (``geo.position_type``, include/ser_hip.h a35):
+      "rotary"    ser_rope_rows_v rotates the layer-normed rows; q | k are projected from the rotated planes and v from the plain ones into
+                  one packed buffer, then ser_attention_v;
+      "relative"  one packed projection whose q carries pos_bias_u, P = linear_pos(pe) by ser_gemm in fixed 256-row chunks anchored at
+                  distance 0 (a row of P has the same bits whatever the table's length), ser_relpos_bias_v, ser_attention_rb_v.
+    hidden_states[i < L] is layer i's input, hidden_states[L] = encoder.layer_norm of the last layer's output.  Every utterance alone."""
+
+    P_CHUNK = 256            # rows per launch of the P GEMM, and the granule of the distance table's half-length
+
+    def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "f16x", normalize: bool = True):
+        from .weights import fold_batch_norm, fold_pos_bias_u, fold_w2v_bert_ffn, rotary_inv_freq
+        _WaveIO.__init__(self, geo, device, mode, post_ln=True)       # the conformer modes are the post-LayerNorm encoders': f16x, fp32x, bf16
+        if geo.family != FAMILY_W2V_CONFORMER:
+            raise ValueError(f"ConformerSpeechEncoder runs the {FAMILY_W2V_CONFORMER} family")
+        self.normalize = bool(normalize)
+        sd = state_dict
+        D, H, dh, K = geo.hidden, geo.heads, geo.head_dim, geo.conv_depthwise_kernel
+        if geo.position_type not in ("rotary", "relative"):
+            raise ValueError(f"position type '{geo.position_type}' is not built (rotary / relative)")
+        if geo.feat_extract_norm != "layer":
+            raise NotImplementedError("the conformer encoders are built behind the layer-norm conv stem")
+        if dh != 64:
+            raise ValueError(f"the conformer attention is built for heads of 64 (hidden {D} / {H} heads = {dh})")
+        if D % 64 or geo.ffn % 64 or D > 2048:
+            raise ValueError(f"hidden {D} / intermediate {geo.ffn} must be multiples of 64, hidden <= 2048")
+        if not (K & 1) or K > 31:
+            raise ValueError(f"depthwise kernel {K} (odd, <= 31) unsupported")
+        self.relative = geo.position_type == "relative"
+        self._init_stem(sd)
+        self.enc_ln = self._ln_pair(sd, "encoder.layer_norm")
+        scale = dh ** -0.5 * 1.4426950408889634                        # what the projection's col_scale gives q (exp2-domain softmax)
+        if not self.relative:
+            inv = sd.get("encoder.embed_positions.inv_freq")           # a checkpoint stores HF's buffer; synthetic weights do not
+            self.inv_freq = (inv.detach().float().cpu() if inv is not None else rotary_inv_freq(dh, geo.rotary_base))
+            if tuple(self.inv_freq.shape) != (dh // 2,):
+                raise ValueError(f"encoder.embed_positions.inv_freq: shape {tuple(self.inv_freq.shape)}, expected ({dh // 2},)")
+        self._pe: Dict[int, Act] = {}                                  # half-length of the distance table -> operand planes of its pe rows
+        self.layers = []
+        for i in range(geo.num_layers):
+            p = f"encoder.layers.{i}"
+            a, c = p + ".self_attn", p + ".conv_module"
+            lay = {}
+            for f in ("ffn1", "ffn2"):
+                lay[f + "_ln"] = self._ln_pair(sd, f"{p}.{f}_layer_norm")
+                lay[f + "_fc1"] = self._linear(sd[f"{p}.{f}.intermediate_dense.weight"], sd[f"{p}.{f}.intermediate_dense.bias"],
+                                               name=f"{p}.{f}.intermediate_dense.weight")
+                lay[f + "_fc2"] = self._linear(*fold_w2v_bert_ffn(sd[f"{p}.{f}.output_dense.weight"], sd[f"{p}.{f}.output_dense.bias"]),
+                                               name=f"{p}.{f}.output_dense.weight")
+            lay["attn_ln"] = self._ln_pair(sd, p + ".self_attn_layer_norm")
+            w = {n: sd[f"{a}.linear_{n}.weight"] for n in "qkv"}
+            b = {n: sd[f"{a}.linear_{n}.bias"] for n in "qkv"}
+            if self.relative:
+                u, v = sd[a + ".pos_bias_u"], sd[a + ".pos_bias_v"]
+                if tuple(u.shape) != (H, dh) or tuple(v.shape) != (H, dh):
+                    raise ValueError(f"{a}.pos_bias_u / pos_bias_v: shapes {tuple(u.shape)} / {tuple(v.shape)}, expected ({H}, {dh})")
+                lay["qkv"] = self._linear(torch.cat([w[n] for n in "qkv"], 0), torch.cat([fold_pos_bias_u(b["q"], u), b["k"].float(), b["v"].float()], 0),
+                                          name=a + ".linear_{q,k,v}.weight")
+                lay["pos"] = self._linear(sd[a + ".linear_pos.weight"], None, name=a + ".linear_pos.weight")
+                lay["off"] = self._dev_f32(((v.detach().double() - u.detach().double()) * scale).reshape(-1).float())
+            else:
+                lay["qk"] = self._linear(torch.cat([w["q"], w["k"]], 0), torch.cat([b["q"], b["k"]], 0), name=a + ".linear_{q,k}.weight")
+                lay["v"] = self._linear(w["v"], b["v"], name=a + ".linear_v.weight")
+            lay["out"] = self._linear(sd[a + ".linear_out.weight"], sd[a + ".linear_out.bias"], name=a + ".linear_out.weight")
+            lay["conv_ln"] = self._ln_pair(sd, c + ".layer_norm")
+            lay["pw1"] = self._linear(sd[c + ".pointwise_conv1.weight"].reshape(2 * D, D), None, name=c + ".pointwise_conv1.weight")
+            lay["dw"] = self._dev_f32(sd[c + ".depthwise_conv.weight"].reshape(D, K).t())        # [K][D]: a thread's 4 channels are one load
+            bn = c + ".batch_norm"
+            lay["bn"] = tuple(self._dev_f32(t) for t in fold_batch_norm(sd[bn + ".weight"], sd[bn + ".bias"], sd[bn + ".running_mean"],
+                                                                        sd[bn + ".running_var"], 1e-5))      # nn.BatchNorm1d's own eps
+            lay["pw2"] = self._linear(sd[c + ".pointwise_conv2.weight"].reshape(D, D), None, name=c + ".pointwise_conv2.weight")
+            lay["final_ln"] = self._ln_pair(sd, p + ".final_layer_norm")
+            self.layers.append(lay)
+        self._arenas = SlotArenas(self._build_arena)
+
+    def frames(self, num_samples: int) -> int:
+        return self.geo.frames_for(num_samples)
+
+    # ------------------------------------------------------------------ buffers
+    def _pe_rows(self, Tp: int) -> Act:
+        """operand planes of pe(r), r = -Tp .. Tp - 1 (row Tp + r): uploaded once per table length"""
+        act = self._pe.get(Tp)
+        if act is None:
+            from .weights import relpos_pe
+            pe = relpos_pe(Tp + 1, self.geo.hidden)[: 2 * Tp].contiguous().to(self.device)
+            act = self._new_act(2 * Tp, self.geo.hidden)
+            check(lib.ser_split_bf16(pe.data_ptr(), act.ptr, pe.numel(), self.mode, act.plane_stride, _stream()), "ser_split_bf16")
+            torch.cuda.current_stream().synchronize()
+            self._pe[Tp] = act
+        return act
+
+    def _build_arena(self, cap: Dict[str, int]) -> dict:
+        """buffer set of one slot; ``cap``: the stem's rows, frames M, utterances B, longest utterance Tmax (sizes the position tables)"""
+        from .weights import rotary_tables
+        M, B, geo, dev = cap["M"], cap["B"], self.geo, self.device
+        D, F, H = geo.hidden, geo.ffn, geo.heads
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ar = {}
+        self._stem_arena(ar, cap)
+        ar["states"] = f32(geo.num_layers + 1, M, D)
+        ar["r1"], ar["r2"], ar["r3"], ar["r4"], ar["last"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D), f32(M, D)
+        ar["f1"], ar["pw"] = f32(M, F), f32(M, 2 * D)
+        ar["xa"], ar["ctx"], ar["cv"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
+        ar["qkv"], ar["ffn"] = self._new_act(M, 3 * D), self._new_act(M, F)
+        if self.relative:
+            Tp = -(-cap["Tmax"] // self.P_CHUNK) * self.P_CHUNK
+            ar["P_T"], ar["pe"], ar["P"] = Tp, self._pe_rows(Tp), f32(2 * Tp, D)
+            ar["ld_pb"] = -(-cap["Tmax"] // 64) * 64
+            ar["pb"] = f32(M * H, ar["ld_pb"])
+        else:
+            cos, sin = rotary_tables(cap["Tmax"], self.inv_freq)
+            ar["table_T"], ar["cos"], ar["sin"] = cap["Tmax"], cos.to(dev), sin.to(dev)
+            ar["ln"], ar["xr"] = f32(M, D), self._new_act(M, D)
+        ar["tab"] = TableBlob(B, 2 * len(geo.conv_dim), dev)                 # sample_offs | offs[0..nl) (int32) | conv bases [1..nl)
+        if self.fp16_planes:
+            ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        return ar
+
+    def _plan(self, lengths: Sequence[int], slot: int = 0) -> dict:
+        lengths = tuple(int(n) for n in lengths)
+        B, H = len(lengths), self.geo.heads
+        offs = self._stem_offsets(lengths)
+        M, Tmax = int(offs[-1][-1]), int(np.diff(offs[-1]).max())
+        ar = self._arenas.fit(slot, rows0=int(offs[0][-1]), rows1=int(offs[1][-1]) if len(offs) > 1 else 1, M=M, B=B, Tmax=Tmax)
+        if ar["plan"] is not None and ar["plan"]["lengths"] == lengths:
+            return ar["plan"]
+        tab = ar["tab"].begin()
+        pl = dict(ar)
+        offs_dev, base_conv = self._stem_tables(pl, tab, lengths, offs)
+        tab.send()
+        pl["sizes"].update(M=M, B=B, Tmax=Tmax)
+        pl.update(B=Sz(B, "B"), lengths=lengths, M=Sz(M, "M"), Tmax=Sz(Tmax, "Tmax"), states=ar["states"][:, :M])
+        self._stem_index(pl, ar, offs_dev, base_conv, _stream())
+        ar["plan"] = pl
+        return pl
+
+    # ------------------------------------------------------------------ launches
+    _swish_rows = W2vBertEncoder._swish_rows
+    _ffn_half = W2vBertEncoder._ffn_half
+
+    def _conv_mid(self, pl, lay) -> None:
+        geo, out = self.geo, pl["cv"]
+        a = self._cmd("conformer_conv_bn")
+        a.y, a.ldy, a.w, a.scale, a.shift = pl["pw"].data_ptr(), 2 * geo.hidden, lay["dw"].data_ptr(), lay["bn"][0].data_ptr(), lay["bn"][1].data_ptr()
+        a.frame_offs, a.out_act, a.ldo_act, a.out_plane_stride = pl["frame_offs"].data_ptr(), out.ptr, out.cols, out.plane_stride
+        a.range_flag = self._flag
+        a.B, a.D, a.K, a.max_frames, a.rows, a.mode = pl["B"], geo.hidden, geo.conv_depthwise_kernel, pl["Tmax"], pl["M"], self.mode
+        self._issue(_lib.OP_CONFORMER_CONV_BN, a, "ser_conformer_conv_bn", B=pl["B"], max_frames=pl["Tmax"], rows=pl["M"])
+
+    def _rotary_attention(self, pl, lay, scale: float) -> None:
+        """LN rows (fp32 ``ln`` + plain planes ``xa``) -> rotated planes -> q | k from them, v from the plain ones -> ser_attention_v"""
+        geo = self.geo
+        M, D, out = pl["M"], geo.hidden, pl["xr"]
+        a = self._cmd("rope_rows")
+        a.x, a.ldx, a.cos_t, a.sin_t, a.frame_offs = pl["ln"].data_ptr(), D, pl["cos"].data_ptr(), pl["sin"].data_ptr(), pl["frame_offs"].data_ptr()
+        a.out_act, a.ldo_act, a.out_plane_stride, a.range_flag = out.ptr, out.cols, out.plane_stride, self._flag
+        a.B, a.rows, a.D, a.dh, a.table_T, a.max_frames, a.mode = pl["B"], M, D, geo.head_dim, pl["table_T"], pl["Tmax"], self.mode
+        self._issue(_lib.OP_ROPE_ROWS, a, "ser_rope_rows", B=pl["B"], rows=M, max_frames=pl["Tmax"])
+        self._gemm(pl["xr"], lay["qk"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
+        self._gemm(pl["xa"], lay["v"], M, out_act=pl["qkv"], out_col=2 * D)
+        self._attention(pl["qkv"], pl["frame_offs"], pl["B"], pl["Tmax"], pl["ctx"])
+
+    def _relative_attention(self, pl, lay, scale: float) -> None:
+        """packed projection (q carries pos_bias_u) -> P = linear_pos(pe) -> the positional term per (row, head, key) -> ser_attention_rb_v"""
+        geo = self.geo
+        M, D, H, Tp = pl["M"], geo.hidden, geo.heads, pl["P_T"]
+        qkv, out, pe = pl["qkv"], pl["ctx"], pl["pe"]
+        self._gemm(pl["xa"], lay["qkv"], M, out_act=qkv, col_scale=scale, col_scale_end=D)
+        for r0 in range(0, 2 * Tp, self.P_CHUNK):
+            self._gemm(pe, lay["pos"], self.P_CHUNK, a_ptr_offset=2 * r0 * pe.cols, out_f32=pl["P"][r0: r0 + self.P_CHUNK], ldo_f32=D)
+        t = self._cmd("relpos_bias")
+        t.qkv, t.ld, t.plane_stride, t.P, t.ldp, t.off = qkv.ptr, qkv.cols, qkv.plane_stride, pl["P"].data_ptr(), D, lay["off"].data_ptr()
+        t.frame_offs, t.pb, t.ld_pb = pl["frame_offs"].data_ptr(), pl["pb"].data_ptr(), pl["ld_pb"]
+        t.q_col, t.B, t.H, t.dh, t.P_T, t.max_frames, t.rows, t.mode = 0, pl["B"], H, geo.head_dim, Tp, pl["Tmax"], M, self.mode
+        self._issue(_lib.OP_RELPOS_BIAS, t, "ser_relpos_bias", B=pl["B"], max_frames=pl["Tmax"], rows=M)
+        r = self._cmd("attention_rb")
+        a = r.base
+        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
+        a.q_col, a.k_col, a.v_col, a.B = 0, D, 2 * D, pl["B"]
+        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
+        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
+        a.H, a.dh, a.scale, a.mode = H, geo.head_dim, -1.0, self.mode          # q is pre-scaled
+        r.pb, r.ld_pb = pl["pb"].data_ptr(), pl["ld_pb"]
+        if self._rec is not None:                                               # the per-batch sizes live in the embedded base struct
+            self._rec.patches += [(a, "B", "B"), (a, "max_frames", "Tmax")]
+        self._issue(_lib.OP_ATTENTION_RB, r, "ser_attention_rb")
+
+    def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
+        geo = self.geo
+        M, D, L = pl["M"], geo.hidden, geo.num_layers
+        states = pl["states"]
+        scale = geo.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
+        eps = 1e-5                                                  # the layer's own norms: nn.LayerNorm's default, whatever the config says
+        self._conv_stack(pl, packed_wave)
+        self._gemm(pl["feat_act"], self.proj, M, out_f32=states[0], ldo_f32=D, stem=True)
+        if self._state_done(0, last_state):
+            return
+        for i, lay in enumerate(self.layers):
+            last = i + 1 == L
+            self._ffn_half(pl, lay, "ffn1", states[i], pl["r1"], eps=eps)
+            if self.relative:
+                self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_act=pl["xa"], eps=eps)
+                self._relative_attention(pl, lay, scale)
+            else:
+                self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_f32=pl["ln"], out_act=pl["xa"], eps=eps)
+                self._rotary_attention(pl, lay, scale)
+            self._gemm(pl["ctx"], lay["out"], M, residual=pl["r1"], ldr=D, out_f32=pl["r2"], ldo_f32=D)
+            self._layernorm(pl["r2"], D, lay["conv_ln"], M, D, out_act=pl["xa"], eps=eps)
+            self._gemm(pl["xa"], lay["pw1"], M, out_f32=pl["pw"], ldo_f32=2 * D)
+            self._conv_mid(pl, lay)
+            self._gemm(pl["cv"], lay["pw2"], M, residual=pl["r2"], ldr=D, out_f32=pl["r3"], ldo_f32=D)
+            self._ffn_half(pl, lay, "ffn2", pl["r3"], pl["r4"], eps=eps)
+            self._layernorm(pl["r4"], D, lay["final_ln"], M, D, out_f32=pl["last"] if last else states[i + 1], eps=eps)
+            if last:
+                self._layernorm(pl["last"], D, self.enc_ln, M, D, out_f32=states[L])
+            if self._state_done(i + 1, last_state):
+                return
+
+    @_on_stream
+    def forward(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0,
+                last_state: Optional[int] = None) -> HiddenStates:
+        """packed raw samples [sum(lengths)] fp32 on the device -> L + 1 hidden states"""
+        pl = self._plan(lengths, slot)
+        return self._launch_or_replay(self._arenas[slot], pl, packed_wave, self._check_last_state(last_state))
+
+
 def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16", normalize: bool = True):
     """``normalize``: the speech families' input normalisation (``do_normalize`` of the checkpoint's feature extractor)."""
     if geo.family == "deberta":
@@ -3913,4 +4185,6 @@ def build_encoder(geo: EncoderGeometry, state_dict, device="cuda:0", mode="bf16"
         return WhisperEncoder(geo, state_dict, device, mode)
     if geo.family == FAMILY_W2V_BERT:
         return W2vBertEncoder(geo, state_dict, device, mode)
+    if geo.family == FAMILY_W2V_CONFORMER:
+        return ConformerSpeechEncoder(geo, state_dict, device, mode, normalize=normalize)
     return SpeechEncoder(geo, state_dict, device, mode, normalize=normalize)

@@ -21,7 +21,8 @@ from typing import Dict
 import numpy as np
 import torch
 
-from .config import EncoderGeometry, FAMILY_DEBERTA, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_WAVLM, FAMILY_WHISPER
+from .config import (EncoderGeometry, FAMILY_DEBERTA, FAMILY_ROBERTA, FAMILY_W2V_BERT, FAMILY_W2V_CONFORMER, FAMILY_WAVLM,
+                     FAMILY_WHISPER)
 
 StateDict = Dict[str, torch.Tensor]
 
@@ -188,6 +189,38 @@ def synthetic_state_dict(geo: EncoderGeometry, seed: int = 0, fast: bool = False
         _layer_norm(sd, r, "feature_projection.layer_norm", cin)
     _linear(sd, r, "feature_projection.projection", D, cin)
 
+    if geo.family == FAMILY_W2V_CONFORMER:
+        # HF Wav2Vec2ConformerModel names behind wav2vec2's stem and projection (above); no positional convolution (HF builds the module
+        # and never calls it).  A branch of its own: the other families' streams stay as they were.
+        K = geo.conv_depthwise_kernel
+        _layer_norm(sd, r, "encoder.layer_norm", D)
+        for i in range(geo.num_layers):
+            p = f"encoder.layers.{i}"
+            for f in ("ffn1", "ffn2"):
+                _layer_norm(sd, r, f"{p}.{f}_layer_norm", D)
+                _linear(sd, r, f"{p}.{f}.intermediate_dense", Fd, D)
+                _linear(sd, r, f"{p}.{f}.output_dense", D, Fd)
+            _layer_norm(sd, r, p + ".self_attn_layer_norm", D)
+            _linear(sd, r, p + ".self_attn.linear_q", D, D, gain=1.6)
+            _linear(sd, r, p + ".self_attn.linear_k", D, D, gain=1.6)
+            _linear(sd, r, p + ".self_attn.linear_v", D, D)
+            _linear(sd, r, p + ".self_attn.linear_out", D, D)
+            if geo.position_type == "relative":
+                # |P_h(r)| ~ 1.6 sqrt(dh / 2) like a key row, and u, v of the size of a query's entries: all four terms carry signal
+                _linear(sd, r, p + ".self_attn.linear_pos", D, D, gain=1.6, bias=False)
+                sd[p + ".self_attn.pos_bias_u"] = r.normal(H, dh, std=0.5)
+                sd[p + ".self_attn.pos_bias_v"] = r.normal(H, dh, std=0.5)
+            c = p + ".conv_module"
+            _layer_norm(sd, r, c + ".layer_norm", D)
+            sd[c + ".pointwise_conv1.weight"] = r.normal(2 * D, D, 1, std=1.0 / math.sqrt(D))
+            sd[c + ".depthwise_conv.weight"] = r.normal(D, 1, K, std=1.0 / math.sqrt(K))
+            _layer_norm(sd, r, c + ".batch_norm", D)
+            sd[c + ".batch_norm.running_mean"] = r.normal(D, std=0.3)
+            sd[c + ".batch_norm.running_var"] = torch.exp2(r.normal(D, std=1.0).clamp(-2.0, 2.0))      # in [0.25, 4]: the fold cannot amplify
+            sd[c + ".pointwise_conv2.weight"] = r.normal(D, D, 1, std=0.7 / math.sqrt(D))
+            _layer_norm(sd, r, p + ".final_layer_norm", D)
+        return sd
+
     cg = D // geo.pos_conv_groups
     if geo.pos_conv_norm == "layer":
         # data2vec-audio: pos_conv_layers plain grouped convs (HF Data2VecAudioPositionalConvLayer; no weight norm, LayerNorm without
@@ -275,7 +308,7 @@ def apply_stress(sd: StateDict, geo: EncoderGeometry, kind: str) -> StateDict:
     return sd
 
 
-_STRIP_PREFIXES = ("wavlm.", "wav2vec2_bert.", "wav2vec2.", "hubert.", "data2vec_audio.", "model.", "roberta.", "deberta.")
+_STRIP_PREFIXES = ("wavlm.", "wav2vec2_bert.", "wav2vec2_conformer.", "wav2vec2.", "hubert.", "data2vec_audio.", "model.", "roberta.", "deberta.")
 
 
 def normalize_names(sd: StateDict, keep: tuple = ()) -> StateDict:
@@ -467,6 +500,56 @@ def fold_w2v_bert_ffn(w: torch.Tensor, b: torch.Tensor):
     """The conformer layer adds HALF of each feed-forward block to the residual stream (HF Wav2Vec2BertEncoderLayer: ``x * 0.5 + residual``).
     The factor goes into the block's output Linear at load: 0.5 is a power of two, so every product and sum keeps its rounding."""
     return w.detach().to(torch.float32) * 0.5, b.detach().to(torch.float32) * 0.5
+
+
+def fold_batch_norm(gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, eps: float = 1e-5):
+    """``BatchNorm1d`` in eval is a per-channel affine: (scale, shift) with scale = gamma / sqrt(running_var + eps) and
+    shift = beta - running_mean scale, in float64, each rounded to fp32 once (ser_conformer_conv_bn_v's operands)."""
+    g, b, m, v = (t.detach().double() for t in (gamma, beta, mean, var))
+    scale = g / torch.sqrt(v + float(eps))
+    return scale.float(), (b - m * scale).float()
+
+
+def fold_pos_bias_u(bq: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """Transformer-XL's content bias into ``linear_q``'s bias: the projection emits q + u ([H, dh] flattened head-major, as the
+    projection's columns are)."""
+    return (bq.detach().double() + u.detach().double().reshape(-1)).float()
+
+
+def rotary_inv_freq(head_dim: int, base: float = 10000.0) -> torch.Tensor:
+    """HF's ``inv_freq`` buffer, by HF's own fp32 expression (Wav2Vec2ConformerRotaryPositionalEmbedding.__init__).  A checkpoint stores
+    the buffer (``encoder.embed_positions.inv_freq``); where it does, the encoder reads that instead."""
+    return 1.0 / (float(base) ** (torch.arange(0, head_dim, 2, dtype=torch.int64).float() / head_dim))
+
+
+def rotary_tables(frames: int, inv_freq: torch.Tensor):
+    """(cos, sin) fp32 [frames][dh] of HF's rotary embedding: cos / sin(t inv_freq) duplicated over the two halves, with the fp32
+    ``inv_freq`` [dh / 2]; the products t inv_freq and the functions in float64 (numpy), rounded to fp32 once.  Row t depends on t alone:
+    a longer table starts with the shorter one's bits."""
+    inv = inv_freq.detach().to(torch.float32).cpu().numpy().astype(np.float64)
+    ang = np.arange(int(frames), dtype=np.float64)[:, None] * inv[None, :]
+    ang = np.concatenate([ang, ang], axis=1)
+    return torch.from_numpy(np.cos(ang).astype(np.float32)), torch.from_numpy(np.sin(ang).astype(np.float32))
+
+
+def relpos_div_term(hidden: int) -> torch.Tensor:
+    """HF's fp32 ``div_term`` [D / 2], by HF's own expression (Wav2Vec2ConformerRelPositionalEmbedding.extend_pe)."""
+    return torch.exp(torch.arange(0, hidden, 2, dtype=torch.int64).float() * -(math.log(10000.0) / hidden))
+
+
+def relpos_pe(frames: int, hidden: int) -> torch.Tensor:
+    """The sinusoid rows of Transformer-XL's relative positions, fp32 [2 frames - 1][D]: row ``frames - 1 + r`` is pe(r) for the distance
+    r = i - j in -(frames - 1) .. frames - 1 (positive: the key is to the left), pe(r)[0::2] = sin(r div), pe(r)[1::2] = cos(r div).
+    HF's arithmetic, statement for statement (fp32 position times the fp32 ``div_term``, torch's fp32 sin / cos), so that the rows are the
+    bits of the buffer HF's module holds -- taken ONE ROW AT A TIME on a [D / 2] tensor: the row for r is then a function of r and D
+    alone, the same bits whatever ``frames`` is (a vectorised function may treat the tail of a longer tensor differently)."""
+    div = relpos_div_term(hidden)
+    pe = torch.empty((2 * int(frames) - 1, hidden), dtype=torch.float32)
+    for row, r in enumerate(range(-(int(frames) - 1), int(frames))):
+        arg = torch.tensor(float(r), dtype=torch.float32) * div
+        pe[row, 0::2] = torch.sin(arg)
+        pe[row, 1::2] = torch.cos(arg)
+    return pe
 
 
 F16_MAX = 65504.0

@@ -10,7 +10,7 @@ with the float64 hidden states (Whisper: their mean over the 1 500 rows and max|
 The head's seed is the first for which the fixture has the property the GPU test relies on: for at least two of the three waveforms HF's
 top-two margin exceeds twice the logit bound of the f16x and fp32x modes (eps 1e-3, tests/test_gpu_audio_cls.py; the bf16 bound, eps 3e-2, is wider than any margin here).
 
-    python tools/make_golden_audio_cls.py
+    python tools/make_golden_audio_cls.py [output directory [one fixture's tag]]
 """
 from __future__ import annotations
 
@@ -41,7 +41,10 @@ CASES = (
     ("tiny_cls_wavlm_base", C.TINY_WAVLM_BASE, 43, True, 64, 4, 400),
     ("tiny_cls_w2v_bert", C.TINY_W2V_BERT, 44, True, 32, 130, 560),
     ("tiny_cls_whisper", C.TINY_WHISPER, 45, True, 40, 1, 400),
+    ("tiny_cls_w2v_conformer", C.TINY_W2V_CONFORMER_ROPE, 46, True, 48, EMOTIONS, 400),
 )
+# the prefix the HF class puts in front of its encoder's parameter names (tests/audio_cls_ref.py's, and the conformer family's)
+WRAPPER = dict(R.WRAPPER, **{C.FAMILY_W2V_CONFORMER: "wav2vec2_conformer."})
 
 
 def hf_model(geo, weighted: bool, proj: int, labels):
@@ -63,6 +66,15 @@ def hf_model(geo, weighted: bool, proj: int, labels):
             left_max_position_embeddings=geo.left_max_positions, right_max_position_embeddings=geo.right_max_positions,
             layer_norm_eps=geo.layer_norm_eps, apply_spec_augment=False, **head)
         return tf.Wav2Vec2BertForSequenceClassification(cfg).eval()
+    if geo.family == C.FAMILY_W2V_CONFORMER:
+        cfg = tf.Wav2Vec2ConformerConfig(
+            hidden_size=geo.hidden, num_hidden_layers=geo.num_layers, num_attention_heads=geo.heads, intermediate_size=geo.ffn,
+            conv_dim=list(geo.conv_dim), conv_kernel=list(geo.conv_kernel), conv_stride=list(geo.conv_stride), conv_bias=geo.conv_bias,
+            feat_extract_norm="layer", feat_extract_activation="gelu", hidden_act="swish", position_embeddings_type=geo.position_type,
+            rotary_embedding_base=geo.rotary_base, max_source_positions=geo.max_source_positions,
+            conv_depthwise_kernel_size=geo.conv_depthwise_kernel, layer_norm_eps=geo.layer_norm_eps, apply_spec_augment=False,
+            vocab_size=32, **head)
+        return tf.Wav2Vec2ConformerForSequenceClassification(cfg).eval()
     common = dict(hidden_size=geo.hidden, num_hidden_layers=geo.num_layers, num_attention_heads=geo.heads,
                   intermediate_size=geo.ffn, conv_dim=list(geo.conv_dim), conv_kernel=list(geo.conv_kernel),
                   conv_stride=list(geo.conv_stride), conv_bias=geo.conv_bias, feat_extract_norm=geo.feat_extract_norm,
@@ -99,6 +111,13 @@ def draw_head(D: int, L1: int, proj: int, n: int, weighted: bool, seed: int) -> 
     return head
 
 
+def forget_cached_positions(model) -> None:
+    """HF's rotary module keeps its cos / sin by sequence length alone: a table made in fp32 would serve the float64 run"""
+    for m in model.modules():
+        if hasattr(m, "cached_sequence_length"):
+            m.cached_sequence_length = None
+
+
 def make_case(tag, geo, seed, weighted, proj, labels, shortest):
     torch.manual_seed(0)
     model = hf_model(geo, weighted, proj, labels)
@@ -111,10 +130,13 @@ def make_case(tag, geo, seed, weighted, proj, labels, shortest):
     cfg["architectures"] = [type(model).__name__]
     for head_seed in range(seed * 100, seed * 100 + 50):
         head = draw_head(geo.hidden, geo.num_layers + 1, proj, n, weighted, head_seed)
-        sd = {R.WRAPPER[geo.family] + k: v for k, v in enc.items()}
+        sd = {WRAPPER[geo.family] + k: v for k, v in enc.items()}
         sd.update({k: torch.from_numpy(v) for k, v in head.items()})
         res = model.float().load_state_dict(sd, strict=False)
-        extra = [k for k in res.missing_keys if "masked_spec_embed" not in k]
+        # off the encoder's path: the mask embedding; for the conformer family the positional convolution HF builds and never calls,
+        # BatchNorm's step counter and the rotary buffer HF computes at construction
+        extra = [k for k in res.missing_keys if "masked_spec_embed" not in k and not (
+            geo.family == C.FAMILY_W2V_CONFORMER and ("pos_conv_embed." in k or k.endswith(("num_batches_tracked", "inv_freq"))))]
         assert not res.unexpected_keys and not extra, res
         rec = {"config": np.array(json.dumps(cfg, sort_keys=True)), "preprocessor": np.array(json.dumps(pre, sort_keys=True)),
                "seed": np.array(seed), "head_seed": np.array(head_seed), "digest": np.array(state_dict_digest(enc)),
@@ -131,8 +153,10 @@ def make_case(tag, geo, seed, weighted, proj, labels, shortest):
             with torch.no_grad():
                 out32 = model.float()(**inputs, output_hidden_states=True)
                 in64 = {k: (v.double() if v.is_floating_point() else v) for k, v in inputs.items()}
+                forget_cached_positions(model)
                 out64 = model.double()(**in64, output_hidden_states=True)
             model.float()
+            forget_cached_positions(model)
             hs = torch.stack([h[0] for h in out64.hidden_states])
             if mask is not None:
                 hs = hs[:, mask]
@@ -158,9 +182,11 @@ def make_case(tag, geo, seed, weighted, proj, labels, shortest):
     raise AssertionError(f"{tag}: no head seed gives two wide margins")
 
 
-def main(out_dir: str = OUT) -> None:
+def main(out_dir: str = OUT, only: str = "") -> None:
     torch.set_num_threads(1)           # one summation order for the CPU convolutions: regenerating gives the same arrays
     for case in CASES:
+        if only and case[0] != only:
+            continue
         rec = make_case(*case)
         path = os.path.join(out_dir, case[0] + ".npz")
         np.savez_compressed(path, **rec)
@@ -169,4 +195,4 @@ def main(out_dir: str = OUT) -> None:
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else OUT)
+    main(sys.argv[1] if len(sys.argv) > 1 else OUT, sys.argv[2] if len(sys.argv) > 2 else "")
