@@ -1396,6 +1396,35 @@ typedef struct ser_attention_rb_args {
 } ser_attention_rb_args;
 int ser_attention_rb_v(const ser_attention_rb_args* args, void* stream);
 
+/* a36 (added under ABI 18: one new entry point, one ser_cmd member and one SER_OP code only; ser_dec_select_v and every struct above are
+ * what they were)  Whisper segment timestamps: the model's own <|0.00|> text <|6.44|> tokens, HF's generate(return_timestamps=True).
+ *
+ * ser_dec_select_ts_v (SER_OP_DEC_SELECT_TS): ser_dec_select_v with HF's WhisperTimeStampLogitsProcessor between the static mask and
+ * the argmax -- HF's order is begin-suppress, suppress, then the timestamp processor.  One block per row; finished and forced rows, ids,
+ * margin, finished, the tickets in `work`, *unfinished, *pos and the error bits are ser_dec_select_v's.  With p = *pos and
+ * n = p + 1 - begin_index generated tokens (n < 0, a prompt step such as the language step: ser_dec_select_v's choice, no rule), per row b:
+ *   1. x[v] = logits[b, v] + mask[phase[p], v];  x[no_ts] = -inf
+ *   2. last = ids[b, p] (n >= 1), pen = ids[b, p - 1] (n >= 2);  last_ts = n >= 1 and last >= ts_begin;  pen_ts = n < 2 or pen >= ts_begin
+ *      last_ts and pen_ts      -> x[ts_begin:] = -inf         (a closed pair: text follows)
+ *      last_ts and not pen_ts  -> x[:eos] = -inf              (text, then a timestamp: its pair or eos follows)
+ *   3. t = the LAST id >= ts_begin among ids[b, begin_index .. p] (not the largest: a teacher-forced row need not be monotone); if there is
+ *      one, x[ts_begin:bound] = -inf with bound = t when last_ts and not pen_ts, else t + 1
+ *   4. n == 0 -> x[:ts_begin] = -inf, and with max_initial >= 0 also x[ts_begin + max_initial + 1:] = -inf
+ *   5. L = log sum_{v >= ts_begin} exp(x[v]) in float64, M = max_{v < ts_begin} x[v];  L > M -> x[:ts_begin] = -inf  (L == M keeps the text).
+ *      HF compares the two log-softmax values; their difference is L - M, so the normaliser is not computed.
+ *      ts_gap[b, p] = |L - M|, +inf when either side is not finite or nothing was decided
+ *   6. token = argmax x, the lowest index on a tie; margin[b, p] = top-1 minus top-2 of the final x
+ * The float64 sum runs over a fixed tree of (thread, wave) slots, a function of V and ts_begin alone; a row's result does not depend on
+ * what shares its batch, bit for bit.  Columns >= V are never read.  *err bit 0: the winner is not finite (an all-masked row), or the row
+ * holds a NaN in a column < V, live or masked (a NaN counts as +inf where it is live); bit 2 as ser_dec_select_v's.
+ * 0 < ts_begin < V, 0 <= no_ts, eos < V, 1 <= begin_index < max_pos, max_initial >= -1 (-1: none); ts_gap float64 [B, ld_gap >= max_pos - 1]. */
+typedef struct ser_dec_select_ts_args {
+    ser_dec_select_args base;
+    double* ts_gap; int64_t ld_gap;
+    int32_t ts_begin, no_ts, begin_index, max_initial;
+} ser_dec_select_ts_args;
+int ser_dec_select_ts_v(const ser_dec_select_ts_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -1426,6 +1455,7 @@ int ser_attention_rb_v(const ser_attention_rb_args* args, void* stream);
 #define SER_OP_CONFORMER_CONV_BN 28
 #define SER_OP_RELPOS_BIAS 29
 #define SER_OP_ATTENTION_RB 30
+#define SER_OP_DEC_SELECT_TS 31
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -1459,6 +1489,7 @@ typedef struct ser_cmd {
         ser_conformer_conv_bn_args conformer_conv_bn;
         ser_relpos_bias_args relpos_bias;
         ser_attention_rb_args attention_rb;
+        ser_dec_select_ts_args dec_select_ts;
     } u;
 } ser_cmd;
 

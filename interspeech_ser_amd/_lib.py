@@ -396,6 +396,12 @@ class BeamSelectArgs(C.Structure):
     ]
 
 
+class DecSelectTsArgs(C.Structure):
+    """Mirror of ``ser_dec_select_ts_args``."""
+    _fields_ = [("base", DecSelectArgs), ("ts_gap", c_void_p), ("ld_gap", c_i64),
+                ("ts_begin", C.c_int32), ("no_ts", C.c_int32), ("begin_index", C.c_int32), ("max_initial", C.c_int32)]
+
+
 class ProsodyMelArgs(C.Structure):
     """Mirror of ``ser_prosody_mel_args``."""
     _fields_ = [
@@ -570,7 +576,7 @@ class _CmdUnion(C.Union):
                 ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs), ("dec_keep_q", DecKeepQArgs),
                 ("dec_attn_beam", DecAttnBeamArgs), ("beam_select", BeamSelectArgs),
                 ("rope_rows", RopeRowsArgs), ("conformer_conv_bn", ConformerConvBnArgs), ("relpos_bias", RelposBiasArgs),
-                ("attention_rb", AttentionRbArgs)]
+                ("attention_rb", AttentionRbArgs), ("dec_select_ts", DecSelectTsArgs)]
 
 
 class Cmd(C.Structure):
@@ -586,6 +592,7 @@ OP_FBANK, OP_RELKEY_TABLE, OP_ATTENTION_RK, OP_CONFORMER_CONV, OP_SWISH_ROWS = 1
 OP_DEC_KEEP_Q = 24
 OP_DEC_ATTN_BEAM, OP_BEAM_SELECT = 25, 26
 OP_ROPE_ROWS, OP_CONFORMER_CONV_BN, OP_RELPOS_BIAS, OP_ATTENTION_RB = 27, 28, 29, 30
+OP_DEC_SELECT_TS = 31
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -602,6 +609,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_dtw_args": DtwArgs, "ser_dec_attn_beam_args": DecAttnBeamArgs, "ser_beam_select_args": BeamSelectArgs,
                   "ser_rope_rows_args": RopeRowsArgs, "ser_conformer_conv_bn_args": ConformerConvBnArgs,
                   "ser_relpos_bias_args": RelposBiasArgs, "ser_attention_rb_args": AttentionRbArgs,
+                  "ser_dec_select_ts_args": DecSelectTsArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -666,6 +674,7 @@ _SIGNATURES = {
     "ser_conformer_conv_bn_v": (c_int, [c_void_p, c_void_p]),
     "ser_relpos_bias_v": (c_int, [c_void_p, c_void_p]),
     "ser_attention_rb_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dec_select_ts_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

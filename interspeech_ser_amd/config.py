@@ -612,10 +612,21 @@ class GenerationSpec:
     median_filter_width: int = 7       # config.json's (not generation_config.json's): the transcriber fills it in
     num_beams: int = 1                 # 1: greedy; 2..8: HF's beam search with early_stopping = False (engine.WhisperDecoder.generate)
     length_penalty: float = 1.0        # the exponent of the generated length a finished beam's score is divided by
+    max_initial_timestamp_index: Optional[int] = None   # None when absent, as HF's WhisperTimeStampLogitsProcessor reads it
 
     PROMPT_LEN = 4
     MAX_BEAMS = 8
     TIME_PRECISION = 0.02              # seconds per encoder frame
+
+    def prompt_len(self, timestamps: bool = False) -> int:
+        """The prompt length of a run: ``PROMPT_LEN`` with ``<|notimestamps|>``, one less for a segment-timestamps run, whose prompt is
+        ``[start, language, task]``."""
+        return self.PROMPT_LEN - 1 if timestamps else self.PROMPT_LEN
+
+    @property
+    def timestamp_begin(self) -> int:
+        """The id of ``<|0.00|>``: every id from here on is a timestamp token (HF: ``no_timestamps_token_id + 1``)."""
+        return self.no_timestamps_token_id + 1
 
     def require_alignment_heads(self) -> Tuple[Tuple[int, int], ...]:
         """The alignment heads, or the error that names what is missing: token times were asked of a checkpoint that has none."""
@@ -652,12 +663,15 @@ class GenerationSpec:
         beams = 1 if beams is None else beams
         if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= GenerationSpec.MAX_BEAMS:
             raise OSError(f"generation_config.json: num_beams={beams!r} (1..{GenerationSpec.MAX_BEAMS})")
+        initial = cfg.get("max_initial_timestamp_index")
+        if initial is not None and (isinstance(initial, bool) or not isinstance(initial, int) or initial < 0):
+            raise OSError(f"generation_config.json: max_initial_timestamp_index={initial!r} (a non-negative integer, or absent)")
         penalty = cfg.get("length_penalty")
         penalty = 1.0 if penalty is None else penalty
         if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or penalty != penalty or abs(penalty) == float("inf"):
             raise OSError(f"generation_config.json: length_penalty={penalty!r} (a finite number)")
         return GenerationSpec(
-            num_beams=beams, length_penalty=float(penalty),
+            num_beams=beams, length_penalty=float(penalty), max_initial_timestamp_index=initial,
             decoder_start_token_id=int(cfg["decoder_start_token_id"]), eos_token_id=eos, pad_token_id=eos if pad is None else int(pad),
             suppress_tokens=tuple(int(t) for t in cfg.get("suppress_tokens") or ()),
             begin_suppress_tokens=tuple(int(t) for t in cfg.get("begin_suppress_tokens") or ()),

@@ -155,6 +155,10 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_attention_rb_v(&c.u.attention_rb, stream);
                 break;
             }
+            case SER_OP_DEC_SELECT_TS: {
+                rc = ser_dec_select_ts_v(&c.u.dec_select_ts, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

@@ -2675,10 +2675,16 @@ class DecodeResult:
     first beam step, ``run`` int32 [n, B, K, 2] and ``cand`` int32 [n, B, 2K, 2] = (parent, token) of the running rows and of the candidates
     of every position, ``cand_scores`` float64 [n, B, 2K], ``fin_scores`` / ``fin_handles`` / ``n_fin`` / ``flags`` / ``done_step``: the
     finished sets and flags as the device left them, ``run_scores`` float64 [B, K]) and ``beam_gaps`` float64 [n, B] (per position the
-    smallest gap of a comparison that decided the step, +inf where none did).  ``margins`` then covers the prompt positions only."""
+    smallest gap of a comparison that decided the step, +inf where none did).  ``margins`` then covers the prompt positions only.
+    After a segment-timestamps run (``generate(..., timestamps=True)``) ``sequences`` / ``lists`` hold the timestamp tokens too (prompt
+    ``[start, language, task]``), and also: ``segments`` (per utterance a list of ``(start_s, end_s, ids)``, ``transcribe.segments_of`` of
+    its list), ``next_seek`` (int64 [B]: the frames HF's seek would advance by), ``ts_gaps`` float64 [B, n - 1] (ser_dec_select_ts_v's
+    |L - M| of position p's decision, +inf where the sum rule compared nothing) and, with ``keep_logits``, ``step_logits`` (fp32
+    [steps, B, V] on the device: the logits of every step from the first generated position on)."""
 
     token_times = token_frames = ts_status = ts_matrix = None
     nbest = beam_scores = beam_trace = beam_gaps = beam_logits = None
+    segments = next_seek = ts_gaps = step_logits = None
 
     def __init__(self, sequences, languages, lists, margins, range_bits, err):
         self.sequences, self.languages, self.lists, self.margins = sequences, languages, lists, margins
@@ -2752,12 +2758,15 @@ class WhisperDecoder(_LaunchHost):
         return (self._dev_f32(sd[prefix + ".weight"]), self._dev_f32(sd[prefix + ".bias"]))
 
     # ------------------------------------------------------------------ buffers
-    def _plan(self, B: int, slot: int, heads=None, beams: int = 1):
+    def _plan(self, B: int, slot: int, heads=None, beams: int = 1, timestamps: bool = False):
         """``heads``: the alignment heads of the capture variant of the step (``generate(token_times=True)``), part of the plan's key; the
-        default plan (None) records exactly the launches it always did.  ``beams`` K >= 2: the beam plan, keyed (slot, B, "beam", K)."""
+        default plan (None) records exactly the launches it always did.  ``beams`` K >= 2: the beam plan, keyed (slot, B, "beam", K).
+        ``timestamps``: the segment-timestamps plan, keyed (slot, B, "ts"), whose step ends in ser_dec_select_ts_v."""
         if beams > 1:
             return self._beam_plan(B, slot, beams)
         key = (slot, B) if heads is None else (slot, B, tuple(heads))
+        if timestamps:
+            key = (slot, B, "ts")
         pl = self._plans.get(key)
         if pl is not None:
             return pl
@@ -2777,6 +2786,9 @@ class WhisperDecoder(_LaunchHost):
         pl["cross"] = cr[: L * B * S * 2 * D].view(L, B * S, 2 * D)
         pl["host"] = torch.empty(3, dtype=torch.int32).pin_memory()
         pl["heads"] = None
+        if timestamps:
+            pl["timestamps"] = True
+            pl["ts_gap"] = torch.empty((B, T), dtype=torch.float64, device=dev)
         if heads is not None:
             heads = tuple((int(l), int(h)) for l, h in heads)
             if not 1 <= len(heads) <= _lib.TS_MAX_HEADS or any(not (0 <= l < L and 0 <= h < geo.decoder_attention_heads) for l, h in heads):
@@ -2946,7 +2958,8 @@ class WhisperDecoder(_LaunchHost):
         self._layernorm(x0, D, self.final_ln, B, D, out_act=pl["xa"])
         self._gemm(pl["xa"], self.proj, B, out_f32=pl["logits"], ldo_f32=self.Vp)
         pl["n_logits"] = self._rec.n if self._rec is not None else None
-        s = self._cmd("dec_select")
+        x = self._cmd("dec_select_ts") if pl.get("timestamps") else None
+        s = self._cmd("dec_select") if x is None else x.base
         s.logits, s.ldl = pl["logits"].data_ptr(), self.Vp
         s.mask, s.ldm = 0, geo.decoder_vocab_size                      # the spec's masks: set per generate() call (_bind_spec)
         s.phase, s.forced = pl["phase"].data_ptr(), pl["forced"].data_ptr()
@@ -2955,6 +2968,13 @@ class WhisperDecoder(_LaunchHost):
         s.pos, s.unfinished, s.work, s.err = pl["pos"].data_ptr(), pl["unfinished"].data_ptr(), pl["work"].data_ptr(), pl["err"].data_ptr()
         s.B, s.V, s.eos, s.pad, s.max_pos = B, geo.decoder_vocab_size, 0, 0, T
         pl["select"] = s
+        if x is not None:
+            # the spec's token layout (begin): placeholders that pass the launcher's checks while the step is recorded
+            x.ts_gap, x.ld_gap = pl["ts_gap"].data_ptr(), T
+            x.ts_begin, x.no_ts, x.begin_index, x.max_initial = 1, 0, 1, -1
+            pl["select_ts"] = x
+            self._issue(_lib.OP_DEC_SELECT_TS, x, "ser_dec_select_ts")
+            return
         self._issue(_lib.OP_DEC_SELECT, s, "ser_dec_select")
         if pl.get("K"):
             # the second tail of a beam plan: from the first generated position the step ends with ser_beam_select_v instead
@@ -3034,18 +3054,22 @@ class WhisperDecoder(_LaunchHost):
             check(rc, f"ser_run (decoder step, command {tape._failed.value})")
 
     def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None, token_times: bool = False, num_beams: int = 1,
-              length_penalty: float = 1.0):
+              length_penalty: float = 1.0, timestamps: bool = False):
         """Reset the slot's decoding state for a batch of B: ids[:, 0] = start, position 0, nothing finished.  ``forced_ids`` (tests:
         teacher forcing): a whole id row to follow instead of the spec's prompt.  ``token_times``: the capture variant of the step.
         ``num_beams`` K >= 2: the beam plan (B K rows) with its state reset: running scores [0, -inf, ..], empty finished sets, flags up,
-        the identity ancestor table."""
+        the identity ancestor table.  ``timestamps``: the segment-timestamps plan and its prompt ``[start, language, task]``; with
+        ``forced_ids`` the rule still counts its generated tokens from position 3."""
         spec = spec or self.spec
         if spec is None:
             raise ValueError("WhisperDecoder needs a GenerationSpec")
+        if timestamps and (token_times or num_beams > 1):
+            raise ValueError("timestamps=True does not go with " + ("token_times" if token_times else "num_beams > 1") + ": not built")
         geo = self.geo
         T = geo.max_target_positions
         n_max = min(int(spec.max_length), T)
-        pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None, beams=num_beams)
+        P = spec.prompt_len(timestamps)
+        pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None, beams=num_beams, timestamps=timestamps)
         language = spec.language if language is None else language
         forced = np.full(T, -1, dtype=np.int32)
         phase = np.zeros(T, dtype=np.int32)
@@ -3054,11 +3078,13 @@ class WhisperDecoder(_LaunchHost):
             start = int(forced_ids[0])
         else:
             start = spec.decoder_start_token_id
-            forced[1], forced[2] = spec.task_id, spec.no_timestamps_token_id
+            forced[1] = spec.task_id
+            if not timestamps:
+                forced[2] = spec.no_timestamps_token_id
             if language is not None:
                 forced[0] = int(language)
-            phase[0], phase[spec.PROMPT_LEN - 1] = self.PHASE_LANG, self.PHASE_FIRST
-        pl["forced_host"], pl["n_max"], pl["spec"] = forced, n_max, spec
+            phase[0], phase[P - 1] = self.PHASE_LANG, self.PHASE_FIRST
+        pl["forced_host"], pl["n_max"], pl["spec"], pl["P"] = forced, n_max, spec, P
         pl["forced"].copy_(torch.from_numpy(forced))
         pl["phase"].copy_(torch.from_numpy(phase))
         for k in ("finished", "pos", "unfinished", "work", "err") + (("range_flag",) if pl["range_flag"] is not None else ()):
@@ -3069,6 +3095,16 @@ class WhisperDecoder(_LaunchHost):
         s = pl["select"]
         s.mask, s.eos, s.pad = self._spec_masks(spec).data_ptr(), spec.eos_token_id, spec.pad_token_id
         self._flag = None if pl["range_flag"] is None else pl["range_flag"].data_ptr()
+        if timestamps:
+            V = geo.decoder_vocab_size
+            initial = spec.max_initial_timestamp_index
+            if not 0 < spec.timestamp_begin < V or not 0 <= spec.eos_token_id < V:
+                raise ValueError(f"segment timestamps need timestamp tokens behind no_timestamps_token_id={spec.no_timestamps_token_id} "
+                                 f"and eos inside the vocabulary of {V}")
+            x = pl["select_ts"]
+            x.ts_begin, x.no_ts, x.begin_index = spec.timestamp_begin, spec.no_timestamps_token_id, P
+            x.max_initial = -1 if initial is None else int(initial)
+            pl["ts_gap"].fill_(float("inf"))
         if pl.get("K"):
             from .beam import lenpow_table
             if n_max <= spec.PROMPT_LEN:
@@ -3093,17 +3129,27 @@ class WhisperDecoder(_LaunchHost):
     @_on_stream
     def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0, token_times: bool = False,
                  lengths: Optional[Sequence[int]] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
-                 keep_logits: bool = False) -> DecodeResult:
+                 keep_logits: bool = False, timestamps: bool = False) -> DecodeResult:
         """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``).
         ``token_times``: also HF's ``token_timestamps`` of every utterance given alone (``DecodeResult.token_times``), from the alignment
         heads' cross-attention; needs ``lengths``, the utterances' sample counts (HF's ``num_frames`` = length // 160).
         ``num_beams`` / ``length_penalty``: None takes the spec's; 1 is the greedy path and its plan, untouched; K >= 2 is HF's beam search
         (early_stopping = False) on the device.  ``keep_logits`` (tests): a beam run keeps the fp32 logits of every beam step in
-        ``DecodeResult.beam_logits`` [n, B K, V] on the device."""
+        ``DecodeResult.beam_logits`` [n, B K, V] on the device.
+        ``timestamps``: the model's own segment times (HF's ``return_timestamps=True`` for one 30 s window): the prompt is
+        ``[start, language, task]``, the step ends in ser_dec_select_ts_v on a plan of its own, and the result has ``segments``,
+        ``next_seek`` and ``ts_gaps``; ``lengths`` (sample counts) bound the window, absent: the whole 30 s.  ``keep_logits`` then
+        keeps ``DecodeResult.step_logits``.  Does not go with ``token_times`` or ``num_beams > 1``."""
         sp = spec or self.spec
         K = int(getattr(sp, "num_beams", 1) if num_beams is None else num_beams)
         if not 1 <= K <= _lib.BEAM_MAX_K:
             raise ValueError(f"num_beams={K} (1..{_lib.BEAM_MAX_K})")
+        if timestamps and token_times:
+            raise ValueError("timestamps=True with token_times: segment timestamps with token times are not built")
+        if timestamps and K > 1:
+            raise ValueError("timestamps=True with num_beams > 1: segment timestamps with beam search are not built")
+        if timestamps and lengths is not None and len(lengths) != B:
+            raise ValueError("lengths: one sample count per utterance")
         if K > 1:
             if token_times:
                 raise ValueError("token times with beam search are not built: run with num_beams=1")
@@ -3111,16 +3157,20 @@ class WhisperDecoder(_LaunchHost):
             return self._generate_beams(enc_last, B, spec, language, slot, K, lp, keep_logits)
         if token_times and (lengths is None or len(lengths) != B):
             raise ValueError("token times need the sample count of every utterance (lengths)")
-        pl = self.begin(B, spec, language, slot, token_times=token_times)
+        pl = self.begin(B, spec, language, slot, token_times=token_times, timestamps=timestamps)
         spec = pl["spec"]
         self.project_cross(pl, enc_last)
-        n_max, forced = pl["n_max"], pl["forced_host"]
+        n_max, forced, P = pl["n_max"], pl["forced_host"], pl["P"]
         host = pl["host"]
+        kept = [] if keep_logits and timestamps else None
+        V = self.geo.decoder_vocab_size
         steps = 0
         for pos in range(n_max - 1):
             self._run_step(pl, with_logits=forced[pos] < 0)
             steps += 1
-            if steps % self.CHECK_EVERY == 0 and pos >= spec.PROMPT_LEN - 1:
+            if kept is not None and pos >= P - 1:
+                kept.append(pl["logits"][:, :V].clone())
+            if steps % self.CHECK_EVERY == 0 and pos >= P - 1:
                 host[0:1].copy_(pl["unfinished"], non_blocking=True)
                 torch.cuda.current_stream().synchronize()
                 if int(host[0]) == 0:
@@ -3128,6 +3178,16 @@ class WhisperDecoder(_LaunchHost):
         res = self.result(pl, steps)
         if token_times:
             self._token_times(pl, res, lengths)
+        if timestamps:
+            from .transcribe import segments_of, window_frames
+            res.ts_gaps = pl["ts_gap"][:, : res.sequences.shape[1] - 1].cpu().numpy()
+            res.segments, res.next_seek = [], np.zeros(B, dtype=np.int64)
+            for b, ids in enumerate(res.lists):
+                segs, adv = segments_of(ids, spec.timestamp_begin, window_frames(None if lengths is None else lengths[b]))
+                res.segments.append(segs)
+                res.next_seek[b] = adv
+            if kept is not None:
+                res.step_logits = torch.stack(kept) if kept else None
         return res
 
     def _generate_beams(self, enc_last, B: int, spec, language, slot: int, K: int, length_penalty: float, keep_logits: bool) -> DecodeResult:
@@ -3291,7 +3351,7 @@ class WhisperDecoder(_LaunchHost):
         if pl["range_flag"] is not None:
             bits = int(pl["range_flag"].item())
             pl["range_flag"].zero_()
-        P = spec.PROMPT_LEN
+        P = pl.get("P", spec.PROMPT_LEN)
         lists, ends = [], []
         for row in ids:
             gen = row[P:].tolist()

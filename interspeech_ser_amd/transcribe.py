@@ -8,6 +8,10 @@ The reference makes its transcript table with ``AutoModelForSpeechSeq2Seq.genera
 ``transcribe(..., token_times=True)`` also keeps HF's ``token_timestamps`` of every file given alone (``.token_times``), read from the
 alignment heads' cross-attention by the decoder itself (engine.WhisperDecoder.generate); ``token_words`` groups tokens into words as HF's
 ``_combine_tokens_into_words`` does, and ``--times_json`` writes both.
+
+``transcribe(..., timestamps=True)`` runs the model's own segment times instead (HF's ``return_timestamps=True``, one 30 s window):
+``.segments`` and ``.next_seek`` per file, ``segments_of`` being HF's ``_retrieve_segment``; ``--segments_json`` writes them.  The seek
+loop over a longer file is not built: ``next_seek`` says where its next window would begin.
 """
 from __future__ import annotations
 
@@ -25,6 +29,48 @@ from .batchloop import make_batches, run_or_each
 
 N_SAMPLES = 480000            # 30 s: WhisperFeatureExtractor cuts longer input, and so does this path
 BATCH = 16
+N_FRAMES = 3000               # mel frames of a window
+HOP = 160                     # samples per mel frame
+TIME_PRECISION = C.GenerationSpec.TIME_PRECISION  # seconds per timestamp token step (HF: time_precision)
+TIME_PRECISION_FEATURES = 0.01  # seconds per mel frame
+INPUT_STRIDE = 2              # mel frames per timestamp step
+
+
+def window_frames(n_samples: Optional[int]) -> int:
+    """HF's ``seek_num_frames`` of a first window when the feature extractor's attention mask is passed: min(3000, len // 160); None:
+    the whole window."""
+    return N_FRAMES if n_samples is None else min(N_FRAMES, int(n_samples) // HOP)
+
+
+def segments_of(tokens: Sequence[int], ts_begin: int, num_frames: int, time_offset: float = 0.0):
+    """HF's ``WhisperGenerationMixin._retrieve_segment`` for one window's generated tokens (prompt and eos removed): ``(segments,
+    segment_offset)`` with segments ``[(start_s, end_s, ids)]`` and the offset in mel frames.  The tokens are sliced behind every pair of
+    consecutive timestamp tokens; a sequence that ends [text, timestamp] closes its last segment there and the whole window is consumed;
+    otherwise what follows the last pair is dropped and the seek advances to that pair's time.  Without a pair the whole sequence is one
+    segment from the offset to its last timestamp (if it has one other than <|0.00|>), else to the window's end."""
+    tok = [int(t) for t in tokens]
+    n = len(tok)
+    is_ts = [t >= ts_begin for t in tok]
+    single_ending = is_ts[-2:] == [False, True]
+    slices = [i + 1 for i in range(n - 1) if is_ts[i] and is_ts[i + 1]]
+    off = float(time_offset)
+    if slices:
+        if single_ending:
+            slices.append(n)
+        else:
+            slices[-1] += 1                                 # the closing pair stays in the last segment: it was no single ending
+        segments, last = [], 0
+        for i, cur in enumerate(slices):
+            part = tok[last:cur]
+            end_at = -1 if i < len(slices) - 1 or single_ending else -2
+            segments.append((off + float(part[0] - ts_begin) * TIME_PRECISION, off + float(part[end_at] - ts_begin) * TIME_PRECISION, part))
+            last = cur
+        return segments, int(num_frames) if single_ending else (tok[last - 2] - ts_begin) * INPUT_STRIDE
+    stamps = [t for t in tok if t >= ts_begin]
+    last_pos = float(int(num_frames * TIME_PRECISION_FEATURES / TIME_PRECISION))
+    if stamps and stamps[-1] != ts_begin:
+        last_pos = float(stamps[-1] - ts_begin)
+    return [(off, off + last_pos * TIME_PRECISION, tok)], int(num_frames)
 
 
 class WhisperTranscriber:
@@ -37,10 +83,12 @@ class WhisperTranscriber:
         self.enc, self.dec, self.spec = encoder, decoder, spec
         self.last_languages: List[Optional[int]] = []
         self.token_times: List[Optional[List[float]]] = []      # per item of the last transcribe(token_times=True)
+        self.segments: List[Optional[list]] = []                # per item of the last transcribe(timestamps=True): [(start_s, end_s, ids)]
+        self.next_seek: List[Optional[int]] = []                # ... and the mel frames the next window would begin at
         self.failed: List[str] = []                             # names of the files the last transcribe() left out
 
     def _batch(self, waves: Sequence[np.ndarray], slot: int, token_times: bool = False, num_beams: Optional[int] = None,
-               length_penalty: Optional[float] = None):
+               length_penalty: Optional[float] = None, timestamps: bool = False):
         """(DecodeResult, failed) of one batch; one encoder forward serves the decoder (its LAST state: the forward does not stop early)."""
         lengths = [len(w) for w in waves]
         hs = self.enc.forward(self.enc.upload(waves, slot), lengths, slot=slot)
@@ -49,19 +97,28 @@ class WhisperTranscriber:
             extra["num_beams"] = int(num_beams)
         if length_penalty is not None:
             extra["length_penalty"] = float(length_penalty)
+        if timestamps:
+            extra.update(timestamps=True, lengths=lengths)
         res = self.dec.generate(hs.states[-1], len(waves), self.spec, slot=slot, **extra)
         bits = hs.take_range_bits()
         return res, res.failed or bool(bits & 1), hs
 
     def transcribe(self, waves: Sequence[np.ndarray], names: Optional[Sequence[str]] = None, first_batch: int = 0,
-                   token_times: bool = False, num_beams: Optional[int] = None, length_penalty: Optional[float] = None
-                   ) -> List[Optional[List[int]]]:
+                   token_times: bool = False, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
+                   timestamps: bool = False) -> List[Optional[List[int]]]:
         """``first_batch``: the index of the first batch in the caller's own sequence of calls (a driver that hands over 16 files at a time
         keeps the slots alternating with it).  ``token_times``: ``self.token_times[i]`` becomes the seconds of item i's generated non-eos
         tokens.  A file whose times have a status word set (no frame, a matrix entry that is not finite) fails ALONE: it is printed,
         named in ``self.failed`` and has no times (its ids stay: the transcript table does not depend on the flag), and its batch mates are
         neither touched nor run again.  ``num_beams`` / ``length_penalty``: None takes the spec's; K >= 2 returns the best beam's ids
-        (``self.last_scores[i]``: its score) and does not go with ``token_times``."""
+        (``self.last_scores[i]``: its score) and does not go with ``token_times``.  ``timestamps``: the model's own segment times of
+        each file's first 30 s window: ``self.segments[i]`` = ``[(start_s, end_s, ids)]``, ``self.next_seek[i]`` = the mel frames the
+        seek would advance by, and the returned ids are the generated ones with the timestamp tokens removed.  Does not go with
+        ``token_times`` or beams."""
+        if timestamps and token_times:
+            raise ValueError("timestamps=True with token_times: segment timestamps with token times are not built")
+        if timestamps and int(self.spec.num_beams if num_beams is None else num_beams) > 1:
+            raise ValueError("timestamps=True with num_beams > 1: segment timestamps with beam search are not built")
         if token_times:
             self.spec.require_alignment_heads()
         self.last_scores: List[Optional[float]] = [None] * len(waves)
@@ -70,6 +127,7 @@ class WhisperTranscriber:
         out: List[Optional[List[int]]] = [None] * len(waves)
         self.last_languages = [None] * len(waves)
         self.token_times = [None] * len(waves)
+        self.segments, self.next_seek = [None] * len(waves), [None] * len(waves)
         self.failed = []
 
         def fail(j, res):
@@ -78,11 +136,14 @@ class WhisperTranscriber:
 
         for n, idx in enumerate(make_batches(range(len(waves)), BATCH), start=int(first_batch)):
             def run(js):
-                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times, num_beams, length_penalty)
+                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times, num_beams, length_penalty, timestamps)
                 if failed:
                     return res
                 for k, j in enumerate(js):
                     out[j], self.last_languages[j] = res.lists[k], int(res.languages[k])
+                    if timestamps:
+                        out[j] = [t for t in res.lists[k] if t < self.spec.timestamp_begin]
+                        self.segments[j], self.next_seek[j] = res.segments[k], int(res.next_seek[k])
                     if getattr(res, "beam_scores", None) is not None:
                         self.last_scores[j] = float(res.beam_scores[k])
                     if token_times and int(res.ts_status[k]) != 0:
@@ -196,6 +257,15 @@ def write_times_json(path: str, entries: dict) -> None:
         f.write("\n")
 
 
+def segments_entry(segments, next_seek: int, text: str, ts_begin: int, tokenizer=None) -> dict:
+    """``{"text": s, "segments": [[start_s, end_s, text], ...], "next_seek_s": x}``; a segment's text is its ids without the timestamp
+    tokens, decoded -- or, without vocabulary files, as numbers."""
+    r = lambda x: round(float(x), 2)
+    show = lambda t: tokenizer.decode(t, skip_special_tokens=True) if tokenizer is not None else " ".join(str(i) for i in t)
+    return {"text": text, "segments": [[r(a), r(b), show([t for t in s if t < ts_begin])] for a, b, s in segments],
+            "next_seek_s": r(next_seek * TIME_PRECISION_FEATURES)}
+
+
 def times_entry(ids: Sequence[int], times: Sequence[float], text: str, tokenizer=None) -> dict:
     r = lambda x: round(float(x), 2)
     e = {"text": text, "tokens": [[int(t), r(a), r(b)] for t, (a, b) in zip(ids, token_spans(times))]}
@@ -237,6 +307,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_beams", type=int, default=None, choices=range(1, C.GenerationSpec.MAX_BEAMS + 1), metavar="K",
                    help="beam search with K beams (HF's early_stopping=false); default: generation_config.json's num_beams, else greedy")
     p.add_argument("--length_penalty", type=float, default=None, help="with beams: the exponent of the length a finished score is divided by")
+    p.add_argument("--segments_json", type=str, default="", help="decode with the model's own segment timestamps (first 30 s window of "
+                   "each file) and also write them, with where the next window would begin, to this JSON file")
     return p
 
 
@@ -246,6 +318,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     args = p.parse_args(argv)
     if args.num_beams is not None and args.num_beams > 1 and args.times_json:
         p.error("--num_beams with --times_json: token times with beam search are not built")
+    if args.segments_json and args.times_json:
+        p.error("--segments_json with --times_json: segment timestamps with token times are not built")
+    if args.segments_json and args.num_beams is not None and args.num_beams > 1:
+        p.error("--segments_json with --num_beams: segment timestamps with beam search are not built")
     if args.length_penalty is not None and (args.num_beams is None or args.num_beams < 2):
         p.error("--length_penalty needs --num_beams K with K >= 2")
     return args
@@ -305,7 +381,11 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
         except ValueError as e:
             print(f"Error: {e}")
             return 0
-    entries = {}
+    want_segments = bool(args.segments_json)
+    if want_segments and args.num_beams is None and tr.spec.num_beams > 1:
+        print("Error: --segments_json with num_beams > 1 in generation_config.json: segment timestamps with beam search are not built")
+        return 0
+    entries, seg_entries = {}, {}
     for i in range(0, len(names), BATCH):
         chunk, waves = [], []
         for n in names[i:i + BATCH]:
@@ -315,11 +395,18 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
             except Exception as e:                          # noqa: BLE001
                 print(f"Failed to process {n}: {e}")
         beams = {} if args.num_beams is None else dict(num_beams=args.num_beams, length_penalty=args.length_penalty)
+        if want_segments:
+            beams["timestamps"] = True                      # the default call stays the one it always was
         for k, (n, ids) in enumerate(zip(chunk, tr.transcribe(waves, chunk, first_batch=i // BATCH, token_times=want_times, **beams))):
             if ids is not None:
                 rows.append((n, tok.decode(ids, skip_special_tokens=True) if tok is not None else " ".join(str(t) for t in ids)))
                 if want_times and tr.token_times[k] is not None:
                     entries[n] = times_entry(ids, tr.token_times[k], rows[-1][1], tok)
+                if want_segments and tr.segments[k] is not None:
+                    seg_entries[n] = segments_entry(tr.segments[k], tr.next_seek[k], rows[-1][1], tr.spec.timestamp_begin, tok)
+    if want_segments:
+        write_times_json(args.segments_json, seg_entries)
+        print(f"Wrote the segments of {len(seg_entries)} files to {args.segments_json}")
     if want_times:
         write_times_json(args.times_json, entries)
         print(f"Wrote the token times of {len(entries)} files to {args.times_json}")
