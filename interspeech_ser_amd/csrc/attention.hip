@@ -724,18 +724,20 @@ static int launch_attention(const AttnParams& p, const attn_launch& pl, hipStrea
     return ser_check_launch("ser_attention");
 }
 
-// ser_attention_rk_v: the base arguments are planned as ser_attention_v plans them, then moved to the low-occupancy form (the RK forms have
-// no high-occupancy instantiation: the bias registers would not fit its 128).
-extern "C" int ser_attention_rk_v(const ser_attention_rk_args* ra, void* stream) {
-    if (!ra || !ra->qe) return ser_fail(-1, "ser_attention_rk: null pointer");
-    const ser_attention_args* args = &ra->base;
+// What ser_attention_rk_v and ser_attention_rb_v share: the refusals on the base arguments, ser_attention_v's plan moved to the
+// low-occupancy form (the RK forms have no high-occupancy instantiation: the bias registers would not fit its 128), the argument block and
+// the dispatch over mode and RB.  `who` names the entry point in every message.  `own` runs the entry point's own refusals between the
+// base checks and the plan, where they always ran, so a call with two faults keeps its error code.  The bias row of (query row, head) is
+// qe + (row H + head) qe_ld, indexed by clamp(key - query, -Lm, Rm) + Lm, or with rb by the key itself.
+template <class OWN>
+static int launch_attention_biased(const char* who, const ser_attention_args* args, const float* qe, int64_t qe_ld, int Lm, int Rm, bool rb,
+                                   OWN&& own, void* stream) {
     if (args->table || args->gate || args->gru_const || args->gate_x || args->key_lens || args->bias2d || args->out_mode)
-        return ser_fail(-2, "ser_attention_rk: takes no table, gate, key_lens, bias2d or FP16M output");
-    if (args->scale > 0.f || args->dh != 64) return ser_fail(-2, "ser_attention_rk: needs a pre-scaled q (scale <= 0) and head dim 64");
+        return ser_fail(-2, "%s: takes no table, gate, key_lens, bias2d or FP16M output", who);
+    if (args->scale > 0.f || args->dh != 64) return ser_fail(-2, "%s: needs a pre-scaled q (scale <= 0) and head dim 64", who);
     if (args->mode != SER_MODE_BF16 && args->mode != SER_MODE_FP32X && args->mode != SER_MODE_FP16X)
-        return ser_fail(-5, "ser_attention_rk: bad mode %d (bf16 / fp32x / fp16x)", args->mode);
-    if (ra->left_max < 0 || ra->right_max < 0 || ra->left_max + ra->right_max + 1 > 128 || ra->ld_qe < ra->left_max + ra->right_max + 1)
-        return ser_fail(-2, "ser_attention_rk: left_max=%d right_max=%d ld_qe=%lld unsupported", ra->left_max, ra->right_max, (long long)ra->ld_qe);
+        return ser_fail(-5, "%s: bad mode %d (bf16 / fp32x / fp16x)", who, args->mode);
+    if (int rc = own()) return rc;
     attn_launch pl;
     if (int rc = attn_plan(args, &pl)) return rc;
     if (pl.occ) {                                   // the double-buffered form's LDS: two K + V buffers, no bias window
@@ -750,51 +752,39 @@ extern "C" int ser_attention_rk_v(const ser_attention_rk_args* ra, void* stream)
     p.out = (unsigned short*)args->out; p.ldo = args->ldo; p.out_plane = args->out_plane_stride;
     p.H = args->H; p.dh = args->dh; p.scale = args->scale; p.b2d_T = args->max_frames;
     p.B = args->B; p.nq = pl.nq; p.nitems = (int)pl.grid;
-    p.qe = ra->qe; p.qe_ld = ra->ld_qe; p.Lm = ra->left_max; p.Rm = ra->right_max;
+    p.qe = qe; p.qe_ld = qe_ld; p.Lm = Lm; p.Rm = Rm;
     hipStream_t s = (hipStream_t)stream;
     if (!ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(pl.mode, [&](auto M) {
-            hipLaunchKernelGGL((attention_kernel<64, M(), true, false, ATTN_NWV, false, false, false, true>), dim3(pl.grid, 1, 1), dim3(64 * ATTN_NWV),
-                               pl.lds, s, p);
+            ser_with_bool(rb, [&](auto RB) {
+                hipLaunchKernelGGL((attention_kernel<64, M(), true, false, ATTN_NWV, false, false, false, true, decltype(RB)::value>),
+                                   dim3(pl.grid, 1, 1), dim3(64 * ATTN_NWV), pl.lds, s, p);
+            });
         }))
-        return ser_fail(-5, "ser_attention_rk: bad mode %d", pl.mode);
-    return ser_check_launch("ser_attention_rk");
+        return ser_fail(-5, "%s: bad mode %d", who, pl.mode);
+    return ser_check_launch(who);
 }
 
-// ser_attention_rb_v: ser_attention_rk_v's plan and argument block; the table is a bias row per (query row, head), indexed by the key.
+// ser_attention_rk_v: the bias row holds the left_max + right_max + 1 clamped distances (ser_relkey_table_v).
+extern "C" int ser_attention_rk_v(const ser_attention_rk_args* ra, void* stream) {
+    if (!ra || !ra->qe) return ser_fail(-1, "ser_attention_rk: null pointer");
+    return launch_attention_biased("ser_attention_rk", &ra->base, ra->qe, ra->ld_qe, ra->left_max, ra->right_max, false, [&]() {
+        if (ra->left_max < 0 || ra->right_max < 0 || ra->left_max + ra->right_max + 1 > 128 || ra->ld_qe < ra->left_max + ra->right_max + 1)
+            return ser_fail(-2, "ser_attention_rk: left_max=%d right_max=%d ld_qe=%lld unsupported", ra->left_max, ra->right_max, (long long)ra->ld_qe);
+        return 0;
+    }, stream);
+}
+
+// ser_attention_rb_v: the bias row is indexed by the key's index in its utterance (ser_relpos_bias_v).
 extern "C" int ser_attention_rb_v(const ser_attention_rb_args* ra, void* stream) {
     if (!ra || !ra->pb) return ser_fail(-1, "ser_attention_rb: null pointer");
-    const ser_attention_args* args = &ra->base;
-    if (args->table || args->gate || args->gru_const || args->gate_x || args->key_lens || args->bias2d || args->out_mode)
-        return ser_fail(-2, "ser_attention_rb: takes no table, gate, key_lens, bias2d or FP16M output");
-    if (args->scale > 0.f || args->dh != 64) return ser_fail(-2, "ser_attention_rb: needs a pre-scaled q (scale <= 0) and head dim 64");
-    if (args->mode != SER_MODE_BF16 && args->mode != SER_MODE_FP32X && args->mode != SER_MODE_FP16X)
-        return ser_fail(-5, "ser_attention_rb: bad mode %d (bf16 / fp32x / fp16x)", args->mode);
-    if (args->max_frames <= 0 || (ra->ld_pb % ATTN_BKV) || ra->ld_pb < ((int64_t)args->max_frames + ATTN_BKV - 1) / ATTN_BKV * ATTN_BKV ||
-        ((uintptr_t)ra->pb & 15))
-        return ser_fail(-2, "ser_attention_rb: ld_pb=%lld must be a multiple of %d and >= max_frames rounded up to it; pb 16-byte aligned",
-                        (long long)ra->ld_pb, ATTN_BKV);
-    attn_launch pl;
-    if (int rc = attn_plan(args, &pl)) return rc;
-    if (pl.occ) {                                   // as ser_attention_rk_v: the double-buffered form's LDS
-        pl.occ = false;
-        pl.nbuf = 2;
-        pl.lds = (size_t)2 * (attn_qk_planes(pl.mode) + attn_v_planes(pl.mode)) * ATTN_BKV * pl.dhp * 2;
-    }
-    AttnParamsRK p = {};
-    p.qkv = (const unsigned short*)args->qkv; p.ld = args->ld; p.plane = args->plane_stride;
-    p.q_col = args->q_col; p.k_col = args->k_col; p.v_col = args->v_col;
-    p.frame_offs = args->frame_offs;
-    p.out = (unsigned short*)args->out; p.ldo = args->ldo; p.out_plane = args->out_plane_stride;
-    p.H = args->H; p.dh = args->dh; p.scale = args->scale; p.b2d_T = args->max_frames;
-    p.B = args->B; p.nq = pl.nq; p.nitems = (int)pl.grid;
-    p.qe = ra->pb; p.qe_ld = ra->ld_pb; p.Lm = 0; p.Rm = 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (!ser_with_mode<SER_MODE_BF16, SER_MODE_FP32X, SER_MODE_FP16X>(pl.mode, [&](auto M) {
-            hipLaunchKernelGGL((attention_kernel<64, M(), true, false, ATTN_NWV, false, false, false, true, true>), dim3(pl.grid, 1, 1),
-                               dim3(64 * ATTN_NWV), pl.lds, s, p);
-        }))
-        return ser_fail(-5, "ser_attention_rb: bad mode %d", pl.mode);
-    return ser_check_launch("ser_attention_rb");
+    const int max_frames = ra->base.max_frames;
+    return launch_attention_biased("ser_attention_rb", &ra->base, ra->pb, ra->ld_pb, 0, 0, true, [&]() {
+        if (max_frames <= 0 || (ra->ld_pb % ATTN_BKV) || ra->ld_pb < ((int64_t)max_frames + ATTN_BKV - 1) / ATTN_BKV * ATTN_BKV ||
+            ((uintptr_t)ra->pb & 15))
+            return ser_fail(-2, "ser_attention_rb: ld_pb=%lld must be a multiple of %d and >= max_frames rounded up to it; pb 16-byte aligned",
+                            (long long)ra->ld_pb, ATTN_BKV);
+        return 0;
+    }, stream);
 }
 
 extern "C" int ser_attention(const void* qkv, int64_t ld, int64_t plane_stride, int q_col, int k_col, int v_col,

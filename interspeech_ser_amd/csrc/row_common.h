@@ -3,6 +3,9 @@
 #pragma once
 #include "ser_common.h"
 
+// The conformer layers' sigmoid (GLU and swish): accurate expf and a true division, not gru_sigmoid's intrinsics.
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // A lane owns 4 consecutive columns of every 256-column chunk: f(i, c) for chunk i and the lane's first column c of it (may be >= D).
 template <class F>
 __device__ __forceinline__ void row_chunks(int lane, F&& f) {

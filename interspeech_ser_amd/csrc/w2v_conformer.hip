@@ -1,11 +1,9 @@
 // The wav2vec2-conformer encoders' own kernels (ser_hip.h a35; HF modeling_wav2vec2_conformer.py): the rotation of the layer-normed rows in
-// front of linear_q / linear_k (ser_rope_rows_v), the middle of the convolution module with a centred window and BatchNorm in eval
-// (ser_conformer_conv_bn_v) and the positional term of the Transformer-XL scores (ser_relpos_bias_v; the attention that reads it is an
-// instantiation of attention.hip's kernel, ser_attention_rb_v).  The reference ships no conformer encoder; its heads take any [T, D] stream
-// (bin/train_cat_bimodal_lazy_1head.py:220-228).  Plain grids, fixed summation orders, no atomics on float data.
+// front of linear_q / linear_k (ser_rope_rows_v) and the positional term of the Transformer-XL scores (ser_relpos_bias_v; the attention that
+// reads it is an instantiation of attention.hip's kernel, ser_attention_rb_v).  The family's convolution module (ser_conformer_conv_bn_v:
+// centred window, BatchNorm in eval) is an instantiation of conformer.hip's one body.  The reference ships no conformer encoder; its heads
+// take any [T, D] stream (bin/train_cat_bimodal_lazy_1head.py:220-228).  Plain grids, fixed summation orders, no atomics on float data.
 #include "row_common.h"
-
-__device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------------------------- rotary rows
 // Wave per row on the row skeleton: a lane's 4 columns of every 256-column chunk lie in one half of one head (dh % 8 == 0), their partners
@@ -59,89 +57,6 @@ extern "C" int ser_rope_rows_v(const ser_rope_rows_args* a, void* stream) {
         }))
         return ser_fail(-4, "ser_rope_rows: bad mode %d", a->mode);
     return ser_check_launch("ser_rope_rows");
-}
-
-// ----------------------------------------------------------------------------------------------- convolution module, BatchNorm form
-// ser_conformer_conv_v's block (conformer.hip): SER_CCONV_TILE rows of one utterance, thread = 4 columns of every 1024-column slab, the GLU
-// of an input row taken once and added to every output row whose window holds it, output row r's taps in ascending k.  The window is
-// centred -- input rows t0 - (K - 1) / 2 .. t0 + TILE - 1 + (K - 1) / 2 that exist in the utterance -- and a per-channel affine takes the
-// place of the LayerNorm passes, so the block needs no LDS.
-#define CCB_SLABS 2
-template <int MODE>
-__global__ __launch_bounds__(256) void conformer_conv_bn_kernel(ser_conformer_conv_bn_args a) {
-    constexpr int R = SER_CCONV_TILE;
-    const int b = blockIdx.y, t0 = blockIdx.x * R, tid = threadIdx.x;
-    const int row0 = a.frame_offs[b], T = a.frame_offs[b + 1] - row0;
-    if (t0 >= T) return;                                                   // block-uniform
-    const int D = a.D, K = a.K, half = (K - 1) >> 1;
-    f32x4 acc[CCB_SLABS][R];
-#pragma unroll
-    for (int i = 0; i < CCB_SLABS; ++i)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[i][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int s_begin = t0 - half > 0 ? t0 - half : 0;                     // never before the utterance's own first row
-    const int s_end = t0 + R + half < T ? t0 + R + half : T;               // ... nor past its last
-    for (int s = s_begin; s < s_end; ++s) {
-        const float* yr = a.y + (int64_t)(row0 + s) * a.ldy;
-#pragma unroll
-        for (int i = 0; i < CCB_SLABS; ++i) {
-            const int c = i * 1024 + tid * 4;
-            if (c < D) {
-                const f32x4 va = *(const f32x4*)(yr + c), vb = *(const f32x4*)(yr + D + c);
-                f32x4 g;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) g[j] = va[j] * sigmoid_acc(vb[j]);
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int k = s - (t0 + r) + half;                     // tap of input row s in output row t0 + r's window
-                    if (k >= 0 && k < K) {
-                        const f32x4 w = *(const f32x4*)(a.w + (int64_t)k * D + c);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][r][j] = fmaf(w[j], g[j], acc[i][r][j]);
-                    }
-                }
-            }
-        }
-    }
-    float ramax = 0.f;
-#pragma unroll
-    for (int i = 0; i < CCB_SLABS; ++i) {
-        const int c = i * 1024 + tid * 4;
-        if (c < D) {
-            const f32x4 sc = *(const f32x4*)(a.scale + c), sh = *(const f32x4*)(a.shift + c);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (t0 + r < T) {
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float t = fmaf(acc[i][r][j], sc[j], sh[j]);
-                        v[j] = t * sigmoid_acc(t);
-                    }
-                    unsigned short* orow = (unsigned short*)a.out_act + (int64_t)(row0 + t0 + r) * a.ldo_act;
-                    store_act4<MODE>(orow + c, a.out_plane_stride, v[0], v[1], v[2], v[3]);
-                    if constexpr (mode_traits<MODE>::f16) { for (int j = 0; j < 4; ++j) ramax = range_fold(ramax, v[j]); }
-                }
-            }
-        }
-    }
-    if constexpr (mode_traits<MODE>::f16) range_report(a.range_flag, ramax);
-}
-
-extern "C" int ser_conformer_conv_bn_v(const ser_conformer_conv_bn_args* a, void* stream) {
-    if (!a || !a->y || !a->w || !a->scale || !a->shift || !a->frame_offs || !a->out_act) return ser_fail(-1, "ser_conformer_conv_bn: null pointer");
-    if (a->D % 4 || a->D <= 0 || a->D > 1024 * CCB_SLABS || a->K < 1 || a->K > 31 || !(a->K & 1))
-        return ser_fail(-2, "ser_conformer_conv_bn: D=%d (multiple of 4, <= %d) / K=%d (odd, <= 31) unsupported", a->D, 1024 * CCB_SLABS, a->K);
-    if (a->B <= 0 || a->B > 65535 || a->max_frames <= 0 || a->rows < a->max_frames)
-        return ser_fail(-2, "ser_conformer_conv_bn: bad B=%d / max_frames=%d / rows=%d", a->B, a->max_frames, a->rows);
-    if ((a->ldy % 4) || a->ldy < 2 * (int64_t)a->D || (a->ldo_act % 4) || a->ldo_act < a->D)
-        return ser_fail(-3, "ser_conformer_conv_bn: pitches must be multiples of 4, ldy >= 2 D, ldo_act >= D");
-    dim3 grid((a->max_frames + SER_CCONV_TILE - 1) / SER_CCONV_TILE, a->B), block(256);
-    if (!ser_with_mode<SER_MODE_FP32X, SER_MODE_BF16, SER_MODE_FP16, SER_MODE_FP16X>(a->mode, [&](auto M) {
-            hipLaunchKernelGGL(conformer_conv_bn_kernel<M()>, grid, block, 0, (hipStream_t)stream, *a);
-        }))
-        return ser_fail(-4, "ser_conformer_conv_bn: bad mode %d", a->mode);
-    return ser_check_launch("ser_conformer_conv_bn");
 }
 
 // ------------------------------------------------------------------------------------------------------- relative-position bias

@@ -3439,6 +3439,130 @@ class _PreLnStack(_LaunchHost):
         return out
 
 
+class _ConformerLayers:
+    """The conformer layer of ``W2vBertEncoder`` and ``ConformerSpeechEncoder`` (a mixin in front of ``_EncoderBase``):
+        x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(..);  x += FFN2(LN x) / 2;  x = LN x
+    on ser_layernorm_v and ser_gemm, with ser_swish_rows_v between a feed-forward block's GEMMs and ser_conformer_conv_v or
+    ser_conformer_conv_bn_v between the convolution module's pointwise GEMMs.  The two 1/2 factors are folded into the blocks' output
+    Linears at load.  An encoder adds its own front end, attention step (r1 -> ctx) and position weights, buffers and tables."""
+
+    def _q_scale(self) -> float:
+        """q leaves its projection multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)"""
+        return self.geo.head_dim ** -0.5 * 1.4426950408889634
+
+    def _check_conformer_geometry(self, attention: str, distances: Optional[int] = None) -> None:
+        geo = self.geo
+        D, dh, K = geo.hidden, geo.head_dim, geo.conv_depthwise_kernel
+        if dh != 64:
+            raise ValueError(f"the {attention} attention is built for heads of 64 (hidden {D} / {geo.heads} heads = {dh})")
+        if D % 64 or geo.ffn % 64 or D > 2048:
+            raise ValueError(f"hidden {D} / intermediate {geo.ffn} must be multiples of 64, hidden <= 2048")
+        if not (K & 1) or K > 31 or (distances is not None and distances > 128):
+            tail = "" if distances is None else f" / {distances} distances (<= 128)"
+            raise ValueError(f"depthwise kernel {K} (odd, <= 31){tail} unsupported")
+
+    def _conformer_layer_weights(self, sd, i: int) -> dict:
+        """what the families share of layer ``i``; the caller adds its attention projections, position weights and the conv module's norm
+        (``dw_ln``: LayerNorm, or ``bn``: the folded BatchNorm)"""
+        from .weights import fold_w2v_bert_ffn
+        D, K = self.geo.hidden, self.geo.conv_depthwise_kernel
+        p = f"encoder.layers.{i}"
+        a, c = p + ".self_attn", p + ".conv_module"
+        lay = {}
+        for f in ("ffn1", "ffn2"):
+            lay[f + "_ln"] = self._ln_pair(sd, f"{p}.{f}_layer_norm")
+            lay[f + "_fc1"] = self._linear(sd[f"{p}.{f}.intermediate_dense.weight"], sd[f"{p}.{f}.intermediate_dense.bias"],
+                                           name=f"{p}.{f}.intermediate_dense.weight")
+            lay[f + "_fc2"] = self._linear(*fold_w2v_bert_ffn(sd[f"{p}.{f}.output_dense.weight"], sd[f"{p}.{f}.output_dense.bias"]),
+                                           name=f"{p}.{f}.output_dense.weight")
+        lay["attn_ln"] = self._ln_pair(sd, p + ".self_attn_layer_norm")
+        lay["out"] = self._linear(sd[a + ".linear_out.weight"], sd[a + ".linear_out.bias"], name=a + ".linear_out.weight")
+        lay["conv_ln"] = self._ln_pair(sd, c + ".layer_norm")
+        lay["pw1"] = self._linear(sd[c + ".pointwise_conv1.weight"].reshape(2 * D, D), None, name=c + ".pointwise_conv1.weight")
+        lay["dw"] = self._dev_f32(sd[c + ".depthwise_conv.weight"].reshape(D, K).t())        # [K][D]: a thread's 4 channels are one load
+        lay["pw2"] = self._linear(sd[c + ".pointwise_conv2.weight"].reshape(D, D), None, name=c + ".pointwise_conv2.weight")
+        lay["final_ln"] = self._ln_pair(sd, p + ".final_layer_norm")
+        return lay
+
+    def _conformer_buffers(self, ar: dict, M: int) -> None:
+        geo, dev = self.geo, self.device
+        D, F = geo.hidden, geo.ffn
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ar["states"] = f32(geo.num_layers + 1, M, D)
+        ar["r1"], ar["r2"], ar["r3"], ar["r4"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D)
+        ar["f1"], ar["pw"] = f32(M, F), f32(M, 2 * D)
+        ar["xa"], ar["ctx"], ar["cv"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
+        ar["qkv"], ar["ffn"] = self._new_act(M, 3 * D), self._new_act(M, F)
+
+    def _swish_rows(self, x: torch.Tensor, out: Act, rows: int, D: int) -> None:
+        a = self._cmd("swish_rows")
+        a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), D, out.ptr, out.cols, out.plane_stride
+        a.range_flag, a.mode, a.rows, a.D = self._flag, self.mode, rows, D
+        self._issue(_lib.OP_SWISH_ROWS, a, "ser_swish_rows", rows=rows)
+
+    def _ffn_half(self, pl, lay, f: str, x: torch.Tensor, out: torch.Tensor, eps=None) -> None:
+        """out = x + FFN(LN x) / 2 (the half sits in the output Linear); ``eps``: the LayerNorm's, default the geometry's"""
+        M, D, F = pl["M"], self.geo.hidden, self.geo.ffn
+        self._layernorm(x, D, lay[f + "_ln"], M, D, out_act=pl["xa"], eps=eps)
+        self._gemm(pl["xa"], lay[f + "_fc1"], M, out_f32=pl["f1"], ldo_f32=F)
+        self._swish_rows(pl["f1"], pl["ffn"], M, F)
+        self._gemm(pl["ffn"], lay[f + "_fc2"], M, residual=x, ldr=D, out_f32=out, ldo_f32=D)
+
+    def _conv_mid(self, pl, lay) -> None:
+        """pw -> cv through the norm the layer carries: ``bn`` (centred window, ser_conformer_conv_bn_v) or ``dw_ln`` (causal window)"""
+        geo, out, bn = self.geo, pl["cv"], "bn" in lay
+        a = self._cmd("conformer_conv_bn" if bn else "conformer_conv")
+        a.y, a.ldy, a.w = pl["pw"].data_ptr(), 2 * geo.hidden, lay["dw"].data_ptr()
+        if bn:
+            a.scale, a.shift = lay["bn"][0].data_ptr(), lay["bn"][1].data_ptr()
+        else:
+            a.gamma, a.beta, a.eps = lay["dw_ln"][0].data_ptr(), lay["dw_ln"][1].data_ptr(), float(geo.layer_norm_eps)
+        a.frame_offs, a.out_act, a.ldo_act, a.out_plane_stride = pl["frame_offs"].data_ptr(), out.ptr, out.cols, out.plane_stride
+        a.range_flag = self._flag
+        a.B, a.D, a.K, a.max_frames, a.rows, a.mode = pl["B"], geo.hidden, geo.conv_depthwise_kernel, pl["Tmax"], pl["M"], self.mode
+        self._issue(_lib.OP_CONFORMER_CONV_BN if bn else _lib.OP_CONFORMER_CONV, a, "ser_conformer_conv_bn" if bn else "ser_conformer_conv",
+                    B=pl["B"], max_frames=pl["Tmax"], rows=pl["M"])
+
+    def _biased_attention_cmd(self, pl, field: str):
+        """an ``attention_rk`` / ``attention_rb`` command over the packed q | k | v with its embedded ``base`` filled; the caller sets the bias
+        fields and issues it"""
+        geo = self.geo
+        D, qkv, out = geo.hidden, pl["qkv"], pl["ctx"]
+        r = self._cmd(field)
+        a = r.base
+        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
+        a.q_col, a.k_col, a.v_col, a.B = 0, D, 2 * D, pl["B"]
+        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
+        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
+        a.H, a.dh, a.scale, a.mode = geo.heads, geo.head_dim, -1.0, self.mode          # q is pre-scaled
+        if self._rec is not None:                                               # the per-batch sizes live in the embedded base struct
+            self._rec.patches += [(a, "B", "B"), (a, "max_frames", "Tmax")]
+        return r
+
+    def _conformer_layers(self, pl, attention, last_state: Optional[int], eps=None, enc_ln=None) -> None:
+        """the layers from states[0] on.  ``attention(pl, lay, scale)``: the encoder's step from r1 to ctx, the layer's attention LayerNorm
+        included; ``eps``: the layers' LayerNorm eps (None: the geometry's); ``enc_ln``: a LayerNorm over the last layer's output, which
+        then goes through ``last`` (None: every layer writes its state directly)"""
+        geo = self.geo
+        M, D, L = pl["M"], geo.hidden, geo.num_layers
+        states, scale = pl["states"], self._q_scale()
+        for i, lay in enumerate(self.layers):
+            via_last = enc_ln is not None and i + 1 == L
+            self._ffn_half(pl, lay, "ffn1", states[i], pl["r1"], eps=eps)
+            attention(pl, lay, scale)
+            self._gemm(pl["ctx"], lay["out"], M, residual=pl["r1"], ldr=D, out_f32=pl["r2"], ldo_f32=D)
+            self._layernorm(pl["r2"], D, lay["conv_ln"], M, D, out_act=pl["xa"], eps=eps)
+            self._gemm(pl["xa"], lay["pw1"], M, out_f32=pl["pw"], ldo_f32=2 * D)
+            self._conv_mid(pl, lay)
+            self._gemm(pl["cv"], lay["pw2"], M, residual=pl["r2"], ldr=D, out_f32=pl["r3"], ldo_f32=D)
+            self._ffn_half(pl, lay, "ffn2", pl["r3"], pl["r4"], eps=eps)
+            self._layernorm(pl["r4"], D, lay["final_ln"], M, D, out_f32=pl["last"] if via_last else states[i + 1], eps=eps)
+            if via_last:
+                self._layernorm(pl["last"], D, enc_ln, M, D, out_f32=states[L])
+            if self._state_done(i + 1, last_state):
+                return
+
+
 class ProsodyEncoder(_WaveIO, _PreLnStack):
     """The prosody stream of the reference's three-stream heads (preprocessing/preprocess_ns3_prosody.py) on libserhip: NS3 log-mel +
     melspec_linear (ser_prosody_mel_v), melspec_encoder's pre-LayerNorm layers -- ser_layernorm_v, ser_gemm (FC1's k = 5 convolution as an
@@ -3804,26 +3928,19 @@ class SpeakerProsodyEncoder(_WaveIO, _PreLnStack):
                                       pp["frame_offs"], pp["err"], pl["enc"][:M], self.pos0, keep)
 
 
-class W2vBertEncoder(_WaveIO, _EncoderBase):
+class W2vBertEncoder(_ConformerLayers, _WaveIO, _EncoderBase):
     """w2v-BERT 2.0 (HF Wav2Vec2BertModel behind SeamlessM4TFeatureExtractor; not in the reference, whose heads take any [T, D] stream) on
-    libserhip: the Kaldi fbank front end (ser_fbank_v), the feature projection, and per conformer layer
+    libserhip: the Kaldi fbank front end (ser_fbank_v), the feature projection, and ``_ConformerLayers``' layer
         x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(LN x);  x += FFN2(LN x) / 2;  x = LN x
-    on ser_layernorm_v and ser_gemm, with ser_swish_rows_v between a feed-forward block's GEMMs, ser_relkey_table_v + ser_attention_rk_v for
-    the relative-key attention and ser_conformer_conv_v between the convolution module's pointwise GEMMs.  The two 1/2 factors are folded
-    into the blocks' output Linears at load.  Every utterance alone: ``frames(n) = (1 + (n - 400) // 160) // stride`` rows, at least one."""
+    with ser_relkey_table_v + ser_attention_rk_v for the relative-key attention and ser_conformer_conv_v (causal window, LayerNorm) in the
+    convolution module.  Every utterance alone: ``frames(n) = (1 + (n - 400) // 160) // stride`` rows, at least one."""
 
     def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "f16x"):
         from .frontend import w2vbert_dft_table, w2vbert_mel_filters
-        from .weights import fold_w2v_bert_ffn
         super().__init__(geo, device, mode, post_ln=True)
         sd = state_dict
-        D, dh, K = geo.hidden, geo.head_dim, geo.conv_depthwise_kernel
-        if dh != 64:
-            raise ValueError(f"the relative-key attention is built for heads of 64 (hidden {D} / {geo.heads} heads = {dh})")
-        if D % 64 or geo.ffn % 64 or D > 2048:
-            raise ValueError(f"hidden {D} / intermediate {geo.ffn} must be multiples of 64, hidden <= 2048")
-        if not (K & 1) or K > 31 or geo.distance_positions > 128:
-            raise ValueError(f"depthwise kernel {K} (odd, <= 31) / {geo.distance_positions} distances (<= 128) unsupported")
+        D = geo.hidden
+        self._check_conformer_geometry("relative-key", geo.distance_positions)
         melw, rng = w2vbert_mel_filters(geo.fbank_mels)
         self.melw = torch.from_numpy(melw).to(self.device)
         self.mel_range = torch.from_numpy(rng).to(self.device)
@@ -3838,26 +3955,12 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         self.qe_ld = ((geo.distance_positions + 3) // 4) * 4
         self.layers = []
         for i in range(geo.num_layers):
-            p = f"encoder.layers.{i}"
-            a, c = p + ".self_attn", p + ".conv_module"
-            lay = {}
-            for f in ("ffn1", "ffn2"):
-                lay[f + "_ln"] = self._ln_pair(sd, f"{p}.{f}_layer_norm")
-                lay[f + "_fc1"] = self._linear(sd[f"{p}.{f}.intermediate_dense.weight"], sd[f"{p}.{f}.intermediate_dense.bias"],
-                                               name=f"{p}.{f}.intermediate_dense.weight")
-                lay[f + "_fc2"] = self._linear(*fold_w2v_bert_ffn(sd[f"{p}.{f}.output_dense.weight"], sd[f"{p}.{f}.output_dense.bias"]),
-                                               name=f"{p}.{f}.output_dense.weight")
-            lay["attn_ln"] = self._ln_pair(sd, p + ".self_attn_layer_norm")
+            a, c = f"encoder.layers.{i}.self_attn", f"encoder.layers.{i}.conv_module"
+            lay = self._conformer_layer_weights(sd, i)
             lay["qkv"] = self._linear(torch.cat([sd[f"{a}.linear_{n}.weight"] for n in "qkv"], 0), torch.cat([sd[f"{a}.linear_{n}.bias"] for n in "qkv"], 0),
                                       name=a + ".linear_{q,k,v}.weight")
-            lay["out"] = self._linear(sd[a + ".linear_out.weight"], sd[a + ".linear_out.bias"], name=a + ".linear_out.weight")
             lay["E"] = self._dev_f32(sd[a + ".distance_embedding.weight"])
-            lay["conv_ln"] = self._ln_pair(sd, c + ".layer_norm")
-            lay["pw1"] = self._linear(sd[c + ".pointwise_conv1.weight"].reshape(2 * D, D), None, name=c + ".pointwise_conv1.weight")
-            lay["dw"] = self._dev_f32(sd[c + ".depthwise_conv.weight"].reshape(D, K).t())        # [K][D]: a thread's 4 channels are one load
             lay["dw_ln"] = self._ln_pair(sd, c + ".depthwise_layer_norm")
-            lay["pw2"] = self._linear(sd[c + ".pointwise_conv2.weight"].reshape(D, D), None, name=c + ".pointwise_conv2.weight")
-            lay["final_ln"] = self._ln_pair(sd, p + ".final_layer_norm")
             self.layers.append(lay)
         self._arenas = SlotArenas(self._build_arena)
 
@@ -3869,16 +3972,12 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         """buffer set of one slot (pointers fixed between batches: the command list is recorded once per arena); ``cap``: frames M,
         utterances B, mel frames F"""
         M, B, Fr, geo, dev = cap["M"], cap["B"], cap["F"], self.geo, self.device
-        D, F, H = geo.hidden, geo.ffn, geo.heads
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         ar = {}
         ar["mel"], ar["fb"] = f32(Fr, geo.fbank_mels), f32(M, self.fdim)
         ar["fb_act"] = self._new_act(M, self.fpad, zero=True)                 # columns past 160 stay zero
-        ar["states"] = f32(geo.num_layers + 1, M, D)
-        ar["r1"], ar["r2"], ar["r3"], ar["r4"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D)
-        ar["f1"], ar["pw"], ar["qe"] = f32(M, F), f32(M, 2 * D), f32(M * H, self.qe_ld)
-        ar["xa"], ar["ctx"], ar["cv"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
-        ar["qkv"], ar["ffn"] = self._new_act(M, 3 * D), self._new_act(M, F)
+        self._conformer_buffers(ar, M)
+        ar["qe"] = f32(M * geo.heads, self.qe_ld)
         ar["tab"] = TableBlob(B, 3, dev)                                     # sample_offs | mel_offs (int32) | frame_offs (int32)
         if self.fp16_planes:
             ar["range_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -3918,75 +4017,27 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         a.B, a.max_mel_frames, a.n_mels, a.stride = pl["B"], pl["Fmax"], geo.fbank_mels, geo.fbank_stride
         self._issue(_lib.OP_FBANK, a, "ser_fbank", input="wav", B=pl["B"], max_mel_frames=pl["Fmax"])
 
-    def _swish_rows(self, x: torch.Tensor, out: Act, rows: int, D: int) -> None:
-        a = self._cmd("swish_rows")
-        a.x, a.ldx, a.out_act, a.ldo_act, a.out_plane_stride = x.data_ptr(), D, out.ptr, out.cols, out.plane_stride
-        a.range_flag, a.mode, a.rows, a.D = self._flag, self.mode, rows, D
-        self._issue(_lib.OP_SWISH_ROWS, a, "ser_swish_rows", rows=rows)
-
-    def _relkey_attention(self, pl, lay) -> None:
+    def _relkey_attention(self, pl, lay, scale: float) -> None:
+        """LN rows -> packed projection -> the relative-key table per (row, head) -> ser_attention_rk_v"""
         geo = self.geo
-        D, H, P = geo.hidden, geo.heads, geo.distance_positions
-        qkv, out = pl["qkv"], pl["ctx"]
+        M, D, qkv = pl["M"], geo.hidden, pl["qkv"]
+        self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_act=pl["xa"])
+        self._gemm(pl["xa"], lay["qkv"], M, out_act=qkv, col_scale=scale, col_scale_end=D)
         t = self._cmd("relkey_table")
         t.qkv, t.ld, t.plane_stride, t.E, t.qe, t.ld_qe = qkv.ptr, qkv.cols, qkv.plane_stride, lay["E"].data_ptr(), pl["qe"].data_ptr(), self.qe_ld
-        t.q_col, t.rows, t.H, t.dh, t.P, t.mode = 0, pl["M"], H, geo.head_dim, P, self.mode
-        self._issue(_lib.OP_RELKEY_TABLE, t, "ser_relkey_table", rows=pl["M"])
-        r = self._cmd("attention_rk")
-        a = r.base
-        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
-        a.q_col, a.k_col, a.v_col, a.B = 0, D, 2 * D, pl["B"]
-        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
-        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
-        a.H, a.dh, a.scale, a.mode = H, geo.head_dim, -1.0, self.mode          # q is pre-scaled
+        t.q_col, t.rows, t.H, t.dh, t.P, t.mode = 0, M, geo.heads, geo.head_dim, geo.distance_positions, self.mode
+        self._issue(_lib.OP_RELKEY_TABLE, t, "ser_relkey_table", rows=M)
+        r = self._biased_attention_cmd(pl, "attention_rk")
         r.qe, r.ld_qe, r.left_max, r.right_max = pl["qe"].data_ptr(), self.qe_ld, geo.left_max_positions, geo.right_max_positions
-        if self._rec is not None:                                               # the per-batch sizes live in the embedded base struct
-            self._rec.patches += [(a, "B", "B"), (a, "max_frames", "Tmax")]
         self._issue(_lib.OP_ATTENTION_RK, r, "ser_attention_rk")
 
-    def _conv_mid(self, pl, lay) -> None:
-        geo = self.geo
-        out = pl["cv"]
-        a = self._cmd("conformer_conv")
-        a.y, a.ldy, a.w, a.gamma, a.beta = pl["pw"].data_ptr(), 2 * geo.hidden, lay["dw"].data_ptr(), lay["dw_ln"][0].data_ptr(), lay["dw_ln"][1].data_ptr()
-        a.frame_offs, a.out_act, a.ldo_act, a.out_plane_stride = pl["frame_offs"].data_ptr(), out.ptr, out.cols, out.plane_stride
-        a.range_flag, a.eps = self._flag, float(geo.layer_norm_eps)
-        a.B, a.D, a.K, a.max_frames, a.rows, a.mode = pl["B"], geo.hidden, geo.conv_depthwise_kernel, pl["Tmax"], pl["M"], self.mode
-        self._issue(_lib.OP_CONFORMER_CONV, a, "ser_conformer_conv", B=pl["B"], max_frames=pl["Tmax"], rows=pl["M"])
-
-    def _ffn_half(self, pl, lay, f: str, x: torch.Tensor, out: torch.Tensor, eps=None) -> None:
-        """out = x + FFN(LN x) / 2 (the half sits in the output Linear); ``eps``: the LayerNorm's, default the geometry's"""
-        M, D, F = pl["M"], self.geo.hidden, self.geo.ffn
-        self._layernorm(x, D, lay[f + "_ln"], M, D, out_act=pl["xa"], eps=eps)
-        self._gemm(pl["xa"], lay[f + "_fc1"], M, out_f32=pl["f1"], ldo_f32=F)
-        self._swish_rows(pl["f1"], pl["ffn"], M, F)
-        self._gemm(pl["ffn"], lay[f + "_fc2"], M, residual=x, ldr=D, out_f32=out, ldo_f32=D)
-
     def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
-        geo = self.geo
-        M, D = pl["M"], geo.hidden
-        states = pl["states"]
-        scale = geo.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
+        M = pl["M"]
         self._fbank(pl, packed_wave)
         self._layernorm(pl["fb"], self.fdim, self.proj_ln, M, self.fdim, out_act=pl["fb_act"])
-        self._gemm(pl["fb_act"], self.proj, M, out_f32=states[0], ldo_f32=D)
-        if self._state_done(0, last_state):
-            return
-        for i, lay in enumerate(self.layers):
-            x = states[i]
-            self._ffn_half(pl, lay, "ffn1", x, pl["r1"])
-            self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_act=pl["xa"])
-            self._gemm(pl["xa"], lay["qkv"], M, out_act=pl["qkv"], col_scale=scale, col_scale_end=D)
-            self._relkey_attention(pl, lay)
-            self._gemm(pl["ctx"], lay["out"], M, residual=pl["r1"], ldr=D, out_f32=pl["r2"], ldo_f32=D)
-            self._layernorm(pl["r2"], D, lay["conv_ln"], M, D, out_act=pl["xa"])
-            self._gemm(pl["xa"], lay["pw1"], M, out_f32=pl["pw"], ldo_f32=2 * D)
-            self._conv_mid(pl, lay)
-            self._gemm(pl["cv"], lay["pw2"], M, residual=pl["r2"], ldr=D, out_f32=pl["r3"], ldo_f32=D)
-            self._ffn_half(pl, lay, "ffn2", pl["r3"], pl["r4"])
-            self._layernorm(pl["r4"], D, lay["final_ln"], M, D, out_f32=states[i + 1])
-            if self._state_done(i + 1, last_state):
-                return
+        self._gemm(pl["fb_act"], self.proj, M, out_f32=pl["states"][0], ldo_f32=self.geo.hidden)
+        if not self._state_done(0, last_state):
+            self._conformer_layers(pl, self._relkey_attention, last_state)
 
     @_on_stream
     def forward(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0,
@@ -4003,13 +4054,13 @@ class W2vBertEncoder(_WaveIO, _EncoderBase):
         return pl["fb"][: int(pl["M"])]
 
 
-class ConformerSpeechEncoder(SpeechEncoder):
+class ConformerSpeechEncoder(_ConformerLayers, SpeechEncoder):
     """The wav2vec2-conformer encoders (HF Wav2Vec2ConformerModel; not in the reference, whose heads take any [T, D] stream) on libserhip:
-    ``SpeechEncoder``'s layer-norm conv stem and feature projection -- hidden_states[0], there is no positional convolution -- and per
-    conformer layer
+    ``SpeechEncoder``'s layer-norm conv stem and feature projection -- hidden_states[0], there is no positional convolution -- and
+    ``_ConformerLayers``' layer
         x += FFN1(LN x) / 2;  x += Attn(LN x);  x += Conv(x);  x += FFN2(LN x) / 2;  x = LN x
-    on ser_layernorm_v, ser_gemm and ser_swish_rows_v as ``W2vBertEncoder`` runs it, with ser_conformer_conv_bn_v (centred window, BatchNorm
-    in eval folded to a per-channel affine at load) between the convolution module's pointwise GEMMs and one of two position schemes
+    with ser_conformer_conv_bn_v (centred window, BatchNorm in eval folded to a per-channel affine at load) in the convolution module, the
+    layers' own LayerNorm eps of 1e-5 (nn.LayerNorm's default, whatever the config says) and one of two position schemes
     (``geo.position_type``, include/ser_hip.h a35):
       "rotary"    ser_rope_rows_v rotates the layer-normed rows; q | k are projected from the rotated planes and v from the plain ones into
                   one packed buffer, then ser_attention_v;
@@ -4018,29 +4069,25 @@ class ConformerSpeechEncoder(SpeechEncoder):
     hidden_states[i < L] is layer i's input, hidden_states[L] = encoder.layer_norm of the last layer's output.  Every utterance alone."""
 
     P_CHUNK = 256            # rows per launch of the P GEMM, and the granule of the distance table's half-length
+    LN_EPS = 1e-5            # the layer's own norms: nn.LayerNorm's default, whatever the config says
 
     def __init__(self, geo: EncoderGeometry, state_dict, device="cuda:0", mode: str = "f16x", normalize: bool = True):
-        from .weights import fold_batch_norm, fold_pos_bias_u, fold_w2v_bert_ffn, rotary_inv_freq
+        from .weights import fold_batch_norm, fold_pos_bias_u, rotary_inv_freq
         _WaveIO.__init__(self, geo, device, mode, post_ln=True)       # the conformer modes are the post-LayerNorm encoders': f16x, fp32x, bf16
         if geo.family != FAMILY_W2V_CONFORMER:
             raise ValueError(f"ConformerSpeechEncoder runs the {FAMILY_W2V_CONFORMER} family")
         self.normalize = bool(normalize)
         sd = state_dict
-        D, H, dh, K = geo.hidden, geo.heads, geo.head_dim, geo.conv_depthwise_kernel
+        H, dh = geo.heads, geo.head_dim
         if geo.position_type not in ("rotary", "relative"):
             raise ValueError(f"position type '{geo.position_type}' is not built (rotary / relative)")
         if geo.feat_extract_norm != "layer":
             raise NotImplementedError("the conformer encoders are built behind the layer-norm conv stem")
-        if dh != 64:
-            raise ValueError(f"the conformer attention is built for heads of 64 (hidden {D} / {H} heads = {dh})")
-        if D % 64 or geo.ffn % 64 or D > 2048:
-            raise ValueError(f"hidden {D} / intermediate {geo.ffn} must be multiples of 64, hidden <= 2048")
-        if not (K & 1) or K > 31:
-            raise ValueError(f"depthwise kernel {K} (odd, <= 31) unsupported")
+        self._check_conformer_geometry("conformer")
         self.relative = geo.position_type == "relative"
         self._init_stem(sd)
         self.enc_ln = self._ln_pair(sd, "encoder.layer_norm")
-        scale = dh ** -0.5 * 1.4426950408889634                        # what the projection's col_scale gives q (exp2-domain softmax)
+        scale = self._q_scale()                                        # what the projection's col_scale gives q
         if not self.relative:
             inv = sd.get("encoder.embed_positions.inv_freq")           # a checkpoint stores HF's buffer; synthetic weights do not
             self.inv_freq = (inv.detach().float().cpu() if inv is not None else rotary_inv_freq(dh, geo.rotary_base))
@@ -4049,16 +4096,8 @@ class ConformerSpeechEncoder(SpeechEncoder):
         self._pe: Dict[int, Act] = {}                                  # half-length of the distance table -> operand planes of its pe rows
         self.layers = []
         for i in range(geo.num_layers):
-            p = f"encoder.layers.{i}"
-            a, c = p + ".self_attn", p + ".conv_module"
-            lay = {}
-            for f in ("ffn1", "ffn2"):
-                lay[f + "_ln"] = self._ln_pair(sd, f"{p}.{f}_layer_norm")
-                lay[f + "_fc1"] = self._linear(sd[f"{p}.{f}.intermediate_dense.weight"], sd[f"{p}.{f}.intermediate_dense.bias"],
-                                               name=f"{p}.{f}.intermediate_dense.weight")
-                lay[f + "_fc2"] = self._linear(*fold_w2v_bert_ffn(sd[f"{p}.{f}.output_dense.weight"], sd[f"{p}.{f}.output_dense.bias"]),
-                                               name=f"{p}.{f}.output_dense.weight")
-            lay["attn_ln"] = self._ln_pair(sd, p + ".self_attn_layer_norm")
+            a, bn = f"encoder.layers.{i}.self_attn", f"encoder.layers.{i}.conv_module.batch_norm"
+            lay = self._conformer_layer_weights(sd, i)
             w = {n: sd[f"{a}.linear_{n}.weight"] for n in "qkv"}
             b = {n: sd[f"{a}.linear_{n}.bias"] for n in "qkv"}
             if self.relative:
@@ -4072,15 +4111,8 @@ class ConformerSpeechEncoder(SpeechEncoder):
             else:
                 lay["qk"] = self._linear(torch.cat([w["q"], w["k"]], 0), torch.cat([b["q"], b["k"]], 0), name=a + ".linear_{q,k}.weight")
                 lay["v"] = self._linear(w["v"], b["v"], name=a + ".linear_v.weight")
-            lay["out"] = self._linear(sd[a + ".linear_out.weight"], sd[a + ".linear_out.bias"], name=a + ".linear_out.weight")
-            lay["conv_ln"] = self._ln_pair(sd, c + ".layer_norm")
-            lay["pw1"] = self._linear(sd[c + ".pointwise_conv1.weight"].reshape(2 * D, D), None, name=c + ".pointwise_conv1.weight")
-            lay["dw"] = self._dev_f32(sd[c + ".depthwise_conv.weight"].reshape(D, K).t())        # [K][D]: a thread's 4 channels are one load
-            bn = c + ".batch_norm"
             lay["bn"] = tuple(self._dev_f32(t) for t in fold_batch_norm(sd[bn + ".weight"], sd[bn + ".bias"], sd[bn + ".running_mean"],
                                                                         sd[bn + ".running_var"], 1e-5))      # nn.BatchNorm1d's own eps
-            lay["pw2"] = self._linear(sd[c + ".pointwise_conv2.weight"].reshape(D, D), None, name=c + ".pointwise_conv2.weight")
-            lay["final_ln"] = self._ln_pair(sd, p + ".final_layer_norm")
             self.layers.append(lay)
         self._arenas = SlotArenas(self._build_arena)
 
@@ -4104,15 +4136,12 @@ class ConformerSpeechEncoder(SpeechEncoder):
         """buffer set of one slot; ``cap``: the stem's rows, frames M, utterances B, longest utterance Tmax (sizes the position tables)"""
         from .weights import rotary_tables
         M, B, geo, dev = cap["M"], cap["B"], self.geo, self.device
-        D, F, H = geo.hidden, geo.ffn, geo.heads
+        D, H = geo.hidden, geo.heads
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         ar = {}
         self._stem_arena(ar, cap)
-        ar["states"] = f32(geo.num_layers + 1, M, D)
-        ar["r1"], ar["r2"], ar["r3"], ar["r4"], ar["last"] = f32(M, D), f32(M, D), f32(M, D), f32(M, D), f32(M, D)
-        ar["f1"], ar["pw"] = f32(M, F), f32(M, 2 * D)
-        ar["xa"], ar["ctx"], ar["cv"] = self._new_act(M, D), self._new_act(M, D), self._new_act(M, D)
-        ar["qkv"], ar["ffn"] = self._new_act(M, 3 * D), self._new_act(M, F)
+        self._conformer_buffers(ar, M)
+        ar["last"] = f32(M, D)
         if self.relative:
             Tp = -(-cap["Tmax"] // self.P_CHUNK) * self.P_CHUNK
             ar["P_T"], ar["pe"], ar["P"] = Tp, self._pe_rows(Tp), f32(2 * Tp, D)
@@ -4146,22 +4175,11 @@ class ConformerSpeechEncoder(SpeechEncoder):
         return pl
 
     # ------------------------------------------------------------------ launches
-    _swish_rows = W2vBertEncoder._swish_rows
-    _ffn_half = W2vBertEncoder._ffn_half
-
-    def _conv_mid(self, pl, lay) -> None:
-        geo, out = self.geo, pl["cv"]
-        a = self._cmd("conformer_conv_bn")
-        a.y, a.ldy, a.w, a.scale, a.shift = pl["pw"].data_ptr(), 2 * geo.hidden, lay["dw"].data_ptr(), lay["bn"][0].data_ptr(), lay["bn"][1].data_ptr()
-        a.frame_offs, a.out_act, a.ldo_act, a.out_plane_stride = pl["frame_offs"].data_ptr(), out.ptr, out.cols, out.plane_stride
-        a.range_flag = self._flag
-        a.B, a.D, a.K, a.max_frames, a.rows, a.mode = pl["B"], geo.hidden, geo.conv_depthwise_kernel, pl["Tmax"], pl["M"], self.mode
-        self._issue(_lib.OP_CONFORMER_CONV_BN, a, "ser_conformer_conv_bn", B=pl["B"], max_frames=pl["Tmax"], rows=pl["M"])
-
     def _rotary_attention(self, pl, lay, scale: float) -> None:
         """LN rows (fp32 ``ln`` + plain planes ``xa``) -> rotated planes -> q | k from them, v from the plain ones -> ser_attention_v"""
         geo = self.geo
         M, D, out = pl["M"], geo.hidden, pl["xr"]
+        self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_f32=pl["ln"], out_act=pl["xa"], eps=self.LN_EPS)
         a = self._cmd("rope_rows")
         a.x, a.ldx, a.cos_t, a.sin_t, a.frame_offs = pl["ln"].data_ptr(), D, pl["cos"].data_ptr(), pl["sin"].data_ptr(), pl["frame_offs"].data_ptr()
         a.out_act, a.ldo_act, a.out_plane_stride, a.range_flag = out.ptr, out.cols, out.plane_stride, self._flag
@@ -4172,10 +4190,12 @@ class ConformerSpeechEncoder(SpeechEncoder):
         self._attention(pl["qkv"], pl["frame_offs"], pl["B"], pl["Tmax"], pl["ctx"])
 
     def _relative_attention(self, pl, lay, scale: float) -> None:
-        """packed projection (q carries pos_bias_u) -> P = linear_pos(pe) -> the positional term per (row, head, key) -> ser_attention_rb_v"""
+        """LN rows -> packed projection (q carries pos_bias_u) -> P = linear_pos(pe) -> the positional term per (row, head, key) ->
+        ser_attention_rb_v"""
         geo = self.geo
         M, D, H, Tp = pl["M"], geo.hidden, geo.heads, pl["P_T"]
-        qkv, out, pe = pl["qkv"], pl["ctx"], pl["pe"]
+        qkv, pe = pl["qkv"], pl["pe"]
+        self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_act=pl["xa"], eps=self.LN_EPS)
         self._gemm(pl["xa"], lay["qkv"], M, out_act=qkv, col_scale=scale, col_scale_end=D)
         for r0 in range(0, 2 * Tp, self.P_CHUNK):
             self._gemm(pe, lay["pos"], self.P_CHUNK, a_ptr_offset=2 * r0 * pe.cols, out_f32=pl["P"][r0: r0 + self.P_CHUNK], ldo_f32=D)
@@ -4184,48 +4204,16 @@ class ConformerSpeechEncoder(SpeechEncoder):
         t.frame_offs, t.pb, t.ld_pb = pl["frame_offs"].data_ptr(), pl["pb"].data_ptr(), pl["ld_pb"]
         t.q_col, t.B, t.H, t.dh, t.P_T, t.max_frames, t.rows, t.mode = 0, pl["B"], H, geo.head_dim, Tp, pl["Tmax"], M, self.mode
         self._issue(_lib.OP_RELPOS_BIAS, t, "ser_relpos_bias", B=pl["B"], max_frames=pl["Tmax"], rows=M)
-        r = self._cmd("attention_rb")
-        a = r.base
-        a.qkv, a.ld, a.plane_stride = qkv.ptr, qkv.cols, qkv.plane_stride
-        a.q_col, a.k_col, a.v_col, a.B = 0, D, 2 * D, pl["B"]
-        a.frame_offs, a.max_frames = pl["frame_offs"].data_ptr(), pl["Tmax"]
-        a.out, a.ldo, a.out_plane_stride = out.ptr, out.cols, out.plane_stride
-        a.H, a.dh, a.scale, a.mode = H, geo.head_dim, -1.0, self.mode          # q is pre-scaled
+        r = self._biased_attention_cmd(pl, "attention_rb")
         r.pb, r.ld_pb = pl["pb"].data_ptr(), pl["ld_pb"]
-        if self._rec is not None:                                               # the per-batch sizes live in the embedded base struct
-            self._rec.patches += [(a, "B", "B"), (a, "max_frames", "Tmax")]
         self._issue(_lib.OP_ATTENTION_RB, r, "ser_attention_rb")
 
     def _launches(self, pl, packed_wave: torch.Tensor, last_state: Optional[int] = None) -> None:
-        geo = self.geo
-        M, D, L = pl["M"], geo.hidden, geo.num_layers
-        states = pl["states"]
-        scale = geo.head_dim ** -0.5 * 1.4426950408889634          # q leaves multiplied by dh^-0.5 * log2(e) (exp2-domain softmax)
-        eps = 1e-5                                                  # the layer's own norms: nn.LayerNorm's default, whatever the config says
         self._conv_stack(pl, packed_wave)
-        self._gemm(pl["feat_act"], self.proj, M, out_f32=states[0], ldo_f32=D, stem=True)
-        if self._state_done(0, last_state):
-            return
-        for i, lay in enumerate(self.layers):
-            last = i + 1 == L
-            self._ffn_half(pl, lay, "ffn1", states[i], pl["r1"], eps=eps)
-            if self.relative:
-                self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_act=pl["xa"], eps=eps)
-                self._relative_attention(pl, lay, scale)
-            else:
-                self._layernorm(pl["r1"], D, lay["attn_ln"], M, D, out_f32=pl["ln"], out_act=pl["xa"], eps=eps)
-                self._rotary_attention(pl, lay, scale)
-            self._gemm(pl["ctx"], lay["out"], M, residual=pl["r1"], ldr=D, out_f32=pl["r2"], ldo_f32=D)
-            self._layernorm(pl["r2"], D, lay["conv_ln"], M, D, out_act=pl["xa"], eps=eps)
-            self._gemm(pl["xa"], lay["pw1"], M, out_f32=pl["pw"], ldo_f32=2 * D)
-            self._conv_mid(pl, lay)
-            self._gemm(pl["cv"], lay["pw2"], M, residual=pl["r2"], ldr=D, out_f32=pl["r3"], ldo_f32=D)
-            self._ffn_half(pl, lay, "ffn2", pl["r3"], pl["r4"], eps=eps)
-            self._layernorm(pl["r4"], D, lay["final_ln"], M, D, out_f32=pl["last"] if last else states[i + 1], eps=eps)
-            if last:
-                self._layernorm(pl["last"], D, self.enc_ln, M, D, out_f32=states[L])
-            if self._state_done(i + 1, last_state):
-                return
+        self._gemm(pl["feat_act"], self.proj, pl["M"], out_f32=pl["states"][0], ldo_f32=self.geo.hidden, stem=True)
+        if not self._state_done(0, last_state):
+            self._conformer_layers(pl, self._relative_attention if self.relative else self._rotary_attention, last_state,
+                                   eps=self.LN_EPS, enc_ln=self.enc_ln)
 
     @_on_stream
     def forward(self, packed_wave: torch.Tensor, lengths: Sequence[int], slot: int = 0,

@@ -35,6 +35,17 @@ CASES = (("tiny_w2v_conformer_rope", "TINY_W2V_CONFORMER_ROPE"), ("tiny_w2v_conf
 # sha256 of ser_conformer_conv_v's output planes (D 128, K 7, f16x, frames (1, 2, 30, 31, 37, 5), conv_inputs seed 135) from the library
 # built at the commit before this family was added: the kernel keeps its bits
 PARENT_CONV_DIGEST = "e4633d2d87787c8e4947bfc24e147e7188ba63f33497f531dd03f84e4ba24c9a"
+# sha256 of output planes from the library built at the commit before the two conformer families were put on one convolution body and one
+# biased-attention launcher: the kernels keep their bits.
+# ser_conformer_conv_bn_v: D 1280 (the second 1024-column slab partly filled), K 31, frames (1, 8, 9, 37) -- a window longer than the
+# utterance, one SER_CCONV_TILE, a tile plus one row, several tiles -- conv_inputs seed 1311
+PARENT_CONV_BN_1280_DIGESTS = {
+    "bf16": "4b8ece3a9763d05bb580de28f6214c273c9166dfbc584c5c6bf34f54aa5bdb56",
+    "fp32x": "8d8bd1912765ade4bb8a7d3e8541f3ff2526676b282707e847557966f132da71",
+    "f16x": "e07efacc5a67c9758112c17922794693e8e2c8ddf7f9adeddd302035a04ae528",
+}
+# ser_relpos_bias_v + ser_attention_rb_v: H 3, frames (1, 33, 99, 130), P_T 256, f16x, attention_rb_inputs seed 300
+PARENT_ATTENTION_RB_DIGEST = "d6302030b3e033ea6a8018cfd2d757a4757ed9f7630f3ae56b5689e25a77922c"
 
 
 @pytest.fixture(scope="module")
@@ -94,6 +105,10 @@ def act_value(t):
 
 def _bits(t):
     return t.detach().cpu().contiguous().view(torch.int32) if t.dtype == torch.float32 else t.detach().cpu().contiguous().view(torch.int16)
+
+
+def planes_digest(t):
+    return hashlib.sha256(_bits(t).numpy().tobytes()).hexdigest()
 
 
 def offsets(frames):
@@ -208,7 +223,7 @@ def run_conv_bn(L, y, w, scale, shift, frames, mode):
 
 
 @pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
-@pytest.mark.parametrize("D,K", [(128, 3), (128, 31), (192, 3), (192, 31)])
+@pytest.mark.parametrize("D,K", [(128, 3), (128, 31), (192, 3), (192, 31), (1280, 7)])
 def test_conformer_conv_bn(L, D, K, mode):
     m = MODES[mode]
     frames = list(CONV_FRAMES)
@@ -232,6 +247,16 @@ def test_conformer_conv_bn(L, D, K, mode):
         alone, _ = run_conv_bn(L, y[offs[b]: offs[b + 1]].contiguous(), w, scale, shift, [frames[b]], m)
         assert torch.equal(_bits(out2[:, offs[b]: offs[b + 1]]), _bits(alone)), (b, "poisoned neighbour")
         assert torch.equal(_bits(out[:, offs[b]: offs[b + 1]]), _bits(alone)), (b, "batch of one")
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
+def test_conformer_conv_bn_keeps_its_bits_in_the_second_slab(L, mode):
+    D, K, frames = 1280, 31, [1, 8, 9, 37]
+    y, w, scale, shift = conv_inputs(D, K, sum(frames), D + K)
+    out, bits = run_conv_bn(L, y, w, scale, shift, frames, MODES[mode])
+    digest = planes_digest(out)
+    print(f"W2VCONF ser_conformer_conv_bn_v D={D} K={K} {mode} digest {digest}")
+    assert bits == 0 and digest == PARENT_CONV_BN_1280_DIGESTS[mode]
 
 
 def test_conformer_conv_keeps_its_bits(L):
@@ -294,22 +319,29 @@ def run_attention_rb(L, qa, P, off, Ts, H, mode, plain=False, P_T=None):
     return out.cpu(), pb
 
 
+def attention_rb_inputs(H, M, P_T, mode):
+    """operand planes of the packed q | k | v (q + u as the projection's epilogue leaves it: times c), the distance table P (row P_T + r =
+    P(r)), off = (v - u) c, the two position biases and c"""
+    dh, D = 64, H * 64
+    g = torch.Generator().manual_seed(100 * H)
+    c = dh ** -0.5 * 1.4426950408889634
+    qkv = torch.randn(M, 3 * D, generator=g)
+    qkv[:, : 2 * D] *= 1.5
+    P = torch.randn(2 * P_T, D, generator=g) * 0.7
+    u, v = torch.randn(H, dh, generator=g) * 0.5, torch.randn(H, dh, generator=g) * 0.5
+    pre = qkv.clone()
+    pre[:, :D] = (pre[:, :D] + u.reshape(-1)) * c
+    off = ((v.double() - u.double()) * c).reshape(-1).float()
+    return to_act(pre, mode), P, off, u, v, c
+
+
 @pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
 @pytest.mark.parametrize("H", [2, 3])
 def test_relpos_bias_and_attention_rb(L, H, mode):
     m = MODES[mode]
     dh, D, Ts = 64, H * 64, list(ATTN_TS)
     M, P_T = sum(Ts), 256
-    g = torch.Generator().manual_seed(100 * H)
-    c = dh ** -0.5 * 1.4426950408889634
-    qkv = torch.randn(M, 3 * D, generator=g)
-    qkv[:, : 2 * D] *= 1.5
-    P = torch.randn(2 * P_T, D, generator=g) * 0.7                                    # row P_T + r = P(r)
-    u, v = torch.randn(H, dh, generator=g) * 0.5, torch.randn(H, dh, generator=g) * 0.5
-    pre = qkv.clone()
-    pre[:, :D] = (pre[:, :D] + u.reshape(-1)) * c                                     # q + u as the projection's epilogue leaves it
-    off = ((v.double() - u.double()) * c).reshape(-1).float()
-    qa = to_act(pre, m)
+    qa, P, off, u, v, c = attention_rb_inputs(H, M, P_T, m)
     qv = act_value(qa.cpu())
     offs = offsets(Ts)
     ref = torch.empty(M, D, dtype=torch.float64)
@@ -345,6 +377,15 @@ def test_relpos_bias_and_attention_rb(L, H, mode):
         alone, pb1 = run_attention_rb(L, qa[:, offs[b]: offs[b + 1]].contiguous(), P2, off, [T], H, m, P_T=512)
         assert torch.equal(_bits(alone), _bits(out[:, offs[b]: offs[b + 1]])), (b, "batch of one")
         assert torch.equal(_bits(pb1[:, : -(-T // 64) * 64]), _bits(pb[offs[b] * H: offs[b + 1] * H, : -(-T // 64) * 64]))
+
+
+def test_attention_rb_keeps_its_bits(L):
+    H, Ts, P_T = 3, list(ATTN_TS), 256
+    qa, P, off, _, _, _ = attention_rb_inputs(H, sum(Ts), P_T, FP16X)
+    out, _ = run_attention_rb(L, qa, P, off, Ts, H, FP16X, P_T=P_T)
+    digest = planes_digest(out)
+    print(f"W2VCONF ser_attention_rb_v H={H} f16x digest {digest}")
+    assert digest == PARENT_ATTENTION_RB_DIGEST
 
 
 # --------------------------------------------------------------------------------------------------------------------- end to end

@@ -18,6 +18,7 @@ Bounds.
 
 Measured on an MI355X: profiles/w2v_bert.txt.
 """
+import hashlib
 import json
 import math
 import os
@@ -35,6 +36,17 @@ BF16, FP32X, FP16X = 1, 2, 4
 MODES = {"bf16": BF16, "fp32x": FP32X, "f16x": FP16X}
 E2E_TOL = {"f16x": 1e-3, "fp32x": 1e-3, "bf16": 3e-2}
 CASES = (("tiny_w2v_bert_d128h2", "TINY_W2V_BERT"), ("tiny_w2v_bert_d192h3", "TINY_W2V_BERT_H3"))
+# sha256 of output planes from the library built at the commit before the two conformer families were put on one convolution body and one
+# biased-attention launcher: the kernels keep their bits.
+# ser_conformer_conv_v: D 1280 (the second 1024-column slab partly filled), K 31, frames (1, 8, 9, 37) -- a window longer than the
+# utterance, one SER_CCONV_TILE, a tile plus one row, several tiles -- conv_inputs seed 1311
+PARENT_CONV_1280_DIGESTS = {
+    "bf16": "d1d9aea5549f543156b95e4422650c34a46a8c724e00e72cc9ce999566421f71",
+    "fp32x": "98f1cfc1eb37aedc9c4a6f458204ee9d71aa25f10127a0bc7cef4332de27b3d9",
+    "f16x": "c1327ff3c990bc9d65a5012745be3a8ca2056fa93304fbce84b7af802813a388",
+}
+# ser_relkey_table_v + ser_attention_rk_v: H 3, left_max 64, right_max 8, frames (1, 33, 99, 130), f16x, attention_rk_inputs seed 364
+PARENT_ATTENTION_RK_DIGEST = "53330386ef15f2e9e6080c27d08ef8cff45152e1406cbe30e2603b48dc4e6302"
 
 
 @pytest.fixture(scope="module")
@@ -92,6 +104,10 @@ def act_value(t):
 
 def _bits(t):
     return t.detach().cpu().contiguous().view(torch.int32) if t.dtype == torch.float32 else t.detach().cpu().contiguous().view(torch.int16)
+
+
+def planes_digest(t):
+    return hashlib.sha256(_bits(t).numpy().tobytes()).hexdigest()
 
 
 # --------------------------------------------------------------------------------------------------------------------------- fbank
@@ -191,7 +207,7 @@ def conv_inputs(D, K, M, seed):
 
 
 @pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
-@pytest.mark.parametrize("D,K", [(128, 7), (128, 31), (1024, 7), (1024, 31)])
+@pytest.mark.parametrize("D,K", [(128, 7), (128, 31), (1024, 7), (1024, 31), (1280, 7)])
 def test_conformer_conv(L, D, K, mode):
     m = MODES[mode]
     frames = list(CONV_FRAMES)
@@ -213,6 +229,16 @@ def test_conformer_conv(L, D, K, mode):
         alone, _ = run_conv(L, y[offs[b]: offs[b + 1]].contiguous(), w, gamma, beta, [frames[b]], m)
         assert torch.equal(_bits(out2[:, offs[b]: offs[b + 1]]), _bits(alone)), (b, "poisoned neighbour")
         assert torch.equal(_bits(out[:, offs[b]: offs[b + 1]]), _bits(alone)), (b, "batch of one")
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
+def test_conformer_conv_keeps_its_bits_in_the_second_slab(L, mode):
+    D, K, frames = 1280, 31, [1, 8, 9, 37]
+    y, w, gamma, beta = conv_inputs(D, K, sum(frames), D + K)
+    out, bits = run_conv(L, y, w, gamma, beta, frames, MODES[mode])
+    digest = planes_digest(out)
+    print(f"W2VBERT ser_conformer_conv_v D={D} K={K} {mode} digest {digest}")
+    assert bits == 0 and digest == PARENT_CONV_1280_DIGESTS[mode]
 
 
 def test_conformer_conv_reports_the_fp16_range(L):
@@ -281,20 +307,26 @@ def run_attention_rk(L, qa, E, Ts, H, Lm, Rm, mode, plain=False):
     return out.cpu()
 
 
-@pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
-@pytest.mark.parametrize("H,Lm,Rm", [(2, 64, 8), (3, 64, 8), (2, 5, 3), (3, 5, 3)])
-def test_attention_rk(L, H, Lm, Rm, mode):
-    m = MODES[mode]
-    dh, D, Ts = 64, H * 64, list(ATTN_TS)
-    M = sum(Ts)
+def attention_rk_inputs(H, Lm, Rm, M, mode):
+    """operand planes of the packed q | k | v (q as the projection's epilogue leaves it: times c), the distance embedding E, and c"""
+    dh, D = 64, H * 64
     g = torch.Generator().manual_seed(100 * H + Lm)
     c = dh ** -0.5 * 1.4426950408889634
     qkv = torch.randn(M, 3 * D, generator=g)
     qkv[:, : 2 * D] *= 1.5
     E = torch.randn(Lm + Rm + 1, dh, generator=g) * 0.5
     pre = qkv.clone()
-    pre[:, :D] *= c                                                          # q as the projection's epilogue leaves it
-    qa = to_act(pre, m)
+    pre[:, :D] *= c
+    return to_act(pre, mode), E, c
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp32x", "f16x"])
+@pytest.mark.parametrize("H,Lm,Rm", [(2, 64, 8), (3, 64, 8), (2, 5, 3), (3, 5, 3)])
+def test_attention_rk(L, H, Lm, Rm, mode):
+    m = MODES[mode]
+    dh, D, Ts = 64, H * 64, list(ATTN_TS)
+    M = sum(Ts)
+    qa, E, c = attention_rk_inputs(H, Lm, Rm, M, m)
     qv = act_value(qa.cpu())
     offs = np.concatenate([[0], np.cumsum(Ts)])
     ref = torch.empty(M, D, dtype=torch.float64)
@@ -313,6 +345,14 @@ def test_attention_rk(L, H, Lm, Rm, mode):
     zero = run_attention_rk(L, qa, torch.zeros_like(E), Ts, H, Lm, Rm, m)
     plain = run_attention_rk(L, qa, None, Ts, H, Lm, Rm, m, plain=True)
     assert torch.equal(_bits(zero), _bits(plain))
+
+
+def test_attention_rk_keeps_its_bits(L):
+    H, Lm, Rm, Ts = 3, 64, 8, [1, 33, 99, 130]
+    qa, E, _ = attention_rk_inputs(H, Lm, Rm, sum(Ts), FP16X)
+    digest = planes_digest(run_attention_rk(L, qa, E, Ts, H, Lm, Rm, FP16X))
+    print(f"W2VBERT ser_attention_rk_v H={H} Lm={Lm} Rm={Rm} f16x digest {digest}")
+    assert digest == PARENT_ATTENTION_RK_DIGEST
 
 
 # --------------------------------------------------------------------------------------------------------------------- end to end
