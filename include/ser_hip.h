@@ -1425,6 +1425,47 @@ typedef struct ser_dec_select_ts_args {
 } ser_dec_select_ts_args;
 int ser_dec_select_ts_v(const ser_dec_select_ts_args* args, void* stream);
 
+/* a37 (added under ABI 18: two new entry points, two ser_cmd members and two SER_OP codes only; ser_logmel_whisper and every struct above are
+ * what they were)  Whisper long-form features: HF's generate() on input longer than 30 s reads features of the WHOLE file
+ * (WhisperFeatureExtractor(truncation=False)), and a window of its seek loop is a slice of them.
+ *
+ * ser_logmel_long_v (SER_OP_LOGMEL_LONG): B ragged files, packed fp32 samples wav with sample_offs [B + 1] (int64, device; the host's copy
+ * sample_offs_host is what the launcher validates on).  With len_b the file's samples, F_b = len_b / 160 frames (the STFT has 1 + len_b / 160;
+ * the last is dropped) and pitch_b = F_b rounded up to 4:
+ *   p[i]      = x[reflect(i - 200)] about the file's OWN first and last sample
+ *   raw[m, t] = log10(max(sum_k mel[k, m] |DFT_400(p[160 t .. 160 t + 399] hann)[k]|^2, 1e-10)),  t < F_b     (the guard's logarithm is the
+ *               constant -10, as in ser_logmel_whisper: silence is exactly -1.5 after the scaling)
+ *   out[bases[b] + m pitch_b + t] = (max(raw[m, t], max_{m, t < F_b} raw - 8) + 4) / 4
+ * fp32 [n_mels][pitch_b] at the float offset bases[b] (int64, device, a multiple of 4) of `out` (16-byte aligned).  Columns F_b .. pitch_b - 1
+ * are written too (a finite value: the image of a zero frame) and are in no maximum; nothing outside [n_mels][pitch_b] is written.
+ * ser_logmel_whisper's fp64-MFMA DFT tile over 32 frames; the grid is the tile table `tiles` [n_tiles][2] (int32, device) of (file, first frame),
+ * every file's tiles contiguous and ascending; `files` [B][4] (int32, device) = F_b, pitch_b, the file's first tile, its tile count.  A tile
+ * writes its maximum into its own slot of `scratch` (fp32 [n_tiles + B]: no atomics, no reset), a second kernel reduces a file's slots, a third
+ * scales in place: a file gives the same bits alone and in any batch.  `table`: a buffer ser_logmel_init has filled (twiddles and Hann).
+ * Refused before any launch: a null pointer, B <= 0, n_mels <= 0, a file under 201 samples (numpy's reflect pad is undefined there), n_tiles or
+ * max_pitch that are not what the host's offsets give. */
+typedef struct ser_logmel_long_args {
+    const float* wav; const int64_t* sample_offs; const int64_t* sample_offs_host;
+    const float* mel;
+    float* out; const int64_t* bases;
+    const int32_t* tiles; const int32_t* files;
+    const void* table; float* scratch;
+    int32_t B, n_mels, n_tiles, max_pitch;
+} ser_logmel_long_args;
+int ser_logmel_long_v(const ser_logmel_long_args* args, void* stream);
+
+/* ser_mel_window_v (SER_OP_MEL_WINDOW): the [B, n_mels, 3000] input features of B windows, gathered from ser_logmel_long_v's output `src`.
+ * rows [B][5] (int64, device; rows_host: the host's copy, validated by the launcher) = base, pitch, F, seek, nf of each row:
+ *   out[b, m, t] = src[base + m pitch + seek + t]   t < nf;      +0.0f   nf <= t < 3000          (HF's _get_input_segment)
+ * Bit copies; seek need not be a multiple of 4.  Refused before any launch: nf outside 1 .. 3000, seek < 0, seek + nf > F, pitch < F. */
+typedef struct ser_mel_window_args {
+    const float* src;
+    const int64_t* rows; const int64_t* rows_host;
+    float* out;
+    int32_t B, n_mels;
+} ser_mel_window_args;
+int ser_mel_window_v(const ser_mel_window_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -1456,6 +1497,8 @@ int ser_dec_select_ts_v(const ser_dec_select_ts_args* args, void* stream);
 #define SER_OP_RELPOS_BIAS 29
 #define SER_OP_ATTENTION_RB 30
 #define SER_OP_DEC_SELECT_TS 31
+#define SER_OP_LOGMEL_LONG 32
+#define SER_OP_MEL_WINDOW 33
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -1490,6 +1533,8 @@ typedef struct ser_cmd {
         ser_relpos_bias_args relpos_bias;
         ser_attention_rb_args attention_rb;
         ser_dec_select_ts_args dec_select_ts;
+        ser_logmel_long_args logmel_long;
+        ser_mel_window_args  mel_window;
     } u;
 } ser_cmd;
 

@@ -402,6 +402,18 @@ class DecSelectTsArgs(C.Structure):
                 ("ts_begin", C.c_int32), ("no_ts", C.c_int32), ("begin_index", C.c_int32), ("max_initial", C.c_int32)]
 
 
+class LogmelLongArgs(C.Structure):
+    """Mirror of ``ser_logmel_long_args``."""
+    _fields_ = [("wav", c_void_p), ("sample_offs", c_void_p), ("sample_offs_host", c_void_p), ("mel", c_void_p),
+                ("out", c_void_p), ("bases", c_void_p), ("tiles", c_void_p), ("files", c_void_p), ("table", c_void_p), ("scratch", c_void_p),
+                ("B", C.c_int32), ("n_mels", C.c_int32), ("n_tiles", C.c_int32), ("max_pitch", C.c_int32)]
+
+
+class MelWindowArgs(C.Structure):
+    """Mirror of ``ser_mel_window_args``."""
+    _fields_ = [("src", c_void_p), ("rows", c_void_p), ("rows_host", c_void_p), ("out", c_void_p), ("B", C.c_int32), ("n_mels", C.c_int32)]
+
+
 class ProsodyMelArgs(C.Structure):
     """Mirror of ``ser_prosody_mel_args``."""
     _fields_ = [
@@ -576,7 +588,8 @@ class _CmdUnion(C.Union):
                 ("conformer_conv", ConformerConvArgs), ("swish_rows", SwishRowsArgs), ("dec_keep_q", DecKeepQArgs),
                 ("dec_attn_beam", DecAttnBeamArgs), ("beam_select", BeamSelectArgs),
                 ("rope_rows", RopeRowsArgs), ("conformer_conv_bn", ConformerConvBnArgs), ("relpos_bias", RelposBiasArgs),
-                ("attention_rb", AttentionRbArgs), ("dec_select_ts", DecSelectTsArgs)]
+                ("attention_rb", AttentionRbArgs), ("dec_select_ts", DecSelectTsArgs),
+                ("logmel_long", LogmelLongArgs), ("mel_window", MelWindowArgs)]
 
 
 class Cmd(C.Structure):
@@ -593,6 +606,7 @@ OP_DEC_KEEP_Q = 24
 OP_DEC_ATTN_BEAM, OP_BEAM_SELECT = 25, 26
 OP_ROPE_ROWS, OP_CONFORMER_CONV_BN, OP_RELPOS_BIAS, OP_ATTENTION_RB = 27, 28, 29, 30
 OP_DEC_SELECT_TS = 31
+OP_LOGMEL_LONG, OP_MEL_WINDOW = 32, 33
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -610,6 +624,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_rope_rows_args": RopeRowsArgs, "ser_conformer_conv_bn_args": ConformerConvBnArgs,
                   "ser_relpos_bias_args": RelposBiasArgs, "ser_attention_rb_args": AttentionRbArgs,
                   "ser_dec_select_ts_args": DecSelectTsArgs,
+                  "ser_logmel_long_args": LogmelLongArgs, "ser_mel_window_args": MelWindowArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -675,6 +690,8 @@ _SIGNATURES = {
     "ser_relpos_bias_v": (c_int, [c_void_p, c_void_p]),
     "ser_attention_rb_v": (c_int, [c_void_p, c_void_p]),
     "ser_dec_select_ts_v": (c_int, [c_void_p, c_void_p]),
+    "ser_logmel_long_v": (c_int, [c_void_p, c_void_p]),
+    "ser_mel_window_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -159,6 +159,14 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_dec_select_ts_v(&c.u.dec_select_ts, stream);
                 break;
             }
+            case SER_OP_LOGMEL_LONG: {
+                rc = ser_logmel_long_v(&c.u.logmel_long, stream);
+                break;
+            }
+            case SER_OP_MEL_WINDOW: {
+                rc = ser_mel_window_v(&c.u.mel_window, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

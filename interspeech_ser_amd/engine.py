@@ -1451,6 +1451,85 @@ class SpeechEncoder(_WaveIO, _EncoderBase):
                 return
 
 
+class LongMel:
+    """Whole-file Whisper features on the device (``WhisperEncoder.log_mel_long``): one grow-only fp32 buffer that holds every resident
+    file's ``[n_mels][pitch]`` rows at ``bases[file]`` (float offsets, multiples of 4), with ``pitches[file]`` = the frame count rounded
+    up to 4 and ``frames[file]`` = len // 160.  File indices are handed out in order and never reused; ``release(file)`` returns a file's
+    span to a first-fit free list.  A buffer that runs out of room is succeeded by a larger one (the resident rows are copied on the
+    stream), so ``buf`` may change between calls: launches take its address when they are issued."""
+
+    HOP = 160
+
+    def __init__(self, n_mels: int, device):
+        self.n_mels, self.device = int(n_mels), device
+        self.buf = torch.empty(0, dtype=torch.float32, device=device)
+        self.top = 0
+        self.bases: List[Optional[int]] = []
+        self.pitches: List[int] = []
+        self.frames: List[int] = []
+        self.lengths: List[int] = []
+        self._free: List[List[int]] = []                    # [offset, floats], ascending offsets
+
+    def __len__(self) -> int:
+        return len(self.bases)
+
+    def _take(self, size: int) -> int:
+        for k, (o, n) in enumerate(self._free):
+            if n >= size:
+                if n == size:
+                    self._free.pop(k)
+                else:
+                    self._free[k] = [o + size, n - size]
+                return o
+        o = self.top
+        if o + size > self.buf.numel():
+            grown = torch.empty(max(2 * self.buf.numel(), o + size), dtype=torch.float32, device=self.device)
+            grown[:o].copy_(self.buf[:o])
+            self.buf = grown
+        self.top = o + size
+        return o
+
+    def add(self, length: int) -> int:
+        F = int(length) // self.HOP
+        pitch = (F + 3) // 4 * 4
+        self.bases.append(self._take(self.n_mels * pitch))
+        self.pitches.append(pitch)
+        self.frames.append(F)
+        self.lengths.append(int(length))
+        return len(self.bases) - 1
+
+    def release(self, file: int) -> None:
+        base = self.bases[file]
+        if base is None:
+            raise ValueError(f"file {file} was released before")
+        self.bases[file] = None
+        self._free.append([base, self.n_mels * self.pitches[file]])
+        self._free.sort()
+        merged: List[List[int]] = []
+        for o, n in self._free:
+            if merged and merged[-1][0] + merged[-1][1] == o:
+                merged[-1][1] += n
+            else:
+                merged.append([o, n])
+        if merged and merged[-1][0] + merged[-1][1] == self.top:
+            self.top = merged.pop()[0]
+        self._free = merged
+
+    def features(self, file: int) -> torch.Tensor:
+        """[n_mels, F] view of one resident file"""
+        base, pitch = self.bases[file], self.pitches[file]
+        return self.buf[base: base + self.n_mels * pitch].view(self.n_mels, pitch)[:, : self.frames[file]]
+
+    def row_table(self, rows) -> np.ndarray:
+        """int64 [B][5] = base, pitch, F, seek, nf: ser_mel_window_v's row table for ``rows`` = [(file, seek, nf)]"""
+        t = np.zeros((len(rows), 5), dtype=np.int64)
+        for b, (f, seek, nf) in enumerate(rows):
+            if not 0 <= f < len(self.bases) or self.bases[f] is None:
+                raise ValueError(f"row {b}: file {f} is not resident")
+            t[b] = (self.bases[f], self.pitches[f], self.frames[f], int(seek), int(nf))
+        return t
+
+
 class WhisperEncoder(_WaveIO, _EncoderBase):
     """Whisper encoder (log-mel front end + stem convs + pre-LN layers) on libserhip."""
 
@@ -1482,16 +1561,20 @@ class WhisperEncoder(_WaveIO, _EncoderBase):
         """Every Whisper shape is a function of B alone (30 s windows), so buffers are keyed by (slot, B) and a new
         batch only uploads its B+1 sample offsets."""
         lengths = tuple(int(n) for n in lengths)
-        pl = self._cache.pop((slot, len(lengths)), None)
-        if pl is None:
-            pl = self._build_plan(len(lengths), slot)
-        else:
-            self._cache[(slot, len(lengths))] = pl      # re-insert: the dict is kept in least-recently-USED order, the hot
-            #                                             full-batch plans of the pipeline slots are never the ones evicted
+        pl = self._plan_of(len(lengths), slot)
         if pl["lengths"] != lengths:
             pl["sample_offs"] = pl["tab"].begin().put64(np.concatenate([[0], np.cumsum(lengths)]))
             pl["tab"].send()
             pl["lengths"] = lengths
+        return pl
+
+    def _plan_of(self, B: int, slot: int):
+        """the (slot, B) plan, built on a miss; its sample offsets are ``_plan``'s business"""
+        pl = self._cache.pop((slot, B), None)
+        if pl is None:
+            return self._build_plan(B, slot)
+        self._cache[(slot, B)] = pl                     # re-insert: the dict is kept in least-recently-USED order, the hot
+        #                                                 full-batch plans of the pipeline slots are never the ones evicted
         return pl
 
     def _build_plan(self, B: int, slot: int):
@@ -1565,6 +1648,96 @@ class WhisperEncoder(_WaveIO, _EncoderBase):
         flag = self._guard_word(pl)
         self._encoder_launches(pl, input_features)
         return HiddenStates(pl["states"], pl["frame_offs_host"], range_flag=flag)
+
+    # ------------------------------------------------------------------ long-form: whole-file features and windows of them (a37)
+    def _build_long(self, cap: Dict[str, int]) -> dict:
+        """tables and scratch of one ser_logmel_long_v launch: sample offsets [B + 1], bases [B] (int64), files [B][4], tiles [tiles][2] (int32)"""
+        B, tiles = cap["B"], cap["tiles"]
+        words = (B + 1) + B + 2 * B + tiles
+        return dict(pin=Pinned(words, torch.int64), dev=torch.empty(words, dtype=torch.int64, device=self.device),
+                    scratch=torch.empty(tiles + B, dtype=torch.float32, device=self.device))
+
+    @_on_stream
+    def log_mel_long(self, packed_wave: torch.Tensor, lengths: Sequence[int], into: Optional[LongMel] = None) -> LongMel:
+        """HF's long-form input features (``WhisperFeatureExtractor(truncation=False)``) of B ragged files in one ser_logmel_long_v launch:
+        one reflect pad at each file's own ends, len // 160 frames, one max - 8 floor per FILE.  Returns the handle (``LongMel``) that
+        holds the device buffer, the bases, the pitches and the frame counts; ``into``: a handle to add the files to (the window queue
+        admits files while others are resident) -- their indices are ``len(into)`` onwards."""
+        lengths = [int(n) for n in lengths]
+        B = len(lengths)
+        if B < 1 or packed_wave.numel() != sum(lengths):
+            raise ValueError("log_mel_long: one length per file, and the packed samples of exactly these files")
+        for n in lengths:
+            if n < 201:
+                raise ValueError(f"log_mel_long: a file of {n} samples (the reflect pad of 200 needs at least 201)")
+        h = into if into is not None else LongMel(self.geo.n_mels, self.device)
+        if getattr(self, "_long_arenas", None) is None:
+            self._long_arenas = SlotArenas(self._build_long)
+            ws = lib.ser_workspace_bytes(_lib.WS_LOGMEL, 1, 0, 0, 0, self.stem_mode)
+            self._long_table = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            check(lib.ser_logmel_init(self._long_table.data_ptr(), 1, self._s()), "ser_logmel_init")
+        first = len(h)
+        files = [h.add(n) for n in lengths]
+        F = [h.frames[f] for f in files]
+        counts = [(f + 31) // 32 for f in F]
+        n_tiles = int(sum(counts))
+        ar = self._long_arenas.fit(0, B=B, tiles=n_tiles)
+        pin, dev = ar["pin"], ar["dev"]
+        pin.wait()
+        host = pin.host.numpy()
+        o_offs, o_bases, o_files, o_tiles = 0, B + 1, 2 * B + 1, 4 * B + 1
+        host[o_offs: o_offs + B + 1] = np.concatenate([[0], np.cumsum(lengths)])
+        host[o_bases: o_bases + B] = [h.bases[f] for f in files]
+        ft = np.zeros((B, 4), dtype=np.int32)
+        ft[:, 0], ft[:, 1], ft[:, 3] = F, [h.pitches[f] for f in files], counts
+        ft[:, 2] = np.concatenate([[0], np.cumsum(counts)[:-1]])
+        host[o_files: o_files + 2 * B].view(np.int32)[:] = ft.reshape(-1)
+        tt = np.empty((n_tiles, 2), dtype=np.int32)
+        tt[:, 0] = np.repeat(np.arange(B, dtype=np.int32), counts)
+        tt[:, 1] = np.concatenate([np.arange(c, dtype=np.int32) * 32 for c in counts])
+        host[o_tiles: o_tiles + n_tiles].view(np.int32)[:] = tt.reshape(-1)
+        used = o_tiles + n_tiles
+        dev[:used].copy_(pin.host[:used], non_blocking=True)
+        pin.sent()
+        a = self._cmd("logmel_long")
+        a.wav, a.sample_offs, a.sample_offs_host = packed_wave.data_ptr(), dev.data_ptr() + 8 * o_offs, pin.host.data_ptr() + 8 * o_offs
+        a.mel, a.out, a.bases = self.mel.data_ptr(), h.buf.data_ptr(), dev.data_ptr() + 8 * o_bases
+        a.files, a.tiles = dev.data_ptr() + 8 * o_files, dev.data_ptr() + 8 * o_tiles
+        a.table, a.scratch = self._long_table.data_ptr(), ar["scratch"].data_ptr()
+        a.B, a.n_mels, a.n_tiles, a.max_pitch = B, self.geo.n_mels, n_tiles, max(h.pitches[f] for f in files)
+        self._issue(_lib.OP_LOGMEL_LONG, a, "ser_logmel_long_v")
+        assert files[0] == first
+        return h
+
+    def _mel_window(self, pl, win) -> None:
+        a = self._cmd("mel_window")
+        a.src, a.rows, a.rows_host, a.out = win["src"], win["rows"].data_ptr(), win["tab"].host.data_ptr(), pl["mel"].data_ptr()
+        a.B, a.n_mels = pl["B"], self.geo.n_mels
+        self._issue(_lib.OP_MEL_WINDOW, a, "ser_mel_window_v", input="src")
+
+    @_on_stream
+    def forward_windows(self, handle: LongMel, rows: Sequence[tuple], slot: int = 0, last_state: Optional[int] = None) -> HiddenStates:
+        """The encoder over B windows of resident files: ``rows`` = [(file, seek, nf)], window b = the file's features at
+        [seek, seek + nf) followed by 3000 - nf columns of 0.0 (HF's ``_get_input_segment``).  One command list per (slot, B) -- the gather
+        into the plan's ``mel``, then ``forward``'s encoder launches -- recorded once and replayed like ``forward``'s; from window to window
+        only the row table (and, after the handle grew, its buffer's address) changes."""
+        B = len(rows)
+        pl = self._plan_of(B, slot)
+        win = pl.get("win")
+        if win is None:
+            win = pl["win"] = dict(tab=TableBlob(5 * B, 1, self.device))
+        win["rows"] = win["tab"].begin().put64(handle.row_table(rows).reshape(-1))
+        win["tab"].send()
+        win["src"] = handle.buf.data_ptr()
+        flag = self._guard_word(pl)
+        last_state = self._check_last_state(last_state)
+
+        def launch(last):
+            self._mel_window(pl, win)
+            self._encoder_launches(pl, pl["mel"], last)
+        self._replay((win,), {}, launch, win["src"], last_state)
+        return HiddenStates(pl["states"], pl["frame_offs_host"], None if last_state is None else last_state + 1, range_flag=flag,
+                            frame_offs_dev=pl.get("frame_offs"))
 
     def _pack_act(self, pl, input_features: torch.Tensor) -> None:
         """ser_pack_act: the [B, n_mels, 3000] features as conv1's operand rows (channels last, a zero halo row before and after each utterance)."""
@@ -3129,7 +3302,7 @@ class WhisperDecoder(_LaunchHost):
     @_on_stream
     def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0, token_times: bool = False,
                  lengths: Optional[Sequence[int]] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
-                 keep_logits: bool = False, timestamps: bool = False) -> DecodeResult:
+                 keep_logits: bool = False, timestamps: bool = False, num_frames: Optional[Sequence[int]] = None) -> DecodeResult:
         """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``).
         ``token_times``: also HF's ``token_timestamps`` of every utterance given alone (``DecodeResult.token_times``), from the alignment
         heads' cross-attention; needs ``lengths``, the utterances' sample counts (HF's ``num_frames`` = length // 160).
@@ -3139,7 +3312,8 @@ class WhisperDecoder(_LaunchHost):
         ``timestamps``: the model's own segment times (HF's ``return_timestamps=True`` for one 30 s window): the prompt is
         ``[start, language, task]``, the step ends in ser_dec_select_ts_v on a plan of its own, and the result has ``segments``,
         ``next_seek`` and ``ts_gaps``; ``lengths`` (sample counts) bound the window, absent: the whole 30 s.  ``keep_logits`` then
-        keeps ``DecodeResult.step_logits``.  Does not go with ``token_times`` or ``num_beams > 1``."""
+        keeps ``DecodeResult.step_logits``.  ``num_frames`` (with ``timestamps``; the long-form loop): the mel frames of each row's window,
+        given to ``segments_of`` as they are instead of ``lengths``' len // 160.  Does not go with ``token_times`` or ``num_beams > 1``."""
         sp = spec or self.spec
         K = int(getattr(sp, "num_beams", 1) if num_beams is None else num_beams)
         if not 1 <= K <= _lib.BEAM_MAX_K:
@@ -3150,6 +3324,8 @@ class WhisperDecoder(_LaunchHost):
             raise ValueError("timestamps=True with num_beams > 1: segment timestamps with beam search are not built")
         if timestamps and lengths is not None and len(lengths) != B:
             raise ValueError("lengths: one sample count per utterance")
+        if num_frames is not None and (not timestamps or len(num_frames) != B or lengths is not None):
+            raise ValueError("num_frames: one frame count per row of a timestamps run, in place of lengths")
         if K > 1:
             if token_times:
                 raise ValueError("token times with beam search are not built: run with num_beams=1")
@@ -3183,7 +3359,8 @@ class WhisperDecoder(_LaunchHost):
             res.ts_gaps = pl["ts_gap"][:, : res.sequences.shape[1] - 1].cpu().numpy()
             res.segments, res.next_seek = [], np.zeros(B, dtype=np.int64)
             for b, ids in enumerate(res.lists):
-                segs, adv = segments_of(ids, spec.timestamp_begin, window_frames(None if lengths is None else lengths[b]))
+                nf = int(num_frames[b]) if num_frames is not None else window_frames(None if lengths is None else lengths[b])
+                segs, adv = segments_of(ids, spec.timestamp_begin, nf)
                 res.segments.append(segs)
                 res.next_seek[b] = adv
             if kept is not None:

@@ -10,8 +10,10 @@ alignment heads' cross-attention by the decoder itself (engine.WhisperDecoder.ge
 ``_combine_tokens_into_words`` does, and ``--times_json`` writes both.
 
 ``transcribe(..., timestamps=True)`` runs the model's own segment times instead (HF's ``return_timestamps=True``, one 30 s window):
-``.segments`` and ``.next_seek`` per file, ``segments_of`` being HF's ``_retrieve_segment``; ``--segments_json`` writes them.  The seek
-loop over a longer file is not built: ``next_seek`` says where its next window would begin.
+``.segments`` and ``.next_seek`` per file, ``segments_of`` being HF's ``_retrieve_segment``; ``--segments_json`` writes them.
+
+``transcribe_long(items)`` is the seek loop over files longer than 30 s (HF's long-form ``generate``): whole-file features, one window
+per file and round through a window queue, the segments with absolute times; ``--long_form`` runs it.
 """
 from __future__ import annotations
 
@@ -27,7 +29,7 @@ import torch
 from . import config as C
 from .batchloop import make_batches, run_or_each
 
-N_SAMPLES = 480000            # 30 s: WhisperFeatureExtractor cuts longer input, and so does this path
+N_SAMPLES = 480000            # 30 s: WhisperFeatureExtractor cuts longer input, and so does ``transcribe`` (``transcribe_long`` does not)
 BATCH = 16
 N_FRAMES = 3000               # mel frames of a window
 HOP = 160                     # samples per mel frame
@@ -40,6 +42,11 @@ def window_frames(n_samples: Optional[int]) -> int:
     """HF's ``seek_num_frames`` of a first window when the feature extractor's attention mask is passed: min(3000, len // 160); None:
     the whole window."""
     return N_FRAMES if n_samples is None else min(N_FRAMES, int(n_samples) // HOP)
+
+
+def is_long(n_samples: int) -> bool:
+    """more mel frames than one window holds: the file goes through the long-form loop (``WhisperTranscriber.transcribe_long``)"""
+    return int(n_samples) // HOP > N_FRAMES
 
 
 def segments_of(tokens: Sequence[int], ts_begin: int, num_frames: int, time_offset: float = 0.0):
@@ -86,6 +93,9 @@ class WhisperTranscriber:
         self.segments: List[Optional[list]] = []                # per item of the last transcribe(timestamps=True): [(start_s, end_s, ids)]
         self.next_seek: List[Optional[int]] = []                # ... and the mel frames the next window would begin at
         self.failed: List[str] = []                             # names of the files the last transcribe() left out
+        self.sequences: List[Optional[List[int]]] = []          # per item of the last transcribe_long(): the segments' ids, timestamps included
+        self.windows: List[Optional[list]] = []                 # ... its windows [(seek, nf, advance)] in mel frames
+        self.rounds: List[tuple] = []                           # ... and the rounds that ran: (language key, item indices, [(seek, nf)])
 
     def _batch(self, waves: Sequence[np.ndarray], slot: int, token_times: bool = False, num_beams: Optional[int] = None,
                length_penalty: Optional[float] = None, timestamps: bool = False):
@@ -154,6 +164,144 @@ class WhisperTranscriber:
                         self.token_times[j] = [float(t) for t in res.token_times[k][: len(res.lists[k])]]
 
             run_or_each(idx, run, fail, catch=())
+        return out
+
+    def transcribe_long(self, items, batch: int = BATCH) -> List[Optional[List[int]]]:
+        """Long-form transcription (HF's ``generate`` on input over 30 s with ``return_timestamps=True``, greedy, every file given alone)
+        through a WINDOW QUEUE.  ``items``: an iterable of ``(name, wave)``, consumed as room frees up (a driver loads lazily).
+
+        Up to ``batch`` long files (``is_long``) are resident, each with one pending window ``[seek, seek + nf)`` of its whole-file
+        features (``WhisperEncoder.log_mel_long``: one launch for all files admitted in a round).  A round takes up to ``batch`` pending
+        windows -- all of them still to have their language detected, or all of one language: the decoder's forced prompt is one row
+        per batch --, gathers and encodes them (``forward_windows``), decodes on the timestamps plan and advances each file's seek by
+        ``segments_of``.  A file's language is detected on its first window and forced on its later ones; with ``spec.language`` set it
+        is forced from the start.  A finished file leaves and the next item is admitted.
+
+        A round whose error word or range guard is set is run again window by window (``batchloop.run_or_each``); a window that still
+        fails, or whose advance is 0 (HF's loop would not end), fails its FILE: printed, named in ``self.failed``, dropped with its
+        later windows, no partial transcript.  The other files are neither touched nor run again.
+
+        Returns per item the ids without timestamp tokens (None: failed) and fills ``self.sequences`` (HF's: the segments' ids,
+        timestamp tokens included), ``self.segments`` (absolute times), ``self.windows`` (per file ``[(seek, nf, advance)]``),
+        ``self.next_seek`` (the final seek) and ``self.last_languages``.  Short files go through ``transcribe(..., timestamps=True)``."""
+        if int(self.spec.num_beams) > 1:
+            raise ValueError("long-form with num_beams > 1: long-form transcription with beam search is not built")
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("batch >= 1")
+        tsb = self.spec.timestamp_begin
+        out: List[Optional[List[int]]] = []
+        seqs: List[Optional[List[int]]] = []
+        segments: List[Optional[list]] = []
+        windows: List[Optional[list]] = []
+        seeks: List[Optional[int]] = []
+        langs: List[Optional[int]] = []
+        failed: List[str] = []
+        names: List[str] = []
+        rounds: List[tuple] = []                            # (language key or None, [item index], [(seek, nf)]) per round that ran
+        self.rounds = rounds
+
+        def slot_for(name):
+            for lst in (out, seqs, segments, windows, seeks, langs):
+                lst.append(None)
+            names.append(name)
+            return len(out) - 1
+
+        shorts: List[tuple] = []                            # (item index, wave)
+
+        def flush_shorts():
+            if not shorts:
+                return
+            idx = [i for i, _ in shorts]
+            got = self.transcribe([w for _, w in shorts], [names[i] for i in idx], timestamps=True)
+            for k, i in enumerate(idx):
+                out[i], segments[i], seeks[i], langs[i] = got[k], self.segments[k], self.next_seek[k], self.last_languages[k]
+                if got[k] is not None:
+                    seqs[i] = [t for _, _, ids in self.segments[k] for t in ids]
+                    windows[i] = [(0, window_frames(len(shorts[k][1])), int(self.next_seek[k]))]
+            failed.extend(self.failed)
+            shorts.clear()
+
+        it = iter(items)
+        exhausted = False
+        resident: List[dict] = []
+        handle = None
+        forced = self.spec.language
+        n_round = 0
+
+        def drop(f, why=None):
+            resident.remove(f)
+            handle.release(f["file"])
+            if why is not None:
+                failed.append(names[f["i"]])
+                print(f"Failed to process {names[f['i']]}: {why}")
+
+        while True:
+            new = []
+            while not exhausted and len(resident) + len(new) < batch:
+                try:
+                    name, wave = next(it)
+                except StopIteration:
+                    exhausted = True
+                    break
+                wave = np.ascontiguousarray(wave, dtype=np.float32)
+                i = slot_for(str(name))
+                if is_long(len(wave)):
+                    new.append((i, wave))
+                else:
+                    shorts.append((i, wave))
+                    if len(shorts) == BATCH:
+                        flush_shorts()
+            if new:
+                waves = [w for _, w in new]
+                first = 0 if handle is None else len(handle)
+                handle = self.enc.log_mel_long(self.enc.upload(waves, n_round % 2), [len(w) for w in waves], into=handle)
+                for k, (i, w) in enumerate(new):
+                    resident.append(dict(i=i, file=first + k, F=len(w) // HOP, seek=0, lang=forced, last=-1, seq=[], segs=[], wins=[]))
+            if not resident:
+                break
+            key = min(resident, key=lambda f: f["last"])["lang"]      # the window that has waited longest names the round's language
+            chosen = [f for f in resident if f["lang"] == key][:batch]
+            slot = n_round % 2
+            for f in chosen:
+                f["last"] = n_round
+            n_round += 1
+
+            def run(fs):
+                rows = [(f["file"], f["seek"], min(N_FRAMES, f["F"] - f["seek"])) for f in fs]
+                rounds.append((key, [f["i"] for f in fs], [(s, nf) for _, s, nf in rows]))
+                hs = self.enc.forward_windows(handle, rows, slot)
+                res = self.dec.generate(hs.states[-1], len(fs), self.spec, language=key, slot=slot, timestamps=True,
+                                        num_frames=[nf for _, _, nf in rows])
+                bits = hs.take_range_bits()
+                if res.failed or bool(bits & 1):
+                    return res
+                for k, f in enumerate(fs):
+                    seek, nf = rows[k][1], rows[k][2]
+                    segs, adv = segments_of(res.lists[k], tsb, nf, float(seek) * TIME_PRECISION / INPUT_STRIDE)
+                    f["lang"] = int(res.languages[k])
+                    if adv <= 0:
+                        drop(f, f"window at {seek * TIME_PRECISION_FEATURES:g} s made no progress")
+                        continue
+                    f["wins"].append((seek, nf, int(adv)))
+                    f["segs"].extend(segs)
+                    f["seq"].extend(t for _, _, ids in segs for t in ids)
+                    f["seek"] = seek + int(adv)
+                    if f["seek"] >= f["F"]:
+                        i = f["i"]
+                        seqs[i], segments[i], windows[i], seeks[i], langs[i] = f["seq"], f["segs"], f["wins"], f["seek"], f["lang"]
+                        out[i] = [t for t in f["seq"] if t < tsb]
+                        drop(f)
+
+            def fail(f, res):
+                drop(f, f"window at {f['seek'] * TIME_PRECISION_FEATURES:g} s: decoder error word {res.err:#x}, "
+                        f"range-guard bits {res.range_bits:#x}")
+
+            run_or_each(chosen, run, fail, catch=())
+        flush_shorts()
+        self.sequences, self.segments, self.windows, self.next_seek, self.last_languages = seqs, segments, windows, seeks, langs
+        self.failed = failed
+        self.token_times = [None] * len(out)
         return out
 
     def texts(self, waves: Sequence[np.ndarray], tokenizer, names: Optional[Sequence[str]] = None) -> List[Optional[str]]:
@@ -309,6 +457,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--length_penalty", type=float, default=None, help="with beams: the exponent of the length a finished score is divided by")
     p.add_argument("--segments_json", type=str, default="", help="decode with the model's own segment timestamps (first 30 s window of "
                    "each file) and also write them, with where the next window would begin, to this JSON file")
+    p.add_argument("--long_form", action="store_true", help="decode every file with segment timestamps and files over 30 s window by "
+                   "window to their end (HF's long-form generate); with --segments_json the segments carry absolute times")
     return p
 
 
@@ -322,6 +472,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error("--segments_json with --times_json: segment timestamps with token times are not built")
     if args.segments_json and args.num_beams is not None and args.num_beams > 1:
         p.error("--segments_json with --num_beams: segment timestamps with beam search are not built")
+    if args.long_form and args.times_json:
+        p.error("--long_form with --times_json: long-form transcription with token times is not built")
+    if args.long_form and args.num_beams is not None and args.num_beams > 1:
+        p.error("--long_form with --num_beams: long-form transcription with beam search is not built")
     if args.length_penalty is not None and (args.num_beams is None or args.num_beams < 2):
         p.error("--length_penalty needs --num_beams K with K >= 2")
     return args
@@ -385,8 +539,32 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
     if want_segments and args.num_beams is None and tr.spec.num_beams > 1:
         print("Error: --segments_json with num_beams > 1 in generation_config.json: segment timestamps with beam search are not built")
         return 0
+    if args.long_form and tr.spec.num_beams > 1:
+        print("Error: --long_form with num_beams > 1 in generation_config.json: long-form transcription with beam search is not built")
+        return 0
     entries, seg_entries = {}, {}
-    for i in range(0, len(names), BATCH):
+    if args.long_form:
+        loaded = []
+
+        def load_items():
+            for n in names:
+                try:
+                    wave = load_wav_16k(os.path.join(args.wav_dir, n), resample=args.resample)
+                except Exception as e:                      # noqa: BLE001
+                    print(f"Failed to process {n}: {e}")
+                    continue
+                loaded.append(n)
+                yield n, wave
+
+        for k, ids in enumerate(tr.transcribe_long(load_items())):
+            if ids is None:
+                continue
+            n = loaded[k]
+            rows.append((n, tok.decode(ids, skip_special_tokens=True) if tok is not None else " ".join(str(t) for t in ids)))
+            if want_segments and tr.segments[k] is not None:
+                seg_entries[n] = segments_entry(tr.segments[k], tr.next_seek[k], rows[-1][1], tr.spec.timestamp_begin, tok)
+                seg_entries[n]["windows"] = len(tr.windows[k])
+    for i in ([] if args.long_form else range(0, len(names), BATCH)):
         chunk, waves = [], []
         for n in names[i:i + BATCH]:
             try:
