@@ -1466,6 +1466,34 @@ typedef struct ser_mel_window_args {
 } ser_mel_window_args;
 int ser_mel_window_v(const ser_mel_window_args* args, void* stream);
 
+/* a38 (added under ABI 18: one new entry point, one ser_cmd member and one SER_OP code only; ser_dec_select_v, ser_dec_select_ts_v and every
+ * struct above are what they were)  Whisper transcript scores: the log-probability of every generated token and the no-speech
+ * probability, what HF's generate() thresholds (logprob_threshold, no_speech_threshold) read.
+ *
+ * ser_dec_select_score_v (SER_OP_DEC_SELECT_SCORE): rule == 0: ser_dec_select_v's choice and bookkeeping (ts.base alone is read);
+ * rule == 1: ser_dec_select_ts_v's (all of ts).  Token, margin, ts_gap, ids, finished, the tickets in `work`, *unfinished and *pos are
+ * bit for bit those of the unscored launcher on the same inputs.  One block per row.  With p = *pos, per row b also:
+ *   logprob[b, p]  = x[token] - log sum_{v < V} exp(x[v]) in float64, x the PROCESSED row the choice was made from (HF's `scores`):
+ *                    logits + mask[phase[p]], and under the rule also its -inf columns, step 5's among them -- when the timestamps
+ *                    together outweigh the best text token the sum runs over the live timestamp columns only.  Computed around the
+ *                    winner w = max x as (x[token] - w) - log sum exp(x[v] - w), whose first term is 0.  +inf where nothing was decided
+ *                    (forced or finished rows), as margin.
+ *   no_speech[b]   = softmax_{v < V}(logits[b, :])[no_speech_token] in float64, written by the step at p == 0 only, from the RAW row: no
+ *                    mask, no rule, whether the step's token is forced or chosen (HF's WhisperNoSpeechDetection reads the unprocessed
+ *                    logits of the first decoder position).  So the logits of that step must have been computed even when its token is forced.
+ * The float64 sums run over a fixed tree of (thread, wave) slots, a function of V and ts_begin alone; a row's result does not depend on
+ * what shares its batch, bit for bit.  Columns >= V are never read.  *err bit 0 is also set when the row at position 0 holds a NaN or an
+ * infinity (no_speech is then NaN), or when a decided row's normaliser is not finite; otherwise the bits are the unscored launcher's.
+ * logprob float64 [B, ld_logprob >= max_pos - 1], no_speech float64 [B], 0 <= no_speech_token < V; rule == 0 ignores ts.ts_gap (may be
+ * NULL) and the four token fields of ts. */
+typedef struct ser_dec_select_score_args {
+    ser_dec_select_ts_args ts;
+    double* logprob; int64_t ld_logprob;
+    double* no_speech;
+    int32_t no_speech_token, rule;
+} ser_dec_select_score_args;
+int ser_dec_select_score_v(const ser_dec_select_score_args* args, void* stream);
+
 #define SER_OP_GEMM 1
 #define SER_OP_ATTENTION 2
 #define SER_OP_LAYERNORM 3
@@ -1499,6 +1527,7 @@ int ser_mel_window_v(const ser_mel_window_args* args, void* stream);
 #define SER_OP_DEC_SELECT_TS 31
 #define SER_OP_LOGMEL_LONG 32
 #define SER_OP_MEL_WINDOW 33
+#define SER_OP_DEC_SELECT_SCORE 34
 typedef struct ser_cmd {
     int32_t op, reserved0;
     union {
@@ -1535,6 +1564,7 @@ typedef struct ser_cmd {
         ser_dec_select_ts_args dec_select_ts;
         ser_logmel_long_args logmel_long;
         ser_mel_window_args  mel_window;
+        ser_dec_select_score_args dec_select_score;
     } u;
 } ser_cmd;
 

@@ -402,6 +402,12 @@ class DecSelectTsArgs(C.Structure):
                 ("ts_begin", C.c_int32), ("no_ts", C.c_int32), ("begin_index", C.c_int32), ("max_initial", C.c_int32)]
 
 
+class DecSelectScoreArgs(C.Structure):
+    """Mirror of ``ser_dec_select_score_args``."""
+    _fields_ = [("ts", DecSelectTsArgs), ("logprob", c_void_p), ("ld_logprob", c_i64), ("no_speech", c_void_p),
+                ("no_speech_token", C.c_int32), ("rule", C.c_int32)]
+
+
 class LogmelLongArgs(C.Structure):
     """Mirror of ``ser_logmel_long_args``."""
     _fields_ = [("wav", c_void_p), ("sample_offs", c_void_p), ("sample_offs_host", c_void_p), ("mel", c_void_p),
@@ -589,7 +595,7 @@ class _CmdUnion(C.Union):
                 ("dec_attn_beam", DecAttnBeamArgs), ("beam_select", BeamSelectArgs),
                 ("rope_rows", RopeRowsArgs), ("conformer_conv_bn", ConformerConvBnArgs), ("relpos_bias", RelposBiasArgs),
                 ("attention_rb", AttentionRbArgs), ("dec_select_ts", DecSelectTsArgs),
-                ("logmel_long", LogmelLongArgs), ("mel_window", MelWindowArgs)]
+                ("logmel_long", LogmelLongArgs), ("mel_window", MelWindowArgs), ("dec_select_score", DecSelectScoreArgs)]
 
 
 class Cmd(C.Structure):
@@ -607,6 +613,7 @@ OP_DEC_ATTN_BEAM, OP_BEAM_SELECT = 25, 26
 OP_ROPE_ROWS, OP_CONFORMER_CONV_BN, OP_RELPOS_BIAS, OP_ATTENTION_RB = 27, 28, 29, 30
 OP_DEC_SELECT_TS = 31
 OP_LOGMEL_LONG, OP_MEL_WINDOW = 32, 33
+OP_DEC_SELECT_SCORE = 34
 STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs, "ser_layernorm_args": LayerNormArgs,
                   "ser_wave_frames_args": WaveFramesArgs, "ser_row_center_args": RowCenterArgs, "ser_logmel_args": LogmelArgs,
                   "ser_pack_act_args": PackActArgs, "ser_gn_stats_args": GnStatsArgs, "ser_pos_ln_args": PosLnArgs, "ser_resample_args": ResampleArgs, "ser_asp_pool_args": AspPoolArgs,
@@ -625,6 +632,7 @@ STRUCT_MIRRORS = {"ser_gemm_args": GemmArgs, "ser_attention_args": AttentionArgs
                   "ser_relpos_bias_args": RelposBiasArgs, "ser_attention_rb_args": AttentionRbArgs,
                   "ser_dec_select_ts_args": DecSelectTsArgs,
                   "ser_logmel_long_args": LogmelLongArgs, "ser_mel_window_args": MelWindowArgs,
+                  "ser_dec_select_score_args": DecSelectScoreArgs,
                   "ser_cmd": Cmd}
 
 _SIGNATURES = {
@@ -692,6 +700,7 @@ _SIGNATURES = {
     "ser_dec_select_ts_v": (c_int, [c_void_p, c_void_p]),
     "ser_logmel_long_v": (c_int, [c_void_p, c_void_p]),
     "ser_mel_window_v": (c_int, [c_void_p, c_void_p]),
+    "ser_dec_select_score_v": (c_int, [c_void_p, c_void_p]),
     "ser_pack_f16m": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "ser_wavlm_bias_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ser_wavlm_gate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -613,6 +613,10 @@ class GenerationSpec:
     num_beams: int = 1                 # 1: greedy; 2..8: HF's beam search with early_stopping = False (engine.WhisperDecoder.generate)
     length_penalty: float = 1.0        # the exponent of the generated length a finished beam's score is divided by
     max_initial_timestamp_index: Optional[int] = None   # None when absent, as HF's WhisperTimeStampLogitsProcessor reads it
+    no_speech_token_id: Optional[int] = None            # None: HF's own choice, no_timestamps_token_id - 1 (``no_speech_token``)
+    logprob_threshold: Optional[float] = None           # HF generate()'s three thresholds; None: not set (transcribe.need_fallback)
+    no_speech_threshold: Optional[float] = None
+    compression_ratio_threshold: Optional[float] = None
 
     PROMPT_LEN = 4
     MAX_BEAMS = 8
@@ -627,6 +631,17 @@ class GenerationSpec:
     def timestamp_begin(self) -> int:
         """The id of ``<|0.00|>``: every id from here on is a timestamp token (HF: ``no_timestamps_token_id + 1``)."""
         return self.no_timestamps_token_id + 1
+
+    @property
+    def no_speech_token(self) -> int:
+        """The id whose probability at the first decoder position is the no-speech probability (HF: ``no_timestamps_token_id - 1``)."""
+        return self.no_timestamps_token_id - 1 if self.no_speech_token_id is None else int(self.no_speech_token_id)
+
+    @property
+    def thresholds(self) -> dict:
+        """The three thresholds by HF's names, None where not set."""
+        return dict(logprob_threshold=self.logprob_threshold, no_speech_threshold=self.no_speech_threshold,
+                    compression_ratio_threshold=self.compression_ratio_threshold)
 
     def require_alignment_heads(self) -> Tuple[Tuple[int, int], ...]:
         """The alignment heads, or the error that names what is missing: token times were asked of a checkpoint that has none."""
@@ -670,7 +685,17 @@ class GenerationSpec:
         penalty = 1.0 if penalty is None else penalty
         if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or penalty != penalty or abs(penalty) == float("inf"):
             raise OSError(f"generation_config.json: length_penalty={penalty!r} (a finite number)")
+        limits = {}
+        for k in ("logprob_threshold", "no_speech_threshold", "compression_ratio_threshold"):
+            v = cfg.get(k)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf")):
+                raise OSError(f"generation_config.json: {k}={v!r} (a finite number, or absent)")
+            limits[k] = None if v is None else float(v)
+        ns = cfg.get("no_speech_token_id")
+        if ns is not None and (isinstance(ns, bool) or not isinstance(ns, int) or ns < 0):
+            raise OSError(f"generation_config.json: no_speech_token_id={ns!r} (a token id, or absent)")
         return GenerationSpec(
+            no_speech_token_id=ns, **limits,
             num_beams=beams, length_penalty=float(penalty), max_initial_timestamp_index=initial,
             decoder_start_token_id=int(cfg["decoder_start_token_id"]), eos_token_id=eos, pad_token_id=eos if pad is None else int(pad),
             suppress_tokens=tuple(int(t) for t in cfg.get("suppress_tokens") or ()),

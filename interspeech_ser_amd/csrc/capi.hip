@@ -167,6 +167,10 @@ extern "C" int ser_run(const ser_cmd* cmds, int32_t n, int32_t* failed_at, void*
                 rc = ser_mel_window_v(&c.u.mel_window, stream);
                 break;
             }
+            case SER_OP_DEC_SELECT_SCORE: {
+                rc = ser_dec_select_score_v(&c.u.dec_select_score, stream);
+                break;
+            }
             default:
                 rc = ser_fail(-2, "ser_run: command %d has unknown op %d", i, c.op);
         }

@@ -2853,9 +2853,16 @@ class DecodeResult:
     ``[start, language, task]``), and also: ``segments`` (per utterance a list of ``(start_s, end_s, ids)``, ``transcribe.segments_of`` of
     its list), ``next_seek`` (int64 [B]: the frames HF's seek would advance by), ``ts_gaps`` float64 [B, n - 1] (ser_dec_select_ts_v's
     |L - M| of position p's decision, +inf where the sum rule compared nothing) and, with ``keep_logits``, ``step_logits`` (fp32
-    [steps, B, V] on the device: the logits of every step from the first generated position on)."""
+    [steps, B, V] on the device: the logits of every step from the first generated position on).
+    After a scored run (``generate(..., scores=True)``, greedy or with ``timestamps``) also ``token_logprobs`` (per utterance float64
+    [its generated tokens, the first eos included, nothing after it]: log-softmax of the processed row at the chosen token,
+    ser_dec_select_score_v's), ``avg_logprob`` (float64 [B]: their sum in ascending order over their count, HF's
+    ``_retrieve_avg_logprobs`` of a file given alone; NaN for an utterance without a generated token) and ``no_speech_prob`` (float64 [B]:
+    softmax of the first decoder position's raw logits at ``spec.no_speech_token``; with ``keep_logits`` those logits stay in
+    ``first_logits``, fp32 [B, V] on the device)."""
 
     token_times = token_frames = ts_status = ts_matrix = None
+    token_logprobs = avg_logprob = no_speech_prob = first_logits = None
     nbest = beam_scores = beam_trace = beam_gaps = beam_logits = None
     segments = next_seek = ts_gaps = step_logits = None
 
@@ -2931,15 +2938,19 @@ class WhisperDecoder(_LaunchHost):
         return (self._dev_f32(sd[prefix + ".weight"]), self._dev_f32(sd[prefix + ".bias"]))
 
     # ------------------------------------------------------------------ buffers
-    def _plan(self, B: int, slot: int, heads=None, beams: int = 1, timestamps: bool = False):
+    def _plan(self, B: int, slot: int, heads=None, beams: int = 1, timestamps: bool = False, scores: bool = False):
         """``heads``: the alignment heads of the capture variant of the step (``generate(token_times=True)``), part of the plan's key; the
         default plan (None) records exactly the launches it always did.  ``beams`` K >= 2: the beam plan, keyed (slot, B, "beam", K).
-        ``timestamps``: the segment-timestamps plan, keyed (slot, B, "ts"), whose step ends in ser_dec_select_ts_v."""
+        ``timestamps``: the segment-timestamps plan, keyed (slot, B, "ts"), whose step ends in ser_dec_select_ts_v.  ``scores``: the
+        scored forms of the greedy and the timestamps plan, keyed (slot, B, "score") and (slot, B, "ts", "score"), whose step ends in
+        ser_dec_select_score_v; the unscored plans record what they always did."""
         if beams > 1:
             return self._beam_plan(B, slot, beams)
         key = (slot, B) if heads is None else (slot, B, tuple(heads))
         if timestamps:
             key = (slot, B, "ts")
+        if scores:
+            key = (slot, B, "ts", "score") if timestamps else (slot, B, "score")
         pl = self._plans.get(key)
         if pl is not None:
             return pl
@@ -2962,6 +2973,9 @@ class WhisperDecoder(_LaunchHost):
         if timestamps:
             pl["timestamps"] = True
             pl["ts_gap"] = torch.empty((B, T), dtype=torch.float64, device=dev)
+        if scores:
+            pl["scores"] = True
+            pl["score_blob"] = torch.empty(B * T + B, dtype=torch.float64, device=dev)      # logprob [B, T] | no_speech [B]: one copy back
         if heads is not None:
             heads = tuple((int(l), int(h)) for l, h in heads)
             if not 1 <= len(heads) <= _lib.TS_MAX_HEADS or any(not (0 <= l < L and 0 <= h < geo.decoder_attention_heads) for l, h in heads):
@@ -3131,7 +3145,8 @@ class WhisperDecoder(_LaunchHost):
         self._layernorm(x0, D, self.final_ln, B, D, out_act=pl["xa"])
         self._gemm(pl["xa"], self.proj, B, out_f32=pl["logits"], ldo_f32=self.Vp)
         pl["n_logits"] = self._rec.n if self._rec is not None else None
-        x = self._cmd("dec_select_ts") if pl.get("timestamps") else None
+        q = self._cmd("dec_select_score") if pl.get("scores") else None
+        x = q.ts if q is not None else (self._cmd("dec_select_ts") if pl.get("timestamps") else None)
         s = self._cmd("dec_select") if x is None else x.base
         s.logits, s.ldl = pl["logits"].data_ptr(), self.Vp
         s.mask, s.ldm = 0, geo.decoder_vocab_size                      # the spec's masks: set per generate() call (_bind_spec)
@@ -3141,6 +3156,17 @@ class WhisperDecoder(_LaunchHost):
         s.pos, s.unfinished, s.work, s.err = pl["pos"].data_ptr(), pl["unfinished"].data_ptr(), pl["work"].data_ptr(), pl["err"].data_ptr()
         s.B, s.V, s.eos, s.pad, s.max_pos = B, geo.decoder_vocab_size, 0, 0, T
         pl["select"] = s
+        if q is not None:
+            blob = pl["score_blob"]
+            q.logprob, q.ld_logprob, q.no_speech = blob.data_ptr(), T, blob.data_ptr() + 8 * B * T
+            q.no_speech_token, q.rule = 0, 1 if pl.get("timestamps") else 0
+            if q.rule:
+                x.ts_gap, x.ld_gap = pl["ts_gap"].data_ptr(), T
+                x.ts_begin, x.no_ts, x.begin_index, x.max_initial = 1, 0, 1, -1
+                pl["select_ts"] = x
+            pl["select_score"] = q
+            self._issue(_lib.OP_DEC_SELECT_SCORE, q, "ser_dec_select_score")
+            return
         if x is not None:
             # the spec's token layout (begin): placeholders that pass the launcher's checks while the step is recorded
             x.ts_gap, x.ld_gap = pl["ts_gap"].data_ptr(), T
@@ -3227,22 +3253,28 @@ class WhisperDecoder(_LaunchHost):
             check(rc, f"ser_run (decoder step, command {tape._failed.value})")
 
     def begin(self, B: int, spec=None, language=None, slot: int = 0, forced_ids=None, token_times: bool = False, num_beams: int = 1,
-              length_penalty: float = 1.0, timestamps: bool = False):
+              length_penalty: float = 1.0, timestamps: bool = False, scores: bool = False):
         """Reset the slot's decoding state for a batch of B: ids[:, 0] = start, position 0, nothing finished.  ``forced_ids`` (tests:
         teacher forcing): a whole id row to follow instead of the spec's prompt.  ``token_times``: the capture variant of the step.
         ``num_beams`` K >= 2: the beam plan (B K rows) with its state reset: running scores [0, -inf, ..], empty finished sets, flags up,
         the identity ancestor table.  ``timestamps``: the segment-timestamps plan and its prompt ``[start, language, task]``; with
-        ``forced_ids`` the rule still counts its generated tokens from position 3."""
+        ``forced_ids`` the rule still counts its generated tokens from position 3.  ``scores``: the scored form of the greedy or the
+        timestamps plan (ser_dec_select_score_v), its log-probabilities reset to +inf and its no-speech probabilities to NaN."""
         spec = spec or self.spec
         if spec is None:
             raise ValueError("WhisperDecoder needs a GenerationSpec")
+        if scores and (token_times or num_beams > 1):
+            raise ValueError("scores=True does not go with " + ("token_times" if token_times else "num_beams > 1") + ": not built")
         if timestamps and (token_times or num_beams > 1):
             raise ValueError("timestamps=True does not go with " + ("token_times" if token_times else "num_beams > 1") + ": not built")
         geo = self.geo
         T = geo.max_target_positions
         n_max = min(int(spec.max_length), T)
         P = spec.prompt_len(timestamps)
-        pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None, beams=num_beams, timestamps=timestamps)
+        if scores:
+            pl = self._plan(B, slot, timestamps=timestamps, scores=True)
+        else:
+            pl = self._plan(B, slot, spec.require_alignment_heads() if token_times else None, beams=num_beams, timestamps=timestamps)
         language = spec.language if language is None else language
         forced = np.full(T, -1, dtype=np.int32)
         phase = np.zeros(T, dtype=np.int32)
@@ -3278,6 +3310,12 @@ class WhisperDecoder(_LaunchHost):
             x.ts_begin, x.no_ts, x.begin_index = spec.timestamp_begin, spec.no_timestamps_token_id, P
             x.max_initial = -1 if initial is None else int(initial)
             pl["ts_gap"].fill_(float("inf"))
+        if scores:
+            if not 0 <= spec.no_speech_token < geo.decoder_vocab_size:
+                raise ValueError(f"scores need the no-speech token {spec.no_speech_token} inside the vocabulary of {geo.decoder_vocab_size}")
+            pl["select_score"].no_speech_token = spec.no_speech_token
+            pl["score_blob"][: B * T].fill_(float("inf"))
+            pl["score_blob"][B * T:].fill_(float("nan"))
         if pl.get("K"):
             from .beam import lenpow_table
             if n_max <= spec.PROMPT_LEN:
@@ -3302,7 +3340,8 @@ class WhisperDecoder(_LaunchHost):
     @_on_stream
     def generate(self, enc_last: torch.Tensor, B: int, spec=None, language=None, slot: int = 0, token_times: bool = False,
                  lengths: Optional[Sequence[int]] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
-                 keep_logits: bool = False, timestamps: bool = False, num_frames: Optional[Sequence[int]] = None) -> DecodeResult:
+                 keep_logits: bool = False, timestamps: bool = False, num_frames: Optional[Sequence[int]] = None,
+                 scores: bool = False) -> DecodeResult:
         """Greedy transcription of a batch from the encoder's last hidden state (fp32 [B * 1500, D], e.g. ``HiddenStates.states[-1]``).
         ``token_times``: also HF's ``token_timestamps`` of every utterance given alone (``DecodeResult.token_times``), from the alignment
         heads' cross-attention; needs ``lengths``, the utterances' sample counts (HF's ``num_frames`` = length // 160).
@@ -3313,11 +3352,19 @@ class WhisperDecoder(_LaunchHost):
         ``[start, language, task]``, the step ends in ser_dec_select_ts_v on a plan of its own, and the result has ``segments``,
         ``next_seek`` and ``ts_gaps``; ``lengths`` (sample counts) bound the window, absent: the whole 30 s.  ``keep_logits`` then
         keeps ``DecodeResult.step_logits``.  ``num_frames`` (with ``timestamps``; the long-form loop): the mel frames of each row's window,
-        given to ``segments_of`` as they are instead of ``lengths``' len // 160.  Does not go with ``token_times`` or ``num_beams > 1``."""
+        given to ``segments_of`` as they are instead of ``lengths``' len // 160.  Does not go with ``token_times`` or ``num_beams > 1``.
+        ``scores``: the greedy or the timestamps run on a scored plan of its own (the step ends in ser_dec_select_score_v, and the step
+        at position 0 computes its logits even when the language is forced: the no-speech probability reads them); tokens, margins and
+        ts_gaps are those of the unscored run, and the result also has ``token_logprobs``, ``avg_logprob`` and ``no_speech_prob``, read
+        back once after the loop.  Does not go with ``token_times`` or ``num_beams > 1`` (a beam run returns ``beam_scores``)."""
         sp = spec or self.spec
         K = int(getattr(sp, "num_beams", 1) if num_beams is None else num_beams)
         if not 1 <= K <= _lib.BEAM_MAX_K:
             raise ValueError(f"num_beams={K} (1..{_lib.BEAM_MAX_K})")
+        if scores and token_times:
+            raise ValueError("scores=True with token_times: transcript scores with token times are not built")
+        if scores and K > 1:
+            raise ValueError("scores=True with num_beams > 1: transcript scores with beam search are not built (beam_scores are returned)")
         if timestamps and token_times:
             raise ValueError("timestamps=True with token_times: segment timestamps with token times are not built")
         if timestamps and K > 1:
@@ -3333,25 +3380,33 @@ class WhisperDecoder(_LaunchHost):
             return self._generate_beams(enc_last, B, spec, language, slot, K, lp, keep_logits)
         if token_times and (lengths is None or len(lengths) != B):
             raise ValueError("token times need the sample count of every utterance (lengths)")
-        pl = self.begin(B, spec, language, slot, token_times=token_times, timestamps=timestamps)
+        if scores:
+            pl = self.begin(B, spec, language, slot, timestamps=timestamps, scores=True)
+        else:
+            pl = self.begin(B, spec, language, slot, token_times=token_times, timestamps=timestamps)
         spec = pl["spec"]
         self.project_cross(pl, enc_last)
         n_max, forced, P = pl["n_max"], pl["forced_host"], pl["P"]
         host = pl["host"]
-        kept = [] if keep_logits and timestamps else None
+        kept = [] if keep_logits and (timestamps or scores) else None
+        first_logits = None
         V = self.geo.decoder_vocab_size
         steps = 0
         for pos in range(n_max - 1):
-            self._run_step(pl, with_logits=forced[pos] < 0)
+            self._run_step(pl, with_logits=forced[pos] < 0 or (scores and pos == 0))
             steps += 1
             if kept is not None and pos >= P - 1:
                 kept.append(pl["logits"][:, :V].clone())
+            if kept is not None and scores and pos == 0:
+                first_logits = pl["logits"][:, :V].clone()
             if steps % self.CHECK_EVERY == 0 and pos >= P - 1:
                 host[0:1].copy_(pl["unfinished"], non_blocking=True)
                 torch.cuda.current_stream().synchronize()
                 if int(host[0]) == 0:
                     break
         res = self.result(pl, steps)
+        if kept is not None and scores:
+            res.first_logits = first_logits
         if token_times:
             self._token_times(pl, res, lengths)
         if timestamps:
@@ -3363,9 +3418,29 @@ class WhisperDecoder(_LaunchHost):
                 segs, adv = segments_of(ids, spec.timestamp_begin, nf)
                 res.segments.append(segs)
                 res.next_seek[b] = adv
-            if kept is not None:
-                res.step_logits = torch.stack(kept) if kept else None
+        if kept is not None:
+            res.step_logits = torch.stack(kept) if kept else None
+        if scores:
+            self._scores(pl, res)
         return res
+
+    def _scores(self, pl, res: DecodeResult) -> None:
+        """After the loop: ONE copy back of the scored plan's float64 blob (log-probabilities | no-speech probabilities)."""
+        B, T, P, eos = pl["B"], self.geo.max_target_positions, pl["P"], pl["spec"].eos_token_id
+        blob = pl["score_blob"].cpu().numpy()
+        lp = blob[: B * T].reshape(B, T)
+        res.no_speech_prob = blob[B * T:].copy()
+        res.token_logprobs, res.avg_logprob = [], np.full(B, np.nan, dtype=np.float64)
+        for b in range(B):
+            gen = res.sequences[b, P:].tolist()
+            n = gen.index(eos) + 1 if eos in gen else len(gen)                # the first eos included, nothing after it
+            t = lp[b, P - 1: P - 1 + n].copy()                                # position p decides token p + 1
+            res.token_logprobs.append(t)
+            if n:
+                total = 0.0
+                for v in t:                                                   # ascending order, as a cumulative sum over one row
+                    total += float(v)
+                res.avg_logprob[b] = total / n
 
     def _generate_beams(self, enc_last, B: int, spec, language, slot: int, K: int, length_penalty: float, keep_logits: bool) -> DecodeResult:
         """The beam run: the prompt steps through ser_dec_select_v on all B K rows, then ser_beam_select_v as the last command of every

@@ -14,13 +14,20 @@ alignment heads' cross-attention by the decoder itself (engine.WhisperDecoder.ge
 
 ``transcribe_long(items)`` is the seek loop over files longer than 30 s (HF's long-form ``generate``): whole-file features, one window
 per file and round through a window queue, the segments with absolute times; ``--long_form`` runs it.
+
+``transcribe(..., scores=True)`` keeps what HF's ``generate`` thresholds read: ``.scores[i]`` = the file's ``avg_logprob``,
+``no_speech_prob``, ``compression_ratio``, ``needs_fallback`` and ``token_logprobs`` (``--scores_json`` writes them).  ``need_fallback`` is
+HF's ``_need_fallback``; with thresholds in the spec ``transcribe_long`` skips a window whose ``should_skip`` holds, as HF's seek loop does.
+Temperature fallback is not built: ``needs_fallback`` is reported and changes nothing.
 """
 from __future__ import annotations
 
 import argparse
 import csv
 import json
+import math
 import os
+import zlib
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -80,6 +87,53 @@ def segments_of(tokens: Sequence[int], ts_begin: int, num_frames: int, time_offs
     return [(off, off + last_pos * TIME_PRECISION, tok)], int(num_frames)
 
 
+def compression_ratio(tokens: Sequence[int], vocab_size: int) -> float:
+    """HF's ``_retrieve_compression_ratio``: every token as ``int(log2(V) / 8) + 1`` little-endian bytes; the raw length over zlib's."""
+    length = int(math.log2(vocab_size) / 8) + 1
+    raw = b"".join(int(t).to_bytes(length, "little") for t in tokens)
+    return len(raw) / len(zlib.compress(raw))
+
+
+def check_thresholds(thresholds: dict) -> None:
+    """HF's ``_need_fallback`` reads the average log-probability in its no-speech branch and computes it only under
+    ``logprob_threshold``: with ``no_speech_threshold`` alone it raises on the unbound name.  Refused by name instead."""
+    if thresholds.get("no_speech_threshold") is not None and thresholds.get("logprob_threshold") is None:
+        raise ValueError("no_speech_threshold without logprob_threshold: HF's rule compares the average log-probability in its no-speech "
+                         "branch, so --no_speech_threshold needs --logprob_threshold")
+
+
+def need_fallback(tokens_with_eos: Sequence[int], avg_logprob: float, no_speech_prob: float, thresholds: dict, vocab_size: int):
+    """HF's ``WhisperGenerationMixin._need_fallback`` branch by branch -> ``(needs_fallback, should_skip)``.  ``tokens_with_eos``: the
+    window's generated tokens, the closing eos included (HF keeps it for this call); ``thresholds``: ``logprob_threshold``,
+    ``no_speech_threshold`` and ``compression_ratio_threshold``, None or absent where not set."""
+    check_thresholds(thresholds)
+    needs_fallback, should_skip = False, False
+    ratio, logprob, silence = (thresholds.get(k) for k in ("compression_ratio_threshold", "logprob_threshold", "no_speech_threshold"))
+    if ratio is not None:
+        if compression_ratio(tokens_with_eos, vocab_size) > ratio:
+            needs_fallback = True
+    if logprob is not None:
+        if avg_logprob < logprob:
+            needs_fallback = True
+    if silence is not None:
+        if avg_logprob < logprob and no_speech_prob > silence:
+            needs_fallback = False
+            should_skip = True
+    return needs_fallback, should_skip
+
+
+def score_entry(tokens_with_eos: Sequence[int], avg_logprob: float, no_speech_prob: float, thresholds: dict, vocab_size: int) -> dict:
+    """The scores of one decoded window as the JSON files carry them, and ``skipped`` = HF's should_skip."""
+    needs, skip = need_fallback(tokens_with_eos, avg_logprob, no_speech_prob, thresholds, vocab_size)
+    return dict(avg_logprob=float(avg_logprob), no_speech_prob=float(no_speech_prob),
+                compression_ratio=float(compression_ratio(tokens_with_eos, vocab_size)), needs_fallback=bool(needs), skipped=bool(skip))
+
+
+def _with_eos(res, k: int, spec) -> List[int]:
+    """the generated tokens of row k of a DecodeResult, the first eos included: one per entry of its token_logprobs"""
+    return [int(t) for t in res.sequences[k, spec.prompt_len(res.segments is not None):][: len(res.token_logprobs[k])]]
+
+
 class WhisperTranscriber:
     """``transcribe(waves)``: per utterance the generated ids without the prompt, up to and excluding eos (None for a file that failed).
     Batches of ``BATCH`` alternate between the encoder's and decoder's two slots.  A batch whose fp16 range-guard word or decoder error
@@ -96,9 +150,10 @@ class WhisperTranscriber:
         self.sequences: List[Optional[List[int]]] = []          # per item of the last transcribe_long(): the segments' ids, timestamps included
         self.windows: List[Optional[list]] = []                 # ... its windows [(seek, nf, advance)] in mel frames
         self.rounds: List[tuple] = []                           # ... and the rounds that ran: (language key, item indices, [(seek, nf)])
+        self.scores: List[Optional[dict]] = []                  # per item of the last transcribe(scores=True): score_entry + token_logprobs
 
     def _batch(self, waves: Sequence[np.ndarray], slot: int, token_times: bool = False, num_beams: Optional[int] = None,
-               length_penalty: Optional[float] = None, timestamps: bool = False):
+               length_penalty: Optional[float] = None, timestamps: bool = False, scores: bool = False):
         """(DecodeResult, failed) of one batch; one encoder forward serves the decoder (its LAST state: the forward does not stop early)."""
         lengths = [len(w) for w in waves]
         hs = self.enc.forward(self.enc.upload(waves, slot), lengths, slot=slot)
@@ -109,13 +164,15 @@ class WhisperTranscriber:
             extra["length_penalty"] = float(length_penalty)
         if timestamps:
             extra.update(timestamps=True, lengths=lengths)
+        if scores:
+            extra["scores"] = True
         res = self.dec.generate(hs.states[-1], len(waves), self.spec, slot=slot, **extra)
         bits = hs.take_range_bits()
         return res, res.failed or bool(bits & 1), hs
 
     def transcribe(self, waves: Sequence[np.ndarray], names: Optional[Sequence[str]] = None, first_batch: int = 0,
                    token_times: bool = False, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
-                   timestamps: bool = False) -> List[Optional[List[int]]]:
+                   timestamps: bool = False, scores: bool = False) -> List[Optional[List[int]]]:
         """``first_batch``: the index of the first batch in the caller's own sequence of calls (a driver that hands over 16 files at a time
         keeps the slots alternating with it).  ``token_times``: ``self.token_times[i]`` becomes the seconds of item i's generated non-eos
         tokens.  A file whose times have a status word set (no frame, a matrix entry that is not finite) fails ALONE: it is printed,
@@ -124,7 +181,14 @@ class WhisperTranscriber:
         (``self.last_scores[i]``: its score) and does not go with ``token_times``.  ``timestamps``: the model's own segment times of
         each file's first 30 s window: ``self.segments[i]`` = ``[(start_s, end_s, ids)]``, ``self.next_seek[i]`` = the mel frames the
         seek would advance by, and the returned ids are the generated ones with the timestamp tokens removed.  Does not go with
-        ``token_times`` or beams."""
+        ``token_times`` or beams.  ``scores``: the greedy or the timestamps run on the decoder's scored plan; ``self.scores[i]`` =
+        ``score_entry`` of the file's tokens under the spec's thresholds plus ``token_logprobs``.  Nothing is skipped here (HF's skip
+        belongs to its seek loop: ``transcribe_long``).  Does not go with ``token_times`` or beams."""
+        if scores and (token_times or int(self.spec.num_beams if num_beams is None else num_beams) > 1):
+            raise ValueError("scores=True with " + ("token_times" if token_times else "num_beams > 1") + ": transcript scores with "
+                             + ("token times" if token_times else "beam search") + " are not built")
+        if scores:
+            check_thresholds(self.spec.thresholds)
         if timestamps and token_times:
             raise ValueError("timestamps=True with token_times: segment timestamps with token times are not built")
         if timestamps and int(self.spec.num_beams if num_beams is None else num_beams) > 1:
@@ -138,7 +202,9 @@ class WhisperTranscriber:
         self.last_languages = [None] * len(waves)
         self.token_times = [None] * len(waves)
         self.segments, self.next_seek = [None] * len(waves), [None] * len(waves)
+        self.scores = [None] * len(waves)
         self.failed = []
+        V = self.dec.geo.decoder_vocab_size if scores else 0
 
         def fail(j, res):
             self.failed.append(names[j])
@@ -146,7 +212,7 @@ class WhisperTranscriber:
 
         for n, idx in enumerate(make_batches(range(len(waves)), BATCH), start=int(first_batch)):
             def run(js):
-                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times, num_beams, length_penalty, timestamps)
+                res, failed, _ = self._batch([waves[j] for j in js], n % 2, token_times, num_beams, length_penalty, timestamps, scores)
                 if failed:
                     return res
                 for k, j in enumerate(js):
@@ -154,6 +220,10 @@ class WhisperTranscriber:
                     if timestamps:
                         out[j] = [t for t in res.lists[k] if t < self.spec.timestamp_begin]
                         self.segments[j], self.next_seek[j] = res.segments[k], int(res.next_seek[k])
+                    if scores:
+                        self.scores[j] = score_entry(_with_eos(res, k, self.spec), res.avg_logprob[k], res.no_speech_prob[k],
+                                                     self.spec.thresholds, V)
+                        self.scores[j]["token_logprobs"] = [float(x) for x in res.token_logprobs[k]]
                     if getattr(res, "beam_scores", None) is not None:
                         self.last_scores[j] = float(res.beam_scores[k])
                     if token_times and int(res.ts_status[k]) != 0:
@@ -166,7 +236,7 @@ class WhisperTranscriber:
             run_or_each(idx, run, fail, catch=())
         return out
 
-    def transcribe_long(self, items, batch: int = BATCH) -> List[Optional[List[int]]]:
+    def transcribe_long(self, items, batch: int = BATCH, scores: bool = False) -> List[Optional[List[int]]]:
         """Long-form transcription (HF's ``generate`` on input over 30 s with ``return_timestamps=True``, greedy, every file given alone)
         through a WINDOW QUEUE.  ``items``: an iterable of ``(name, wave)``, consumed as room frees up (a driver loads lazily).
 
@@ -181,6 +251,12 @@ class WhisperTranscriber:
         fails, or whose advance is 0 (HF's loop would not end), fails its FILE: printed, named in ``self.failed``, dropped with its
         later windows, no partial transcript.  The other files are neither touched nor run again.
 
+        With thresholds in the spec (``logprob_threshold``, ``no_speech_threshold``, ``compression_ratio_threshold``) every window is
+        decoded on the SCORED timestamps plan, and a window whose ``need_fallback`` says ``should_skip`` contributes no segments and
+        advances the seek by its whole ``nf`` -- HF's seek loop, for every file, one-window files included.  A skipped window is
+        progress.  A file whose windows were all skipped has the empty transcript and is no failure.  ``self.windows`` entries then are
+        ``(seek, nf, advance, score_entry)``; ``scores=True`` asks for the scored plan and these entries without any threshold.
+
         Returns per item the ids without timestamp tokens (None: failed) and fills ``self.sequences`` (HF's: the segments' ids,
         timestamp tokens included), ``self.segments`` (absolute times), ``self.windows`` (per file ``[(seek, nf, advance)]``),
         ``self.next_seek`` (the final seek) and ``self.last_languages``.  Short files go through ``transcribe(..., timestamps=True)``."""
@@ -190,6 +266,10 @@ class WhisperTranscriber:
         if batch < 1:
             raise ValueError("batch >= 1")
         tsb = self.spec.timestamp_begin
+        limits = self.spec.thresholds
+        scored = bool(scores) or any(v is not None for v in limits.values())
+        check_thresholds(limits)
+        V = self.dec.geo.decoder_vocab_size if scored else 0
         out: List[Optional[List[int]]] = []
         seqs: List[Optional[List[int]]] = []
         segments: List[Optional[list]] = []
@@ -213,12 +293,18 @@ class WhisperTranscriber:
             if not shorts:
                 return
             idx = [i for i, _ in shorts]
-            got = self.transcribe([w for _, w in shorts], [names[i] for i in idx], timestamps=True)
+            got = self.transcribe([w for _, w in shorts], [names[i] for i in idx], timestamps=True, **(dict(scores=True) if scored else {}))
             for k, i in enumerate(idx):
                 out[i], segments[i], seeks[i], langs[i] = got[k], self.segments[k], self.next_seek[k], self.last_languages[k]
-                if got[k] is not None:
+                if got[k] is not None and scored and self.scores[k]["skipped"]:
+                    nf = window_frames(len(shorts[k][1]))                  # the one window is skipped whole: no segments, the seek at its end
+                    out[i], segments[i], seqs[i], seeks[i] = [], [], [], nf
+                    windows[i] = [(0, nf, nf, {n: v for n, v in self.scores[k].items() if n != "token_logprobs"})]
+                elif got[k] is not None:
                     seqs[i] = [t for _, _, ids in self.segments[k] for t in ids]
                     windows[i] = [(0, window_frames(len(shorts[k][1])), int(self.next_seek[k]))]
+                    if scored:
+                        windows[i][0] += ({n: v for n, v in self.scores[k].items() if n != "token_logprobs"},)
             failed.extend(self.failed)
             shorts.clear()
 
@@ -272,7 +358,7 @@ class WhisperTranscriber:
                 rounds.append((key, [f["i"] for f in fs], [(s, nf) for _, s, nf in rows]))
                 hs = self.enc.forward_windows(handle, rows, slot)
                 res = self.dec.generate(hs.states[-1], len(fs), self.spec, language=key, slot=slot, timestamps=True,
-                                        num_frames=[nf for _, _, nf in rows])
+                                        num_frames=[nf for _, _, nf in rows], **(dict(scores=True) if scored else {}))
                 bits = hs.take_range_bits()
                 if res.failed or bool(bits & 1):
                     return res
@@ -280,10 +366,15 @@ class WhisperTranscriber:
                     seek, nf = rows[k][1], rows[k][2]
                     segs, adv = segments_of(res.lists[k], tsb, nf, float(seek) * TIME_PRECISION / INPUT_STRIDE)
                     f["lang"] = int(res.languages[k])
-                    if adv <= 0:
+                    entry = None
+                    if scored:
+                        entry = score_entry(_with_eos(res, k, self.spec), res.avg_logprob[k], res.no_speech_prob[k], limits, V)
+                    if entry is not None and entry["skipped"]:
+                        segs, adv = [], nf                                  # HF: seek += seek_num_frames, and nothing is retrieved
+                    elif adv <= 0:
                         drop(f, f"window at {seek * TIME_PRECISION_FEATURES:g} s made no progress")
                         continue
-                    f["wins"].append((seek, nf, int(adv)))
+                    f["wins"].append((seek, nf, int(adv)) if entry is None else (seek, nf, int(adv), entry))
                     f["segs"].extend(segs)
                     f["seq"].extend(t for _, _, ids in segs for t in ids)
                     f["seek"] = seek + int(adv)
@@ -459,6 +550,14 @@ def build_parser() -> argparse.ArgumentParser:
                    "each file) and also write them, with where the next window would begin, to this JSON file")
     p.add_argument("--long_form", action="store_true", help="decode every file with segment timestamps and files over 30 s window by "
                    "window to their end (HF's long-form generate); with --segments_json the segments carry absolute times")
+    p.add_argument("--scores_json", type=str, default="", help="also write avg_logprob, no_speech_prob, compression_ratio, needs_fallback "
+                   "and the token log-probabilities of every file to this JSON file (with --long_form: of every window)")
+    p.add_argument("--logprob_threshold", type=float, default=None, help="with --long_form: HF generate()'s logprob_threshold; default: "
+                   "generation_config.json's, else none")
+    p.add_argument("--no_speech_threshold", type=float, default=None, help="with --long_form: a window whose no-speech probability is "
+                   "above this and whose average log-probability is below --logprob_threshold is skipped whole")
+    p.add_argument("--compression_ratio_threshold", type=float, default=None, help="with --long_form: reported as needs_fallback "
+                   "(temperature fallback itself is not built)")
     return p
 
 
@@ -476,6 +575,15 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error("--long_form with --times_json: long-form transcription with token times is not built")
     if args.long_form and args.num_beams is not None and args.num_beams > 1:
         p.error("--long_form with --num_beams: long-form transcription with beam search is not built")
+    for flag in ("logprob_threshold", "no_speech_threshold", "compression_ratio_threshold"):
+        if getattr(args, flag) is not None and not args.long_form:
+            p.error(f"--{flag} without --long_form: the thresholds act in the long-form loop only (HF's skip of a silent window)")
+    if args.no_speech_threshold is not None and args.logprob_threshold is None:
+        p.error("--no_speech_threshold without --logprob_threshold: HF's rule compares the average log-probability in its no-speech branch")
+    if args.scores_json and args.times_json:
+        p.error("--scores_json with --times_json: transcript scores with token times are not built")
+    if args.scores_json and args.num_beams is not None and args.num_beams > 1:
+        p.error("--scores_json with --num_beams: transcript scores with beam search are not built")
     if args.length_penalty is not None and (args.num_beams is None or args.num_beams < 2):
         p.error("--length_penalty needs --num_beams K with K >= 2")
     return args
@@ -542,7 +650,21 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
     if args.long_form and tr.spec.num_beams > 1:
         print("Error: --long_form with num_beams > 1 in generation_config.json: long-form transcription with beam search is not built")
         return 0
-    entries, seg_entries = {}, {}
+    want_scores = bool(args.scores_json)
+    if want_scores and args.num_beams is None and tr.spec.num_beams > 1:
+        print("Error: --scores_json with num_beams > 1 in generation_config.json: transcript scores with beam search are not built")
+        return 0
+    given = {k: getattr(args, k) for k in ("logprob_threshold", "no_speech_threshold", "compression_ratio_threshold") if getattr(args, k) is not None}
+    if given:                                               # the command line overrides generation_config.json's
+        import dataclasses
+        tr.spec = tr.dec.spec = dataclasses.replace(tr.spec, **given)
+    if want_scores or args.long_form:                       # nothing else reads the thresholds: every other run is what it was
+        try:
+            check_thresholds(tr.spec.thresholds)
+        except ValueError as e:
+            print(f"Error: {e}")
+            return 0
+    entries, seg_entries, score_entries = {}, {}, {}
     if args.long_form:
         loaded = []
 
@@ -556,7 +678,7 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
                 loaded.append(n)
                 yield n, wave
 
-        for k, ids in enumerate(tr.transcribe_long(load_items())):
+        for k, ids in enumerate(tr.transcribe_long(load_items(), **(dict(scores=True) if want_scores else {}))):
             if ids is None:
                 continue
             n = loaded[k]
@@ -564,6 +686,8 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
             if want_segments and tr.segments[k] is not None:
                 seg_entries[n] = segments_entry(tr.segments[k], tr.next_seek[k], rows[-1][1], tr.spec.timestamp_begin, tok)
                 seg_entries[n]["windows"] = len(tr.windows[k])
+            if want_scores:
+                score_entries[n] = {"windows": [dict(seek_s=round(w[0] * TIME_PRECISION_FEATURES, 2), nf=int(w[1]), **w[3]) for w in tr.windows[k]]}
     for i in ([] if args.long_form else range(0, len(names), BATCH)):
         chunk, waves = [], []
         for n in names[i:i + BATCH]:
@@ -575,6 +699,8 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
         beams = {} if args.num_beams is None else dict(num_beams=args.num_beams, length_penalty=args.length_penalty)
         if want_segments:
             beams["timestamps"] = True                      # the default call stays the one it always was
+        if want_scores:
+            beams["scores"] = True
         for k, (n, ids) in enumerate(zip(chunk, tr.transcribe(waves, chunk, first_batch=i // BATCH, token_times=want_times, **beams))):
             if ids is not None:
                 rows.append((n, tok.decode(ids, skip_special_tokens=True) if tok is not None else " ".join(str(t) for t in ids)))
@@ -582,6 +708,11 @@ def run(argv: Optional[Sequence[str]] = None, spec: Optional[C.GenerationSpec] =
                     entries[n] = times_entry(ids, tr.token_times[k], rows[-1][1], tok)
                 if want_segments and tr.segments[k] is not None:
                     seg_entries[n] = segments_entry(tr.segments[k], tr.next_seek[k], rows[-1][1], tr.spec.timestamp_begin, tok)
+                if want_scores and tr.scores[k] is not None:
+                    score_entries[n] = {f: v for f, v in tr.scores[k].items() if f != "skipped"}
+    if want_scores:
+        write_times_json(args.scores_json, score_entries)
+        print(f"Wrote the scores of {len(score_entries)} files to {args.scores_json}")
     if want_segments:
         write_times_json(args.segments_json, seg_entries)
         print(f"Wrote the segments of {len(seg_entries)} files to {args.segments_json}")
